@@ -18,12 +18,22 @@ carries the ncclUniqueId, the set-up barriers and the max over ranks.  No torch 
 it, so libamc.so binds the system's HIP runtime and RCCL in every rank exactly as in a single process.  config.rccl_ranks is
 what ncclCommCount reports for that communicator; the RCCL / HIP runtime versions and files really bound are in the line too.
 
+A plain run sets up, ramps the clock, warms up, times the K steps and prints the line; nothing else runs.  The ensemble
+starts over from x0 ~ U(-2, 2) at step 0 after the clock ramp (whose length is a matter of time, not of arguments), so
+what the timed steps compute depends on the arguments alone.
+
+    --dump-outputs DIR   after the timed steps, what they computed as DIR/<name>.npy (float64): the positions and energies
+                         of the chains (all of them up to 2^20 chains per rank, else a fixed seeded sample of 2^20, with their
+                         global chain ids), what the callbacks return (energy, acceptance) and the counter totals.
+    --full               everything else the line has held: the objects below.
+
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline      algorithmic HBM bytes (16 B/update: read x + write x) / average launch duration measured
                 with HIP events on the engine's stream over the timed region, vs 8 TB/s; `regime` says which memory
-                level serves the state at this size, `ladder` repeats the measurement at 4e7 and 1.6e8 chains
-                (state >> the 256 MiB Infinity Cache); `traffic` / `valu_busy` come from committed rocprofv3 PMC passes
+                level serves the state at this size; `traffic` / `valu_busy` come from committed rocprofv3 PMC passes
                 and carry their source, commit and whether the kernel sources changed since.
+With --full also:
+  roofline.ladder  the measurement repeated at 4e7 and 1.6e8 chains (state >> the 256 MiB Infinity Cache).
   repeat        the K-step block repeated (untimed by `value`): min / median ms per step.
   fused_sweepstep16  the same ensemble with 16 MH steps per launch (reported separately, no roofline fraction).
   other_configs BASELINE configs 3 (double well, K = 2) and 5 (PGMC) end to end, us per time step with callbacks every 10.
@@ -44,6 +54,9 @@ BETA, SIGMA, SEED = 2.0, 0.1, 1
 BYTES_PER_UPDATE = 16            # f64 read x + write x; counters reduce in-kernel for K = 1
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 CALLBACK_EVERY_MULTI = 10        # configs[3]: callbacks all-reduced every 10 sweeps when N > 1
+PREBLOCK_STEPS_MAX = 24_000      # the untimed blocks of the timed region's shape hold at most this many steps in all
+DUMP_SAMPLE = 1 << 20            # --dump-outputs: chains per rank written in full up to this count, a seeded sample beyond it
+DUMP_SEED = 20240607
 
 
 def cpu_allotment():
@@ -297,6 +310,25 @@ def other_configs(A, m, device, periods=40):
     return out
 
 
+def dump_outputs(out_dir, eng, first_chain, sums):
+    """--dump-outputs: what the timed steps computed, as a caller of that path receives it, one float64 .npy per array -- the
+    positions and energies of this rank's chains (all of them up to DUMP_SAMPLE, else a sample of DUMP_SAMPLE chains drawn with
+    DUMP_SEED) with their global chain ids, what the callbacks of the whole ensemble return (callback_energy: <e>;
+    callback_acceptance: the mean acceptance of each move) and this rank's counter totals (accepted, total)."""
+    import numpy as np
+    x, e = eng.download_state()
+    n = x.size
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    accepted, total = eng.counter_totals()
+    n_chains = sums[3]                    # amc_reduce's layout: sum of e at 0, the chain count at 3, the acceptance sums from 4
+    arrays = {"x": x[idx], "e": e[idx], "chain_id": first_chain + idx,
+              "callback_energy": sums[:1] / n_chains, "callback_acceptance": sums[4:] / n_chains,
+              "accepted": accepted, "total": total}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def pick_device(local_rank, n_dev):
     """The device ordinal of this rank: AMC_BENCH_DEVICE if given, else LOCAL_RANK -- or 0 where the launcher hands every rank ONE
     visible device of its own (HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES set per rank: each process then sees a single device 0).
@@ -351,16 +383,26 @@ def main():
     ap.add_argument("--spinup-cap-s", type=float, default=3.0,
                     help="... and the ramp's upper bound: it ends earlier once three consecutive 200-launch blocks agree within 1 %%")
     ap.add_argument("--preblocks", type=int, default=12,
-                    help="untimed blocks of the timed region's own shape (barrier, K steps, drain) between the ramp and the W warm-up steps")
+                    help="untimed blocks of the timed region's own shape (barrier, K steps, drain) between the ramp and the W warm-up steps "
+                         f"(as many as fit in {PREBLOCK_STEPS_MAX} steps in all)")
     ap.add_argument("--chains-per-gpu", type=int, default=M_PER_GPU)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="extra repetitions of the K-step block for min / median (not part of value)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed as DIR/<name>.npy (float64; positions and energies: all chains up to "
+                         f"{DUMP_SAMPLE} per rank, a fixed seeded sample beyond)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: CPU baseline, repeated blocks, the sweepstep = 16 form, "
+                         "the chain-count ladder, BASELINE configs 3 and 5 and the widened paths")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="with --full: extra repetitions of the K-step block for min / median (not part of value)")
     ap.add_argument("--min-gpu-seconds", type=float, default=8.0,
-                    help="keep repeating the K-step block (not part of value) until this much wall clock has gone by, so that a "
-                         "coarse outside sampler of GPU activity sees the device busy; 0: just --repeats blocks")
-    ap.add_argument("--no-ladder", action="store_true", help="skip the 4e7 / 1.6e8-chain launches behind roofline.ladder")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the config-3 / config-5 end-to-end figures")
+                    help="with --full: keep repeating the K-step block (not part of value) until this much wall clock has gone by, so "
+                         "that a coarse outside sampler of GPU activity sees the device busy; 0: just --repeats blocks")
+    ap.add_argument("--no-ladder", action="store_true", help="with --full: skip the 4e7 / 1.6e8-chain launches behind roofline.ladder")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the config-3 / config-5 end-to-end figures")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
 
     # ONE JSON line on stdout: RCCL / the HIP runtime may print banners to fd 1 (e.g. RCCL's version block at
     # communicator creation), so fd 1 is pointed at stderr for the whole run and the line goes to a private copy.
@@ -396,7 +438,7 @@ def main():
     # activity finds it (with the baseline last, ~4 s of GPU work used to precede 22 s of host-only work).  The checker is
     # loaded and timed here and nowhere near the product path below.
     cpu_line = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_line = cpu_baseline()
 
     from montecarlo_amd import _capi as A
@@ -525,11 +567,18 @@ def main():
         # every rank must leave after the same number of collectives: the ranks agree through one more of them
         elif sharding.all_ranks(time_up, eng):
             break
+    # the ramp ran for as long as the clock took: the ensemble starts over (same x0, step 0, counters 0), so that the state the
+    # timed steps leave -- and the line's `check` -- depend on the arguments alone (every launch reads and writes all of x whatever
+    # it decides, so the state does not change what a step costs)
+    eng.init_uniform(-2.0, 2.0)
+    eng.step = 0
+    eng.set_counter_totals(0, 0)
     # ... and then in the timed region's own rhythm: untimed blocks of the very bracket that follows (barrier, K steps, drain), so that
     # the timed block is one more block of a steady sequence and not the first of its kind after the ramp's 200-launch stretches
     # (the two HIP-event records that bracket the timed launches cost it ~1.5 % at K = 20 against the blocks of `repeat`, which carry
-    # none: measured by leaving them out, three runs each way on one box; they stay -- roofline.frac_events is taken over the timed region)
-    for _ in range(max(0, args.preblocks)):
+    # none: measured by leaving them out, three runs each way on one box; they stay -- roofline.frac_events is taken over the timed region);
+    # a count fixed by the arguments, at most PREBLOCK_STEPS_MAX steps in all (a long timed region needs no lead-in of its own shape)
+    for _ in range(min(max(0, args.preblocks), PREBLOCK_STEPS_MAX // args.steps)):
         barrier()
         run_steps(args.steps)
         finish_callback()
@@ -550,13 +599,24 @@ def main():
         both = grp.allgather((elapsed, event_ms))              # max over ranks
         elapsed, event_ms = max(b[0] for b in both), max(b[1] for b in both)
 
+    def callback_sums():
+        """callback_energy and callback_acceptance of the whole ensemble as of now: the shards' exact records, merged"""
+        rec, steps_counted = eng.reduce_exact()
+        return eng.reduce_records_value(sharding.allreduce_xsum(rec, eng), steps_counted)
+
+    red = None
+    if args.dump_outputs or not args.full:
+        red = callback_sums()                  # what the timed steps left (every rank takes part in the merge)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, start, red)
+
     # the same K-step block, repeated (not part of `value`): a 20-step driver run is 0.7 ms of timed region, and one slow
     # launch moves it by 5 %
     # ... and, with --min-gpu-seconds, for at least that long: the device stays busy long enough for a sampler outside this
     # process to see it at work (every block is the timed region's own: same steps, same barriers)
     rep_ms = []
     t_rep = time.perf_counter()
-    while True:
+    while args.full:
         n_done = len(rep_ms)
         more = n_done < max(0, args.repeats) or (args.repeats > 0 and time.perf_counter() - t_rep < args.min_gpu_seconds)
         if grp is not None:
@@ -572,15 +632,15 @@ def main():
     if grp is not None and rep_ms:
         rep_ms = [max(col) for col in zip(*grp.allgather(rep_ms))]
 
-    rec, steps_counted = eng.reduce_exact()
-    red = eng.reduce_records_value(sharding.allreduce_xsum(rec, eng), steps_counted)
+    if args.full:
+        red = callback_sums()                  # after the repeated blocks too
     n = red[3]
     energy, acceptance = red[0] / n, red[4] / n
 
     # the sweepstep = 16 form, reported separately -- the state stays in registers between the 16 MH steps of a
     # launch, so bytes per update fall to 1 and a fraction of the HBM roofline means nothing there
     fused = None
-    if world == 1:
+    if args.full and world == 1:
         for _ in range(5):
             eng.sweep(16)
         eng.sync()
@@ -596,10 +656,10 @@ def main():
                          "round trip per sweep, roofline fraction not meaningful"}
 
     ladder_rows = None
-    if rank == 0 and world == 1 and not args.no_ladder and args.chains_per_gpu == M_PER_GPU:
+    if args.full and rank == 0 and world == 1 and not args.no_ladder and args.chains_per_gpu == M_PER_GPU:
         ladder_rows = ladder(A, (4 * M_PER_GPU, 16 * M_PER_GPU), local_rank)
     others = None
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         others = other_configs(A, stop - start, local_rank)
     if rank == 0:
         prof = pmc_profile()
@@ -624,6 +684,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": "particle_1d Harmonic, beta=2.0, Gaussian Displacement sigma=0.1 (K=1), Metropolis, "
                             f"sweepstep=1, M={m_local} chains per GPU ({m_global} total), x0~U(-2,2), seed=1",

@@ -61,7 +61,7 @@ def check_line(d, n_gpus, cb_every):
 
 
 def test_single_process_line():
-    d = run_bench({}, "--no-cpu-baseline")
+    d = run_bench({}, "--full", "--no-cpu-baseline")
     check_line(d, 1, 0)
     assert "cpu_baseline" not in d
     c = d["config"]
@@ -86,7 +86,7 @@ def test_single_process_line():
 def test_distributed_path_on_one_rank():
     env = {"AMC_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29531", "RANK": "0",
            "LOCAL_RANK": "0", "WORLD_SIZE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
-    d = run_bench(env, "--gpus", "1", "--no-cpu-baseline")
+    d = run_bench(env, "--gpus", "1", "--full", "--no-cpu-baseline")
     check_line(d, 1, 10)
     c = d["config"]
     # the communicator itself says how many ranks it spans (ncclCommCount): a SCALE line shows "RCCL saw N ranks" by itself
@@ -128,7 +128,7 @@ def test_min_gpu_seconds_keeps_the_device_busy():
     sampler of GPU activity outside the process finds the device at work."""
     env = dict(os.environ)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "10", "--spinup-s", "0.05", "--repeats", "2",
-           "--min-gpu-seconds", "2.0", "--chains-per-gpu", str(M), "--no-cpu-baseline", "--no-other-configs", "--no-ladder"]
+           "--min-gpu-seconds", "2.0", "--chains-per-gpu", str(M), "--full", "--no-cpu-baseline", "--no-other-configs", "--no-ladder"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
@@ -147,7 +147,7 @@ def test_default_size_line_carries_the_ladder():
     """At the default ensemble size the line also holds the M-ladder (4e7 and 1.6e8 chains: state far beyond the 256 MiB
     Infinity Cache) next to the headline figure and its regime."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--spinup-s", "0.2", "--repeats", "2",
-           "--min-gpu-seconds", "0", "--no-cpu-baseline"]
+           "--min-gpu-seconds", "0", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
@@ -178,7 +178,7 @@ def test_two_ranks_on_one_device_fall_back_to_the_store():
     env = dict(os.environ, AMC_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40",
-           "--warmup", "10", "--spinup-s", "0.05", "--repeats", "3", "--min-gpu-seconds", "0", "--chains-per-gpu", str(M)]
+           "--warmup", "10", "--spinup-s", "0.05", "--repeats", "3", "--min-gpu-seconds", "0", "--chains-per-gpu", str(M), "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-4000:]
@@ -195,3 +195,34 @@ def test_two_ranks_on_one_device_fall_back_to_the_store():
         assert d["config"]["rccl_ranks"] == 2 and r.returncode == 0
         # whole-job value: both shards' updates over the slowest rank's wall time
         assert abs(d["value"] - 2 * M * 40 / (d["ms_per_step"] * 1e-3 * 40)) < 1e-6 * d["value"]
+
+
+def test_plain_line_is_lean_and_its_outputs_repeat(tmp_path):
+    """A plain run (no --full) times the K steps and prints the line without the extras; --dump-outputs writes what the timed
+    steps computed, float64, with the same bits from run to run under the same arguments -- and under --full, whose extras come after."""
+    import numpy as np
+    a, b, c = tmp_path / "a", tmp_path / "b", tmp_path / "c"
+    d = run_bench({}, "--dump-outputs", str(a))
+    assert d["full"] is False and d["steps"] == 40 and d["warmup"] == 10 and d["ms_per_step"] > 0
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["unit"] == "chain-updates/s"
+    assert abs(d["value"] - M * 40 / (d["ms_per_step"] * 1e-3 * 40)) < 1e-6 * d["value"]
+    for key in ("repeat", "fused_sweepstep16", "other_configs"):
+        assert d[key] is None, key
+    assert d["roofline"]["ladder"] is None and "cpu_baseline" not in d
+    run_bench({}, "--dump-outputs", str(b))
+    full = run_bench({}, "--full", "--no-cpu-baseline", "--no-other-configs", "--dump-outputs", str(c))
+    assert full["full"] is True and full["repeat"]["blocks"] == 3
+    names = sorted(os.listdir(a))
+    assert names == ["accepted.npy", "callback_acceptance.npy", "callback_energy.npy", "chain_id.npy", "e.npy", "total.npy", "x.npy"]
+    for name in names:
+        want = np.load(a / name)
+        assert want.dtype == np.float64 and want.size > 0 and np.all(np.isfinite(want)), name
+        for other in (b, c):
+            assert np.array_equal(np.load(other / name), want, equal_nan=True), (name, other)
+    x, e = np.load(a / "x.npy"), np.load(a / "e.npy")
+    assert x.shape == e.shape == (M,) and np.array_equal(np.load(a / "chain_id.npy"), np.arange(M))
+    # the ensemble started over after the clock ramp: 12 blocks of the timed region's shape, the W warm-up steps, the K timed ones
+    assert np.array_equal(np.load(a / "total.npy"), [M * (12 * 40 + 10 + 40)])
+    energy, acceptance = np.load(a / "callback_energy.npy"), np.load(a / "callback_acceptance.npy")
+    assert energy.shape == acceptance.shape == (1,) and energy[0] == pytest.approx(float(np.mean(e)), rel=1e-12)
+    assert d["check"]["mean_energy"] == energy[0] and d["check"]["acceptance"] == acceptance[0]

@@ -140,7 +140,7 @@ def test_bench_gpus_n_over_the_stand_in(fake_rccl, world):
     all-reduced every 10 sweeps, max over ranks, ONE JSON line whose config says what the communicator reported."""
     M = 400_000
     args = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "40", "--warmup", "10", "--spinup-s", "0.05", "--repeats", "2",
-            "--min-gpu-seconds", "0", "--chains-per-gpu", str(M)]
+            "--min-gpu-seconds", "0", "--chains-per-gpu", str(M), "--full"]
     r = launch(args, world, dict(AMC_RCCL_LIBRARY=fake_rccl, AMC_BENCH_DEVICE="0", AMC_BENCH_ALLOW_FORCED_RCCL="1"))
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -560,3 +560,39 @@ def test_bench_cpu_baseline_reports_the_cpus_it_was_granted(oracle, monkeypatch)
     monkeypatch.setattr(bench, "cpu_allotment", lambda: (64, None))
     line = bench.cpu_baseline(budget_s=0.2)
     assert line["cores"] == line["threads"] and "quota" not in line["sample"]
+
+
+def test_bench_dump_outputs_samples_a_large_ensemble_the_same_way_every_time(tmp_path):
+    """bench.py --dump-outputs above DUMP_SAMPLE chains per rank: a sorted sample of DUMP_SAMPLE distinct chains drawn with a fixed
+    seed (so two runs, or two builds, are compared chain for chain), float64 files, within 64 MB in all."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 3 * bench.DUMP_SAMPLE + 17
+
+    class Engine:                       # what HipEngine hands back after the timed steps
+        def download_state(self):
+            x = np.arange(n, dtype=np.float64) * 0.5
+            return x, x * x
+        def counter_totals(self):
+            return np.array([7], dtype=np.int64), np.array([11], dtype=np.int64)
+
+    sums = np.array([1.0, np.nan, np.nan, n, 0.9])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), Engine(), 1000, sums)
+    size = 0
+    for name in ("x", "e", "chain_id", "callback_energy", "callback_acceptance", "accepted", "total"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.all(np.isfinite(a)) and np.array_equal(a, b), name
+        size += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert size <= 64 << 20
+    ids = np.load(tmp_path / "a" / "chain_id.npy")
+    assert ids.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(ids) > 0) and ids[0] >= 1000 and ids[-1] < 1000 + n
+    x = np.load(tmp_path / "a" / "x.npy")
+    assert np.array_equal(x, (ids - 1000) * 0.5) and np.array_equal(np.load(tmp_path / "a" / "e.npy"), x * x)
+    # the callbacks' values, not amc_reduce's raw layout (whose columns not asked for are NaN)
+    assert np.load(tmp_path / "a" / "callback_energy.npy").tolist() == [1.0 / n]
+    assert np.load(tmp_path / "a" / "callback_acceptance.npy").tolist() == [0.9 / n]
+    assert np.load(tmp_path / "a" / "accepted.npy").tolist() == [7.0] and np.load(tmp_path / "a" / "total.npy").tolist() == [11.0]

@@ -10,9 +10,9 @@ rm -rf $O; mkdir -p $O
 # the GPU box has no .git: the caller leaves the commit in .profile_commit (git rev-parse --short HEAD > .profile_commit)
 [ -f $R/.profile_commit ] && export AMC_COMMIT=$(cat $R/.profile_commit)
 cd /tmp; export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python3 $R/bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats -d $O/bench_trace --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-ladder > $O/bench_prof.json 2> $O/bench_prof.err
+rocprofv3 --kernel-trace --stats -d $O/bench_trace --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-ladder > $O/bench_prof.json 2> $O/bench_prof.err
 echo "bench trace done"
 W="python3 $R/tools/gpu_workload.py"
 export AMC_RTC_CACHE_DIR=$O/rtc_cache; mkdir -p $AMC_RTC_CACHE_DIR      # the script-defined workloads build once, outside the profiled runs

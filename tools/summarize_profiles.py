@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Turns the rocprofv3 outputs of tools/gpu_profile.sh (merged into gpurun_out/<tag>/; tag = AMC_ROUND_TAG, default r03) into the committed summaries:
 
-  profiles/<tag>_bench_kernel_stats.csv            rocprofv3 --kernel-trace --stats of `python3 bench.py` (the headline command)
+  profiles/<tag>_bench_kernel_stats.csv            rocprofv3 --kernel-trace --stats of `python3 bench.py --full`
   profiles/<tag>_<workload>_kernel_stats.csv       the same for the ladder sizes, the K = 2 sweep (config 3 shape), the fused
                                                  PGMC step (config 5) and the estimator launch alone
   profiles/<tag>_pmc_summary.json                  per workload and kernel: per-launch means of the PMC passes and what follows
