@@ -33,7 +33,7 @@ static int load_rccl(Rccl& r)
     if (r.lib) return AMC_OK;
     // AMC_RCCL_LIBRARY=<file>: that library and no other (a site's own RCCL build; the tests' shared-memory stand-in that
     // lets several ranks share the one GPU of a test box, tests/aux/fake_rccl.c)
-    if (const char* forced = std::getenv("AMC_RCCL_LIBRARY")) {
+    if (const char* forced = amc_env("AMC_RCCL_LIBRARY")) {
         r.lib = dlopen(forced, RTLD_NOW | RTLD_LOCAL);
         if (!r.lib) return fail(AMC_ERR_COMM, "cannot dlopen AMC_RCCL_LIBRARY=%s: %s", forced, dlerror());
     } else {
@@ -234,7 +234,7 @@ int amc_allreduce_xsum(amc_handle* h, double* records, int n_records)
 int amc_comm_library_forced(int* forced)
 {
     if (!forced) return fail(AMC_ERR_BAD_ARG, "amc_comm_library_forced: NULL argument");
-    const char* f = std::getenv("AMC_RCCL_LIBRARY");
+    const char* f = amc_env("AMC_RCCL_LIBRARY");
     *forced = (f && *f) ? 1 : 0;
     return AMC_OK;
 }

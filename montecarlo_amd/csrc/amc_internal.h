@@ -1,12 +1,17 @@
 // amc_internal.h -- what the host-side translation units of libamc.so share: the handle, the error convention, the RCCL and
 // hiprtc surfaces resolved with dlopen.  Nothing here is part of the C ABI (include/amc.h); the functions declared here have
 // hidden visibility.
-//   amc_api.hip       handles, state, sweeps, callback reductions
-//   amc_pg.hip        the estimator's host side (amc_pg_*, amc_pgmc_steps*)
-//   amc_rtc.hip       kernels compiled at run time for script-defined models (hiprtc, code-object cache)
-//   amc_comm.hip      the engine's own RCCL communicator (amc_comm_*, amc_allreduce_*)
-//   amc_selftest.hip  parity-test hooks
-//   amc_pg_fused.hip  kernel instantiations built with other code-generation options
+//   amc_api.hip         errors, expression checks, handle creation and destruction, the knob reader (amc_knobs)
+//   amc_state.hip       the ensemble's state: upload / download, histograms, step indices, stream, timing
+//   amc_counters.hip    the step log and the per-chain counters (fold, totals, 64-bit carry, upload / download)
+//   amc_sweeps.hip      sweep launches (amc_sweep*)
+//   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
+//   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
+//   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
+//   amc_rtc.hip         kernels compiled at run time for script-defined models (hiprtc, code-object cache)
+//   amc_comm.hip        the engine's own RCCL communicator (amc_comm_*, amc_allreduce_*)
+//   amc_selftest.hip    parity-test hooks
+//   amc_pg_fused.hip    kernel instantiations built with other code-generation options
 #pragma once
 
 #include "../../include/amc.h"
@@ -48,6 +53,44 @@ AMC_INTERNAL int fail(int code, const char* fmt, ...);
                         #call, hipGetErrorString(e_));                                             \
     } while (0)
 
+// ---- environment variables --------------------------------------------------------------------------------
+// Every AMC_* variable libamc.so reads is listed here and read through amc_env() (amc_api.hip), and nowhere else.  Handle knobs are
+// read by amc_knobs() in one go: amc_create copies them into the handle, which keeps them for its life; amc_model_check and
+// amc_potential_check read them afresh per call.  "dev": exists for A/B measurements and tests only.  Flags count as set when
+// atoi(value) != 0, except where "set" says that any value, empty included, sets them.
+struct AmcKnobs {
+    //                                   variable                       accepted         default  purpose
+    int blocks_per_cu = 0;            // AMC_BLOCKS_PER_CU              1..64            0: none  tuning: blocks per CU of every launch
+    int blocks_per_cu_single = 0;     // AMC_BLOCKS_PER_CU_SINGLE       1..64            0: none  tuning: ... of single-step sweeps
+    int blocks_per_cu_reduce = 0;     // AMC_BLOCKS_PER_CU_REDUCE       1..64            0: none  tuning: ... of sweeps forming the callback sums
+    int log_depth = 0;                // AMC_LOG_DEPTH                  1..255           0: none  tuning: rows of the step log
+    bool exact_accept = false;        // AMC_EXACT_ACCEPT               flag             off      no accept filter: the reference's arithmetic
+    bool wide_counters = false;       // AMC_WIDE_COUNTERS              not "0..."       off      dev: u32 counter arrays where u16 planes do
+    bool wide_red_rows = false;       // AMC_WIDE_RED_ROWS              flag             off      dev: the wide rows of the callback sums
+    bool shard_route_one_rank = false;  // AMC_SHARD_ROUTE_ON_ONE_RANK  flag             off      dev: one rank takes the estimator route of several
+    bool no_deferred_update = false;  // AMC_NO_DEFERRED_UPDATE         flag             off      dev: each fused time step takes its learning step
+    bool class_per_move = false;      // AMC_CLASS_PER_MOVE             flag             off      dev: class pools: an estimator launch per move
+    bool no_column_skip = false;      // AMC_NO_COLUMN_SKIP             flag             off      dev: fused script steps sum every column
+    bool np_small_launches = false;   // AMC_NP_SMALL_LAUNCHES          flag             off      dev: P > 1, several moves: records + small launches
+    bool no_sweep_estimator_fusion = false;  // AMC_NO_SWEEP_ESTIMATOR_FUSION  set       off      dev: no sweep rides in an estimator launch
+    bool debug_plan = false;          // AMC_DEBUG_PLAN                 set              off      dev: the estimator's launch plans on stderr
+    std::string rtc_licm;             // AMC_RTC_LICM                   all-off, est-off, off-for-none: run-time builds without Machine LICM
+    bool rtc_waves_set = false;       // AMC_RTC_WAVES                  integer          unset    dev: waves per EU of script estimator forms
+    std::string rtc_waves;            //   ... its text (the cache keys carry it as given)
+    bool no_gauss_class_rows = false; // AMC_NO_GAUSS_CLASS_ROWS        set              off      dev: Gaussian classes without table rows
+    bool no_sigma_memo = false;       // AMC_NO_SIGMA_MEMO              set              off      dev: amc_log(sigma) per lane and step
+    bool model_check_f32 = false;     // AMC_MODEL_CHECK_F32            "1..."           off      dev: amc_model_check: Float32 state
+    std::string model_check_inst;     // AMC_MODEL_CHECK_INST           instantiation    ""       dev: amc_model_check builds it (tools/rtc_isa.py)
+};
+// Process settings: read where they are used, through amc_env().
+//   AMC_RTC_CACHE_DIR     directory        none             code objects compiled at run time, kept across processes
+//   AMC_RTC_WORKER        path             beside the .so   the run-time compiler's program
+//   AMC_RTC_TIMEOUT_S     seconds > 0      600              time limit of one run-time build
+//   AMC_RTC_IN_PROCESS    "1..."           off              dev: run-time builds inside this process (under a debugger)
+//   AMC_RCCL_LIBRARY      path             librccl          that RCCL library and no other
+AMC_INTERNAL const char* amc_env(const char* name);
+AMC_INTERNAL AmcKnobs amc_knobs();
+
 // Minimal RCCL surface, resolved with dlopen so the library has no link-time RCCL
 // dependency and shares the instance a host process may already have loaded.
 struct Rccl {
@@ -86,6 +129,7 @@ struct RedTicket {
 };
 
 struct amc_handle {
+    AmcKnobs knobs;             // the environment's knobs as amc_create found them
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -118,7 +162,7 @@ struct amc_handle {
     uint64_t t_base = 0;
     unsigned long long base_acc_total[AMC_MAX_MOVES] = {0}, base_tot_total[AMC_MAX_MOVES] = {0};
     uint8_t* d_log = nullptr;   // [log_depth][M_pad / 2 or M_pad] step log: (move << 1) | accepted per chain and MH step (log_form)
-    int log_depth = 32;         // rows of the step log: 2 GiB worth, between 16 and 128 (env AMC_LOG_DEPTH, 1..255: the fold counts rows in bytes)
+    int log_depth = 32;         // rows of the step log: 2 GiB worth, between 16 and 128 (AMC_LOG_DEPTH, 1..255: the fold counts rows in bytes)
     int log_fill = 0;           // rows written since the last fold into d_acc / d_tot
     double* d_ptab = nullptr;
     uint8_t* d_pick = nullptr;  // [AMC_PICK_CELLS] move pick by the 12 leading bits of the pick uniform (K > 1)
@@ -133,13 +177,10 @@ struct amc_handle {
     double* h_pg_out = nullptr; // pinned: records of amc_pg_estimate
     int red_blocks = 0;
     int red_cols = amc::RED_WANT_ALL;   // the callback sums a reduction forms (amc_set_reduce_columns)
-    bool wide_red_rows = false;         // env AMC_WIDE_RED_ROWS=1 (read at amc_create; tests): the wide row form whatever the launch
-    bool shard_route_one_rank = false;  // env AMC_SHARD_ROUTE_ON_ONE_RANK=1 (measurement, tests): a communicator of one rank takes the route of several
-    bool no_deferred_update = false;    // env AMC_NO_DEFERRED_UPDATE=1 (read at amc_create; tests, A/B): every fused time step takes its own learning step
     int n_cu = 256;
     int blocks_per_cu = 8;      // grid cap = n_cu * blocks_per_cu blocks of 256, grid-stride beyond
     int blocks_per_cu_single = 8;   // ... of single-step sweep launches (6 for the K = 1 pool-wide-counter form)
-    int blocks_per_cu_red = 5;      // ... of the sweep launch that also forms the callback sums (env AMC_BLOCKS_PER_CU_REDUCE)
+    int blocks_per_cu_red = 5;      // ... of the sweep launch that also forms the callback sums (AMC_BLOCKS_PER_CU_REDUCE)
     int blocks_per_cu_pg = 0;       // ... of the estimator kernels when AMC_BLOCKS_PER_CU is given; 0: what a CU HOLDS of the kernel form at hand
                                     // (hipOccupancyMaxActiveBlocksPerMultiprocessor: 5 for the built-in forms, 4 for most hiprtc ones), see pg_plan
     int occ_query = 0;              // out-slot of a launch_pg call made with grid < 0 (a query, nothing is launched)
@@ -147,9 +188,6 @@ struct amc_handle {
     std::map<int, std::string> class_form_errors;  // pools of several classes: the several-move estimator forms (nl, sweep, reduce) that do NOT build, with
                                                    // the compiler's last words about each (amc_pg.hip class_general_route, amc_pg_route)
     std::string class_form_error;   // ... of the form the last class_general_route call asked about ("" when it builds)
-    bool no_column_skip = false;    // env AMC_NO_COLUMN_SKIP=1 (A/B, tests): fused script-defined steps sum every GradientData column whatever the optimiser reads
-    bool np_small_launches = false;    // A/B knob (AMC_NP_SMALL_LAUNCHES=1): several parameters, several learnable moves: records + the small accumulate / update launches, as before round 6
-    bool class_per_move_forced = false;     // env AMC_CLASS_PER_MOVE=1 (read at amc_create; A/B, tests): class pools take one estimator launch per learnable move
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     unsigned long long* d_hist = nullptr;   // running histogram of amc_histogram_accumulate: [hist_bins + 3]
     int hist_bins = 0;
@@ -187,7 +225,6 @@ struct amc_handle {
     amc::PgTail pg_tail_host;           // ... and what it holds now (rewritten only when it changes)
     bool pg_tail_valid = false;
     Rccl rccl;
-    bool exact_accept = false;    // env AMC_EXACT_ACCEPT=1: no accept filter (every decision in the reference's arithmetic)
     std::string arch = AMC_BUILD_ARCH;   // the device's ISA name (gcnArchName up to its first ':'): what hiprtc compiles for
     std::string pot_expr;         // AMC_POTENTIAL_CUSTOM: the C expression of potential(x); '\x02' in front: Float32 state
     bool f32 = false;             // state_dtype == AMC_DTYPE_F32: d_x / d_beta hold floats
@@ -204,25 +241,29 @@ struct amc_handle {
 };
 
 // ---- shared between the translation units ----------------------------------------------------------------------------------------
-AMC_INTERNAL int pg_resolve(amc_handle* h);      // takes a pending learning step now (amc_pg.hip)
-// launch plumbing of amc_api.hip that the estimator's host code (amc_pg.hip) shares
-AMC_INTERNAL int grid_for(const amc_handle* h, int64_t n_items, int blocks_per_cu = 0);
-AMC_INTERNAL int log_form(const amc_handle* h);
+AMC_INTERNAL int grid_for(const amc_handle* h, int64_t n_items, int blocks_per_cu = 0);   // amc_api.hip
+AMC_INTERNAL hipError_t wait_stream(hipStream_t stream);                                  // amc_state.hip
+AMC_INTERNAL hipError_t wait_event(hipEvent_t ev);
+AMC_INTERNAL int log_form(const amc_handle* h);                                           // amc_counters.hip
 AMC_INTERNAL int log_room(amc_handle* h, int* rows);
-AMC_INTERNAL int red_form(const amc_handle* h);
-AMC_INTERNAL int nl_capacity(int n_learn);
-AMC_INTERNAL hipError_t wait_stream(hipStream_t stream);
+AMC_INTERNAL int fold_log(amc_handle* h, bool with_ratio = false, int* ratio_rows = nullptr, amc::xs_word* ratio_dst = nullptr);
+AMC_INTERNAL hipError_t alloc_counters(amc_handle* h, bool narrow);
 AMC_INTERNAL int counter_room(amc_handle* h, const char* who, uint64_t steps);
-AMC_INTERNAL int red_row_stride(const amc_handle* h, int grid);
-AMC_INTERNAL amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps);
+AMC_INTERNAL amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps);        // amc_sweeps.hip
+AMC_INTERNAL int reduce_sweep_grid(const amc_handle* h);
 AMC_INTERNAL int sweep_impl(amc_handle* h, int64_t n_sweeps, bool fuse_reduce, int* grid_out);
+AMC_INTERNAL int red_form(const amc_handle* h);                                           // amc_reduce.hip
+AMC_INTERNAL int red_row_stride(const amc_handle* h, int grid);
 AMC_INTERNAL RedTicket* red_next(amc_handle* h);
 AMC_INTERNAL int finish_fused_reduce(amc_handle* h, int grid);
 AMC_INTERNAL bool reduce_fits_in_grid(const amc_handle* h, int grid);
+AMC_INTERNAL int push_params(amc_handle* h, const double* sigma, const double* weight);  // amc_parameters.hip
+AMC_INTERNAL int pg_resolve(amc_handle* h);      // takes a pending learning step now (amc_pg.hip)
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };
 AMC_INTERNAL int validate_potential_expr(const char* expr, const char* what = "custom potential", const char* var = "x");
-AMC_INTERNAL int rtc_compile(const std::string& expr_in, const std::string& inst, const std::string& arch, const RtcCode** out, std::string* log_out);
+AMC_INTERNAL int rtc_compile(const std::string& expr_in, const std::string& inst, const std::string& arch, const AmcKnobs& knobs, const RtcCode** out,
+                             std::string* log_out);
 AMC_INTERNAL int rtc_function(amc_handle* h, const std::string& inst, hipFunction_t* fn);
 AMC_INTERNAL int rtc_launch(amc_handle* h, const std::string& inst, int grid, void** params);

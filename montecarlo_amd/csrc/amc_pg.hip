@@ -5,6 +5,8 @@
 #define AMC_KERNEL_LINKAGE static      // this object's own copies of the small kernels it launches (accumulate / update / resolve / tail record)
 #include "amc_internal.h"
 
+static int nl_capacity(int n_learn) { return n_learn <= 1 ? 1 : n_learn <= 2 ? 2 : n_learn <= 4 ? 4 : 8; }
+
 // defined in amc_pg_fused.hip (compiled with other code-generation options, see there): not instantiated here
 namespace amc {
 #define AMC_PG_FUSED(POT, NL, BETA)                                                                                     \
@@ -113,7 +115,7 @@ extern "C" {
 // parameter table up to date.  Everything that reads or writes the moves' parameters, gradients_data or the status flag -- other
 // than the next fused launch, which takes the step in its prologue -- calls this first.  (The device's tail record still describes
 // the pending step's configuration: a launch that changes it resolves before it rewrites.)
-extern "C++" int pg_resolve(amc_handle* h)      // (declared in amc_internal.h: amc_api.hip and amc_comm.hip call it too)
+extern "C++" int pg_resolve(amc_handle* h)      // (declared in amc_internal.h: the other units call it too)
 {
     if (!h->pend.active) return AMC_OK;
     AMC_HIP(hipSetDevice(h->device));
@@ -127,7 +129,7 @@ extern "C++" int pg_resolve(amc_handle* h)      // (declared in amc_internal.h: 
 // potentials' Gaussian policy (kind-Q sums), at most two learnable moves
 static bool pg_form_defers(const amc_handle* h, int n_learn)
 {
-    return !h->no_deferred_update && !h->use_rtc && h->n_params == 1 && h->n_classes == 1 && n_learn >= 1 && n_learn <= 2;
+    return !h->knobs.no_deferred_update && !h->use_rtc && h->n_params == 1 && h->n_classes == 1 && n_learn >= 1 && n_learn <= 2;
 }
 
 // The estimator's grid over this shard.
@@ -166,7 +168,7 @@ static int pg_plan(amc_handle* h, int nl, int sweep, bool reduce, int q_batch, P
                            : (h->potential == AMC_POTENTIAL_DOUBLE_WELL) ? launch_pg<amc::POT_DOUBLE_WELL>(h, a0, s0, -1, nl, sweep, red, mid)
                                                                          : launch_pg<amc::POT_HARMONIC>(h, a0, s0, -1, nl, sweep, red, mid);
             if (rc != AMC_OK) return rc;
-            if (std::getenv("AMC_DEBUG_PLAN")) std::fprintf(stderr, "[amc] estimator form nl=%d sweep=%d reduce=%d mid=%d: %d resident blocks per CU\n", nl, sweep, (int)red, (int)mid, h->occ_query);
+            if (h->knobs.debug_plan) std::fprintf(stderr, "[amc] estimator form nl=%d sweep=%d reduce=%d mid=%d: %d resident blocks per CU\n", nl, sweep, (int)red, (int)mid, h->occ_query);
             it = h->pg_resident.emplace(key, h->occ_query > 0 ? h->occ_query : 5).first;
         }
         *per_cu = it->second;
@@ -203,7 +205,7 @@ static bool np_single_launch(const amc_handle* h, int n_learn) { return h->n_par
 // ... and with SEVERAL learnable moves on one shard, a chain of such launches, one per move, each with its own tail (pg_accumulate_impl)
 static bool np_move_chain(const amc_handle* h, int n_learn)
 {
-    return h->n_params > 1 && h->n_classes == 1 && !h->comm && n_learn > 1 && !h->np_small_launches;
+    return h->n_params > 1 && h->n_classes == 1 && !h->comm && n_learn > 1 && !h->knobs.np_small_launches;
 }
 
 // A pool of several classes: does this call go down the general route?  *general = the kernel form the call needs builds.  The
@@ -213,7 +215,7 @@ static int class_general_route(amc_handle* h, int n_learn, bool with_sweep, bool
 {
     *general = true;
     if (h->n_classes <= 1 || h->n_params > 1) return AMC_OK;
-    if (h->class_per_move_forced) { *general = false; return AMC_OK; }
+    if (h->knobs.class_per_move) { *general = false; return AMC_OK; }
     if (n_learn < 1 || n_learn > AMC_MAX_LEARN || q_batch < 1 || q_batch > AMC_MAX_QBATCH) return AMC_OK;      // (the call's own validation speaks)
     const int nl = nl_capacity(n_learn);
     const int sweep = with_sweep ? (h->K > 1 ? 2 : (h->d_log ? 1 : 3)) : 0;
@@ -228,7 +230,7 @@ static int class_general_route(amc_handle* h, int n_learn, bool with_sweep, bool
     if (rc != AMC_ERR_COMPILE) return rc;
     h->class_form_error = amc_last_error();
     h->class_form_errors[key] = h->class_form_error;
-    if (std::getenv("AMC_DEBUG_PLAN"))
+    if (h->knobs.debug_plan)
         std::fprintf(stderr, "[amc] class pool: estimator form nl=%d sweep=%d reduce=%d does not build, one launch per learnable move instead: %s\n", nl, sweep, (int)red, h->class_form_error.c_str());
     *general = false;
     return AMC_OK;
@@ -279,7 +281,7 @@ static int pg_launch(amc_handle* h, const char* who, int n_learn, const int* lea
     a.tail_mode = tail;
     // a script-defined form whose own tail takes the learning step: the column groups the moves' optimisers never read are not summed
     // (amc_estimator.h; gradients_data is consumed and reset in that tail, so nothing of them could be seen afterwards)
-    if (opt && (tail == 3 || tail == (int)amc::PG_TAIL_GROUPS) && h->use_rtc && !h->no_column_skip)
+    if (opt && (tail == 3 || tail == (int)amc::PG_TAIL_GROUPS) && h->use_rtc && !h->knobs.no_column_skip)
         a.tail_mode |= amc::pg_skip_bits(opt->kind + (call_ids ? l_base : 0), n_learn);
     a.l_base = l_base;
     {
@@ -550,7 +552,7 @@ static int pg_accumulate_impl(amc_handle* h, int n_learn, const int* learn_ids, 
     }
     // (a communicator of ONE rank: its all-reduce is the identity -- the single-shard forms, no collective; AMC_SHARD_ROUTE_ON_ONE_RANK=1
     // sends it down the shards' route all the same: the only way to time that route's launches and collective on a one-GPU box)
-    const bool shards = h->comm && (h->comm_ranks > 1 || h->shard_route_one_rank);
+    const bool shards = h->comm && (h->comm_ranks > 1 || h->knobs.shard_route_one_rank);
     // A fused time step that also updates may leave the learning step to the next launch's prologue (amc::pg_apply_pending,
     // round 5): the tail then ends at the group sums -- between shards: at this shard's records and the all-reduce behind them --
     // instead of going on through the second level of sums, a ticket and the update (single shard: 63.3 -> 62.5 us per
@@ -566,7 +568,7 @@ static int pg_accumulate_impl(amc_handle* h, int n_learn, const int* learn_ids, 
     // of capacity <= 4 hold four each -- the pool of the reference's test/pgmc_test.jl (six learnable moves, q_batch_size = 10) at 1e7
     // chains: 29.6 -> 25.x us per sample.  The launches take the call's moves in order, so every chain sees its samples in the
     // reference's order (move-major), the draws are named by the move's index in the call (l_base): the same bits.
-    if (!shards && !with_sweep && n_learn > 4 && !h->use_rtc && !h->np_small_launches) {
+    if (!shards && !with_sweep && n_learn > 4 && !h->use_rtc && !h->knobs.np_small_launches) {
         PgPlan whole;
         { const int rcp = pg_plan(h, nl_capacity(n_learn), 0, false, q_batch, &whole); if (rcp != AMC_OK) return rcp; }
         if (whole.mid) {
@@ -641,7 +643,7 @@ int amc_pg_route(amc_handle* h, int n_learn, int q_batch, int fused, char* why, 
     AMC_HIP(hipSetDevice(h->device));
     // the conditions of pgmc_steps_impl's `fused`: the sweep rides in the estimator launch
     const bool can_fuse = (!per_move_launches(h) || (np_single_launch(h, n_learn) && !h->comm)) && h->sweepstep == 1 && (h->d_log != nullptr || h->K == 1) &&
-                          n_learn <= 2 && log_form(h) != AMC_LOG_BYTES && std::getenv("AMC_NO_SWEEP_ESTIMATOR_FUSION") == nullptr;
+                          n_learn <= 2 && log_form(h) != AMC_LOG_BYTES && !h->knobs.no_sweep_estimator_fusion;
     auto say_why = [&]() {
         if (why && why_capacity > 0 && !h->class_form_error.empty()) {
             std::strncpy(why, h->class_form_error.c_str(), (size_t)why_capacity - 1);
@@ -723,11 +725,11 @@ static int pgmc_steps_impl(amc_handle* h, const char* who, int64_t n_steps, int 
     // moves (the kernel forms offered with a leading sweep: K = 1 with either counter form, K > 1 with its step log)
     // (pools of more than AMC_PACKED_LOG_MOVES moves take the two launches: the fused forms write the packed step log)
     bool fused = (!per_move_launches(h) || (np_single_launch(h, n_learn) && !h->comm)) && h->sweepstep == 1 && (h->d_log != nullptr || h->K == 1) && n_learn >= 1 && n_learn <= 2 &&
-                 log_form(h) != AMC_LOG_BYTES && std::getenv("AMC_NO_SWEEP_ESTIMATOR_FUSION") == nullptr;
+                 log_form(h) != AMC_LOG_BYTES && !h->knobs.no_sweep_estimator_fusion;
     // several parameters, several learnable moves, one shard: the sweep rides in the first move's launch of the chain
     const bool chain = np_move_chain(h, n_learn);
     if (chain)
-        fused = h->sweepstep == 1 && (h->d_log != nullptr || h->K == 1) && log_form(h) != AMC_LOG_BYTES && std::getenv("AMC_NO_SWEEP_ESTIMATOR_FUSION") == nullptr;
+        fused = h->sweepstep == 1 && (h->d_log != nullptr || h->K == 1) && log_form(h) != AMC_LOG_BYTES && !h->knobs.no_sweep_estimator_fusion;
     if (fused && h->n_classes > 1) {      // a pool of several classes: the fused form where it builds (class_general_route)
         const int rcg = class_general_route(h, n_learn, true, false, q_batch, &fused);
         if (rcg != AMC_OK) return rcg;

@@ -38,7 +38,7 @@ struct Hiprtc {
 
 std::mutex g_rtc_mu;
 Hiprtc g_hiprtc;
-std::map<std::string, RtcCode> g_rtc_code;        // key: expression '\n' instantiation
+std::map<std::string, RtcCode> g_rtc_code;        // key: arch, expression, instantiation, variant (rtc_compile)
 std::map<std::string, std::string> g_rtc_broken;  // same key: instantiations the compiler DIED on (its last words), not to be asked for again
 
 int load_hiprtc(Hiprtc& r)
@@ -104,7 +104,7 @@ uint64_t fnv1a(const std::string& s, uint64_t h = 1469598103934665603ull)
 
 std::string rtc_cache_path(const std::string& expr, const std::string& inst, const std::string& arch, const std::string& toolchain)
 {
-    const char* dir = std::getenv("AMC_RTC_CACHE_DIR");
+    const char* dir = amc_env("AMC_RTC_CACHE_DIR");
     if (!dir || !*dir) return std::string();
     uint64_t h = fnv1a(expr);
     h = fnv1a(inst, h ^ 0x9E3779B97F4A7C15ull);
@@ -200,7 +200,7 @@ const uint64_t WORKER_MAGIC_ANSWER = 0x3141435452434d41ull;       // "AMCRTCA1"
 
 std::string worker_path()
 {
-    if (const char* env = std::getenv("AMC_RTC_WORKER")) return env;
+    if (const char* env = amc_env("AMC_RTC_WORKER")) return env;
     Dl_info info;
     if (dladdr((const void*)&worker_path, &info) == 0 || !info.dli_fname) return std::string();
     std::string dir = info.dli_fname;
@@ -242,7 +242,7 @@ int build_in_child(const std::string& src, const std::string& inst, const std::v
     for (int i = 0; i < AMC_RTC_N_SOURCES; ++i) put_blob(&req, AMC_RTC_SOURCE_TEXTS[i], std::strlen(AMC_RTC_SOURCE_TEXTS[i]));
 
     double timeout_s = 600.0;
-    if (const char* env = std::getenv("AMC_RTC_TIMEOUT_S")) { const double v = std::atof(env); if (v > 0.0) timeout_s = v; }
+    if (const char* env = amc_env("AMC_RTC_TIMEOUT_S")) { const double v = std::atof(env); if (v > 0.0) timeout_s = v; }
 
     int sv[2] = {-1, -1}, ep[2] = {-1, -1};
     if (socketpair(AF_UNIX, SOCK_STREAM | SOCK_CLOEXEC, 0, sv) != 0) return fail(AMC_ERR_COMPILE, "run-time kernel build: socketpair: %s", std::strerror(errno));
@@ -370,32 +370,20 @@ int build_in_child(const std::string& src, const std::string& inst, const std::v
 
 // Compiles (or finds) the code object holding ONE instantiation, e.g. "amc::sweep_kernel<2,false,false,false,true,false>".
 // Needs no device.  On a compile error the hiprtc log goes into the error message (and *log_out).
-int rtc_compile(const std::string& expr_in, const std::string& inst, const std::string& arch, const RtcCode** out, std::string* log_out)
+// knobs: the variant of the kernel sources to build (AMC_RTC_*, AMC_NO_GAUSS_CLASS_ROWS, AMC_NO_SIGMA_MEMO).
+int rtc_compile(const std::string& expr_in, const std::string& inst, const std::string& arch, const AmcKnobs& knobs, const RtcCode** out,
+                std::string* log_out)
 {
     std::lock_guard<std::mutex> lock(g_rtc_mu);
-    const std::string key = arch + "\n" + expr_in + "\n" + inst + (std::getenv("AMC_NO_GAUSS_CLASS_ROWS") ? "\nno-gauss-rows" : "") +
-                            (std::getenv("AMC_NO_SIGMA_MEMO") ? "\nno-sigma-memo" : "") +
-                            (std::getenv("AMC_RTC_WAVES") ? std::string("\nwaves") + std::getenv("AMC_RTC_WAVES") : std::string());
-    auto it = g_rtc_code.find(key);
-    if (it != g_rtc_code.end()) { *out = &it->second; return AMC_OK; }
-    {
-        auto bk = g_rtc_broken.find(key);
-        if (bk != g_rtc_broken.end()) return fail(AMC_ERR_COMPILE, "%s", bk->second.c_str());
-    }
-    { const int rc = load_hiprtc(g_hiprtc); if (rc != AMC_OK) return rc; }
-    int rtc_major = 0, rtc_minor = 0;
-    (void)g_hiprtc.Version(&rtc_major, &rtc_minor);
     // the K > 1 fused sweep + estimator kernels are built with Machine LICM off, like their offline twins (amc_pg_fused.hip),
     // (decided from the instantiation's FOURTH template argument, SWEEP == 2 -- `<POT, NL, BETA, SWEEP, REDUCE, MIDFLUSH>`: a
     // substring test would also catch NL = 2 followed by BETA)
     const bool licm_off = [&] {
         // AMC_RTC_LICM=all-off / est-off / off-for-none (developer knob, A/B): every form, every estimator form, no form
-        if (const char* env = std::getenv("AMC_RTC_LICM")) {
-            const std::string v = env;
-            if (v == "all-off") return true;
-            if (v == "off-for-none") return false;
-            if (v == "est-off") return inst.rfind("amc::pg_estimate_kernel<", 0) == 0;
-        }
+        const std::string& v = knobs.rtc_licm;
+        if (v == "all-off") return true;
+        if (v == "off-for-none") return false;
+        if (v == "est-off") return inst.rfind("amc::pg_estimate_kernel<", 0) == 0;
         const std::string head = "amc::pg_estimate_kernel<";
         if (inst.rfind(head, 0) != 0) return false;
         size_t at = head.size();
@@ -411,11 +399,20 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
         // VGPRs, 66 -> 20 scalar spills, 151 -> 144 us at 1e7 chains; the one-parameter forms are indifferent)
         return expr_in.find('\x0e') != std::string::npos;
     }();
-    const std::string cache_file = rtc_cache_path(expr_in, inst, arch, "hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) +
-                                                                           (licm_off ? " licm-off" : "") +
-                                                                           (std::getenv("AMC_NO_GAUSS_CLASS_ROWS") ? " no-gauss-rows" : "") +
-                                                                           (std::getenv("AMC_NO_SIGMA_MEMO") ? " no-sigma-memo" : "") +
-                                                                           (std::getenv("AMC_RTC_WAVES") ? std::string(" waves") + std::getenv("AMC_RTC_WAVES") : std::string()));
+    // the variant of the sources, as the disk cache key has always spelt it (the in-process key carries the same text)
+    const std::string variant = std::string(licm_off ? " licm-off" : "") + (knobs.no_gauss_class_rows ? " no-gauss-rows" : "") +
+                                (knobs.no_sigma_memo ? " no-sigma-memo" : "") + (knobs.rtc_waves_set ? " waves" + knobs.rtc_waves : std::string());
+    const std::string key = arch + "\n" + expr_in + "\n" + inst + "\n" + variant;
+    auto it = g_rtc_code.find(key);
+    if (it != g_rtc_code.end()) { *out = &it->second; return AMC_OK; }
+    {
+        auto bk = g_rtc_broken.find(key);
+        if (bk != g_rtc_broken.end()) return fail(AMC_ERR_COMPILE, "%s", bk->second.c_str());
+    }
+    { const int rc = load_hiprtc(g_hiprtc); if (rc != AMC_OK) return rc; }
+    int rtc_major = 0, rtc_minor = 0;
+    (void)g_hiprtc.Version(&rtc_major, &rtc_minor);
+    const std::string cache_file = rtc_cache_path(expr_in, inst, arch, "hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) + variant);
     {
         RtcCode cached;
         if (rtc_cache_load(cache_file, &cached)) {
@@ -448,8 +445,8 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
     // built at run time, for Float32 state, are asked for by name: those builds keep them.)
     if (inst.find('<') != std::string::npos) src += "#define AMC_PLAIN_KERNELS 0\n";
     if (f32) src += "#define AMC_STATE_F32 1\n";
-    if (std::getenv("AMC_NO_SIGMA_MEMO")) src += "#define AMC_NO_SIGMA_MEMO 1\n";      // A/B: amc_log(sigma) per lane and step in K > 1 sweeps (amc_model.h SigmaArg)
-    if (const char* w = std::getenv("AMC_RTC_WAVES")) src += "#define AMC_RTC_WAVES " + std::to_string(std::atoi(w)) + "\n";       // A/B: amdgpu_waves_per_eu of the script-defined estimator forms
+    if (knobs.no_sigma_memo) src += "#define AMC_NO_SIGMA_MEMO 1\n";      // A/B: amc_log(sigma) per lane and step in K > 1 sweeps (amc_model.h SigmaArg)
+    if (knobs.rtc_waves_set) src += "#define AMC_RTC_WAVES " + std::to_string(std::atoi(knobs.rtc_waves.c_str())) + "\n";       // A/B: amdgpu_waves_per_eu of the script-defined estimator forms
     auto cut_tail = [&](char mark) -> std::string {      // removes and returns what follows the LAST section mark
         const size_t at = expr.find(mark);
         if (at == std::string::npos) return std::string();
@@ -511,7 +508,7 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
             }
             at = nxt;
         }
-        if (gauss_mask != 0u && std::getenv("AMC_NO_GAUSS_CLASS_ROWS") == nullptr) {
+        if (gauss_mask != 0u && !knobs.no_gauss_class_rows) {
             src += "#define AMC_CLASS_GAUSS_MASK " + std::to_string(gauss_mask) + "\n";
             if (gauss_est_mask != 0u) src += "#define AMC_CLASS_GAUSS_EST_MASK " + std::to_string(gauss_est_mask) + "\n";
         }
@@ -529,7 +526,7 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
     if (licm_off) { opts.push_back("-mllvm"); opts.push_back("-disable-machine-licm"); }
     Built built;
     {
-        const char* inproc = std::getenv("AMC_RTC_IN_PROCESS");
+        const char* inproc = amc_env("AMC_RTC_IN_PROCESS");
         const int rcb = (inproc && inproc[0] == '1') ? build_in_process(src, inst, opts, &built) : build_in_child(src, inst, opts, &built);
         if (rcb != AMC_OK) {                           // the compiler could not be run, died or timed out: AMC_ERR_COMPILE, message set
             if (built.died) {                          // ... died: it will again -- remembered for the process and, with a cache directory, beyond
@@ -567,7 +564,7 @@ int rtc_function(amc_handle* h, const std::string& inst, hipFunction_t* fn)
     auto it = h->rtc_fn.find(inst);
     if (it != h->rtc_fn.end()) { *fn = it->second; return AMC_OK; }
     const RtcCode* code = nullptr;
-    { const int rc = rtc_compile(h->pot_expr, inst, h->arch, &code, nullptr); if (rc != AMC_OK) return rc; }
+    { const int rc = rtc_compile(h->pot_expr, inst, h->arch, h->knobs, &code, nullptr); if (rc != AMC_OK) return rc; }
     hipModule_t mod = nullptr;
     AMC_HIP(hipModuleLoadData(&mod, code->code.data()));
     h->rtc_mods.push_back(mod);
@@ -595,7 +592,7 @@ int amc_potential_check(const char* potential_expr, char* log, int log_capacity)
     { const int rc = validate_potential_expr(potential_expr); if (rc != AMC_OK) return rc; }
     const RtcCode* code = nullptr;
     std::string text;
-    const int rc = rtc_compile(potential_expr, "amc::energy_kernel<2>", AMC_BUILD_ARCH, &code, &text);
+    const int rc = rtc_compile(potential_expr, "amc::energy_kernel<2>", AMC_BUILD_ARCH, amc_knobs(), &code, &text);
     if (log && log_capacity > 0) {
         std::strncpy(log, text.c_str(), (size_t)log_capacity - 1);
         log[log_capacity - 1] = 0;

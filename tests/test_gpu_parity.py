@@ -1155,7 +1155,7 @@ def test_per_chain_counters_count_past_2_to_the_32(gpu, oracle, K):
 @pytest.mark.parametrize("K", [1, 2, 3])
 def test_counters_across_the_16_bit_mark(gpu, oracle, K):
     """Handles with K <= 4 keep their per-chain counters as two u16 planes; the high plane stays out of the folds until the call
-    that would count past 65 535 steps (amc_api.hip counter_room) and is written only where a low half carries: counts,
+    that would count past 65 535 steps (amc_counters.hip counter_room) and is written only where a low half carries: counts,
     acceptance sums and the states on both sides of the mark against the oracle's increments, with neighbouring counters at
     0xFFFF and 0 (the packing of the 16-bit quads, carries in some lanes of a quad only)."""
     M = 2051
