@@ -28,12 +28,15 @@ def main(argv=None):
     ap.add_argument("--beta", type=float, default=2.0)
     ap.add_argument("--path", default=None)
     ap.add_argument("--dtype", default="f64", choices=("f64", "f32"), help="Particle{T}: Float64 (reference scripts) or Float32")
+    ap.add_argument("--param-dtype", default="f64", choices=("f64", "f32"),
+                    help="eltype of Move.parameters: Float64, or Float32 (sigma = 0.1f0; needs --dtype f32: the all-Float32 model)")
     args = ap.parse_args(argv)
 
     seed, beta, M, steps = args.seed, args.beta, args.chains, args.steps
     burn = min(1000, steps // 10)
     chains = ma.ParticleChains.uniform(M, beta, -2.0, 2.0, dtype=args.dtype)                    # x0 = 4 rand() - 2; potential(x) = x^2
-    pool = (ma.Move(ma.Displacement(0.0), ma.StandardGaussian(), {"sigma": 0.1}, 1.0),)
+    sigma = np.float32([0.1]) if args.param_dtype == "f32" else {"sigma": 0.1}                  # ComponentArray(σ = 0.1f0) / (σ = 0.1)
+    pool = (ma.Move(ma.Displacement(0.0), ma.StandardGaussian(), sigma, 1.0),)
     sampletimes = ma.build_schedule(steps, burn, [0, 10])
     path = args.path or f"data/MC/particle_1d/Harmonic/beta{beta}/M{M}/seed{seed}"
 

@@ -85,6 +85,22 @@ typedef enum amc_state_dtype {
     AMC_DTYPE_F32 = 1
 } amc_state_dtype;
 
+/* The policy parameters have a type of their own (amc_config.param_dtype, an amc_state_dtype value).  AMC_DTYPE_F64 is the above:
+ * ComponentArray(sigma = 0.1) next to any Particle{T}.  AMC_DTYPE_F32 is the all-Float32 model, ComponentArray(sigma = 0.1f0) next
+ * to Particle(0f0, 2f0): sigma, the normal variate (randn(rng, Float32)), delta = sigma * z and the
+ * quotient -(delta^2) / (2 sigma^2) of log_proposal_density are Float32; log(2 pi sigma^2) / 2 (2 pi is a Float64 in Julia), the
+ * acceptance probability and the uniforms stay Float64.  It requires state_dtype = AMC_DTYPE_F32 (a Float32 sigma under Float64
+ * state promotes back to the Float64 arithmetic: AMC_ERR_BAD_ARG rather than an alias).  cfg->sigma[k], and what amc_set_parameters
+ * takes, must then be Float32 VALUES -- a parameter is checked, not rounded: AMC_ERR_BAD_ARG if (double)(float)s != s -- in
+ * [AMC_SIGMA_F32_MIN, AMC_SIGMA_F32_MAX] = [2^-63, 2^60]: sigma^2 >= 2^-126 keeps sigma * sigma and 2 sigma^2 normal Float32s, and
+ * sigma <= 2^60 keeps delta^2 = (sigma z)^2 <= 2^120 * 73.5 finite for every normal variate (|z| <= 8.58), so the acceptance
+ * argument is never NaN; 2 sigma^2 <= 2^121 does not overflow.
+ * Such a handle sweeps (every amc_sweep* / amc_reduce* / counter / state entry; amc_create and amc_create_custom); the estimator
+ * (amc_pg_*, amc_pgmc_*: AMC_ERR_STATE) and the creators of script-defined policies (amc_create_policy_model with a scale,
+ * amc_create_proposal_model, _action_model, _vector_policy_model, _mixed_model: AMC_ERR_BAD_ARG) refuse it. */
+#define AMC_SIGMA_F32_MIN 0x1.0p-63
+#define AMC_SIGMA_F32_MAX 0x1.0p+60
+
 typedef struct amc_handle amc_handle;
 
 /* Mirrors Metropolis(chains; pool, sweepstep=1, seed=1, ...) metropolis.jl:288-291
@@ -100,7 +116,8 @@ typedef struct amc_config {
     double   beta;               /* Particle.beta (particle_1d.jl:11), shared by all chains
                                     unless amc_upload_state passes a per-chain array */
     const double *sigma;         /* [K] StandardGaussian parameters sigma_k (particle_1d.jl:50),
-                                    each in [1e-100, 1e100] */
+                                    each in [1e-100, 1e100]; param_dtype = AMC_DTYPE_F32: Float32 values in
+                                    [AMC_SIGMA_F32_MIN, AMC_SIGMA_F32_MAX] */
     const double *weight;        /* [K] Move.weight (metropolis.jl:144); must sum to ~1 */
     uint64_t seed;               /* Metropolis.seed (metropolis.jl:235) -> Philox key */
     int32_t  sweepstep;          /* Metropolis.sweepstep (metropolis.jl:234), >= 1 */
@@ -110,7 +127,8 @@ typedef struct amc_config {
     void    *stream;             /* optional hipStream_t to run on; NULL -> library-owned */
     int32_t  state_dtype;        /* amc_state_dtype.  Callers built against the 0.1 layout (struct_size 88, without
                                     this field) get AMC_DTYPE_F64 */
-    int32_t  reserved;           /* must be 0 */
+    int32_t  param_dtype;        /* amc_state_dtype of the policy parameters (see above).  0 = AMC_DTYPE_F64: every caller
+                                    that wrote the 0 this field ("reserved") used to demand */
 } amc_config;
 #define AMC_CONFIG_SIZE_V0_1 88u
 

@@ -60,7 +60,7 @@ struct AmcConfig
     per_chain_counters::Int32
     stream::Ptr{Cvoid}
     state_dtype::Int32            # 0: Float64, 1: Float32 (Particle{Float32}); host buffers stay Float64 either way
-    reserved::Int32
+    param_dtype::Int32            # eltype(move.parameters): 0 Float64, 1 Float32 (needs state_dtype 1); sigma then holds Float32 values
 end
 
 const POTENTIAL_HARMONIC = Int32(0)
@@ -153,6 +153,14 @@ function HIPMetropolis(chains; pool=missing, sweepstep=1, seed=1, device=0, pote
     K = length(template)
     pools = LazyPools(template, length(chains), Matrix{Int64}(undef, 0, K), Matrix{Int64}(undef, 0, K))
     n_params = length(template[1].parameters)
+    # eltype(move.parameters): Float32 parameters (ComponentArray(σ = 0.1f0)) next to Particle{Float32} are the all-Float32 model
+    # (amc_config.param_dtype, DESIGN.md section 3.12); Float64.(σ) of a Float32 is exact, which is what the engine checks.  A pool
+    # that mixes the two types, or Float32 parameters on Float64 chains, is refused here as the engine would.
+    param_types = unique([eltype(move.parameters) for move in template])
+    length(param_types) == 1 || error("HIPMetropolis: every move of a pool carries parameters of one type (got $(param_types))")
+    param_f32 = param_types[1] === Float32
+    param_f32 && eltype_of_state(chains) !== Float32 &&
+        error("HIPMetropolis: Float32 parameters need Float32 chains (param_dtype requires state_dtype = Float32)")
     thetas = [Float64.(collect(move.parameters)) for move in template]
     # parameter 0 at creation must pass sigma's range check; the full vectors follow through amc_set_parameters
     sigma = n_params == 1 ? Float64[th[1] for th in thetas] : ones(Float64, K)
@@ -166,7 +174,7 @@ function HIPMetropolis(chains; pool=missing, sweepstep=1, seed=1, device=0, pote
                         pot_id,
                         Int32(K), chains[1].β, pointer(sigma), pointer(weight), UInt64(seed),
                         Int32(sweepstep), Int32(per_chain_counters), C_NULL,
-                        Int32(eltype_of_state(chains) === Float32 ? 1 : 0), Int32(0))
+                        Int32(eltype_of_state(chains) === Float32 ? 1 : 0), Int32(param_f32 ? 1 : 0))
         if classes !== nothing
             # a pool that mixes policy / action types: one (sample, logq, dlogq, perform, invert) per class (nothing: not given),
             # class_of_move[k] (1-based here) the class of move k -- amc_create_mixed_model

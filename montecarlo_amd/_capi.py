@@ -46,7 +46,7 @@ class AmcConfig(C.Structure):
         ("per_chain_counters", C.c_int32),
         ("stream", C.c_void_p),
         ("state_dtype", C.c_int32),
-        ("reserved", C.c_int32),
+        ("param_dtype", C.c_int32),
     ]
 
 
@@ -267,8 +267,11 @@ class HipEngine:
                  per_chain_counters: bool = True, device: int = 0, stream: Optional[int] = None,
                  reward_expr: Optional[str] = None, dtype: str = "f64", scale_expr: Optional[str] = None,
                  proposal: Optional[Sequence[Optional[str]]] = None, n_params: int = 1,
-                 classes: Optional[Sequence[Sequence[Optional[str]]]] = None, class_of_move: Optional[Sequence[int]] = None):
-        """``n_params`` > 1 (with ``proposal``): a policy with several parameters (amc_create_vector_policy_model) -- the
+                 classes: Optional[Sequence[Sequence[Optional[str]]]] = None, class_of_move: Optional[Sequence[int]] = None,
+                 param_dtype: str = "f64"):
+        """``param_dtype`` "f32" (with ``dtype`` "f32"): the all-Float32 model -- sigma, the normal variate and the displacement
+        are Float32 (amc_config.param_dtype); ``sigma`` must then hold Float32 values.  Sweeps with the built-in policy only.
+        ``n_params`` > 1 (with ``proposal``): a policy with several parameters (amc_create_vector_policy_model) -- the
         expressions see theta0 .. theta{P-1}, ``proposal[2]`` is the list of the P partials of logq (or None), and ``sigma``
         holds one parameter VECTOR per move.
         ``classes`` (with ``class_of_move``): a pool that MIXES policy / action types (amc_create_mixed_model) -- one
@@ -277,6 +280,9 @@ class HipEngine:
         if str(dtype) not in STATE_DTYPES:
             raise AmcError(f"unknown state dtype {dtype!r}; one of {sorted(STATE_DTYPES)}")
         self.dtype = "f32" if STATE_DTYPES[str(dtype)] else "f64"
+        if str(param_dtype) not in STATE_DTYPES:
+            raise AmcError(f"unknown param_dtype {param_dtype!r}; one of {sorted(STATE_DTYPES)}")
+        self.param_dtype = "f32" if STATE_DTYPES[str(param_dtype)] else "f64"
         expr = getattr(potential, "expr", None)        # system.CustomPotential: a C expression in x
         if expr is None and potential not in POTENTIALS:
             raise AmcError(f"unknown potential {potential!r}; the HIP engine offers {sorted(POTENTIALS)} "
@@ -312,6 +318,7 @@ class HipEngine:
         cfg.per_chain_counters = 1 if per_chain_counters else 0
         cfg.stream = stream
         cfg.state_dtype = STATE_DTYPES[self.dtype]
+        cfg.param_dtype = STATE_DTYPES[self.param_dtype]
         self._lib = lib
         self._h = C.c_void_p()
         enc = lambda t: None if t is None else str(t).encode()

@@ -153,8 +153,16 @@ static int create_impl(const amc_config* cfg, const char* potential_expr, amc_ha
     const int state_dtype = cfg->struct_size == sizeof(amc_config) ? cfg->state_dtype : (int)AMC_DTYPE_F64;
     if (state_dtype != AMC_DTYPE_F64 && state_dtype != AMC_DTYPE_F32)
         return fail(AMC_ERR_BAD_ARG, "amc_create: unknown state_dtype %d", state_dtype);
-    if (cfg->struct_size == sizeof(amc_config) && cfg->reserved != 0)
-        return fail(AMC_ERR_BAD_ARG, "amc_create: reserved must be 0");
+    const int param_dtype = cfg->struct_size == sizeof(amc_config) ? cfg->param_dtype : (int)AMC_DTYPE_F64;
+    if (param_dtype != AMC_DTYPE_F64 && param_dtype != AMC_DTYPE_F32)
+        return fail(AMC_ERR_BAD_ARG, "amc_create: unknown param_dtype %d", param_dtype);
+    const bool param_f32 = param_dtype == AMC_DTYPE_F32;
+    if (param_f32 && state_dtype != AMC_DTYPE_F32)
+        return fail(AMC_ERR_BAD_ARG, "amc_create: param_dtype = AMC_DTYPE_F32 requires state_dtype = AMC_DTYPE_F32 (a Float32 sigma under "
+                                     "Float64 state promotes to the Float64 arithmetic: ask for param_dtype = AMC_DTYPE_F64)");
+    if (param_f32 && (scale_expr || proposal))
+        return fail(AMC_ERR_BAD_ARG, "amc_create: script-defined policies are not available with param_dtype = AMC_DTYPE_F32 "
+                                     "(Float32 policy parameters: the built-in Gaussian policy only)");
     if (cfg->n_chains < 1) return fail(AMC_ERR_BAD_ARG, "amc_create: n_chains must be >= 1");
     if (cfg->chain_offset < 0 || (cfg->chain_offset & 1))
         return fail(AMC_ERR_BAD_ARG, "amc_create: chain_offset must be even and >= 0 (shards split on chain pairs)");
@@ -188,7 +196,10 @@ static int create_impl(const amc_config* cfg, const char* potential_expr, amc_ha
     if (!cfg->sigma || !cfg->weight) return fail(AMC_ERR_BAD_ARG, "amc_create: sigma/weight is NULL");
     double wsum = 0.0;
     for (int k = 0; k < cfg->n_moves; ++k) {
-        if (!(cfg->sigma[k] >= 1e-100) || !(cfg->sigma[k] <= 1e100))
+        if (param_f32) {
+            const int rc_s = check_sigma_f32("amc_create", k, cfg->sigma[k]);
+            if (rc_s != AMC_OK) return rc_s;
+        } else if (!(cfg->sigma[k] >= 1e-100) || !(cfg->sigma[k] <= 1e100))
             return fail(AMC_ERR_BAD_ARG, "amc_create: sigma[%d] must lie in [1e-100, 1e100]", k);
         if (!(cfg->weight[k] >= 0.0) || !std::isfinite(cfg->weight[k]))
             return fail(AMC_ERR_BAD_ARG, "amc_create: weight[%d] must be finite and >= 0", k);
@@ -244,8 +255,10 @@ static int create_impl(const amc_config* cfg, const char* potential_expr, amc_ha
     h->M_global = cfg->n_chains_global;
     h->potential = cfg->potential;
     h->f32 = state_dtype == AMC_DTYPE_F32;
+    h->param_f32 = param_f32;
     h->use_rtc = h->f32 || cfg->potential == AMC_POTENTIAL_CUSTOM;
     h->pot_expr = encode_model_expr(h->f32, potential_expr, reward_expr, scale_expr, proposal);
+    if (param_f32) h->pot_expr.insert(1, "\x15");        // behind the '\x02' of Float32 state: the kernels are built with AMC_PARAM_F32
     if (potential_expr && scale_expr) h->scaled_policy = true;
     if (potential_expr && proposal) {
         if (proposal->n_classes > 1) {

@@ -228,6 +228,8 @@ struct amc_handle {
     std::string arch = AMC_BUILD_ARCH;   // the device's ISA name (gcnArchName up to its first ':'): what hiprtc compiles for
     std::string pot_expr;         // AMC_POTENTIAL_CUSTOM: the C expression of potential(x); '\x02' in front: Float32 state
     bool f32 = false;             // state_dtype == AMC_DTYPE_F32: d_x / d_beta hold floats
+    bool param_f32 = false;       // param_dtype == AMC_DTYPE_F32 (needs f32): sigma, the normal variate, delta = sigma z and the quotient of
+                                  // log_proposal_density are Float32 (kernels built with AMC_PARAM_F32); sweeps with the built-in policy only
     bool scaled_policy = false;   // the proposal width is sigma * scale(x) (amc_create_policy_model)
     bool script_policy = false;   // sample_action! / log_proposal_density are script-defined expressions (amc_create_proposal_model)
     bool script_dlogq = false;    // ... and so is d logq / d sigma: the estimator is available
@@ -258,6 +260,14 @@ AMC_INTERNAL RedTicket* red_next(amc_handle* h);
 AMC_INTERNAL int finish_fused_reduce(amc_handle* h, int grid);
 AMC_INTERNAL bool reduce_fits_in_grid(const amc_handle* h, int grid);
 AMC_INTERNAL int push_params(amc_handle* h, const double* sigma, const double* weight);  // amc_parameters.hip
+AMC_INTERNAL int check_sigma_f32(const char* who, int k, double s);     // a sigma of a param_dtype = AMC_DTYPE_F32 handle
+// The policy-gradient estimator with Float32 parameters (Dual{Float32}) does not exist yet: its entries refuse such a handle
+// before any launch and any compile.
+#define AMC_REFUSE_PARAM_F32(h, who)                                                                                        \
+    do {                                                                                                                    \
+        if ((h)->param_f32)                                                                                                 \
+            return fail(AMC_ERR_STATE, "%s: not available with param_dtype = AMC_DTYPE_F32 (Float32 policy parameters: sweeps only)", (who)); \
+    } while (0)
 AMC_INTERNAL int pg_resolve(amc_handle* h);      // takes a pending learning step now (amc_pg.hip)
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)

@@ -45,6 +45,20 @@ typedef double real_t;
 typedef double2 real2;
 #endif
 
+// Type of the policy parameters.  A handle created with param_dtype = AMC_DTYPE_F32 (Float32 state only) is the all-Float32 model --
+// Particle(0f0, 2f0) next to ComponentArray(sigma = 0.1f0) -- and gets these sources with AMC_PARAM_F32 defined as well: sigma, the
+// normal variate (randn(rng, Float32): box_muller_f32), delta = sigma * z and the quotient -(delta^2) / (2 sigma^2) are Float32;
+// log(2 pi sigma^2) / 2 (2 pi is a Float64 in Julia), arg, the acceptance probability and the uniforms stay Float64.  DESIGN.md section 3.12.
+// Only the sweep with the built-in Gaussian policy exists in this form (the host refuses everything else for such a handle).
+#ifdef AMC_PARAM_F32
+#ifndef AMC_STATE_F32
+#error "AMC_PARAM_F32 needs AMC_STATE_F32: a Float32 sigma under Float64 state promotes back to the Float64 arithmetic"
+#endif
+typedef float param_t;
+#else
+typedef double param_t;
+#endif
+
 // Rows of the per-move parameter table.
 enum { PT_SIGMA = 0, PT_DEN = 1, PT_LOGC = 2, PT_CUM = 3, PT_DDEN = 4, PT_DLHALF = 5, PT_WEIGHT = 6,
        PT_RDEN = 7, PT_C3HI = 8, PT_C3LO = 9,
@@ -485,13 +499,17 @@ struct Proposal {
 };
 
 template <int POT>
-__device__ __forceinline__ Proposal propose(real_t x, real_t beta, double sigma, double z, const double* T)
+__device__ __forceinline__ Proposal propose(real_t x, real_t beta, param_t sigma, param_t z, const double* T)
 {
     Proposal p;
     // Displacement.delta::T = rand(rng, Normal(zero(T), sigma::Float64)) = 0.0 + sigma*z.  fma(sigma, z, 0.0) is that value
     // bit for bit in every case: the product is rounded once either way and adding +0.0 changes nothing but the sign of a
     // zero product (-0.0 -> +0.0 in both forms; NaN and infinities pass through alike).  One instruction instead of two.
+#ifdef AMC_PARAM_F32
+    p.delta = __builtin_fmaf(sigma, z, 0.0f);        // 0f0 + sigma * randn(rng, Float32): all Float32 (same argument)
+#else
     p.delta = (real_t)__builtin_fma(sigma, z, 0.0);
+#endif
     const real_t e1 = potential<POT>(x, T);
     p.xn = x + p.delta;
     const real_t e2 = potential<POT>(p.xn, T);
@@ -505,11 +523,17 @@ __device__ __forceinline__ Proposal propose(real_t x, real_t beta, double sigma,
 //   -708 <= arg < 0    -> alpha == exp(arg) (<= 1)                  : accept iff exp(arg) > u
 //   arg < -708 or NaN  -> alpha == 0 or NaN (Julia's min keeps NaN) : reject
 // (bitwise | and & on purpose: no short-circuit branches)
-__device__ __forceinline__ bool accept_exact(real_t delta, real_t dlogp, double den, double rden, double logc, double u,
+__device__ __forceinline__ bool accept_exact(real_t delta, real_t dlogp, param_t den, double rden, double logc, double u,
                                              const double* T)
 {
+#ifdef AMC_PARAM_F32
+    // Float32 sigma: -(delta^2) / (2 sigma^2) is a Float32 quotient (IEEE: -fno-fast-math), then Float64 with the Float64 log term
+    (void)rden;
+    const double logq = (double)((-(delta * delta)) / den) - logc;
+#else
     // (delta)^2 and its negation are formed in T, the division by the Float64 2 sigma^2 promotes
     const double logq = div_by_const((double)(-(delta * delta)), den, rden) - logc;   // == (-(d*d)) / den - logc, bit for bit
+#endif
     const double arg = ((double)dlogp + logq) - logq;
     const bool c_pos = arg >= 0.0, c_rng = arg >= -708.0, c_exp = exp_core_f64(arg, T) > u;
     return c_pos | (c_rng & c_exp);
@@ -521,6 +545,8 @@ __device__ __forceinline__ bool accept_exact(real_t delta, real_t dlogp, double 
 //   arg vs dlogp      arg = fl(fl(dlogp + logq) - logq), |arg - dlogp| <= 2^-53 (2|dlogp| + |logq|) with
 //                     |logq| <= z^2/2 (1 + 2^-50) + |log(2 pi s^2)/2| <= 37 + 231 (|z| <= 8.5, 1e-100 <= s <= 1e100)
 //                                                                                                       < 4e-14
+//                     (AMC_PARAM_F32: |logq| <= z^2/2 (1 + 2^-21) + |log(2 pi s^2)/2| <= 37 + 45 (|z| <= 8.58,
+//                     2^-63 <= s <= 2^60; delta^2 <= 2^127 stays finite, so arg is no NaN), 2^-53 (34 + 82) = 1.3e-14: same line)
 //   float(dlogp)      2^-24 * 17                                                                          1.1e-6
 //   * log2e (float)   constant 1.3e-8 rel + product rounding 6e-8, times |y| <= 24.6, times ln 2          1.3e-6
 //   v_exp_f32         1 ulp by the ISA; amc_selftest_accept_filter measures it exhaustively               < 5e-7
@@ -674,7 +700,8 @@ __device__ __forceinline__ ScriptStep mh_script(real_t x, real_t beta, S sigma, 
 // K == 1: the pool's only move, wave-uniform scalars.  K > 1: read from the LDS copy of the move table by the chain's
 // move index -- inside the undecided arm only, the common path reads sigma alone.
 struct MoveExact {
-    double dn, rd, lc;
+    param_t dn;
+    double rd, lc;
 };
 
 // One mc_step! of both chains of a pair.  force_mask (wave-uniform, all ones or zero; tests) sends every wave through
@@ -684,8 +711,8 @@ struct MoveExact {
 // per chain-step, ~1.5 % of wave-steps).  `pu` / `have_pu` (wave-uniform): the accept draw, if the move pick of this
 // step already needed it (pair_steps).
 template <int POT, bool MULTI>
-__device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, double sg0, double sg1, int k0, int k1,
-                                        const double* s_tab, MoveExact m1, double z0, double z1, u32x4 pn, u32x4 pu,
+__device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t sg0, param_t sg1, int k0, int k1,
+                                        const double* s_tab, MoveExact m1, param_t z0, param_t z1, u32x4 pn, u32x4 pu,
                                         bool have_pu, u32x4 accept_ctr, uint32_t key0, uint32_t key1, const double* T,
                                         unsigned long long force_mask, uint32_t& acc_bits, unsigned long long& m0,
                                         unsigned long long& m1_out, const UserTheta& th1)
@@ -747,8 +774,14 @@ __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, double 
         }
         MoveExact e0 = m1, e1 = m1;
         if (MULTI) {
+#ifdef AMC_PARAM_F32
+            // row 0 of the table holds Float32 pairs in this form: sigma [0, 64), 2 sigma^2 [64, 128) (sweep_kernel)
+            e0.dn = reinterpret_cast<const float*>(s_tab)[AMC_MAX_MOVES + k0]; e0.lc = s_tab[2 * AMC_MAX_MOVES + k0];
+            e1.dn = reinterpret_cast<const float*>(s_tab)[AMC_MAX_MOVES + k1]; e1.lc = s_tab[2 * AMC_MAX_MOVES + k1];
+#else
             e0.dn = s_tab[AMC_MAX_MOVES + k0]; e0.lc = s_tab[2 * AMC_MAX_MOVES + k0]; e0.rd = s_tab[4 * AMC_MAX_MOVES + k0];
             e1.dn = s_tab[AMC_MAX_MOVES + k1]; e1.lc = s_tab[2 * AMC_MAX_MOVES + k1]; e1.rd = s_tab[4 * AMC_MAX_MOVES + k1];
+#endif
         }
         const bool a0 = accept_exact(p0.delta, p0.dlogp, e0.dn, e0.rd, e0.lc, uniform_accept(a0_12, pu.x, pu.y), T);
         const bool a1 = accept_exact(p1.delta, p1.dlogp, e1.dn, e1.rd, e1.lc, uniform_accept(a1_12, pu.z, pu.w), T);

@@ -3,6 +3,26 @@
 #define AMC_KERNEL_LINKAGE static      // this object's own copies of the plain kernels it launches (parameter tables)
 #include "amc_internal.h"
 
+// Float32 policy parameters: a parameter is checked, not rounded -- no caller gets a sigma they did not write -- and the range is
+// the one in which the Float32 arithmetic on sigma stays normal and finite (include/amc.h, amc_config.param_dtype).
+int check_sigma_f32(const char* who, int k, double s)
+{
+    if (!((double)(float)s == s))
+        return fail(AMC_ERR_BAD_ARG, "%s: sigma[%d] = %.17g is not a Float32 value (param_dtype = AMC_DTYPE_F32 takes (double)(float)sigma)", who, k, s);
+    if (!(s >= AMC_SIGMA_F32_MIN) || !(s <= AMC_SIGMA_F32_MAX))
+        return fail(AMC_ERR_BAD_ARG, "%s: sigma[%d] must lie in [2^-63, 2^60] with param_dtype = AMC_DTYPE_F32 (got %.9g)", who, k, s);
+    return AMC_OK;
+}
+
+// what derives from sigma, in the arithmetic of the handle's parameter type
+static int launch_prepare_params(amc_handle* h)
+{
+    if (h->param_f32) hipLaunchKernelGGL(amc::prepare_params_f32_kernel, dim3(1), dim3(64), 0, h->stream, h->d_ptab, h->K);
+    else hipLaunchKernelGGL(amc::prepare_params_kernel, dim3(1), dim3(64), 0, h->stream, h->d_ptab, h->K);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
 int push_params(amc_handle* h, const double* sigma, const double* weight)
 {
     { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
@@ -15,8 +35,7 @@ int push_params(amc_handle* h, const double* sigma, const double* weight)
     }
     AMC_HIP(hipMemcpyAsync(h->d_ptab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));   // tab is a stack-scoped host buffer
-    hipLaunchKernelGGL(amc::prepare_params_kernel, dim3(1), dim3(64), 0, h->stream, h->d_ptab, h->K);
-    AMC_HIP(hipGetLastError());
+    { const int rc = launch_prepare_params(h); if (rc != AMC_OK) return rc; }
     if (weight && h->K > 1) {      // the cumulative weights changed: rebuild the 12-bit move-pick table from them
         hipLaunchKernelGGL(amc::prepare_pick_kernel, dim3(AMC_PICK_CELLS / AMC_BLOCK), dim3(AMC_BLOCK), 0, h->stream, h->d_ptab, h->K,
                            h->d_pick);
@@ -50,7 +69,10 @@ int amc_set_parameters(amc_handle* h, int k, const double* p, int n)
         return fail(AMC_ERR_BAD_ARG, h->n_params == 1 ? "amc_set_parameters: StandardGaussian has exactly 1 parameter (sigma)"
                                                      : "amc_set_parameters: this handle's policy has %d parameters", h->n_params);
     if (h->n_params == 1) {
-        if (!(p[0] >= 1e-100) || !(p[0] <= 1e100))
+        if (h->param_f32) {
+            const int rc = check_sigma_f32("amc_set_parameters", k, p[0]);
+            if (rc != AMC_OK) return rc;
+        } else if (!(p[0] >= 1e-100) || !(p[0] <= 1e100))
             return fail(AMC_ERR_BAD_ARG, "amc_set_parameters: sigma must lie in [1e-100, 1e100] (got %.17g)", p[0]);
     } else {
         for (int i = 0; i < n; ++i)
@@ -62,8 +84,8 @@ int amc_set_parameters(amc_handle* h, int k, const double* p, int n)
         AMC_HIP(hipMemcpyAsync(h->d_ptab + theta_row(i) * AMC_MAX_MOVES + k, p + i, sizeof(double), hipMemcpyHostToDevice, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));
     if (h->n_params == 1) {            // what derives from sigma (the script kernels of a policy with several parameters read none of it)
-        hipLaunchKernelGGL(amc::prepare_params_kernel, dim3(1), dim3(64), 0, h->stream, h->d_ptab, h->K);
-        AMC_HIP(hipGetLastError());
+        const int rc = launch_prepare_params(h);
+        if (rc != AMC_OK) return rc;
     }
     return AMC_OK;
 }

@@ -85,6 +85,28 @@ AMC_KERNEL_LINKAGE __global__ void prepare_params_kernel(double* ptab, int n_mov
 }
 #endif
 
+// Float32 policy parameters (param_dtype = AMC_DTYPE_F32): sigma is a Float32 value, and what the sweep reads
+// besides it is what Julia forms from a Float32 sigma in log_proposal_density (particle_1d.jl:53):
+//   PT_DEN = PT_RDEN = 2 * sigma^2   Float32 operations (2 * sigma^2 with an Int 2 stays Float32), held exactly in the table's doubles
+//   PT_LOGC = log(2pi * sigma^2) / 2   2pi is a Float64 (2 * pi::Irrational), so the Float32 sigma^2 is converted and the rest is Float64
+// The other rows keep what prepare_params left (the estimator, their only reader, is refused for such a handle).
+#if AMC_PLAIN_KERNELS
+AMC_KERNEL_LINKAGE __global__ void prepare_params_f32_kernel(double* ptab, int n_moves)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    prepare_params(ptab, n_moves);
+    const double TWO_PI = 0x1.921fb54442d18p+2;
+    for (int k = 0; k < n_moves; ++k) {
+        const float sigma = (float)ptab[PT_SIGMA * AMC_MAX_MOVES + k];
+        const float s2 = sigma * sigma;
+        const float den = 2.0f * s2;
+        ptab[PT_DEN * AMC_MAX_MOVES + k] = (double)den;
+        ptab[PT_RDEN * AMC_MAX_MOVES + k] = (double)den;
+        ptab[PT_LOGC * AMC_MAX_MOVES + k] = log_f64(TWO_PI * (double)s2) / 2.0;
+    }
+}
+#endif
+
 // The move-pick table (see AMC_PICK_CELLS): cell c covers the pick uniforms r in [c, c+1) 2^-12 (both ends exact).
 // The walk's count #(cum[i] <= r), i < K-1, is monotone in r, so it is the same for every r of the cell iff it is the
 // same at the two ends: #(cum[i] <= c 2^-12) == #(cum[i] < (c+1) 2^-12).  Launched after prepare_params (same stream)

@@ -434,10 +434,11 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
             }
         }
     }
-    // expr_in = [ '\x02' (Float32 state) ] [ potential [ '\x01' reward ] [ '\x03' scale ] [ '\x04' sample '\x05' logq [ '\x06' dlogq ]
+    // expr_in = [ '\x02' (Float32 state) [ '\x15' (Float32 policy parameters) ] ] [ potential [ '\x01' reward ] [ '\x03' scale ] [ '\x04' sample '\x05' logq [ '\x06' dlogq ]
     //             [ '\x07' perform ] [ '\x08' invert ] ] ]
     const bool f32 = !expr_in.empty() && expr_in[0] == '\x02';
-    const std::string expr_full = expr_in.substr(f32 ? 1 : 0);
+    const bool param_f32 = f32 && expr_in.size() > 1 && expr_in[1] == '\x15';      // [ '\x15' (Float32 policy parameters) ] behind '\x02' only
+    const std::string expr_full = expr_in.substr((f32 ? 1 : 0) + (param_f32 ? 1 : 0));
     std::string expr = expr_full;
     std::string src;
     // a template instantiation is all this translation unit is asked for: the headers' plain kernels (initial ensemble, parameter
@@ -445,6 +446,7 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
     // built at run time, for Float32 state, are asked for by name: those builds keep them.)
     if (inst.find('<') != std::string::npos) src += "#define AMC_PLAIN_KERNELS 0\n";
     if (f32) src += "#define AMC_STATE_F32 1\n";
+    if (param_f32) src += "#define AMC_PARAM_F32 1\n";
     if (knobs.no_sigma_memo) src += "#define AMC_NO_SIGMA_MEMO 1\n";      // A/B: amc_log(sigma) per lane and step in K > 1 sweeps (amc_model.h SigmaArg)
     if (knobs.rtc_waves_set) src += "#define AMC_RTC_WAVES " + std::to_string(std::atoi(knobs.rtc_waves.c_str())) + "\n";       // A/B: amdgpu_waves_per_eu of the script-defined estimator forms
     auto cut_tail = [&](char mark) -> std::string {      // removes and returns what follows the LAST section mark

@@ -104,10 +104,11 @@ __device__ __forceinline__ void store_log_pair(const SweepArgs& a, int row, int6
 template <int POT, bool MULTI, int LOG, bool SINGLE, bool PRE = false>
 __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t b0, real_t b1, uint64_t pair,
                                            int64_t p, bool v0, bool v1, const double* s_tab, const uint8_t* s_pick,
-                                           const double* s_math, double sigma1, double den1, double rden1, double logc1,
+                                           const double* s_math, param_t sigma1, param_t den1, double rden1, double logc1,
                                            unsigned long long& wave_acc, uint32_t& log_word,
                                            const StepDraws* pre = nullptr, const MathK& mk = math_k_literal(),
-                                           const UserTheta& th1 = UserTheta{0.0, 0.0, 0.0, 0.0, 0.0, 0.0})
+                                           const UserTheta& th1 = UserTheta{0.0, 0.0, 0.0, 0.0, 0.0, 0.0},
+                                           const float2* s_mathf = nullptr)      // AMC_PARAM_F32: the Float32 tables (box_muller_f32)
 {
     static_assert(!PRE || SINGLE, "pre-formed draws cover exactly one step");
     const int K = a.n_moves;
@@ -118,7 +119,7 @@ __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t
         const uint64_t t = a.t0 + (uint64_t)s;
         const StepDraws dr = PRE ? *pre : step_draws(a, pair, t);
         const u32x4 accept_ctr = draw_counter(pair, t, DRAW_ACCEPT, STREAM_METROPOLIS);
-        double sg0 = sigma1, sg1 = sigma1;
+        param_t sg0 = sigma1, sg1 = sigma1;
         int k0 = 0, k1 = 0;
         u32x4 pu = {0u, 0u, 0u, 0u};
         bool have_pu = false;                        // wave-uniform
@@ -136,11 +137,22 @@ __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t
                 k0 = categorical_walk(s_tab, K, uniform_pick(q0, pu.x));
                 k1 = categorical_walk(s_tab, K, uniform_pick(q1, pu.z));
             }
+#ifdef AMC_PARAM_F32
+            sg0 = reinterpret_cast<const float*>(s_tab)[k0];       // row 0 holds Float32 pairs in this form (sweep_kernel)
+            sg1 = reinterpret_cast<const float*>(s_tab)[k1];
+#else
             sg0 = s_tab[k0];
             sg1 = s_tab[k1];
+#endif
         }
-        double z0, z1;
+        param_t z0, z1;
+#ifdef AMC_PARAM_F32
+        (void)mk;
+        box_muller_f32(dr.normal, z0, z1, s_mathf);
+#else
+        (void)s_mathf;
         box_muller(dr.normal, z0, z1, s_math, mk);
+#endif
         unsigned long long m0, m1m;
         uint32_t acc_bits;
         mh_pair<POT, MULTI>(xv, b0, b1, sg0, sg1, k0, k1, s_tab, m1, z0, z1, dr.normal, pu, have_pu, accept_ctr, a.key0,
@@ -179,11 +191,24 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     __shared__ double s_tab[MULTI ? (5 + AMC_SIGMA_MEMO) * AMC_MAX_MOVES : 1];
     __shared__ __attribute__((aligned(16))) uint8_t s_pick[MULTI ? AMC_PICK_CELLS : 16];
     __shared__ double s_math[TAB_DOUBLES];        // exp / log / sincospi tables, 4.4 KB
+#ifdef AMC_PARAM_F32
+    __shared__ float2 s_mathf_store[TABF_PAIRS];  // the Float32 log and sincospi tables of box_muller_f32, 2 KB
+    const float2* s_mathf = s_mathf_store;
+    stage_math_tables_f32(s_mathf_store, threadIdx.x, AMC_BLOCK);      // visible after the barrier that ends stage_math_tables below
+#else
+    const float2* s_mathf = nullptr;
+#endif
     const int K = a.n_moves;
     if (MULTI) {
         stage_pick_table(s_pick, a.pick_tab);
         for (int i = threadIdx.x; i < K; i += AMC_BLOCK) {
+#ifdef AMC_PARAM_F32
+            // sigma and 2 sigma^2 are Float32 values (the table holds them exactly): the lanes read them as floats from row 0
+            reinterpret_cast<float*>(s_tab)[i] = (float)a.ptab[PT_SIGMA * AMC_MAX_MOVES + i];
+            reinterpret_cast<float*>(s_tab)[AMC_MAX_MOVES + i] = (float)a.ptab[PT_DEN * AMC_MAX_MOVES + i];
+#else
             s_tab[0 * AMC_MAX_MOVES + i] = a.ptab[PT_SIGMA * AMC_MAX_MOVES + i];
+#endif
             s_tab[1 * AMC_MAX_MOVES + i] = a.ptab[PT_DEN * AMC_MAX_MOVES + i];
             s_tab[2 * AMC_MAX_MOVES + i] = a.ptab[PT_LOGC * AMC_MAX_MOVES + i];
             s_tab[3 * AMC_MAX_MOVES + i] = a.ptab[PT_CUM * AMC_MAX_MOVES + i];
@@ -193,8 +218,8 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
         // visible to the block after the barrier that ends stage_math_tables below
     }
     // K == 1: wave-uniform scalars (s_load)
-    const double sigma1 = a.ptab[PT_SIGMA * AMC_MAX_MOVES];
-    const double den1 = a.ptab[PT_DEN * AMC_MAX_MOVES];
+    const param_t sigma1 = (param_t)a.ptab[PT_SIGMA * AMC_MAX_MOVES];      // (AMC_PARAM_F32: exact, the table holds Float32 values)
+    const param_t den1 = (param_t)a.ptab[PT_DEN * AMC_MAX_MOVES];
     const double logc1 = a.ptab[PT_LOGC * AMC_MAX_MOVES];
     const double rden1 = a.ptab[PT_RDEN * AMC_MAX_MOVES];
     UserTheta th1 = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -263,7 +288,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
         const StepDraws dr = dr_nxt;
         uint32_t lw = 0;
         pair_steps<POT, MULTI, LOG, SINGLE, AHEAD>(a, xv, b0, b1, a.pair0 + (uint64_t)p, p, true, true, s_tab, s_pick, s_math,
-                                                   sigma1, den1, rden1, logc1, wave_acc, lw, &dr, math_k_literal(), th1);
+                                                   sigma1, den1, rden1, logc1, wave_acc, lw, &dr, math_k_literal(), th1, s_mathf);
         // a successor exists (loop condition); lanes past the end of a ragged one form draws nobody uses
         if (AHEAD) dr_nxt = step_draws(a, a.pair0 + (uint64_t)(p + stride), a.t0);
         if (REDUCE) {
@@ -284,7 +309,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
         }
         uint32_t lw = 0;
         pair_steps<POT, MULTI, LOG, SINGLE, AHEAD>(a, xv, b_nxt.x, b_nxt.y, a.pair0 + (uint64_t)(v0 ? p : 0), p, v0, v1,
-                                                   s_tab, s_pick, s_math, sigma1, den1, rden1, logc1, wave_acc, lw, &dr_nxt, math_k_literal(), th1);
+                                                   s_tab, s_pick, s_math, sigma1, den1, rden1, logc1, wave_acc, lw, &dr_nxt, math_k_literal(), th1, s_mathf);
         // a lone last chain (odd n_chains) writes its whole pair (x and log): the odd slot is padding
         if (v0) {
             store_pair_block_writethrough(a.x + 2 * base, xv);

@@ -93,6 +93,18 @@ class Metropolis(AriannaAlgorithm):
         extra = {} if getattr(chains, "reward", None) is None else {"reward_expr": chains.reward}
         if getattr(chains, "dtype", "f64") != "f64":
             extra["dtype"] = chains.dtype
+        # eltype(move.parameters): one type per pool, and Float32 parameters belong to Float32 chains (under Float64 state Julia
+        # promotes sigma * z back to Float64: that model is the Float64 one, so it is not offered under a second name)
+        kinds_p = {getattr(m, "param_dtype", "f64") for m in self.pool}
+        if len(kinds_p) > 1:
+            raise ValueError("Metropolis: a pool mixes numpy.float32 and Float64 parameters; every move of a pool carries "
+                             "parameters of one type (all numpy.float32, or none)")
+        self.param_dtype = kinds_p.pop()
+        if self.param_dtype == "f32":
+            if getattr(chains, "dtype", "f64") != "f32":
+                raise ValueError("Metropolis: numpy.float32 parameters need Float32 chains (ParticleChains(..., dtype=\"f32\")); "
+                                 "a Float32 sigma on Float64 chains promotes to the Float64 arithmetic: pass Float64 parameters")
+            extra["param_dtype"] = "f32"
         n_params = 1
         kinds = [_move_signature(m) for m in self.pool]
         if len(set(kinds)) > 1:
@@ -219,7 +231,7 @@ class Metropolis(AriannaAlgorithm):
     # ---- state the dependants read (pools, parameters) ------------------------------------
     def set_parameters(self, k: int, parameters) -> None:
         """Push Move.parameters of move k to the device copy (after learning_step!, update.jl:53)."""
-        p = np.atleast_1d(np.asarray(parameters, dtype=np.float64))
+        p = np.atleast_1d(np.asarray(parameters, dtype=np.float64))      # (a Float32 value is a Float64 value; the engine checks)
         self.engine.set_parameters(k, p)
         if self.pool[k].parameters is not parameters:
             self.pool[k].parameters[...] = p

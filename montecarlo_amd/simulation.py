@@ -91,6 +91,9 @@ def _unique(vals: Iterable[int]) -> List[int]:
 def julia_repr(v) -> str:
     """string(v) as Julia prints Float64 / Vector{Float64}: shortest round-trip digits, fixed
     notation for 1e-4 <= |x| < 1e6, otherwise d.ddde±n; NaN, Inf; vectors as [a, b]."""
+    if isinstance(v, np.ndarray) and v.dtype == np.float32:
+        # Vector{Float32}: Float32[0.1, 1.0f-5] -- the shortest digits that round-trip in Float32
+        return "Float32[" + ", ".join(julia_repr(float(str(x))).replace("e", "f") for x in v) + "]"
     if isinstance(v, (list, tuple, np.ndarray)):
         return "[" + ", ".join(julia_repr(x) for x in np.asarray(v).tolist()) + "]"
     if isinstance(v, (int, np.integer)) and not isinstance(v, bool):

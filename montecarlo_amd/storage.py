@@ -146,7 +146,7 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
     data = dict(x=x, shard=np.array([start, stop]), n_chains_global=len(metropolis.chains), seed=metropolis.seed,
                 sweepstep=metropolis.sweepstep, step=eng.step, estimator_step=eng.estimator_step,
                 sigma=np.array([m.sigma for m in metropolis.pool]), weight=np.array([m.weight for m in metropolis.pool]),
-                accepted_total=acc_tot, total_total=tot_tot)
+                accepted_total=acc_tot, total_total=tot_tot, param_dtype=getattr(metropolis, "param_dtype", "f64"))
     try:
         acc, tot = eng.download_counters()
         data.update(accepted=acc, total=tot)
@@ -168,6 +168,11 @@ def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
     start, stop = metropolis.shard
     if list(d["shard"]) != [start, stop] or int(d["seed"]) != metropolis.seed or int(d["n_chains_global"]) != len(metropolis.chains):
         raise ValueError("checkpoint does not match this Metropolis (shard / seed / ensemble size)")
+    saved_pd = str(d["param_dtype"]) if "param_dtype" in d else "f64"
+    if saved_pd != getattr(metropolis, "param_dtype", "f64"):
+        raise ValueError(f"checkpoint was written with param_dtype {saved_pd!r}, this Metropolis has "
+                         f"{getattr(metropolis, 'param_dtype', 'f64')!r}: the two run different arithmetic (pass the moves' "
+                         "parameters in the checkpoint's type)")
     eng = metropolis.engine
     eng.upload_state(d["x"], d["beta"] if "beta" in d else None)
     for k, s in enumerate(d["sigma"]):

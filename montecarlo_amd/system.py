@@ -193,7 +193,9 @@ class Move:
     """Move(action, policy, parameters, weight) (src/metropolis.jl:140-162).
 
     ``parameters`` is a 1-element float array (ComponentArray(sigma=...) in the reference),
-    shared by every chain (metropolis.jl:252-260).  ``total_calls`` / ``accepted_calls`` are
+    shared by every chain (metropolis.jl:252-260).  Parameters that come as ``numpy.float32`` (an array or a scalar of that
+    dtype: ComponentArray(sigma=0.1f0)) stay Float32 -- ``param_dtype`` is then "f32" and the array keeps that dtype --, which
+    asks the engine for the all-Float32 model (Float32 chains only; every move of a pool alike).  ``total_calls`` / ``accepted_calls`` are
     pool-wide sums here; per-chain values come from ``Metropolis.download_counters``.
     """
     action: Displacement
@@ -207,7 +209,10 @@ class Move:
         p = self.parameters
         if isinstance(p, dict):
             p = [p["sigma"]]
-        self.parameters = np.atleast_1d(np.asarray(p, dtype=np.float64)).copy()
+        # eltype(move.parameters): Float32 only where the caller wrote Float32 values (Python floats and lists of them are Float64)
+        self.param_dtype = "f32" if getattr(p, "dtype", None) == np.float32 or (
+            isinstance(p, (list, tuple)) and len(p) > 0 and all(isinstance(v, np.float32) for v in p)) else "f64"
+        self.parameters = np.atleast_1d(np.asarray(p, dtype=np.float32 if self.param_dtype == "f32" else np.float64)).copy()
         n_params = int(getattr(self.policy, "n_params", 1))
         if self.parameters.shape != (n_params,):
             raise ValueError("StandardGaussian has exactly one parameter (sigma)" if n_params == 1

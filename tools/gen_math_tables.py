@@ -11,6 +11,15 @@ Writes the SAME literal values (C99 hex floats, correctly rounded from 60-digit 
                 intervals that touch 1, so log(1) = 0 exactly), INVC = 1/c rounded to 9 fractional
                 bits (exact in f64), LOGC = RN(-log INVC)
   SINPI[128], COSPI[128]         sin/cos(pi * j / 64), exact 0 / +-1 where they are exact
+
+Float32 policy parameters (box_muller_f32) read two tables of Float32 PAIRS, written to
+    montecarlo_amd/csrc/amc_tables.h      (AMC_MATH_TABLES_F32, staged into LDS per block by the forms that use it)
+    tests/aux/f32_param_tables.inc        (the host twin of the tests; it shares no header with csrc/)
+
+  LOGF[129]     (INVC, RN_f32(2 log INVC)) on the same 129 intervals: INVC has 9 fractional bits, exact in Float32;
+                (1, 0) for the two intervals that touch 1
+  SINCOSF[128]  (RN_f32 sin, RN_f32 cos)(pi * j / 64), exact 0 / +-1 where they are exact
+Every Float32 entry is rounded ONCE, from the 60-digit decimal (no detour through a double).
 """
 import os
 from decimal import Decimal, getcontext
@@ -89,6 +98,44 @@ def sincos_tables():
     return sn, cs
 
 
+def rn_f32(d):
+    """The Float32 nearest to the Decimal d (ties to even), as a C99 hex float.  |d| is 0 or a normal Float32."""
+    d = Decimal(d)
+    if d == 0:
+        return "0x0.0p+0"
+    sign, a = ("-" if d < 0 else ""), abs(d)
+    e = a.adjusted() * 4 - 8                      # a power of two safely below a ...
+    while Decimal(2) ** (e + 1) <= a:             # ... raised to floor(log2 a)
+        e += 1
+    q = int((a / Decimal(2) ** (e - 23)).to_integral_value(rounding="ROUND_HALF_EVEN"))     # 24-bit significand, 2^23 <= q <= 2^24
+    if q == 1 << 24:
+        q, e = 1 << 23, e + 1
+    assert (1 << 23) <= q < (1 << 24) and -126 <= e <= 127
+    return f"{sign}0x1.{(q - (1 << 23)) << 1:06x}p{e:+d}"
+
+
+def f32_tables():
+    """LOGF and SINCOSF as flat lists of pairs (see the module's head)."""
+    logf, scf = [], []
+    invc, _ = log_tables()
+    for h in invc:
+        q = Decimal(float.fromhex(h))             # 9 fractional bits: exact
+        logf += [rn_f32(q), rn_f32(2 * q.ln()) if q != 1 else "0x0.0p+0"]
+    for j in range(128):
+        q, r = divmod(j, 32)
+        if r == 0:
+            s0, c0 = Decimal(0), Decimal(1)
+        elif r == 16:
+            s0 = c0 = Decimal(0.5).sqrt()
+        elif r < 16:
+            s0, c0 = dsin(PI * r / 64), dcos(PI * r / 64)
+        else:
+            s0, c0 = dcos(PI * (32 - r) / 64), dsin(PI * (32 - r) / 64)
+        s, c = [(s0, c0), (c0, -s0), (-s0, -c0), (-c0, s0)][q]
+        scf += [rn_f32(s), rn_f32(c)]
+    return logf, scf
+
+
 def emit(name, vals, per_line=4):
     out = [f"static const double {name}[{len(vals)}] = {{"]
     for i in range(0, len(vals), per_line):
@@ -110,17 +157,29 @@ def main():
         f.write(head + "#define AMC_TAB_LOG_IDX_MIN 53\n" + body + "\n")
     allv = e2 + invc + logc + sn + cs
     dev = emit("AMC_MATH_TABLES", allv).replace("static const double", "__device__ const double")
+    logf, scf = f32_tables()
+    assert len(logf) == 258 and len(scf) == 256
+    suffix = lambda vals: [v + "f" for v in vals]
+    devf = emit("AMC_MATH_TABLES_F32", suffix(logf + scf)).replace("static const double", "__device__ const float")
+    with open(os.path.join(ROOT, "tests", "aux", "f32_param_tables.inc"), "w") as f:
+        f.write("/* GENERATED by tools/gen_math_tables.py -- do not edit.  Float32 tables of box_muller_f32 (DESIGN.md section 3.12):\n"
+                " * pairs (INVC, 2 log INVC) and (sin, cos)(pi j / 64), the literals the HIP kernels carry. */\n"
+                "#define TWIN_LOG_IDX_MIN 53\n" + emit("TWIN_LOGF", suffix(logf)).replace("const double", "const float") + "\n" +
+                emit("TWIN_SINCOSF", suffix(scf)).replace("const double", "const float") + "\n")
     with open(os.path.join(ROOT, "montecarlo_amd", "csrc", "amc_tables.h"), "w") as f:
         f.write(head + "#pragma once\n#ifndef __HIPCC_RTC__   /* hiprtc (custom potentials) predefines the device API */\n#include <hip/hip_runtime.h>\n#endif\nnamespace amc {\n"
                 "// one array: EXP2[32] | LOG_INVC[129] | LOG_LOGC[129] | SINPI[128] | COSPI[128]; the log tables are\n"
                 "// indexed by idx - TAB_LOG_IDX_MIN (only idx in [53, 181] can occur)\n"
                 "enum { TAB_EXP2 = 0, TAB_LOG_INVC = 32, TAB_LOG_LOGC = 161, TAB_SINPI = 290, TAB_COSPI = 418,\n"
-                "       TAB_DOUBLES = 546, TAB_LOG_IDX_MIN = 53 };\n" + dev + "\n}  // namespace amc\n")
+                "       TAB_DOUBLES = 546, TAB_LOG_IDX_MIN = 53 };\n" + dev + "\n"
+                "// Float32 policy parameters (box_muller_f32): pairs -- LOGF[129] (INVC, 2 log INVC), same index as above;\n"
+                "// SINCOSF[128] (sin, cos)(pi j / 64).  TABF_* count PAIRS.\n"
+                "enum { TABF_LOG = 0, TABF_SINCOS = 129, TABF_PAIRS = 257 };\n" + devf + "\n}  // namespace amc\n")
     def jl(name, vals):
         dec = [repr(float.fromhex(v)) for v in vals]        # shortest round-trip decimals: exact when parsed
         return f"const {name} = Float64[\n    " + ",\n    ".join(", ".join(dec[i:i + 4]) for i in range(0, len(dec), 4)) + "]\n"
-    os.makedirs(os.path.join(ROOT, "julia"), exist_ok=True)
-    with open(os.path.join(ROOT, "julia", "amc_tables.jl"), "w") as f:
+    os.makedirs(os.path.join(ROOT, "julia", "src"), exist_ok=True)
+    with open(os.path.join(ROOT, "julia", "src", "amc_tables.jl"), "w") as f:
         f.write("# GENERATED by tools/gen_math_tables.py -- do not edit.  Same literals as oracle/amc_tables.inc.\n"
                 "const AMC_TAB_LOG_IDX_MIN = 53\n" + jl("AMC_TAB_LOG_INVC", invc) + jl("AMC_TAB_LOG_LOGC", logc) +
                 jl("AMC_TAB_SINPI", sn) + jl("AMC_TAB_COSPI", cs))

@@ -3,6 +3,9 @@
 
   tools/gpu_ab.py snapshot NAME      copy the built package to tools/_variants/NAME (run on the build host)
   tools/gpu_ab.py run [ROUNDS]       time every variant, interleaved, ROUNDS times (run on the GPU box)
+  tools/gpu_ab.py forms [ROUNDS]     the single-sweep launch (tools/gpu_workload.py ladder, 1e7 chains) of every variant in the forms it
+                                     has -- f64, Float32 state, and Float32 state + Float32 parameters where the variant knows
+                                     param_dtype --, interleaved, ROUNDS times; medians, minima and spreads per (variant, form)
 Devices of one type differ by several percent on VALU-bound kernels, so variants are only comparable inside one call.
 """
 import os, shutil, subprocess, sys
@@ -41,6 +44,28 @@ if sys.argv[1] == "snapshot":
     shutil.copytree(os.path.join(ROOT, "montecarlo_amd"), os.path.join(dst, "montecarlo_amd"),
                     ignore=shutil.ignore_patterns("__pycache__", "csrc"))
     print("snapshot ->", dst)
+elif sys.argv[1] == "forms":
+    import re, statistics
+    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    names = sorted(os.listdir(VAR))
+    forms = [("f64", {}), ("f32_state", {"DTYPE": "f32"}), ("f32_param", {"DTYPE": "f32", "PARAM_DTYPE": "f32"})]
+    res = {}
+    for _ in range(rounds):
+        for n in names:
+            has_param = "param_dtype" in open(os.path.join(VAR, n, "montecarlo_amd", "_capi.py")).read()
+            for form, env in forms:
+                if form == "f32_param" and not has_param:
+                    continue
+                out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gpu_workload.py"), "ladder", "10000000"], capture_output=True, text=True,
+                                     env={**os.environ, **env, "AMC_PKG_ROOT": os.path.join(VAR, n)}, timeout=300)
+                m = re.search(r": ([0-9.]+) us per launch", out.stdout)
+                if out.returncode != 0 or not m:
+                    sys.exit(f"{n} {form}: exit {out.returncode}: {out.stderr.strip()[-300:]}")      # nothing more is started after a failure
+                res.setdefault((n, form), []).append(float(m.group(1)))
+    print("us per single-sweep launch at 1e7 chains (harmonic, K = 1, pool-wide counter), wall clock per launch of 300, second of two passes; "
+          f"{rounds} interleaved rounds")
+    for (n, form), v in res.items():
+        print(f"{n:12s} {form:10s} median {statistics.median(v):6.2f}  min {min(v):6.2f}  max {max(v):6.2f}  spread {max(v) - min(v):5.2f}   all " + " ".join(f"{x:.2f}" for x in v), flush=True)
 else:
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     names = sorted(os.listdir(VAR))

@@ -8,6 +8,7 @@
   vec / vec1 / mixed   PGMC time steps of a two-parameter policy, its one-parameter script twin, a pool of two policy classes
   pgmc7        the pool of the reference's test/pgmc_test.jl:16-27 at 1e7 chains: K = 7 Gaussian displacements, six of them learnable, one
                optimiser each (VPG .. BLANPG), q_batch_size = 10 (QBATCH), sweep + estimator + learning step per time step
+               DTYPE=f32: Float32 state (the f32_state workload of bench.py); with PARAM_DTYPE=f32 the all-Float32 model (sigma = 0.1f0)
 Environment: LAUNCHES, PIPELINED, PRECOUNT, COLS (which sums the callbacks ask for), COMM=1 (pgmc: connect a one-rank communicator).
 """
 import os, sys, time
@@ -49,7 +50,14 @@ def spin(e, seconds=0.5):
 
 if mode == "ladder":
     M = int(sys.argv[2])
-    e = A.HipEngine(n_chains=M, potential="harmonic", beta=2.0, sigma=[0.1], weight=[1.0], seed=1, per_chain_counters=False)
+    dt, pdt = os.environ.get("DTYPE", "f64"), os.environ.get("PARAM_DTYPE", "f64")
+    kw = {}
+    if dt != "f64":
+        kw["dtype"] = dt
+    if pdt != "f64":
+        import numpy as np
+        kw.update(param_dtype=pdt, sigma=[float(np.float32(0.1))])
+    e = A.HipEngine(**{**dict(n_chains=M, potential="harmonic", beta=2.0, sigma=[0.1], weight=[1.0], seed=1, per_chain_counters=False), **kw})
     e.init_uniform(-2, 2)
     spin(e)
     n = max(20, min(n, int(3_000_000_000 // M)))
@@ -58,7 +66,7 @@ if mode == "ladder":
         for _ in range(n):
             e.sweep(1)
         us = e.timing_end() * 1e3 / n
-    print(f"ladder M={M}: {us:.2f} us per launch, {16 * M / us / 1e3:.1f} GB/s")
+    print(f"ladder M={M} state {dt} parameters {pdt}: {us:.2f} us per launch, {(16 if dt == 'f64' else 8) * M / us / 1e3:.1f} GB/s")
 elif mode == "k2":
     M = 10_000_000
     e = A.HipEngine(n_chains=M, potential="double_well", beta=2.0, sigma=[0.1, 1.0], weight=[0.5, 0.5], seed=1)
