@@ -49,7 +49,7 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
     if (REDUCE && SWEEP == 3 && threadIdx.x == 0)
         for (int sl = (int)blockIdx.x; sl < sw.n_slots; sl += (int)gridDim.x) slots_before += sw.acc_total[sl];
     __shared__ double s_math[TAB_DOUBLES];
-    __shared__ double s_tab[SWEEP == 2 ? (5 + AMC_SIGMA_MEMO) * AMC_MAX_MOVES : 1];
+    __shared__ double s_tab[SWEEP == 2 ? MT_ROWS * AMC_MAX_MOVES : 1];
     __shared__ __attribute__((aligned(16))) uint8_t s_pick[SWEEP == 2 ? AMC_PICK_CELLS : 16];
     // the GradientData fold: wave slots of the columns' integer totals
     __shared__ QSlot s_gq[AMC_BLOCK / 64][QK ? NV : 1];
@@ -57,12 +57,13 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
     if (SWEEP == 2) {
         stage_pick_table(s_pick, sw.pick_tab);
         for (int i = threadIdx.x; i < sw.n_moves; i += AMC_BLOCK) {
-            s_tab[0 * AMC_MAX_MOVES + i] = sw.ptab[PT_SIGMA * AMC_MAX_MOVES + i];
-            s_tab[1 * AMC_MAX_MOVES + i] = sw.ptab[PT_DEN * AMC_MAX_MOVES + i];
-            s_tab[2 * AMC_MAX_MOVES + i] = sw.ptab[PT_LOGC * AMC_MAX_MOVES + i];
-            s_tab[3 * AMC_MAX_MOVES + i] = sw.ptab[PT_CUM * AMC_MAX_MOVES + i];
-            s_tab[4 * AMC_MAX_MOVES + i] = sw.ptab[PT_RDEN * AMC_MAX_MOVES + i];
-            if (AMC_SIGMA_MEMO) s_tab[(AMC_SIGMA_MEMO ? 5 : 0) * AMC_MAX_MOVES + i] = log_f64(sw.ptab[PT_SIGMA * AMC_MAX_MOVES + i]);      // (SigmaArg)
+            mt_set_sigma(s_tab, i, sw.ptab[PT_SIGMA * AMC_MAX_MOVES + i]);
+            mt_set_den_f32(s_tab, i, sw.ptab[PT_DEN * AMC_MAX_MOVES + i]);       // (AMC_PARAM_F32: the Float32 copy, beside the row below)
+            s_tab[MT_DEN * AMC_MAX_MOVES + i] = sw.ptab[PT_DEN * AMC_MAX_MOVES + i];
+            s_tab[MT_LOGC * AMC_MAX_MOVES + i] = sw.ptab[PT_LOGC * AMC_MAX_MOVES + i];
+            s_tab[MT_CUM * AMC_MAX_MOVES + i] = sw.ptab[PT_CUM * AMC_MAX_MOVES + i];
+            s_tab[MT_RDEN * AMC_MAX_MOVES + i] = sw.ptab[PT_RDEN * AMC_MAX_MOVES + i];
+            if (AMC_SIGMA_MEMO) mt_set_log_sigma(s_tab, i, log_f64(sw.ptab[PT_SIGMA * AMC_MAX_MOVES + i]));      // (SigmaArg)
         }
     }
     double sw_sigma1 = SWEEP ? sw.ptab[PT_SIGMA * AMC_MAX_MOVES] : 0.0;
@@ -82,8 +83,9 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
 #endif
     // a learning step the previous launch left pending (pg_apply_pending): wave-uniform
     constexpr bool CAN_DEFER = QK && NL <= 2 && AMC_NP == 1;
-    // the pending branch below rewrites the learnable moves' rows 0, 1, 2, 4 of s_tab from sigma', NOT row 5 (the memoised
-    // log(sigma_k) of script-defined proposals): forms with the memo are kind R and never defer -- keep it that way, or add the row
+    // the pending branch below rewrites the learnable moves' rows MT_SIGMA, MT_DEN, MT_LOGC, MT_RDEN of s_tab from sigma',
+    // NOT MT_LOG_SIGMA (the memoised log(sigma_k) of script-defined proposals): forms with the memo are kind R and
+    // never defer -- keep it that way, or add the row
     static_assert(!(CAN_DEFER && AMC_SIGMA_MEMO), "a deferred learning step would leave the memoised log(sigma) one step behind");
     const int pending = CAN_DEFER ? pg_pending_of(a.tail_mode) : 0;
     __shared__ double s_pend_val[CAN_DEFER ? NL * 4 : 1];
@@ -104,10 +106,11 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
             for (int l = 0; l < NL; ++l)                  // the pool's table in LDS: the learnable moves' rows from sigma'
                 if (l < a.n_learn) {                      // (constant indices into the kernel argument: no private copy of it)
                     const int k = a.learn_ids[l];
-                    s_tab[0 * AMC_MAX_MOVES + k] = s_def[CAN_DEFER ? l : 0][DEF_SIGMA];
-                    s_tab[1 * AMC_MAX_MOVES + k] = s_def[CAN_DEFER ? l : 0][DEF_DEN];
-                    s_tab[2 * AMC_MAX_MOVES + k] = s_def[CAN_DEFER ? l : 0][DEF_LOGC];
-                    s_tab[4 * AMC_MAX_MOVES + k] = s_def[CAN_DEFER ? l : 0][DEF_RDEN];
+                    mt_set_sigma(s_tab, k, s_def[CAN_DEFER ? l : 0][DEF_SIGMA]);
+                    mt_set_den_f32(s_tab, k, s_def[CAN_DEFER ? l : 0][DEF_DEN]);
+                    s_tab[MT_DEN * AMC_MAX_MOVES + k] = s_def[CAN_DEFER ? l : 0][DEF_DEN];
+                    s_tab[MT_LOGC * AMC_MAX_MOVES + k] = s_def[CAN_DEFER ? l : 0][DEF_LOGC];
+                    s_tab[MT_RDEN * AMC_MAX_MOVES + k] = s_def[CAN_DEFER ? l : 0][DEF_RDEN];
                 }
         }
     }
@@ -119,8 +122,9 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
     auto mh = [&](real2& xv, real_t b0, real_t b1, uint64_t pair, int64_t p, bool v0, bool v1) {
         uint32_t lw = 0;
         // SWEEP == 3: K == 1 with the pool-wide counter only -- no step log
-        pair_steps<POT, SWEEP == 2, (SWEEP != 3 ? AMC_LOG_PACKED : AMC_LOG_NONE), true>(sw, xv, b0, b1, pair, p, v0, v1, s_tab, s_pick, s_math, sw_sigma1, sw_den1,
-                                                      sw_rden1, sw_logc1, wave_acc, lw, nullptr, mk, sw_th1);
+        // (no draws formed ahead; no Float32 tables: the host refuses Float32 parameters here)
+        pair_steps<POT, SWEEP == 2, (SWEEP != 3 ? AMC_LOG_PACKED : AMC_LOG_NONE), true, false>(
+            sw, xv, b0, b1, pair, p, v0, v1, s_tab, s_pick, s_math, sw_sigma1, sw_den1, sw_rden1, sw_logc1, wave_acc, lw, nullptr, mk, sw_th1, nullptr);
         if (SWEEP != 3 && v0) store_log_pair<AMC_LOG_PACKED>(sw, sw.log_pos, p, lw);
     };
     const int64_t n_pairs = (a.n_chains + 1) >> 1;

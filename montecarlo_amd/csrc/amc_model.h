@@ -1,6 +1,7 @@
-// amc_model.h -- the model on the path: configuration of a translation unit (state type, policy parameters, classes), the script-defined
-// hooks (potential, reward, proposal, action), potential / proposal / acceptance of the built-in Gaussian displacement, the accept
-// filter, one mc_step! of a chain pair (mh_pair) and the 16-byte loads / write-through stores of a pair.
+// amc_model.h -- the model on the path: configuration of a translation unit (state type, policy parameters, classes), the rows of the
+// parameter table (PT_*) and of its LDS copy in a K > 1 sweep (MT_*, with the accessors of the rows that are no plain doubles), the
+// script-defined hooks (potential, reward, proposal, action), potential / proposal / acceptance of the built-in Gaussian displacement,
+// the accept filter, one mc_step! of a chain pair (mh_pair) and the 16-byte loads / write-through stores of a pair.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
 #pragma once
 
@@ -163,7 +164,7 @@ __device__ __forceinline__ double user_scale(real_t x, const double* amc_tables_
 // perform_action_cached! (the revert) re-applies the inverted action, as the reference does (metropolis.jl:119,187).
 // `sigma` as the expressions see it in a K > 1 sweep: the lane's sigma with log(sigma) beside it.  There the lanes of a wave hold
 // different moves, so no function of sigma alone leaves the loop the way it does where the move is wave-uniform -- but sigma takes
-// only K values: the block forms amc_log(sigma_k) once per launch (row 5 of the sweep's LDS table, the same log_f64 on the same
+// only K values: the block forms amc_log(sigma_k) once per launch (row MT_LOG_SIGMA of the sweep's LDS table, the same log_f64 on the same
 // operand: the same bits) and `amc_log(sigma)` in an expression -- the Langevin proposal's normalisation, say -- reads it instead of
 // spending fifty vector instructions per lane and step.  Everywhere else SigmaArg is a double: it converts, and only this one call
 // knows it.  AMC_SIGMA_MEMO: the row exists (script-defined proposals; AMC_NO_SIGMA_MEMO, set by the run-time compiler for A/B, drops it).
@@ -177,6 +178,52 @@ struct SigmaArg {
     __device__ __forceinline__ operator double() const { return v; }
 };
 __device__ __forceinline__ double log_f64(const SigmaArg& s) { return s.logv; }
+
+// Rows of the LDS copy of the parameter table that a K > 1 sweep keeps per block (s_tab[MT_ROWS * AMC_MAX_MOVES], staged by
+// sweep_kernel and by the fused pg_estimate_kernel): what the lanes read by their move index.  A row is AMC_MAX_MOVES doubles,
+// s_tab[MT_x * AMC_MAX_MOVES + k], with two exceptions that go through the accessors below.  Under AMC_PARAM_F32 the row
+// MT_SIGMA holds two Float32 half-rows, sigma in [0, 64) and 2 sigma^2 in [64, 128) (the table holds Float32 values exactly;
+// the row MT_DEN keeps the Float64 copy).  And the memoised log(sigma) is a row of its own with AMC_SIGMA_MEMO only: without
+// the memo MT_LOG_SIGMA is another name of MT_SIGMA, so that code nobody runs then still indexes inside the table.
+enum { MT_SIGMA = 0, MT_DEN = 1, MT_LOGC = 2, MT_CUM = 3, MT_RDEN = 4, MT_LOG_SIGMA = AMC_SIGMA_MEMO ? 5 : MT_SIGMA,
+       MT_ROWS = 5 + AMC_SIGMA_MEMO };
+__device__ __forceinline__ param_t mt_sigma(const double* s_tab, int k)
+{
+#ifdef AMC_PARAM_F32
+    return reinterpret_cast<const float*>(s_tab)[k];
+#else
+    return s_tab[MT_SIGMA * AMC_MAX_MOVES + k];
+#endif
+}
+__device__ __forceinline__ param_t mt_den(const double* s_tab, int k)
+{
+#ifdef AMC_PARAM_F32
+    return reinterpret_cast<const float*>(s_tab)[AMC_MAX_MOVES + k];
+#else
+    return s_tab[MT_DEN * AMC_MAX_MOVES + k];
+#endif
+}
+__device__ __forceinline__ void mt_set_sigma(double* s_tab, int k, double sigma)
+{
+#ifdef AMC_PARAM_F32
+    reinterpret_cast<float*>(s_tab)[k] = (float)sigma;
+#else
+    s_tab[MT_SIGMA * AMC_MAX_MOVES + k] = sigma;
+#endif
+}
+// AMC_PARAM_F32: the Float32 copy of 2 sigma^2 beside sigma, nothing otherwise; the caller writes the row MT_DEN itself, next to it
+// (a setter that wrote both moved a spill in the fused estimator forms held to 96 VGPRs: profiles/sweep_refactor_isa.md)
+__device__ __forceinline__ void mt_set_den_f32(double* s_tab, int k, double den)
+{
+#ifdef AMC_PARAM_F32
+    reinterpret_cast<float*>(s_tab)[AMC_MAX_MOVES + k] = (float)den;
+#else
+    (void)s_tab; (void)k; (void)den;
+#endif
+}
+// the memoised log(sigma_k) (AMC_SIGMA_MEMO; nobody calls these without it)
+__device__ __forceinline__ double mt_log_sigma(const double* s_tab, int k) { return s_tab[MT_LOG_SIGMA * AMC_MAX_MOVES + k]; }
+__device__ __forceinline__ void mt_set_log_sigma(double* s_tab, int k, double v) { s_tab[MT_LOG_SIGMA * AMC_MAX_MOVES + k] = v; }
 }  // namespace amc
 #include "amc_dual.h"          // forward-mode differentiation of script-defined densities (dual numbers over the same vocabulary)
 namespace amc {
@@ -658,14 +705,14 @@ struct GaussRow {
     double den, logc;
 };
 __device__ __forceinline__ GaussRow gauss_row_off() { return GaussRow{false, 0.0, 0.0}; }
-// k: the move key (move | class << 8); s_tab: the sweep's LDS copy of the parameter table (rows sigma, den, logc, cum, rden)
+// k: the move key (move | class << 8); s_tab: the sweep's LDS copy of the parameter table (MT_*)
 __device__ __forceinline__ GaussRow gauss_row_of(int k, const double* s_tab)
 {
 #if AMC_NCLASS > 1 && defined(AMC_CLASS_GAUSS_MASK)
     GaussRow g;
     g.on = (((unsigned)AMC_CLASS_GAUSS_MASK >> (k >> 8)) & 1u) != 0u;
-    g.den = s_tab[1 * AMC_MAX_MOVES + (k & 0xFF)];
-    g.logc = s_tab[2 * AMC_MAX_MOVES + (k & 0xFF)];
+    g.den = s_tab[MT_DEN * AMC_MAX_MOVES + (k & 0xFF)];
+    g.logc = s_tab[MT_LOGC * AMC_MAX_MOVES + (k & 0xFF)];
     return g;
 #else
     (void)k; (void)s_tab;
@@ -725,7 +772,7 @@ __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t
         const int mk0 = user_move_key(MULTI ? k0 : 0), mk1 = user_move_key(MULTI ? k1 : 0);
         ScriptStep s0, s1;
         if (MULTI && AMC_SIGMA_MEMO) {          // the lane's sigma with its log from the block's table (SigmaArg)
-            const SigmaArg a0 = {sg0, s_tab[(AMC_SIGMA_MEMO ? 5 : 0) * AMC_MAX_MOVES + (MULTI ? k0 : 0)]}, a1 = {sg1, s_tab[(AMC_SIGMA_MEMO ? 5 : 0) * AMC_MAX_MOVES + (MULTI ? k1 : 0)]};
+            const SigmaArg a0 = {sg0, mt_log_sigma(s_tab, MULTI ? k0 : 0)}, a1 = {sg1, mt_log_sigma(s_tab, MULTI ? k1 : 0)};
             s0 = mh_script<POT>(xv.x, b0, a0, z0, T, mk0, user_theta_lds(mk0), gauss_row_of(mk0, s_tab));
             s1 = mh_script<POT>(xv.y, b1, a1, z1, T, mk1, user_theta_lds(mk1), gauss_row_of(mk1, s_tab));
         } else {
@@ -774,14 +821,9 @@ __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t
         }
         MoveExact e0 = m1, e1 = m1;
         if (MULTI) {
-#ifdef AMC_PARAM_F32
-            // row 0 of the table holds Float32 pairs in this form: sigma [0, 64), 2 sigma^2 [64, 128) (sweep_kernel)
-            e0.dn = reinterpret_cast<const float*>(s_tab)[AMC_MAX_MOVES + k0]; e0.lc = s_tab[2 * AMC_MAX_MOVES + k0];
-            e1.dn = reinterpret_cast<const float*>(s_tab)[AMC_MAX_MOVES + k1]; e1.lc = s_tab[2 * AMC_MAX_MOVES + k1];
-#else
-            e0.dn = s_tab[AMC_MAX_MOVES + k0]; e0.lc = s_tab[2 * AMC_MAX_MOVES + k0]; e0.rd = s_tab[4 * AMC_MAX_MOVES + k0];
-            e1.dn = s_tab[AMC_MAX_MOVES + k1]; e1.lc = s_tab[2 * AMC_MAX_MOVES + k1]; e1.rd = s_tab[4 * AMC_MAX_MOVES + k1];
-#endif
+            // (rd: nobody reads it under AMC_PARAM_F32, whose Float32 quotient is an IEEE division -- accept_exact)
+            e0.dn = mt_den(s_tab, k0); e0.lc = s_tab[MT_LOGC * AMC_MAX_MOVES + k0]; e0.rd = s_tab[MT_RDEN * AMC_MAX_MOVES + k0];
+            e1.dn = mt_den(s_tab, k1); e1.lc = s_tab[MT_LOGC * AMC_MAX_MOVES + k1]; e1.rd = s_tab[MT_RDEN * AMC_MAX_MOVES + k1];
         }
         const bool a0 = accept_exact(p0.delta, p0.dlogp, e0.dn, e0.rd, e0.lc, uniform_accept(a0_12, pu.x, pu.y), T);
         const bool a1 = accept_exact(p1.delta, p1.dlogp, e1.dn, e1.rd, e1.lc, uniform_accept(a1_12, pu.z, pu.w), T);

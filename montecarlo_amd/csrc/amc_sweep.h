@@ -1,5 +1,6 @@
-// amc_sweep.h -- K1, the sweep (make_step!(::Metropolis)): launch arguments, the draws of a step, the move pick, pair_steps, sweep_kernel,
-// and the fold of the step log into the per-chain counters (fold_log_kernel).
+// amc_sweep.h -- K1, the sweep (make_step!(::Metropolis)): launch arguments, the draws of a step, the staging of the block's pick
+// table, the move pick, the step log's stores, pair_steps, sweep_kernel, and the fold of the step log into the per-chain counters
+// (fold_log_kernel).
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
 #pragma once
 
@@ -64,7 +65,7 @@ __device__ __forceinline__ void stage_pick_table(uint8_t* lds, const uint8_t* ta
 __device__ __forceinline__ int categorical_walk(const double* s_tab, int K, double r)
 {
     int k = 0;
-    for (int i = 0; i < K - 1; ++i) k += (s_tab[3 * AMC_MAX_MOVES + i] <= r) ? 1 : 0;     // cp = w1; while cp <= r && i < K: cp += w[i+1]
+    for (int i = 0; i < K - 1; ++i) k += (s_tab[MT_CUM * AMC_MAX_MOVES + i] <= r) ? 1 : 0;     // cp = w1; while cp <= r && i < K: cp += w[i+1]
     return k;
 }
 
@@ -98,17 +99,16 @@ __device__ __forceinline__ void store_log_pair(const SweepArgs& a, int row, int6
 }
 
 // `n_steps` fused MH steps of one chain pair held in registers (the body of mc_sweep!, metropolis.jl:205-210).
-// PRE: the draws of the (single) step were formed ahead by the caller and come in `pre`.
+// PRE: the draws of the (single) step were formed ahead by the caller and come in `pre` (nullptr otherwise).
 // LOG: the step-log word of the pair; SINGLE launches hand it back in `log_word` (the caller stores it together
 // with x), multi-step launches store one word per step right away.
-template <int POT, bool MULTI, int LOG, bool SINGLE, bool PRE = false>
+template <int POT, bool MULTI, int LOG, bool SINGLE, bool PRE>
 __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t b0, real_t b1, uint64_t pair,
                                            int64_t p, bool v0, bool v1, const double* s_tab, const uint8_t* s_pick,
                                            const double* s_math, param_t sigma1, param_t den1, double rden1, double logc1,
                                            unsigned long long& wave_acc, uint32_t& log_word,
-                                           const StepDraws* pre = nullptr, const MathK& mk = math_k_literal(),
-                                           const UserTheta& th1 = UserTheta{0.0, 0.0, 0.0, 0.0, 0.0, 0.0},
-                                           const float2* s_mathf = nullptr)      // AMC_PARAM_F32: the Float32 tables (box_muller_f32)
+                                           const StepDraws* pre, const MathK& mk, const UserTheta& th1,
+                                           const float2* s_mathf)      // AMC_PARAM_F32: the Float32 tables (box_muller_f32), else nullptr
 {
     static_assert(!PRE || SINGLE, "pre-formed draws cover exactly one step");
     const int K = a.n_moves;
@@ -137,13 +137,8 @@ __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t
                 k0 = categorical_walk(s_tab, K, uniform_pick(q0, pu.x));
                 k1 = categorical_walk(s_tab, K, uniform_pick(q1, pu.z));
             }
-#ifdef AMC_PARAM_F32
-            sg0 = reinterpret_cast<const float*>(s_tab)[k0];       // row 0 holds Float32 pairs in this form (sweep_kernel)
-            sg1 = reinterpret_cast<const float*>(s_tab)[k1];
-#else
-            sg0 = s_tab[k0];
-            sg1 = s_tab[k1];
-#endif
+            sg0 = mt_sigma(s_tab, k0);
+            sg1 = mt_sigma(s_tab, k1);
         }
         param_t z0, z1;
 #ifdef AMC_PARAM_F32
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     RLanes<RNC> red;
     __shared__ xs::PartR s_red[REDUCE ? AMC_BLOCK / 64 : 1][RNC];
     if (REDUCE) r_init(red, s_red[threadIdx.x >> 6]);
-    __shared__ double s_tab[MULTI ? (5 + AMC_SIGMA_MEMO) * AMC_MAX_MOVES : 1];
+    __shared__ double s_tab[MULTI ? MT_ROWS * AMC_MAX_MOVES : 1];
     __shared__ __attribute__((aligned(16))) uint8_t s_pick[MULTI ? AMC_PICK_CELLS : 16];
     __shared__ double s_math[TAB_DOUBLES];        // exp / log / sincospi tables, 4.4 KB
 #ifdef AMC_PARAM_F32
@@ -202,18 +197,13 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     if (MULTI) {
         stage_pick_table(s_pick, a.pick_tab);
         for (int i = threadIdx.x; i < K; i += AMC_BLOCK) {
-#ifdef AMC_PARAM_F32
-            // sigma and 2 sigma^2 are Float32 values (the table holds them exactly): the lanes read them as floats from row 0
-            reinterpret_cast<float*>(s_tab)[i] = (float)a.ptab[PT_SIGMA * AMC_MAX_MOVES + i];
-            reinterpret_cast<float*>(s_tab)[AMC_MAX_MOVES + i] = (float)a.ptab[PT_DEN * AMC_MAX_MOVES + i];
-#else
-            s_tab[0 * AMC_MAX_MOVES + i] = a.ptab[PT_SIGMA * AMC_MAX_MOVES + i];
-#endif
-            s_tab[1 * AMC_MAX_MOVES + i] = a.ptab[PT_DEN * AMC_MAX_MOVES + i];
-            s_tab[2 * AMC_MAX_MOVES + i] = a.ptab[PT_LOGC * AMC_MAX_MOVES + i];
-            s_tab[3 * AMC_MAX_MOVES + i] = a.ptab[PT_CUM * AMC_MAX_MOVES + i];
-            s_tab[4 * AMC_MAX_MOVES + i] = a.ptab[PT_RDEN * AMC_MAX_MOVES + i];
-            if (AMC_SIGMA_MEMO) s_tab[(AMC_SIGMA_MEMO ? 5 : 0) * AMC_MAX_MOVES + i] = log_f64(a.ptab[PT_SIGMA * AMC_MAX_MOVES + i]);      // (SigmaArg)
+            mt_set_sigma(s_tab, i, a.ptab[PT_SIGMA * AMC_MAX_MOVES + i]);
+            mt_set_den_f32(s_tab, i, a.ptab[PT_DEN * AMC_MAX_MOVES + i]);       // (AMC_PARAM_F32: the Float32 copy, beside the row below)
+            s_tab[MT_DEN * AMC_MAX_MOVES + i] = a.ptab[PT_DEN * AMC_MAX_MOVES + i];
+            s_tab[MT_LOGC * AMC_MAX_MOVES + i] = a.ptab[PT_LOGC * AMC_MAX_MOVES + i];
+            s_tab[MT_CUM * AMC_MAX_MOVES + i] = a.ptab[PT_CUM * AMC_MAX_MOVES + i];
+            s_tab[MT_RDEN * AMC_MAX_MOVES + i] = a.ptab[PT_RDEN * AMC_MAX_MOVES + i];
+            if (AMC_SIGMA_MEMO) mt_set_log_sigma(s_tab, i, log_f64(a.ptab[PT_SIGMA * AMC_MAX_MOVES + i]));      // (SigmaArg)
         }
         // visible to the block after the barrier that ends stage_math_tables below
     }
