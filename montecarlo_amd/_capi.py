@@ -332,8 +332,6 @@ class HipEngine:
             arr = lambda i, need: ((C.c_char_p * n)(*[enc(c[i]) for c in cl]) if need else None)
             have_d = any(c[2] is not None for c in cl)       # a class without one has its logq differentiated by the engine (NULL entry)
             com = (C.c_int * self.n_moves)(*[int(v) for v in class_of_move])
-            if expr is None:
-                cfg.potential = POTENTIALS[potential]
             _check(lib.amc_create_mixed_model(C.byref(cfg), n, com, enc(expr), enc(reward_expr), arr(0, True), arr(1, True), arr(2, have_d),
                                               arr(3, any(c[3] is not None for c in cl)), arr(4, any(c[4] is not None for c in cl)),
                                               C.byref(self._h)))
@@ -343,8 +341,6 @@ class HipEngine:
             if scale_expr is not None:
                 raise AmcError("a script-defined proposal and a ScaledGaussian scale cannot be combined")
             sample, logq, dlogq, perform, invert = (list(proposal) + [None] * 4)[:5]
-            if expr is None:
-                cfg.potential = POTENTIALS[potential]
             if self.n_params > 1:
                 partials = None
                 if dlogq is not None:
@@ -360,19 +356,12 @@ class HipEngine:
                                                    enc(perform), enc(invert), C.byref(self._h)))
         elif scale_expr is not None:
             # script-defined policy of the Gaussian-displacement family: proposal width sigma * scale(x)
-            if expr is None:
-                cfg.potential = POTENTIALS[potential]
-            _check(lib.amc_create_policy_model(C.byref(cfg), None if expr is None else str(expr).encode(),
-                                               None if reward_expr is None else str(reward_expr).encode(),
-                                               str(scale_expr).encode(), C.byref(self._h)))
+            _check(lib.amc_create_policy_model(C.byref(cfg), enc(expr), enc(reward_expr), enc(scale_expr), C.byref(self._h)))
         elif reward_expr is not None:
             # script-defined reward(action, system) (gradients.jl:20): an expression in delta and the new position x
-            if expr is None:
-                cfg.potential = POTENTIALS[potential]
-            _check(lib.amc_create_model(C.byref(cfg), None if expr is None else str(expr).encode(),
-                                        str(reward_expr).encode(), C.byref(self._h)))
+            _check(lib.amc_create_model(C.byref(cfg), enc(expr), enc(reward_expr), C.byref(self._h)))
         elif expr is not None:
-            _check(lib.amc_create_custom(C.byref(cfg), str(expr).encode(), C.byref(self._h)))
+            _check(lib.amc_create_custom(C.byref(cfg), enc(expr), C.byref(self._h)))
         else:
             _check(lib.amc_create(C.byref(cfg), C.byref(self._h)))
 

@@ -80,71 +80,66 @@ int amc_device_count(int* count)
     return AMC_OK;
 }
 
-struct ClassExprs { const char *sample, *logq, *dlogq, *perform, *invert; };
-struct ProposalExprs { const char *sample, *logq, *dlogq, *perform, *invert; int n_params; const char* const* dlogq_more;   // dlogq_more: partials 1 .. n_params - 1
-                       int n_classes; const ClassExprs* more_classes; const int* class_of_move; };   // pools that mix policies / actions: classes 1 .. n_classes - 1
-
-// The expressions of a script-defined proposal, checked as text (validate_potential_expr: one line of ordinary expression text
-// that mentions what it must).
-static int validate_proposal_exprs(const ProposalExprs* proposal)
+// The expressions of a model's classes, checked as text (validate_potential_expr: one line of ordinary expression text that
+// mentions what it must).  The derivative of a class with one parameter must mention it where the class is the model's first --
+// sigma, or theta0, its other name --; the partials of several parameters need not mention anything.
+static int validate_classes(const ModelSpec& spec)
 {
-    int rc_p = validate_potential_expr(proposal->sample, "sample_action expression", "z");
-    if (rc_p == AMC_OK) rc_p = validate_potential_expr(proposal->logq, "log_proposal_density expression", "delta");
-    if (rc_p == AMC_OK && proposal->dlogq) {
-        rc_p = validate_potential_expr(proposal->dlogq, "d log_proposal_density / d sigma expression", proposal->n_params > 1 ? "" : "sigma");
-        if (rc_p != AMC_OK && proposal->n_params == 1 &&         // theta0 is another name of sigma
-            validate_potential_expr(proposal->dlogq, "d log_proposal_density / d sigma expression", "theta0") == AMC_OK)
-            rc_p = AMC_OK;
+    int rc = AMC_OK;
+    for (size_t c = 0; rc == AMC_OK && c < spec.classes.size(); ++c) {
+        const PolicyClass& pc = spec.classes[c];
+        rc = validate_potential_expr(pc.sample.c_str(), "sample_action expression", "z");
+        if (rc == AMC_OK) rc = validate_potential_expr(pc.logq.c_str(), "log_proposal_density expression", "delta");
+        if (rc == AMC_OK && !pc.dlogq.empty()) {
+            const char* d0 = pc.dlogq[0].c_str();
+            const bool named = c == 0 && spec.n_params == 1;
+            rc = validate_potential_expr(d0, "d log_proposal_density / d sigma expression", named ? "sigma" : "");
+            if (rc != AMC_OK && named && validate_potential_expr(d0, "d log_proposal_density / d sigma expression", "theta0") == AMC_OK) rc = AMC_OK;
+        }
+        for (size_t p = 1; rc == AMC_OK && p < pc.dlogq.size(); ++p)
+            rc = validate_potential_expr(pc.dlogq[p].c_str(), "d log_proposal_density / d theta expression", "");
+        if (rc == AMC_OK && pc.perform.empty() != pc.invert.empty())      // (the entries that take arrays have checked it, class by class)
+            rc = fail(AMC_ERR_BAD_ARG, "amc_create_action_model: perform_expr and invert_expr come together (No invert_action! is defined)");
+        if (rc == AMC_OK && !pc.perform.empty()) rc = validate_potential_expr(pc.perform.c_str(), "perform_action expression", "delta");
+        if (rc == AMC_OK && !pc.invert.empty()) rc = validate_potential_expr(pc.invert.c_str(), "invert_action expression", "delta");
     }
-    for (int pidx = 1; rc_p == AMC_OK && proposal->dlogq && pidx < proposal->n_params; ++pidx)
-        rc_p = validate_potential_expr(proposal->dlogq_more[pidx - 1], "d log_proposal_density / d theta expression", "");
-    if (rc_p == AMC_OK && (proposal->perform != nullptr) != (proposal->invert != nullptr))
-        rc_p = fail(AMC_ERR_BAD_ARG, "amc_create_action_model: perform_expr and invert_expr come together (No invert_action! is defined)");
-    if (rc_p == AMC_OK && proposal->perform) rc_p = validate_potential_expr(proposal->perform, "perform_action expression", "delta");
-    if (rc_p == AMC_OK && proposal->invert) rc_p = validate_potential_expr(proposal->invert, "invert_action expression", "delta");
-    for (int c = 1; rc_p == AMC_OK && c < proposal->n_classes; ++c) {
-        const ClassExprs& ce = proposal->more_classes[c - 1];
-        rc_p = validate_potential_expr(ce.sample, "sample_action expression", "z");
-        if (rc_p == AMC_OK) rc_p = validate_potential_expr(ce.logq, "log_proposal_density expression", "delta");
-        if (rc_p == AMC_OK && ce.dlogq) rc_p = validate_potential_expr(ce.dlogq, "d log_proposal_density / d sigma expression", "");
-        if (rc_p == AMC_OK && ce.perform) rc_p = validate_potential_expr(ce.perform, "perform_action expression", "delta");
-        if (rc_p == AMC_OK && ce.invert) rc_p = validate_potential_expr(ce.invert, "invert_action expression", "delta");
-    }
-    return rc_p;
+    return rc;
 }
 
-// What the run-time compiler is given for a script-defined model: the expressions in one string, section marks between them
-// (amc_rtc.hip rtc_compile takes it apart again).  A derivative section that is absent means: differentiate logq (amc_dual.h).
-static std::string encode_model_expr(bool f32, const char* potential_expr, const char* reward_expr, const char* scale_expr, const ProposalExprs* proposal)
+// An expression of the C ABI as a ModelSpec field.  NULL: not given.  An empty one stays given -- a NUL character, which
+// validate_potential_expr reads as the empty expression it refuses.
+static std::string given(const char* expr) { return !expr ? std::string() : *expr ? std::string(expr) : std::string(1, '\0'); }
+
+// The C arguments of a script-defined model as a ModelSpec.  The arrays hold one entry per class -- dlogq_exprs the partials of the
+// one class where n_params > 1 --; a NULL array or entry: not given.  who != nullptr: with the checks of the entries that take
+// arrays (every class has sample and logq, perform and invert come together), `note` behind the first one's message.
+static int model_spec(const char* who, const char* note, const char* potential_expr, const char* reward_expr, const char* scale_expr, int n_params,
+                      int n_classes, const char* const* sample_exprs, const char* const* logq_exprs, const char* const* dlogq_exprs,
+                      const char* const* perform_exprs, const char* const* invert_exprs, ModelSpec* spec)
 {
-    std::string e;
-    if (f32) e = "\x02";
-    if (potential_expr) e += potential_expr;
-    if (potential_expr && reward_expr) e += std::string("\x01") + reward_expr;
-    if (potential_expr && scale_expr) e += std::string("\x03") + scale_expr;
-    if (potential_expr && proposal) {
-        e += std::string("\x04") + proposal->sample + std::string("\x05") + proposal->logq;
-        if (proposal->dlogq) {
-            e += std::string("\x06") + proposal->dlogq;
-            for (int pidx = 1; pidx < proposal->n_params; ++pidx) e += std::string("\x0b") + proposal->dlogq_more[pidx - 1];
-        }
-        if (proposal->perform) e += std::string("\x07") + proposal->perform + std::string("\x08") + proposal->invert;
-        if (proposal->n_params > 1) e += std::string("\x0e") + std::to_string(proposal->n_params);
-        if (proposal->n_classes > 1) {
-            // [ '\x0f' n_classes { '\x10' sample '\x11' logq '\x12' dlogq '\x13' perform '\x14' invert } per class 1 .. ]: empty = not given
-            e += std::string("\x0f") + std::to_string(proposal->n_classes);
-            for (int c = 1; c < proposal->n_classes; ++c) {
-                const ClassExprs& ce = proposal->more_classes[c - 1];
-                e += std::string("\x10") + ce.sample + std::string("\x11") + ce.logq + std::string("\x12") + (ce.dlogq ? ce.dlogq : "") +
-                     std::string("\x13") + (ce.perform ? ce.perform : "") + std::string("\x14") + (ce.invert ? ce.invert : "");
-            }
-        }
+    for (int c = 0; who && c < n_classes; ++c) {
+        if (!sample_exprs[c] || !logq_exprs[c]) return fail(AMC_ERR_BAD_ARG, "%s: class %d has no sample / logq expression%s", who, c, note);
+        const bool p = perform_exprs && perform_exprs[c], i = invert_exprs && invert_exprs[c];
+        if (p != i) return fail(AMC_ERR_BAD_ARG, "%s: class %d: perform_expr and invert_expr come together (No invert_action! is defined)", who, c);
     }
-    return e;
+    spec->potential = given(potential_expr);
+    spec->reward = given(reward_expr);
+    spec->scale = given(scale_expr);
+    spec->n_params = n_params;
+    for (int c = 0; c < n_classes; ++c) {
+        PolicyClass pc;
+        pc.sample = given(sample_exprs[c]);
+        pc.logq = given(logq_exprs[c]);
+        for (int q = 0; dlogq_exprs && dlogq_exprs[c] && q < n_params; ++q) pc.dlogq.push_back(given(dlogq_exprs[c + q]));
+        pc.perform = given(perform_exprs ? perform_exprs[c] : nullptr);
+        pc.invert = given(invert_exprs ? invert_exprs[c] : nullptr);
+        spec->classes.push_back(pc);
+    }
+    return AMC_OK;
 }
 
-static int create_impl(const amc_config* cfg, const char* potential_expr, amc_handle** out, const char* reward_expr = nullptr,
-                       const char* scale_expr = nullptr, const ProposalExprs* proposal = nullptr)
+// spec: the script-defined part of the model (an empty one: amc_create's); its dtype switches are set here, from the config
+static int create_impl(const amc_config* cfg, const ModelSpec& spec, amc_handle** out)
 {
     if (!cfg || !out) return fail(AMC_ERR_BAD_ARG, "amc_create: NULL argument");
     *out = nullptr;
@@ -160,7 +155,7 @@ static int create_impl(const amc_config* cfg, const char* potential_expr, amc_ha
     if (param_f32 && state_dtype != AMC_DTYPE_F32)
         return fail(AMC_ERR_BAD_ARG, "amc_create: param_dtype = AMC_DTYPE_F32 requires state_dtype = AMC_DTYPE_F32 (a Float32 sigma under "
                                      "Float64 state promotes to the Float64 arithmetic: ask for param_dtype = AMC_DTYPE_F64)");
-    if (param_f32 && (scale_expr || proposal))
+    if (param_f32 && (!spec.scale.empty() || !spec.classes.empty()))
         return fail(AMC_ERR_BAD_ARG, "amc_create: script-defined policies are not available with param_dtype = AMC_DTYPE_F32 "
                                      "(Float32 policy parameters: the built-in Gaussian policy only)");
     if (cfg->n_chains < 1) return fail(AMC_ERR_BAD_ARG, "amc_create: n_chains must be >= 1");
@@ -172,23 +167,14 @@ static int create_impl(const amc_config* cfg, const char* potential_expr, amc_ha
         return fail(AMC_ERR_BAD_ARG, "amc_create: n_moves must be in [1, %d]", AMC_MAX_MOVES);
     if (cfg->sweepstep < 1) return fail(AMC_ERR_BAD_ARG, "amc_create: sweepstep must be >= 1");
     if (cfg->potential == AMC_POTENTIAL_CUSTOM) {
-        if (!potential_expr)
+        if (spec.potential.empty())
             return fail(AMC_ERR_BAD_ARG, "amc_create: AMC_POTENTIAL_CUSTOM needs its expression: use amc_create_custom");
-        const int rc_expr = validate_potential_expr(potential_expr);
+        int rc_expr = validate_potential_expr(spec.potential.c_str());
+        if (rc_expr == AMC_OK && !spec.reward.empty()) rc_expr = validate_potential_expr(spec.reward.c_str(), "custom reward", "delta");
+        if (rc_expr == AMC_OK && !spec.scale.empty()) rc_expr = validate_potential_expr(spec.scale.c_str(), "proposal-width scale", "x");
+        if (rc_expr == AMC_OK) rc_expr = validate_classes(spec);
         if (rc_expr != AMC_OK) return rc_expr;
-        if (reward_expr) {
-            const int rc_rew = validate_potential_expr(reward_expr, "custom reward", "delta");
-            if (rc_rew != AMC_OK) return rc_rew;
-        }
-        if (scale_expr) {
-            const int rc_sc = validate_potential_expr(scale_expr, "proposal-width scale", "x");
-            if (rc_sc != AMC_OK) return rc_sc;
-        }
-        if (proposal) {
-            const int rc_p = validate_proposal_exprs(proposal);
-            if (rc_p != AMC_OK) return rc_p;
-        }
-    } else if (potential_expr) {
+    } else if (!spec.potential.empty()) {
         return fail(AMC_ERR_BAD_ARG, "amc_create_custom: cfg->potential must be AMC_POTENTIAL_CUSTOM");
     } else if (cfg->potential != AMC_POTENTIAL_HARMONIC && cfg->potential != AMC_POTENTIAL_DOUBLE_WELL) {
         return fail(AMC_ERR_BAD_ARG, "amc_create: unknown potential id %d", cfg->potential);
@@ -257,17 +243,17 @@ static int create_impl(const amc_config* cfg, const char* potential_expr, amc_ha
     h->f32 = state_dtype == AMC_DTYPE_F32;
     h->param_f32 = param_f32;
     h->use_rtc = h->f32 || cfg->potential == AMC_POTENTIAL_CUSTOM;
-    h->pot_expr = encode_model_expr(h->f32, potential_expr, reward_expr, scale_expr, proposal);
-    if (param_f32) h->pot_expr.insert(1, "\x15");        // behind the '\x02' of Float32 state: the kernels are built with AMC_PARAM_F32
-    if (potential_expr && scale_expr) h->scaled_policy = true;
-    if (potential_expr && proposal) {
-        if (proposal->n_classes > 1) {
-            h->n_classes = proposal->n_classes;
-            for (int k = 0; k < cfg->n_moves; ++k) h->class_of_move[k] = proposal->class_of_move[k];
-        }
-        h->script_policy = true;
-        h->script_dlogq = proposal->dlogq != nullptr;
-        h->n_params = proposal->n_params;
+    // the model, and what the other units read of it
+    h->model = spec;
+    h->model.f32 = h->f32;
+    h->model.param_f32 = param_f32;
+    h->scaled_policy = !spec.scale.empty();
+    h->script_policy = !spec.classes.empty();
+    h->script_dlogq = h->script_policy && !spec.classes[0].dlogq.empty();
+    h->n_params = spec.n_params;
+    if (spec.classes.size() > 1) {
+        h->n_classes = (int)spec.classes.size();
+        for (int k = 0; k < cfg->n_moves; ++k) h->class_of_move[k] = spec.class_of_move[k];
     }
     h->K = cfg->n_moves;
     h->sweepstep = cfg->sweepstep;
@@ -374,40 +360,49 @@ static int create_impl(const amc_config* cfg, const char* potential_expr, amc_ha
     return AMC_OK;
 }
 
-int amc_create(const amc_config* cfg, amc_handle** out) { return create_impl(cfg, nullptr, out); }
+int amc_create(const amc_config* cfg, amc_handle** out) { return create_impl(cfg, ModelSpec(), out); }
 
 int amc_create_custom(const amc_config* cfg, const char* potential_expr, amc_handle** out)
 {
     if (!potential_expr) return fail(AMC_ERR_BAD_ARG, "amc_create_custom: potential_expr is NULL");
-    return create_impl(cfg, potential_expr, out);
+    ModelSpec spec;
+    spec.potential = given(potential_expr);
+    return create_impl(cfg, spec, out);
 }
 
-// The creators of run-time compiled models: the potential's text (the script's, or the built-in's own expression where the script
-// names cfg->potential -- compiled at run time it is the built-in bit for bit; with Float32 state the double well subtracts a Float32
-// one, as Julia's `(x^2 - 1)^2` does) and the caller's config as an AMC_POTENTIAL_CUSTOM one (a 0.1 caller's struct is shorter).
-static int as_custom_model(const amc_config* cfg, const char* potential_expr, const char* who, const char** pot, amc_config* c2)
+// The one path of the creators of run-time compiled models (class_checks: model_spec's, for the entry that takes arrays; the other
+// arguments as model_spec's).  The potential is the script's, or the built-in's own expression where the script names
+// cfg->potential -- compiled at run time it is the built-in bit for bit; with Float32 state the double well subtracts a Float32 one,
+// as Julia's `(x^2 - 1)^2` does --, and the handle is made from the caller's config as an AMC_POTENTIAL_CUSTOM one (a 0.1 caller's
+// struct is shorter).
+static int create_model(const char* who, bool class_checks, const amc_config* cfg, const char* potential_expr, const char* reward_expr,
+                        const char* scale_expr, int n_params, int n_classes, const int* class_of_move, const char* const* sample_exprs,
+                        const char* const* logq_exprs, const char* const* dlogq_exprs, const char* const* perform_exprs,
+                        const char* const* invert_exprs, amc_handle** out)
 {
-    *pot = potential_expr;
-    if (!*pot) {
+    ModelSpec spec;
+    const int rc = model_spec(class_checks ? who : nullptr, " (No sample_action! / log_proposal_density is defined)", potential_expr, reward_expr, scale_expr, n_params,
+                              n_classes, sample_exprs, logq_exprs, dlogq_exprs, perform_exprs, invert_exprs, &spec);
+    if (rc != AMC_OK) return rc;
+    if (!potential_expr) {
         const bool f32 = cfg->struct_size == sizeof(amc_config) && cfg->state_dtype == AMC_DTYPE_F32;
-        if (cfg->potential == AMC_POTENTIAL_HARMONIC) *pot = "x*x";
-        else if (cfg->potential == AMC_POTENTIAL_DOUBLE_WELL) *pot = f32 ? "(x*x - 1.0f)*(x*x - 1.0f)" : "(x*x - 1.0)*(x*x - 1.0)";
+        if (cfg->potential == AMC_POTENTIAL_HARMONIC) spec.potential = "x*x";
+        else if (cfg->potential == AMC_POTENTIAL_DOUBLE_WELL) spec.potential = f32 ? "(x*x - 1.0f)*(x*x - 1.0f)" : "(x*x - 1.0)*(x*x - 1.0)";
         else return fail(AMC_ERR_BAD_ARG, "%s: potential_expr is NULL and cfg->potential names no built-in", who);
     }
-    std::memset(c2, 0, sizeof(*c2));
-    std::memcpy(c2, cfg, cfg->struct_size < sizeof(*c2) ? (cfg->struct_size >= 4 ? cfg->struct_size : 4) : sizeof(*c2));
-    c2->potential = AMC_POTENTIAL_CUSTOM;
-    return AMC_OK;
+    if (class_of_move) spec.class_of_move.assign(class_of_move, class_of_move + cfg->n_moves);
+    amc_config c2;
+    std::memset(&c2, 0, sizeof(c2));
+    std::memcpy(&c2, cfg, cfg->struct_size < sizeof(c2) ? (cfg->struct_size >= 4 ? cfg->struct_size : 4) : sizeof(c2));
+    c2.potential = AMC_POTENTIAL_CUSTOM;
+    return create_impl(&c2, spec, out);
 }
 
 int amc_create_model(const amc_config* cfg, const char* potential_expr, const char* reward_expr, amc_handle** out)
 {
     if (!cfg) return fail(AMC_ERR_BAD_ARG, "amc_create_model: NULL argument");
-    // a built-in potential with a custom reward: the built-in's own expression, compiled at run time (bit-identical)
-    const char* pot = nullptr;
-    amc_config c2;
-    { const int rc = as_custom_model(cfg, potential_expr, "amc_create_model", &pot, &c2); if (rc != AMC_OK) return rc; }
-    return create_impl(&c2, pot, out, reward_expr);
+    // (a built-in potential with a custom reward: the built-in's own expression, compiled at run time)
+    return create_model("amc_create_model", false, cfg, potential_expr, reward_expr, nullptr, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int amc_create_policy_model(const amc_config* cfg, const char* potential_expr, const char* reward_expr, const char* scale_expr,
@@ -415,10 +410,7 @@ int amc_create_policy_model(const amc_config* cfg, const char* potential_expr, c
 {
     if (!cfg) return fail(AMC_ERR_BAD_ARG, "amc_create_policy_model: NULL argument");
     if (!scale_expr) return amc_create_model(cfg, potential_expr, reward_expr, out);
-    const char* pot = nullptr;
-    amc_config c2;
-    { const int rc = as_custom_model(cfg, potential_expr, "amc_create_policy_model", &pot, &c2); if (rc != AMC_OK) return rc; }
-    return create_impl(&c2, pot, out, reward_expr, scale_expr);
+    return create_model("amc_create_policy_model", false, cfg, potential_expr, reward_expr, scale_expr, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int amc_create_proposal_model(const amc_config* cfg, const char* potential_expr, const char* reward_expr, const char* sample_expr,
@@ -439,12 +431,8 @@ int amc_create_vector_policy_model(const amc_config* cfg, int n_params, const ch
     if (dlogq_exprs)
         for (int p = 0; p < n_params; ++p)
             if (!dlogq_exprs[p]) return fail(AMC_ERR_BAD_ARG, "amc_create_vector_policy_model: dlogq_exprs[%d] is NULL (one expression per parameter, or none at all)", p);
-    const char* pot = nullptr;
-    amc_config c2;
-    { const int rc = as_custom_model(cfg, potential_expr, "amc_create_vector_policy_model", &pot, &c2); if (rc != AMC_OK) return rc; }
-    const ProposalExprs prop = {sample_expr, logq_expr, dlogq_exprs ? dlogq_exprs[0] : nullptr, perform_expr, invert_expr, n_params,
-                                dlogq_exprs ? dlogq_exprs + 1 : nullptr, 1, nullptr, nullptr};
-    return create_impl(&c2, pot, out, reward_expr, nullptr, &prop);
+    return create_model("amc_create_vector_policy_model", false, cfg, potential_expr, reward_expr, nullptr, n_params, 1, nullptr, &sample_expr, &logq_expr,
+                        dlogq_exprs, &perform_expr, &invert_expr, out);
 }
 
 int amc_create_action_model(const amc_config* cfg, const char* potential_expr, const char* reward_expr, const char* sample_expr,
@@ -454,11 +442,8 @@ int amc_create_action_model(const amc_config* cfg, const char* potential_expr, c
     if (!cfg) return fail(AMC_ERR_BAD_ARG, "amc_create_proposal_model: NULL argument");
     if (!sample_expr || !logq_expr)
         return fail(AMC_ERR_BAD_ARG, "amc_create_proposal_model: sample_expr and logq_expr are both required (No sample_action! / log_proposal_density is defined)");
-    const char* pot = nullptr;
-    amc_config c2;
-    { const int rc = as_custom_model(cfg, potential_expr, "amc_create_proposal_model", &pot, &c2); if (rc != AMC_OK) return rc; }
-    const ProposalExprs prop = {sample_expr, logq_expr, dlogq_expr, perform_expr, invert_expr, 1, nullptr, 1, nullptr, nullptr};
-    return create_impl(&c2, pot, out, reward_expr, nullptr, &prop);
+    return create_model("amc_create_proposal_model", false, cfg, potential_expr, reward_expr, nullptr, 1, 1, nullptr, &sample_expr, &logq_expr, &dlogq_expr,
+                        &perform_expr, &invert_expr, out);
 }
 
 int amc_create_mixed_model(const amc_config* cfg, int n_classes, const int* class_of_move, const char* potential_expr,
@@ -473,22 +458,8 @@ int amc_create_mixed_model(const amc_config* cfg, int n_classes, const int* clas
     for (int k = 0; k < cfg->n_moves; ++k)
         if (class_of_move[k] < 0 || class_of_move[k] >= n_classes)
             return fail(AMC_ERR_BAD_ARG, "amc_create_mixed_model: class_of_move[%d] = %d is no class", k, class_of_move[k]);
-    for (int c = 0; c < n_classes; ++c) {
-        if (!sample_exprs[c] || !logq_exprs[c])
-            return fail(AMC_ERR_BAD_ARG, "amc_create_mixed_model: class %d has no sample / logq expression (No sample_action! / log_proposal_density is defined)", c);
-        const bool p = perform_exprs && perform_exprs[c], i = invert_exprs && invert_exprs[c];
-        if (p != i) return fail(AMC_ERR_BAD_ARG, "amc_create_mixed_model: class %d: perform_expr and invert_expr come together (No invert_action! is defined)", c);
-    }
-    const char* pot = nullptr;
-    amc_config c2;
-    { const int rc = as_custom_model(cfg, potential_expr, "amc_create_mixed_model", &pot, &c2); if (rc != AMC_OK) return rc; }
-    ClassExprs more[AMC_MAX_CLASSES];
-    for (int c = 1; c < n_classes; ++c)
-        more[c - 1] = ClassExprs{sample_exprs[c], logq_exprs[c], dlogq_exprs ? dlogq_exprs[c] : nullptr, perform_exprs ? perform_exprs[c] : nullptr,
-                                 invert_exprs ? invert_exprs[c] : nullptr};
-    const ProposalExprs prop = {sample_exprs[0], logq_exprs[0], dlogq_exprs ? dlogq_exprs[0] : nullptr, perform_exprs ? perform_exprs[0] : nullptr,
-                                invert_exprs ? invert_exprs[0] : nullptr, 1, nullptr, n_classes, more, class_of_move};
-    return create_impl(&c2, pot, out, reward_expr, nullptr, &prop);
+    return create_model("amc_create_mixed_model", true, cfg, potential_expr, reward_expr, nullptr, 1, n_classes, class_of_move, sample_exprs,
+                        logq_exprs, dlogq_exprs, perform_exprs, invert_exprs, out);
 }
 
 int amc_model_check(int n_params, int n_classes, const char* potential_expr, const char* reward_expr, const char* const* sample_exprs,
@@ -500,35 +471,26 @@ int amc_model_check(int n_params, int n_classes, const char* potential_expr, con
     if (n_classes < 1 || n_classes > AMC_MAX_CLASSES) return fail(AMC_ERR_BAD_ARG, "amc_model_check: n_classes must be in [1, %d]", AMC_MAX_CLASSES);
     if (n_params < 1 || n_params > AMC_MAX_NP || (n_params > 1 && n_classes > 1))
         return fail(AMC_ERR_BAD_ARG, "amc_model_check: n_params must be in [1, %d], and 1 for a pool of several classes", AMC_MAX_NP);
-    for (int c = 0; c < n_classes; ++c) {
-        if (!sample_exprs[c] || !logq_exprs[c]) return fail(AMC_ERR_BAD_ARG, "amc_model_check: class %d has no sample / logq expression", c);
-        const bool p = perform_exprs && perform_exprs[c], i = invert_exprs && invert_exprs[c];
-        if (p != i) return fail(AMC_ERR_BAD_ARG, "amc_model_check: class %d: perform_expr and invert_expr come together (No invert_action! is defined)", c);
-    }
+    ModelSpec spec;
+    int rc = model_spec("amc_model_check", "", potential_expr ? potential_expr : "x*x", reward_expr, nullptr, n_params, n_classes, sample_exprs, logq_exprs,
+                        dlogq_exprs, perform_exprs, invert_exprs, &spec);
+    if (rc != AMC_OK) return rc;
     // several parameters: dlogq_exprs holds the P partials of the one class (all or none); several classes: one entry per class, NULL entries allowed
     if (n_params > 1 && dlogq_exprs)
         for (int q = 0; q < n_params; ++q)
             if (!dlogq_exprs[q]) return fail(AMC_ERR_BAD_ARG, "amc_model_check: dlogq_exprs[%d] is NULL (one expression per parameter, or none at all)", q);
-    const char* pot = potential_expr ? potential_expr : "x*x";
-    { const int rc = validate_potential_expr(pot); if (rc != AMC_OK) return rc; }
-    if (reward_expr) { const int rc = validate_potential_expr(reward_expr, "custom reward", "delta"); if (rc != AMC_OK) return rc; }
-    ClassExprs more[AMC_MAX_CLASSES];
-    for (int c = 1; c < n_classes; ++c)
-        more[c - 1] = ClassExprs{sample_exprs[c], logq_exprs[c], dlogq_exprs ? dlogq_exprs[c] : nullptr, perform_exprs ? perform_exprs[c] : nullptr,
-                                 invert_exprs ? invert_exprs[c] : nullptr};
-    const int com[1] = {0};
-    const ProposalExprs prop = {sample_exprs[0], logq_exprs[0], dlogq_exprs ? dlogq_exprs[0] : nullptr, perform_exprs ? perform_exprs[0] : nullptr,
-                                invert_exprs ? invert_exprs[0] : nullptr, n_params, (dlogq_exprs && n_params > 1) ? dlogq_exprs + 1 : nullptr,
-                                n_classes, more, com};
-    { const int rc = validate_proposal_exprs(&prop); if (rc != AMC_OK) return rc; }
+    rc = validate_potential_expr(spec.potential.c_str());
+    if (rc == AMC_OK && !spec.reward.empty()) rc = validate_potential_expr(spec.reward.c_str(), "custom reward", "delta");
+    if (rc == AMC_OK) rc = validate_classes(spec);
+    if (rc != AMC_OK) return rc;
     const AmcKnobs knobs = amc_knobs();
-    const std::string expr = encode_model_expr(knobs.model_check_f32, pot, reward_expr, nullptr, &prop);
+    spec.f32 = knobs.model_check_f32;
     // the estimator kernel is the one that uses every expression (sample, logq, its derivative, perform / invert, reward); with
     // AMC_RTC_CACHE_DIR the code object lands in a file that llvm-objdump reads (tools/rtc_isa.py)
     const RtcCode* code = nullptr;
     std::string text;
     const std::string inst = knobs.model_check_inst.empty() ? "amc::pg_estimate_kernel<2,1,false,0,0,false>" : knobs.model_check_inst;
-    const int rc = rtc_compile(expr, inst, AMC_BUILD_ARCH, knobs, &code, &text);
+    rc = rtc_compile(spec, inst, AMC_BUILD_ARCH, knobs, &code, &text);
     if (log && log_capacity > 0) {
         std::strncpy(log, text.c_str(), (size_t)log_capacity - 1);
         log[log_capacity - 1] = 0;

@@ -128,6 +128,21 @@ struct RedTicket {
     unsigned long long* h_ratio_acc = nullptr;   // pinned copy
 };
 
+// A model as the run-time compiler is given it (amc_rtc.hip model_prelude): C expressions, "" where one is not given.
+struct PolicyClass {
+    std::string sample, logq;          // sample_action!(z, x, sigma), log_proposal_density(delta, x, sigma)
+    std::vector<std::string> dlogq;    // d logq / d parameter: none (logq is differentiated, amc_dual.h) or one per parameter
+    std::string perform, invert;       // the action's perform_action!(x, delta) / invert_action!(delta, x): both or neither (a displacement)
+};
+struct ModelSpec {
+    bool f32 = false, param_f32 = false;     // Float32 state; ... and Float32 policy parameters (kernels built with AMC_PARAM_F32)
+    std::string potential, reward, scale;    // "": the built-in potential / the default reward / no proposal-width scale(x)
+    int n_params = 1;                        // parameters of the policy (> 1: of the one class)
+    std::vector<PolicyClass> classes;        // empty: the built-in Gaussian policy; several: a pool that mixes policies / actions
+    std::vector<int> class_of_move;          // ... and the class of each move (the handle's table row: no part of what is compiled)
+    std::string cache_text() const;          // the model in the code-object caches' keys (amc_rtc.hip)
+};
+
 struct amc_handle {
     AmcKnobs knobs;             // the environment's knobs as amc_create found them
     int device = 0;
@@ -226,7 +241,7 @@ struct amc_handle {
     bool pg_tail_valid = false;
     Rccl rccl;
     std::string arch = AMC_BUILD_ARCH;   // the device's ISA name (gcnArchName up to its first ':'): what hiprtc compiles for
-    std::string pot_expr;         // AMC_POTENTIAL_CUSTOM: the C expression of potential(x); '\x02' in front: Float32 state
+    ModelSpec model;              // what the run-time compiler builds this handle's kernels from; the fields below are derived from it
     bool f32 = false;             // state_dtype == AMC_DTYPE_F32: d_x / d_beta hold floats
     bool param_f32 = false;       // param_dtype == AMC_DTYPE_F32 (needs f32): sigma, the normal variate, delta = sigma z and the quotient of
                                   // log_proposal_density are Float32 (kernels built with AMC_PARAM_F32); sweeps with the built-in policy only
@@ -273,7 +288,7 @@ AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communica
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };
 AMC_INTERNAL int validate_potential_expr(const char* expr, const char* what = "custom potential", const char* var = "x");
-AMC_INTERNAL int rtc_compile(const std::string& expr_in, const std::string& inst, const std::string& arch, const AmcKnobs& knobs, const RtcCode** out,
+AMC_INTERNAL int rtc_compile(const ModelSpec& spec, const std::string& inst, const std::string& arch, const AmcKnobs& knobs, const RtcCode** out,
                              std::string* log_out);
 AMC_INTERNAL int rtc_function(amc_handle* h, const std::string& inst, hipFunction_t* fn);
 AMC_INTERNAL int rtc_launch(amc_handle* h, const std::string& inst, int grid, void** params);

@@ -1,6 +1,8 @@
-// amc_rtc.hip -- kernels compiled at run time: script-defined potentials, rewards, policies, actions and the Float32 state
-// (amc_create_custom / _model / _policy_model / _action_model / _vector_policy_model / _mixed_model).  hiprtc is resolved with
-// dlopen; the kernel sources travel in the library as string literals (amc_rtc_sources.gen.h, made by embed_sources.py).
+// amc_rtc.hip -- kernels compiled at run time: script-defined potentials, rewards, policies, actions and the Float32 state.  A
+// model arrives as a ModelSpec (amc_internal.h; amc_api.hip's creators fill it in); model_prelude writes it out as the #defines
+// the kernel headers read, ModelSpec::cache_text as the text the code-object caches key it by.  hiprtc is resolved with dlopen and
+// runs in a child process (amc_rtc_worker); the kernel sources travel in the library as string literals (amc_rtc_sources.gen.h,
+// made by embed_sources.py).
 #define AMC_KERNEL_LINKAGE static      // the kernel headers are included for their types only: no kernel of theirs in this object
 #include "amc_internal.h"
 #include "amc_rtc_sources.gen.h"
@@ -38,7 +40,7 @@ struct Hiprtc {
 
 std::mutex g_rtc_mu;
 Hiprtc g_hiprtc;
-std::map<std::string, RtcCode> g_rtc_code;        // key: arch, expression, instantiation, variant (rtc_compile)
+std::map<std::string, RtcCode> g_rtc_code;        // key: arch, model (cache_text), instantiation, variant (rtc_compile)
 std::map<std::string, std::string> g_rtc_broken;  // same key: instantiations the compiler DIED on (its last words), not to be asked for again
 
 int load_hiprtc(Hiprtc& r)
@@ -368,10 +370,94 @@ int build_in_child(const std::string& src, const std::string& inst, const std::v
 
 }  // namespace
 
+// The model in the keys of the code-object caches (in process and under AMC_RTC_CACHE_DIR): its expressions in one string, a control
+// character in front of each section.  It is hashed and compared, never taken apart, and spelt the way the cache directories in
+// use were filled:
+//   [ '\x02' (Float32 state) [ '\x15' (Float32 policy parameters) ] ]
+//   [ potential [ '\x01' reward ] [ '\x03' scale ]
+//     [ '\x04' sample '\x05' logq [ '\x06' dlogq { '\x0b' dlogq of parameter 1 .. } ] [ '\x07' perform '\x08' invert ] [ '\x0e' n_params, if > 1 ]
+//       [ '\x0f' n_classes, if > 1, { '\x10' sample '\x11' logq '\x12' dlogq '\x13' perform '\x14' invert } of the classes 1 .. : every mark,
+//         nothing behind it where the class has no such expression ] ] ]
+std::string ModelSpec::cache_text() const
+{
+    std::string t;
+    if (f32) t = param_f32 ? "\x02\x15" : "\x02";
+    t += potential;
+    if (!reward.empty()) t += '\x01' + reward;
+    if (!scale.empty()) t += '\x03' + scale;
+    for (size_t c = 0; c < classes.size(); ++c) {
+        const PolicyClass& pc = classes[c];
+        if (c == 0) {
+            t += '\x04' + pc.sample + '\x05' + pc.logq;
+            for (size_t p = 0; p < pc.dlogq.size(); ++p) t += (p == 0 ? '\x06' : '\x0b') + pc.dlogq[p];
+            if (!pc.perform.empty()) t += '\x07' + pc.perform + '\x08' + pc.invert;
+            if (n_params > 1) t += '\x0e' + std::to_string(n_params);
+            if (classes.size() > 1) t += '\x0f' + std::to_string(classes.size());
+        } else
+            t += '\x10' + pc.sample + '\x11' + pc.logq + '\x12' + (pc.dlogq.empty() ? std::string() : pc.dlogq[0]) + '\x13' + pc.perform + '\x14' + pc.invert;
+    }
+    return t;
+}
+
+// What stands in front of `#include "amc_kernels.h"` in a run-time build of `inst`: the model and the knobs' variant of the sources as
+// the macros the kernel headers look for.  No other place knows their names.  The order of the lines is part of the compiler's input.
+static std::string model_prelude(const ModelSpec& spec, const std::string& inst, const AmcKnobs& knobs)
+{
+    std::string src;
+    // a template instantiation is all this translation unit is asked for: the headers' plain kernels (initial ensemble, parameter
+    // tables, accumulate / update, the selftest hooks: ~9 000 instructions of ISA) stay out of it.  (The two plain kernels that ARE
+    // built at run time, for Float32 state, are asked for by name: those builds keep them.)
+    if (inst.find('<') != std::string::npos) src += "#define AMC_PLAIN_KERNELS 0\n";
+    if (spec.f32) src += "#define AMC_STATE_F32 1\n";
+    if (spec.f32 && spec.param_f32) src += "#define AMC_PARAM_F32 1\n";
+    if (knobs.no_sigma_memo) src += "#define AMC_NO_SIGMA_MEMO 1\n";      // A/B: amc_log(sigma) per lane and step in K > 1 sweeps (amc_model.h SigmaArg)
+    if (knobs.rtc_waves_set) src += "#define AMC_RTC_WAVES " + std::to_string(std::atoi(knobs.rtc_waves.c_str())) + "\n";       // A/B: amdgpu_waves_per_eu of the script-defined estimator forms
+    if (!spec.scale.empty()) src += "#define AMC_USER_SCALE(x) (" + spec.scale + ")\n";      // (a model has a scale or classes, never both)
+    // a class whose expressions are the built-in Gaussian displacement's, as the host mirror writes them out (montecarlo_amd/metropolis.py
+    // GAUSS_SAMPLE / GAUSS_LOGQ, the displacement's own perform / invert): the sweep takes its density from the move's table row
+    // (amc_model.h GaussRow)
+    auto is_gauss = [](const PolicyClass& pc) {
+        return pc.sample == "sigma*z" && pc.logq == "-(delta*delta)/(2.0*(sigma*sigma)) - amc_log(6.283185307179586*(sigma*sigma))/2.0" &&
+               pc.perform.empty() && pc.invert.empty();
+    };
+    // ... derivative included (GAUSS_DLOGQ): the estimator then knows the backward density and derivative without forming them
+    auto is_gauss_d = [](const PolicyClass& pc) { return pc.dlogq.size() == 1 && pc.dlogq[0] == "(delta*delta)/(sigma*sigma*sigma) - 1.0/sigma"; };
+    unsigned gauss_mask = 0u, gauss_est_mask = 0u;
+    for (size_t c = 0; c < spec.classes.size(); ++c) {
+        const PolicyClass& pc = spec.classes[c];
+        const std::string sfx = c == 0 ? std::string() : "_" + std::to_string(c);
+        // class 0 names its action in front of its policy, and only when it has one; the classes 1 .. behind it, a displacement's where
+        // they have none
+        std::string action, policy;
+        if (c > 0 || !pc.perform.empty())
+            action += "#define AMC_USER_PERFORM" + sfx + "(x, delta) (" + (pc.perform.empty() ? std::string("(x) + (delta)") : pc.perform) + ")\n";
+        if (c > 0 || !pc.invert.empty())
+            action += "#define AMC_USER_INVERT" + sfx + "(delta, x) (" + (pc.invert.empty() ? std::string("-(delta)") : pc.invert) + ")\n";
+        policy += "#define AMC_USER_SAMPLE" + sfx + "(z, x, sigma) (" + pc.sample + ")\n";
+        policy += "#define AMC_USER_LOGQ" + sfx + "(delta, x, sigma) (" + pc.logq + ")\n";
+        if (c == 0 && spec.n_params > 1) policy += "#define AMC_NP " + std::to_string(spec.n_params) + "\n";
+        for (size_t p = 0; p < pc.dlogq.size(); ++p)      // the partials 1 .. of the one class with several parameters: AMC_USER_DLOGQ1 ..
+            policy += "#define AMC_USER_DLOGQ" + (p == 0 ? std::string() : std::to_string(p)) + sfx + "(delta, x, sigma) (" + pc.dlogq[p] + ")\n";
+        src += c == 0 ? action + policy : policy + action;
+        if (c == 0 && spec.classes.size() > 1) src += "#define AMC_NCLASS " + std::to_string(spec.classes.size()) + "\n";
+        if (is_gauss(pc)) {
+            gauss_mask |= 1u << c;
+            if (is_gauss_d(pc)) gauss_est_mask |= 1u << c;
+        }
+    }
+    if (spec.classes.size() > 1 && gauss_mask != 0u && !knobs.no_gauss_class_rows) {
+        src += "#define AMC_CLASS_GAUSS_MASK " + std::to_string(gauss_mask) + "\n";
+        if (gauss_est_mask != 0u) src += "#define AMC_CLASS_GAUSS_EST_MASK " + std::to_string(gauss_est_mask) + "\n";
+    }
+    if (!spec.potential.empty()) src += "#define AMC_USER_POTENTIAL(x) (" + spec.potential + ")\n";
+    if (!spec.reward.empty()) src += "#define AMC_USER_REWARD(delta, x) (" + spec.reward + ")\n";
+    return src + "#include \"amc_kernels.h\"\n";
+}
+
 // Compiles (or finds) the code object holding ONE instantiation, e.g. "amc::sweep_kernel<2,false,false,false,true,false>".
 // Needs no device.  On a compile error the hiprtc log goes into the error message (and *log_out).
 // knobs: the variant of the kernel sources to build (AMC_RTC_*, AMC_NO_GAUSS_CLASS_ROWS, AMC_NO_SIGMA_MEMO).
-int rtc_compile(const std::string& expr_in, const std::string& inst, const std::string& arch, const AmcKnobs& knobs, const RtcCode** out,
+int rtc_compile(const ModelSpec& spec, const std::string& inst, const std::string& arch, const AmcKnobs& knobs, const RtcCode** out,
                 std::string* log_out)
 {
     std::lock_guard<std::mutex> lock(g_rtc_mu);
@@ -394,15 +480,16 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
         }
         const size_t end = inst.find_first_of(",>", at);
         if (end != std::string::npos && inst.substr(at, end - at) == "2") return true;
-        // ... and the estimator forms of policies with several parameters ('\x0e' section of the expression): with 8 to 19 two-level
+        // ... and the estimator forms of policies with several parameters: with 8 to 19 two-level
         // accumulator columns live, what the pass hoists costs registers the kernel does not have (two-parameter fused step: 133 -> 123
         // VGPRs, 66 -> 20 scalar spills, 151 -> 144 us at 1e7 chains; the one-parameter forms are indifferent)
-        return expr_in.find('\x0e') != std::string::npos;
+        return spec.n_params > 1;
     }();
     // the variant of the sources, as the disk cache key has always spelt it (the in-process key carries the same text)
     const std::string variant = std::string(licm_off ? " licm-off" : "") + (knobs.no_gauss_class_rows ? " no-gauss-rows" : "") +
                                 (knobs.no_sigma_memo ? " no-sigma-memo" : "") + (knobs.rtc_waves_set ? " waves" + knobs.rtc_waves : std::string());
-    const std::string key = arch + "\n" + expr_in + "\n" + inst + "\n" + variant;
+    const std::string model = spec.cache_text();
+    const std::string key = arch + "\n" + model + "\n" + inst + "\n" + variant;
     auto it = g_rtc_code.find(key);
     if (it != g_rtc_code.end()) { *out = &it->second; return AMC_OK; }
     {
@@ -412,7 +499,7 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
     { const int rc = load_hiprtc(g_hiprtc); if (rc != AMC_OK) return rc; }
     int rtc_major = 0, rtc_minor = 0;
     (void)g_hiprtc.Version(&rtc_major, &rtc_minor);
-    const std::string cache_file = rtc_cache_path(expr_in, inst, arch, "hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) + variant);
+    const std::string cache_file = rtc_cache_path(model, inst, arch, "hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) + variant);
     {
         RtcCode cached;
         if (rtc_cache_load(cache_file, &cached)) {
@@ -434,91 +521,7 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
             }
         }
     }
-    // expr_in = [ '\x02' (Float32 state) [ '\x15' (Float32 policy parameters) ] ] [ potential [ '\x01' reward ] [ '\x03' scale ] [ '\x04' sample '\x05' logq [ '\x06' dlogq ]
-    //             [ '\x07' perform ] [ '\x08' invert ] ] ]
-    const bool f32 = !expr_in.empty() && expr_in[0] == '\x02';
-    const bool param_f32 = f32 && expr_in.size() > 1 && expr_in[1] == '\x15';      // [ '\x15' (Float32 policy parameters) ] behind '\x02' only
-    const std::string expr_full = expr_in.substr((f32 ? 1 : 0) + (param_f32 ? 1 : 0));
-    std::string expr = expr_full;
-    std::string src;
-    // a template instantiation is all this translation unit is asked for: the headers' plain kernels (initial ensemble, parameter
-    // tables, accumulate / update, the selftest hooks: ~9 000 instructions of ISA) stay out of it.  (The two plain kernels that ARE
-    // built at run time, for Float32 state, are asked for by name: those builds keep them.)
-    if (inst.find('<') != std::string::npos) src += "#define AMC_PLAIN_KERNELS 0\n";
-    if (f32) src += "#define AMC_STATE_F32 1\n";
-    if (param_f32) src += "#define AMC_PARAM_F32 1\n";
-    if (knobs.no_sigma_memo) src += "#define AMC_NO_SIGMA_MEMO 1\n";      // A/B: amc_log(sigma) per lane and step in K > 1 sweeps (amc_model.h SigmaArg)
-    if (knobs.rtc_waves_set) src += "#define AMC_RTC_WAVES " + std::to_string(std::atoi(knobs.rtc_waves.c_str())) + "\n";       // A/B: amdgpu_waves_per_eu of the script-defined estimator forms
-    auto cut_tail = [&](char mark) -> std::string {      // removes and returns what follows the LAST section mark
-        const size_t at = expr.find(mark);
-        if (at == std::string::npos) return std::string();
-        const std::string tail = expr.substr(at + 1);
-        expr.erase(at);
-        return tail;
-    };
-    const std::string e_classes = cut_tail('\x0f');      // [ '\x0f' n_classes { sections of the classes 1 .. } ]: pools that mix policies / actions
-    const std::string e_np = cut_tail('\x0e');           // [ '\x0e' P ]: parameters of the policy, when more than one; the dlogq section then holds P
-                                                         // expressions, '\x0b' between them
-    const std::string e_invert = cut_tail('\x08'), e_perform = cut_tail('\x07');
-    const std::string e_dlogq = cut_tail('\x06'), e_logq = cut_tail('\x05'), e_sample = cut_tail('\x04'), e_scale = cut_tail('\x03');
-    if (!e_perform.empty()) src += "#define AMC_USER_PERFORM(x, delta) (" + e_perform + ")\n";
-    if (!e_invert.empty()) src += "#define AMC_USER_INVERT(delta, x) (" + e_invert + ")\n";
-    if (!e_sample.empty()) src += "#define AMC_USER_SAMPLE(z, x, sigma) (" + e_sample + ")\n";
-    if (!e_logq.empty()) src += "#define AMC_USER_LOGQ(delta, x, sigma) (" + e_logq + ")\n";
-    if (!e_np.empty()) src += "#define AMC_NP " + e_np + "\n";
-    if (!e_dlogq.empty()) {
-        size_t from = 0;
-        for (int pidx = 0; from <= e_dlogq.size(); ++pidx) {
-            const size_t to = e_dlogq.find('\x0b', from);
-            const std::string one = e_dlogq.substr(from, to == std::string::npos ? std::string::npos : to - from);
-            src += "#define AMC_USER_DLOGQ" + (pidx == 0 ? std::string() : std::to_string(pidx)) + "(delta, x, sigma) (" + one + ")\n";
-            if (to == std::string::npos) break;
-            from = to + 1;
-        }
-    }
-    if (!e_scale.empty()) src += "#define AMC_USER_SCALE(x) (" + e_scale + ")\n";
-    // a class whose expressions are the built-in Gaussian displacement's, as the host mirror writes them out (montecarlo_amd/metropolis.py
-    // GAUSS_SAMPLE / GAUSS_LOGQ, the displacement's own perform / invert): the sweep takes its density from the move's table row
-    // (amc_model.h GaussRow)
-    auto is_gauss = [](const std::string& sample, const std::string& logq, const std::string& perform, const std::string& invert) {
-        return sample == "sigma*z" && logq == "-(delta*delta)/(2.0*(sigma*sigma)) - amc_log(6.283185307179586*(sigma*sigma))/2.0" &&
-               perform.empty() && invert.empty();
-    };
-    // ... derivative included (GAUSS_DLOGQ): the estimator then knows the backward density and derivative without forming them
-    auto is_gauss_d = [](const std::string& dlogq) { return dlogq == "(delta*delta)/(sigma*sigma*sigma) - 1.0/sigma"; };
-    unsigned gauss_mask = is_gauss(e_sample, e_logq, e_perform, e_invert) ? 1u : 0u;
-    unsigned gauss_est_mask = (gauss_mask && is_gauss_d(e_dlogq)) ? 1u : 0u;
-    if (!e_classes.empty()) {
-        const size_t first = e_classes.find('\x10');
-        src += "#define AMC_NCLASS " + e_classes.substr(0, first) + "\n";
-        size_t at = first;
-        for (int c = 1; at != std::string::npos; ++c) {
-            const size_t nxt = e_classes.find('\x10', at + 1);
-            const std::string blob = e_classes.substr(at + 1, nxt == std::string::npos ? std::string::npos : nxt - at - 1);
-            const size_t m1 = blob.find('\x11'), m2 = blob.find('\x12'), m3 = blob.find('\x13'), m4 = blob.find('\x14');
-            const std::string sfx = "_" + std::to_string(c);
-            const std::string c_sample = blob.substr(0, m1), c_logq = blob.substr(m1 + 1, m2 - m1 - 1), c_dlogq = blob.substr(m2 + 1, m3 - m2 - 1),
-                              c_perform = blob.substr(m3 + 1, m4 - m3 - 1), c_invert = blob.substr(m4 + 1);
-            src += "#define AMC_USER_SAMPLE" + sfx + "(z, x, sigma) (" + c_sample + ")\n";
-            src += "#define AMC_USER_LOGQ" + sfx + "(delta, x, sigma) (" + c_logq + ")\n";
-            if (!c_dlogq.empty()) src += "#define AMC_USER_DLOGQ" + sfx + "(delta, x, sigma) (" + c_dlogq + ")\n";
-            src += "#define AMC_USER_PERFORM" + sfx + "(x, delta) (" + (c_perform.empty() ? std::string("(x) + (delta)") : c_perform) + ")\n";
-            src += "#define AMC_USER_INVERT" + sfx + "(delta, x) (" + (c_invert.empty() ? std::string("-(delta)") : c_invert) + ")\n";
-            if (is_gauss(c_sample, c_logq, c_perform, c_invert)) {
-                gauss_mask |= 1u << c;
-                if (is_gauss_d(c_dlogq)) gauss_est_mask |= 1u << c;
-            }
-            at = nxt;
-        }
-        if (gauss_mask != 0u && !knobs.no_gauss_class_rows) {
-            src += "#define AMC_CLASS_GAUSS_MASK " + std::to_string(gauss_mask) + "\n";
-            if (gauss_est_mask != 0u) src += "#define AMC_CLASS_GAUSS_EST_MASK " + std::to_string(gauss_est_mask) + "\n";
-        }
-    }
-    const size_t cut = expr.find('\x01');
-    if (!expr.empty()) src += "#define AMC_USER_POTENTIAL(x) (" + expr.substr(0, cut) + ")\n";
-    if (cut != std::string::npos) src += "#define AMC_USER_REWARD(delta, x) (" + expr.substr(cut + 1) + ")\n";
-    src += "#include \"amc_kernels.h\"\n";
+    const std::string src = model_prelude(spec, inst, knobs);
     // the kernel sources travel in the library (amc_rtc_sources.gen.h): hiprtc finds every `#include "amc_*.h"` among them by name.
     // The flags of the offline build (Makefile): only the explicit fma()s may fuse.
     // (-disable-machine-licm is one of LLVM's generic code-generation options; a back end without it does not return an error but ends
@@ -548,7 +551,7 @@ int rtc_compile(const std::string& expr_in, const std::string& inst, const std::
         const std::string& log = built.log;
         size_t from = log.find("error:");
         from = from == std::string::npos ? 0 : log.rfind('\n', from) + 1;       // (npos + 1 == 0: the log's first line)
-        return fail(AMC_ERR_BAD_ARG, "%s: %.400s", expr_full.empty() ? "run-time kernel build failed" : "custom potential does not compile",
+        return fail(AMC_ERR_BAD_ARG, "%s: %.400s", spec.potential.empty() ? "run-time kernel build failed" : "custom potential does not compile",
                     log.empty() ? "(no log)" : log.c_str() + from);
     }
     if (built.stage != 0 || built.code.empty() || built.lowered.empty()) return fail(AMC_ERR_HIP, "hiprtc produced no code for %s", inst.c_str());
@@ -566,7 +569,7 @@ int rtc_function(amc_handle* h, const std::string& inst, hipFunction_t* fn)
     auto it = h->rtc_fn.find(inst);
     if (it != h->rtc_fn.end()) { *fn = it->second; return AMC_OK; }
     const RtcCode* code = nullptr;
-    { const int rc = rtc_compile(h->pot_expr, inst, h->arch, h->knobs, &code, nullptr); if (rc != AMC_OK) return rc; }
+    { const int rc = rtc_compile(h->model, inst, h->arch, h->knobs, &code, nullptr); if (rc != AMC_OK) return rc; }
     hipModule_t mod = nullptr;
     AMC_HIP(hipModuleLoadData(&mod, code->code.data()));
     h->rtc_mods.push_back(mod);
@@ -594,7 +597,9 @@ int amc_potential_check(const char* potential_expr, char* log, int log_capacity)
     { const int rc = validate_potential_expr(potential_expr); if (rc != AMC_OK) return rc; }
     const RtcCode* code = nullptr;
     std::string text;
-    const int rc = rtc_compile(potential_expr, "amc::energy_kernel<2>", AMC_BUILD_ARCH, amc_knobs(), &code, &text);
+    ModelSpec spec;
+    spec.potential = potential_expr;
+    const int rc = rtc_compile(spec, "amc::energy_kernel<2>", AMC_BUILD_ARCH, amc_knobs(), &code, &text);
     if (log && log_capacity > 0) {
         std::strncpy(log, text.c_str(), (size_t)log_capacity - 1);
         log[log_capacity - 1] = 0;

@@ -137,6 +137,84 @@ for d, env, name in %r:
         assert line == d + " True", (env, sorted(os.listdir(d)), name)
 
 
+def _model_text(sample, logq, dlogq=None, perform=None, invert=None, n_params=1, potential=None, reward=None, f32=False):
+    """A script-defined model as the disk key has always spelt it, from _capi.model_check's arguments: the expressions in one
+    string with a control character in front of each section (classes 1.. of a pool: every section, empty where not given)."""
+    many = isinstance(sample, (list, tuple))
+    n = len(sample) if many else 1
+    col = lambda v: list(v) if many and v is not None else [v] + [None] * (n - 1)
+    sample, logq, perform, invert = col(sample), col(logq), col(perform), col(invert)
+    partials = list(dlogq) if n_params > 1 and dlogq is not None else None          # one policy with several parameters
+    dlogq = col(dlogq) if partials is None else [partials[0]]
+    t = ("\x02" if f32 else "") + (potential or "x*x") + ("\x01" + reward if reward else "")
+    t += "\x04" + sample[0] + "\x05" + logq[0]
+    if dlogq[0]:
+        t += "\x06" + ("\x0b".join(partials) if partials else dlogq[0])
+    if perform[0]:
+        t += "\x07" + perform[0] + "\x08" + invert[0]
+    if n_params > 1:
+        t += "\x0e%d" % n_params
+    if n > 1:
+        t += "\x0f%d" % n
+        for c in range(1, n):
+            t += "\x10" + sample[c] + "\x11" + logq[c] + "\x12" + (dlogq[c] or "") + "\x13" + (perform[c] or "") + "\x14" + (invert[c] or "")
+    return t
+
+
+_LOGQ = "-(delta*delta)/(2.0*(sigma*sigma)) - amc_log(sigma)"
+_DLOGQ = "(delta*delta)/(sigma*sigma*sigma) - 1.0/sigma"
+_LOGQ2 = "-((delta - theta1*x)*(delta - theta1*x))/(2.0*(theta0*theta0)) - amc_log(theta0)"
+_DLOGQ2 = ["((delta - theta1*x)*(delta - theta1*x))/(theta0*theta0*theta0) - 1.0/theta0", "x*(delta - theta1*x)/(theta0*theta0)"]
+_FIRST = dict(sample="sigma*z", logq=_LOGQ, dlogq=_DLOGQ, potential="x*x*x*x - 2.0*x*x", reward="-delta*delta - 0.25*x")
+# (_capi.model_check's arguments, environment, the variant text: the default instantiation is an estimator form, built without
+# Machine LICM under AMC_RTC_LICM=est-off and for policies of several parameters)
+MODEL_CACHE_CASES = [
+    (_FIRST, {}, ""),
+    (dict(sample="sigma*z", logq=_LOGQ), {}, ""),
+    (dict(sample="sigma*z", logq=_LOGQ, dlogq=_DLOGQ, perform="x + 0.5*delta", invert="-delta"), {}, ""),
+    (dict(sample="theta1*x + theta0*z", logq=_LOGQ2, dlogq=_DLOGQ2, n_params=2), {}, " licm-off"),
+    (dict(sample="theta1*x + theta0*z", logq=_LOGQ2, n_params=2), {}, " licm-off"),
+    (dict(sample=["sigma*z", "0.5*sigma*z", "sigma*z - 0.125*x"], logq=[_LOGQ, "-2.0*(delta*delta)/(sigma*sigma) - amc_log(sigma)", _LOGQ],
+          dlogq=[_DLOGQ, None, _DLOGQ], perform=[None, None, "x + 0.5*delta"], invert=[None, None, "-delta"], reward="-delta*delta"), {}, ""),
+    (_FIRST, {"AMC_MODEL_CHECK_F32": "1"}, ""),
+    (_FIRST, {"AMC_RTC_LICM": "est-off"}, " licm-off"),
+]
+
+
+def test_disk_cache_key_of_script_models_is_unchanged(tmp_path):
+    """The same for script-defined models (amc_model_check): one class with and without its derivative, with an action, several
+    parameters, a pool of classes, Float32 state -- each found under the name its control-character spelling hashes to."""
+    major, minor = _hiprtc_version()
+    inst = "amc::pg_estimate_kernel<2,1,false,0,0,false>"
+    dirs = []
+    for i, (model, env, variant) in enumerate(MODEL_CACHE_CASES):
+        d = tmp_path / str(i)
+        d.mkdir()
+        text = _model_text(f32=env.get("AMC_MODEL_CHECK_F32") == "1", **model)
+        name = _cache_name(text, inst, "gfx950", "hiprtc %d.%d%s" % (major, minor, variant))
+        lowered, code = b"planted", b"not a code object"
+        (d / name).write_bytes(struct.pack("<3Q", 0x31435452434d41, len(lowered), len(code)) + lowered + code)
+        dirs.append((str(d), env, name, model))
+    script = """
+import os, sys
+sys.path.insert(0, %r)
+from montecarlo_amd import _capi
+for d, env, name, model in %r:
+    for k in ("AMC_MODEL_CHECK_F32", "AMC_MODEL_CHECK_INST", "AMC_NO_SIGMA_MEMO", "AMC_NO_GAUSS_CLASS_ROWS", "AMC_RTC_WAVES", "AMC_RTC_LICM"):
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    os.environ["AMC_RTC_CACHE_DIR"] = d
+    assert _capi.model_check(**model) == ""
+    print(d, sorted(os.listdir(d)) == [name], flush=True)
+""" % (ROOT, dirs)
+    r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(dirs)
+    for (d, env, name, model), line in zip(dirs, lines):
+        assert line == d + " True", (model, env, sorted(os.listdir(d)), name)
+
+
 @pytest.mark.gpu
 def test_handle_knobs_are_read_at_create(gpu, monkeypatch):
     """AMC_NO_SWEEP_ESTIMATOR_FUSION counts as the handle found it: set after creation it changes nothing, set before it
