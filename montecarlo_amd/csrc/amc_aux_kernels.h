@@ -130,9 +130,12 @@ AMC_KERNEL_LINKAGE __global__ void selftest_math_kernel(int fn, const double* a,
 }
 #endif
 
-// Exhaustive check of the accept filter's float estimate (accept_filter): for EVERY float t with bit pattern in
-// [bits_lo, bits_hi] the relative deviation of v_exp_f32(max(t, -17) * log2e) from the spec's f64 exp(t); the maximum
-// over the range lands in out_max_bits (bits of a non-negative double compare like integers).
+// Exhaustive check of the accept filter's float estimate (accept_filter_f32) on the range where the filter relies on its
+// ACCURACY, -17 <= t <= 0: for EVERY float t with bit pattern in [bits_lo, bits_hi] the relative deviation of
+// v_exp_f32(max(t, -17) * log2e) from the spec's f64 exp(t); the maximum over the range lands in out_max_bits (bits of a
+// non-negative double compare like integers).  The filter itself does not clamp: below -17 it needs only the bound ex < 4.3e-8,
+// and this kernel says nothing about that range (there it measures the clamped formula).  The product and v_exp_f32 are the same
+// per-element operations in the filter's packed form.
 #if AMC_PLAIN_KERNELS
 AMC_KERNEL_LINKAGE __global__ __launch_bounds__(256) void selftest_filter_kernel(uint32_t bits_lo, uint64_t count, unsigned long long* out_max_bits)
 {

@@ -266,7 +266,7 @@ AMC_INTERNAL int log_room(amc_handle* h, int* rows);
 AMC_INTERNAL int fold_log(amc_handle* h, bool with_ratio = false, int* ratio_rows = nullptr, amc::xs_word* ratio_dst = nullptr);
 AMC_INTERNAL hipError_t alloc_counters(amc_handle* h, bool narrow);
 AMC_INTERNAL int counter_room(amc_handle* h, const char* who, uint64_t steps);
-AMC_INTERNAL amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps);        // amc_sweeps.hip
+AMC_INTERNAL amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps, int grid);        // amc_sweeps.hip
 AMC_INTERNAL int reduce_sweep_grid(const amc_handle* h);
 AMC_INTERNAL int sweep_impl(amc_handle* h, int64_t n_sweeps, bool fuse_reduce, int* grid_out);
 AMC_INTERNAL int red_form(const amc_handle* h);                                           // amc_reduce.hip

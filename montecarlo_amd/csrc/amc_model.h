@@ -587,8 +587,11 @@ __device__ __forceinline__ bool accept_exact(real_t delta, real_t dlogp, param_t
 }
 
 // Filter.  Inputs: dlogp (exact, f64) and k = the top 12 bits of u's 52-bit significand -- the bits the step's normal
-// draw supplies (spec v5) --, so k 2^-12 <= u < (k+1) 2^-12 with both ends exact floats.  Error budget of the estimate
-// ex = v_exp_f32(log2e * float(dlogp)) against the spec's exp(arg), for -17 <= dlogp < 1e-12 (relative):
+// draw supplies (spec v5) --, so k 2^-12 <= u < (k+1) 2^-12 with both ends exact floats.  The filter only has to be SOUND: it may
+// claim "accept" (lo) or "reject" (hi) only where accept_exact says the same, and everything it leaves open goes to accept_exact.
+// With t = RN_f32(dlogp), y = RN(t * log2e) and ex = v_exp_f32(y) (no clamp, no sign test), by the range of dlogp:
+//
+// -17 <= dlogp <= 0.  Error budget of ex against the spec's exp(arg) (relative):
 //   arg vs dlogp      arg = fl(fl(dlogp + logq) - logq), |arg - dlogp| <= 2^-53 (2|dlogp| + |logq|) with
 //                     |logq| <= z^2/2 (1 + 2^-50) + |log(2 pi s^2)/2| <= 37 + 231 (|z| <= 8.5, 1e-100 <= s <= 1e100)
 //                                                                                                       < 4e-14
@@ -599,56 +602,80 @@ __device__ __forceinline__ bool accept_exact(real_t delta, real_t dlogp, param_t
 //   v_exp_f32         1 ulp by the ISA; amc_selftest_accept_filter measures it exhaustively               < 5e-7
 //   spec exp vs exp   2 ulp f64                                                                            4e-16
 //   * (1 -+ eps)      one float rounding                                                                    6e-8
-// total < 3.1e-6; eps = 2^-16 = 1.5e-5 leaves a factor 5.  Outside the range: dlogp > 1e-12 -> arg > 0 -> accept;
-// dlogp < -17 -> the clamped estimate e^-17 is an upper bound only, and serves as one: its "lower bound minus one" is
-// negative, so it can never claim an accept.  dlogp >= 0 gives ex >= 1, whose upper bound 4096 (1 + eps) exceeds every
-// k, so it can never claim a reject.  NaN compares false everywhere -> undecided.
+// total < 3.1e-6; eps = 2^-16 = 1.5e-5 leaves a factor 5: lo1 + 1 <= exp(arg) 2^12 <= hi, so lo1 > k implies exp(arg) > (k+1) 2^-12
+// > u and hi < k implies exp(arg) < k 2^-12 <= u.
+//
+// dlogp > 0 (also +Inf).  accept_exact accepts whatever u is: fl(dlogp + logq) >= logq (rounding is monotone), so arg >= 0.  The
+// filter cannot claim a reject: t >= 0, y >= 0, ex >= 1 - 2^-23 (1 ulp below 2^y >= 1), hi >= 4096 (1 + 2^-16)(1 - 2^-23)(1 - 2^-24)
+// > 4095 >= k.  A claimed accept is right.  It claims one for every k <= 4094 (lo1 >= 4096 (1 - 2^-16)(1 - 2^-23) - 1 - 2^-12
+// > 4094.9); for k = 4095 only if ex (1 - eps) 4096 - 1 > 4095, i.e. dlogp above ~2.7e-4 (eps 4096 = 1/16 plus the roundings of
+// lo1, whose ulp is 2^-12 there).  So a chain-step with 0 < dlogp < 2.7e-4 and k = 4095 is left open where the sign test used to
+// settle it: at most 2^-12 = 2.4e-4 per chain-step if EVERY proposal were that small an uphill step (sigma -> 0; 3 % of
+// wave-steps of 128 chains then), and 2^-12 P(0 < dlogp < 2.7e-4) ~ 1e-7 at the benchmark's settings -- next to the 1.2e-4 below.
+//
+// dlogp < -17 (also -Inf).  Here ex needs no relative accuracy, only a bound: t <= -17, y <= RN(-17 log2e) < -24.5, so
+// ex <= 2^-24.5 (1 + 2^-23) < 4.3e-8 (denormal or zero far below; never negative).  lo1 <= 4096 * 4.3e-8 - 1 < 0 <= k: no accept is
+// claimed.  hi <= 4096 (1 + 2^-16) 4.3e-8 (1 + 2^-23) < 1.8e-4 < 1, and hi >= +0: a reject is claimed exactly for k >= 1, where
+// u >= 2^-12 = 2.4e-4, and accept_exact rejects there too: arg <= dlogp (1 - 2^-51) + 2^-53 * 268 < -16.99, so either arg < -708 (its
+// range test rejects) or exp(arg) (1 + 2^-51) < 4.2e-8 < u.  k = 0 stays open (hi < 0 never holds).
+//
+// NaN compares false everywhere -> undecided.
 // Undecided when u's cell touches the interval (~1.2e-4 per chain-step, ~1.5 % of wave-steps); then the whole wave
 // forms the accept draw and takes accept_exact.
 #define AMC_FILTER_EPS 0x1.0p-16f
-// The three primitive comparisons of one chain; the decision masks are formed from their ballots on the scalar unit
-// (a ballot of a COMPOUND bool goes through a 0/1 VGPR and a second compare).  The sign test uses the float t:
-// t > 2e-12 implies dlogp > 1e-12 with room to spare (t = RN(dlogp), relative 6e-8); a dlogp that underflows to
-// t = 0 simply is not settled by its sign.
+// The two primitive comparisons of one chain; the decision masks are formed from their ballots on the scalar unit
+// (a ballot of a COMPOUND bool goes through a 0/1 VGPR and a second compare).
 struct FilterCmp {
-    bool pos, lo, hi;
+    bool lo, hi;
 };
 
-__device__ __forceinline__ FilterCmp accept_filter(real_t dlogp, uint32_t k)
+// Both chains of a pair at once.  PACKED: the products and the fma on a two-element vector -- single IEEE Float32 operations
+// per element either way, one packed instruction for the pair (v_pk_mul_f32, v_pk_fma_f32) instead of two.  The K == 1 kernels
+// take that form; in the K > 1 kernels the packed operands (adjacent register pairs) cost 8-10 VGPRs and a wave per SIMD
+// (profiles/lean_sweep_isa.md), so they keep one operation per chain.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <bool PACKED>
+__device__ __forceinline__ void accept_filter_f32(float t0, float t1, uint32_t k0, uint32_t k1, FilterCmp& c0, FilterCmp& c1)
 {
-    const float t = (float)dlogp;
-    const float ex = __builtin_amdgcn_exp2f(__builtin_fmaxf(t, -17.0f) * 0x1.715476p+0f);
-    const float kf = (float)k;                                             // exact: k < 2^12
-    constexpr float SCALE = 4096.0f;
+    const float kf0 = (float)k0, kf1 = (float)k1;                          // exact: k < 2^12
+    constexpr float LOG2E = 0x1.715476p+0f, SCALE = 4096.0f;
     // lower / upper bound of exp(arg) 2^12, the lower one already minus 1: one rounding each (in the budget)
-    const float lo1 = __builtin_fmaf(ex, (1.0f - AMC_FILTER_EPS) * SCALE, -1.0f);
-    const float hi = ex * ((1.0f + AMC_FILTER_EPS) * SCALE);
-    FilterCmp c;
-    c.pos = t > 2e-12f;                 // arg > 0: accept whatever u is
-    c.lo = lo1 > kf;                    // exp(arg) > (k+1) 2^-12 > u   (never true below -17: lo1 < 0)
-    c.hi = hi < kf;                     // exp(arg) < k 2^-12 <= u      (never true for arg >= 0: hi > 4096)
-    return c;
+    constexpr float LO = (1.0f - AMC_FILTER_EPS) * SCALE, HI = (1.0f + AMC_FILTER_EPS) * SCALE;
+    f32x2 lo1, hi;
+    if (PACKED) {
+        const f32x2 y = f32x2{t0, t1} * LOG2E;
+        const f32x2 ex = {__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
+        lo1 = __builtin_elementwise_fma(ex, f32x2{LO, LO}, f32x2{-1.0f, -1.0f});
+        hi = ex * HI;
+    } else {
+        const float e0 = __builtin_amdgcn_exp2f(t0 * LOG2E), e1 = __builtin_amdgcn_exp2f(t1 * LOG2E);
+        lo1 = f32x2{__builtin_fmaf(e0, LO, -1.0f), __builtin_fmaf(e1, LO, -1.0f)};
+        hi = f32x2{e0 * HI, e1 * HI};
+    }
+    c0.lo = lo1.x > kf0;                // exp(arg) > (k+1) 2^-12 > u   (never true below -17: lo1 < 0)
+    c0.hi = hi.x < kf0;                 // exp(arg) < k 2^-12 <= u      (never true for arg >= 0: hi > 4095)
+    c1.lo = lo1.y > kf1;
+    c1.hi = hi.y < kf1;
+}
+
+template <bool PACKED>
+__device__ __forceinline__ void accept_filter(real_t dlogp0, real_t dlogp1, uint32_t k0, uint32_t k1, FilterCmp& c0, FilterCmp& c1)
+{
+    accept_filter_f32<PACKED>((float)dlogp0, (float)dlogp1, k0, k1, c0, c1);
 }
 
 // The same filter for a decision whose ARGUMENT is known in full -- the script-defined proposals below form arg = (dlogp + logq_b) -
 // logq_f in the reference's operations, nothing cancels -- : what the filter saves there is exp(arg) in Float64 and the accept draw
-// (a second Philox call per pair and step), for all but the ~1.5 % of wave-steps it leaves open.  pos is the exact comparison;
-// t = RN_f32(arg) moves the estimate's argument by at most 17 * 2^-24 = 1.0e-6, inside AMC_FILTER_EPS with the 3.1e-6 of the estimate
-// itself.  arg = NaN or -Inf: fmaxf returns -17, the filter rejects for k >= 1 -- as the exact form does (no comparison with a NaN
-// holds, and below -708 the exact form rejects) -- and leaves k = 0 open.
-__device__ __forceinline__ FilterCmp accept_filter_arg(double arg, uint32_t k)
+// (a second Philox call per pair and step), for all but the ~1.5 % of wave-steps it leaves open.  The three ranges above hold with
+// arg in the place of dlogp and no "arg vs dlogp" line: t = RN_f32(arg) moves the estimate's argument by at most 17 * 2^-24 = 1.0e-6
+// for -17 <= arg <= 0, inside AMC_FILTER_EPS with the 3.1e-6 of the estimate itself; arg > 0 -> t >= 0 -> no reject claimed, and the
+// exact form accepts; arg < -17 -> t <= -17 -> no accept claimed, a reject for k >= 1 only, as the exact form decides (below -708 and
+// for -Inf by its range test).  arg = NaN: nothing is claimed, and the exact form rejects (no comparison with a NaN holds).
+template <bool PACKED>
+__device__ __forceinline__ void accept_filter_arg(double arg0, double arg1, uint32_t k0, uint32_t k1, FilterCmp& c0, FilterCmp& c1)
 {
-    const float t = (float)arg;
-    const float ex = __builtin_amdgcn_exp2f(__builtin_fmaxf(t, -17.0f) * 0x1.715476p+0f);
-    const float kf = (float)k;
-    constexpr float SCALE = 4096.0f;
-    const float lo1 = __builtin_fmaf(ex, (1.0f - AMC_FILTER_EPS) * SCALE, -1.0f);
-    const float hi = ex * ((1.0f + AMC_FILTER_EPS) * SCALE);
-    FilterCmp c;
-    c.pos = arg >= 0.0;
-    c.lo = lo1 > kf;
-    c.hi = hi < kf;
-    return c;
+    accept_filter_f32<PACKED>((float)arg0, (float)arg1, k0, k1, c0, c1);
 }
 // the reference-ordered decision from arg and the full uniform: alpha = min(1, exp(arg)) > u (metropolis.jl:183-185)
 __device__ __forceinline__ bool accept_exact_arg(double arg, double u, const double* T)
@@ -784,11 +811,12 @@ __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t
 #endif
         // round 5: the 12-bit bracket of u settles these decisions too (accept_filter_arg); exp(arg) in Float64 and the accept draw
         // are formed by the waves in which some lane's bracket leaves its decision open, for all their lanes
-        const FilterCmp c0 = accept_filter_arg(s0.arg, a0_12), c1 = accept_filter_arg(s1.arg, a1_12);
-        const unsigned long long acc0 = __builtin_amdgcn_ballot_w64(c0.pos | c0.lo), rej0 = __builtin_amdgcn_ballot_w64(c0.hi);
-        const unsigned long long acc1 = __builtin_amdgcn_ballot_w64(c1.pos | c1.lo), rej1 = __builtin_amdgcn_ballot_w64(c1.hi);
+        FilterCmp c0, c1;
+        accept_filter_arg<!MULTI>(s0.arg, s1.arg, a0_12, a1_12, c0, c1);
+        const unsigned long long acc0 = __builtin_amdgcn_ballot_w64(c0.lo), rej0 = __builtin_amdgcn_ballot_w64(c0.hi);
+        const unsigned long long acc1 = __builtin_amdgcn_ballot_w64(c1.lo), rej1 = __builtin_amdgcn_ballot_w64(c1.hi);
         const unsigned long long undecided = __builtin_amdgcn_ballot_w64(true) & ~((acc0 | rej0) & (acc1 | rej1));
-        bool a0 = c0.pos | c0.lo, a1 = c1.pos | c1.lo;
+        bool a0 = c0.lo, a1 = c1.lo;
         if ((undecided | force_mask) != 0ull) {
             if (!have_pu) {
                 asm volatile("" : "+v"(accept_ctr.z));       // pins the second Philox call inside this arm (no speculation)
@@ -806,13 +834,29 @@ __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t
     }
 #endif
     const Proposal p0 = propose<POT>(xv.x, b0, sg0, z0, T), p1 = propose<POT>(xv.y, b1, sg1, z1, T);
-    const real_t xr0 = p0.xn + (-p0.delta), xr1 = p1.xn + (-p1.delta);
-    const FilterCmp c0 = accept_filter(p0.dlogp, a0_12), c1 = accept_filter(p1.dlogp, a1_12);
+    FilterCmp c0, c1;
+    accept_filter<!MULTI>(p0.dlogp, p1.dlogp, a0_12, a1_12, c0, c1);
 #define AMC_B(c) __builtin_amdgcn_ballot_w64(c)
-    const unsigned long long acc0 = AMC_B(c0.pos) | AMC_B(c0.lo), rej0 = AMC_B(c0.hi);
-    const unsigned long long acc1 = AMC_B(c1.pos) | AMC_B(c1.lo), rej1 = AMC_B(c1.hi);
+    const unsigned long long acc0 = AMC_B(c0.lo), rej0 = AMC_B(c0.hi);
+    const unsigned long long acc1 = AMC_B(c1.lo), rej1 = AMC_B(c1.hi);
     const unsigned long long undecided = AMC_B(true) & ~((acc0 | rej0) & (acc1 | rej1));
 #undef AMC_B
+    // The state after the decision: the proposed position, and where the step is rejected perform_action_cached!'s
+    // x = (x + d) + (-d), formed under the reject mask alone -- one add per chain in the lanes that keep its result (the masks
+    // live on the scalar unit) instead of the add in every lane and a two-word select.  The empty asm keeps the update a
+    // branch on the mask: without it the compiler turns it back into add + select.
+    auto settle = [&](bool r0, bool r1, bool a0, bool a1) {
+        if (MULTI) {                 // (K > 1: the select form; the masked one costs those kernels 6-8 VGPRs, see accept_filter_f32)
+            xv.x = r0 ? p0.xn + (-p0.delta) : p0.xn;
+            xv.y = r1 ? p1.xn + (-p1.delta) : p1.xn;
+        } else {
+            xv.x = p0.xn;
+            xv.y = p1.xn;
+            if (r0) { xv.x = p0.xn + (-p0.delta); asm volatile("" : "+v"(xv.x)); }
+            if (r1) { xv.y = p1.xn + (-p1.delta); asm volatile("" : "+v"(xv.y)); }
+        }
+        acc_bits = (a0 ? 1u : 0u) | (a1 ? 0x100u : 0u);
+    };
     if ((undecided | force_mask) != 0ull) {
         // the reference-ordered arithmetic decides (it agrees with the filter wherever the filter decided)
         if (!have_pu) {
@@ -829,16 +873,11 @@ __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t
         const bool a1 = accept_exact(p1.delta, p1.dlogp, e1.dn, e1.rd, e1.lc, uniform_accept(a1_12, pu.z, pu.w), T);
         m0 = __builtin_amdgcn_ballot_w64(a0);
         m1_out = __builtin_amdgcn_ballot_w64(a1);
-        xv.x = a0 ? p0.xn : xr0;
-        xv.y = a1 ? p1.xn : xr1;
-        acc_bits = (a0 ? 1u : 0u) | (a1 ? 0x100u : 0u);
+        settle(!a0, !a1, a0, a1);
     } else {
-        const bool a0 = c0.pos | c0.lo, a1 = c1.pos | c1.lo;
         m0 = acc0;
         m1_out = acc1;
-        xv.x = a0 ? p0.xn : xr0;
-        xv.y = a1 ? p1.xn : xr1;
-        acc_bits = (a0 ? 1u : 0u) | (a1 ? 0x100u : 0u);
+        settle(c0.hi, c1.hi, c0.lo, c1.lo);       // every lane is decided here: not accepted is the reject claim itself
     }
 }
 

@@ -343,7 +343,7 @@ static int pg_launch(amc_handle* h, const char* who, int n_learn, const int* lea
     const int grid = plan.grid;
     const bool mid = plan.mid;
     if (grid_out) *grid_out = grid;
-    amc::SweepArgs sw = make_sweep_args(h, 1);
+    amc::SweepArgs sw = make_sweep_args(h, 1, 0);      // (no sweep_kernel launch: the estimator has its own loop)
     sw.red_stride = red_row_stride(h, grid);
     const int rc = h->use_rtc                                    ? launch_pg_custom(h, a, sw, grid, nl, sweep, red, mid)
                    : (h->potential == AMC_POTENTIAL_DOUBLE_WELL) ? launch_pg<amc::POT_DOUBLE_WELL>(h, a, sw, grid, nl, sweep, red, mid)

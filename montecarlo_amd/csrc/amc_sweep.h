@@ -31,6 +31,11 @@ struct SweepArgs {
     int32_t log_pos;              // row of the step log the first step of this launch writes
     int32_t exact_accept;         // != 0: skip the accept filter, every decision by accept_exact (tests; AMC_EXACT_ACCEPT)
     int32_t n_slots;              // length of acc_total (launches of different grids share it)
+    // sweep_kernel's trip count, from the host (the grid is its choice; make_sweep_args fills both from it): with R = grid *
+    // AMC_BLOCK pairs per round of the grid, every block takes n_pairs / R whole rounds and the blocks whose first pair lies below
+    // n_pairs % R one more.  The kernel trusts them: they must agree with n_chains and the launch's grid.
+    int32_t full_rounds;
+    int32_t tail_pairs;
 };
 
 // The Philox result every MH step of a pair needs -- its normal draw: a pure function of (seed, pair, step), so it can
@@ -43,7 +48,8 @@ struct StepDraws {
 __device__ __forceinline__ StepDraws step_draws(const SweepArgs& a, uint64_t pair, uint64_t t)
 {
     StepDraws d;
-    d.normal = philox4x32_10(draw_counter(pair, t, DRAW_NORMAL, STREAM_METROPOLIS), a.key0, a.key1);
+    // t is the launch's step: wave-uniform, as the form asks for
+    d.normal = philox4x32_10_uniform_xy(draw_counter(pair, t, DRAW_NORMAL, STREAM_METROPOLIS), a.key0, a.key1);
     return d;
 }
 
@@ -242,17 +248,27 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     // peeled.  Loads need no clamp either: the arrays carry AMC_PAD_DOUBLES of readable padding.
     auto load_x = [&](int64_t b) -> real2 { return load_pair_block(a.x + 2 * b); };
     auto load_b = [&](int64_t b) -> real2 { return load_pair_block(a.beta_arr + 2 * b); };
+    // The loop's own condition stays on the scalar unit: the block's trips as a 32-bit count (a 64-bit signed compare of pair indices has
+    // no scalar form and costs the loop a v_mov_b64 + v_cmp_lt_i64 pair per test), the last one -- the only one that can be ragged -- peeled.
+    // (The first trip's "nothing to store yet" is still the test base_done >= 0, one v_cmp_lt_i64: as a 32-bit test of the
+    // trip count or as base != first it costs the K == 1 forms 2-3 VGPRs, and the per-chain-beta and REDUCE forms a wave per SIMD.)
+    const int trips = a.full_rounds + ((int)(blockIdx.x * AMC_BLOCK) < a.tail_pairs ? 1 : 0);
     real2 x_nxt = {(real_t)0.0, (real_t)0.0}, b_nxt = {(real_t)a.beta, (real_t)a.beta};
-    if (first < n_pairs) {
+    if (trips > 0) {
         x_nxt = load_x(first);
         if (BETA) b_nxt = load_b(first);
     }
+    // The lane's global pair id runs along with the trips: one 64-bit add of the (uniform) stride per trip.
+    // (Opaque to the compiler: left to see that pair - threadIdx.x - pair0 is the block's base, its loop strength reduction forms
+    // the id from the base again in every trip -- the second 64-bit add this variable is there to save.)
+    uint64_t pair = a.pair0 + (uint64_t)(first + threadIdx.x);
+    asm volatile("" : "+v"(pair));
     // SINGLE: the Philox draws of an iteration are formed one iteration ahead -- those of the first iteration
     // right here, while the first load and the table loads are in flight (the arithmetic of ~80 VALU
     // instructions per wave would otherwise start only after both have landed).
     constexpr bool AHEAD = SINGLE;
     StepDraws dr_nxt = {};
-    if (AHEAD && first < n_pairs) dr_nxt = step_draws(a, a.pair0 + (uint64_t)(first + threadIdx.x), a.t0);
+    if (AHEAD && trips > 0) dr_nxt = step_draws(a, pair, a.t0);
 #ifdef AMC_USER_LOGQ
     stage_user_theta(a.ptab, MULTI);
 #endif
@@ -265,8 +281,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     uint32_t lw_done = 0;
     int64_t base_done = -1;                                  // block-uniform
     int64_t base = first;
-    for (; base + stride < n_pairs; base += stride) {        // full iterations
-        const int64_t p = base + threadIdx.x;
+    for (int full = trips - 1; full > 0; --full, base += stride) {        // full iterations
         real2 xv = x_nxt;
         const real_t b0 = b_nxt.x, b1 = b_nxt.y;
         x_nxt = load_x(base + stride);
@@ -277,10 +292,11 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
         }
         const StepDraws dr = dr_nxt;
         uint32_t lw = 0;
-        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD>(a, xv, b0, b1, a.pair0 + (uint64_t)p, p, true, true, s_tab, s_pick, s_math,
+        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD>(a, xv, b0, b1, pair, base + threadIdx.x, true, true, s_tab, s_pick, s_math,
                                                    sigma1, den1, rden1, logc1, wave_acc, lw, &dr, math_k_literal(), th1, s_mathf);
+        pair += (uint64_t)stride;
         // a successor exists (loop condition); lanes past the end of a ragged one form draws nobody uses
-        if (AHEAD) dr_nxt = step_draws(a, a.pair0 + (uint64_t)(p + stride), a.t0);
+        if (AHEAD) dr_nxt = step_draws(a, pair, a.t0);
         if (REDUCE) {
             red_add_pair<POT, RED_E>(red, xv, true, true, s_math, s_red[threadIdx.x >> 6], a.red_cols);
         }
@@ -288,7 +304,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
         lw_done = lw;
         base_done = base;
     }
-    if (base < n_pairs) {                                    // last, possibly ragged, iteration
+    if (trips > 0) {                                         // last, possibly ragged, iteration
         const int64_t p = base + threadIdx.x;
         const bool v0 = p < n_pairs;
         const bool v1 = v0 && (2 * p + 1 < a.n_chains);
@@ -298,7 +314,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
             if (LOG && SINGLE) store_log_pair<LOG>(a, a.log_pos, base_done + threadIdx.x, lw_done);
         }
         uint32_t lw = 0;
-        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD>(a, xv, b_nxt.x, b_nxt.y, a.pair0 + (uint64_t)(v0 ? p : 0), p, v0, v1,
+        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD>(a, xv, b_nxt.x, b_nxt.y, v0 ? pair : a.pair0, p, v0, v1,
                                                    s_tab, s_pick, s_math, sigma1, den1, rden1, logc1, wave_acc, lw, &dr_nxt, math_k_literal(), th1, s_mathf);
         // a lone last chain (odd n_chains) writes its whole pair (x and log): the odd slot is padding
         if (v0) {

@@ -49,7 +49,9 @@ static int launch_sweep_custom(amc_handle* h, amc::SweepArgs& a, int grid, bool 
     return rtc_launch(h, inst, grid, params);
 }
 
-amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps)
+// grid: the grid of the sweep_kernel launch the arguments are for (its trip count depends on it); 0: no such launch (the estimator
+// kernels take SweepArgs too and have loops of their own)
+amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps, int grid)
 {
     amc::SweepArgs a;
     a.x = h->d_x;
@@ -73,6 +75,12 @@ amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps)
     a.red_cols = h->red_cols;
     a.exact_accept = h->knobs.exact_accept ? 1 : 0;
     a.n_slots = h->n_slots;
+    a.full_rounds = a.tail_pairs = 0;
+    if (grid > 0) {
+        const int64_t n_pairs = (h->M + 1) / 2, round = (int64_t)grid * AMC_BLOCK;
+        a.full_rounds = (int32_t)(n_pairs / round);
+        a.tail_pairs = (int32_t)(n_pairs % round);
+    }
     return a;
 }
 
@@ -95,6 +103,8 @@ int sweep_impl(amc_handle* h, int64_t n_sweeps, bool fuse_reduce, int* grid_out)
     const int grid = fuse_reduce ? reduce_sweep_grid(h) : grid_for(h, (h->M + 1) / 2, remaining == 1 ? h->blocks_per_cu_single : 0);
     if (fuse_reduce && grid > h->n_slots) return fail(AMC_ERR_STATE, "sweep_impl: a grid of %d blocks has no rows to leave its callback sums in (%d)", grid, h->n_slots);
     if (grid_out) *grid_out = grid;
+    if (h->knobs.debug_plan)
+        std::fprintf(stderr, "[amc] sweep: %lld pairs in a grid of %d blocks, %lld pairs per round\n", (long long)((h->M + 1) / 2), grid, (long long)grid * AMC_BLOCK);
     while (remaining > 0) {
         int32_t chunk = remaining > (1 << 20) ? (1 << 20) : (int32_t)remaining;
         if (h->d_log) {      // per-chain counters: one log row per MH step; a full log is folded before it is reused
@@ -104,7 +114,7 @@ int sweep_impl(amc_handle* h, int64_t n_sweeps, bool fuse_reduce, int* grid_out)
             if (chunk > room) chunk = room;
         }
         { const int rc = counter_room(h, "amc_sweep", (uint64_t)chunk); if (rc != AMC_OK) return rc; }      // (may carry the counters: arrays restart at zero)
-        amc::SweepArgs a = make_sweep_args(h, chunk);
+        amc::SweepArgs a = make_sweep_args(h, chunk, grid);
         a.red_stride = red_row_stride(h, grid);
         const bool last = remaining == chunk;
         const bool reduce = fuse_reduce && last;

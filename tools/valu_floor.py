@@ -261,7 +261,8 @@ def main():
         details.extend(d)
     out.extend(details)
     text = "\n".join(out) + "\n"
-    note = os.path.join(ROOT, "profiles", "r03_valu_floor_verdict.md")
+    # the verdict written for rounds 3-6 belongs to their kernels; a later tag brings its own file or none
+    note = os.path.join(ROOT, "profiles", TAG + "_valu_floor_verdict.md" if TAG > "r06" else "r03_valu_floor_verdict.md")
     if os.path.exists(note):
         text += "\n" + open(note).read()
     open(os.path.join(ROOT, "profiles", TAG + "_valu_floor.md"), "w").write(text)
