@@ -45,6 +45,7 @@ extern "C" {
 #define AMC_MAX_MOVES 64        /* K: moves in a pool (Move, metropolis.jl:140-147) */
 #define AMC_MAX_LEARN 8         /* learnable moves per estimator call */
 #define AMC_MAX_QBATCH 256      /* q_batch_size * n_learn must stay < 4096 (12-bit draw id) */
+#define AMC_MAX_RUNGS 64        /* R: rungs of a temperature ladder (amc_set_ladder) */
 
 typedef enum amc_status {
     AMC_OK = 0,
@@ -337,6 +338,37 @@ int  amc_sweep(amc_handle *h, int64_t n_sweeps);
  * benchmark's definition of a step; src/simulation.jl:184-191 calls make_step! once per t).  Identical to n calls of
  * amc_sweep(h, 1), minus n - 1 crossings of the language boundary. */
 int  amc_sweep_launches(amc_handle *h, int64_t n_launches);
+/* Replica exchange (parallel tempering) along a temperature ladder -- an EXTENSION: the reference has no such algorithm of its own,
+ * a user writes it as an AriannaAlgorithm whose make_step! walks simulation.chains (the plugin protocol, src/algorithms.jl:6-37);
+ * here the chains live on the device, so the engine provides the cross-chain move.
+ * amc_set_ladder(h, R), 2 <= R <= AMC_MAX_RUNGS: ladder l is the R consecutive GLOBAL chain ids [l R, (l + 1) R), the rung of chain c is
+ * c mod R, its beta whatever the per-chain beta array holds (typically beta[c] = ladder[c mod R]).  Needs a per-chain beta array
+ * (amc_upload_state with beta: AMC_ERR_STATE otherwise) and n_chains_global, chain_offset, n_chains all multiples of R -- no ladder
+ * straddles a shard -- (AMC_ERR_BAD_ARG naming the number).  R may be odd.  R = 0 clears the ladder.  Setting a ladder zeroes the gap
+ * counters (the gaps of another ladder are other gaps); amc_upload_state leaves them alone, like the Move counters.  The exchange step
+ * index t_x is a property of the HANDLE, not of the ladder: it starts at 0 at creation and survives clearing and re-setting the ladder,
+ * so the parity and the draws of the next exchange step continue where the last one stopped (amc_set_exchange_step changes it).
+ * A handle without a ladder behaves as it always did.
+ * Exchange step n (n = the exchange step index t_x, a counter of its own beside amc_get_step / amc_get_estimator_step): in every ladder
+ * the gaps r -- chains a = l R + r and b = a + 1 -- with r mod 2 == n mod 2 and r + 1 < R are attempted,
+ *     delta = (((-e_b) beta_a) + ((-e_a) beta_b)) - (((-e_a) beta_a) + ((-e_b) beta_b)),   e = potential(x)   (particle_1d.jl:20-22)
+ *     accept iff min(1, exp(delta)) > u  (strict; NaN rejects),  u = rand(Float64) of draw (id = global id of chain a, t = n, draw 0, stream 3)
+ * and an accepted swap exchanges x_a and x_b; beta, the Move counters and the step log stay with the rung.  Float32 state: e, beta and
+ * delta are Float32, exp and u Float64.  amc_exchange leaves the MH step index, the estimator step index and every Move counter alone.
+ * All asynchronous on the handle's stream except where a result comes back. */
+int  amc_set_ladder(amc_handle *h, int n_rungs);
+int  amc_exchange(amc_handle *h, int64_t n_steps);
+/* n_rounds x [ amc_sweep(h, sweeps_per_round); amc_exchange(h, 1) ] queued by one host call; identical to the separate calls. */
+int  amc_sweep_exchange(amc_handle *h, int64_t n_rounds, int64_t sweeps_per_round);
+/* Per gap r in [0, R - 1): swaps accepted / attempted over the local ladders since the ladder was set (or what
+ * amc_set_exchange_counters restored): exact integers, add across shards.  Synchronises. */
+int  amc_exchange_counters(amc_handle *h, int64_t *accepted, int64_t *attempted);
+int  amc_set_exchange_counters(amc_handle *h, const int64_t *accepted, const int64_t *attempted);
+int  amc_get_exchange_step(amc_handle *h, uint64_t *t);
+int  amc_set_exchange_step(amc_handle *h, uint64_t t);
+/* amc_histogram by rung: counts[r * (n_bins + 3) + i], r < R, layout of a row as amc_histogram's.  Local shard only (sum across shards). */
+int  amc_histogram_rungs(amc_handle *h, double lo, double hi, int n_bins, uint64_t *counts);
+
 /* MH steps done per chain so far (the Philox step index); settable for resume. */
 int  amc_get_step(amc_handle *h, uint64_t *t);
 int  amc_set_step(amc_handle *h, uint64_t t);

@@ -154,6 +154,14 @@ def load() -> C.CDLL:
         "amc_set_reduce_columns": (C.c_int, [H, C.c_int]),
         "amc_parameters_end_all": (C.c_int, [H, dp, C.c_int]),
         "amc_selftest_wave_totals": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "amc_set_ladder": (C.c_int, [H, C.c_int]),
+        "amc_exchange": (C.c_int, [H, C.c_int64]),
+        "amc_sweep_exchange": (C.c_int, [H, C.c_int64, C.c_int64]),
+        "amc_exchange_counters": (C.c_int, [H, i64p, i64p]),
+        "amc_set_exchange_counters": (C.c_int, [H, i64p, i64p]),
+        "amc_get_exchange_step": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "amc_set_exchange_step": (C.c_int, [H, C.c_uint64]),
+        "amc_histogram_rungs": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -613,6 +621,56 @@ class HipEngine:
         ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
         a = np.ascontiguousarray(rows, dtype=np.float64).reshape(n, self.gd_stride)
         _check(self._lib.amc_pg_set_accumulated(self._h, n, ids, _dptr(a)))
+
+    # -- replica exchange along a temperature ladder (include/amc.h) ----------------
+    def set_ladder(self, n_rungs: int) -> None:
+        """Ladders of ``n_rungs`` consecutive global chain ids (0: none).  Needs a per-chain beta array and a shard made of whole
+        ladders; zeroes the gap counters."""
+        _check(self._lib.amc_set_ladder(self._h, int(n_rungs)))
+        self.n_rungs = int(n_rungs)
+
+    def exchange(self, n_steps: int = 1) -> None:
+        """n exchange steps (asynchronous); the parity of the gaps alternates with the exchange step index."""
+        _check(self._lib.amc_exchange(self._h, int(n_steps)))
+
+    def sweep_exchange(self, n_rounds: int, sweeps_per_round: int = 1) -> None:
+        """n_rounds x [sweep(sweeps_per_round); exchange(1)] queued by one call."""
+        _check(self._lib.amc_sweep_exchange(self._h, int(n_rounds), int(sweeps_per_round)))
+
+    def exchange_counters(self):
+        """(accepted, attempted), one entry per gap r < R - 1: exact counts over this shard's ladders."""
+        n = max(int(getattr(self, "n_rungs", 0)) - 1, 1)
+        acc = np.zeros(n, dtype=np.int64)
+        att = np.zeros(n, dtype=np.int64)
+        p = C.POINTER(C.c_int64)
+        _check(self._lib.amc_exchange_counters(self._h, acc.ctypes.data_as(p), att.ctypes.data_as(p)))
+        return acc, att
+
+    def set_exchange_counters(self, accepted, attempted) -> None:
+        n = max(int(getattr(self, "n_rungs", 0)) - 1, 1)
+        acc = np.ascontiguousarray(accepted, dtype=np.int64).reshape(-1)
+        att = np.ascontiguousarray(attempted, dtype=np.int64).reshape(-1)
+        if acc.size != n or att.size != n:
+            raise AmcError(f"set_exchange_counters: one entry per gap ({n}) each")
+        p = C.POINTER(C.c_int64)
+        _check(self._lib.amc_set_exchange_counters(self._h, acc.ctypes.data_as(p), att.ctypes.data_as(p)))
+
+    @property
+    def exchange_step(self) -> int:
+        t = C.c_uint64(0)
+        _check(self._lib.amc_get_exchange_step(self._h, C.byref(t)))
+        return t.value
+
+    @exchange_step.setter
+    def exchange_step(self, t: int) -> None:
+        _check(self._lib.amc_set_exchange_step(self._h, int(t)))
+
+    def histogram_rungs(self, lo: float, hi: float, n_bins: int) -> np.ndarray:
+        """counts[R][n_bins + 3]: histogram() by rung (this shard only)."""
+        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        out = np.zeros((n, int(n_bins) + 3), dtype=np.uint64)
+        _check(self._lib.amc_histogram_rungs(self._h, float(lo), float(hi), int(n_bins), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
 
     def sync(self) -> None:
         _check(self._lib.amc_sync(self._h))

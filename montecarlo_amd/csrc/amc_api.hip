@@ -542,6 +542,7 @@ int amc_destroy(amc_handle* h)
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);
     (void)hipFree(h->d_hist);
+    (void)hipFree(h->d_xcnt);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

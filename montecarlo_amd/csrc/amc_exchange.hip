@@ -1,0 +1,162 @@
+// amc_exchange.hip -- replica exchange along a temperature ladder: the ladder of a handle, exchange steps
+// (amc_exchange, amc_sweep_exchange), the per-gap counters and the exchange step index.  amc_histogram_rungs is with the other
+// histograms in amc_state.hip.
+#define AMC_KERNEL_LINKAGE static      // this object launches template instantiations only
+#include "amc_internal.h"
+
+// AMC_MAX_RUNGS has two definitions, include/amc.h's (the ABI) and amc_exchange.h's (the kernel sources, which the run-time compiler
+// builds without amc.h); the kernel's LDS counters and the layout of d_xcnt need them equal.  This unit sees both: a later definition
+// with another value is a redefinition error, and the value the kernel was written for is pinned here.
+static_assert(AMC_MAX_RUNGS == 64 && sizeof(((amc::ExchangeArgs*)nullptr)->counts[0]) == 8, "AMC_MAX_RUNGS of include/amc.h and amc_exchange.h");
+
+// Every block ends with one 64-bit atomic per touched gap on the SAME few addresses, and those serialise (~13 ns each per address,
+// amc_state.hip hist_grid): with the sweeps' 8 blocks per CU that tail is as long as the pass over the chains.  10^7 chains, R = 8, even /
+// odd step: 48.4 / 47.7 us with 8 blocks per CU, 42.4 / 45.8 with 4, 38.7 / 43.1 with 2 (profiles/exchange.md).  AMC_BLOCKS_PER_CU overrides.
+static const int EXCHANGE_BLOCKS_PER_CU = 2;
+
+static const size_t XCNT_BYTES = 2 * AMC_MAX_RUNGS * sizeof(unsigned long long);   // d_xcnt: attempted[AMC_MAX_RUNGS], accepted[AMC_MAX_RUNGS]
+
+// One exchange step on the stream: the gaps r with r mod 2 == t_x mod 2 of every local ladder.  A parity without gaps (R = 2, odd
+// steps) launches nothing and still counts as a step.
+static int exchange_step(amc_handle* h)
+{
+    // (what a sweep does before it launches: a learning step left pending by a fused time step is taken now -- it belongs in front
+    // of this point of the stream; reductions in flight were queued on the same stream and have read x before this launch writes it)
+    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    if (h->t_x >> 48) return fail(AMC_ERR_STATE, "amc_exchange: the exchange step index has reached 2^48");
+    const int parity = (int)(h->t_x & 1u);
+    const int n_gaps = (h->n_rungs - parity) / 2;
+    if (n_gaps > 0) {
+        amc::ExchangeArgs a;
+        a.x = h->d_x;
+        a.beta = h->d_beta;
+        a.counts = h->d_xcnt;
+        a.n_ladders = h->M / h->n_rungs;
+        a.chain0 = (uint64_t)h->offset;
+        a.t_x = h->t_x;
+        a.n_rungs = h->n_rungs;
+        a.n_gaps = n_gaps;
+        a.key0 = (uint32_t)h->seed;
+        a.key1 = (uint32_t)(h->seed >> 32);
+        const int grid = grid_for(h, a.n_ladders * n_gaps, h->knobs.blocks_per_cu ? 0 : EXCHANGE_BLOCKS_PER_CU);
+        if (h->use_rtc) {
+            void* params[] = {&a};
+            const int rc = rtc_launch(h, "amc::exchange_kernel<" + std::to_string(h->potential) + ">", grid, params);
+            if (rc != AMC_OK) return rc;
+        } else {
+            if (h->potential == AMC_POTENTIAL_DOUBLE_WELL)
+                hipLaunchKernelGGL((amc::exchange_kernel<amc::POT_DOUBLE_WELL>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
+            else
+                hipLaunchKernelGGL((amc::exchange_kernel<amc::POT_HARMONIC>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
+            AMC_HIP(hipGetLastError());
+        }
+    }
+    h->t_x += 1;
+    return AMC_OK;
+}
+
+extern "C" {
+
+int amc_set_ladder(amc_handle* h, int n_rungs)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: NULL handle");
+    if (n_rungs == 0) { h->n_rungs = 0; return AMC_OK; }
+    if (n_rungs < 2 || n_rungs > AMC_MAX_RUNGS)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: n_rungs = %d must be 0 (no ladder) or in [2, %d]", n_rungs, AMC_MAX_RUNGS);
+    if (!h->beta_arr)
+        return fail(AMC_ERR_STATE, "amc_set_ladder: a ladder of %d rungs needs a per-chain beta array (amc_upload_state with beta)", n_rungs);
+    if (h->M_global % n_rungs)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: n_chains_global = %lld is no multiple of n_rungs = %d", (long long)h->M_global, n_rungs);
+    if (h->offset % n_rungs)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: chain_offset = %lld is no multiple of n_rungs = %d (no ladder may straddle a shard)",
+                    (long long)h->offset, n_rungs);
+    if (h->M % n_rungs)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: n_chains = %lld is no multiple of n_rungs = %d (no ladder may straddle a shard)",
+                    (long long)h->M, n_rungs);
+    AMC_HIP(hipSetDevice(h->device));
+    if (!h->d_xcnt) AMC_HIP(hipMalloc(&h->d_xcnt, XCNT_BYTES));
+    AMC_HIP(hipMemsetAsync(h->d_xcnt, 0, XCNT_BYTES, h->stream));      // the gaps of another ladder are other gaps
+    h->n_rungs = n_rungs;
+    return AMC_OK;
+}
+
+int amc_exchange(amc_handle* h, int64_t n_steps)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_exchange: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_exchange: the handle has no ladder (amc_set_ladder)");
+    if (n_steps < 0) return fail(AMC_ERR_BAD_ARG, "amc_exchange: n_steps < 0");
+    AMC_HIP(hipSetDevice(h->device));
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const int rc = exchange_step(h);
+        if (rc != AMC_OK) return rc;
+    }
+    return AMC_OK;
+}
+
+int amc_sweep_exchange(amc_handle* h, int64_t n_rounds, int64_t sweeps_per_round)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_sweep_exchange: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_sweep_exchange: the handle has no ladder (amc_set_ladder)");
+    if (n_rounds < 0 || sweeps_per_round < 0) return fail(AMC_ERR_BAD_ARG, "amc_sweep_exchange: n_rounds < 0 or sweeps_per_round < 0");
+    AMC_HIP(hipSetDevice(h->device));
+    for (int64_t i = 0; i < n_rounds; ++i) {
+        if (sweeps_per_round > 0) {
+            const int rc = sweep_impl(h, sweeps_per_round, false, nullptr);
+            if (rc != AMC_OK) return rc;
+        }
+        const int rc = exchange_step(h);
+        if (rc != AMC_OK) return rc;
+    }
+    return AMC_OK;
+}
+
+int amc_exchange_counters(amc_handle* h, int64_t* accepted, int64_t* attempted)
+{
+    if (!h || !accepted || !attempted) return fail(AMC_ERR_BAD_ARG, "amc_exchange_counters: NULL argument");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_exchange_counters: the handle has no ladder (amc_set_ladder)");
+    AMC_HIP(hipSetDevice(h->device));
+    unsigned long long host[2 * AMC_MAX_RUNGS];
+    AMC_HIP(hipMemcpyAsync(host, h->d_xcnt, XCNT_BYTES, hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    for (int r = 0; r + 1 < h->n_rungs; ++r) {
+        attempted[r] = (int64_t)host[r];
+        accepted[r] = (int64_t)host[AMC_MAX_RUNGS + r];
+    }
+    return AMC_OK;
+}
+
+int amc_set_exchange_counters(amc_handle* h, const int64_t* accepted, const int64_t* attempted)
+{
+    if (!h || !accepted || !attempted) return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_counters: NULL argument");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_exchange_counters: the handle has no ladder (amc_set_ladder)");
+    unsigned long long host[2 * AMC_MAX_RUNGS] = {0};
+    for (int r = 0; r + 1 < h->n_rungs; ++r) {
+        if (accepted[r] < 0 || attempted[r] < accepted[r])
+            return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_counters: gap %d: need 0 <= accepted <= attempted", r);
+        host[r] = (unsigned long long)attempted[r];
+        host[AMC_MAX_RUNGS + r] = (unsigned long long)accepted[r];
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_HIP(hipMemcpyAsync(h->d_xcnt, host, XCNT_BYTES, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
+    return AMC_OK;
+}
+
+int amc_get_exchange_step(amc_handle* h, uint64_t* t)
+{
+    if (!h || !t) return fail(AMC_ERR_BAD_ARG, "amc_get_exchange_step: NULL argument");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_get_exchange_step: the handle has no ladder (amc_set_ladder)");
+    *t = h->t_x;
+    return AMC_OK;
+}
+
+int amc_set_exchange_step(amc_handle* h, uint64_t t)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_step: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_exchange_step: the handle has no ladder (amc_set_ladder)");
+    if (t >> 48) return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_step: step index must fit 48 bits");
+    h->t_x = t;
+    return AMC_OK;
+}
+
+}  // extern "C"

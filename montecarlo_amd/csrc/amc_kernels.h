@@ -20,6 +20,7 @@
 //   amc_pg_tail.h      estimator launch records, GradientData samples, accumulate / update kernels, pending learning steps
 //   amc_estimator.h    K3: pg_estimate_kernel (optionally fused with the sweep and the callback sums)
 //   amc_aux_kernels.h  histogram / energy / conversion kernels, parity-test hooks
+//   amc_exchange.h     replica exchange along a temperature ladder: exchange_kernel, the histogram by rung
 #pragma once
 
 #include "amc_model.h"
@@ -30,3 +31,4 @@
 #include "amc_pg_tail.h"
 #include "amc_estimator.h"
 #include "amc_aux_kernels.h"
+#include "amc_exchange.h"

@@ -1,5 +1,5 @@
 // amc_state.hip -- the ensemble's state: upload / download (Float32 state through a Float64 staging copy), the initial ensemble,
-// histograms, strided downloads, the step indices, the stream and the timing events.
+// histograms (pooled, running, by rung of a temperature ladder), strided downloads, the step indices, the stream and the timing events.
 #define AMC_KERNEL_LINKAGE static      // this object's own copies of the plain kernels it launches (initial ensemble, histograms, gathers)
 #include "amc_internal.h"
 
@@ -179,6 +179,32 @@ int amc_histogram(amc_handle* h, double lo, double hi, int n_bins, uint64_t* cou
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     (void)hipFree(d_counts);
     if (e != hipSuccess) return fail(AMC_ERR_HIP, "amc_histogram: %s", hipGetErrorString(e));
+    return AMC_OK;
+}
+
+int amc_histogram_rungs(amc_handle* h, double lo, double hi, int n_bins, uint64_t* counts)
+{
+    if (!h || !counts) return fail(AMC_ERR_BAD_ARG, "amc_histogram_rungs: NULL argument");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_histogram_rungs: the handle has no ladder (amc_set_ladder)");
+    if (n_bins < 1 || n_bins > 8192 || !(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi))
+        return fail(AMC_ERR_BAD_ARG, "amc_histogram_rungs: need 1 <= n_bins <= 8192 and finite lo < hi");
+    AMC_HIP(hipSetDevice(h->device));
+    const int cells = (n_bins + 3) * h->n_rungs;
+    unsigned long long* d_counts = nullptr;
+    const size_t bytes = (size_t)cells * sizeof(unsigned long long);
+    AMC_HIP(hipMalloc(&d_counts, bytes));
+    AMC_HIP(hipMemsetAsync(d_counts, 0, bytes, h->stream));
+    const double inv_w = (double)n_bins / (hi - lo);
+    const double* d_pos = nullptr;
+    { const int rc = positions_f64(h, &d_pos); if (rc != AMC_OK) { (void)hipFree(d_counts); return rc; } }
+    const int lds_rows = cells <= 12288 ? 1 : 0;      // 48 KiB of u32 counters; beyond that one global atomic per position
+    hipLaunchKernelGGL(amc::rung_histogram_kernel, dim3(hist_grid(h)), dim3(AMC_BLOCK), lds_rows ? (size_t)cells * sizeof(unsigned int) : 0,
+                       h->stream, d_pos, h->M, h->n_rungs, lo, hi, inv_w, n_bins, lds_rows, d_counts);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_counts);
+    if (e != hipSuccess) return fail(AMC_ERR_HIP, "amc_histogram_rungs: %s", hipGetErrorString(e));
     return AMC_OK;
 }
 

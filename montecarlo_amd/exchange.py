@@ -1,0 +1,99 @@
+"""``ReplicaExchange``: parallel tempering along a temperature ladder, on the device.
+
+An extension over the reference.  There a user who wants replica exchange writes an ``AriannaAlgorithm`` whose ``make_step!`` walks
+``simulation.chains`` and swaps neighbours (the plugin protocol, src/algorithms.jl:6-37, hands every algorithm the chains); here the
+chains live in HBM behind the C ABI, so the engine provides the cross-chain move (include/amc.h) and this
+algorithm schedules it like any other.
+
+Ladder l is the R consecutive global chain ids [l R, (l + 1) R); the rung of chain c is c mod R and its beta is whatever the per-chain
+beta array holds (``ParticleChains.ladder`` tiles a list of betas).  One exchange step attempts, in every ladder, the gaps of one
+parity; the parity alternates from step to step.  An accepted swap exchanges the POSITIONS of the two chains: beta, the Move counters
+and everything else indexed by chain stay with the rung, so ``x[r::R]`` is always the sample at beta_r.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import sharding
+from .metropolis import Metropolis
+from .simulation import AriannaAlgorithm, Simulation, _calls
+from .system import potential as _potential
+
+
+class ReplicaExchange(AriannaAlgorithm):
+    """ReplicaExchange(chains; dependencies=(Metropolis,), n_rungs=R): one exchange step of the Metropolis' engine per scheduled time.
+
+    Listed behind its Metropolis, a time step at which both are due is [sweep; exchange], and ``run(fuse=True)`` queues a stretch
+    of such rounds that nothing else observes with one engine call (``sweep_exchange``): the same launches, the same results."""
+
+    mutates_chains = True          # a callback due behind it at the same t observes the state AFTER the swaps (simulation._observed_next)
+
+    def __init__(self, chains, dependencies=None, n_rungs=None, path=None, **extras):
+        assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
+        self.metropolis: Metropolis = dependencies[0]
+        if n_rungs is None:
+            n_rungs = getattr(chains, "n_rungs", None)
+        if n_rungs is None:
+            raise ValueError("ReplicaExchange: n_rungs is missing (and the chains were not made by ParticleChains.ladder)")
+        self.n_rungs = int(n_rungs)
+        self.rank, _ = sharding.world()
+
+    def initialise(self, simulation: Simulation) -> None:
+        self.metropolis.set_ladder(self.n_rungs)       # (the per-chain beta array is on the device by now: Metropolis comes first)
+
+    def make_step(self, simulation: Simulation) -> None:
+        self.metropolis.engine.exchange(1)
+        self.metropolis.invalidate_reductions()
+
+    def make_rounds(self, simulation: Simulation, n_rounds: int, sweeps_per_round: int) -> None:
+        """n_rounds x [sweeps_per_round x make_step!(::Metropolis); make_step!(::ReplicaExchange)] as one engine call."""
+        self.metropolis.sweep_exchange(n_rounds, sweeps_per_round)
+
+    def acceptance(self) -> np.ndarray:
+        """Accepted / attempted swaps per gap over ALL shards, R - 1 ratios (0/0 = NaN before the first attempt)."""
+        acc, att = self.metropolis.engine.exchange_counters()
+        tot = sharding.allreduce_sum(np.concatenate([acc, att]).astype(np.float64), self.metropolis.engine)
+        n = self.n_rungs - 1
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return tot[:n] / tot[n:]
+
+    def write_algorithm(self, io, scheduler) -> None:
+        io.write("\tReplicaExchange\n")
+        io.write(f"\t\tCalls: {_calls(scheduler)}\n")
+        io.write(f"\t\tRungs: {self.n_rungs}\n")
+        io.write(f"\t\tLadders: {len(self.metropolis.chains) // self.n_rungs}\n")
+
+
+def _find_exchange(simulation: Simulation) -> ReplicaExchange:
+    found = [a for a in simulation.algorithms if isinstance(a, ReplicaExchange)]
+    if len(found) != 1:
+        raise ValueError(f"this callback needs exactly one ReplicaExchange in the algorithm list, found {len(found)}")
+    return found[0]
+
+
+def callback_exchange_acceptance(simulation: Simulation) -> np.ndarray:
+    """Per gap of the ladder, accepted / attempted swaps since the start: a vector of R - 1 ratios, NaN before the first attempt
+    (callback_acceptance's convention, src/metropolis.jl:319-321).  Reads the gap counters: the host waits for the queued steps."""
+    return _find_exchange(simulation).acceptance()
+
+
+def rung_energy(simulation: Simulation) -> np.ndarray:
+    """Mean energy per rung, a vector of R means over the ladders of all shards.  A HOST pass: one strided download per rung
+    (8 M bytes in all), potential(x) and a plain Float64 sum on the host -- not one of the engine's reproducible sums, so the last
+    bits may depend on the split into shards.  Built-in potentials only."""
+    rx = _find_exchange(simulation)
+    met, R = rx.metropolis, rx.n_rungs
+    start, stop = met.shard
+    count = (stop - start) // R
+    def energies(x):
+        if getattr(met.chains, "dtype", "f64") != "f32":
+            return _potential(met.chains.potential, x)
+        x32 = x.astype(np.float32)                      # Particle{Float32}.e: potential(x) in Float32
+        if met.chains.potential == "double_well":
+            q = x32 * x32 - np.float32(1.0)
+            return (q * q).astype(np.float64)
+        _potential(met.chains.potential, x[:0])         # (raises for a CustomPotential)
+        return (x32 * x32).astype(np.float64)
+    sums = np.array([float(np.sum(energies(met.engine.download_strided(r, R, count)))) for r in range(R)])
+    tot = sharding.allreduce_sum(np.concatenate([sums, [float(count)]]), met.engine)
+    return tot[:R] / tot[R]

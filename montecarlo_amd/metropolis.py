@@ -197,6 +197,31 @@ class Metropolis(AriannaAlgorithm):
         self.engine.sweep(n)
         self._epoch += 1
 
+    # ---- replica exchange (exchange.ReplicaExchange) ------------------------------------------
+    def set_ladder(self, n_rungs: int) -> None:
+        """Ladders of ``n_rungs`` consecutive global chains on the engine (amc_set_ladder).  No ladder may straddle a shard; the
+        shard splitter does not know about ladders, so a split that cuts one is an error here."""
+        R = int(n_rungs)
+        start, stop = self.shard
+        if R < 2 or len(self.chains) % R or start % R or stop % R:
+            raise ValueError(f"ReplicaExchange: ladders of R = {R} rungs do not tile this shard: chains [{start}, {stop}) of "
+                             f"{len(self.chains)} (R >= 2, and the ensemble size and both shard bounds must be multiples of R; "
+                             "choose the number of ladders so that shards split on ladders)")
+        if self.chains.beta_array is None:
+            raise ValueError("ReplicaExchange: the chains need a per-chain beta array (ParticleChains.ladder)")
+        if not hasattr(self.engine, "set_ladder"):
+            raise ValueError("ReplicaExchange: this engine has no exchange move (streams > 1 is not supported)")
+        if getattr(self, "n_rungs", 0) == R:
+            return                              # set already (storage.restore): setting it again would zero the gap counters
+        self.engine.set_ladder(R)
+        self.n_rungs = R
+
+    def sweep_exchange(self, n_rounds: int, sweeps_per_round: int) -> None:
+        """n_rounds x [sweeps_per_round make_step!s; one exchange step] queued by one engine call."""
+        self._drop_pending_reduction()
+        self.engine.sweep_exchange(n_rounds, sweeps_per_round)
+        self._epoch += 1
+
     def finalise(self, simulation: Simulation) -> None:
         self._drop_pending_reduction()
         self._settle_claimed()

@@ -261,6 +261,12 @@ def run(simulation: Simulation, fuse: bool = True) -> None:
             sim.t = t
             advance = 1
             due = [k for k in range(n_alg) if _due(sim, k) == t]
+            if fuse and due and getattr(sim.algorithms[due[0]], "fusable", False):
+                taken = _exchange_group(sim, due, t)          # time steps, not rounds
+                if taken:
+                    sim.t = t + taken - 1
+                    t += taken
+                    continue
             if fuse and len(due) == 1 and getattr(sim.algorithms[due[0]], "fusable", False):
                 k = due[0]
                 others = [d for j in range(n_alg) if j != k for d in [_due(sim, j)] if d is not None]
@@ -308,6 +314,37 @@ def run(simulation: Simulation, fuse: bool = True) -> None:
         for alg in sim.algorithms:                                                  # :196-198
             alg.finalise(sim)
         sim._finalise_summary()
+
+
+def _exchange_group(simulation: Simulation, due: Sequence[int], t: int) -> int:
+    """[fusable Metropolis every t, its ReplicaExchange every s] with nothing else due: the next rounds of (s sweeps, one exchange
+    step) go out as ONE engine call (ReplicaExchange.make_rounds).  ``due`` is [Metropolis] or [Metropolis, ReplicaExchange] at t.
+    The stretch ends the step before anything else is due.  Returns the time steps taken (0: the pattern does not apply)."""
+    sim = simulation
+    k = due[0]
+    met = sim.algorithms[k]
+    rx = [j for j in range(k + 1, len(sim.algorithms))
+          if hasattr(sim.algorithms[j], "make_rounds") and getattr(sim.algorithms[j], "metropolis", None) is met]
+    if len(rx) != 1 or list(due[1:]) not in ([], rx):
+        return 0
+    j = rx[0]
+    d0 = _due(sim, j)
+    if d0 is None:
+        return 0
+    others = [d for i in range(len(sim.algorithms)) if i not in (k, j) for d in [_due(sim, i)] if d is not None]
+    t_last = min(min(others, default=sim.steps + 1) - 1, sim.steps)
+    t_last = min(t_last, t + _consecutive(sim.schedulers[k], sim.counters[k], t, t_last) - 1)     # Metropolis at every step up to it
+    s = d0 - t + 1
+    sched, c = sim.schedulers[j], sim.counters[j]
+    n = 0
+    while c + n < len(sched) and sched[c + n] == d0 + n * s and sched[c + n] <= t_last:
+        n += 1
+    if n == 0 or n * s < 2:
+        return 0
+    sim.algorithms[j].make_rounds(sim, n, s)
+    sim.counters[k] += n * s
+    sim.counters[j] += n
+    return n * s
 
 
 def _pgmc_group(simulation: Simulation, due: Sequence[int], t: int):

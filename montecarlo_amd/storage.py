@@ -154,6 +154,9 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
         pass                                       # pool-wide counter mode: totals above are the state
     if metropolis.chains.beta_array is not None:
         data["beta"] = metropolis.chains.beta_array[start:stop]
+    if getattr(metropolis, "n_rungs", 0):           # a temperature ladder: the exchange step index and the gap counters are state
+        acc_x, att_x = eng.exchange_counters()
+        data.update(n_rungs=metropolis.n_rungs, exchange_step=eng.exchange_step, exchange_accepted=acc_x, exchange_attempted=att_x)
     if estimator is not None:
         data["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in estimator.gradients_data])
     os.makedirs(path, exist_ok=True)
@@ -183,6 +186,10 @@ def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
         eng.upload_counters(d["accepted"], d["total"])
     else:
         eng.set_counter_totals(int(d["accepted_total"][0]), int(d["total_total"][0]) // (stop - start))
+    if "n_rungs" in d:
+        metropolis.set_ladder(int(d["n_rungs"]))
+        eng.exchange_step = int(d["exchange_step"])
+        eng.set_exchange_counters(d["exchange_accepted"], d["exchange_attempted"])
     if estimator is not None and "gd" in d:
         from .policy_guided import GradientData
         estimator.gradients_data = [GradientData(float(r[0]), np.array([r[1]]), np.array([r[2]]), np.array([[r[3]]]), int(r[4]))

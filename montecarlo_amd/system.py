@@ -101,6 +101,19 @@ class ParticleChains(AriannaSystem):
                 dtype: str = "f64"):
         return cls(n_chains, beta, potential, init_uniform=(float(lo), float(hi)), reward=reward, dtype=dtype)
 
+    @classmethod
+    def ladder(cls, n_ladders: int, betas, potential="harmonic", x: Optional[np.ndarray] = None, init_uniform: Optional[tuple] = None,
+               reward: Optional[str] = None, dtype: str = "f64"):
+        """n_ladders temperature ladders of R = len(betas) rungs for ReplicaExchange: n_ladders * R chains, chain c at
+        beta = betas[c mod R] (ladder l is the consecutive chains [l R, (l + 1) R)).  ``n_rungs`` remembers R."""
+        betas = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        if betas.size < 2:
+            raise ValueError("ParticleChains.ladder: a ladder has at least two rungs")
+        chains = cls(int(n_ladders) * betas.size, np.tile(betas, int(n_ladders)), potential, x=x, init_uniform=init_uniform,
+                     reward=reward, dtype=dtype)
+        chains.n_rungs = int(betas.size)
+        return chains
+
     def __len__(self) -> int:
         return self.n_chains
 
