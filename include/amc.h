@@ -368,6 +368,16 @@ int  amc_get_exchange_step(amc_handle *h, uint64_t *t);
 int  amc_set_exchange_step(amc_handle *h, uint64_t t);
 /* amc_histogram by rung: counts[r * (n_bins + 3) + i], r < R, layout of a row as amc_histogram's.  Local shard only (sum across shards). */
 int  amc_histogram_rungs(amc_handle *h, double lo, double hi, int n_bins, uint64_t *counts);
+/* Per-rung reproducible sums ("Reproducible sums" below): for rung r and column c the kind-R sum over the
+ * local ladders l of ONE chain's summand, chain l R + r -- double(potential(x)) (the potential in the state type), double(x),
+ * fl(double(x) * double(x)).  The level of a sum is fixed by the largest summand of its own rung and column; NaN / +-Inf flag their own
+ * record.  Integer sums: independent of lanes, blocks, grid and shards -- the shards' records merged and rounded once are the bits of a
+ * single handle holding all ladders; every rung has n_chains / R local summands.
+ * records[(r * 3 + c) * AMC_XSUM_WORDS ...], r < R, c = 0 sum e, 1 sum x, 2 sum x^2 over the LOCAL ladders; columns: AMC_REDUCE_* bits,
+ * a column not asked for is an all-zero record.  Synchronises.  Merge across shards with amc_xsum_merge / amc_allreduce_xsum.
+ * Runs on the handle's stream behind whatever is queued; leaves the step indices, the step log, every counter and the reductions in
+ * flight alone.  AMC_ERR_STATE without a ladder; AMC_ERR_BAD_ARG for columns == 0 or bits outside AMC_REDUCE_ALL. */
+int  amc_reduce_rungs_exact(amc_handle *h, int columns, double *records);
 
 /* MH steps done per chain so far (the Philox step index); settable for resume. */
 int  amc_get_step(amc_handle *h, uint64_t *t);

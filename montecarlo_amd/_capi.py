@@ -20,6 +20,7 @@ AMC_MAX_LEARN = 8
 AMC_RED_HEADER = 4
 AMC_GD_STRIDE = 5
 AMC_XSUM_WORDS = 12      # doubles per record of a reproducible sum (include/amc.h)
+AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_REDUCE_ALL = 1, 2, 4, 7      # the sums over x a reduction forms (include/amc.h)
 
 POTENTIALS = {"harmonic": 0, "double_well": 1}
 AMC_POTENTIAL_CUSTOM = 2
@@ -162,6 +163,7 @@ def load() -> C.CDLL:
         "amc_get_exchange_step": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "amc_set_exchange_step": (C.c_int, [H, C.c_uint64]),
         "amc_histogram_rungs": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64)]),
+        "amc_reduce_rungs_exact": (C.c_int, [H, C.c_int, dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -670,6 +672,15 @@ class HipEngine:
         n = max(int(getattr(self, "n_rungs", 0)), 1)
         out = np.zeros((n, int(n_bins) + 3), dtype=np.uint64)
         _check(self._lib.amc_histogram_rungs(self._h, float(lo), float(hi), int(n_bins), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def reduce_rungs(self, columns: int = AMC_REDUCE_ALL) -> np.ndarray:
+        """records[R][3][AMC_XSUM_WORDS]: per rung the reproducible sums of e, x, x^2 over this shard's ladders, one chain per summand
+        (amc_reduce_rungs_exact); ``columns``: AMC_REDUCE_* bits, a column not asked for is an all-zero record.  What shards exchange
+        (sharding.allreduce_xsum); ``xsum_round`` yields the Float64s.  Observes the state behind everything queued; synchronises."""
+        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        out = np.zeros((n, 3, AMC_XSUM_WORDS), dtype=np.float64)
+        _check(self._lib.amc_reduce_rungs_exact(self._h, int(columns), _dptr(out)))
         return out
 
     def sync(self) -> None:

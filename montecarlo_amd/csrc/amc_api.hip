@@ -543,6 +543,8 @@ int amc_destroy(amc_handle* h)
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);
     (void)hipFree(h->d_hist);
     (void)hipFree(h->d_xcnt);
+    (void)hipFree(h->d_rung_rows);
+    (void)hipFree(h->d_rung_recs);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

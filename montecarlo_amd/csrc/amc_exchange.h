@@ -1,5 +1,6 @@
 // amc_exchange.h -- replica exchange along a temperature ladder: exchange_kernel, one step of neighbour
-// swaps inside every ladder of R consecutive chains, and rung_histogram_kernel, amc_histogram's binning resolved by rung.
+// swaps inside every ladder of R consecutive chains, rung_sums_kernel / rung_finish_kernel, the reproducible sums of e, x, x^2 resolved
+// by rung, and rung_histogram_kernel, amc_histogram's binning resolved by rung.
 // The reference has no such algorithm of its own: a user writes it as an AriannaAlgorithm whose make_step! walks simulation.chains
 // (the plugin protocol, src/algorithms.jl:6-37); with the chains in HBM the engine provides the cross-chain move.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
@@ -72,6 +73,139 @@ __global__ __launch_bounds__(AMC_BLOCK) void exchange_kernel(const ExchangeArgs 
     __syncthreads();
     if (threadIdx.x < 2 * AMC_MAX_RUNGS && s_cnt[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
+
+// ---- per-rung reproducible sums (amc_reduce_rungs_exact; DESIGN.md section 3.13 "Per-rung sums") ------------------------------------
+// S[r][c], c = sum e, sum x, sum x^2: the kind-R sum (amc_xsum.h) over the ladders l of ONE chain's summand, chain l R + r --
+// double(potential_T(x)), double(x), fl(double(x) double(x)) -- its level fixed by the largest summand of that rung and column alone.
+struct RungSumsArgs {
+    const real_t* x;              // [n_ladders * n_rungs] positions of the local shard
+    xs_word* rows;                // [gridDim.x][n_rungs][RED_COLS][XS_ROW_R]: this launch's block rows
+    int64_t l_begin, l_end;       // the ladders of this launch: at most XS_LANE_CAP - 2 trips per lane (the host splits beyond)
+    int32_t n_rungs;              // R
+    int32_t cols;                 // RED_WANT_* bits: columns nobody asked for are neither formed nor written
+};
+
+// One memory-bound pass, 8 B per chain (4 B for Float32 state).  Work items as in exchange_kernel: thread id = l0 R + r, a thread keeps
+// its rung for the whole launch and advances by (threads / R) ladders per trip, so neighbouring lanes read neighbouring chains and the
+// loop divides nothing; four loads are in flight per lane.  The lanes of a wave hold DIFFERENT rungs, so each lane keeps its own
+// running top (RLaneCols, amc_wave_sums.h) where the whole-ensemble sums keep a wave-uniform one.
+// End of block, per slot s = r RED_COLS + c in LDS: (1) the slot's top = max of its lanes' tops and the OR of their flags -- integer
+// max / or, order-free --, barrier; (2) the level is settled: every lane brings its two integers to it (part_r_raise: at the top k1, k2
+// add; one level below k1 adds to k2; further below nothing is left) and adds them with 64-bit integer LDS atomics, low 32 bits and
+// high parts apart (128 lanes x 2^62 do not fit 64 bits; k = hi 2^32 + lo), barrier; (3) the block stores its rows, consecutive words
+// by consecutive threads.  No floating-point atomic anywhere; rung_finish_kernel merges the blocks' rows (integers: any order).
+template <int POT>
+__device__ __forceinline__ void rung_add(RLaneCols<RED_COLS>& L, real_t x, const double* s_math, int cols)
+{
+    const double xd = (double)x;
+    if (cols & RED_WANT_E) rl_deposit(L, 0, (double)potential<POT>(x, s_math));
+    if (cols & RED_WANT_X) rl_deposit(L, 1, xd);
+    if (cols & RED_WANT_XX) rl_deposit(L, 2, xd * xd);
+    L.n += 1;
+}
+__device__ __forceinline__ void rung_lds_add(unsigned long long* lo_hi, long long k)
+{
+    if (k == 0) return;
+    atomicAdd(lo_hi, (unsigned long long)(k & 0xFFFFFFFFll));
+    atomicAdd(lo_hi + 1, (unsigned long long)(k >> 32));
+}
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void rung_sums_kernel(const RungSumsArgs a)
+{
+    constexpr int MAX_SLOTS = AMC_MAX_RUNGS * RED_COLS;
+    __shared__ double s_math[POT == POT_CUSTOM ? TAB_DOUBLES : 1];      // a custom potential may call amc_exp
+    __shared__ int s_top[MAX_SLOTS];
+    __shared__ unsigned int s_flags[MAX_SLOTS];
+    __shared__ unsigned long long s_k[MAX_SLOTS][4];                    // k1.lo, k1.hi, k2.lo, k2.hi (hi: two's complement)
+    const int n_slots = a.n_rungs * RED_COLS;
+    for (int s = threadIdx.x; s < n_slots; s += AMC_BLOCK) {
+        s_top[s] = xs::XS_LMIN;
+        s_flags[s] = 0u;
+        s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
+    }
+    if (POT == POT_CUSTOM) stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);        // (ends in a barrier)
+
+    const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
+    const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / a.n_rungs;
+    const int64_t l0 = tid / a.n_rungs;
+    const int r = (int)(tid - l0 * a.n_rungs);
+    RLaneCols<RED_COLS> L;
+    rl_init(L);
+    if (l0 < ladders_per_trip) {
+        const int64_t step = ladders_per_trip * a.n_rungs;        // chains per trip
+        const int64_t end = a.l_end * a.n_rungs;                  // chain l R + r lies below it exactly when l < l_end
+        int64_t i = (a.l_begin + l0) * a.n_rungs + r;
+        for (; i + 3 * step < end; i += 4 * step) {
+            const real_t x0 = a.x[i], x1 = a.x[i + step], x2 = a.x[i + 2 * step], x3 = a.x[i + 3 * step];
+            rung_add<POT>(L, x0, s_math, a.cols);
+            rung_add<POT>(L, x1, s_math, a.cols);
+            rung_add<POT>(L, x2, s_math, a.cols);
+            rung_add<POT>(L, x3, s_math, a.cols);
+        }
+        for (; i < end; i += step) rung_add<POT>(L, a.x[i], s_math, a.cols);
+    }
+    __syncthreads();                                              // the slots are cleared
+    const bool mine = L.n > 0;
+#pragma unroll
+    for (int c = 0; c < RED_COLS; ++c)
+        if (mine && ((a.cols >> c) & 1)) {
+            atomicMax(&s_top[r * RED_COLS + c], L.top[c]);
+            if (L.flags[c]) atomicOr(&s_flags[r * RED_COLS + c], L.flags[c]);
+        }
+    __syncthreads();                                              // the levels are settled
+#pragma unroll
+    for (int c = 0; c < RED_COLS; ++c)
+        if (mine && ((a.cols >> c) & 1)) {
+            const int s = r * RED_COLS + c;
+            long long k1, k2;
+            rl_multiples(L, c, k1, k2);
+            const int d = s_top[s] - L.top[c];
+            if (d == 0) {
+                rung_lds_add(&s_k[s][0], k1);
+                rung_lds_add(&s_k[s][2], k2);
+            } else if (d == 1) {
+                rung_lds_add(&s_k[s][2], k1);
+            }
+        }
+    __syncthreads();
+    xs_word* out = a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R;
+    for (int w = threadIdx.x; w < n_slots * XS_ROW_R; w += AMC_BLOCK) {
+        const int s = w / XS_ROW_R, j = w - s * XS_ROW_R;
+        if (!((a.cols >> (s % RED_COLS)) & 1)) continue;
+        xs_word v = 0ull;
+        if (j == 0) v = (xs_word)(uint32_t)s_top[s] | ((xs_word)s_flags[s] << 32);
+        else if (j < 5) {
+            const int which = (j - 1) >> 1;                       // k1 / k2
+            const xs::i128 k = xs::i128_add(xs::i128_shl(xs::i128_of((long long)s_k[s][2 * which + 1]), 32), xs::i128{(uint64_t)s_k[s][2 * which], 0});
+            v = ((j - 1) & 1) ? (xs_word)k.hi : (xs_word)k.lo;
+        }
+        out[w] = v;
+    }
+}
+
+// The records of the rung sums from the block rows of the launches: block s = r RED_COLS + c of 64 threads, lane i merges the rows
+// i, i + 64, ... (part_r_merge: integers, so the order is immaterial), thread 0 the lanes' partials, and leaves one record of
+// XS_WORDS doubles -- all zero for a column nobody asked for.
+#if AMC_PLAIN_KERNELS
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void rung_finish_kernel(const xs_word* rows, int n_rows, int n_rungs, int cols, double* recs)
+{
+    __shared__ xs::PartR s_part[64];
+    const int s = blockIdx.x, n_slots = n_rungs * RED_COLS;
+    double* rec = recs + (int64_t)s * xs::XS_WORDS;
+    if (!((cols >> (s % RED_COLS)) & 1)) {
+        if (threadIdx.x < xs::XS_WORDS) rec[threadIdx.x] = 0.0;
+        return;
+    }
+    xs::PartR p = xs::part_r_empty();
+    for (int b = threadIdx.x; b < n_rows; b += 64) xs::part_r_merge(p, xs_load_r_row(rows + ((int64_t)b * n_slots + s) * XS_ROW_R));
+    s_part[threadIdx.x] = p;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
+        xs::rec_from_r(rec, p);
+    }
+}
+#endif
 
 // amc_histogram's binning (histogram_kernel) with a row per rung: counts[n_rungs][n_bins + 3], the rung of local chain c being
 // c mod n_rungs (the shard starts at a multiple of n_rungs).  Rows live in LDS while (n_bins + 3) n_rungs counters fit

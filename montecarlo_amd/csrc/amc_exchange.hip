@@ -1,7 +1,7 @@
 // amc_exchange.hip -- replica exchange along a temperature ladder: the ladder of a handle, exchange steps
-// (amc_exchange, amc_sweep_exchange), the per-gap counters and the exchange step index.  amc_histogram_rungs is with the other
-// histograms in amc_state.hip.
-#define AMC_KERNEL_LINKAGE static      // this object launches template instantiations only
+// (amc_exchange, amc_sweep_exchange), the per-gap counters and the exchange step index, the per-rung reproducible sums
+// (amc_reduce_rungs_exact).  amc_histogram_rungs is with the other histograms in amc_state.hip.
+#define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copy of the one plain kernel it launches (rung_finish_kernel)
 #include "amc_internal.h"
 
 // AMC_MAX_RUNGS has two definitions, include/amc.h's (the ABI) and amc_exchange.h's (the kernel sources, which the run-time compiler
@@ -13,6 +13,11 @@ static_assert(AMC_MAX_RUNGS == 64 && sizeof(((amc::ExchangeArgs*)nullptr)->count
 // amc_state.hip hist_grid): with the sweeps' 8 blocks per CU that tail is as long as the pass over the chains.  10^7 chains, R = 8, even /
 // odd step: 48.4 / 47.7 us with 8 blocks per CU, 42.4 / 45.8 with 4, 38.7 / 43.1 with 2 (profiles/exchange.md).  AMC_BLOCKS_PER_CU overrides.
 static const int EXCHANGE_BLOCKS_PER_CU = 2;
+
+// The rung sums end every block with its rows, R x 3 x 48 bytes of them, and rung_finish_kernel reads them all again: with the sweeps' 8
+// blocks per CU and R = 64 that is a quarter of the pass's own traffic.  Four loads in flight per lane keep the memory system busy
+// with fewer blocks.  AMC_BLOCKS_PER_CU overrides.
+static const int RUNG_SUMS_BLOCKS_PER_CU = 4;
 
 static const size_t XCNT_BYTES = 2 * AMC_MAX_RUNGS * sizeof(unsigned long long);   // d_xcnt: attempted[AMC_MAX_RUNGS], accepted[AMC_MAX_RUNGS]
 
@@ -139,6 +144,62 @@ int amc_set_exchange_counters(amc_handle* h, const int64_t* accepted, const int6
     AMC_HIP(hipSetDevice(h->device));
     AMC_HIP(hipMemcpyAsync(h->d_xcnt, host, XCNT_BYTES, hipMemcpyHostToDevice, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
+    return AMC_OK;
+}
+
+int amc_reduce_rungs_exact(amc_handle* h, int columns, double* records)
+{
+    if (!h || !records) return fail(AMC_ERR_BAD_ARG, "amc_reduce_rungs_exact: NULL argument");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_reduce_rungs_exact: the handle has no ladder (amc_set_ladder)");
+    if (columns <= 0 || (columns & ~AMC_REDUCE_ALL))
+        return fail(AMC_ERR_BAD_ARG, "amc_reduce_rungs_exact: columns = %d must be a non-empty combination of AMC_REDUCE_E / _X / _XX", columns);
+    AMC_HIP(hipSetDevice(h->device));
+    // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
+    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    const int R = h->n_rungs;
+    const int64_t n_ladders = h->M / R;
+    const int grid = grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU);
+    // a lane adds one summand per trip and column and holds XS_LANE_CAP of them (amc_xsum.h): ensembles beyond that many trips of the
+    // grid (2^28 chains and more) take several launches, each with block rows of its own
+    const int64_t per_launch = (((int64_t)grid * AMC_BLOCK) / R) * (amc::xs::XS_LANE_CAP - 2);
+    const int64_t n_launches = (n_ladders + per_launch - 1) / per_launch;
+    const size_t slot_words = (size_t)R * amc::RED_COLS * amc::XS_ROW_R;
+    const size_t need = (size_t)n_launches * (size_t)grid * slot_words;
+    if (need > h->rung_rows_words) {
+        AMC_HIP(hipStreamSynchronize(h->stream));               // (nothing queued reads the old rows after this call's predecessor returned)
+        (void)hipFree(h->d_rung_rows);
+        h->d_rung_rows = nullptr;
+        h->rung_rows_words = 0;
+        AMC_HIP(hipMalloc(&h->d_rung_rows, need * sizeof(amc::xs_word)));
+        h->rung_rows_words = need;
+    }
+    if (!h->d_rung_recs) AMC_HIP(hipMalloc(&h->d_rung_recs, (size_t)AMC_MAX_RUNGS * amc::RED_COLS * amc::xs::XS_WORDS * sizeof(double)));
+    for (int64_t i = 0; i < n_launches; ++i) {
+        amc::RungSumsArgs a;
+        a.x = h->d_x;
+        a.rows = h->d_rung_rows + (size_t)i * (size_t)grid * slot_words;
+        a.l_begin = i * per_launch;
+        a.l_end = std::min(n_ladders, (i + 1) * per_launch);
+        a.n_rungs = R;
+        a.cols = columns;
+        if (h->use_rtc) {
+            void* params[] = {&a};
+            const int rc = rtc_launch(h, "amc::rung_sums_kernel<" + std::to_string(h->potential) + ">", grid, params);
+            if (rc != AMC_OK) return rc;
+        } else {
+            if (h->potential == AMC_POTENTIAL_DOUBLE_WELL)
+                hipLaunchKernelGGL((amc::rung_sums_kernel<amc::POT_DOUBLE_WELL>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
+            else
+                hipLaunchKernelGGL((amc::rung_sums_kernel<amc::POT_HARMONIC>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
+            AMC_HIP(hipGetLastError());
+        }
+    }
+    const int n_slots = R * amc::RED_COLS;
+    hipLaunchKernelGGL(amc::rung_finish_kernel, dim3(n_slots), dim3(64), 0, h->stream, (const amc::xs_word*)h->d_rung_rows,
+                       (int)(n_launches * grid), R, columns, h->d_rung_recs);
+    AMC_HIP(hipGetLastError());
+    AMC_HIP(hipMemcpyAsync(records, h->d_rung_recs, (size_t)n_slots * amc::xs::XS_WORDS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
     return AMC_OK;
 }
 

@@ -5,7 +5,8 @@
 //   amc_state.hip       the ensemble's state: upload / download, histograms, step indices, stream, timing
 //   amc_counters.hip    the step log and the per-chain counters (fold, totals, 64-bit carry, upload / download)
 //   amc_sweeps.hip      sweep launches (amc_sweep*)
-//   amc_exchange.hip    replica exchange along a temperature ladder (amc_set_ladder, amc_exchange, amc_sweep_exchange, gap counters)
+//   amc_exchange.hip    replica exchange along a temperature ladder (amc_set_ladder, amc_exchange, amc_sweep_exchange, gap counters,
+//                       the per-rung reproducible sums: amc_reduce_rungs_exact)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -161,6 +162,9 @@ struct amc_handle {
     int n_rungs = 0;            // R of the temperature ladder (amc_set_ladder); 0: none
     uint64_t t_x = 0;           // exchange steps done (their own Philox step index; its parity picks the gaps)
     unsigned long long* d_xcnt = nullptr;   // [2][AMC_MAX_RUNGS] exchange attempts and accepted swaps per gap (allocated with the ladder)
+    amc::xs_word* d_rung_rows = nullptr;    // [launches * grid][n_rungs][RED_COLS][XS_ROW_R] block rows of the rung sums (amc_reduce_rungs_exact,
+    size_t rung_rows_words = 0;             //   allocated at its first use, grown when a call needs more); the words it holds
+    double* d_rung_recs = nullptr;          // [AMC_MAX_RUNGS][RED_COLS][XS_WORDS] their records (rung_finish_kernel)
     double* d_x = nullptr;
     double* d_beta = nullptr;
     uint32_t* d_acc = nullptr;

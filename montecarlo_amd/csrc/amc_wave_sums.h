@@ -455,6 +455,75 @@ __device__ __forceinline__ void r_flush(RLanes<NC>& L, xs::PartR* slot)
     }
 }
 
+// Kind R with the top PER LANE (rung_sums_kernel, amc_exchange.h): the lanes of a wave hold different rungs of a ladder, and a rung's
+// level is a function of that rung's summands alone -- a wave-uniform top would let a large value of one rung coarsen the quantum of
+// its neighbours.  top[] and flags[] live in vector registers; a1[] / a2[] are the sums of bit patterns of RLanes.  The arithmetic of a
+// deposit is r_deposit's (lsb1, c1 + v, the exact remainder, c2 + r), the raise r_slow's (one level up k1 becomes k2, further up
+// both are dropped), the flags r_slow_classify's; the rare arm is taken by the lanes that need it and by no other (it may diverge).
+// n: the summands on the books of EVERY column a caller deposits into -- one deposit per such column, then ++n (rl_deposit leaves
+// it alone) --, at most XS_LANE_CAP - 2 of them before rl_multiples: |k| < n 2^49 < 2^62.
+template <int NC>
+struct RLaneCols {
+    unsigned long long a1[NC], a2[NC];
+    int top[NC];
+    uint32_t flags[NC];
+    int n;
+};
+template <int NC>
+__device__ __forceinline__ void rl_init(RLaneCols<NC>& L)
+{
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        L.a1[c] = L.a2[c] = 0ull;
+        L.top[c] = xs::XS_LMIN;
+        L.flags[c] = 0u;
+    }
+    L.n = 0;
+}
+// the rare arm: this lane's value is one its top cannot take, or one that is not finite (or as good as: |v| >= 2^999)
+template <int NC>
+__device__ __forceinline__ void rl_slow(RLaneCols<NC>& L, int c, double& v)
+{
+    const uint64_t bits = (uint64_t)__double_as_longlong(v);
+    const int need = xs::xs_level_of(v);                   // > LMAX for infinities, NaN and finite |v| >= 2^999
+    if (need > xs::XS_LMAX) {
+        const bool nan = ((bits >> 52) & 0x7FFull) == 0x7FFull && (bits & 0xFFFFFFFFFFFFFull) != 0ull;
+        L.flags[c] |= nan ? xs::XS_F_NAN : ((bits >> 63) ? xs::XS_F_NINF : xs::XS_F_PINF);
+        v = 0.0;                                           // the flags carry it
+        return;
+    }
+    if (need > L.top[c]) {
+        const unsigned long long n = (unsigned long long)(unsigned)L.n;
+        const unsigned long long k1 = L.a1[c] - n * xs::xs_level_c_bits(L.top[c]);
+        const bool one_up = need - L.top[c] == 1;
+        L.top[c] = need;
+        L.a1[c] = n * xs::xs_level_c_bits(need);
+        L.a2[c] = (one_up ? k1 : 0ull) + n * xs::xs_level_c_bits(need - 1);
+    }
+}
+template <int NC>
+__device__ __forceinline__ void rl_deposit(RLaneCols<NC>& L, int c, double v)
+{
+    // |v| < 2^(50 top + 49) (NaN compares false: it takes the rare arm like infinities and finite values of 2^999 or more)
+    if (!(__builtin_fabs(v) < xs::xs_level_cap(L.top[c]))) rl_slow(L, c, v);
+    const double c1 = __longlong_as_double((long long)xs::xs_level_c_bits(L.top[c]));
+    const double c2 = __longlong_as_double((long long)xs::xs_level_c_bits(L.top[c] - 1));
+    const double v1 = __longlong_as_double(__double_as_longlong(v) | 1ll);
+    const double t = c1 + v1;
+    const double r = v1 - (t - c1);
+    const double t2 = c2 + __longlong_as_double(__double_as_longlong(r) | 1ll);
+    L.a1[c] += (unsigned long long)__double_as_longlong(t);
+    L.a2[c] += (unsigned long long)__double_as_longlong(t2);
+}
+// the lane's two integers of column c: the multiples of q_top and of q_(top - 1)
+template <int NC>
+__device__ __forceinline__ void rl_multiples(const RLaneCols<NC>& L, int c, long long& k1, long long& k2)
+{
+    const unsigned long long n = (unsigned long long)(unsigned)L.n;
+    k1 = (long long)(L.a1[c] - n * xs::xs_level_c_bits(L.top[c]));
+    k2 = (long long)(L.a2[c] - n * xs::xs_level_c_bits(L.top[c] - 1));
+}
+
 // The block's row of a kind-R / kind-Q column from its wave slots slots[wave][NC] (thread 0, after a barrier).
 template <int NC>
 __device__ __forceinline__ xs::PartR r_block_total(const xs::PartR (*slots)[NC], int c)

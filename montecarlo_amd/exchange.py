@@ -15,9 +15,16 @@ from __future__ import annotations
 import numpy as np
 
 from . import sharding
+from ._capi import (AMC_MAX_MOVES, AMC_RED_HEADER, AMC_REDUCE_ALL, AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_XSUM_WORDS,
+                    xsum_round)
 from .metropolis import Metropolis
 from .simulation import AriannaAlgorithm, Simulation, _calls
 from .system import potential as _potential
+
+
+# Records per all-reduce of rung_sums: amc_allreduce_xsum takes what the communicator's buffers hold, never less than the records of
+# one callback reduction (AMC_RED_HEADER + AMC_MAX_MOVES per rank, amc_comm_init); the 3 R records of a ladder reach 192.
+XSUM_CHUNK = AMC_RED_HEADER + AMC_MAX_MOVES
 
 
 class ReplicaExchange(AriannaAlgorithm):
@@ -57,6 +64,21 @@ class ReplicaExchange(AriannaAlgorithm):
         with np.errstate(invalid="ignore", divide="ignore"):
             return tot[:n] / tot[n:]
 
+    def rung_sums(self, columns: int = AMC_REDUCE_ALL) -> np.ndarray:
+        """Per rung the means of e, x and x^2 over the ladders of ALL shards: an array of shape (R, 3), column c = 0 <e>, 1 <x>,
+        2 <x^2> (NaN for a column ``columns``, AMC_REDUCE_* bits, does not name).  Reproducible sums formed on the device
+        (amc_reduce_rungs_exact): the shards' integer records are merged, rounded once and divided by the
+        global ladder count, so the bits do not depend on the split into shards.  The host waits for the queued steps."""
+        eng = self.metropolis.engine
+        rec = np.ascontiguousarray(eng.reduce_rungs(columns), dtype=np.float64).reshape(-1, AMC_XSUM_WORDS)
+        merged = np.concatenate([sharding.allreduce_xsum(rec[i:i + XSUM_CHUNK], eng).reshape(-1, AMC_XSUM_WORDS)
+                                 for i in range(0, rec.shape[0], XSUM_CHUNK)])
+        sums = xsum_round(merged).reshape(self.n_rungs, 3)
+        asked = np.array([bool(int(columns) & bit) for bit in (AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX)])
+        out = sums / float(len(self.metropolis.chains) // self.n_rungs)
+        out[:, ~asked] = np.nan
+        return out
+
     def write_algorithm(self, io, scheduler) -> None:
         io.write("\tReplicaExchange\n")
         io.write(f"\t\tCalls: {_calls(scheduler)}\n")
@@ -77,10 +99,23 @@ def callback_exchange_acceptance(simulation: Simulation) -> np.ndarray:
     return _find_exchange(simulation).acceptance()
 
 
+def callback_rung_energy(simulation: Simulation) -> np.ndarray:
+    """Mean energy per rung, a vector of R means over the ladders of all shards: reproducible sums formed on the device
+    (ReplicaExchange.rung_sums), the same bits on any number of shards.  Any potential, Float64 or Float32 state."""
+    return _find_exchange(simulation).rung_sums(AMC_REDUCE_E)[:, 0].copy()
+
+
+def callback_rung_moments(simulation: Simulation) -> np.ndarray:
+    """<x> and <x^2> per rung over the ladders of all shards, an array of shape (2, R): row 0 the means, row 1 the second moments
+    (ReplicaExchange.rung_sums)."""
+    return np.ascontiguousarray(_find_exchange(simulation).rung_sums(AMC_REDUCE_X | AMC_REDUCE_XX)[:, 1:].T)
+
+
 def rung_energy(simulation: Simulation) -> np.ndarray:
     """Mean energy per rung, a vector of R means over the ladders of all shards.  A HOST pass: one strided download per rung
     (8 M bytes in all), potential(x) and a plain Float64 sum on the host -- not one of the engine's reproducible sums, so the last
-    bits may depend on the split into shards.  Built-in potentials only."""
+    bits may depend on the split into shards.  Built-in potentials only.  (callback_rung_energy is the device-side, reproducible
+    form.)"""
     rx = _find_exchange(simulation)
     met, R = rx.metropolis, rx.n_rungs
     start, stop = met.shard
