@@ -90,8 +90,9 @@ struct RungSumsArgs {
 // loop divides nothing; four loads are in flight per lane.  The lanes of a wave hold DIFFERENT rungs, so each lane keeps its own
 // running top (RLaneCols, amc_wave_sums.h) where the whole-ensemble sums keep a wave-uniform one.
 // End of block, per slot s = r RED_COLS + c in LDS: (1) the slot's top = max of its lanes' tops and the OR of their flags -- integer
-// max / or, order-free --, barrier; (2) the level is settled: every lane brings its two integers to it (part_r_raise: at the top k1, k2
-// add; one level below k1 adds to k2; further below nothing is left) and adds them with 64-bit integer LDS atomics, low 32 bits and
+// max / or, order-free --, barrier; (2) the level is settled: every lane brings its two integers (xs_r_multiples) to
+// it (xs_r_settle's rule as the choice of the slot: at the top k1, k2 add; one level below k1 adds to k2; further below nothing is
+// left) and adds them with 64-bit integer LDS atomics, low 32 bits and
 // high parts apart (128 lanes x 2^62 do not fit 64 bits; k = hi 2^32 + lo), barrier; (3) the block stores its rows, consecutive words
 // by consecutive threads.  No floating-point atomic anywhere; rung_finish_kernel merges the blocks' rows (integers: any order).
 template <int POT>
@@ -157,14 +158,13 @@ __global__ __launch_bounds__(AMC_BLOCK) void rung_sums_kernel(const RungSumsArgs
     for (int c = 0; c < RED_COLS; ++c)
         if (mine && ((a.cols >> c) & 1)) {
             const int s = r * RED_COLS + c;
-            long long k1, k2;
-            rl_multiples(L, c, k1, k2);
+            xs::RPair k = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n, L.top[c]);
             const int d = s_top[s] - L.top[c];
             if (d == 0) {
-                rung_lds_add(&s_k[s][0], k1);
-                rung_lds_add(&s_k[s][2], k2);
+                rung_lds_add(&s_k[s][0], k.k1);
+                rung_lds_add(&s_k[s][2], k.k2);
             } else if (d == 1) {
-                rung_lds_add(&s_k[s][2], k1);
+                rung_lds_add(&s_k[s][2], k.k1);
             }
         }
     __syncthreads();

@@ -271,22 +271,15 @@ __device__ __forceinline__ void q_flush_int(unsigned long long& acc, QSlot* slot
 // One acceptance ratio accepted / total (callback_acceptance, metropolis.jl:319-321: Int / Int -> Float64) as a multiple of
 // 2^XS_E_RATIO, added to the lane's integer; a chain that never picked the move has 0 / 0 = NaN (`nan` is set; the
 // division is then by 1).
-__device__ __forceinline__ void ratio_add(unsigned long long& acc, bool& nan, uint32_t accepted, uint32_t total)
+// U: uint32_t, or unsigned long long for counts beyond 32 bits (a handle whose counters have been carried into their 64-bit bases,
+// counter_rebase_kernel): Int / Int of the reference, both below 2^53.
+template <class U>
+__device__ __forceinline__ void ratio_add(unsigned long long& acc, bool& nan, U accepted, U total)
 {
-    const uint32_t den = total > 1u ? total : 1u;
-    nan = nan | (total == 0u);
+    const U den = total > (U)1 ? total : (U)1;
+    nan = nan | (total == (U)0);
     const double q = (double)accepted / (double)den;
-    const double t = xs::xs_c(xs::XS_E_RATIO) + __longlong_as_double(__double_as_longlong(q) | 1ll);
-    acc += (unsigned long long)__double_as_longlong(t) - xs::xs_c_bits(xs::XS_E_RATIO);
-}
-// ... for counts beyond 32 bits (a handle whose counters have been carried into their 64-bit bases, counter_rebase_kernel): Int / Int
-// of the reference, both below 2^53
-__device__ __forceinline__ void ratio_add(unsigned long long& acc, bool& nan, unsigned long long accepted, unsigned long long total)
-{
-    const unsigned long long den = total > 1ull ? total : 1ull;
-    nan = nan | (total == 0ull);
-    const double q = (double)accepted / (double)den;
-    const double t = xs::xs_c(xs::XS_E_RATIO) + __longlong_as_double(__double_as_longlong(q) | 1ll);
+    const double t = xs::xs_c(xs::XS_E_RATIO) + xs::xs_lsb1(q);
     acc += (unsigned long long)__double_as_longlong(t) - xs::xs_c_bits(xs::XS_E_RATIO);
 }
 __device__ __forceinline__ xs::PartQ q_slot_value(const QSlot& s)
@@ -298,14 +291,14 @@ __device__ __forceinline__ xs::PartQ q_slot_value(const QSlot& s)
 }
 
 // Kind R: the running-top accumulators of NC columns.  top[] is wave-uniform -- every assignment comes from a readfirstlane --;
-// a1[] / a2[] are the lane's 64-bit sums of the BIT PATTERNS of t = c1 + lsb1(v) and t2 = c2 + lsb1(r) (amc_xsum.h):
-// n bits(c) + the sum of the multiples, n[] = summands since the last flush.  The two levels' constants and the bound are
+// a1[] / a2[] / n[] are the lane's accumulators of amc_xsum.h ("kind R in a lane": xs_r_split, xs_r_multiples, xs_r_rebase),
+// n[] = summands since the last flush.  The two levels' constants and the bound are
 // formed from top where they are used (a handful of scalar-unit integer operations): kept in registers across the sampling
 // loops they would be ten more SGPRs per column in kernels that have none to spare -- spilled to VGPR lanes and fetched back
 // with v_readlane, a vector-unit instruction, at every use (measured: +50 VALU instructions per trip).
 template <int NC>
 struct RLanes {
-    unsigned long long a1[NC], a2[NC];
+    uint64_t a1[NC], a2[NC];
     int top[NC];
     int n[NC];
 };
@@ -346,16 +339,12 @@ __device__ __forceinline__ int r_slow_classify(int c, double& v, xs::PartR* slot
 {
     int need = xs::XS_LMIN;
     uint32_t fl = 0u;
-    {
-        const uint64_t bits = (uint64_t)__double_as_longlong(v);
-        const bool nan = ((bits >> 52) & 0x7FFull) == 0x7FFull && (bits & 0xFFFFFFFFFFFFFull) != 0ull;
-        const int l = xs::xs_level_of(v);                  // > LMAX for infinities, NaN and finite |v| >= 2^999
-        if (l > xs::XS_LMAX) {
-            fl = nan ? xs::XS_F_NAN : ((bits >> 63) ? xs::XS_F_NINF : xs::XS_F_PINF);
-            v = 0.0;                                       // the flags carry it
-        } else {
-            need = l;
-        }
+    const int l = xs::xs_level_of(v);                      // > LMAX for infinities, NaN and finite |v| >= 2^999
+    if (l > xs::XS_LMAX) {
+        fl = xs::xs_r_flag_beyond((uint64_t)__double_as_longlong(v));
+        v = 0.0;                                           // the flags carry it
+    } else {
+        need = l;
     }
     const bool lane0 = (threadIdx.x & 63) == 0;
     const uint32_t f_nan = __builtin_amdgcn_ballot_w64((fl & xs::XS_F_NAN) != 0u) ? xs::XS_F_NAN : 0u;
@@ -371,14 +360,7 @@ __device__ __forceinline__ void r_slow(RLanes<NC>& L, int c, double& v, xs::Part
     const int be_max = (int)(wave_max_u32((uint32_t)((uint64_t)__double_as_longlong(v) >> 32) & 0x7FFFFFFFu) >> 20);
     const int need = be_max >= (int)xs::XS_BE_BEYOND ? r_slow_classify<NC>(c, v, slot) : xs::xs_level_of_exponent(be_max);
     if (need > L.top[c]) {
-        // one level up the level-1 multiples ARE the new level-2 multiples; further up nothing of what was taken so far is
-        // as large as half a quantum of the new lower level.  (n summands are on the books: n times the new constants' bits.)
-        const unsigned long long n = (unsigned long long)(unsigned)L.n[c];
-        const unsigned long long k1 = L.a1[c] - n * xs::xs_level_c_bits(L.top[c]);
-        const bool one_up = need - L.top[c] == 1;
-        L.top[c] = need;
-        L.a1[c] = n * xs::xs_level_c_bits(need);
-        L.a2[c] = (one_up ? k1 : 0ull) + n * xs::xs_level_c_bits(need - 1);
+        xs::xs_r_rebase(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n[c], L.top[c], need);
         if (lane0) xs::part_r_raise(slot[c], need);
     }
 }
@@ -390,12 +372,10 @@ __device__ __forceinline__ void r_deposit(RLanes<NC>& L, int c, double v, xs::Pa
     // |v| < 2^(50 top + 49) (NaN compares false: it takes the rare arm like infinities and finite values of 2^999 or more)
     if (__builtin_amdgcn_ballot_w64(!(__builtin_fabs(v) < r_level(L.top[c]).cap)) != 0ull) r_slow(L, c, v, slot);
     const RLevel lv = r_level(L.top[c]);
-    const double v1 = __longlong_as_double(__double_as_longlong(v) | 1ll);
-    const double t = lv.c1 + v1;
-    const double r = v1 - (t - lv.c1);
-    const double t2 = lv.c2 + __longlong_as_double(__double_as_longlong(r) | 1ll);
-    L.a1[c] += (unsigned long long)__double_as_longlong(t);
-    L.a2[c] += (unsigned long long)__double_as_longlong(t2);
+    uint64_t t, t2;
+    xs::xs_r_split(v, lv.c1, lv.c2, t, t2);
+    L.a1[c] += t;
+    L.a2[c] += t2;
     L.n[c] += 1;
 }
 
@@ -411,9 +391,8 @@ __device__ __forceinline__ void r_flush(RLanes<NC>& L, xs::PartR* slot)
 #pragma unroll
     for (int c = 0; c < NC; ++c) n_max = L.n[c] > n_max ? L.n[c] : n_max;
     auto multiples = [&](int c, long long& k1, long long& k2) {
-        const unsigned long long n = (unsigned long long)(unsigned)L.n[c];
-        k1 = (long long)(L.a1[c] - n * xs::xs_level_c_bits(L.top[c]));
-        k2 = (long long)(L.a2[c] - n * xs::xs_level_c_bits(L.top[c] - 1));
+        const xs::RPair k = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n[c], L.top[c]);
+        k1 = k.k1; k2 = k.k2;
         L.a1[c] = L.a2[c] = 0ull;
         L.n[c] = 0;
     };
@@ -457,14 +436,14 @@ __device__ __forceinline__ void r_flush(RLanes<NC>& L, xs::PartR* slot)
 
 // Kind R with the top PER LANE (rung_sums_kernel, amc_exchange.h): the lanes of a wave hold different rungs of a ladder, and a rung's
 // level is a function of that rung's summands alone -- a wave-uniform top would let a large value of one rung coarsen the quantum of
-// its neighbours.  top[] and flags[] live in vector registers; a1[] / a2[] are the sums of bit patterns of RLanes.  The arithmetic of a
-// deposit is r_deposit's (lsb1, c1 + v, the exact remainder, c2 + r), the raise r_slow's (one level up k1 becomes k2, further up
-// both are dropped), the flags r_slow_classify's; the rare arm is taken by the lanes that need it and by no other (it may diverge).
+// its neighbours.  top[] and flags[] live in vector registers; a1[] / a2[] are the sums of bit patterns of RLanes, and the arithmetic
+// is the same primitives' (amc_xsum.h, "kind R in a lane"); the rare arm is taken by the lanes that need it and by no other (it may
+// diverge).
 // n: the summands on the books of EVERY column a caller deposits into -- one deposit per such column, then ++n (rl_deposit leaves
-// it alone) --, at most XS_LANE_CAP - 2 of them before rl_multiples: |k| < n 2^49 < 2^62.
+// it alone) --, at most XS_LANE_CAP - 2 of them before xs_r_multiples: |k| < n 2^49 < 2^62.
 template <int NC>
 struct RLaneCols {
-    unsigned long long a1[NC], a2[NC];
+    uint64_t a1[NC], a2[NC];
     int top[NC];
     uint32_t flags[NC];
     int n;
@@ -484,44 +463,23 @@ __device__ __forceinline__ void rl_init(RLaneCols<NC>& L)
 template <int NC>
 __device__ __forceinline__ void rl_slow(RLaneCols<NC>& L, int c, double& v)
 {
-    const uint64_t bits = (uint64_t)__double_as_longlong(v);
     const int need = xs::xs_level_of(v);                   // > LMAX for infinities, NaN and finite |v| >= 2^999
     if (need > xs::XS_LMAX) {
-        const bool nan = ((bits >> 52) & 0x7FFull) == 0x7FFull && (bits & 0xFFFFFFFFFFFFFull) != 0ull;
-        L.flags[c] |= nan ? xs::XS_F_NAN : ((bits >> 63) ? xs::XS_F_NINF : xs::XS_F_PINF);
+        L.flags[c] |= xs::xs_r_flag_beyond((uint64_t)__double_as_longlong(v));
         v = 0.0;                                           // the flags carry it
         return;
     }
-    if (need > L.top[c]) {
-        const unsigned long long n = (unsigned long long)(unsigned)L.n;
-        const unsigned long long k1 = L.a1[c] - n * xs::xs_level_c_bits(L.top[c]);
-        const bool one_up = need - L.top[c] == 1;
-        L.top[c] = need;
-        L.a1[c] = n * xs::xs_level_c_bits(need);
-        L.a2[c] = (one_up ? k1 : 0ull) + n * xs::xs_level_c_bits(need - 1);
-    }
+    xs::xs_r_rebase(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n, L.top[c], need);
 }
 template <int NC>
 __device__ __forceinline__ void rl_deposit(RLaneCols<NC>& L, int c, double v)
 {
     // |v| < 2^(50 top + 49) (NaN compares false: it takes the rare arm like infinities and finite values of 2^999 or more)
     if (!(__builtin_fabs(v) < xs::xs_level_cap(L.top[c]))) rl_slow(L, c, v);
-    const double c1 = __longlong_as_double((long long)xs::xs_level_c_bits(L.top[c]));
-    const double c2 = __longlong_as_double((long long)xs::xs_level_c_bits(L.top[c] - 1));
-    const double v1 = __longlong_as_double(__double_as_longlong(v) | 1ll);
-    const double t = c1 + v1;
-    const double r = v1 - (t - c1);
-    const double t2 = c2 + __longlong_as_double(__double_as_longlong(r) | 1ll);
-    L.a1[c] += (unsigned long long)__double_as_longlong(t);
-    L.a2[c] += (unsigned long long)__double_as_longlong(t2);
-}
-// the lane's two integers of column c: the multiples of q_top and of q_(top - 1)
-template <int NC>
-__device__ __forceinline__ void rl_multiples(const RLaneCols<NC>& L, int c, long long& k1, long long& k2)
-{
-    const unsigned long long n = (unsigned long long)(unsigned)L.n;
-    k1 = (long long)(L.a1[c] - n * xs::xs_level_c_bits(L.top[c]));
-    k2 = (long long)(L.a2[c] - n * xs::xs_level_c_bits(L.top[c] - 1));
+    uint64_t t, t2;
+    xs::xs_r_split(v, xs::xs_bits_double(xs::xs_level_c_bits(L.top[c])), xs::xs_bits_double(xs::xs_level_c_bits(L.top[c] - 1)), t, t2);
+    L.a1[c] += t;
+    L.a2[c] += t2;
 }
 
 // The block's row of a kind-R / kind-Q column from its wave slots slots[wave][NC] (thread 0, after a barrier).
@@ -619,9 +577,9 @@ __device__ __forceinline__ void red_finish(RLanes<RedCols<POT, EONLY>::NC>& L, x
         long long k[2 * NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const unsigned long long n = (unsigned long long)(unsigned)L.n[c];
-            k[2 * c] = (long long)(L.a1[c] - n * xs::xs_level_c_bits(L.top[c]));
-            k[2 * c + 1] = (long long)(L.a2[c] - n * xs::xs_level_c_bits(L.top[c] - 1));
+            const xs::RPair kc = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n[c], L.top[c]);
+            k[2 * c] = kc.k1;
+            k[2 * c + 1] = kc.k2;
         }
         // (the common request is sum e alone -- callback_energy --: its two integers travel by themselves, the columns nobody
         // deposited into are zero without a sum)

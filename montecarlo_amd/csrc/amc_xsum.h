@@ -163,6 +163,7 @@ AMC_XS_HD double xs_lsb1(double v) { return xs_bits_double(xs_double_bits(v) | 1
 // of itself; over the 1e7+ chains of a fold the rounding errors average out to far below the Float64 rounding of the total.)
 struct GdExponents { int e[4]; };
 AMC_XS_HD int xs_gd_es(double sigma) { return (int)((xs_double_bits(sigma) >> 52) & 0x7FFu) - 1023 + 1; }
+// the table of the four formulas above ...
 AMC_XS_HD GdExponents xs_gd_exponents_es(int es)
 {
     const int drop = 51 - XS_GD_CAP_BITS;
@@ -173,23 +174,14 @@ AMC_XS_HD GdExponents xs_gd_exponents_es(int es)
     g.e[3] = 15 - 2 * es - drop;
     return g;
 }
-// column i's exponent by itself (an index that is not a constant would put the four of them in private memory)
+// ... and its row i by itself: the same four formulas, restated without the array because an index that is not a constant would
+// put the four of them in private memory.  Whoever changes one of the two changes the other.
 AMC_XS_HD int xs_gd_exponent_of(double sigma, int i)
 {
     const int es = xs_gd_es(sigma), drop = 51 - XS_GD_CAP_BITS;
     return i == 0 ? 2 * es + 7 - drop : i == 1 ? es + 13 - drop : i == 2 ? 8 - es - drop : 15 - 2 * es - drop;
 }
-AMC_XS_HD GdExponents xs_gd_exponents(double sigma)
-{
-    const int es = xs_gd_es(sigma);
-    const int drop = 51 - XS_GD_CAP_BITS;
-    GdExponents g;
-    g.e[0] = 2 * es + 7 - drop;
-    g.e[1] = es + 13 - drop;
-    g.e[2] = 8 - es - drop;
-    g.e[3] = 15 - 2 * es - drop;
-    return g;
-}
+AMC_XS_HD GdExponents xs_gd_exponents(double sigma) { return xs_gd_exponents_es(xs_gd_es(sigma)); }
 
 // ---- partial sums in integer form ----
 struct PartQ {            // kind Q
@@ -202,13 +194,22 @@ struct PartR {            // kind R
     i128 k1, k2;
 };
 AMC_XS_HD PartR part_r_empty() { return PartR{XS_LMIN, 0u, i128{0, 0}, i128{0, 0}}; }
-// bring a partial to a higher top (exact, see the header comment)
+// Bring a partial's two integers to a top that is d >= 0 levels above its own (exact, see the header comment): at its own top
+// nothing changes; one level up the k1 total IS the k2 total and the old k2 total is dropped; further up nothing is left.
+// One body for both widths: 64 bits in a lane (xs_r_rebase), 128 in a partial sum (part_r_raise).  (red_finish's compact arm and
+// rung_sums_kernel apply the rule as the CHOICE of the slot a word is added to: through this function they cost vector instructions.)
+template <class K>
+AMC_XS_HD void xs_r_settle(int d, K& k1, K& k2)
+{
+    if (d <= 0) return;
+    k2 = (d == 1) ? k1 : K{};
+    k1 = K{};
+}
 AMC_XS_HD void part_r_raise(PartR& a, int top)
 {
     const int d = top - a.top;
     if (d <= 0) return;
-    a.k2 = (d == 1) ? a.k1 : i128{0, 0};
-    a.k1 = i128{0, 0};
+    xs_r_settle(d, a.k1, a.k2);
     a.top = top;
 }
 AMC_XS_HD void part_r_merge(PartR& a, PartR b)
@@ -233,6 +234,45 @@ AMC_XS_HD double part_q_round(const PartQ& a, int e)
 {
     if (a.flags) return flags_value(a.flags);
     return i128_round_scaled(a.k, e);
+}
+
+// ---- kind R in a lane: the accumulators a1 / a2 are 64-bit sums of the BIT PATTERNS of t = c1 + lsb1(v) and t2 = c2 + lsb1(r)
+// (header comment), n the summands on the books, top their level.  RLanes and RLaneCols (amc_wave_sums.h) call these, and so
+// does the host (tests/aux/xsum_lanes_host.cpp).  The four additions of a deposit.  c1, c2: the constants of the lane's top and of the level below (xs_level_c_bits as doubles),
+// formed by the caller -- on the scalar unit where the top is wave-uniform.  |v| < xs_level_cap(top).
+AMC_XS_HD void xs_r_split(double v, double c1, double c2, uint64_t& t_bits, uint64_t& t2_bits)
+{
+    const double v1 = xs_lsb1(v);
+    const double t = c1 + v1;
+    const double r = v1 - (t - c1);                     // exact
+    const double t2 = c2 + xs_lsb1(r);
+    t_bits = xs_double_bits(t);
+    t2_bits = xs_double_bits(t2);
+}
+// The lane's two integers: the multiples of q_top and of q_(top - 1), |.| < n 2^49 (arithmetic modulo 2^64 holds them).
+struct RPair {
+    int64_t k1, k2;
+};
+AMC_XS_HD RPair xs_r_multiples(uint64_t a1, uint64_t a2, uint64_t n, int top)
+{
+    return RPair{(int64_t)(a1 - n * xs_level_c_bits(top)), (int64_t)(a2 - n * xs_level_c_bits(top - 1))};
+}
+// Raise the accumulators to the level `need` (no-op when need <= top): what was taken is settled there, n summands are re-seeded.
+AMC_XS_HD void xs_r_rebase(uint64_t& a1, uint64_t& a2, uint64_t n, int& top, int need)
+{
+    if (need <= top) return;
+    RPair k = xs_r_multiples(a1, a2, n, top);
+    xs_r_settle(need - top, k.k1, k.k2);
+    top = need;
+    a1 = (uint64_t)k.k1 + n * xs_level_c_bits(need);
+    a2 = (uint64_t)k.k2 + n * xs_level_c_bits(need - 1);
+}
+// The flag that carries a value NO level takes (xs_level_of(v) > XS_LMAX, which the caller has found: it needs the level anyway):
+// NaN, or the infinity of its sign for +-Inf and for finite values of 2^999 or more.
+AMC_XS_HD uint32_t xs_r_flag_beyond(uint64_t bits)
+{
+    const bool nan = ((bits >> 52) & 0x7FFull) == 0x7FFull && (bits & 0xFFFFFFFFFFFFFull) != 0ull;
+    return nan ? XS_F_NAN : ((bits >> 63) ? XS_F_NINF : XS_F_PINF);
 }
 
 // ---- records: XS_WORDS doubles, each an integer below 2^53 in magnitude ----

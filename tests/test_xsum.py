@@ -1,7 +1,10 @@
 """Reproducible cross-chain sums on the CPU: the oracle's restatement against an independent
 big-integer model, order / partition independence, and the host-side record arithmetic of libamc.so (amc_xsum_merge /
-amc_xsum_round: pure host functions) against the oracle's.  The device side is checked in tests/test_gpu_xsum.py."""
+amc_xsum_round: pure host functions) against the oracle's, and the kind-R lane arithmetic the kernels run, compiled for the host
+(tests/aux/xsum_lanes_host.cpp).  The device side is checked in tests/test_gpu_xsum.py."""
 import math
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -198,3 +201,93 @@ def test_oracle_callback_sums_agree_with_the_plain_left_to_right_sums():
     gp = sim2.pg_estimate_plain([1], 3)
     assert np.allclose(g, gp, rtol=1e-10, atol=1e-10)
     assert np.array_equal(sim.state()[0], sim2.state()[0])
+
+
+# ---- the lane arithmetic the kernels run (amc_xsum.h "kind R in a lane"), on the host: tests/aux/xsum_lanes_host.cpp ----------------
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_LANES_SRC = os.path.join(_HERE, "aux", "xsum_lanes_host.cpp")
+_CSRC = os.path.join(os.path.dirname(_HERE), "montecarlo_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def lanes_host(tmp_path_factory):
+    """run(values, L, blocks=1) -> records (blocks, XS_WORDS) of the host program, compiled once per module run."""
+    d = tmp_path_factory.mktemp("xsum_lanes")
+    exe, data = str(d / "xsum_lanes_host"), str(d / "values.f64")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-I", _CSRC, _LANES_SRC, "-o", exe], check=True, capture_output=True)
+
+    def run(values, n_lanes, blocks=1):
+        np.ascontiguousarray(values, dtype="<f8").tofile(data)
+        out = subprocess.run([exe, data, str(n_lanes), str(blocks)], check=True, capture_output=True, text=True).stdout
+        rec = np.array([[float(w) for w in line.split()] for line in out.splitlines()])
+        assert rec.shape == (blocks, O.XS_WORDS)
+        return rec
+    return run
+
+
+def _rising():
+    """the vector of test_running_top_sum_does_not_depend_on_the_order_or_the_split: the top rises by one and by several levels"""
+    rng = np.random.default_rng(5)
+    return np.concatenate([rng.standard_normal(200) * 0.4, rng.standard_normal(50) * 1e-9, [0.75, 2.0 ** 49, -2.0 ** 48.5, 3.1e16],
+                           rng.standard_normal(5) * 1e40])
+
+
+def _lane_cases():
+    cases = {f"wild{seed}": _wild(np.random.default_rng(seed), 400) for seed in range(4)}
+    v = _rising()
+    cases["rising"] = v
+    for i in range(3):
+        cases[f"rising_perm{i}"] = np.random.default_rng(50 + i).permutation(v)
+    # every lane's first value is its largest / its last is (lane i mod L takes every L-th value of a sorted vector)
+    by_size = v[np.argsort(np.abs(v), kind="stable")]
+    cases["largest_last"] = by_size
+    cases["largest_first"] = by_size[::-1]
+    # the level boundaries 2^(50 l + 49), l = -1, 0, 1, and one ulp to either side, both signs, among values that stay below
+    edge = np.array([2.0 ** (50 * l + 49) for l in (-1, 0, 1)])
+    edges = np.concatenate([np.nextafter(edge, 0.0), edge, np.nextafter(edge, np.inf)])
+    small = np.random.default_rng(7).standard_normal(40) * 2.0 ** -8
+    for i, e in enumerate(edges):
+        cases[f"edge{i}"] = np.concatenate([small[:20], [e], small[20:], [-e, 0.5 * e]])
+    cases["edges_rising"] = np.concatenate([small, np.sort(np.concatenate([edges, -edges]))])
+    cases["edges_falling"] = cases["edges_rising"][::-1]
+    cases["two_values"] = np.array([0.3, -2.0 ** 60])          # L = 3, 64: lanes without a summand
+    cases["nothing"] = np.array([])
+    return cases
+
+
+_LANE_CASES = _lane_cases()
+
+
+@pytest.mark.parametrize("n_lanes", [1, 3, 64])
+@pytest.mark.parametrize("case", list(_LANE_CASES))
+def test_lane_arithmetic_of_the_kernels_equals_the_oracle(lanes_host, case, n_lanes):
+    """All XS_WORDS words: the constant-plus-value bit patterns, the rebase of a lane whose top rises, the settling of the lanes'
+    integers at the block's top, against the oracle's restatement of the DEFINITION on the same values."""
+    v = _LANE_CASES[case]
+    assert np.array_equal(lanes_host(v, n_lanes)[0], O.xsum_r(v))
+
+
+@pytest.mark.parametrize("n_lanes", [1, 3, 64])
+def test_lane_arithmetic_flags_of_values_no_level_takes(lanes_host, n_lanes):
+    big = 2.0 ** 999
+    finite = [1.0, -3.5e20, 2.0 ** -700, 5.0e300]              # 5.0e300 < 2^999: the last level takes it
+    for special, flags in (([math.nan], 1), ([math.inf], 2), ([-math.inf], 4), ([big], 2), ([-1.5 * big], 4), ([np.nextafter(big, 0.0)], 0),
+                           ([math.inf, -big], 6), ([math.nan, math.inf, -math.inf, big], 7)):
+        for v in (np.array(finite[:2] + special + finite[2:]), np.array(special + finite), np.array(finite + special)):
+            rec = lanes_host(v, n_lanes)[0]
+            assert np.array_equal(rec, O.xsum_r(v))
+            assert rec[2] == flags
+            if flags:
+                assert not rec[3:].any()                       # the integers mean nothing: canonically zero
+
+
+@pytest.mark.parametrize("n_lanes", [1, 3, 64])
+@pytest.mark.parametrize("case", ["wild0", "wild1", "rising", "rising_perm0", "largest_first", "largest_last", "edges_rising", "two_values"])
+def test_lane_arithmetic_over_two_blocks_merges_to_the_oracle_record(lanes_host, case, n_lanes):
+    v = _LANE_CASES[case]
+    blocks = lanes_host(v, n_lanes, blocks=2)
+    acc = np.zeros((1, A.AMC_XSUM_WORDS))
+    for rec in blocks:
+        acc = A.xsum_merge(acc, rec)                           # libamc.so's host-side merge
+    assert np.array_equal(acc[0], O.xsum_r(v))
