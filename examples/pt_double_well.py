@@ -6,7 +6,10 @@ A temperature ladder with neighbour swaps (ReplicaExchange) lets positions trave
 down.  Every chain starts in the right well; the script runs the same schedule with and without exchange steps and prints, per
 rung, the fraction of chains left of the barrier, the mean energy and the swap acceptance of every gap.
 
-    python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...]
+    python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track]
+
+--track also follows every replica through the swaps and prints, at the end, the flow fraction f(r) -- of the replicas at rung r that
+have been to an end of the ladder, the share that came from the hot end (rung 0) last -- and the round trips per ladder.
 """
 import argparse
 import os
@@ -28,7 +31,7 @@ def one_run(args, path, exchange: bool):
     algorithm_list = [dict(algorithm=ma.Metropolis, pool=pool, seed=args.seed)]
     callbacks = [ma.callback_energy]
     if exchange:
-        algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,)))          # every time step
+        algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), track=args.track))   # every time step
         callbacks.append(ma.callback_exchange_acceptance)
     algorithm_list.append(dict(algorithm=ma.StoreCallbacks, callbacks=tuple(callbacks),
                                scheduler=ma.build_schedule(args.steps, 0, max(1, args.steps // 10))))
@@ -48,6 +51,7 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--path", default=None)
+    ap.add_argument("--track", action="store_true", help="follow the replicas: print the flow fraction per rung and the round trips")
     args = ap.parse_args(argv)
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
@@ -59,6 +63,11 @@ def main(argv=None):
     print("mean energy, without          : " + "  ".join(f"{v:7.4f}" for v in energy_plain))
     print("swap acceptance per gap       : " + "  ".join(f"{v:7.4f}" for v in accept))
     print("coldest rung, 8 bins of [-2, 2): " + " ".join(str(int(v)) for v in hist[-1][:8]))
+    if args.track:
+        rx = sim.algorithms[1]
+        trips = rx.round_trips()
+        print("flow fraction f(r)            : " + "  ".join(f"{v:7.4f}" for v in rx.flow()))
+        print(f"round trips per ladder        : {trips[0] / args.ladders:7.4f}  (up trips {trips[1] / args.ladders:7.4f})")
     return sim, left, left_plain, accept
 
 

@@ -378,6 +378,30 @@ int  amc_histogram_rungs(amc_handle *h, double lo, double hi, int n_bins, uint64
  * Runs on the handle's stream behind whatever is queued; leaves the step indices, the step log, every counter and the reductions in
  * flight alone.  AMC_ERR_STATE without a ladder; AMC_ERR_BAD_ARG for columns == 0 or bits outside AMC_REDUCE_ALL. */
 int  amc_reduce_rungs_exact(amc_handle *h, int columns, double *records);
+/* Walker tracking (DESIGN.md section 3.13 "Walker tracking"): which replica sits at which rung, round trips and flow.  One label byte
+ * per local chain, lab = w | (d << 6): w in [0, R) the walker id -- the rung the replica sat at when tracking was turned on --, d the end
+ * it last visited: 0 none yet, 1 "up" (last at rung 0), 2 "down" (last at rung R - 1); d = 3 never occurs.
+ * amc_set_tracking(h, 1) needs a ladder (AMC_ERR_STATE otherwise), sets lab[l R + r] = r | (d0(r) << 6) with d0(0) = 1, d0(R - 1) = 2 and 0
+ * elsewhere, and zeroes the two trip counters; amc_set_tracking(h, 0) frees the labels.  amc_set_ladder turns tracking off on every
+ * call that succeeds, n_rungs = 0 included (another ladder has other walkers); amc_upload_state leaves the labels alone.
+ * With tracking on an exchange step (amc_exchange, amc_sweep_exchange) decides as it always does and an accepted swap of gap r
+ * exchanges the two labels along with x; then, if r == 0, the label now at rung 0 counts a round trip when its d is 2 and gets d = 1,
+ * and if r + 1 == R - 1 the label now at rung R - 1 counts an up trip when its d is 1 and gets d = 2.  x, e, every counter and every
+ * step index of a tracked handle equal those of an untracked one bit for bit; a handle without tracking launches what it always did.
+ * Every entry below except amc_set_tracking returns AMC_ERR_STATE while tracking is off.
+ * amc_download_labels / amc_upload_labels: n_chains bytes of the local shard; both synchronise.  amc_upload_labels checks on the host,
+ * before anything reaches the device, and refuses with AMC_ERR_BAD_ARG naming the first offending chain: w >= R, d == 3, a label at
+ * rung 0 whose d is not 1, a label at rung R - 1 whose d is not 2, a ladder whose walker ids are no permutation of 0 .. R - 1.
+ * amc_flow_rungs: counts[r * 3 + d] = local chains at rung r whose label has direction d (sum across shards; the flow fraction is
+ * f(r) = counts[r][1] / (counts[r][1] + counts[r][2])).  amc_tracking_counters: round trips (a "down" label arrived at rung 0) and up
+ * trips (an "up" label arrived at rung R - 1) over the local ladders since tracking was turned on (or what amc_set_tracking_counters
+ * restored): exact integers, add across shards.  Both run on the handle's stream behind whatever is queued, synchronise and change nothing. */
+int  amc_set_tracking(amc_handle *h, int on);
+int  amc_download_labels(amc_handle *h, uint8_t *labels);
+int  amc_upload_labels(amc_handle *h, const uint8_t *labels);
+int  amc_flow_rungs(amc_handle *h, uint64_t *counts);
+int  amc_tracking_counters(amc_handle *h, int64_t *round_trips, int64_t *up_trips);
+int  amc_set_tracking_counters(amc_handle *h, int64_t round_trips, int64_t up_trips);
 
 /* MH steps done per chain so far (the Philox step index); settable for resume. */
 int  amc_get_step(amc_handle *h, uint64_t *t);

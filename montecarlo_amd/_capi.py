@@ -164,6 +164,12 @@ def load() -> C.CDLL:
         "amc_set_exchange_step": (C.c_int, [H, C.c_uint64]),
         "amc_histogram_rungs": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64)]),
         "amc_reduce_rungs_exact": (C.c_int, [H, C.c_int, dp]),
+        "amc_set_tracking": (C.c_int, [H, C.c_int]),
+        "amc_download_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
+        "amc_upload_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
+        "amc_flow_rungs": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "amc_tracking_counters": (C.c_int, [H, i64p, i64p]),
+        "amc_set_tracking_counters": (C.c_int, [H, C.c_int64, C.c_int64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -682,6 +688,44 @@ class HipEngine:
         out = np.zeros((n, 3, AMC_XSUM_WORDS), dtype=np.float64)
         _check(self._lib.amc_reduce_rungs_exact(self._h, int(columns), _dptr(out)))
         return out
+
+    # -- walker tracking (include/amc.h; DESIGN.md section 3.13 "Walker tracking") ----------------
+    def set_tracking(self, on: bool = True) -> None:
+        """Turn walker tracking on (needs a ladder; labels start as the identity, the trip counters at zero) or off (frees the labels)."""
+        _check(self._lib.amc_set_tracking(self._h, 1 if on else 0))
+
+    def labels(self):
+        """(walker, direction), two uint8 arrays with one entry per local chain: the walker id in [0, R) and the end the replica last
+        visited (0 none yet, 1 rung 0, 2 rung R - 1).  Synchronises."""
+        lab = np.zeros(self.n_chains, dtype=np.uint8)
+        _check(self._lib.amc_download_labels(self._h, lab.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return lab & np.uint8(63), lab >> np.uint8(6)
+
+    def set_labels(self, walker, direction) -> None:
+        w = np.ascontiguousarray(walker, dtype=np.int64).reshape(-1)
+        d = np.ascontiguousarray(direction, dtype=np.int64).reshape(-1)
+        if w.size != self.n_chains or d.size != self.n_chains:
+            raise AmcError(f"set_labels: one walker id and one direction per local chain ({self.n_chains}) each")
+        if w.size and (w.min() < 0 or w.max() > 63 or d.min() < 0 or d.max() > 3):
+            raise AmcError("set_labels: walker ids must lie in [0, 64) and directions in [0, 4)")
+        lab = np.ascontiguousarray(w | (d << 6), dtype=np.uint8)
+        _check(self._lib.amc_upload_labels(self._h, lab.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def flow_rungs(self) -> np.ndarray:
+        """counts[R][3]: the local chains at rung r whose label has direction d (this shard only), int64."""
+        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        out = np.zeros((n, 3), dtype=np.uint64)
+        _check(self._lib.amc_flow_rungs(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out.astype(np.int64)
+
+    def tracking_counters(self):
+        """(round_trips, up_trips) over this shard's ladders since tracking was turned on: exact counts."""
+        rt, up = C.c_int64(0), C.c_int64(0)
+        _check(self._lib.amc_tracking_counters(self._h, C.byref(rt), C.byref(up)))
+        return rt.value, up.value
+
+    def set_tracking_counters(self, round_trips: int, up_trips: int) -> None:
+        _check(self._lib.amc_set_tracking_counters(self._h, int(round_trips), int(up_trips)))
 
     def sync(self) -> None:
         _check(self._lib.amc_sync(self._h))

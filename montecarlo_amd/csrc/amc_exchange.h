@@ -1,6 +1,7 @@
 // amc_exchange.h -- replica exchange along a temperature ladder: exchange_kernel, one step of neighbour
 // swaps inside every ladder of R consecutive chains, rung_sums_kernel / rung_finish_kernel, the reproducible sums of e, x, x^2 resolved
-// by rung, and rung_histogram_kernel, amc_histogram's binning resolved by rung.
+// by rung, rung_histogram_kernel, amc_histogram's binning resolved by rung, and walker tracking: exchange_tracked_kernel, the exchange step
+// that also moves one label byte per chain and counts trips between the ends, and rung_flow_kernel, the labels counted by rung and direction.
 // The reference has no such algorithm of its own: a user writes it as an AriannaAlgorithm whose make_step! walks simulation.chains
 // (the plugin protocol, src/algorithms.jl:6-37); with the chains in HBM the engine provides the cross-chain move.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
@@ -73,6 +74,121 @@ __global__ __launch_bounds__(AMC_BLOCK) void exchange_kernel(const ExchangeArgs 
     __syncthreads();
     if (threadIdx.x < 2 * AMC_MAX_RUNGS && s_cnt[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
+
+// ---- walker tracking (amc_set_tracking; DESIGN.md section 3.13 "Walker tracking") ------------------------------------------------------
+// One label byte per local chain, lab = w | (d << 6): w the walker id (the rung the replica sat at when tracking was turned on), d the
+// end it last visited (0 none yet, 1 "up": rung 0, 2 "down": rung R - 1; 3 never occurs).
+enum : uint32_t { LAB_WALKER = 0x3Fu, LAB_UP = 1u << 6, LAB_DOWN = 2u << 6 };
+
+struct ExchangeTrackArgs {
+    ExchangeArgs step;            // the step itself, as exchange_kernel takes it
+    uint8_t* lab;                 // [n_ladders * n_rungs] the labels of the local shard
+    unsigned long long* trips;    // [2]: round_trips (a "down" label arrives at rung 0), up_trips (an "up" label arrives at rung R - 1)
+};
+
+// exchange_kernel's step -- the same loads, the same decision, the same stores of x and the same counts, statement for statement -- that
+// also carries the labels: the two label bytes are loaded with x and beta, an accepted swap stores them crosswise (byte stores; the
+// gaps of one parity share no chain, so no two items touch the same byte, and neighbouring lanes own neighbouring byte pairs), and the
+// lanes of the first and the last gap -- a property of the lane, settled before the loop -- apply the end rules to the label that
+// arrives at rung 0 / rung R - 1.  With R = 2 the one gap is both.  Trips: two registers, one LDS add per lane, one 64-bit atomic per
+// block and touched counter, as the gap counts.  exchange_kernel is kept as it is: a handle without tracking launches it and nothing else.
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void exchange_tracked_kernel(const ExchangeTrackArgs ta)
+{
+    const ExchangeArgs& a = ta.step;
+    __shared__ double s_math[TAB_DOUBLES];
+    __shared__ unsigned int s_cnt[2 * AMC_MAX_RUNGS];
+    __shared__ unsigned int s_trips[2];
+    if (threadIdx.x < 2 * AMC_MAX_RUNGS) s_cnt[threadIdx.x] = 0u;
+    if (threadIdx.x < 2) s_trips[threadIdx.x] = 0u;
+    stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);        // (ends in a barrier)
+
+    const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
+    const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / a.n_gaps;
+    const int64_t l0 = tid / a.n_gaps;
+    const int r = (int)(a.t_x & 1u) + 2 * (int)(tid - l0 * a.n_gaps);
+    const bool at_bottom = r == 0, at_top = r + 1 == a.n_rungs - 1;
+    unsigned int attempted = 0u, accepted = 0u, round_trips = 0u, up_trips = 0u;
+    if (l0 < ladders_per_trip) {
+        for (int64_t l = l0; l < a.n_ladders; l += ladders_per_trip) {
+            const int64_t ia = l * a.n_rungs + r;                 // r + 1 < n_rungs: ia + 1 is a chain of the same ladder
+            const real_t xa = a.x[ia], xb = a.x[ia + 1];
+            const real_t ba = a.beta[ia], bb = a.beta[ia + 1];
+            const uint32_t la = ta.lab[ia], lb = ta.lab[ia + 1];
+            const u32x4 w = philox4x32_10(draw_counter(a.chain0 + (uint64_t)ia, a.t_x, 0u, STREAM_EXCHANGE), a.key0, a.key1);
+            const double u = uniform_co(w.x, w.y);
+            const real_t nea = -potential<POT>(xa, s_math), neb = -potential<POT>(xb, s_math);
+            const real_t delta = ((neb * ba) + (nea * bb)) - ((nea * ba) + (neb * bb));
+            const double ex = exp_f64((double)delta, s_math);
+            const double alpha = (ex != ex) ? ex : (ex < 1.0 ? ex : 1.0);     // min(1, ex) that keeps a NaN
+            ++attempted;
+            if (alpha > u) {
+                a.x[ia] = xb;
+                a.x[ia + 1] = xa;
+                ++accepted;
+                uint32_t na = lb, nb = la;                        // the labels now at rung r and at rung r + 1
+                if (at_bottom) {
+                    round_trips += (na >> 6) == 2u;
+                    na = (na & LAB_WALKER) | LAB_UP;
+                }
+                if (at_top) {
+                    up_trips += (nb >> 6) == 1u;
+                    nb = (nb & LAB_WALKER) | LAB_DOWN;
+                }
+                ta.lab[ia] = (uint8_t)na;
+                ta.lab[ia + 1] = (uint8_t)nb;
+            }
+        }
+    }
+    if (attempted) atomicAdd(&s_cnt[r], attempted);
+    if (accepted) atomicAdd(&s_cnt[AMC_MAX_RUNGS + r], accepted);
+    if (round_trips) atomicAdd(&s_trips[0], round_trips);
+    if (up_trips) atomicAdd(&s_trips[1], up_trips);
+    __syncthreads();
+    if (threadIdx.x < 2 * AMC_MAX_RUNGS && s_cnt[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    if (threadIdx.x < 2 && s_trips[threadIdx.x]) atomicAdd(&ta.trips[threadIdx.x], (unsigned long long)s_trips[threadIdx.x]);
+}
+
+// The flow snapshot: counts[r * 3 + d] = local chains at rung r whose label has direction d, one pass over the label bytes.  A thread
+// reads four labels as one 32-bit word where the buffer allows (the bytes in front of the first 4-byte boundary and behind the last go
+// one by one, thread by thread); the rung of local byte c is c mod R, formed once per word and stepped along its bytes.  Counters live
+// in LDS (192 cells at most), then one 64-bit atomic per block and non-zero cell, as rung_histogram_kernel does.
+__device__ __forceinline__ void flow_count(unsigned int* s_flow, int r, uint32_t lab)
+{
+    const uint32_t d = (lab >> 6) & 3u;
+    if (d < 3u) atomicAdd(&s_flow[r * 3 + (int)d], 1u);       // (d == 3 never occurs; it must not reach the next rung's cells)
+}
+#if AMC_PLAIN_KERNELS
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void rung_flow_kernel(const uint8_t* lab, int64_t n_chains, int n_rungs, unsigned long long* counts)
+{
+    __shared__ unsigned int s_flow[3 * AMC_MAX_RUNGS];
+    const int cells = 3 * n_rungs;
+    for (int i = threadIdx.x; i < cells; i += AMC_BLOCK) s_flow[i] = 0u;
+    __syncthreads();
+    const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * AMC_BLOCK;
+    int64_t head = (int64_t)((4u - (uint32_t)(uint64_t)lab) & 3u);
+    if (head > n_chains) head = n_chains;
+    const int64_t n_words = (n_chains - head) >> 2;
+    const int64_t tail = head + 4 * n_words;
+    const uint32_t* words = (const uint32_t*)(lab + head);
+    for (int64_t i = tid; i < n_words; i += stride) {
+        uint32_t v = words[i];
+        int r = (int)((head + 4 * i) % n_rungs);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            flow_count(s_flow, r, v & 0xFFu);
+            v >>= 8;
+            r = r + 1 == n_rungs ? 0 : r + 1;
+        }
+    }
+    if (tid < head) flow_count(s_flow, (int)(tid % n_rungs), lab[tid]);                                   // head <= 3
+    if (tid < n_chains - tail) flow_count(s_flow, (int)((tail + tid) % n_rungs), lab[tail + tid]);       // n_chains - tail <= 3
+    __syncthreads();
+    for (int i = threadIdx.x; i < cells; i += AMC_BLOCK)
+        if (s_flow[i]) atomicAdd(&counts[i], (unsigned long long)s_flow[i]);
+}
+#endif
 
 // ---- per-rung reproducible sums (amc_reduce_rungs_exact; DESIGN.md section 3.13 "Per-rung sums") ------------------------------------
 // S[r][c], c = sum e, sum x, sum x^2: the kind-R sum (amc_xsum.h) over the ladders l of ONE chain's summand, chain l R + r --

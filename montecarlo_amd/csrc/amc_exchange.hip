@@ -1,7 +1,8 @@
 // amc_exchange.hip -- replica exchange along a temperature ladder: the ladder of a handle, exchange steps
 // (amc_exchange, amc_sweep_exchange), the per-gap counters and the exchange step index, the per-rung reproducible sums
-// (amc_reduce_rungs_exact).  amc_histogram_rungs is with the other histograms in amc_state.hip.
-#define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copy of the one plain kernel it launches (rung_finish_kernel)
+// (amc_reduce_rungs_exact), walker tracking (amc_set_tracking .. amc_set_tracking_counters).  amc_histogram_rungs is with the other
+// histograms in amc_state.hip.
+#define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copies of the plain kernels it launches (rung_finish_kernel, rung_flow_kernel)
 #include "amc_internal.h"
 
 // AMC_MAX_RUNGS has two definitions, include/amc.h's (the ABI) and amc_exchange.h's (the kernel sources, which the run-time compiler
@@ -20,6 +21,22 @@ static const int EXCHANGE_BLOCKS_PER_CU = 2;
 static const int RUNG_SUMS_BLOCKS_PER_CU = 4;
 
 static const size_t XCNT_BYTES = 2 * AMC_MAX_RUNGS * sizeof(unsigned long long);   // d_xcnt: attempted[AMC_MAX_RUNGS], accepted[AMC_MAX_RUNGS]
+
+// d_track: round_trips, up_trips, then the cells of one flow snapshot (amc_flow_rungs' scratch)
+static const int TRACK_FLOW_CELLS = 3 * AMC_MAX_RUNGS;
+static const size_t TRACK_BYTES = (2 + TRACK_FLOW_CELLS) * sizeof(unsigned long long);
+
+// Tracking off: the labels and the trip counters go.  Launches queued on the stream may still use them.
+static int tracking_off(amc_handle* h)
+{
+    if (!h->d_lab) return AMC_OK;
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    (void)hipFree(h->d_lab);
+    (void)hipFree(h->d_track);
+    h->d_lab = nullptr;
+    h->d_track = nullptr;
+    return AMC_OK;
+}
 
 // One exchange step on the stream: the gaps r with r mod 2 == t_x mod 2 of every local ladder.  A parity without gaps (R = 2, odd
 // steps) launches nothing and still counts as a step.
@@ -44,12 +61,22 @@ static int exchange_step(amc_handle* h)
         a.key0 = (uint32_t)h->seed;
         a.key1 = (uint32_t)(h->seed >> 32);
         const int grid = grid_for(h, a.n_ladders * n_gaps, h->knobs.blocks_per_cu ? 0 : EXCHANGE_BLOCKS_PER_CU);
+        amc::ExchangeTrackArgs ta;        // tracking on: the same step by the kernel that carries the labels along
+        ta.step = a;
+        ta.lab = h->d_lab;
+        ta.trips = h->d_track;
+        const bool track = h->d_lab != nullptr;
         if (h->use_rtc) {
-            void* params[] = {&a};
-            const int rc = rtc_launch(h, "amc::exchange_kernel<" + std::to_string(h->potential) + ">", grid, params);
+            void* params[] = {track ? (void*)&ta : (void*)&a};
+            const int rc = rtc_launch(h, (track ? "amc::exchange_tracked_kernel<" : "amc::exchange_kernel<") + std::to_string(h->potential) + ">", grid, params);
             if (rc != AMC_OK) return rc;
         } else {
-            if (h->potential == AMC_POTENTIAL_DOUBLE_WELL)
+            const bool dw = h->potential == AMC_POTENTIAL_DOUBLE_WELL;
+            if (track && dw)
+                hipLaunchKernelGGL((amc::exchange_tracked_kernel<amc::POT_DOUBLE_WELL>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, ta);
+            else if (track)
+                hipLaunchKernelGGL((amc::exchange_tracked_kernel<amc::POT_HARMONIC>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, ta);
+            else if (dw)
                 hipLaunchKernelGGL((amc::exchange_kernel<amc::POT_DOUBLE_WELL>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
             else
                 hipLaunchKernelGGL((amc::exchange_kernel<amc::POT_HARMONIC>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
@@ -65,7 +92,12 @@ extern "C" {
 int amc_set_ladder(amc_handle* h, int n_rungs)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: NULL handle");
-    if (n_rungs == 0) { h->n_rungs = 0; return AMC_OK; }
+    if (n_rungs == 0) {
+        AMC_HIP(hipSetDevice(h->device));
+        { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }
+        h->n_rungs = 0;
+        return AMC_OK;
+    }
     if (n_rungs < 2 || n_rungs > AMC_MAX_RUNGS)
         return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: n_rungs = %d must be 0 (no ladder) or in [2, %d]", n_rungs, AMC_MAX_RUNGS);
     if (!h->beta_arr)
@@ -79,6 +111,7 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
         return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: n_chains = %lld is no multiple of n_rungs = %d (no ladder may straddle a shard)",
                     (long long)h->M, n_rungs);
     AMC_HIP(hipSetDevice(h->device));
+    { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }      // another ladder has other walkers
     if (!h->d_xcnt) AMC_HIP(hipMalloc(&h->d_xcnt, XCNT_BYTES));
     AMC_HIP(hipMemsetAsync(h->d_xcnt, 0, XCNT_BYTES, h->stream));      // the gaps of another ladder are other gaps
     h->n_rungs = n_rungs;
@@ -217,6 +250,120 @@ int amc_set_exchange_step(amc_handle* h, uint64_t t)
     if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_exchange_step: the handle has no ladder (amc_set_ladder)");
     if (t >> 48) return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_step: step index must fit 48 bits");
     h->t_x = t;
+    return AMC_OK;
+}
+
+// ---- walker tracking (DESIGN.md section 3.13 "Walker tracking") ---------------------------------------------------------------------
+// Tracking is on exactly while d_lab is allocated.
+#define AMC_NEED_TRACKING(who)                                                                                              \
+    if (!h->d_lab) return fail(AMC_ERR_STATE, who ": tracking is off (amc_set_tracking)")
+
+int amc_set_tracking(amc_handle* h, int on)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_tracking: NULL handle");
+    AMC_HIP(hipSetDevice(h->device));
+    if (!on) return tracking_off(h);
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_tracking: the handle has no ladder (amc_set_ladder)");
+    if (!h->d_lab) {
+        AMC_HIP(hipMalloc(&h->d_lab, (size_t)h->M));
+        const hipError_t e = hipMalloc(&h->d_track, TRACK_BYTES);
+        if (e != hipSuccess) {
+            (void)hipFree(h->d_lab);
+            h->d_lab = nullptr;
+            h->d_track = nullptr;
+            return fail(e == hipErrorOutOfMemory ? AMC_ERR_OOM : AMC_ERR_HIP, "amc_set_tracking: %s", hipGetErrorString(e));
+        }
+    }
+    const int R = h->n_rungs;
+    std::vector<uint8_t> lab((size_t)h->M);
+    for (int64_t c = 0; c < h->M; ++c) {
+        const int r = (int)(c % R);
+        lab[(size_t)c] = (uint8_t)(r | (r == 0 ? amc::LAB_UP : r == R - 1 ? amc::LAB_DOWN : 0u));
+    }
+    AMC_HIP(hipMemcpyAsync(h->d_lab, lab.data(), (size_t)h->M, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipMemsetAsync(h->d_track, 0, TRACK_BYTES, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));      // `lab` is only valid during the call
+    return AMC_OK;
+}
+
+int amc_download_labels(amc_handle* h, uint8_t* labels)
+{
+    if (!h || !labels) return fail(AMC_ERR_BAD_ARG, "amc_download_labels: NULL argument");
+    AMC_NEED_TRACKING("amc_download_labels");
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_HIP(hipMemcpyAsync(labels, h->d_lab, (size_t)h->M, hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    return AMC_OK;
+}
+
+int amc_upload_labels(amc_handle* h, const uint8_t* labels)
+{
+    if (!h || !labels) return fail(AMC_ERR_BAD_ARG, "amc_upload_labels: NULL argument");
+    AMC_NEED_TRACKING("amc_upload_labels");
+    const int R = h->n_rungs;
+    for (int64_t c0 = 0; c0 < h->M; c0 += R) {
+        uint64_t seen = 0;
+        for (int r = 0; r < R; ++r) {
+            const int64_t c = c0 + r;
+            const int w = labels[c] & amc::LAB_WALKER, d = labels[c] >> 6;
+            if (w >= R) return fail(AMC_ERR_BAD_ARG, "amc_upload_labels: chain %lld: walker id %d >= n_rungs = %d", (long long)c, w, R);
+            if (d == 3) return fail(AMC_ERR_BAD_ARG, "amc_upload_labels: chain %lld: direction 3", (long long)c);
+            if (r == 0 && d != 1) return fail(AMC_ERR_BAD_ARG, "amc_upload_labels: chain %lld sits at rung 0, its direction must be 1, not %d", (long long)c, d);
+            if (r == R - 1 && d != 2)
+                return fail(AMC_ERR_BAD_ARG, "amc_upload_labels: chain %lld sits at rung %d, its direction must be 2, not %d", (long long)c, R - 1, d);
+            if ((seen >> w) & 1u)
+                return fail(AMC_ERR_BAD_ARG, "amc_upload_labels: chain %lld: walker id %d occurs twice in its ladder (not a permutation)", (long long)c, w);
+            seen |= (uint64_t)1 << w;
+        }
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_HIP(hipMemcpyAsync(h->d_lab, labels, (size_t)h->M, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));      // `labels` is only valid during the call
+    return AMC_OK;
+}
+
+int amc_flow_rungs(amc_handle* h, uint64_t* counts)
+{
+    if (!h || !counts) return fail(AMC_ERR_BAD_ARG, "amc_flow_rungs: NULL argument");
+    AMC_NEED_TRACKING("amc_flow_rungs");
+    AMC_HIP(hipSetDevice(h->device));
+    // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
+    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    unsigned long long* d_flow = h->d_track + 2;
+    const size_t bytes = (size_t)(3 * h->n_rungs) * sizeof(unsigned long long);
+    AMC_HIP(hipMemsetAsync(d_flow, 0, bytes, h->stream));
+    const int grid = grid_for(h, (h->M + 3) / 4, h->knobs.blocks_per_cu ? 0 : EXCHANGE_BLOCKS_PER_CU);     // a thread per 4 labels; the atomics' tail again
+    hipLaunchKernelGGL(amc::rung_flow_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint8_t*)h->d_lab, h->M, h->n_rungs, d_flow);
+    AMC_HIP(hipGetLastError());
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "counts are copied as they are");
+    AMC_HIP(hipMemcpyAsync(counts, d_flow, bytes, hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    return AMC_OK;
+}
+
+int amc_tracking_counters(amc_handle* h, int64_t* round_trips, int64_t* up_trips)
+{
+    if (!h || !round_trips || !up_trips) return fail(AMC_ERR_BAD_ARG, "amc_tracking_counters: NULL argument");
+    AMC_NEED_TRACKING("amc_tracking_counters");
+    AMC_HIP(hipSetDevice(h->device));
+    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    unsigned long long host[2];
+    AMC_HIP(hipMemcpyAsync(host, h->d_track, sizeof host, hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    *round_trips = (int64_t)host[0];
+    *up_trips = (int64_t)host[1];
+    return AMC_OK;
+}
+
+int amc_set_tracking_counters(amc_handle* h, int64_t round_trips, int64_t up_trips)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_tracking_counters: NULL handle");
+    AMC_NEED_TRACKING("amc_set_tracking_counters");
+    if (round_trips < 0 || up_trips < 0) return fail(AMC_ERR_BAD_ARG, "amc_set_tracking_counters: need round_trips >= 0 and up_trips >= 0");
+    const unsigned long long host[2] = {(unsigned long long)round_trips, (unsigned long long)up_trips};
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_HIP(hipMemcpyAsync(h->d_track, host, sizeof host, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
     return AMC_OK;
 }
 

@@ -6,7 +6,7 @@
 //   amc_counters.hip    the step log and the per-chain counters (fold, totals, 64-bit carry, upload / download)
 //   amc_sweeps.hip      sweep launches (amc_sweep*)
 //   amc_exchange.hip    replica exchange along a temperature ladder (amc_set_ladder, amc_exchange, amc_sweep_exchange, gap counters,
-//                       the per-rung reproducible sums: amc_reduce_rungs_exact)
+//                       the per-rung reproducible sums: amc_reduce_rungs_exact, walker tracking: amc_set_tracking ..)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -165,6 +165,8 @@ struct amc_handle {
     amc::xs_word* d_rung_rows = nullptr;    // [launches * grid][n_rungs][RED_COLS][XS_ROW_R] block rows of the rung sums (amc_reduce_rungs_exact,
     size_t rung_rows_words = 0;             //   allocated at its first use, grown when a call needs more); the words it holds
     double* d_rung_recs = nullptr;          // [AMC_MAX_RUNGS][RED_COLS][XS_WORDS] their records (rung_finish_kernel)
+    uint8_t* d_lab = nullptr;               // [M] walker labels, w | (d << 6) per chain; allocated exactly while tracking is on (amc_set_tracking)
+    unsigned long long* d_track = nullptr;  // [2 + 3 * AMC_MAX_RUNGS] round_trips, up_trips, the cells of one flow snapshot (allocated with d_lab)
     double* d_x = nullptr;
     double* d_beta = nullptr;
     uint32_t* d_acc = nullptr;

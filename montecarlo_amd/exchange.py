@@ -9,6 +9,10 @@ Ladder l is the R consecutive global chain ids [l R, (l + 1) R); the rung of cha
 beta array holds (``ParticleChains.ladder`` tiles a list of betas).  One exchange step attempts, in every ladder, the gaps of one
 parity; the parity alternates from step to step.  An accepted swap exchanges the POSITIONS of the two chains: beta, the Move counters
 and everything else indexed by chain stay with the rung, so ``x[r::R]`` is always the sample at beta_r.
+
+``track=True`` turns walker tracking on (DESIGN.md section 3.13 "Walker tracking"): the engine carries one label per chain -- which
+replica sits there and which end of the ladder it visited last -- through every accepted swap, and ``flow()`` / ``round_trips()``
+answer whether replicas actually travel between the hot and the cold end, which the acceptance per gap alone cannot.
 """
 from __future__ import annotations
 
@@ -35,7 +39,7 @@ class ReplicaExchange(AriannaAlgorithm):
 
     mutates_chains = True          # a callback due behind it at the same t observes the state AFTER the swaps (simulation._observed_next)
 
-    def __init__(self, chains, dependencies=None, n_rungs=None, path=None, **extras):
+    def __init__(self, chains, dependencies=None, n_rungs=None, path=None, track=False, **extras):
         assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
         self.metropolis: Metropolis = dependencies[0]
         if n_rungs is None:
@@ -43,10 +47,14 @@ class ReplicaExchange(AriannaAlgorithm):
         if n_rungs is None:
             raise ValueError("ReplicaExchange: n_rungs is missing (and the chains were not made by ParticleChains.ladder)")
         self.n_rungs = int(n_rungs)
+        self.track = bool(track)
         self.rank, _ = sharding.world()
 
     def initialise(self, simulation: Simulation) -> None:
         self.metropolis.set_ladder(self.n_rungs)       # (the per-chain beta array is on the device by now: Metropolis comes first)
+        if self.track and not getattr(self.metropolis, "tracking", False):     # (on already: storage.restore brought the labels back)
+            self.metropolis.engine.set_tracking(True)
+            self.metropolis.tracking = True
 
     def make_step(self, simulation: Simulation) -> None:
         self.metropolis.engine.exchange(1)
@@ -63,6 +71,27 @@ class ReplicaExchange(AriannaAlgorithm):
         n = self.n_rungs - 1
         with np.errstate(invalid="ignore", divide="ignore"):
             return tot[:n] / tot[n:]
+
+    def _need_tracking(self, what: str) -> None:
+        if not self.track:
+            raise ValueError(f"{what} needs walker tracking: build the ReplicaExchange with track=True")
+
+    def flow(self) -> np.ndarray:
+        """The flow fraction per rung over ALL shards, R values: of the replicas at rung r that have visited an end, the share that
+        last visited rung 0 -- f(0) = 1, f(R - 1) = 0, 0/0 = NaN where no replica has been to an end yet.  A ladder that works
+        falls about linearly in between; a step marks the bottleneck.  The host waits for the queued steps."""
+        self._need_tracking("ReplicaExchange.flow")
+        eng = self.metropolis.engine
+        n = sharding.allreduce_sum(eng.flow_rungs().astype(np.float64).reshape(-1), eng).reshape(self.n_rungs, 3)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return n[:, 1] / (n[:, 1] + n[:, 2])
+
+    def round_trips(self) -> np.ndarray:
+        """(round_trips, up_trips) over ALL shards since tracking was turned on: arrivals at rung 0 of a replica that last visited
+        rung R - 1, and arrivals at rung R - 1 of one that last visited rung 0.  The host waits for the queued steps."""
+        self._need_tracking("ReplicaExchange.round_trips")
+        eng = self.metropolis.engine
+        return sharding.allreduce_sum(np.array(eng.tracking_counters(), dtype=np.float64), eng)
 
     def rung_sums(self, columns: int = AMC_REDUCE_ALL) -> np.ndarray:
         """Per rung the means of e, x and x^2 over the ladders of ALL shards: an array of shape (R, 3), column c = 0 <e>, 1 <x>,
@@ -97,6 +126,17 @@ def callback_exchange_acceptance(simulation: Simulation) -> np.ndarray:
     """Per gap of the ladder, accepted / attempted swaps since the start: a vector of R - 1 ratios, NaN before the first attempt
     (callback_acceptance's convention, src/metropolis.jl:319-321).  Reads the gap counters: the host waits for the queued steps."""
     return _find_exchange(simulation).acceptance()
+
+
+def callback_flow_fraction(simulation: Simulation) -> np.ndarray:
+    """The flow fraction f(r) per rung, a vector of R values (ReplicaExchange.flow).  Needs ReplicaExchange(..., track=True)."""
+    return _find_exchange(simulation).flow()
+
+
+def callback_round_trips(simulation: Simulation) -> np.ndarray:
+    """(round trips, up trips) over all ladders since the start, a vector of 2 values (ReplicaExchange.round_trips).  Needs
+    ReplicaExchange(..., track=True)."""
+    return _find_exchange(simulation).round_trips()
 
 
 def callback_rung_energy(simulation: Simulation) -> np.ndarray:

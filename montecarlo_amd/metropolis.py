@@ -215,6 +215,7 @@ class Metropolis(AriannaAlgorithm):
             return                              # set already (storage.restore): setting it again would zero the gap counters
         self.engine.set_ladder(R)
         self.n_rungs = R
+        self.tracking = False                   # (amc_set_ladder turns walker tracking off; ReplicaExchange(track=True) and restore turn it on)
 
     def sweep_exchange(self, n_rounds: int, sweeps_per_round: int) -> None:
         """n_rounds x [sweeps_per_round make_step!s; one exchange step] queued by one engine call."""

@@ -157,6 +157,9 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
     if getattr(metropolis, "n_rungs", 0):           # a temperature ladder: the exchange step index and the gap counters are state
         acc_x, att_x = eng.exchange_counters()
         data.update(n_rungs=metropolis.n_rungs, exchange_step=eng.exchange_step, exchange_accepted=acc_x, exchange_attempted=att_x)
+        if getattr(metropolis, "tracking", False):  # walker tracking is on: the labels and the trip counters are state too
+            walker, direction = eng.labels()
+            data.update(walker=walker, direction=direction, trips=np.array(eng.tracking_counters(), dtype=np.int64))
     if estimator is not None:
         data["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in estimator.gradients_data])
     os.makedirs(path, exist_ok=True)
@@ -190,6 +193,11 @@ def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
         metropolis.set_ladder(int(d["n_rungs"]))
         eng.exchange_step = int(d["exchange_step"])
         eng.set_exchange_counters(d["exchange_accepted"], d["exchange_attempted"])
+        if "walker" in d:
+            eng.set_tracking(True)
+            eng.set_labels(d["walker"], d["direction"])
+            eng.set_tracking_counters(int(d["trips"][0]), int(d["trips"][1]))
+            metropolis.tracking = True
     if estimator is not None and "gd" in d:
         from .policy_guided import GradientData
         estimator.gradients_data = [GradientData(float(r[0]), np.array([r[1]]), np.array([r[2]]), np.array([[r[3]]]), int(r[4]))
