@@ -10,6 +10,22 @@ namespace amc {
 // histogram of the chain positions over half-open bins [lo + i w, lo + (i+1) w), i < n_bins, with
 // bin = floor((x - lo) * inv_w) in this exact f64 form; counts[n_bins..n_bins+2] = below lo, >= hi, NaN.
 // Per-block LDS histogram (u32 LDS atomics), flushed with one u64 global atomic per non-empty bin.
+__device__ __forceinline__ int hist_bin(double v, double lo, double hi, double inv_w, int n_bins)
+{
+    if (v != v) return n_bins + 2;
+    if (v < lo) return n_bins;
+    if (v >= hi) return n_bins + 1;
+    const int b = (int)((v - lo) * inv_w);
+    return b < n_bins ? b : n_bins - 1;       // (hi - ulp - lo) * inv_w can round up to n_bins
+}
+
+// End of a block (behind a barrier): its LDS counters go to the global ones, one 64-bit atomic per non-zero cell.
+__device__ __forceinline__ void flush_cells(const unsigned int* s_cells, unsigned long long* counts, int cells)
+{
+    for (int i = threadIdx.x; i < cells; i += AMC_BLOCK)
+        if (s_cells[i]) atomicAdd(&counts[i], (unsigned long long)s_cells[i]);
+}
+
 #if AMC_PLAIN_KERNELS
 AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void histogram_kernel(const double* x, int64_t n_chains, double lo, double hi,
                                                                double inv_w, int n_bins, unsigned long long* counts)
@@ -17,17 +33,7 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void histogram_kernel
     extern __shared__ unsigned int s_hist[];
     for (int i = threadIdx.x; i < n_bins + 3; i += AMC_BLOCK) s_hist[i] = 0u;
     __syncthreads();
-    auto count = [&](double v) {
-        int b;
-        if (v != v) b = n_bins + 2;
-        else if (v < lo) b = n_bins;
-        else if (v >= hi) b = n_bins + 1;
-        else {
-            b = (int)((v - lo) * inv_w);
-            b = b < n_bins ? b : n_bins - 1;       // (hi - ulp - lo) * inv_w can round up to n_bins
-        }
-        atomicAdd(&s_hist[b], 1u);
-    };
+    auto count = [&](double v) { atomicAdd(&s_hist[hist_bin(v, lo, hi, inv_w, n_bins)], 1u); };
     // four positions per lane and trip, both 16-byte loads issued before the first is used (one 8-byte load per trip left the
     // pass waiting for latency: ~50 us for 80 MB)
     const int64_t stride = (int64_t)gridDim.x * AMC_BLOCK;
@@ -39,8 +45,7 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void histogram_kernel
     }
     if (blockIdx.x == 0 && threadIdx.x < (n_chains & 3)) count(x[4 * n_quads + threadIdx.x]);
     __syncthreads();
-    for (int i = threadIdx.x; i < n_bins + 3; i += AMC_BLOCK)
-        if (s_hist[i]) atomicAdd(&counts[i], (unsigned long long)s_hist[i]);
+    flush_cells(s_hist, counts, n_bins + 3);
 }
 #endif
 

@@ -1,7 +1,8 @@
 // amc_exchange.h -- replica exchange along a temperature ladder: exchange_kernel, one step of neighbour
 // swaps inside every ladder of R consecutive chains, rung_sums_kernel / rung_finish_kernel, the reproducible sums of e, x, x^2 resolved
-// by rung, rung_histogram_kernel, amc_histogram's binning resolved by rung, and walker tracking: exchange_tracked_kernel, the exchange step
-// that also moves one label byte per chain and counts trips between the ends, and rung_flow_kernel, the labels counted by rung and direction.
+// by rung, rung_histogram_kernel, amc_histogram's binning resolved by rung, and walker tracking: exchange_tracked_kernel, the same step
+// with TRACK on -- it also moves one label byte per chain and counts trips between the ends --, and rung_flow_kernel, the labels counted by
+// rung and direction.
 // The reference has no such algorithm of its own: a user writes it as an AriannaAlgorithm whose make_step! walks simulation.chains
 // (the plugin protocol, src/algorithms.jl:6-37); with the chains in HBM the engine provides the cross-chain move.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
@@ -27,54 +28,6 @@ struct ExchangeArgs {
     uint32_t key0, key1;
 };
 
-// One exchange step.  Gap r of ladder l pairs the chains a = l R + r and b = a + 1; the step attempts the gaps with r mod 2 == t_x mod 2.
-//   e = potential(x)      (Particle.e is potential(x) by construction, particle_1d.jl:13-15,33)
-//   delta = (((-e_b) beta_a) + ((-e_a) beta_b)) - (((-e_a) beta_a) + ((-e_b) beta_b))       in T, the log target of particle_1d.jl:20-22
-//   alpha = min(1, exp(delta)), Julia's min (a NaN stays a NaN); accept iff alpha > u (strict), u = rand(Float64) of the gap's own draw
-//   accept: x_a <-> x_b, bit patterns unchanged; beta stays with the rung
-// Work items: a thread keeps ONE gap index j (r = parity + 2 j) for the whole launch and walks ladders -- thread id = l0 * n_gaps + j,
-// l advancing by (threads / n_gaps) per trip -- so neighbouring lanes read neighbouring chains, the loop divides nothing, and the
-// per-gap counts live in two registers until the block's end: one LDS add per lane, then one 64-bit atomic per block and touched
-// gap (same-address atomics serialise, ~13 ns each: amc_state.hip hist_grid).  The gaps of one parity share no chain: no two items
-// touch the same position.
-template <int POT>
-__global__ __launch_bounds__(AMC_BLOCK) void exchange_kernel(const ExchangeArgs a)
-{
-    __shared__ double s_math[TAB_DOUBLES];
-    __shared__ unsigned int s_cnt[2 * AMC_MAX_RUNGS];
-    if (threadIdx.x < 2 * AMC_MAX_RUNGS) s_cnt[threadIdx.x] = 0u;
-    stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);        // (ends in a barrier)
-
-    const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
-    const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / a.n_gaps;
-    const int64_t l0 = tid / a.n_gaps;
-    const int r = (int)(a.t_x & 1u) + 2 * (int)(tid - l0 * a.n_gaps);
-    unsigned int attempted = 0u, accepted = 0u;
-    if (l0 < ladders_per_trip) {
-        for (int64_t l = l0; l < a.n_ladders; l += ladders_per_trip) {
-            const int64_t ia = l * a.n_rungs + r;                 // r + 1 < n_rungs: ia + 1 is a chain of the same ladder
-            const real_t xa = a.x[ia], xb = a.x[ia + 1];
-            const real_t ba = a.beta[ia], bb = a.beta[ia + 1];
-            const u32x4 w = philox4x32_10(draw_counter(a.chain0 + (uint64_t)ia, a.t_x, 0u, STREAM_EXCHANGE), a.key0, a.key1);
-            const double u = uniform_co(w.x, w.y);
-            const real_t nea = -potential<POT>(xa, s_math), neb = -potential<POT>(xb, s_math);
-            const real_t delta = ((neb * ba) + (nea * bb)) - ((nea * ba) + (neb * bb));
-            const double ex = exp_f64((double)delta, s_math);
-            const double alpha = (ex != ex) ? ex : (ex < 1.0 ? ex : 1.0);     // min(1, ex) that keeps a NaN
-            ++attempted;
-            if (alpha > u) {
-                a.x[ia] = xb;
-                a.x[ia + 1] = xa;
-                ++accepted;
-            }
-        }
-    }
-    if (attempted) atomicAdd(&s_cnt[r], attempted);
-    if (accepted) atomicAdd(&s_cnt[AMC_MAX_RUNGS + r], accepted);
-    __syncthreads();
-    if (threadIdx.x < 2 * AMC_MAX_RUNGS && s_cnt[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
-}
-
 // ---- walker tracking (amc_set_tracking; DESIGN.md section 3.13 "Walker tracking") ------------------------------------------------------
 // One label byte per local chain, lab = w | (d << 6): w the walker id (the rung the replica sat at when tracking was turned on), d the
 // end it last visited (0 none yet, 1 "up": rung 0, 2 "down": rung R - 1; 3 never occurs).
@@ -86,21 +39,31 @@ struct ExchangeTrackArgs {
     unsigned long long* trips;    // [2]: round_trips (a "down" label arrives at rung 0), up_trips (an "up" label arrives at rung R - 1)
 };
 
-// exchange_kernel's step -- the same loads, the same decision, the same stores of x and the same counts, statement for statement -- that
-// also carries the labels: the two label bytes are loaded with x and beta, an accepted swap stores them crosswise (byte stores; the
-// gaps of one parity share no chain, so no two items touch the same byte, and neighbouring lanes own neighbouring byte pairs), and the
-// lanes of the first and the last gap -- a property of the lane, settled before the loop -- apply the end rules to the label that
-// arrives at rung 0 / rung R - 1.  With R = 2 the one gap is both.  Trips: two registers, one LDS add per lane, one 64-bit atomic per
-// block and touched counter, as the gap counts.  exchange_kernel is kept as it is: a handle without tracking launches it and nothing else.
-template <int POT>
-__global__ __launch_bounds__(AMC_BLOCK) void exchange_tracked_kernel(const ExchangeTrackArgs ta)
+// One exchange step.  Gap r of ladder l pairs the chains a = l R + r and b = a + 1; the step attempts the gaps with r mod 2 == t_x mod 2.
+//   e = potential(x)      (Particle.e is potential(x) by construction, particle_1d.jl:13-15,33)
+//   delta = (((-e_b) beta_a) + ((-e_a) beta_b)) - (((-e_a) beta_a) + ((-e_b) beta_b))       in T, the log target of particle_1d.jl:20-22
+//   alpha = min(1, exp(delta)), Julia's min (a NaN stays a NaN); accept iff alpha > u (strict), u = rand(Float64) of the gap's own draw
+//   accept: x_a <-> x_b, bit patterns unchanged; beta stays with the rung
+// Work items: a thread keeps ONE gap index j (r = parity + 2 j) for the whole launch and walks ladders -- thread id = l0 * n_gaps + j,
+// l advancing by (threads / n_gaps) per trip -- so neighbouring lanes read neighbouring chains, the loop divides nothing, and the
+// per-gap counts live in two registers until the block's end: one LDS add per lane, then one 64-bit atomic per block and touched
+// gap (same-address atomics serialise, ~13 ns each: amc_state.hip hist_grid).  The gaps of one parity share no chain: no two items
+// touch the same position.
+// TRACK (exchange_tracked_kernel) also carries the labels: the two label bytes are loaded with x and beta, an accepted swap stores them
+// crosswise (byte stores; the gaps of one parity share no chain, so no two items touch the same byte, and neighbouring lanes own
+// neighbouring byte pairs), and the lanes of the first and the last gap -- a property of the lane, settled before the loop -- apply
+// the end rules to the label that arrives at rung 0 / rung R - 1.  With R = 2 the one gap is both.  Trips: two registers, one LDS add
+// per lane, one 64-bit atomic per block and touched counter, as the gap counts.  Without TRACK none of that is compiled: a handle
+// without tracking launches exchange_kernel and nothing else.
+template <int POT, bool TRACK>
+__device__ __forceinline__ void exchange_step(const ExchangeArgs& a, uint8_t* lab, unsigned long long* trips)
 {
-    const ExchangeArgs& a = ta.step;
     __shared__ double s_math[TAB_DOUBLES];
     __shared__ unsigned int s_cnt[2 * AMC_MAX_RUNGS];
-    __shared__ unsigned int s_trips[2];
+    __shared__ unsigned int s_trips[TRACK ? 2 : 1];
     if (threadIdx.x < 2 * AMC_MAX_RUNGS) s_cnt[threadIdx.x] = 0u;
-    if (threadIdx.x < 2) s_trips[threadIdx.x] = 0u;
+    if constexpr (TRACK)
+        if (threadIdx.x < 2) s_trips[threadIdx.x] = 0u;
     stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);        // (ends in a barrier)
 
     const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
@@ -114,7 +77,11 @@ __global__ __launch_bounds__(AMC_BLOCK) void exchange_tracked_kernel(const Excha
             const int64_t ia = l * a.n_rungs + r;                 // r + 1 < n_rungs: ia + 1 is a chain of the same ladder
             const real_t xa = a.x[ia], xb = a.x[ia + 1];
             const real_t ba = a.beta[ia], bb = a.beta[ia + 1];
-            const uint32_t la = ta.lab[ia], lb = ta.lab[ia + 1];
+            uint32_t la = 0u, lb = 0u;
+            if constexpr (TRACK) {
+                la = lab[ia];
+                lb = lab[ia + 1];
+            }
             const u32x4 w = philox4x32_10(draw_counter(a.chain0 + (uint64_t)ia, a.t_x, 0u, STREAM_EXCHANGE), a.key0, a.key1);
             const double u = uniform_co(w.x, w.y);
             const real_t nea = -potential<POT>(xa, s_math), neb = -potential<POT>(xb, s_math);
@@ -126,27 +93,41 @@ __global__ __launch_bounds__(AMC_BLOCK) void exchange_tracked_kernel(const Excha
                 a.x[ia] = xb;
                 a.x[ia + 1] = xa;
                 ++accepted;
-                uint32_t na = lb, nb = la;                        // the labels now at rung r and at rung r + 1
-                if (at_bottom) {
-                    round_trips += (na >> 6) == 2u;
-                    na = (na & LAB_WALKER) | LAB_UP;
+                if constexpr (TRACK) {
+                    uint32_t na = lb, nb = la;                    // the labels now at rung r and at rung r + 1
+                    if (at_bottom) {
+                        round_trips += (na >> 6) == 2u;
+                        na = (na & LAB_WALKER) | LAB_UP;
+                    }
+                    if (at_top) {
+                        up_trips += (nb >> 6) == 1u;
+                        nb = (nb & LAB_WALKER) | LAB_DOWN;
+                    }
+                    lab[ia] = (uint8_t)na;
+                    lab[ia + 1] = (uint8_t)nb;
                 }
-                if (at_top) {
-                    up_trips += (nb >> 6) == 1u;
-                    nb = (nb & LAB_WALKER) | LAB_DOWN;
-                }
-                ta.lab[ia] = (uint8_t)na;
-                ta.lab[ia + 1] = (uint8_t)nb;
             }
         }
     }
     if (attempted) atomicAdd(&s_cnt[r], attempted);
     if (accepted) atomicAdd(&s_cnt[AMC_MAX_RUNGS + r], accepted);
-    if (round_trips) atomicAdd(&s_trips[0], round_trips);
-    if (up_trips) atomicAdd(&s_trips[1], up_trips);
+    if constexpr (TRACK) {
+        if (round_trips) atomicAdd(&s_trips[0], round_trips);
+        if (up_trips) atomicAdd(&s_trips[1], up_trips);
+    }
     __syncthreads();
-    if (threadIdx.x < 2 * AMC_MAX_RUNGS && s_cnt[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
-    if (threadIdx.x < 2 && s_trips[threadIdx.x]) atomicAdd(&ta.trips[threadIdx.x], (unsigned long long)s_trips[threadIdx.x]);
+    flush_cells(s_cnt, a.counts, 2 * AMC_MAX_RUNGS);
+    if constexpr (TRACK) flush_cells(s_trips, trips, 2);
+}
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void exchange_kernel(const ExchangeArgs a)
+{
+    exchange_step<POT, false>(a, nullptr, nullptr);
+}
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void exchange_tracked_kernel(const ExchangeTrackArgs ta)
+{
+    exchange_step<POT, true>(ta.step, ta.lab, ta.trips);
 }
 
 // The flow snapshot: counts[r * 3 + d] = local chains at rung r whose label has direction d, one pass over the label bytes.  A thread
@@ -185,8 +166,7 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void rung_flow_kernel
     if (tid < head) flow_count(s_flow, (int)(tid % n_rungs), lab[tid]);                                   // head <= 3
     if (tid < n_chains - tail) flow_count(s_flow, (int)((tail + tid) % n_rungs), lab[tail + tid]);       // n_chains - tail <= 3
     __syncthreads();
-    for (int i = threadIdx.x; i < cells; i += AMC_BLOCK)
-        if (s_flow[i]) atomicAdd(&counts[i], (unsigned long long)s_flow[i]);
+    flush_cells(s_flow, counts, cells);
 }
 #endif
 
@@ -338,23 +318,14 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void rung_histogram_k
     }
     const int64_t stride = (int64_t)gridDim.x * AMC_BLOCK;
     for (int64_t c = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x; c < n_chains; c += stride) {
-        const double v = x[c];
-        int b;
-        if (v != v) b = n_bins + 2;
-        else if (v < lo) b = n_bins;
-        else if (v >= hi) b = n_bins + 1;
-        else {
-            b = (int)((v - lo) * inv_w);
-            b = b < n_bins ? b : n_bins - 1;       // (hi - ulp - lo) * inv_w can round up to n_bins
-        }
+        const int b = hist_bin(x[c], lo, hi, inv_w, n_bins);
         const int cell = (int)(c % n_rungs) * (n_bins + 3) + b;
         if (lds_rows) atomicAdd(&s_rows[cell], 1u);
         else atomicAdd(&counts[cell], 1ull);
     }
     if (lds_rows) {
         __syncthreads();
-        for (int i = threadIdx.x; i < cells; i += AMC_BLOCK)
-            if (s_rows[i]) atomicAdd(&counts[i], (unsigned long long)s_rows[i]);
+        flush_cells(s_rows, counts, cells);
     }
 }
 #endif

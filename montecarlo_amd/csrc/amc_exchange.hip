@@ -66,22 +66,12 @@ static int exchange_step(amc_handle* h)
         ta.lab = h->d_lab;
         ta.trips = h->d_track;
         const bool track = h->d_lab != nullptr;
-        if (h->use_rtc) {
-            void* params[] = {track ? (void*)&ta : (void*)&a};
-            const int rc = rtc_launch(h, (track ? "amc::exchange_tracked_kernel<" : "amc::exchange_kernel<") + std::to_string(h->potential) + ">", grid, params);
-            if (rc != AMC_OK) return rc;
-        } else {
-            const bool dw = h->potential == AMC_POTENTIAL_DOUBLE_WELL;
-            if (track && dw)
-                hipLaunchKernelGGL((amc::exchange_tracked_kernel<amc::POT_DOUBLE_WELL>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, ta);
-            else if (track)
-                hipLaunchKernelGGL((amc::exchange_tracked_kernel<amc::POT_HARMONIC>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, ta);
-            else if (dw)
-                hipLaunchKernelGGL((amc::exchange_kernel<amc::POT_DOUBLE_WELL>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
-            else
-                hipLaunchKernelGGL((amc::exchange_kernel<amc::POT_HARMONIC>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
-            AMC_HIP(hipGetLastError());
-        }
+        void* params[] = {track ? (void*)&ta : (void*)&a};
+        const int rc = track ? launch_by_potential(h, "amc::exchange_tracked_kernel", (const void*)amc::exchange_tracked_kernel<amc::POT_DOUBLE_WELL>,
+                                                   (const void*)amc::exchange_tracked_kernel<amc::POT_HARMONIC>, grid, params)
+                             : launch_by_potential(h, "amc::exchange_kernel", (const void*)amc::exchange_kernel<amc::POT_DOUBLE_WELL>,
+                                                   (const void*)amc::exchange_kernel<amc::POT_HARMONIC>, grid, params);
+        if (rc != AMC_OK) return rc;
     }
     h->t_x += 1;
     return AMC_OK;
@@ -215,17 +205,10 @@ int amc_reduce_rungs_exact(amc_handle* h, int columns, double* records)
         a.l_end = std::min(n_ladders, (i + 1) * per_launch);
         a.n_rungs = R;
         a.cols = columns;
-        if (h->use_rtc) {
-            void* params[] = {&a};
-            const int rc = rtc_launch(h, "amc::rung_sums_kernel<" + std::to_string(h->potential) + ">", grid, params);
-            if (rc != AMC_OK) return rc;
-        } else {
-            if (h->potential == AMC_POTENTIAL_DOUBLE_WELL)
-                hipLaunchKernelGGL((amc::rung_sums_kernel<amc::POT_DOUBLE_WELL>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
-            else
-                hipLaunchKernelGGL((amc::rung_sums_kernel<amc::POT_HARMONIC>), dim3(grid), dim3(AMC_BLOCK), 0, h->stream, a);
-            AMC_HIP(hipGetLastError());
-        }
+        void* params[] = {&a};
+        const int rc = launch_by_potential(h, "amc::rung_sums_kernel", (const void*)amc::rung_sums_kernel<amc::POT_DOUBLE_WELL>,
+                                           (const void*)amc::rung_sums_kernel<amc::POT_HARMONIC>, grid, params);
+        if (rc != AMC_OK) return rc;
     }
     const int n_slots = R * amc::RED_COLS;
     hipLaunchKernelGGL(amc::rung_finish_kernel, dim3(n_slots), dim3(64), 0, h->stream, (const amc::xs_word*)h->d_rung_rows,

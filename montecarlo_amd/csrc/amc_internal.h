@@ -302,3 +302,14 @@ AMC_INTERNAL int rtc_compile(const ModelSpec& spec, const std::string& inst, con
                              std::string* log_out);
 AMC_INTERNAL int rtc_function(amc_handle* h, const std::string& inst, hipFunction_t* fn);
 AMC_INTERNAL int rtc_launch(amc_handle* h, const std::string& inst, int grid, void** params);
+
+// One launch of a kernel whose only template argument is the potential: the instantiation name<potential> compiled at run time
+// (use_rtc), or the offline one of the built-in potential at hand.  AMC_BLOCK threads, no dynamic LDS, the handle's stream; params
+// as hipLaunchKernel takes them.
+static inline int launch_by_potential(amc_handle* h, const char* name, const void* double_well, const void* harmonic, int grid, void** params)
+{
+    if (h->use_rtc) return rtc_launch(h, std::string(name) + "<" + std::to_string(h->potential) + ">", grid, params);
+    (void)hipLaunchKernel(h->potential == AMC_POTENTIAL_DOUBLE_WELL ? double_well : harmonic, dim3(grid), dim3(AMC_BLOCK), params, 0, h->stream);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}

@@ -148,30 +148,15 @@ int amc_reduce_begin(amc_handle* h)
     // amc_reduce_end (integers: amc_xsum.h) -- no final-pass launches (~5 us each even when empty) and no D2H copy in
     // stream order (which would hold the next sweep back for a copy-engine round trip).
     amc::xs_word* rows = t->h_rows;
-    const int stride = red_row_stride(h, h->red_blocks);
+    int stride = red_row_stride(h, h->red_blocks);
     int cols = h->red_cols;
     const unsigned long long* slots = (ratio_mode == 0 && t->ratio_rows == 0) ? h->d_acc_slots : nullptr;
     unsigned long long* racc = t->d_ratio_acc;
-    if (h->use_rtc) {
-        const double* d_x = h->d_x;
-        const uint32_t *d_acc = h->d_acc, *d_tot = h->d_tot;
-        int64_t m = h->M, m_pad = h->M_pad;
-        int k = h->K, mode = ratio_mode, st = stride, n_slots = h->n_slots;
-        uint64_t t_counted = h->t_counted;
-        const unsigned long long *acc_base = h->d_acc_base, *tot_base = h->d_tot_base;
-        uint64_t t_base = h->t_base;
-        void* params[] = {&d_x, &d_acc, &d_tot, &m, &m_pad, &k, &mode, &t_counted, &rows, &st, &slots, &n_slots, &racc, &cols, &acc_base, &tot_base, &t_base};
-        const int rc = rtc_launch(h, "amc::reduce_kernel<" + std::to_string(h->potential) + ">", h->red_blocks, params);
-        if (rc != AMC_OK) return rc;
-    } else if (h->potential == AMC_POTENTIAL_DOUBLE_WELL)
-        hipLaunchKernelGGL(amc::reduce_kernel<amc::POT_DOUBLE_WELL>, dim3(h->red_blocks), dim3(AMC_BLOCK), 0, h->stream,
-                           h->d_x, h->d_acc, h->d_tot, h->M, h->M_pad, h->K, ratio_mode, h->t_counted, rows, stride, slots,
-                           h->n_slots, racc, cols, h->d_acc_base, h->d_tot_base, h->t_base);
-    else
-        hipLaunchKernelGGL(amc::reduce_kernel<amc::POT_HARMONIC>, dim3(h->red_blocks), dim3(AMC_BLOCK), 0, h->stream,
-                           h->d_x, h->d_acc, h->d_tot, h->M, h->M_pad, h->K, ratio_mode, h->t_counted, rows, stride, slots,
-                           h->n_slots, racc, cols, h->d_acc_base, h->d_tot_base, h->t_base);
-    AMC_HIP(hipGetLastError());
+    void* params[] = {&h->d_x, &h->d_acc, &h->d_tot, &h->M, &h->M_pad, &h->K, &ratio_mode, &h->t_counted, &rows, &stride, &slots, &h->n_slots, &racc, &cols,
+                      &h->d_acc_base, &h->d_tot_base, &h->t_base};
+    const int rc = launch_by_potential(h, "amc::reduce_kernel", (const void*)amc::reduce_kernel<amc::POT_DOUBLE_WELL>, (const void*)amc::reduce_kernel<amc::POT_HARMONIC>,
+                                       h->red_blocks, params);
+    if (rc != AMC_OK) return rc;
     if (t->ratio_acc)
         AMC_HIP(hipMemcpyAsync(t->h_ratio_acc, t->d_ratio_acc, (size_t)h->K * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                h->stream));

@@ -61,6 +61,37 @@ static int positions_f64(amc_handle* h, const double** out)
     return widen_to_x64(h);
 }
 
+// What every histogram entry asks of its bins; the message is left for amc_last_error().
+static bool hist_args_ok(const char* who, double lo, double hi, int n_bins)
+{
+    if (n_bins >= 1 && n_bins <= 8192 && hi > lo && std::isfinite(lo) && std::isfinite(hi)) return true;
+    fail(AMC_ERR_BAD_ARG, "%s: need 1 <= n_bins <= 8192 and finite lo < hi", who);
+    return false;
+}
+
+// A histogram launch into a scratch buffer of `cells` cleared counters, copied to the caller's `counts`: launch(d_pos, d_counts) queues
+// the kernel on the stream.  The buffer is freed on every path.
+template <class Launch>
+static int hist_to_host(amc_handle* h, const char* who, int cells, uint64_t* counts, Launch launch)
+{
+    unsigned long long* d_counts = nullptr;
+    const size_t bytes = (size_t)cells * sizeof(unsigned long long);
+    AMC_HIP(hipMalloc(&d_counts, bytes));
+    hipError_t e = hipMemsetAsync(d_counts, 0, bytes, h->stream);
+    const double* d_pos = nullptr;
+    const int rc = e == hipSuccess ? positions_f64(h, &d_pos) : AMC_OK;
+    if (e == hipSuccess && rc == AMC_OK) {
+        launch(d_pos, d_counts);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, bytes, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    }
+    (void)hipFree(d_counts);
+    if (rc != AMC_OK) return rc;
+    if (e != hipSuccess) return fail(AMC_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return AMC_OK;
+}
+
 extern "C" {
 
 int amc_upload_state(amc_handle* h, const double* x, const double* beta_or_null)
@@ -162,57 +193,34 @@ static int hist_grid(const amc_handle* h)
 int amc_histogram(amc_handle* h, double lo, double hi, int n_bins, uint64_t* counts)
 {
     if (!h || !counts) return fail(AMC_ERR_BAD_ARG, "amc_histogram: NULL argument");
-    if (n_bins < 1 || n_bins > 8192 || !(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi))
-        return fail(AMC_ERR_BAD_ARG, "amc_histogram: need 1 <= n_bins <= 8192 and finite lo < hi");
+    if (!hist_args_ok("amc_histogram", lo, hi, n_bins)) return AMC_ERR_BAD_ARG;
     AMC_HIP(hipSetDevice(h->device));
-    unsigned long long* d_counts = nullptr;
-    const size_t bytes = (size_t)(n_bins + 3) * sizeof(unsigned long long);
-    AMC_HIP(hipMalloc(&d_counts, bytes));
-    AMC_HIP(hipMemsetAsync(d_counts, 0, bytes, h->stream));
     const double inv_w = (double)n_bins / (hi - lo);
-    const double* d_pos = nullptr;
-    { const int rc = positions_f64(h, &d_pos); if (rc != AMC_OK) { (void)hipFree(d_counts); return rc; } }
-    hipLaunchKernelGGL(amc::histogram_kernel, dim3(hist_grid(h)), dim3(AMC_BLOCK), (size_t)(n_bins + 3) * sizeof(unsigned int),
-                       h->stream, d_pos, h->M, lo, hi, inv_w, n_bins, d_counts);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_counts);
-    if (e != hipSuccess) return fail(AMC_ERR_HIP, "amc_histogram: %s", hipGetErrorString(e));
-    return AMC_OK;
+    return hist_to_host(h, "amc_histogram", n_bins + 3, counts, [&](const double* d_pos, unsigned long long* d_counts) {
+        hipLaunchKernelGGL(amc::histogram_kernel, dim3(hist_grid(h)), dim3(AMC_BLOCK), (size_t)(n_bins + 3) * sizeof(unsigned int),
+                           h->stream, d_pos, h->M, lo, hi, inv_w, n_bins, d_counts);
+    });
 }
 
 int amc_histogram_rungs(amc_handle* h, double lo, double hi, int n_bins, uint64_t* counts)
 {
     if (!h || !counts) return fail(AMC_ERR_BAD_ARG, "amc_histogram_rungs: NULL argument");
     if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_histogram_rungs: the handle has no ladder (amc_set_ladder)");
-    if (n_bins < 1 || n_bins > 8192 || !(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi))
-        return fail(AMC_ERR_BAD_ARG, "amc_histogram_rungs: need 1 <= n_bins <= 8192 and finite lo < hi");
+    if (!hist_args_ok("amc_histogram_rungs", lo, hi, n_bins)) return AMC_ERR_BAD_ARG;
     AMC_HIP(hipSetDevice(h->device));
     const int cells = (n_bins + 3) * h->n_rungs;
-    unsigned long long* d_counts = nullptr;
-    const size_t bytes = (size_t)cells * sizeof(unsigned long long);
-    AMC_HIP(hipMalloc(&d_counts, bytes));
-    AMC_HIP(hipMemsetAsync(d_counts, 0, bytes, h->stream));
     const double inv_w = (double)n_bins / (hi - lo);
-    const double* d_pos = nullptr;
-    { const int rc = positions_f64(h, &d_pos); if (rc != AMC_OK) { (void)hipFree(d_counts); return rc; } }
     const int lds_rows = cells <= 12288 ? 1 : 0;      // 48 KiB of u32 counters; beyond that one global atomic per position
-    hipLaunchKernelGGL(amc::rung_histogram_kernel, dim3(hist_grid(h)), dim3(AMC_BLOCK), lds_rows ? (size_t)cells * sizeof(unsigned int) : 0,
-                       h->stream, d_pos, h->M, h->n_rungs, lo, hi, inv_w, n_bins, lds_rows, d_counts);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_counts);
-    if (e != hipSuccess) return fail(AMC_ERR_HIP, "amc_histogram_rungs: %s", hipGetErrorString(e));
-    return AMC_OK;
+    return hist_to_host(h, "amc_histogram_rungs", cells, counts, [&](const double* d_pos, unsigned long long* d_counts) {
+        hipLaunchKernelGGL(amc::rung_histogram_kernel, dim3(hist_grid(h)), dim3(AMC_BLOCK), lds_rows ? (size_t)cells * sizeof(unsigned int) : 0,
+                           h->stream, d_pos, h->M, h->n_rungs, lo, hi, inv_w, n_bins, lds_rows, d_counts);
+    });
 }
 
 int amc_histogram_accumulate(amc_handle* h, double lo, double hi, int n_bins)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_histogram_accumulate: NULL handle");
-    if (n_bins < 1 || n_bins > 8192 || !(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi))
-        return fail(AMC_ERR_BAD_ARG, "amc_histogram_accumulate: need 1 <= n_bins <= 8192 and finite lo < hi");
+    if (!hist_args_ok("amc_histogram_accumulate", lo, hi, n_bins)) return AMC_ERR_BAD_ARG;
     AMC_HIP(hipSetDevice(h->device));
     if (h->d_hist && (n_bins != h->hist_bins || lo != h->hist_lo || hi != h->hist_hi))
         return fail(AMC_ERR_STATE, "amc_histogram_accumulate: the running histogram has other bins (fetch it with reset first)");

@@ -91,8 +91,12 @@ class ExchangeTwin:
                     if swap_decision(self.pot, x[a], x[a + 1], self.beta[a], self.beta[a + 1], u, self.f32):
                         x[a], x[a + 1] = x[a + 1], x[a]
                         self.accepted[r] += 1
+                        self._swapped(a, r)
             self.state.put(x, self.pot)
             self.t_x += 1
+
+    def _swapped(self, a: int, r: int):
+        """Called once per accepted swap of gap r, after x[a] and x[a + 1] have changed places (track_twin.TrackTwin: the labels)."""
 
     def sweep(self, n: int = 1):
         s = self.sim

@@ -273,20 +273,25 @@ def test_histogram_by_rung(gpu, dtype):
     x = eng.download_state()[0]
     x[7], x[13] = np.nan, np.inf
     eng.upload_state(x)
+
+    def expected(n):
+        want = np.zeros((R, n + 3), dtype=np.uint64)
+        inv_w = n / (hi - lo)
+        for r in range(R):
+            v = x[r::R]
+            nan = np.isnan(v)
+            below, above = (v < lo) & ~nan, (v >= hi) & ~nan
+            inside = ~(nan | below | above)
+            want[r, :n] = np.bincount(np.minimum(((v[inside] - lo) * inv_w).astype(np.int64), n - 1), minlength=n)
+            want[r, n], want[r, n + 1], want[r, n + 2] = below.sum(), above.sum(), nan.sum()
+        return want
+
     got = eng.histogram_rungs(lo, hi, nb)
     assert got.shape == (R, nb + 3)
-    inv_w = nb / (hi - lo)
-    for r in range(R):
-        v = x[r::R]
-        nan = np.isnan(v)
-        below, above = (v < lo) & ~nan, (v >= hi) & ~nan
-        inside = ~(nan | below | above)
-        want = np.zeros(nb + 3, dtype=np.uint64)
-        want[:nb] = np.bincount(np.minimum(((v[inside] - lo) * inv_w).astype(np.int64), nb - 1), minlength=nb)
-        want[nb], want[nb + 1], want[nb + 2] = below.sum(), above.sum(), nan.sum()
-        assert np.array_equal(got[r], want), r
+    assert np.array_equal(got, expected(nb)), np.argwhere(got != expected(nb))
     assert np.array_equal(got.sum(axis=0), eng.histogram(lo, hi, nb))
-    wide = eng.histogram_rungs(lo, hi, 4000)                   # rows too large for LDS: the global-atomic form
+    wide = eng.histogram_rungs(lo, hi, 4000)                   # rows too large for LDS: the global-atomic form, the same bin rule
+    assert np.array_equal(wide, expected(4000)), np.argwhere(wide != expected(4000))
     assert np.array_equal(wide.sum(axis=0), eng.histogram(lo, hi, 4000)) and wide.sum() == R * L
     eng.close()
 

@@ -2,7 +2,7 @@
 
 Written from the DESIGN text: one label per local chain, lab = w | (d << 6); an accepted swap of gap r exchanges the two labels along
 with x, then the label now at rung 0 (r == 0) or at rung R - 1 (r + 1 == R - 1) counts a trip when it last visited the other end and
-takes the direction of the end it arrived at.  The decision is ExchangeTwin's: the same gaps_of_step, draw_uniform, swap_decision.
+takes the direction of the end it arrived at.  The step and its decision are ExchangeTwin's; TrackTwin fills in its per-swap hook.
 It shares no code with the product."""
 import numpy as np
 
@@ -45,29 +45,17 @@ class TrackTwin(X.ExchangeTwin):
         self.lab = initial_labels(self.beta.size, self.R) if on else None
         self.round_trips = self.up_trips = 0
 
-    def exchange(self, n: int = 1):
-        if self.lab is None:
-            return super().exchange(n)
-        R, lab = self.R, self.lab
-        for _ in range(int(n)):
-            x = self.state.get()
-            for r in X.gaps_of_step(R, self.t_x):
-                for a in range(r, x.size, R):
-                    u = X.draw_uniform(self.seed, self.offset + a, self.t_x)
-                    self.attempted[r] += 1
-                    if not X.swap_decision(self.pot, x[a], x[a + 1], self.beta[a], self.beta[a + 1], u, self.f32):
-                        continue                                    # a rejected swap writes nothing
-                    x[a], x[a + 1] = x[a + 1], x[a]
-                    lab[a], lab[a + 1] = lab[a + 1], lab[a]
-                    self.accepted[r] += 1
-                    if r == 0:
-                        self.round_trips += int(lab[a] >> 6 == DOWN)
-                        lab[a] = (lab[a] & 63) | (UP << 6)
-                    if r + 1 == R - 1:
-                        self.up_trips += int(lab[a + 1] >> 6 == UP)
-                        lab[a + 1] = (lab[a + 1] & 63) | (DOWN << 6)
-            self.state.put(x, self.pot)
-            self.t_x += 1
+    def _swapped(self, a: int, r: int):
+        lab = self.lab
+        if lab is None:
+            return
+        lab[a], lab[a + 1] = lab[a + 1], lab[a]
+        if r == 0:
+            self.round_trips += int(lab[a] >> 6 == DOWN)
+            lab[a] = (lab[a] & 63) | (UP << 6)
+        if r + 1 == self.R - 1:
+            self.up_trips += int(lab[a + 1] >> 6 == UP)
+            lab[a + 1] = (lab[a + 1] & 63) | (DOWN << 6)
 
     def flow_rungs(self):
         return flow_counts(self.lab, self.R)
