@@ -53,6 +53,9 @@ AmcKnobs amc_knobs()
     k.no_column_skip = flag("AMC_NO_COLUMN_SKIP");
     k.np_small_launches = flag("AMC_NP_SMALL_LAUNCHES");
     k.no_sweep_estimator_fusion = set("AMC_NO_SWEEP_ESTIMATOR_FUSION");
+    k.sweep_slices = in("AMC_SWEEP_SLICES", 1, amc::AMC_MAX_SLICES);
+    k.sweep_slice_blocks_per_cu = in("AMC_SWEEP_SLICE_BLOCKS_PER_CU", 1, 64);
+    { const char* e = amc_env("AMC_SWEEP_SLICE_MIN_CHAINS"); const long long v = e && *e ? std::atoll(e) : -1; k.sweep_slice_min_chains = v >= 0 ? v : -1; }
     k.debug_plan = set("AMC_DEBUG_PLAN");
     k.rtc_licm = text("AMC_RTC_LICM");
     k.rtc_waves_set = set("AMC_RTC_WAVES");
@@ -233,6 +236,9 @@ static int create_impl(const amc_config* cfg, const ModelSpec& spec, amc_handle*
     if (h->knobs.blocks_per_cu) h->blocks_per_cu = h->blocks_per_cu_single = h->blocks_per_cu_pg = h->knobs.blocks_per_cu;
     if (h->knobs.blocks_per_cu_single) h->blocks_per_cu_single = h->knobs.blocks_per_cu_single;
     if (h->knobs.blocks_per_cu_reduce) h->blocks_per_cu_red = h->knobs.blocks_per_cu_reduce;
+    if (h->knobs.sweep_slices) h->sweep_slices = h->knobs.sweep_slices;
+    if (h->knobs.sweep_slice_blocks_per_cu) h->slice_blocks_per_cu = h->knobs.sweep_slice_blocks_per_cu;
+    if (h->knobs.sweep_slice_min_chains >= 0) h->slice_min_chains = h->knobs.sweep_slice_min_chains;
     h->M = cfg->n_chains;
     // padding: unclamped 16-B tail loads stay in bounds; rows of every per-chain array start on a 256-byte boundary
     // (M_pad is a multiple of 256): a wave's 128-byte step-log store then covers exactly one aligned line
@@ -538,6 +544,11 @@ int amc_destroy(amc_handle* h)
     }
     (void)hipFree(h->d_out);
     if (h->h_pg_out) (void)hipHostFree(h->h_pg_out);
+    for (int i = 0; i < amc::AMC_MAX_SLICES - 1; ++i) {
+        if (h->slice_stream[i]) { (void)hipStreamSynchronize(h->slice_stream[i]); (void)hipStreamDestroy(h->slice_stream[i]); }
+        if (h->slice_join[i]) (void)hipEventDestroy(h->slice_join[i]);
+    }
+    if (h->slice_fork) (void)hipEventDestroy(h->slice_fork);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "amc_kernels.h"
+#include "amc_slices.h"
 
 #ifndef AMC_BUILD_ARCH
 #define AMC_BUILD_ARCH "gfx950"      // the Makefile passes the arch the offline kernels were compiled for
@@ -75,6 +76,9 @@ struct AmcKnobs {
     bool no_column_skip = false;      // AMC_NO_COLUMN_SKIP             flag             off      dev: fused script steps sum every column
     bool np_small_launches = false;   // AMC_NP_SMALL_LAUNCHES          flag             off      dev: P > 1, several moves: records + small launches
     bool no_sweep_estimator_fusion = false;  // AMC_NO_SWEEP_ESTIMATOR_FUSION  set       off      dev: no sweep rides in an estimator launch
+    int sweep_slices = 0;             // AMC_SWEEP_SLICES               1..3             0: none  tuning: concurrent slices of a single-sweep launch (default 2)
+    int sweep_slice_blocks_per_cu = 0;  // AMC_SWEEP_SLICE_BLOCKS_PER_CU  1..64          0: none  tuning: blocks per CU of each slice's launch (default 3)
+    int64_t sweep_slice_min_chains = -1;  // AMC_SWEEP_SLICE_MIN_CHAINS  >= 0           -1: none tuning: smallest shard that takes the sliced route (2 500 000)
     bool debug_plan = false;          // AMC_DEBUG_PLAN                 set              off      dev: the estimator's launch plans on stderr
     std::string rtc_licm;             // AMC_RTC_LICM                   all-off, est-off, off-for-none: run-time builds without Machine LICM
     bool rtc_waves_set = false;       // AMC_RTC_WAVES                  integer          unset    dev: waves per EU of script estimator forms
@@ -213,6 +217,15 @@ struct amc_handle {
     std::map<int, std::string> class_form_errors;  // pools of several classes: the several-move estimator forms (nl, sweep, reduce) that do NOT build, with
                                                    // the compiler's last words about each (amc_pg.hip class_general_route, amc_pg_route)
     std::string class_form_error;   // ... of the form the last class_general_route call asked about ("" when it builds)
+    // Single-sweep launches in slices (amc_sweeps.hip sweep_launches_sliced): slice 0 runs on `stream`, the others on streams of
+    // the handle's own, made at the first sliced call; forked and joined with events once per call
+    // (defaults by the ladder of profiles/sliced_launches_ab.md: two slices of 3 blocks per CU each, 25.6 against 28.4 us per step at 1e7
+    // chains; the smallest size of the ladder at which slices are not slower)
+    int sweep_slices = 2;                // S: slices of a single-sweep launch (1: whole launches; set back to 1 for good when a stream cannot be made)
+    int slice_blocks_per_cu = 3;         // blocks per CU of each slice's launch
+    int64_t slice_min_chains = 2500000;  // shards below it keep whole launches
+    hipStream_t slice_stream[amc::AMC_MAX_SLICES - 1] = {nullptr, nullptr};
+    hipEvent_t slice_fork = nullptr, slice_join[amc::AMC_MAX_SLICES - 1] = {nullptr, nullptr};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     unsigned long long* d_hist = nullptr;   // running histogram of amc_histogram_accumulate: [hist_bins + 3]
     int hist_bins = 0;
