@@ -6,10 +6,13 @@ A temperature ladder with neighbour swaps (ReplicaExchange) lets positions trave
 down.  Every chain starts in the right well; the script runs the same schedule with and without exchange steps and prints, per
 rung, the fraction of chains left of the barrier, the mean energy and the swap acceptance of every gap.
 
-    python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track]
+    python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track] [--rung-sigma]
 
 --track also follows every replica through the swaps and prints, at the end, the flow fraction f(r) -- of the replicas at rung r that
 have been to an end of the ladder, the share that came from the hot end (rung 0) last -- and the round trips per ladder.
+
+--rung-sigma gives every rung a proposal width of its own, sigma_r = sigma_0 sqrt(beta_0 / beta_r) (Metropolis(..., rung_sigma=...)): the
+hot rungs then take the long steps they are there for.  The acceptance of the move per rung is printed beside the swap acceptance.
 """
 import argparse
 import os
@@ -21,14 +24,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import montecarlo_amd as ma   # noqa: E402
 
 BETAS = (0.5, 1.0, 2.0, 4.0, 8.0)
+SIGMA0 = 0.3
 
 
 def one_run(args, path, exchange: bool):
     R, L = len(BETAS), args.ladders
     x0 = 0.8 + 0.4 * ((np.arange(R * L) * 0.6180339887498949) % 1.0)          # every chain in the right well
     chains = ma.ParticleChains.ladder(L, BETAS, potential="double_well", x=x0)
-    pool = (ma.Move(ma.Displacement(0.0), ma.StandardGaussian(), [0.3], 1.0),)
+    pool = (ma.Move(ma.Displacement(0.0), ma.StandardGaussian(), [SIGMA0], 1.0),)
     algorithm_list = [dict(algorithm=ma.Metropolis, pool=pool, seed=args.seed)]
+    if exchange and args.rung_sigma:
+        # sigma_0 is the width of the hottest rung; the equilibrium width of a well shrinks like 1 / sqrt(beta)
+        algorithm_list[0]["rung_sigma"] = [SIGMA0 * np.sqrt(BETAS[0] / b) for b in BETAS]
     callbacks = [ma.callback_energy]
     if exchange:
         algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), track=args.track))   # every time step
@@ -52,6 +59,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--path", default=None)
     ap.add_argument("--track", action="store_true", help="follow the replicas: print the flow fraction per rung and the round trips")
+    ap.add_argument("--rung-sigma", action="store_true", help="a proposal width per rung, sigma_r = sigma_0 sqrt(beta_0 / beta_r); print the move's acceptance per rung")
     args = ap.parse_args(argv)
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
@@ -62,6 +70,9 @@ def main(argv=None):
     print("mean energy, with exchange    : " + "  ".join(f"{v:7.4f}" for v in energy))
     print("mean energy, without          : " + "  ".join(f"{v:7.4f}" for v in energy_plain))
     print("swap acceptance per gap       : " + "  ".join(f"{v:7.4f}" for v in accept))
+    if args.rung_sigma:
+        print("proposal width per rung       : " + "  ".join(f"{v:7.4f}" for v in sim.algorithms[0].rung_sigma[0]))
+        print("move acceptance per rung      : " + "  ".join(f"{v:7.4f}" for v in ma.callback_rung_acceptance(sim)[0]))
     print("coldest rung, 8 bins of [-2, 2): " + " ".join(str(int(v)) for v in hist[-1][:8]))
     if args.track:
         rx = sim.algorithms[1]

@@ -402,6 +402,25 @@ int  amc_upload_labels(amc_handle *h, const uint8_t *labels);
 int  amc_flow_rungs(amc_handle *h, uint64_t *counts);
 int  amc_tracking_counters(amc_handle *h, int64_t *round_trips, int64_t *up_trips);
 int  amc_set_tracking_counters(amc_handle *h, int64_t round_trips, int64_t up_trips);
+/* Proposal widths per rung (DESIGN.md section 3.13 "Widths per rung"): sigma[k * R + r] is the width of move k for the chains at rung r
+ * (r = global chain id mod R), n = K * R <= AMC_MAX_MOVES.  While a table is set, every sweep steps chain c with the widths of its rung:
+ * bit for bit chain c of a handle without a table whose pool has sigma_k = sigma[k * R + (c mod R)].  The move pick (the pool's weights),
+ * the step log and the Move counters know nothing of rungs; exchange steps, tracking, rung sums and histograms are untouched: sigma stays
+ * with the rung, like beta.  amc_set_parameters / amc_get_parameters go on writing and reading the pool's shared sigma_k, which the sweeps
+ * then do not use.  sigma == NULL or n == 0 clears the table (never an error); amc_set_ladder clears it on every call that succeeds.
+ * Stream-ordered behind what is queued (a pending learning step is taken first); does not synchronise.
+ * AMC_ERR_STATE: no ladder, per_chain_counters = 0, param_dtype = AMC_DTYPE_F32, a handle made by amc_create_policy_model /
+ * _proposal_model / _vector_policy_model / _mixed_model (script-defined policies, classes, actions).  AMC_ERR_BAD_ARG naming the entry:
+ * K * R > AMC_MAX_MOVES, n != K * R, a sigma that is not finite in [1e-100, 1e100]; the handle stays as it was.  While a table is set every
+ * estimator entry (amc_pg_*, amc_pgmc_steps*) returns AMC_ERR_STATE before any launch: the estimator learns one sigma per move.
+ * amc_get_rung_sigma: the table as it was given (AMC_ERR_STATE when none is set). */
+int  amc_set_rung_sigma(amc_handle *h, const double *sigma, int n);
+int  amc_get_rung_sigma(amc_handle *h, double *sigma, int n);
+/* Move.accepted_calls / total_calls summed over the local ladders per (move, rung): accepted[k * R + r], total[k * R + r], exact 64-bit
+ * integers formed on the device (add across shards); their sum over r is amc_counter_totals.  Needs a ladder and per-chain counters
+ * (AMC_ERR_STATE otherwise), with or without widths per rung.  Folds pending rows of the step log first, synchronises, changes nothing.
+ * Either output may be NULL. */
+int  amc_rung_counter_totals(amc_handle *h, int64_t *accepted, int64_t *total);
 
 /* MH steps done per chain so far (the Philox step index); settable for resume. */
 int  amc_get_step(amc_handle *h, uint64_t *t);

@@ -170,6 +170,9 @@ def load() -> C.CDLL:
         "amc_flow_rungs": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "amc_tracking_counters": (C.c_int, [H, i64p, i64p]),
         "amc_set_tracking_counters": (C.c_int, [H, C.c_int64, C.c_int64]),
+        "amc_set_rung_sigma": (C.c_int, [H, dp, C.c_int]),
+        "amc_get_rung_sigma": (C.c_int, [H, dp, C.c_int]),
+        "amc_rung_counter_totals": (C.c_int, [H, i64p, i64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -726,6 +729,32 @@ class HipEngine:
 
     def set_tracking_counters(self, round_trips: int, up_trips: int) -> None:
         _check(self._lib.amc_set_tracking_counters(self._h, int(round_trips), int(up_trips)))
+
+    # -- proposal widths per rung (include/amc.h; DESIGN.md section 3.13 "Widths per rung") ----------------
+    def set_rung_sigma(self, sigma) -> None:
+        """``sigma[K][R]``: the width of move k for the chains at rung r (needs a ladder and per-chain counters); ``None`` clears the
+        table.  Stream-ordered; the sweeps that follow step every chain with the widths of its rung."""
+        if sigma is None:
+            _check(self._lib.amc_set_rung_sigma(self._h, None, 0))
+            return
+        s = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
+        _check(self._lib.amc_set_rung_sigma(self._h, _dptr(s), int(s.size)))
+
+    def rung_sigma(self) -> np.ndarray:
+        """The table as it was set, shape (K, R)."""
+        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        out = np.zeros((self.n_moves, n), dtype=np.float64)
+        _check(self._lib.amc_get_rung_sigma(self._h, _dptr(out), int(out.size)))
+        return out
+
+    def rung_counter_totals(self):
+        """(accepted, total), each of shape (K, R): the Move counters summed over this shard's ladders per (move, rung), exact."""
+        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        acc = np.zeros((self.n_moves, n), dtype=np.int64)
+        tot = np.zeros((self.n_moves, n), dtype=np.int64)
+        p = C.POINTER(C.c_int64)
+        _check(self._lib.amc_rung_counter_totals(self._h, acc.ctypes.data_as(p), tot.ctypes.data_as(p)))
+        return acc, tot
 
     def sync(self) -> None:
         _check(self._lib.amc_sync(self._h))

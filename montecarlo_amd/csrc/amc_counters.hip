@@ -312,6 +312,55 @@ int amc_counter_totals(amc_handle* h, int64_t* accepted, int64_t* total)
     return AMC_OK;
 }
 
+int amc_rung_counter_totals(amc_handle* h, int64_t* accepted, int64_t* total)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_rung_counter_totals: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_rung_counter_totals: the handle has no ladder (amc_set_ladder)");
+    if (!h->counters) return fail(AMC_ERR_STATE, "amc_rung_counter_totals: handle was created with per_chain_counters = 0");
+    AMC_HIP(hipSetDevice(h->device));
+    { const int rc = fold_log(h); if (rc != AMC_OK) return rc; }
+    const int R = h->n_rungs;
+    const size_t cells = (size_t)h->K * (size_t)R;
+    if (cells > h->rung_cnt_cells) {
+        AMC_HIP(hipStreamSynchronize(h->stream));               // (nothing queued reads the old cells after this call's predecessor returned)
+        (void)hipFree(h->d_rung_cnt);
+        h->d_rung_cnt = nullptr;
+        h->rung_cnt_cells = 0;
+        AMC_HIP(hipMalloc(&h->d_rung_cnt, 2 * cells * sizeof(unsigned long long)));
+        h->rung_cnt_cells = cells;
+    }
+    unsigned long long* out_acc = h->d_rung_cnt;
+    unsigned long long* out_tot = h->d_rung_cnt + cells;
+    AMC_HIP(hipMemsetAsync(h->d_rung_cnt, 0, 2 * cells * sizeof(unsigned long long), h->stream));
+    const int grid = grid_for(h, h->M);
+    if (h->narrow)
+        hipLaunchKernelGGL(amc::rung_counter_totals_kernel<uint16_t>, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint16_t*)h->d_acc16,
+                           (const uint16_t*)h->d_tot16, (const uint16_t*)(h->use_high ? h->d_acc_hi : nullptr),
+                           (const uint16_t*)(h->use_high ? h->d_tot_hi : nullptr), (const unsigned long long*)h->d_acc_base,
+                           (const unsigned long long*)h->d_tot_base, h->M, h->M_pad, h->K, R, out_acc, out_tot);
+    else
+        hipLaunchKernelGGL(amc::rung_counter_totals_kernel<uint32_t>, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint32_t*)h->d_acc,
+                           (const uint32_t*)h->d_tot, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const unsigned long long*)h->d_acc_base,
+                           (const unsigned long long*)h->d_tot_base, h->M, h->M_pad, h->K, R, out_acc, out_tot);
+    AMC_HIP(hipGetLastError());
+    std::vector<unsigned long long> host(2 * cells);
+    AMC_HIP(hipMemcpyAsync(host.data(), h->d_rung_cnt, 2 * cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    // the last move's total: every chain of a rung has taken all counted steps, what the other moves left is its own
+    const unsigned long long steps_per_rung = (h->t_base + h->t_counted) * (uint64_t)(h->M / R);
+    for (int r = 0; r < R; ++r) {
+        unsigned long long others = 0;
+        for (int k = 0; k < h->K; ++k) {
+            const size_t e = (size_t)k * (size_t)R + (size_t)r;
+            const unsigned long long tk = (k + 1 < h->K) ? host[cells + e] : steps_per_rung - others;
+            others += tk;
+            if (accepted) accepted[e] = (int64_t)host[e];
+            if (total) total[e] = (int64_t)tk;
+        }
+    }
+    return AMC_OK;
+}
+
 int amc_upload_counters(amc_handle* h, const int64_t* accepted, const int64_t* total)
 {
     if (!h || !accepted) return fail(AMC_ERR_BAD_ARG, "amc_upload_counters: NULL argument");

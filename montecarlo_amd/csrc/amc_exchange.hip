@@ -1,6 +1,7 @@
 // amc_exchange.hip -- replica exchange along a temperature ladder: the ladder of a handle, exchange steps
 // (amc_exchange, amc_sweep_exchange), the per-gap counters and the exchange step index, the per-rung reproducible sums
-// (amc_reduce_rungs_exact), walker tracking (amc_set_tracking .. amc_set_tracking_counters).  amc_histogram_rungs is with the other
+// (amc_reduce_rungs_exact), walker tracking (amc_set_tracking .. amc_set_tracking_counters), proposal widths per rung
+// (amc_set_rung_sigma, amc_get_rung_sigma).  amc_histogram_rungs is with the other
 // histograms in amc_state.hip.
 #define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copies of the plain kernels it launches (rung_finish_kernel, rung_flow_kernel)
 #include "amc_internal.h"
@@ -85,6 +86,7 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
     if (n_rungs == 0) {
         AMC_HIP(hipSetDevice(h->device));
         { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }
+        h->rung_on = false;
         h->n_rungs = 0;
         return AMC_OK;
     }
@@ -104,7 +106,60 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
     { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }      // another ladder has other walkers
     if (!h->d_xcnt) AMC_HIP(hipMalloc(&h->d_xcnt, XCNT_BYTES));
     AMC_HIP(hipMemsetAsync(h->d_xcnt, 0, XCNT_BYTES, h->stream));      // the gaps of another ladder are other gaps
+    h->rung_on = false;                                                // ... and its rungs other rungs: no widths per rung until they are set again
     h->n_rungs = n_rungs;
+    return AMC_OK;
+}
+
+// ---- proposal widths per rung (DESIGN.md section 3.13 "Widths per rung") --------------------------------------------------------------
+int amc_set_rung_sigma(amc_handle* h, const double* sigma, int n)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_rung_sigma: NULL handle");
+    if (!sigma || n == 0) {              // no table: the sweeps read the pool's sigma_k again
+        // Host state only, so no hipSetDevice: the next sweep picks its form from this flag when it is queued, and the table's
+        // memory stays for the sweeps already queued.  No pg_resolve either: every estimator entry is refused while a table is
+        // set, and setting it took the step that was pending then, so none can be pending here.
+        h->rung_on = false;
+        return AMC_OK;
+    }
+    if (!h->model.classes.empty() || h->script_policy || h->scaled_policy || h->n_params > 1 || h->n_classes > 1)
+        return fail(AMC_ERR_STATE, "amc_set_rung_sigma: widths per rung belong to the built-in Gaussian policy; this handle has a script-defined policy, "
+                                   "class or action");
+    if (h->param_f32)
+        return fail(AMC_ERR_STATE, "amc_set_rung_sigma: not available with param_dtype = AMC_DTYPE_F32 (the rung table holds Float64 widths)");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_rung_sigma: the handle has no ladder (amc_set_ladder)");
+    if (!h->counters)
+        return fail(AMC_ERR_STATE, "amc_set_rung_sigma: handle was created with per_chain_counters = 0 (the acceptance per rung needs them)");
+    const int R = h->n_rungs;
+    if (h->K * R > AMC_MAX_MOVES)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_rung_sigma: %d moves x %d rungs = %d entries, the table holds %d", h->K, R, h->K * R, AMC_MAX_MOVES);
+    if (n != h->K * R)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_rung_sigma: n = %d, the table of %d moves x %d rungs has %d entries", n, h->K, R, h->K * R);
+    for (int e = 0; e < n; ++e)
+        if (!(std::isfinite(sigma[e]) && sigma[e] >= 1e-100 && sigma[e] <= 1e100))
+            return fail(AMC_ERR_BAD_ARG, "amc_set_rung_sigma: sigma[%d] (move %d, rung %d) = %g is not a finite value in [1e-100, 1e100]", e, e / R, e % R,
+                        sigma[e]);
+    AMC_HIP(hipSetDevice(h->device));
+    // (as in front of a sweep: a learning step left pending belongs in front of this point of the stream)
+    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    if (!h->d_rung_tab) AMC_HIP(hipMalloc(&h->d_rung_tab, (size_t)amc::RT_ROWS * AMC_MAX_MOVES * sizeof(double)));
+    amc::RungSigma s;
+    for (int e = 0; e < AMC_MAX_MOVES; ++e) s.sigma[e] = e < n ? sigma[e] : 1.0;
+    // on the stream, behind the sweeps that read the rows as they are
+    hipLaunchKernelGGL(amc::prepare_rung_params_kernel, dim3(1), dim3(AMC_MAX_MOVES), 0, h->stream, h->d_rung_tab, s, n);
+    AMC_HIP(hipGetLastError());
+    std::memcpy(h->rung_sigma, s.sigma, sizeof(h->rung_sigma));
+    h->rung_on = true;
+    return AMC_OK;
+}
+
+int amc_get_rung_sigma(amc_handle* h, double* sigma, int n)
+{
+    if (!h || !sigma) return fail(AMC_ERR_BAD_ARG, "amc_get_rung_sigma: NULL argument");
+    if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_get_rung_sigma: no widths per rung are set (amc_set_rung_sigma)");
+    if (n != h->K * h->n_rungs)
+        return fail(AMC_ERR_BAD_ARG, "amc_get_rung_sigma: n = %d, the table of %d moves x %d rungs has %d entries", n, h->K, h->n_rungs, h->K * h->n_rungs);
+    std::memcpy(sigma, h->rung_sigma, (size_t)n * sizeof(double));
     return AMC_OK;
 }
 

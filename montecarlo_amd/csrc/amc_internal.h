@@ -3,10 +3,11 @@
 // hidden visibility.
 //   amc_api.hip         errors, expression checks, handle creation and destruction, the knob reader (amc_knobs)
 //   amc_state.hip       the ensemble's state: upload / download, histograms, step indices, stream, timing
-//   amc_counters.hip    the step log and the per-chain counters (fold, totals, 64-bit carry, upload / download)
+//   amc_counters.hip    the step log and the per-chain counters (fold, totals, totals per rung, 64-bit carry, upload / download)
 //   amc_sweeps.hip      sweep launches (amc_sweep*)
 //   amc_exchange.hip    replica exchange along a temperature ladder (amc_set_ladder, amc_exchange, amc_sweep_exchange, gap counters,
-//                       the per-rung reproducible sums: amc_reduce_rungs_exact, walker tracking: amc_set_tracking ..)
+//                       the per-rung reproducible sums: amc_reduce_rungs_exact, walker tracking: amc_set_tracking ..,
+//                       proposal widths per rung: amc_set_rung_sigma / amc_get_rung_sigma)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -171,6 +172,13 @@ struct amc_handle {
     double* d_rung_recs = nullptr;          // [AMC_MAX_RUNGS][RED_COLS][XS_WORDS] their records (rung_finish_kernel)
     uint8_t* d_lab = nullptr;               // [M] walker labels, w | (d << 6) per chain; allocated exactly while tracking is on (amc_set_tracking)
     unsigned long long* d_track = nullptr;  // [2 + 3 * AMC_MAX_RUNGS] round_trips, up_trips, the cells of one flow snapshot (allocated with d_lab)
+    // Proposal widths per (move, rung) (amc_set_rung_sigma): a table is set exactly while rung_on; the sweeps then launch the RUNG form,
+    // which reads d_rung_tab where the others read ptab's rows
+    bool rung_on = false;
+    double* d_rung_tab = nullptr;           // [RT_ROWS][AMC_MAX_MOVES] derived rows of entry k * n_rungs + r (allocated by the first table, kept)
+    double rung_sigma[AMC_MAX_MOVES] = {0}; // the table as it was given (amc_get_rung_sigma)
+    unsigned long long* d_rung_cnt = nullptr;   // [2][cells] accepted, total per (move, rung) (amc_rung_counter_totals; allocated at its first use,
+    size_t rung_cnt_cells = 0;                  //   grown when a call needs more)
     double* d_x = nullptr;
     double* d_beta = nullptr;
     uint32_t* d_acc = nullptr;
@@ -305,6 +313,12 @@ AMC_INTERNAL int check_sigma_f32(const char* who, int k, double s);     // a sig
     do {                                                                                                                    \
         if ((h)->param_f32)                                                                                                 \
             return fail(AMC_ERR_STATE, "%s: not available with param_dtype = AMC_DTYPE_F32 (Float32 policy parameters: sweeps only)", (who)); \
+    } while (0)
+// ... and it learns one sigma per move: while a table of widths per rung is set (amc_set_rung_sigma) its entries refuse the handle too.
+#define AMC_REFUSE_RUNG_SIGMA(h, who)                                                                                       \
+    do {                                                                                                                    \
+        if ((h)->rung_on)                                                                                                   \
+            return fail(AMC_ERR_STATE, "%s: not available while widths per rung are set (amc_set_rung_sigma): the estimator learns one sigma per move", (who)); \
     } while (0)
 AMC_INTERNAL int pg_resolve(amc_handle* h);      // takes a pending learning step now (amc_pg.hip)
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)

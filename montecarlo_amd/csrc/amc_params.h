@@ -107,6 +107,27 @@ AMC_KERNEL_LINKAGE __global__ void prepare_params_f32_kernel(double* ptab, int n
 }
 #endif
 
+// The rung table (SweepArgs.rung_tab; DESIGN.md section 3.13 "Widths per rung"): entry e = k R + r holds what prepare_move_params
+// leaves in ptab for a move whose sigma is sigma[e] -- the same derive_move_params, so a chain stepped from entry e takes the
+// arithmetic of a pool whose move k has that sigma.  The table comes as a kernel argument: the launch is ordered on the stream
+// behind the sweeps that still read the old rows, and nothing is copied from the caller's memory after the call returns.
+struct RungSigma {
+    double sigma[AMC_MAX_MOVES];
+};
+#if AMC_PLAIN_KERNELS
+AMC_KERNEL_LINKAGE __global__ void prepare_rung_params_kernel(double* rung_tab, const RungSigma s, int n)
+{
+    const int e = (int)threadIdx.x;
+    if (blockIdx.x != 0 || e >= n) return;
+    double d[DEF_N];
+    derive_move_params(s.sigma[e], d);
+    rung_tab[RT_SIGMA * AMC_MAX_MOVES + e] = d[DEF_SIGMA];
+    rung_tab[RT_DEN * AMC_MAX_MOVES + e] = d[DEF_DEN];
+    rung_tab[RT_RDEN * AMC_MAX_MOVES + e] = d[DEF_RDEN];
+    rung_tab[RT_LOGC * AMC_MAX_MOVES + e] = d[DEF_LOGC];
+}
+#endif
+
 // The move-pick table (see AMC_PICK_CELLS): cell c covers the pick uniforms r in [c, c+1) 2^-12 (both ends exact).
 // The walk's count #(cum[i] <= r), i < K-1, is monotone in r, so it is the same for every r of the cell iff it is the
 // same at the two ends: #(cum[i] <= c 2^-12) == #(cum[i] < (c+1) 2^-12).  Launched after prepare_params (same stream)

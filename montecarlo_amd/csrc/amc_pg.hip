@@ -410,6 +410,7 @@ int amc_pg_estimate(amc_handle* h, int n_learn, const int* learn_ids, int q_batc
 {
     if (!h || !out) return fail(AMC_ERR_BAD_ARG, "amc_pg_estimate: NULL argument");
     AMC_REFUSE_PARAM_F32(h, "amc_pg_estimate");
+    AMC_REFUSE_RUNG_SIGMA(h, "amc_pg_estimate");
     const double* recs = nullptr;
     const int rc = pg_estimate_records(h, "amc_pg_estimate", n_learn, learn_ids, q_batch, &recs);
     if (rc != AMC_OK || n_learn == 0) return rc;
@@ -434,6 +435,7 @@ int amc_pg_estimate_exact(amc_handle* h, int n_learn, const int* learn_ids, int 
 {
     if (!h || !records) return fail(AMC_ERR_BAD_ARG, "amc_pg_estimate_exact: NULL argument");
     AMC_REFUSE_PARAM_F32(h, "amc_pg_estimate_exact");
+    AMC_REFUSE_RUNG_SIGMA(h, "amc_pg_estimate_exact");
     const double* recs = nullptr;
     const int rc = pg_estimate_records(h, "amc_pg_estimate_exact", n_learn, learn_ids, q_batch, &recs);
     if (rc != AMC_OK || n_learn == 0) return rc;
@@ -640,6 +642,7 @@ int amc_pg_route(amc_handle* h, int n_learn, int q_batch, int fused, char* why, 
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_pg_route: NULL handle");
     AMC_REFUSE_PARAM_F32(h, "amc_pg_route");
+    AMC_REFUSE_RUNG_SIGMA(h, "amc_pg_route");
     if (n_learn < 1 || n_learn > AMC_MAX_LEARN) return fail(AMC_ERR_BAD_ARG, "amc_pg_route: n_learn must be in [1, %d]", AMC_MAX_LEARN);
     if (q_batch < 1 || q_batch > AMC_MAX_QBATCH) return fail(AMC_ERR_BAD_ARG, "amc_pg_route: q_batch must be in [1, %d]", AMC_MAX_QBATCH);
     if (why && why_capacity > 0) why[0] = 0;
@@ -670,6 +673,7 @@ int amc_pg_accumulate(amc_handle* h, int n_learn, const int* learn_ids, int q_ba
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_pg_accumulate: NULL handle");
     AMC_REFUSE_PARAM_F32(h, "amc_pg_accumulate");
+    AMC_REFUSE_RUNG_SIGMA(h, "amc_pg_accumulate");
     return pg_accumulate_impl(h, n_learn, learn_ids, q_batch, nullptr);
 }
 
@@ -694,6 +698,7 @@ int amc_pg_update(amc_handle* h, int n_learn, const int* learn_ids, const int* o
     if (!h || (n_learn > 0 && (!learn_ids || !optimiser || !hyper0 || !hyper1)))
         return fail(AMC_ERR_BAD_ARG, "amc_pg_update: NULL argument");
     AMC_REFUSE_PARAM_F32(h, "amc_pg_update");
+    AMC_REFUSE_RUNG_SIGMA(h, "amc_pg_update");
     if (n_learn < 0 || n_learn > AMC_MAX_LEARN) return fail(AMC_ERR_BAD_ARG, "amc_pg_update: n_learn must be in [0, %d]", AMC_MAX_LEARN);
     if (n_learn == 0) return AMC_OK;
     amc::PgOpts opt;
@@ -714,6 +719,7 @@ static int pgmc_steps_impl(amc_handle* h, const char* who, int64_t n_steps, int 
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "%s: NULL handle", who);
     AMC_REFUSE_PARAM_F32(h, who);
+    AMC_REFUSE_RUNG_SIGMA(h, who);
     if (n_steps < 0) return fail(AMC_ERR_BAD_ARG, "%s: n_steps < 0", who);
     if (n_learn < 0 || n_learn > AMC_MAX_LEARN) return fail(AMC_ERR_BAD_ARG, "%s: n_learn must be in [0, %d]", who, AMC_MAX_LEARN);
     if (n_learn > 0 && (!learn_ids || (do_update && (!optimiser || !hyper0 || !hyper1))))
@@ -782,6 +788,7 @@ int amc_pg_get_accumulated(amc_handle* h, int n_learn, const int* learn_ids, dou
 {
     if (!h || !out || (n_learn > 0 && !learn_ids)) return fail(AMC_ERR_BAD_ARG, "amc_pg_get_accumulated: NULL argument");
     AMC_REFUSE_PARAM_F32(h, "amc_pg_get_accumulated");
+    AMC_REFUSE_RUNG_SIGMA(h, "amc_pg_get_accumulated");
     AMC_HIP(hipSetDevice(h->device));
     { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }      // (a pending step may set the status flag)
     const int np = h->n_params;
@@ -805,6 +812,7 @@ int amc_pg_set_accumulated(amc_handle* h, int n_learn, const int* learn_ids, con
 {
     if (!h || (n_learn > 0 && (!learn_ids || !in))) return fail(AMC_ERR_BAD_ARG, "amc_pg_set_accumulated: NULL argument");
     AMC_REFUSE_PARAM_F32(h, "amc_pg_set_accumulated");
+    AMC_REFUSE_RUNG_SIGMA(h, "amc_pg_set_accumulated");
     if (n_learn < 0 || n_learn > AMC_MAX_LEARN) return fail(AMC_ERR_BAD_ARG, "amc_pg_set_accumulated: n_learn must be in [0, %d]", AMC_MAX_LEARN);
     for (int l = 0; l < n_learn; ++l) {
         if (learn_ids[l] < 0 || learn_ids[l] >= h->K) return fail(AMC_ERR_BAD_ARG, "amc_pg_set_accumulated: learn_ids[%d] out of range", l);

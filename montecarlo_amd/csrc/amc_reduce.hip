@@ -171,7 +171,8 @@ int amc_sweep_reduce_begin(amc_handle* h, int64_t n_sweeps)
         return fail(AMC_ERR_STATE, "amc_sweep_reduce_begin: %d reductions are already in flight (call amc_reduce_end)", RED_TICKETS);
     // the ratio sums need the counters of every move (K > 4), or arrays plus their 64-bit bases (a handle that has counted past
     // 2^32 steps): sweep, then the reduction pass
-    if (h->K > 4 || h->d_acc_base || !reduce_fits_in_grid(h, reduce_sweep_grid(h))) {
+    // (and so does a handle with widths per rung: its sweep form carries no sums -- reproducible sums, the same bits either way)
+    if (h->K > 4 || h->d_acc_base || h->rung_on || !reduce_fits_in_grid(h, reduce_sweep_grid(h))) {
         const int rc = sweep_impl(h, n_sweeps, false, nullptr);
         return rc != AMC_OK ? rc : amc_reduce_begin(h);
     }

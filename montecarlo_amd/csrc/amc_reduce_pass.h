@@ -171,4 +171,66 @@ __global__ __launch_bounds__(AMC_BLOCK) void counter_totals_kernel(const CT* acc
         __syncthreads();
     }
 }
+
+// The same totals resolved by rung of a temperature ladder (amc_rung_counter_totals): out[k R + r] += sum over the local ladders l of
+// the counter of chain l R + r -- accepted for every move, total for the moves that have a total array (the host completes the last
+// move's from the step count, as amc_counter_totals does).  Every storage the counters have: u16 low planes with or without their
+// high planes, u32 arrays, and the 64-bit bases of a handle that has carried.  Work items as in rung_sums_kernel: thread id = l0 R + r,
+// a thread keeps its rung and advances by (threads / R) ladders per trip, so neighbouring lanes read neighbouring counters and the
+// loop divides nothing.  Moves in groups of up to four per pass over the ladders (as the fold groups them), their counts in
+// registers; then one 64-bit integer LDS add per lane and non-zero count, one 64-bit atomic per block and non-zero cell.  Integers
+// throughout: the order of the additions does not matter.
+#define AMC_RUNG_CELL_RUNGS 64      // R <= AMC_MAX_RUNGS (amc_exchange.h, included after this file; amc_exchange.hip pins the value)
+template <typename CT>
+__global__ __launch_bounds__(AMC_BLOCK) void rung_counter_totals_kernel(const CT* acc, const CT* tot, const uint16_t* acc_hi,
+                                                                         const uint16_t* tot_hi, const unsigned long long* acc_base,
+                                                                         const unsigned long long* tot_base, int64_t n_chains,
+                                                                         int64_t m_stride, int n_moves, int n_rungs,
+                                                                         unsigned long long* out_acc, unsigned long long* out_tot)
+{
+    __shared__ unsigned long long s_cell[2][4][AMC_RUNG_CELL_RUNGS];      // [accepted, total][move of the group][rung]
+    const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
+    const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / n_rungs;
+    const int64_t l0 = tid / n_rungs;
+    const int r = (int)(tid - l0 * n_rungs);
+    const int64_t step = ladders_per_trip * n_rungs;                    // chains per trip
+    for (int k0 = 0; k0 < n_moves; k0 += 4) {
+        const int kn = n_moves - k0 < 4 ? n_moves - k0 : 4;
+        for (int i = threadIdx.x; i < 2 * 4 * AMC_RUNG_CELL_RUNGS; i += AMC_BLOCK) (&s_cell[0][0][0])[i] = 0ull;
+        __syncthreads();
+        unsigned long long ca[4] = {0ull, 0ull, 0ull, 0ull}, ct[4] = {0ull, 0ull, 0ull, 0ull};
+        if (l0 < ladders_per_trip) {
+            for (int64_t c = l0 * n_rungs + r; c < n_chains; c += step) {      // n_chains is a multiple of R: whole ladders only
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j >= kn) break;
+                    const int64_t at = (int64_t)(k0 + j) * m_stride + c;
+                    unsigned long long va = acc[at];
+                    if (acc_hi) va |= (unsigned long long)acc_hi[at] << 16;
+                    if (acc_base) va += acc_base[at];
+                    ca[j] += va;
+                    if (k0 + j + 1 < n_moves) {                                 // the pool's last move has no total array
+                        unsigned long long vt = tot[at];
+                        if (tot_hi) vt |= (unsigned long long)tot_hi[at] << 16;
+                        if (tot_base) vt += tot_base[at];
+                        ct[j] += vt;
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (ca[j]) atomicAdd(&s_cell[0][j][r], ca[j]);
+                if (ct[j]) atomicAdd(&s_cell[1][j][r], ct[j]);
+            }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * kn * n_rungs; i += AMC_BLOCK) {
+            const int which = i / (kn * n_rungs), rest = i - which * kn * n_rungs;
+            const int j = rest / n_rungs, rr = rest - j * n_rungs;
+            const unsigned long long v = s_cell[which][j][rr];
+            if (v) atomicAdd((which ? out_tot : out_acc) + (int64_t)(k0 + j) * n_rungs + rr, v);
+        }
+        __syncthreads();                                                // the next group clears the cells
+    }
+}
 }  // namespace amc

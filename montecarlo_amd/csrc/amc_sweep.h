@@ -23,9 +23,13 @@ struct SweepArgs {
     int32_t n_moves;
     uint32_t key0, key1;
     double beta;
+    union {                       // (a launch is REDUCE or RUNG or neither, never both: sweep_kernel's static_assert)
     xs_word* red_partials;        // REDUCE launches: [grid][red_stride] block rows, pinned host memory: three kind-R columns
                                   // (sum e, sum x, sum x^2: XS_ROW_R words each), then as doubles the count and this block's
                                   // pool-wide accepted slot after the launch (RED_ROW_COUNT, RED_ROW_SLOT)
+    const double* rung_tab;       // RUNG launches (widths per move and rung, amc_set_rung_sigma): [RT_ROWS][AMC_MAX_MOVES], the derived
+                                  // rows of entry e = k * n_rungs + r
+    };
     int32_t red_stride;           // words per row: RED_ROW_WORDS, or RED_COMPACT_WORDS for the compact form (red_finish)
     int32_t red_cols;             // RED_WANT_* bits: the sums this launch forms
     int32_t log_pos;              // row of the step log the first step of this launch writes
@@ -36,7 +40,14 @@ struct SweepArgs {
     // n_pairs % R one more.  The kernel trusts them: they must agree with n_chains and the launch's grid.
     int32_t full_rounds;
     int32_t tail_pairs;
+    int32_t n_rungs;              // RUNG launches: the ladder's R
 };
+// The kernels' implicit arguments follow the struct in the kernel argument segment: a size that changes moves them under every
+// instantiation that exists.  rung_tab and n_rungs take a pointer no RUNG launch reads and the struct's tail padding.
+static_assert(sizeof(SweepArgs) == 144, "SweepArgs: the size every sweep and estimator kernel was compiled against");
+
+// Rows of the rung table: what prepare_move_params leaves in ptab for a move of that sigma, as far as the sweep reads it.
+enum { RT_SIGMA = 0, RT_DEN = 1, RT_RDEN = 2, RT_LOGC = 3, RT_ROWS = 4 };
 
 // The Philox result every MH step of a pair needs -- its normal draw: a pure function of (seed, pair, step), so it can
 // be formed before the pair's state has arrived from memory.  (Its spare bits lead the accept and pick uniforms; the
@@ -108,13 +119,16 @@ __device__ __forceinline__ void store_log_pair(const SweepArgs& a, int row, int6
 // PRE: the draws of the (single) step were formed ahead by the caller and come in `pre` (nullptr otherwise).
 // LOG: the step-log word of the pair; SINGLE launches hand it back in `log_word` (the caller stores it together
 // with x), multi-step launches store one word per step right away.
-template <int POT, bool MULTI, int LOG, bool SINGLE, bool PRE>
+// RUNG: the widths come from the rung table's entry k * n_rungs + r (staged in s_tab's rows where a K > 1 sweep keeps its pool's):
+// rung0 / rung1 are the rungs of the lane's two chains.  The step log keeps the move k.
+template <int POT, bool MULTI, int LOG, bool SINGLE, bool PRE, bool RUNG = false>
 __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t b0, real_t b1, uint64_t pair,
                                            int64_t p, bool v0, bool v1, const double* s_tab, const uint8_t* s_pick,
                                            const double* s_math, param_t sigma1, param_t den1, double rden1, double logc1,
                                            unsigned long long& wave_acc, uint32_t& log_word,
                                            const StepDraws* pre, const MathK& mk, const UserTheta& th1,
-                                           const float2* s_mathf)      // AMC_PARAM_F32: the Float32 tables (box_muller_f32), else nullptr
+                                           const float2* s_mathf,      // AMC_PARAM_F32: the Float32 tables (box_muller_f32), else nullptr
+                                           int rung0 = 0, int rung1 = 0)
 {
     static_assert(!PRE || SINGLE, "pre-formed draws cover exactly one step");
     const int K = a.n_moves;
@@ -143,8 +157,16 @@ __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t
                 k0 = categorical_walk(s_tab, K, uniform_pick(q0, pu.x));
                 k1 = categorical_walk(s_tab, K, uniform_pick(q1, pu.z));
             }
-            sg0 = mt_sigma(s_tab, k0);
-            sg1 = mt_sigma(s_tab, k1);
+            if (!RUNG) {
+                sg0 = mt_sigma(s_tab, k0);
+                sg1 = mt_sigma(s_tab, k1);
+            }
+        }
+        // RUNG: the table's entry of (move, rung) stands where the move does
+        const int e0 = RUNG ? k0 * a.n_rungs + rung0 : k0, e1 = RUNG ? k1 * a.n_rungs + rung1 : k1;
+        if (RUNG) {
+            sg0 = mt_sigma(s_tab, e0);
+            sg1 = mt_sigma(s_tab, e1);
         }
         param_t z0, z1;
 #ifdef AMC_PARAM_F32
@@ -156,8 +178,8 @@ __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t
 #endif
         unsigned long long m0, m1m;
         uint32_t acc_bits;
-        mh_pair<POT, MULTI>(xv, b0, b1, sg0, sg1, k0, k1, s_tab, m1, z0, z1, dr.normal, pu, have_pu, accept_ctr, a.key0,
-                            a.key1, s_math, force_mask, acc_bits, m0, m1m, th1);
+        mh_pair<POT, MULTI || RUNG>(xv, b0, b1, sg0, sg1, e0, e1, s_tab, m1, z0, z1, dr.normal, pu, have_pu, accept_ctr, a.key0,
+                                    a.key1, s_math, force_mask, acc_bits, m0, m1m, th1);
         // K == 1: wavefront-ballot accept mask -> one scalar popcount per chain slot (pool-wide total)
         if (!MULTI) wave_acc += __popcll(m0 & __builtin_amdgcn_ballot_w64(v0)) + __popcll(m1m & __builtin_amdgcn_ballot_w64(v1));
         if (LOG) {
@@ -177,9 +199,13 @@ __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t
 //         and, pool-wide counter only, the accepted total), so a sweep that is followed by callback_energy /
 //         callback_acceptance needs no second pass over x.  RED_FORM_COLS: the sums SweepArgs.red_cols names; RED_FORM_E: sum e
 //         alone, compiled in (RedCols) -- what the host launches when nothing else is asked for
-template <int POT, bool MULTI, int LOG, bool BETA, bool SINGLE, int REDUCE = RED_FORM_NONE>
+// RUNG: a width per (move, rung) of a temperature ladder (DESIGN.md section 3.13 "Widths per rung"): chain c sits at rung
+//         (global chain id) mod R and takes the rung table's entry k R + r where the other forms take move k's row; at K == 1 too
+//         (MULTI still says whether there is a move pick).  Always with LOG and BETA, never with REDUCE.
+template <int POT, bool MULTI, int LOG, bool BETA, bool SINGLE, int REDUCE = RED_FORM_NONE, bool RUNG = false>
 __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
 {
+    static_assert(!RUNG || (LOG && BETA && !REDUCE), "rung widths: per-chain counters, a beta array, no callback sums");
     // REDUCE with LOG (per-chain counters): rows carry the sums over x only; the acceptance ratios of the same
     // callback come from the fold of the step log that follows (fold_log_kernel<KS, true>)
     static_assert(!MULTI || LOG, "K > 1 always keeps per-chain counters");
@@ -189,7 +215,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     RLanes<RNC> red;
     __shared__ xs::PartR s_red[REDUCE ? AMC_BLOCK / 64 : 1][RNC];
     if (REDUCE) r_init(red, s_red[threadIdx.x >> 6]);
-    __shared__ double s_tab[MULTI ? MT_ROWS * AMC_MAX_MOVES : 1];
+    __shared__ double s_tab[(MULTI || RUNG) ? MT_ROWS * AMC_MAX_MOVES : 1];
     __shared__ __attribute__((aligned(16))) uint8_t s_pick[MULTI ? AMC_PICK_CELLS : 16];
     __shared__ double s_math[TAB_DOUBLES];        // exp / log / sincospi tables, 4.4 KB
 #ifdef AMC_PARAM_F32
@@ -203,6 +229,10 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     if (MULTI) {
         stage_pick_table(s_pick, a.pick_tab);
         for (int i = threadIdx.x; i < K; i += AMC_BLOCK) {
+            if (RUNG) {                      // the pool gives the pick alone
+                s_tab[MT_CUM * AMC_MAX_MOVES + i] = a.ptab[PT_CUM * AMC_MAX_MOVES + i];
+                continue;
+            }
             mt_set_sigma(s_tab, i, a.ptab[PT_SIGMA * AMC_MAX_MOVES + i]);
             mt_set_den_f32(s_tab, i, a.ptab[PT_DEN * AMC_MAX_MOVES + i]);       // (AMC_PARAM_F32: the Float32 copy, beside the row below)
             s_tab[MT_DEN * AMC_MAX_MOVES + i] = a.ptab[PT_DEN * AMC_MAX_MOVES + i];
@@ -212,6 +242,14 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
             if (AMC_SIGMA_MEMO) mt_set_log_sigma(s_tab, i, log_f64(a.ptab[PT_SIGMA * AMC_MAX_MOVES + i]));      // (SigmaArg)
         }
         // visible to the block after the barrier that ends stage_math_tables below
+    }
+    if (RUNG) {
+        for (int i = threadIdx.x; i < K * a.n_rungs; i += AMC_BLOCK) {       // (<= AMC_MAX_MOVES entries: amc_set_rung_sigma)
+            mt_set_sigma(s_tab, i, a.rung_tab[RT_SIGMA * AMC_MAX_MOVES + i]);
+            s_tab[MT_DEN * AMC_MAX_MOVES + i] = a.rung_tab[RT_DEN * AMC_MAX_MOVES + i];
+            s_tab[MT_LOGC * AMC_MAX_MOVES + i] = a.rung_tab[RT_LOGC * AMC_MAX_MOVES + i];
+            s_tab[MT_RDEN * AMC_MAX_MOVES + i] = a.rung_tab[RT_RDEN * AMC_MAX_MOVES + i];
+        }
     }
     // K == 1: wave-uniform scalars (s_load)
     const param_t sigma1 = (param_t)a.ptab[PT_SIGMA * AMC_MAX_MOVES];      // (AMC_PARAM_F32: exact, the table holds Float32 values)
@@ -269,6 +307,13 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     constexpr bool AHEAD = SINGLE;
     StepDraws dr_nxt = {};
     if (AHEAD && trips > 0) dr_nxt = step_draws(a, pair, a.t0);
+    // RUNG: the rung of the lane's even chain, (2 pair) mod R, kept in a register and stepped by (2 stride) mod R per trip.  A ladder
+    // never straddles a shard, so 2 pair0 is a multiple of R and the local pair index -- below 2^31 within the block's first trip --
+    // gives the same remainder.
+    const uint32_t n_rungs = RUNG ? (uint32_t)a.n_rungs : 1u;
+    uint32_t rung = RUNG ? (2u * (uint32_t)(first + threadIdx.x)) % n_rungs : 0u;
+    const uint32_t rung_step = RUNG ? (uint32_t)((2u * (uint64_t)stride) % n_rungs) : 0u;
+    auto rung_next = [&](uint32_t r) { const uint32_t s = r + 1u; return (int)(s >= n_rungs ? s - n_rungs : s); };
 #ifdef AMC_USER_LOGQ
     stage_user_theta(a.ptab, MULTI);
 #endif
@@ -292,9 +337,14 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
         }
         const StepDraws dr = dr_nxt;
         uint32_t lw = 0;
-        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD>(a, xv, b0, b1, pair, base + threadIdx.x, true, true, s_tab, s_pick, s_math,
-                                                   sigma1, den1, rden1, logc1, wave_acc, lw, &dr, math_k_literal(), th1, s_mathf);
+        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD, RUNG>(a, xv, b0, b1, pair, base + threadIdx.x, true, true, s_tab, s_pick, s_math,
+                                                         sigma1, den1, rden1, logc1, wave_acc, lw, &dr, math_k_literal(), th1, s_mathf,
+                                                         (int)rung, rung_next(rung));
         pair += (uint64_t)stride;
+        if (RUNG) {
+            rung += rung_step;
+            if (rung >= n_rungs) rung -= n_rungs;
+        }
         // a successor exists (loop condition); lanes past the end of a ragged one form draws nobody uses
         if (AHEAD) dr_nxt = step_draws(a, pair, a.t0);
         if (REDUCE) {
@@ -314,8 +364,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
             if (LOG && SINGLE) store_log_pair<LOG>(a, a.log_pos, base_done + threadIdx.x, lw_done);
         }
         uint32_t lw = 0;
-        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD>(a, xv, b_nxt.x, b_nxt.y, v0 ? pair : a.pair0, p, v0, v1,
-                                                   s_tab, s_pick, s_math, sigma1, den1, rden1, logc1, wave_acc, lw, &dr_nxt, math_k_literal(), th1, s_mathf);
+        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD, RUNG>(a, xv, b_nxt.x, b_nxt.y, v0 ? pair : a.pair0, p, v0, v1,
+                                                         s_tab, s_pick, s_math, sigma1, den1, rden1, logc1, wave_acc, lw, &dr_nxt, math_k_literal(), th1, s_mathf,
+                                                         (int)rung, rung_next(rung));
         // a lone last chain (odd n_chains) writes its whole pair (x and log): the odd slot is padding
         if (v0) {
             store_pair_block_writethrough(a.x + 2 * base, xv);

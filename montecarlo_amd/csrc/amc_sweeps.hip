@@ -16,9 +16,28 @@ int launch_sweep_beta(amc_handle* h, const amc::SweepArgs& a, int grid, hipStrea
     return AMC_OK;
 }
 
+// sweep_kernel<POT, MULTI, LOG, true, SINGLE, RED_FORM_NONE, true>: the form that takes its widths from the rung table
+template <int POT, bool MULTI, int LOG>
+int launch_sweep_rung(const amc::SweepArgs& a, int grid, hipStream_t stream)
+{
+    if (a.n_steps == 1)
+        hipLaunchKernelGGL((amc::sweep_kernel<POT, MULTI, LOG, true, true, amc::RED_FORM_NONE, true>), dim3(grid), dim3(AMC_BLOCK), 0, stream, a);
+    else
+        hipLaunchKernelGGL((amc::sweep_kernel<POT, MULTI, LOG, true, false, amc::RED_FORM_NONE, true>), dim3(grid), dim3(AMC_BLOCK), 0, stream, a);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
 template <int POT, int FORM>
 int launch_sweep_form(amc_handle* h, const amc::SweepArgs& a, int grid, hipStream_t stream)
 {
+    if (h->rung_on) {
+        // widths per rung (amc_set_rung_sigma): a ladder and per-chain counters are given; the callback sums come from a pass of their own
+        if (FORM != amc::RED_FORM_NONE) return fail(AMC_ERR_STATE, "sweep: no launch forms the callback sums while widths per rung are set");
+        if (h->K > 1 && log_form(h) == AMC_LOG_PACKED) return launch_sweep_rung<POT, true, AMC_LOG_PACKED>(a, grid, stream);
+        if (h->K > 1) return launch_sweep_rung<POT, true, AMC_LOG_BYTES>(a, grid, stream);
+        return launch_sweep_rung<POT, false, AMC_LOG_PACKED>(a, grid, stream);
+    }
 #define AMC_SWEEP(MULTI, LOG)                                                                                                 \
     (a.n_steps == 1 ? launch_sweep_beta<POT, MULTI, LOG, true, FORM>(h, a, grid, stream) : launch_sweep_beta<POT, MULTI, LOG, false, FORM>(h, a, grid, stream))
     // K > 1 always keeps per-chain counters (callback_acceptance is a mean of per-chain ratios); the step log's form is
@@ -45,7 +64,8 @@ static int launch_sweep_custom(amc_handle* h, amc::SweepArgs& a, int grid, bool 
 {
     const bool multi = h->K > 1;
     const std::string inst = "amc::sweep_kernel<" + std::to_string(h->potential) + "," + tf(multi) + "," + std::to_string(log_form(h)) + "," + tf(h->beta_arr) + "," +
-                             tf(a.n_steps == 1) + "," + std::to_string(reduce ? red_form(h) : (int)amc::RED_FORM_NONE) + ">";
+                             tf(a.n_steps == 1) + "," + std::to_string(reduce ? red_form(h) : (int)amc::RED_FORM_NONE) + (h->rung_on ? ",true>" : ">");
+    if (h->rung_on && reduce) return fail(AMC_ERR_STATE, "sweep: no launch forms the callback sums while widths per rung are set");
     void* params[] = {&a};
     return rtc_launch(h, inst, grid, params);
 }
@@ -76,6 +96,8 @@ amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps, int grid)
     a.red_cols = h->red_cols;
     a.exact_accept = h->knobs.exact_accept ? 1 : 0;
     a.n_slots = h->n_slots;
+    if (h->rung_on) a.rung_tab = h->d_rung_tab;       // (in red_partials' place: no launch of such a handle forms the callback sums)
+    a.n_rungs = h->n_rungs;
     a.full_rounds = a.tail_pairs = 0;
     if (grid > 0) {
         const int64_t n_pairs = (h->M + 1) / 2, round = (int64_t)grid * AMC_BLOCK;

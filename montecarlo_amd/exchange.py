@@ -128,6 +128,13 @@ def callback_exchange_acceptance(simulation: Simulation) -> np.ndarray:
     return _find_exchange(simulation).acceptance()
 
 
+def callback_rung_acceptance(simulation: Simulation) -> np.ndarray:
+    """accepted / total calls of every Metropolis move per rung over all shards, an array of shape (K, R), NaN where a move was
+    never picked at a rung (Metropolis.rung_acceptance): the figure a width per rung (``Metropolis(..., rung_sigma=...)``) is tuned
+    by.  Reads the per-chain counters: the host waits for the queued steps."""
+    return _find_exchange(simulation).metropolis.rung_acceptance()
+
+
 def callback_flow_fraction(simulation: Simulation) -> np.ndarray:
     """The flow fraction f(r) per rung, a vector of R values (ReplicaExchange.flow).  Needs ReplicaExchange(..., track=True)."""
     return _find_exchange(simulation).flow()

@@ -13,7 +13,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import sharding
-from ._capi import AMC_RED_HEADER, HipEngine, SplitEngine
+from ._capi import AMC_MAX_MOVES, AMC_RED_HEADER, HipEngine, SplitEngine
 from .simulation import AriannaAlgorithm, Simulation, _calls, julia_repr
 from .system import Move, ParticleChains
 
@@ -21,6 +21,34 @@ from .system import Move, ParticleChains
 GAUSS_SAMPLE = "sigma*z"
 GAUSS_LOGQ = "-(delta*delta)/(2.0*(sigma*sigma)) - amc_log(6.283185307179586*(sigma*sigma))/2.0"      # particle_1d.jl:52-54
 GAUSS_DLOGQ = "(delta*delta)/(sigma*sigma*sigma) - 1.0/sigma"
+
+
+def _check_rung_sigma(rung_sigma, pool, streams: int) -> np.ndarray:
+    """``rung_sigma`` as a Float64 array [K][R], or a ValueError that names the numbers."""
+    K = len(pool)
+    try:
+        s = np.array(rung_sigma, dtype=np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"Metropolis: rung_sigma must be an array [K = {K}][R] of widths ({exc})") from None
+    if s.ndim == 1 and K == 1:
+        s = s.reshape(1, -1)
+    if s.ndim != 2 or s.shape[0] != K or s.shape[1] < 2:
+        raise ValueError(f"Metropolis: rung_sigma has shape {s.shape}, expected (K = {K}, R) with R >= 2: one width per move and rung")
+    bad = np.argwhere(~(np.isfinite(s) & (s >= 1e-100) & (s <= 1e100)))
+    if len(bad):
+        k, r = (int(v) for v in bad[0])
+        raise ValueError(f"Metropolis: rung_sigma[{k}][{r}] = {s[k, r]!r} is not a positive finite width in [1e-100, 1e100]")
+    if s.size > AMC_MAX_MOVES:
+        raise ValueError(f"Metropolis: rung_sigma has K x R = {K} x {s.shape[1]} = {s.size} entries, the engine's table holds {AMC_MAX_MOVES}")
+    for k, m in enumerate(pool):
+        if _move_signature(m) != ("gauss", None, None):
+            raise ValueError(f"Metropolis: rung_sigma needs the built-in Gaussian policy and displacement; move {k} of {K} has a "
+                             f"{_move_signature(m)[0]} policy or a script-defined action")
+        if getattr(m, "param_dtype", "f64") != "f64":
+            raise ValueError(f"Metropolis: rung_sigma needs Float64 parameters; move {k} carries numpy.float32 parameters")
+    if streams != 1:
+        raise ValueError(f"Metropolis: rung_sigma needs streams = 1 (got streams = {streams}): sub-shards on streams have no exchange move")
+    return np.ascontiguousarray(s)
 
 
 def _move_signature(m):
@@ -54,6 +82,9 @@ class Metropolis(AriannaAlgorithm):
     Default: only when the pool has more than one move (``callback_acceptance`` is then a mean of per-chain ratios); for a
     single move every chain has the same ``total_calls``, the pool-wide accepted total gives the same callback and
     ``Move`` totals, and the sweep is ~20 % faster without the per-chain step log.
+    ``rung_sigma``: proposal widths per (move, rung) of a temperature ladder, an array [K][R] (K = 1: a list of R will do): the chains
+    at rung r propose with ``rung_sigma[k][r]`` where the others use the move's shared sigma.  Turns per-chain counters on; handed to
+    the engine when the ladder is set (ReplicaExchange); ``rung_acceptance()`` reads the acceptance it is there to tune.
     ``streams``: > 1 splits this rank's shard into that many sub-shards on separate HIP streams of the same GPU, so that
     the launch boundary of one overlaps the body of another (~8 % faster back-to-back single-sweep launches with 2 at
     1e7 chains -- visible only where the step loop is not host-bound, which a Python loop with a callback at every
@@ -67,12 +98,17 @@ class Metropolis(AriannaAlgorithm):
     def __init__(self, chains: ParticleChains, pool: Optional[Sequence[Move]] = None, sweepstep: int = 1,
                  seed: int = 1, R=None, parallel: bool = False, device: Optional[int] = None,
                  per_chain_counters: Optional[bool] = None, download_on_finalise: bool = True,
-                 engine_factory: Optional[Callable[..., object]] = None, streams: int = 1, **extras):
+                 engine_factory: Optional[Callable[..., object]] = None, streams: int = 1, rung_sigma=None, **extras):
         if pool is None or len(pool) == 0:
             raise ValueError("Metropolis: pool is missing")
         if not all(isinstance(m, Move) for m in pool):
             raise TypeError("Metropolis: pool must hold Move objects")
         self.pool = tuple(pool)
+        # widths per (move, rung) of a temperature ladder (DESIGN.md section 3.13 "Widths per rung"): checked here, before an engine
+        # exists, handed to the engine when the ladder is set (set_ladder)
+        self.rung_sigma = None if rung_sigma is None else _check_rung_sigma(rung_sigma, self.pool, int(streams))
+        if self.rung_sigma is not None:
+            per_chain_counters = True           # the acceptance per rung is read from the per-chain counters
         self.sweepstep = int(sweepstep)
         self.seed = int(seed)
         self.parallel = bool(parallel)
@@ -213,9 +249,25 @@ class Metropolis(AriannaAlgorithm):
             raise ValueError("ReplicaExchange: this engine has no exchange move (streams > 1 is not supported)")
         if getattr(self, "n_rungs", 0) == R:
             return                              # set already (storage.restore): setting it again would zero the gap counters
+        if self.rung_sigma is not None and self.rung_sigma.shape[1] != R:
+            raise ValueError(f"Metropolis: rung_sigma has {self.rung_sigma.shape[1]} rungs per move, the ladder has R = {R}")
         self.engine.set_ladder(R)
         self.n_rungs = R
         self.tracking = False                   # (amc_set_ladder turns walker tracking off; ReplicaExchange(track=True) and restore turn it on)
+        if self.rung_sigma is not None:         # (amc_set_ladder clears the table too)
+            self.engine.set_rung_sigma(self.rung_sigma)
+
+    def rung_acceptance(self) -> np.ndarray:
+        """accepted_calls / total_calls of every move per rung over ALL shards, shape (K, R): the exact integer totals of the
+        per-chain counters (amc_rung_counter_totals) added across shards, then divided; 0/0 = NaN.  Needs a ladder and per-chain
+        counters, with or without ``rung_sigma``.  The host waits for the queued steps."""
+        if not getattr(self, "n_rungs", 0):
+            raise ValueError("Metropolis.rung_acceptance: the chains have no ladder (ReplicaExchange)")
+        acc, tot = self.engine.rung_counter_totals()
+        both = sharding.allreduce_sum(np.concatenate([acc.reshape(-1), tot.reshape(-1)]).astype(np.float64), self.engine)
+        n = acc.size
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (both[:n] / both[n:]).reshape(acc.shape)
 
     def sweep_exchange(self, n_rounds: int, sweeps_per_round: int) -> None:
         """n_rounds x [sweeps_per_round make_step!s; one exchange step] queued by one engine call."""

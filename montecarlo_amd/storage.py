@@ -19,7 +19,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import sharding
-from .metropolis import Metropolis
+from .metropolis import Metropolis, _check_rung_sigma
 from .simulation import AriannaAlgorithm, Simulation, _calls
 
 
@@ -157,6 +157,8 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
     if getattr(metropolis, "n_rungs", 0):           # a temperature ladder: the exchange step index and the gap counters are state
         acc_x, att_x = eng.exchange_counters()
         data.update(n_rungs=metropolis.n_rungs, exchange_step=eng.exchange_step, exchange_accepted=acc_x, exchange_attempted=att_x)
+        if getattr(metropolis, "rung_sigma", None) is not None:     # widths per rung: the table is state (no field without one)
+            data["rung_sigma"] = np.asarray(metropolis.rung_sigma, dtype=np.float64)
         if getattr(metropolis, "tracking", False):  # walker tracking is on: the labels and the trip counters are state too
             walker, direction = eng.labels()
             data.update(walker=walker, direction=direction, trips=np.array(eng.tracking_counters(), dtype=np.int64))
@@ -190,7 +192,18 @@ def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
     else:
         eng.set_counter_totals(int(d["accepted_total"][0]), int(d["total_total"][0]) // (stop - start))
     if "n_rungs" in d:
-        metropolis.set_ladder(int(d["n_rungs"]))
+        R = int(d["n_rungs"])
+        tab = None
+        if "rung_sigma" in d:                       # widths per rung: checked like the constructor's against this pool and ladder
+            tab = _check_rung_sigma(d["rung_sigma"], metropolis.pool, 1)
+            if tab.shape[1] != R:
+                raise ValueError(f"checkpoint holds rung_sigma of {tab.shape[1]} rungs per move for a ladder of R = {R}")
+        metropolis.rung_sigma = tab                 # the checkpoint's table, or none, replaces the constructor's
+        metropolis.set_ladder(R)
+        # set_ladder does nothing where the ladder is set already, so the table goes to the engine here: what the engine sweeps
+        # with is what the next checkpoint writes
+        if tab is not None or hasattr(eng, "set_rung_sigma"):
+            eng.set_rung_sigma(tab)
         eng.exchange_step = int(d["exchange_step"])
         eng.set_exchange_counters(d["exchange_accepted"], d["exchange_attempted"])
         if "walker" in d:
