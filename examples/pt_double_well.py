@@ -6,13 +6,18 @@ A temperature ladder with neighbour swaps (ReplicaExchange) lets positions trave
 down.  Every chain starts in the right well; the script runs the same schedule with and without exchange steps and prints, per
 rung, the fraction of chains left of the barrier, the mean energy and the swap acceptance of every gap.
 
-    python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track] [--rung-sigma]
+    python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track] [--rung-sigma] [--adapt flow|acceptance]
 
 --track also follows every replica through the swaps and prints, at the end, the flow fraction f(r) -- of the replicas at rung r that
 have been to an end of the ladder, the share that came from the hot end (rung 0) last -- and the round trips per ladder.
 
 --rung-sigma gives every rung a proposal width of its own, sigma_r = sigma_0 sqrt(beta_0 / beta_r) (Metropolis(..., rung_sigma=...)): the
 hot rungs then take the long steps they are there for.  The acceptance of the move per rung is printed beside the swap acceptance.
+
+--adapt flow|acceptance respaces the ladder on the device during the first half of the run (RespaceLadder, five damped respacings, the
+last at steps / 2; "flow" turns tracking on) and leaves it alone afterwards -- moving beta breaks detailed balance, so the first half is
+burn-in.  A respacing zeroes the gap counters and restarts the tracking, so the swap acceptance per gap and the round trips printed at
+the end are those of the second half, on the final ladder, which is printed too.
 """
 import argparse
 import os
@@ -38,8 +43,15 @@ def one_run(args, path, exchange: bool):
         algorithm_list[0]["rung_sigma"] = [SIGMA0 * np.sqrt(BETAS[0] / b) for b in BETAS]
     callbacks = [ma.callback_energy]
     if exchange:
-        algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), track=args.track))   # every time step
+        track = args.track or args.adapt == "flow"
+        algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), track=track))   # every time step
         callbacks.append(ma.callback_exchange_acceptance)
+        if args.adapt:
+            half = args.steps // 2
+            every = max(1, half // 5)
+            algorithm_list.append(dict(algorithm=ma.RespaceLadder, dependencies=(ma.ReplicaExchange,), rule=args.adapt, gamma=0.7, eps=0.01,
+                                       scheduler=list(range(half - 4 * every, half + 1, every)), until=half))
+            callbacks.append(ma.callback_ladder)
     algorithm_list.append(dict(algorithm=ma.StoreCallbacks, callbacks=tuple(callbacks),
                                scheduler=ma.build_schedule(args.steps, 0, max(1, args.steps // 10))))
     simulation = ma.Simulation(chains, algorithm_list, args.steps, path=path)
@@ -60,6 +72,8 @@ def main(argv=None):
     ap.add_argument("--path", default=None)
     ap.add_argument("--track", action="store_true", help="follow the replicas: print the flow fraction per rung and the round trips")
     ap.add_argument("--rung-sigma", action="store_true", help="a proposal width per rung, sigma_r = sigma_0 sqrt(beta_0 / beta_r); print the move's acceptance per rung")
+    ap.add_argument("--adapt", choices=("flow", "acceptance"), default=None,
+                    help="respace the ladder during the first half of the run; print the ladder, and the swap acceptance and round trips of the second half")
     args = ap.parse_args(argv)
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
@@ -74,7 +88,10 @@ def main(argv=None):
         print("proposal width per rung       : " + "  ".join(f"{v:7.4f}" for v in sim.algorithms[0].rung_sigma[0]))
         print("move acceptance per rung      : " + "  ".join(f"{v:7.4f}" for v in ma.callback_rung_acceptance(sim)[0]))
     print("coldest rung, 8 bins of [-2, 2): " + " ".join(str(int(v)) for v in hist[-1][:8]))
-    if args.track:
+    if args.adapt:
+        rx = sim.algorithms[1]
+        print(f"ladder after {rx.metropolis.engine.respace_status()[1]} respacings   : " + "  ".join(f"{b:7.4f}" for b in rx.betas()) + "   (second half: the lines above and below)")
+    if args.track or args.adapt == "flow":
         rx = sim.algorithms[1]
         trips = rx.round_trips()
         print("flow fraction f(r)            : " + "  ".join(f"{v:7.4f}" for v in rx.flow()))

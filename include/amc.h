@@ -421,6 +421,32 @@ int  amc_get_rung_sigma(amc_handle *h, double *sigma, int n);
  * (AMC_ERR_STATE otherwise), with or without widths per rung.  Folds pending rows of the step log first, synchronises, changes nothing.
  * Either output may be NULL. */
 int  amc_rung_counter_totals(amc_handle *h, int64_t *accepted, int64_t *total);
+/* Respacing the ladder (DESIGN.md section 3.13 "Respacing", which holds the rule operation by operation): new beta values for the
+ * interior rungs, computed on the device from the swap counts per gap (AMC_RESPACE_ACCEPTANCE: equalise the rejection rate) or from the
+ * flow counts per rung (AMC_RESPACE_FLOW: the feedback-optimised ladder, rung density ~ sqrt(df/dbeta / dbeta)); gamma in (0, 1] damps the
+ * move of every rung, eps in [0, 1) is the floor of a gap's weight as a share of the mean weight.  The end rungs keep their bits.
+ * counts == NULL: the handle's own device counters -- right only when the handle holds every ladder; nothing synchronises and nothing is
+ * read back.  Otherwise counts are the GLOBAL counts, summed over all shards by the caller, and travel with the launch:
+ * AMC_RESPACE_ACCEPTANCE attempted[R - 1] then accepted[R - 1], AMC_RESPACE_FLOW n[R][3] as amc_flow_rungs gives them; every shard given
+ * the same counts computes the same ladder.  Stream-ordered behind what is queued (a pending learning step is taken first); does not
+ * synchronise.  The ladder at hand is read from the first local ladder.
+ * Status (amc_respace_status, of the last call): 0 respaced; 1 no weight to spread (W is not positive and finite); 2 a count the rule
+ * divides by is zero (a gap never attempted; a rung without a label that has visited an end); 3 the ladder at hand is not finite or not
+ * strictly monotone; 4 the new ladder is not.  Status 0 writes beta_c = T(out[c mod R]) for every local chain (a Float32 ladder is
+ * rounded once, here), zeroes the gap counters and, with tracking on, sets the labels back to r | (d0(r) << 6) and zeroes both trip
+ * counters: a new ladder restarts the measurement.  Any other status leaves the handle exactly as it was.  x, the step indices, the step
+ * log, the Move counters and the widths per rung are left alone in every case.
+ * AMC_ERR_STATE: no ladder; rule AMC_RESPACE_FLOW with counts == NULL while tracking is off.  AMC_ERR_BAD_ARG naming the argument: an
+ * unknown rule, gamma outside (0, 1], eps outside [0, 1) (NaN included), counts with more accepted than attempted swaps.
+ * amc_respace_status: the status of the last respacing (0 before the first) and the number of status-0 respacings since the ladder was
+ * set (amc_set_ladder resets it, amc_upload_state leaves it alone; amc_set_respaced restores it on resume).  amc_get_ladder: the R beta
+ * values of the first local ladder as the device holds them.  Both synchronise. */
+#define AMC_RESPACE_ACCEPTANCE 1
+#define AMC_RESPACE_FLOW 2
+int  amc_respace_ladder(amc_handle *h, int rule, double gamma, double eps, const uint64_t *counts);
+int  amc_respace_status(amc_handle *h, int *status, int64_t *n_respaced);
+int  amc_set_respaced(amc_handle *h, int64_t n_respaced);
+int  amc_get_ladder(amc_handle *h, double *betas);
 
 /* MH steps done per chain so far (the Philox step index); settable for resume. */
 int  amc_get_step(amc_handle *h, uint64_t *t);

@@ -21,6 +21,8 @@ AMC_RED_HEADER = 4
 AMC_GD_STRIDE = 5
 AMC_XSUM_WORDS = 12      # doubles per record of a reproducible sum (include/amc.h)
 AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_REDUCE_ALL = 1, 2, 4, 7      # the sums over x a reduction forms (include/amc.h)
+AMC_RESPACE_ACCEPTANCE, AMC_RESPACE_FLOW = 1, 2      # the rules of amc_respace_ladder (include/amc.h)
+RESPACE_RULES = {"acceptance": AMC_RESPACE_ACCEPTANCE, "flow": AMC_RESPACE_FLOW}
 
 POTENTIALS = {"harmonic": 0, "double_well": 1}
 AMC_POTENTIAL_CUSTOM = 2
@@ -172,6 +174,10 @@ def load() -> C.CDLL:
         "amc_set_tracking_counters": (C.c_int, [H, C.c_int64, C.c_int64]),
         "amc_set_rung_sigma": (C.c_int, [H, dp, C.c_int]),
         "amc_get_rung_sigma": (C.c_int, [H, dp, C.c_int]),
+        "amc_respace_ladder": (C.c_int, [H, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),
+        "amc_respace_status": (C.c_int, [H, C.POINTER(C.c_int), i64p]),
+        "amc_set_respaced": (C.c_int, [H, C.c_int64]),
+        "amc_get_ladder": (C.c_int, [H, dp]),
         "amc_rung_counter_totals": (C.c_int, [H, i64p, i64p]),
     }
     for name, (res, args) in sig.items():
@@ -745,6 +751,43 @@ class HipEngine:
         n = max(int(getattr(self, "n_rungs", 0)), 1)
         out = np.zeros((self.n_moves, n), dtype=np.float64)
         _check(self._lib.amc_get_rung_sigma(self._h, _dptr(out), int(out.size)))
+        return out
+
+    # -- respacing the ladder (include/amc.h; DESIGN.md section 3.13 "Respacing") ----------------
+    def respace_ladder(self, rule, gamma: float = 1.0, eps: float = 0.0, counts=None) -> None:
+        """Queue one respacing of the ladder: ``rule`` "acceptance" (equalise the rejection rate per gap) or "flow" (the
+        feedback-optimised ladder; needs tracking when ``counts`` is None).  ``counts`` None: this handle's own counters, right only
+        when it holds every ladder -- nothing synchronises.  Otherwise the GLOBAL counts: for "acceptance" attempted[R - 1] then
+        accepted[R - 1], for "flow" n[R][3] as ``flow_rungs`` gives them.  ``respace_status`` tells what became of it."""
+        rule_id = RESPACE_RULES.get(rule, rule)
+        if not isinstance(rule_id, (int, np.integer)):
+            raise AmcError(f"respace_ladder: rule {rule!r} is none of {sorted(RESPACE_RULES)}")
+        ptr = None
+        if counts is not None:
+            R = int(getattr(self, "n_rungs", 0))
+            c = np.ascontiguousarray(counts).reshape(-1)
+            if c.size and (not np.all(np.isfinite(c)) or c.min() < 0 or np.any(c != np.floor(c))):
+                raise AmcError("respace_ladder: counts must be non-negative integers")
+            c = np.ascontiguousarray(c, dtype=np.uint64)
+            need = 2 * (R - 1) if rule_id == AMC_RESPACE_ACCEPTANCE else 3 * R
+            if c.size != need:
+                raise AmcError(f"respace_ladder: counts has {c.size} entries, rule {rule!r} with {R} rungs takes {need}")
+            ptr = c.ctypes.data_as(C.POINTER(C.c_uint64))
+        _check(self._lib.amc_respace_ladder(self._h, int(rule_id), float(gamma), float(eps), ptr))
+
+    def respace_status(self):
+        """(status of the last respacing, number of status-0 respacings since the ladder was set).  Synchronises."""
+        st, n = C.c_int(0), C.c_int64(0)
+        _check(self._lib.amc_respace_status(self._h, C.byref(st), C.byref(n)))
+        return st.value, n.value
+
+    def set_respaced(self, n_respaced: int) -> None:
+        _check(self._lib.amc_set_respaced(self._h, int(n_respaced)))
+
+    def ladder(self) -> np.ndarray:
+        """The R beta values of the ladder as the device holds them (the first local ladder).  Synchronises."""
+        out = np.zeros(max(int(getattr(self, "n_rungs", 0)), 1), dtype=np.float64)
+        _check(self._lib.amc_get_ladder(self._h, _dptr(out)))
         return out
 
     def rung_counter_totals(self):

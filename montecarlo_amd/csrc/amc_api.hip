@@ -558,6 +558,7 @@ int amc_destroy(amc_handle* h)
     (void)hipFree(h->d_rung_recs);
     (void)hipFree(h->d_lab);
     (void)hipFree(h->d_track);
+    (void)hipFree(h->d_respace);
     (void)hipFree(h->d_rung_tab);
     (void)hipFree(h->d_rung_cnt);
     if (h->h_params) (void)hipHostFree(h->h_params);

@@ -1,14 +1,18 @@
 // amc_exchange.h -- replica exchange along a temperature ladder: exchange_kernel, one step of neighbour
 // swaps inside every ladder of R consecutive chains, rung_sums_kernel / rung_finish_kernel, the reproducible sums of e, x, x^2 resolved
 // by rung, rung_histogram_kernel, amc_histogram's binning resolved by rung, and walker tracking: exchange_tracked_kernel, the same step
-// with TRACK on -- it also moves one label byte per chain and counts trips between the ends --, and rung_flow_kernel, the labels counted by
-// rung and direction.
+// with TRACK on -- it also moves one label byte per chain and counts trips between the ends --, rung_flow_kernel, the labels counted by
+// rung and direction, and respacing: ladder_respace_kernel, new beta values for the interior rungs from the gap or the flow counts
+// (the rule itself is amc_respace.h), and ladder_retile_kernel, which lays them over the chains.
 // The reference has no such algorithm of its own: a user writes it as an AriannaAlgorithm whose make_step! walks simulation.chains
 // (the plugin protocol, src/algorithms.jl:6-37); with the chains in HBM the engine provides the cross-chain move.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
 #pragma once
 
 #include "amc_aux_kernels.h"
+#if AMC_PLAIN_KERNELS
+#include "amc_respace.h"      // (the rule of ladder_respace_kernel, a plain kernel)
+#endif
 
 #define AMC_MAX_RUNGS 64
 
@@ -167,6 +171,89 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void rung_flow_kernel
     if (tid < n_chains - tail) flow_count(s_flow, (int)((tail + tid) % n_rungs), lab[tail + tid]);       // n_chains - tail <= 3
     __syncthreads();
     flush_cells(s_flow, counts, cells);
+}
+#endif
+
+// ---- respacing the ladder (amc_respace_ladder; DESIGN.md section 3.13 "Respacing") ---------------------------------------------------
+// The record of a handle's respacings in device memory, 64-bit words: the status of the last one, the number of status-0 ones, and
+// the ladder the last one computed (Float64 bit patterns; read by ladder_retile_kernel when the status is 0).
+enum { RESPACE_STATUS = 0, RESPACE_COUNT = 1, RESPACE_OUT = 2, RESPACE_WORDS = 2 + AMC_MAX_RUNGS };
+
+#if AMC_PLAIN_KERNELS
+struct RespaceCounts {
+    unsigned long long c[3 * AMC_MAX_RUNGS];      // the GLOBAL counts of a call that brings them: the rule's own layout (amc_respace.h)
+};
+struct RespaceArgs {
+    const void* beta;                   // the per-chain beta array: doubles, or floats with f32; the first local ladder is read
+    const unsigned long long* xcnt;     // local counts, RS_ACCEPTANCE: d_xcnt, attempted[AMC_MAX_RUNGS] then accepted[AMC_MAX_RUNGS]
+    const unsigned long long* flow;     // local counts, RS_FLOW: the flow snapshot n[R][3] rung_flow_kernel has just left
+    unsigned long long* gaps;           // d_xcnt again: zeroed with status 0
+    unsigned long long* trips;          // [2] the trip counters, zeroed with status 0; nullptr without tracking
+    unsigned long long* rec;            // [RESPACE_WORDS] the record above
+    double gamma, eps;
+    int32_t rule, n_rungs, f32, counts_given;
+};
+
+// One block of 64 threads.  Lane r brings b[r] and its counts -- from device memory, or from the kernel argument when the call
+// brought global counts -- into LDS; lane 0 runs the rule (serial, a few hundred Float64 operations at most: microseconds); then the
+// lanes store the record and, with status 0, zero the gap and the trip counters.
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void ladder_respace_kernel(const RespaceArgs a, const RespaceCounts given)
+{
+    __shared__ double s_b[AMC_MAX_RUNGS], s_out[AMC_MAX_RUNGS], s_w[AMC_MAX_RUNGS], s_G[AMC_MAX_RUNGS];
+    __shared__ uint64_t s_c[3 * AMC_MAX_RUNGS];
+    __shared__ int s_status;
+    const int r = threadIdx.x, R = a.n_rungs;
+    s_out[r] = 0.0;
+    if (r < R) {
+        s_b[r] = a.f32 ? (double)((const float*)a.beta)[r] : ((const double*)a.beta)[r];
+        if (a.rule == rs::RS_ACCEPTANCE) {
+            if (r < R - 1) {
+                s_c[r] = a.counts_given ? given.c[r] : a.xcnt[r];
+                s_c[R - 1 + r] = a.counts_given ? given.c[R - 1 + r] : a.xcnt[AMC_MAX_RUNGS + r];
+            }
+        } else {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) s_c[3 * r + d] = a.counts_given ? given.c[3 * r + d] : a.flow[3 * r + d];
+        }
+    }
+    __syncthreads();
+    if (r == 0) s_status = rs::respace_rule(a.rule, R, s_b, s_c, a.gamma, a.eps, s_out, s_w, s_G);
+    __syncthreads();
+    const int status = s_status;
+    a.rec[RESPACE_OUT + r] = (unsigned long long)__double_as_longlong(s_out[r]);
+    if (r == 0) {
+        a.rec[RESPACE_STATUS] = (unsigned long long)status;
+        if (status == rs::RS_OK) a.rec[RESPACE_COUNT] += 1ull;
+    }
+    if (status == rs::RS_OK) {
+        a.gaps[r] = 0ull;
+        a.gaps[AMC_MAX_RUNGS + r] = 0ull;
+        if (a.trips && r < 2) a.trips[r] = 0ull;
+    }
+}
+
+// The new ladder laid over every local chain: beta_c = T(out[c mod R]), and with tracking the label byte r | (d0(r) << 6).  Returns at
+// once unless the record says status 0.  Memory-bound, stores only: 8 B (4 B) per chain, 9 B (5 B) with labels.  Work items as in
+// the other exchange kernels: thread id = l0 R + r, a thread keeps its rung -- its beta and its label are formed once -- and advances
+// by (threads / R) ladders per trip, so the loop divides nothing and neighbouring lanes write neighbouring chains.
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void ladder_retile_kernel(void* beta, int f32, uint8_t* lab, int64_t n_ladders, int n_rungs,
+                                                                                      const unsigned long long* rec)
+{
+    if (rec[RESPACE_STATUS] != 0ull) return;
+    const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
+    const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / n_rungs;
+    const int64_t l0 = tid / n_rungs;
+    if (l0 >= ladders_per_trip) return;
+    const int r = (int)(tid - l0 * n_rungs);
+    const double b = __longlong_as_double((long long)rec[RESPACE_OUT + r]);
+    const float b32 = (float)b;
+    const uint8_t label = (uint8_t)((uint32_t)r | (r == 0 ? LAB_UP : r == n_rungs - 1 ? LAB_DOWN : 0u));
+    const int64_t step = ladders_per_trip * n_rungs, end = n_ladders * n_rungs;
+    for (int64_t i = l0 * n_rungs + r; i < end; i += step) {
+        if (f32) ((float*)beta)[i] = b32;
+        else ((double*)beta)[i] = b;
+        if (lab) lab[i] = label;
+    }
 }
 #endif
 

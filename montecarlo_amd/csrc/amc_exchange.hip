@@ -1,7 +1,7 @@
 // amc_exchange.hip -- replica exchange along a temperature ladder: the ladder of a handle, exchange steps
 // (amc_exchange, amc_sweep_exchange), the per-gap counters and the exchange step index, the per-rung reproducible sums
 // (amc_reduce_rungs_exact), walker tracking (amc_set_tracking .. amc_set_tracking_counters), proposal widths per rung
-// (amc_set_rung_sigma, amc_get_rung_sigma).  amc_histogram_rungs is with the other
+// (amc_set_rung_sigma, amc_get_rung_sigma), respacing the ladder (amc_respace_ladder .. amc_get_ladder).  amc_histogram_rungs is with the other
 // histograms in amc_state.hip.
 #define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copies of the plain kernels it launches (rung_finish_kernel, rung_flow_kernel)
 #include "amc_internal.h"
@@ -26,6 +26,9 @@ static const size_t XCNT_BYTES = 2 * AMC_MAX_RUNGS * sizeof(unsigned long long);
 // d_track: round_trips, up_trips, then the cells of one flow snapshot (amc_flow_rungs' scratch)
 static const int TRACK_FLOW_CELLS = 3 * AMC_MAX_RUNGS;
 static const size_t TRACK_BYTES = (2 + TRACK_FLOW_CELLS) * sizeof(unsigned long long);
+
+static const size_t RESPACE_BYTES = amc::RESPACE_WORDS * sizeof(unsigned long long);   // d_respace (amc_exchange.h RESPACE_*)
+static_assert(AMC_RESPACE_ACCEPTANCE == amc::rs::RS_ACCEPTANCE && AMC_RESPACE_FLOW == amc::rs::RS_FLOW, "the rules of include/amc.h and amc_respace.h");
 
 // Tracking off: the labels and the trip counters go.  Launches queued on the stream may still use them.
 static int tracking_off(amc_handle* h)
@@ -86,6 +89,7 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
     if (n_rungs == 0) {
         AMC_HIP(hipSetDevice(h->device));
         { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }
+        if (h->d_respace) AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));
         h->rung_on = false;
         h->n_rungs = 0;
         return AMC_OK;
@@ -106,6 +110,7 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
     { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }      // another ladder has other walkers
     if (!h->d_xcnt) AMC_HIP(hipMalloc(&h->d_xcnt, XCNT_BYTES));
     AMC_HIP(hipMemsetAsync(h->d_xcnt, 0, XCNT_BYTES, h->stream));      // the gaps of another ladder are other gaps
+    if (h->d_respace) AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));      // ... and nobody has respaced it
     h->rung_on = false;                                                // ... and its rungs other rungs: no widths per rung until they are set again
     h->n_rungs = n_rungs;
     return AMC_OK;
@@ -402,6 +407,111 @@ int amc_set_tracking_counters(amc_handle* h, int64_t round_trips, int64_t up_tri
     AMC_HIP(hipSetDevice(h->device));
     AMC_HIP(hipMemcpyAsync(h->d_track, host, sizeof host, hipMemcpyHostToDevice, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
+    return AMC_OK;
+}
+
+// ---- respacing the ladder (DESIGN.md section 3.13 "Respacing") -----------------------------------------------------------------------
+static int respace_record(amc_handle* h)
+{
+    if (h->d_respace) return AMC_OK;
+    AMC_HIP(hipMalloc(&h->d_respace, RESPACE_BYTES));
+    AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));
+    return AMC_OK;
+}
+
+int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const uint64_t* counts)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_respace_ladder: the handle has no ladder (amc_set_ladder)");
+    if (rule != AMC_RESPACE_ACCEPTANCE && rule != AMC_RESPACE_FLOW)
+        return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: rule = %d must be AMC_RESPACE_ACCEPTANCE (%d) or AMC_RESPACE_FLOW (%d)", rule,
+                    AMC_RESPACE_ACCEPTANCE, AMC_RESPACE_FLOW);
+    if (!(gamma > 0.0 && gamma <= 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: gamma = %g must lie in (0, 1]", gamma);
+    if (!(eps >= 0.0 && eps < 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: eps = %g must lie in [0, 1)", eps);
+    if (rule == AMC_RESPACE_FLOW && !counts && !h->d_lab)
+        return fail(AMC_ERR_STATE, "amc_respace_ladder: rule AMC_RESPACE_FLOW with counts == NULL reads this handle's labels, and tracking is off "
+                                   "(amc_set_tracking)");
+    const int R = h->n_rungs;
+    amc::RespaceCounts given;
+    std::memset(&given, 0, sizeof given);
+    if (counts) {
+        if (rule == AMC_RESPACE_ACCEPTANCE)
+            for (int j = 0; j < R - 1; ++j)
+                if (counts[R - 1 + j] > counts[j])
+                    return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: counts: gap %d has more accepted swaps than attempted ones", j);
+        const int n = rule == AMC_RESPACE_ACCEPTANCE ? 2 * (R - 1) : 3 * R;
+        for (int i = 0; i < n; ++i) given.c[i] = (unsigned long long)counts[i];
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
+    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    { const int rc = respace_record(h); if (rc != AMC_OK) return rc; }
+    unsigned long long* d_flow = h->d_lab ? h->d_track + 2 : nullptr;
+    if (rule == AMC_RESPACE_FLOW && !counts) {      // the flow snapshot of this handle's labels, into amc_flow_rungs' scratch
+        AMC_HIP(hipMemsetAsync(d_flow, 0, (size_t)(3 * R) * sizeof(unsigned long long), h->stream));
+        const int grid = grid_for(h, (h->M + 3) / 4, h->knobs.blocks_per_cu ? 0 : EXCHANGE_BLOCKS_PER_CU);
+        hipLaunchKernelGGL(amc::rung_flow_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint8_t*)h->d_lab, h->M, R, d_flow);
+        AMC_HIP(hipGetLastError());
+    }
+    amc::RespaceArgs a;
+    a.beta = h->d_beta;
+    a.xcnt = h->d_xcnt;
+    a.flow = d_flow;
+    a.gaps = h->d_xcnt;
+    a.trips = h->d_lab ? h->d_track : nullptr;
+    a.rec = h->d_respace;
+    a.gamma = gamma;
+    a.eps = eps;
+    a.rule = rule;
+    a.n_rungs = R;
+    a.f32 = h->f32 ? 1 : 0;
+    a.counts_given = counts ? 1 : 0;
+    hipLaunchKernelGGL(amc::ladder_respace_kernel, dim3(1), dim3(64), 0, h->stream, a, given);
+    AMC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(amc::ladder_retile_kernel, dim3(grid_for(h, h->M)), dim3(AMC_BLOCK), 0, h->stream, (void*)h->d_beta, a.f32, h->d_lab, h->M / R, R,
+                       (const unsigned long long*)h->d_respace);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
+int amc_respace_status(amc_handle* h, int* status, int64_t* n_respaced)
+{
+    if (!h || !status || !n_respaced) return fail(AMC_ERR_BAD_ARG, "amc_respace_status: NULL argument");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_respace_status: the handle has no ladder (amc_set_ladder)");
+    unsigned long long host[2] = {0ull, 0ull};
+    AMC_HIP(hipSetDevice(h->device));
+    if (h->d_respace) AMC_HIP(hipMemcpyAsync(host, h->d_respace, sizeof host, hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    *status = (int)host[amc::RESPACE_STATUS];
+    *n_respaced = (int64_t)host[amc::RESPACE_COUNT];
+    return AMC_OK;
+}
+
+int amc_set_respaced(amc_handle* h, int64_t n_respaced)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_respaced: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_respaced: the handle has no ladder (amc_set_ladder)");
+    if (n_respaced < 0) return fail(AMC_ERR_BAD_ARG, "amc_set_respaced: n_respaced < 0");
+    AMC_HIP(hipSetDevice(h->device));
+    { const int rc = respace_record(h); if (rc != AMC_OK) return rc; }
+    const unsigned long long host = (unsigned long long)n_respaced;
+    AMC_HIP(hipMemcpyAsync(h->d_respace + amc::RESPACE_COUNT, &host, sizeof host, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
+    return AMC_OK;
+}
+
+int amc_get_ladder(amc_handle* h, double* betas)
+{
+    if (!h || !betas) return fail(AMC_ERR_BAD_ARG, "amc_get_ladder: NULL argument");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_get_ladder: the handle has no ladder (amc_set_ladder)");
+    AMC_HIP(hipSetDevice(h->device));
+    double host[AMC_MAX_RUNGS];      // the first local ladder as the device holds it
+    float host32[AMC_MAX_RUNGS];
+    const int R = h->n_rungs;
+    if (h->f32) AMC_HIP(hipMemcpyAsync(host32, h->d_beta, (size_t)R * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    else AMC_HIP(hipMemcpyAsync(host, h->d_beta, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    for (int r = 0; r < R; ++r) betas[r] = h->f32 ? (double)host32[r] : host[r];
     return AMC_OK;
 }
 

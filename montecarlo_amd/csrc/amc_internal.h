@@ -7,7 +7,7 @@
 //   amc_sweeps.hip      sweep launches (amc_sweep*)
 //   amc_exchange.hip    replica exchange along a temperature ladder (amc_set_ladder, amc_exchange, amc_sweep_exchange, gap counters,
 //                       the per-rung reproducible sums: amc_reduce_rungs_exact, walker tracking: amc_set_tracking ..,
-//                       proposal widths per rung: amc_set_rung_sigma / amc_get_rung_sigma)
+//                       proposal widths per rung: amc_set_rung_sigma / amc_get_rung_sigma, respacing: amc_respace_ladder ..)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -172,6 +172,8 @@ struct amc_handle {
     double* d_rung_recs = nullptr;          // [AMC_MAX_RUNGS][RED_COLS][XS_WORDS] their records (rung_finish_kernel)
     uint8_t* d_lab = nullptr;               // [M] walker labels, w | (d << 6) per chain; allocated exactly while tracking is on (amc_set_tracking)
     unsigned long long* d_track = nullptr;  // [2 + 3 * AMC_MAX_RUNGS] round_trips, up_trips, the cells of one flow snapshot (allocated with d_lab)
+    unsigned long long* d_respace = nullptr;   // [RESPACE_WORDS] status of the last respacing, the count of status-0 ones, the ladder it computed
+                                               // (amc_respace_ladder; allocated at its first use, zeroed by amc_set_ladder)
     // Proposal widths per (move, rung) (amc_set_rung_sigma): a table is set exactly while rung_on; the sweeps then launch the RUNG form,
     // which reads d_rung_tab where the others read ptab's rows
     bool rung_on = false;

@@ -108,11 +108,84 @@ class ReplicaExchange(AriannaAlgorithm):
         out[:, ~asked] = np.nan
         return out
 
+    def betas(self) -> np.ndarray:
+        """The ladder as the device holds it now, R beta values (Float32 state: the Float32 values, widened).  The host waits for
+        the queued steps."""
+        return self.metropolis.engine.ladder()
+
+    def respace(self, rule: str = "flow", gamma: float = 1.0, eps: float = 0.01):
+        """Respace the ladder on the device (DESIGN.md section 3.13 "Respacing"): "flow" puts the rungs where the flow fraction
+        falls (the feedback-optimised ladder; needs track=True), "acceptance" equalises the rejection rate per gap; ``gamma`` in
+        (0, 1] damps the move, ``eps`` in [0, 1) is the floor of a gap's weight.  With one shard the engine uses its own counters and
+        nothing is read back before the ladder is; with several the counts are summed over the shards as acceptance() and flow() sum
+        them and every shard is given the sums, so all compute the same ladder.  A respacing that is taken (status 0) zeroes the gap
+        counters and restarts the tracking: the measurement belongs to a ladder.  ``chains.beta_array`` follows, so a checkpoint
+        written afterwards carries the new ladder.  Returns (status, n_respaced) (amc_respace_status).
+        Changing beta during a run breaks detailed balance: respace during burn-in (see RespaceLadder)."""
+        if rule == "flow":
+            self._need_tracking('ReplicaExchange.respace("flow")')
+        elif rule != "acceptance":
+            raise ValueError(f"ReplicaExchange.respace: rule {rule!r} is neither 'flow' nor 'acceptance'")
+        met = self.metropolis
+        eng = met.engine
+        counts = None
+        if sharding.world()[1] > 1:
+            if rule == "acceptance":
+                acc, att = eng.exchange_counters()
+                local = np.concatenate([att, acc])
+            else:
+                local = eng.flow_rungs().reshape(-1)
+            counts = np.rint(sharding.allreduce_sum(local.astype(np.float64), eng)).astype(np.int64)
+        eng.respace_ladder(rule, gamma, eps, counts=counts)
+        met.invalidate_reductions()
+        status = eng.respace_status()
+        if status[0] == 0 and met.chains.beta_array is not None:
+            ladder = eng.ladder()
+            met.chains.beta_array[:] = np.tile(ladder, len(met.chains) // self.n_rungs)
+        return status
+
     def write_algorithm(self, io, scheduler) -> None:
         io.write("\tReplicaExchange\n")
         io.write(f"\t\tCalls: {_calls(scheduler)}\n")
         io.write(f"\t\tRungs: {self.n_rungs}\n")
         io.write(f"\t\tLadders: {len(self.metropolis.chains) // self.n_rungs}\n")
+
+
+class RespaceLadder(AriannaAlgorithm):
+    """RespaceLadder(chains; dependencies=(ReplicaExchange,), rule="flow", gamma=1.0, eps=0.01, until=None): one respacing of the
+    ReplicaExchange's ladder per scheduled time (ReplicaExchange.respace), and none after time step ``until``.
+
+    A BURN-IN tool: changing beta in the middle of a run breaks detailed balance, so the samples taken while the ladder still moves
+    are not samples of the final ladder's ensemble.  Schedule it over the first part of the run, or give ``until``, and measure
+    afterwards.  An algorithm of its own, so the schedule decides when it runs; a time step at which it is due ends a fused stretch
+    of ``run(fuse=True)`` like any other algorithm that is due."""
+
+    mutates_chains = True          # (beta moves: a callback due behind it at the same t observes the new ladder)
+
+    def __init__(self, chains, dependencies=None, rule="flow", gamma=1.0, eps=0.01, until=None, path=None, **extras):
+        assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], ReplicaExchange)
+        self.exchange: ReplicaExchange = dependencies[0]
+        if rule not in ("flow", "acceptance"):
+            raise ValueError(f"RespaceLadder: rule {rule!r} is neither 'flow' nor 'acceptance'")
+        if rule == "flow" and not self.exchange.track:
+            raise ValueError('RespaceLadder: rule "flow" needs walker tracking: build the ReplicaExchange with track=True')
+        self.rule, self.gamma, self.eps = rule, float(gamma), float(eps)
+        self.until = None if until is None else int(until)
+        self.statuses = []         # (t, status) of every respacing asked for
+
+    def make_step(self, simulation: Simulation) -> None:
+        if self.until is not None and simulation.t > self.until:
+            return
+        status, _ = self.exchange.respace(self.rule, self.gamma, self.eps)
+        self.statuses.append((simulation.t, status))
+
+    def write_algorithm(self, io, scheduler) -> None:
+        io.write("\tRespaceLadder\n")
+        io.write(f"\t\tCalls: {_calls(scheduler)}\n")
+        io.write(f"\t\tRule: {self.rule}\n")
+        io.write(f"\t\tGamma: {self.gamma}\n")
+        io.write(f"\t\tEps: {self.eps}\n")
+        io.write(f"\t\tUntil: {self.until}\n")
 
 
 def _find_exchange(simulation: Simulation) -> ReplicaExchange:
@@ -138,6 +211,12 @@ def callback_rung_acceptance(simulation: Simulation) -> np.ndarray:
 def callback_flow_fraction(simulation: Simulation) -> np.ndarray:
     """The flow fraction f(r) per rung, a vector of R values (ReplicaExchange.flow).  Needs ReplicaExchange(..., track=True)."""
     return _find_exchange(simulation).flow()
+
+
+def callback_ladder(simulation: Simulation) -> np.ndarray:
+    """beta per rung as the device holds it now, a vector of R values (ReplicaExchange.betas): with StoreCallbacks, the history of a
+    ladder that RespaceLadder moves.  The host waits for the queued steps."""
+    return _find_exchange(simulation).betas()
 
 
 def callback_round_trips(simulation: Simulation) -> np.ndarray:

@@ -162,6 +162,9 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
         if getattr(metropolis, "tracking", False):  # walker tracking is on: the labels and the trip counters are state too
             walker, direction = eng.labels()
             data.update(walker=walker, direction=direction, trips=np.array(eng.tracking_counters(), dtype=np.int64))
+        n_respaced = eng.respace_status()[1] if hasattr(eng, "respace_status") else 0
+        if n_respaced:                              # the ladder was respaced (ReplicaExchange.respace keeps beta_array current): no field otherwise
+            data["n_respaced"] = n_respaced
     if estimator is not None:
         data["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in estimator.gradients_data])
     os.makedirs(path, exist_ok=True)
@@ -211,6 +214,9 @@ def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
             eng.set_labels(d["walker"], d["direction"])
             eng.set_tracking_counters(int(d["trips"][0]), int(d["trips"][1]))
             metropolis.tracking = True
+        if "n_respaced" in d:                       # a respaced ladder: the host copy follows the checkpoint's beta, as the engine did
+            eng.set_respaced(int(d["n_respaced"]))
+            metropolis.chains.beta_array[start:stop] = d["beta"]
     if estimator is not None and "gd" in d:
         from .policy_guided import GradientData
         estimator.gradients_data = [GradientData(float(r[0]), np.array([r[1]]), np.array([r[2]]), np.array([[r[3]]]), int(r[4]))
