@@ -7,6 +7,7 @@ down.  Every chain starts in the right well; the script runs the same schedule w
 rung, the fraction of chains left of the barrier, the mean energy and the swap acceptance of every gap.
 
     python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track] [--rung-sigma] [--adapt flow|acceptance]
+                                          [--tune-sigma TARGET]
 
 --track also follows every replica through the swaps and prints, at the end, the flow fraction f(r) -- of the replicas at rung r that
 have been to an end of the ladder, the share that came from the hot end (rung 0) last -- and the round trips per ladder.
@@ -18,6 +19,12 @@ hot rungs then take the long steps they are there for.  The acceptance of the mo
 last at steps / 2; "flow" turns tracking on) and leaves it alone afterwards -- moving beta breaks detailed balance, so the first half is
 burn-in.  A respacing zeroes the gap counters and restarts the tracking, so the swap acceptance per gap and the round trips printed at
 the end are those of the second half, on the final ladder, which is printed too.
+
+--tune-sigma TARGET tunes the proposal width of every rung on the device towards the acceptance TARGET during the first half of the run
+(TuneRungSigma, ten tunings, the last at steps / 2; listed behind RespaceLadder, so with --adapt the widths follow the ladder as it moves)
+and leaves the widths alone afterwards -- changing sigma breaks detailed balance across the change, so the first half is burn-in.  The
+table starts from sigma_0 at every rung, or from the table of --rung-sigma.  The tuned table is printed, and beside it the acceptance
+per rung over the window since the last tuning: the second half, under the final table.
 """
 import argparse
 import os
@@ -41,6 +48,8 @@ def one_run(args, path, exchange: bool):
     if exchange and args.rung_sigma:
         # sigma_0 is the width of the hottest rung; the equilibrium width of a well shrinks like 1 / sqrt(beta)
         algorithm_list[0]["rung_sigma"] = [SIGMA0 * np.sqrt(BETAS[0] / b) for b in BETAS]
+    elif exchange and args.tune_sigma is not None:
+        algorithm_list[0]["rung_sigma"] = [SIGMA0] * len(BETAS)
     callbacks = [ma.callback_energy]
     if exchange:
         track = args.track or args.adapt == "flow"
@@ -52,6 +61,12 @@ def one_run(args, path, exchange: bool):
             algorithm_list.append(dict(algorithm=ma.RespaceLadder, dependencies=(ma.ReplicaExchange,), rule=args.adapt, gamma=0.7, eps=0.01,
                                        scheduler=list(range(half - 4 * every, half + 1, every)), until=half))
             callbacks.append(ma.callback_ladder)
+        if args.tune_sigma is not None:
+            half = args.steps // 2
+            every = max(1, half // 10)
+            algorithm_list.append(dict(algorithm=ma.TuneRungSigma, dependencies=(ma.Metropolis,), target=args.tune_sigma, gamma=1.0, min_calls=1000,
+                                       scheduler=list(range(half - 9 * every, half + 1, every)), until=half))
+            callbacks.append(ma.callback_rung_sigma)
     algorithm_list.append(dict(algorithm=ma.StoreCallbacks, callbacks=tuple(callbacks),
                                scheduler=ma.build_schedule(args.steps, 0, max(1, args.steps // 10))))
     simulation = ma.Simulation(chains, algorithm_list, args.steps, path=path)
@@ -74,6 +89,9 @@ def main(argv=None):
     ap.add_argument("--rung-sigma", action="store_true", help="a proposal width per rung, sigma_r = sigma_0 sqrt(beta_0 / beta_r); print the move's acceptance per rung")
     ap.add_argument("--adapt", choices=("flow", "acceptance"), default=None,
                     help="respace the ladder during the first half of the run; print the ladder, and the swap acceptance and round trips of the second half")
+    ap.add_argument("--tune-sigma", type=float, default=None, metavar="TARGET",
+                    help="tune the proposal width of every rung towards this acceptance during the first half of the run; print the table and the "
+                         "acceptance per rung of the second half")
     args = ap.parse_args(argv)
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
@@ -84,7 +102,11 @@ def main(argv=None):
     print("mean energy, with exchange    : " + "  ".join(f"{v:7.4f}" for v in energy))
     print("mean energy, without          : " + "  ".join(f"{v:7.4f}" for v in energy_plain))
     print("swap acceptance per gap       : " + "  ".join(f"{v:7.4f}" for v in accept))
-    if args.rung_sigma:
+    if args.tune_sigma is not None:
+        met = sim.algorithms[0]
+        print(f"width per rung, {met.engine.tune_status()[1]:2d} tunings    : " + "  ".join(f"{v:7.4f}" for v in met.rung_sigma[0]))
+        print("acceptance since the last one : " + "  ".join(f"{v:7.4f}" for v in met.rung_window_acceptance()[0]))
+    elif args.rung_sigma:
         print("proposal width per rung       : " + "  ".join(f"{v:7.4f}" for v in sim.algorithms[0].rung_sigma[0]))
         print("move acceptance per rung      : " + "  ".join(f"{v:7.4f}" for v in ma.callback_rung_acceptance(sim)[0]))
     print("coldest rung, 8 bins of [-2, 2): " + " ".join(str(int(v)) for v in hist[-1][:8]))

@@ -447,6 +447,38 @@ int  amc_respace_ladder(amc_handle *h, int rule, double gamma, double eps, const
 int  amc_respace_status(amc_handle *h, int *status, int64_t *n_respaced);
 int  amc_set_respaced(amc_handle *h, int64_t n_respaced);
 int  amc_get_ladder(amc_handle *h, double *betas);
+/* Tuning the widths per rung (DESIGN.md section 3.13 "Tuning the widths", which holds the rule operation by operation): every entry
+ * e = k * R + r of the table moves by one damped fixed-point step sigma <- sigma * a / target, a = accepted / total calls of move k at
+ * rung r over the current WINDOW, limited to a factor of two per call and clamped to [sigma_lo, sigma_hi]; gamma in (0, 1] damps the step,
+ * an entry with fewer than min_calls calls in the window keeps its width.  Computed on the device from the table the device holds; the
+ * four derived rows of a tuned entry are rewritten as amc_set_rung_sigma forms them, so the sweeps that follow are those of a pool with
+ * the new widths, bit for bit.  Stream-ordered behind what is queued (a pending learning step is taken first); with counts == NULL
+ * nothing synchronises and nothing is read back.
+ * The window: per (move, rung) the Move counters' totals (amc_rung_counter_totals) minus their value at the start of the window, a
+ * device array that exists from its first use (zero then: the first window is "since the counters began").  A tuning ends the window and
+ * starts the next in every case; amc_rung_window_restart does so without tuning.  amc_set_ladder drops the base; nothing else touches
+ * it, and the Move counters themselves are never written.  A cell whose counter is below its base (counters uploaded behind it) is
+ * inconsistent: status 2, not an error.
+ * counts == NULL: the handle's own window -- right only when the handle holds every ladder.  Otherwise counts is the GLOBAL window, summed
+ * over all shards by the caller, accepted[K * R] then total[K * R], and travels with the launch: every shard given the same counts
+ * computes the same table.
+ * Status per entry (amc_tune_status, of the last call): 0 tuned; 1 fewer than min_calls calls, sigma keeps its bits; 2 inconsistent
+ * window, sigma keeps its bits; 3 tuned and clamped.  n_tuned counts the calls that tuned at least one entry (status 0 or 3) since the
+ * table was set: amc_set_rung_sigma and amc_set_ladder reset the record, amc_set_tuned restores the count on resume.
+ * Once a tuning has been queued amc_get_rung_sigma returns the table as the device holds it (and synchronises).
+ * AMC_ERR_STATE: no ladder, per_chain_counters = 0, no table set.  AMC_ERR_BAD_ARG naming the argument: target outside (0, 1), gamma
+ * outside (0, 1], min_calls < 1, sigma_lo or sigma_hi outside [1e-100, 1e100] or sigma_lo > sigma_hi (NaN included), counts that are
+ * negative or hold more accepted calls than calls.  A refused call leaves the handle as it was.
+ * amc_rung_window_counts: the local window per cell, -1 in both outputs for an inconsistent cell; synchronises, changes nothing.
+ * amc_rung_window_base / amc_set_rung_window_base: the base itself, for exact resume.  The amc_rung_window_* entries need a ladder,
+ * per-chain counters and K * R <= AMC_MAX_MOVES (AMC_ERR_STATE otherwise), with or without a table. */
+int  amc_tune_rung_sigma(amc_handle *h, double target, double gamma, int64_t min_calls, double sigma_lo, double sigma_hi, const int64_t *counts);
+int  amc_tune_status(amc_handle *h, int *st, int n, int64_t *n_tuned);
+int  amc_set_tuned(amc_handle *h, int64_t n_tuned);
+int  amc_rung_window_counts(amc_handle *h, int64_t *accepted, int64_t *total);
+int  amc_rung_window_restart(amc_handle *h);
+int  amc_rung_window_base(amc_handle *h, int64_t *accepted, int64_t *total);
+int  amc_set_rung_window_base(amc_handle *h, const int64_t *accepted, const int64_t *total);
 
 /* MH steps done per chain so far (the Philox step index); settable for resume. */
 int  amc_get_step(amc_handle *h, uint64_t *t);

@@ -16,7 +16,8 @@ from .sharding import allreduce_sum, init_store_group, shard_range
 from .simulation import (AriannaAlgorithm, PrintTimeSteps, Simulation, StoreCallbacks, StoreParameters,
                          build_schedule, julia_repr, run)
 from .exchange import (ReplicaExchange, callback_exchange_acceptance, callback_rung_acceptance, callback_flow_fraction, callback_round_trips, callback_rung_energy,
-                       callback_rung_moments, rung_energy, RespaceLadder, callback_ladder)
+                       callback_rung_moments, rung_energy, RespaceLadder, callback_ladder, TuneRungSigma, callback_rung_sigma,
+                       callback_rung_window_acceptance)
 from .storage import StoreHistogram, StoreSnapshots, checkpoint, restore
 from .trajectories import DAT, TXT, StoreBackups, StoreLastFrames, StoreTrajectories
 from .system import Action, AriannaSystem, Policy
@@ -33,7 +34,8 @@ __all__ = [
     "build_schedule", "julia_repr", "run",
     "StoreHistogram", "StoreSnapshots", "checkpoint", "restore",
     "ReplicaExchange", "callback_exchange_acceptance", "callback_rung_acceptance", "callback_flow_fraction", "callback_round_trips", "callback_rung_energy",
-    "callback_rung_moments", "rung_energy", "RespaceLadder", "callback_ladder",
+    "callback_rung_moments", "rung_energy", "RespaceLadder", "callback_ladder", "TuneRungSigma", "callback_rung_sigma",
+    "callback_rung_window_acceptance",
     "DAT", "TXT", "StoreBackups", "StoreLastFrames", "StoreTrajectories",
     "Action", "AriannaSystem", "Policy", "CustomPotential", "Displacement", "Move", "ParticleChains", "ScaledGaussian", "ScriptAction", "ScriptPolicy", "StandardGaussian", "potential",
 ]

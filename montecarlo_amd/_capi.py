@@ -179,6 +179,13 @@ def load() -> C.CDLL:
         "amc_set_respaced": (C.c_int, [H, C.c_int64]),
         "amc_get_ladder": (C.c_int, [H, dp]),
         "amc_rung_counter_totals": (C.c_int, [H, i64p, i64p]),
+        "amc_tune_rung_sigma": (C.c_int, [H, C.c_double, C.c_double, C.c_int64, C.c_double, C.c_double, i64p]),
+        "amc_tune_status": (C.c_int, [H, C.POINTER(C.c_int), C.c_int, i64p]),
+        "amc_set_tuned": (C.c_int, [H, C.c_int64]),
+        "amc_rung_window_counts": (C.c_int, [H, i64p, i64p]),
+        "amc_rung_window_restart": (C.c_int, [H]),
+        "amc_rung_window_base": (C.c_int, [H, i64p, i64p]),
+        "amc_set_rung_window_base": (C.c_int, [H, i64p, i64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -747,7 +754,8 @@ class HipEngine:
         _check(self._lib.amc_set_rung_sigma(self._h, _dptr(s), int(s.size)))
 
     def rung_sigma(self) -> np.ndarray:
-        """The table as it was set, shape (K, R)."""
+        """The table in force, shape (K, R): as it was set, or -- once a tuning has been queued -- as the device holds it (the host
+        then waits for the queued steps)."""
         n = max(int(getattr(self, "n_rungs", 0)), 1)
         out = np.zeros((self.n_moves, n), dtype=np.float64)
         _check(self._lib.amc_get_rung_sigma(self._h, _dptr(out), int(out.size)))
@@ -789,6 +797,72 @@ class HipEngine:
         out = np.zeros(max(int(getattr(self, "n_rungs", 0)), 1), dtype=np.float64)
         _check(self._lib.amc_get_ladder(self._h, _dptr(out)))
         return out
+
+    # -- tuning the widths per rung (include/amc.h; DESIGN.md section 3.13 "Tuning the widths") ----------------
+    def _cells(self):
+        return self.n_moves, max(int(getattr(self, "n_rungs", 0)), 1)
+
+    def tune_rung_sigma(self, target: float = 0.44, gamma: float = 1.0, min_calls: int = 1000, sigma_lo: float = 1e-100,
+                        sigma_hi: float = 1e100, counts=None) -> None:
+        """Queue one tuning of the table: every entry takes the damped step sigma <- sigma a / target with the acceptance a of its
+        window.  ``counts`` None: this handle's own window, right only when it holds every ladder -- nothing synchronises.  Otherwise
+        the GLOBAL window, (accepted, total), each of shape (K, R).  ``tune_status`` tells what became of every entry."""
+        ptr = None
+        if counts is not None:
+            K, R = self._cells()
+            try:
+                c = np.ascontiguousarray(np.concatenate([np.asarray(counts[0]).reshape(-1), np.asarray(counts[1]).reshape(-1)]))
+            except Exception as exc:
+                raise AmcError(f"tune_rung_sigma: counts must be (accepted, total), each of shape ({K}, {R}) ({exc})") from None
+            if c.size != 2 * K * R:
+                raise AmcError(f"tune_rung_sigma: counts has {c.size} entries, the table of {K} moves x {R} rungs takes 2 x {K * R}")
+            if c.dtype.kind not in "iu" and (not np.all(np.isfinite(c)) or np.any(c != np.floor(c))):
+                raise AmcError("tune_rung_sigma: counts must be integers")
+            c = np.ascontiguousarray(c, dtype=np.int64)
+            ptr = c.ctypes.data_as(C.POINTER(C.c_int64))
+        _check(self._lib.amc_tune_rung_sigma(self._h, float(target), float(gamma), int(min_calls), float(sigma_lo), float(sigma_hi), ptr))
+
+    def tune_status(self):
+        """(status per entry of the last tuning, shape (K, R); number of calls that tuned at least one entry since the table was set).
+        Synchronises."""
+        K, R = self._cells()
+        st = np.zeros((K, R), dtype=np.int32)
+        n = C.c_int64(0)
+        _check(self._lib.amc_tune_status(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), int(st.size), C.byref(n)))
+        return st, n.value
+
+    def set_tuned(self, n_tuned: int) -> None:
+        _check(self._lib.amc_set_tuned(self._h, int(n_tuned)))
+
+    def _i64_pair(self, fn):
+        K, R = self._cells()
+        acc = np.zeros((K, R), dtype=np.int64)
+        tot = np.zeros((K, R), dtype=np.int64)
+        p = C.POINTER(C.c_int64)
+        _check(fn(self._h, acc.ctypes.data_as(p), tot.ctypes.data_as(p)))
+        return acc, tot
+
+    def rung_window_counts(self):
+        """(accepted, total) of this shard over the current window, each of shape (K, R); -1 in both where the counters were replaced
+        behind the window's start.  Synchronises, changes nothing."""
+        return self._i64_pair(self._lib.amc_rung_window_counts)
+
+    def rung_window_restart(self) -> None:
+        """The window starts here (stream-ordered, nothing is read back)."""
+        _check(self._lib.amc_rung_window_restart(self._h))
+
+    def rung_window_base(self):
+        """(accepted, total) per (move, rung) as they stood when the window began."""
+        return self._i64_pair(self._lib.amc_rung_window_base)
+
+    def set_rung_window_base(self, accepted, total) -> None:
+        K, R = self._cells()
+        a = np.ascontiguousarray(accepted, dtype=np.int64).reshape(-1)
+        t = np.ascontiguousarray(total, dtype=np.int64).reshape(-1)
+        if a.size != K * R or t.size != K * R:
+            raise AmcError(f"set_rung_window_base: {a.size} and {t.size} entries, the window of {K} moves x {R} rungs has {K * R}")
+        p = C.POINTER(C.c_int64)
+        _check(self._lib.amc_set_rung_window_base(self._h, a.ctypes.data_as(p), t.ctypes.data_as(p)))
 
     def rung_counter_totals(self):
         """(accepted, total), each of shape (K, R): the Move counters summed over this shard's ladders per (move, rung), exact."""

@@ -561,6 +561,8 @@ int amc_destroy(amc_handle* h)
     (void)hipFree(h->d_respace);
     (void)hipFree(h->d_rung_tab);
     (void)hipFree(h->d_rung_cnt);
+    (void)hipFree(h->d_rung_base);
+    (void)hipFree(h->d_tune);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

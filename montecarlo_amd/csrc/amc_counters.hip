@@ -226,6 +226,39 @@ int counter_room(amc_handle* h, const char* who, uint64_t steps)
     return AMC_OK;
 }
 
+// The totals per (move, rung) queued into d_rung_cnt -- accepted[K R] then total[K R], the last move's total cells left at zero (it has
+// no total array; amc_rung_counter_totals completes it on the host, rung_sigma_tune_kernel on the device) -- behind a fold of the
+// pending log rows.  Nothing is read back.  The caller has checked the ladder and the counters and set the device.
+int rung_totals_queue(amc_handle* h)
+{
+    { const int rc = fold_log(h); if (rc != AMC_OK) return rc; }
+    const int R = h->n_rungs;
+    const size_t cells = (size_t)h->K * (size_t)R;
+    if (cells > h->rung_cnt_cells) {
+        AMC_HIP(hipStreamSynchronize(h->stream));               // (nothing queued reads the old cells after this call's predecessor returned)
+        (void)hipFree(h->d_rung_cnt);
+        h->d_rung_cnt = nullptr;
+        h->rung_cnt_cells = 0;
+        AMC_HIP(hipMalloc(&h->d_rung_cnt, 2 * cells * sizeof(unsigned long long)));
+        h->rung_cnt_cells = cells;
+    }
+    unsigned long long* out_acc = h->d_rung_cnt;
+    unsigned long long* out_tot = h->d_rung_cnt + cells;
+    AMC_HIP(hipMemsetAsync(h->d_rung_cnt, 0, 2 * cells * sizeof(unsigned long long), h->stream));
+    const int grid = grid_for(h, h->M);
+    if (h->narrow)
+        hipLaunchKernelGGL(amc::rung_counter_totals_kernel<uint16_t>, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint16_t*)h->d_acc16,
+                           (const uint16_t*)h->d_tot16, (const uint16_t*)(h->use_high ? h->d_acc_hi : nullptr),
+                           (const uint16_t*)(h->use_high ? h->d_tot_hi : nullptr), (const unsigned long long*)h->d_acc_base,
+                           (const unsigned long long*)h->d_tot_base, h->M, h->M_pad, h->K, R, out_acc, out_tot);
+    else
+        hipLaunchKernelGGL(amc::rung_counter_totals_kernel<uint32_t>, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint32_t*)h->d_acc,
+                           (const uint32_t*)h->d_tot, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const unsigned long long*)h->d_acc_base,
+                           (const unsigned long long*)h->d_tot_base, h->M, h->M_pad, h->K, R, out_acc, out_tot);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
 extern "C" {
 
 int amc_download_counters(amc_handle* h, int64_t* accepted, int64_t* total)
@@ -318,31 +351,9 @@ int amc_rung_counter_totals(amc_handle* h, int64_t* accepted, int64_t* total)
     if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_rung_counter_totals: the handle has no ladder (amc_set_ladder)");
     if (!h->counters) return fail(AMC_ERR_STATE, "amc_rung_counter_totals: handle was created with per_chain_counters = 0");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = fold_log(h); if (rc != AMC_OK) return rc; }
+    { const int rc = rung_totals_queue(h); if (rc != AMC_OK) return rc; }
     const int R = h->n_rungs;
     const size_t cells = (size_t)h->K * (size_t)R;
-    if (cells > h->rung_cnt_cells) {
-        AMC_HIP(hipStreamSynchronize(h->stream));               // (nothing queued reads the old cells after this call's predecessor returned)
-        (void)hipFree(h->d_rung_cnt);
-        h->d_rung_cnt = nullptr;
-        h->rung_cnt_cells = 0;
-        AMC_HIP(hipMalloc(&h->d_rung_cnt, 2 * cells * sizeof(unsigned long long)));
-        h->rung_cnt_cells = cells;
-    }
-    unsigned long long* out_acc = h->d_rung_cnt;
-    unsigned long long* out_tot = h->d_rung_cnt + cells;
-    AMC_HIP(hipMemsetAsync(h->d_rung_cnt, 0, 2 * cells * sizeof(unsigned long long), h->stream));
-    const int grid = grid_for(h, h->M);
-    if (h->narrow)
-        hipLaunchKernelGGL(amc::rung_counter_totals_kernel<uint16_t>, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint16_t*)h->d_acc16,
-                           (const uint16_t*)h->d_tot16, (const uint16_t*)(h->use_high ? h->d_acc_hi : nullptr),
-                           (const uint16_t*)(h->use_high ? h->d_tot_hi : nullptr), (const unsigned long long*)h->d_acc_base,
-                           (const unsigned long long*)h->d_tot_base, h->M, h->M_pad, h->K, R, out_acc, out_tot);
-    else
-        hipLaunchKernelGGL(amc::rung_counter_totals_kernel<uint32_t>, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint32_t*)h->d_acc,
-                           (const uint32_t*)h->d_tot, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const unsigned long long*)h->d_acc_base,
-                           (const unsigned long long*)h->d_tot_base, h->M, h->M_pad, h->K, R, out_acc, out_tot);
-    AMC_HIP(hipGetLastError());
     std::vector<unsigned long long> host(2 * cells);
     AMC_HIP(hipMemcpyAsync(host.data(), h->d_rung_cnt, 2 * cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));

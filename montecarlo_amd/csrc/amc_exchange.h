@@ -3,7 +3,8 @@
 // by rung, rung_histogram_kernel, amc_histogram's binning resolved by rung, and walker tracking: exchange_tracked_kernel, the same step
 // with TRACK on -- it also moves one label byte per chain and counts trips between the ends --, rung_flow_kernel, the labels counted by
 // rung and direction, and respacing: ladder_respace_kernel, new beta values for the interior rungs from the gap or the flow counts
-// (the rule itself is amc_respace.h), and ladder_retile_kernel, which lays them over the chains.
+// (the rule itself is amc_respace.h), and ladder_retile_kernel, which lays them over the chains; and tuning the widths per rung:
+// rung_sigma_tune_kernel (the rule itself is amc_tune.h) and rung_window_restart_kernel.
 // The reference has no such algorithm of its own: a user writes it as an AriannaAlgorithm whose make_step! walks simulation.chains
 // (the plugin protocol, src/algorithms.jl:6-37); with the chains in HBM the engine provides the cross-chain move.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
@@ -12,6 +13,7 @@
 #include "amc_aux_kernels.h"
 #if AMC_PLAIN_KERNELS
 #include "amc_respace.h"      // (the rule of ladder_respace_kernel, a plain kernel)
+#include "amc_tune.h"         // (the rule of rung_sigma_tune_kernel, a plain kernel)
 #endif
 
 #define AMC_MAX_RUNGS 64
@@ -254,6 +256,95 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void ladder_retile_ke
         else ((double*)beta)[i] = b;
         if (lab) lab[i] = label;
     }
+}
+#endif
+
+// ---- tuning the widths per rung (amc_tune_rung_sigma; DESIGN.md section 3.13 "Tuning the widths") -------------------------------------
+// The record of a handle's tunings in device memory, 64-bit words: the number of calls that tuned at least one entry (status 0 or 3)
+// since the table was set, then per entry the status of the last call and the width it left (Float64 bit patterns).
+enum { TUNE_COUNT = 0, TUNE_ST = 1, TUNE_SIGMA = 1 + AMC_MAX_MOVES, TUNE_WORDS = 1 + 2 * AMC_MAX_MOVES };
+// The window base d_rung_base: accepted[AMC_MAX_MOVES] then total[AMC_MAX_MOVES] per entry e = k R + r, as they stood when the window began.
+enum { RUNG_BASE_WORDS = 2 * AMC_MAX_MOVES };
+
+#if AMC_PLAIN_KERNELS
+struct TuneCounts {
+    unsigned long long c[2 * AMC_MAX_MOVES];      // the GLOBAL window of a call that brings it: accepted[K R] then total[K R]
+};
+struct TuneArgs {
+    double* rung_tab;                   // [RT_ROWS][AMC_MAX_MOVES] the rung table: RT_SIGMA is read, all four rows of a tuned entry are written
+    const unsigned long long* cnt;      // d_rung_cnt as rung_counter_totals_kernel has just left it: accepted[K R] then total[K R] (the last
+                                        // move's total cells hold nothing: it has no total array)
+    unsigned long long* base;           // [RUNG_BASE_WORDS] the window base
+    unsigned long long* rec;            // [TUNE_WORDS] the record above; nullptr: restart the window only
+    unsigned long long steps_per_rung;  // counted steps x local ladders: the calls of all moves together at one rung
+    unsigned long long min_calls;
+    double target, gamma, lo, hi;
+    int32_t n_moves, n_rungs, counts_given;
+};
+
+// Entry e's current totals: the accepted cell, and the total cell or -- the pool's last move -- what the other moves left of the
+// rung's steps (amc_rung_counter_totals completes it the same way on the host).
+__device__ __forceinline__ void rung_current_totals(const TuneArgs& a, int e, unsigned long long& acc, unsigned long long& tot)
+{
+    const int R = a.n_rungs, K = a.n_moves, cells = K * R;
+    const int k = e / R, r = e - k * R;
+    acc = a.cnt[e];
+    if (k + 1 < K) {
+        tot = a.cnt[cells + e];
+    } else {
+        unsigned long long others = 0ull;
+        for (int j = 0; j + 1 < K; ++j) others += a.cnt[cells + j * R + r];
+        tot = a.steps_per_rung - others;
+    }
+}
+
+// One block of AMC_MAX_MOVES threads, lane e owns entry e = k R + r: its window against the base (or the given global window), the
+// rule, the record, the four derived rows of the rung table (derive_move_params, as prepare_rung_params_kernel forms them; an entry
+// that keeps its sigma keeps its rows), and the base moved to the current totals.  No loop over chains: the only pass over memory
+// is the totals pass queued in front.
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_MAX_MOVES) void rung_sigma_tune_kernel(const TuneArgs a, const TuneCounts given)
+{
+    __shared__ int s_any;
+    const int e = (int)threadIdx.x, n = a.n_moves * a.n_rungs;
+    if (e == 0) s_any = 0;
+    __syncthreads();
+    if (e < n) {
+        unsigned long long acc, tot;
+        rung_current_totals(a, e, acc, tot);
+        const unsigned long long b_acc = a.base[e], b_tot = a.base[AMC_MAX_MOVES + e];
+        const bool bad = !a.counts_given && (acc < b_acc || tot < b_tot);
+        const uint64_t A = a.counts_given ? given.c[e] : acc - b_acc;
+        const uint64_t T = a.counts_given ? given.c[n + e] : tot - b_tot;
+        const double s = a.rung_tab[RT_SIGMA * AMC_MAX_MOVES + e];
+        double out;
+        const int st = tn::tune_rule(s, A, T, bad, a.target, a.gamma, a.min_calls, a.lo, a.hi, &out);
+        a.rec[TUNE_ST + e] = (unsigned long long)st;
+        a.rec[TUNE_SIGMA + e] = (unsigned long long)__double_as_longlong(out);
+        if (st == tn::TN_OK || st == tn::TN_CLAMPED) {
+            double d[DEF_N];
+            derive_move_params(out, d);
+            a.rung_tab[RT_SIGMA * AMC_MAX_MOVES + e] = d[DEF_SIGMA];
+            a.rung_tab[RT_DEN * AMC_MAX_MOVES + e] = d[DEF_DEN];
+            a.rung_tab[RT_RDEN * AMC_MAX_MOVES + e] = d[DEF_RDEN];
+            a.rung_tab[RT_LOGC * AMC_MAX_MOVES + e] = d[DEF_LOGC];
+            s_any = 1;
+        }
+        a.base[e] = acc;
+        a.base[AMC_MAX_MOVES + e] = tot;
+    }
+    __syncthreads();
+    if (e == 0 && s_any) a.rec[TUNE_COUNT] += 1ull;
+}
+
+// The window restarted without tuning: base = current totals.
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_MAX_MOVES) void rung_window_restart_kernel(const TuneArgs a)
+{
+    const int e = (int)threadIdx.x;
+    if (e >= a.n_moves * a.n_rungs) return;
+    unsigned long long acc, tot;
+    rung_current_totals(a, e, acc, tot);
+    a.base[e] = acc;
+    a.base[AMC_MAX_MOVES + e] = tot;
 }
 #endif
 

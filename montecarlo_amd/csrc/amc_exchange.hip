@@ -1,7 +1,8 @@
 // amc_exchange.hip -- replica exchange along a temperature ladder: the ladder of a handle, exchange steps
 // (amc_exchange, amc_sweep_exchange), the per-gap counters and the exchange step index, the per-rung reproducible sums
 // (amc_reduce_rungs_exact), walker tracking (amc_set_tracking .. amc_set_tracking_counters), proposal widths per rung
-// (amc_set_rung_sigma, amc_get_rung_sigma), respacing the ladder (amc_respace_ladder .. amc_get_ladder).  amc_histogram_rungs is with the other
+// (amc_set_rung_sigma, amc_get_rung_sigma), respacing the ladder (amc_respace_ladder .. amc_get_ladder), tuning the widths per rung
+// (amc_tune_rung_sigma .. amc_set_tuned) and the window of the acceptance per rung (amc_rung_window_*).  amc_histogram_rungs is with the other
 // histograms in amc_state.hip.
 #define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copies of the plain kernels it launches (rung_finish_kernel, rung_flow_kernel)
 #include "amc_internal.h"
@@ -28,7 +29,19 @@ static const int TRACK_FLOW_CELLS = 3 * AMC_MAX_RUNGS;
 static const size_t TRACK_BYTES = (2 + TRACK_FLOW_CELLS) * sizeof(unsigned long long);
 
 static const size_t RESPACE_BYTES = amc::RESPACE_WORDS * sizeof(unsigned long long);   // d_respace (amc_exchange.h RESPACE_*)
+static const size_t TUNE_BYTES = amc::TUNE_WORDS * sizeof(unsigned long long);            // d_tune (amc_exchange.h TUNE_*)
+static const size_t RUNG_BASE_BYTES = amc::RUNG_BASE_WORDS * sizeof(unsigned long long);  // d_rung_base
 static_assert(AMC_RESPACE_ACCEPTANCE == amc::rs::RS_ACCEPTANCE && AMC_RESPACE_FLOW == amc::rs::RS_FLOW, "the rules of include/amc.h and amc_respace.h");
+
+// The record of the tunings back to "never tuned"; with_base: the window base too (zero: the window is "since the counters began").
+// Memory a handle never allocated stays unallocated.
+static int tune_reset(amc_handle* h, bool with_base)
+{
+    if (h->d_tune) AMC_HIP(hipMemsetAsync(h->d_tune, 0, TUNE_BYTES, h->stream));
+    if (with_base && h->d_rung_base) AMC_HIP(hipMemsetAsync(h->d_rung_base, 0, RUNG_BASE_BYTES, h->stream));
+    h->tune_queued = false;
+    return AMC_OK;
+}
 
 // Tracking off: the labels and the trip counters go.  Launches queued on the stream may still use them.
 static int tracking_off(amc_handle* h)
@@ -90,6 +103,7 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
         AMC_HIP(hipSetDevice(h->device));
         { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }
         if (h->d_respace) AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));
+        { const int rc = tune_reset(h, true); if (rc != AMC_OK) return rc; }
         h->rung_on = false;
         h->n_rungs = 0;
         return AMC_OK;
@@ -111,6 +125,7 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
     if (!h->d_xcnt) AMC_HIP(hipMalloc(&h->d_xcnt, XCNT_BYTES));
     AMC_HIP(hipMemsetAsync(h->d_xcnt, 0, XCNT_BYTES, h->stream));      // the gaps of another ladder are other gaps
     if (h->d_respace) AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));      // ... and nobody has respaced it
+    { const int rc = tune_reset(h, true); if (rc != AMC_OK) return rc; }                        // ... nor tuned its widths; another R has other cells
     h->rung_on = false;                                                // ... and its rungs other rungs: no widths per rung until they are set again
     h->n_rungs = n_rungs;
     return AMC_OK;
@@ -125,6 +140,7 @@ int amc_set_rung_sigma(amc_handle* h, const double* sigma, int n)
         // memory stays for the sweeps already queued.  No pg_resolve either: every estimator entry is refused while a table is
         // set, and setting it took the step that was pending then, so none can be pending here.
         h->rung_on = false;
+        h->tune_queued = false;          // (the record itself is zeroed when the next table is set)
         return AMC_OK;
     }
     if (!h->model.classes.empty() || h->script_policy || h->scaled_policy || h->n_params > 1 || h->n_classes > 1)
@@ -155,7 +171,7 @@ int amc_set_rung_sigma(amc_handle* h, const double* sigma, int n)
     AMC_HIP(hipGetLastError());
     std::memcpy(h->rung_sigma, s.sigma, sizeof(h->rung_sigma));
     h->rung_on = true;
-    return AMC_OK;
+    return tune_reset(h, false);         // a table that was given has not been tuned; the window is left alone
 }
 
 int amc_get_rung_sigma(amc_handle* h, double* sigma, int n)
@@ -164,7 +180,16 @@ int amc_get_rung_sigma(amc_handle* h, double* sigma, int n)
     if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_get_rung_sigma: no widths per rung are set (amc_set_rung_sigma)");
     if (n != h->K * h->n_rungs)
         return fail(AMC_ERR_BAD_ARG, "amc_get_rung_sigma: n = %d, the table of %d moves x %d rungs has %d entries", n, h->K, h->n_rungs, h->K * h->n_rungs);
-    std::memcpy(sigma, h->rung_sigma, (size_t)n * sizeof(double));
+    if (!h->tune_queued) {               // the table as it was given
+        std::memcpy(sigma, h->rung_sigma, (size_t)n * sizeof(double));
+        return AMC_OK;
+    }
+    // tuned since: the table is the device's (the record holds every entry's width as the last tuning left it)
+    AMC_HIP(hipSetDevice(h->device));
+    unsigned long long host[AMC_MAX_MOVES];
+    AMC_HIP(hipMemcpyAsync(host, h->d_tune + amc::TUNE_SIGMA, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    std::memcpy(sigma, host, (size_t)n * sizeof(double));
     return AMC_OK;
 }
 
@@ -512,6 +537,178 @@ int amc_get_ladder(amc_handle* h, double* betas)
     else AMC_HIP(hipMemcpyAsync(host, h->d_beta, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));
     for (int r = 0; r < R; ++r) betas[r] = h->f32 ? (double)host32[r] : host[r];
+    return AMC_OK;
+}
+
+// ---- tuning the widths per rung (DESIGN.md section 3.13 "Tuning the widths") -----------------------------------------------------------
+static int zeroed_words(amc_handle* h, unsigned long long** p, size_t bytes)
+{
+    if (*p) return AMC_OK;
+    AMC_HIP(hipMalloc(p, bytes));
+    AMC_HIP(hipMemsetAsync(*p, 0, bytes, h->stream));
+    return AMC_OK;
+}
+
+// What every entry of the window needs: a ladder, per-chain counters, cells that fit the base.
+static int window_state(amc_handle* h, const char* who)
+{
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "%s: the handle has no ladder (amc_set_ladder)", who);
+    if (!h->counters) return fail(AMC_ERR_STATE, "%s: handle was created with per_chain_counters = 0", who);
+    if (h->K * h->n_rungs > AMC_MAX_MOVES)
+        return fail(AMC_ERR_STATE, "%s: %d moves x %d rungs = %d cells, the window holds %d", who, h->K, h->n_rungs, h->K * h->n_rungs, AMC_MAX_MOVES);
+    return AMC_OK;
+}
+
+static amc::TuneArgs tune_args(const amc_handle* h)
+{
+    amc::TuneArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.rung_tab = h->d_rung_tab;
+    a.cnt = h->d_rung_cnt;
+    a.base = h->d_rung_base;
+    a.rec = h->d_tune;
+    a.steps_per_rung = (h->t_base + h->t_counted) * (uint64_t)(h->M / h->n_rungs);
+    a.n_moves = h->K;
+    a.n_rungs = h->n_rungs;
+    return a;
+}
+
+int amc_tune_rung_sigma(amc_handle* h, double target, double gamma, int64_t min_calls, double sigma_lo, double sigma_hi, const int64_t* counts)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_tune_rung_sigma: the handle has no ladder (amc_set_ladder)");
+    if (!h->counters) return fail(AMC_ERR_STATE, "amc_tune_rung_sigma: handle was created with per_chain_counters = 0");
+    if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_tune_rung_sigma: no widths per rung are set (amc_set_rung_sigma)");
+    if (!(target > 0.0 && target < 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: target = %g must lie in (0, 1)", target);
+    if (!(gamma > 0.0 && gamma <= 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: gamma = %g must lie in (0, 1]", gamma);
+    if (min_calls < 1) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: min_calls = %lld must be at least 1", (long long)min_calls);
+    if (!(sigma_lo >= 1e-100 && sigma_lo <= 1e100)) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: sigma_lo = %g must lie in [1e-100, 1e100]", sigma_lo);
+    if (!(sigma_hi >= 1e-100 && sigma_hi <= 1e100)) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: sigma_hi = %g must lie in [1e-100, 1e100]", sigma_hi);
+    if (sigma_lo > sigma_hi) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: sigma_lo = %g is above sigma_hi = %g", sigma_lo, sigma_hi);
+    const int R = h->n_rungs, n = h->K * R;      // (n <= AMC_MAX_MOVES: amc_set_rung_sigma)
+    amc::TuneCounts given;
+    std::memset(&given, 0, sizeof given);
+    if (counts) {
+        for (int e = 0; e < n; ++e) {
+            if (counts[e] < 0 || counts[n + e] < 0)
+                return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: counts: entry %d (move %d, rung %d) is negative", e, e / R, e % R);
+            if (counts[e] > counts[n + e])
+                return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: counts: entry %d (move %d, rung %d) has more accepted calls than calls", e, e / R, e % R);
+            given.c[e] = (unsigned long long)counts[e];
+            given.c[n + e] = (unsigned long long)counts[n + e];
+        }
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    // (as in front of amc_set_rung_sigma: a learning step left pending belongs in front of this point of the stream)
+    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    { const int rc = zeroed_words(h, &h->d_rung_base, RUNG_BASE_BYTES); if (rc != AMC_OK) return rc; }
+    { const int rc = zeroed_words(h, &h->d_tune, TUNE_BYTES); if (rc != AMC_OK) return rc; }
+    { const int rc = rung_totals_queue(h); if (rc != AMC_OK) return rc; }
+    amc::TuneArgs a = tune_args(h);
+    a.min_calls = (unsigned long long)min_calls;
+    a.target = target;
+    a.gamma = gamma;
+    a.lo = sigma_lo;
+    a.hi = sigma_hi;
+    a.counts_given = counts ? 1 : 0;
+    hipLaunchKernelGGL(amc::rung_sigma_tune_kernel, dim3(1), dim3(AMC_MAX_MOVES), 0, h->stream, a, given);
+    AMC_HIP(hipGetLastError());
+    h->tune_queued = true;
+    return AMC_OK;
+}
+
+int amc_tune_status(amc_handle* h, int* st, int n, int64_t* n_tuned)
+{
+    if (!h || !st || !n_tuned) return fail(AMC_ERR_BAD_ARG, "amc_tune_status: NULL argument");
+    if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_tune_status: no widths per rung are set (amc_set_rung_sigma)");
+    if (n != h->K * h->n_rungs)
+        return fail(AMC_ERR_BAD_ARG, "amc_tune_status: n = %d, the table of %d moves x %d rungs has %d entries", n, h->K, h->n_rungs, h->K * h->n_rungs);
+    unsigned long long host[1 + AMC_MAX_MOVES] = {0ull};
+    AMC_HIP(hipSetDevice(h->device));
+    if (h->d_tune) AMC_HIP(hipMemcpyAsync(host, h->d_tune, (size_t)(1 + n) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    *n_tuned = (int64_t)host[amc::TUNE_COUNT];
+    for (int e = 0; e < n; ++e) st[e] = (int)host[amc::TUNE_ST + e];
+    return AMC_OK;
+}
+
+int amc_set_tuned(amc_handle* h, int64_t n_tuned)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_tuned: NULL handle");
+    if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_set_tuned: no widths per rung are set (amc_set_rung_sigma)");
+    if (n_tuned < 0) return fail(AMC_ERR_BAD_ARG, "amc_set_tuned: n_tuned < 0");
+    AMC_HIP(hipSetDevice(h->device));
+    { const int rc = zeroed_words(h, &h->d_tune, TUNE_BYTES); if (rc != AMC_OK) return rc; }
+    const unsigned long long host = (unsigned long long)n_tuned;
+    AMC_HIP(hipMemcpyAsync(h->d_tune + amc::TUNE_COUNT, &host, sizeof host, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
+    return AMC_OK;
+}
+
+int amc_rung_window_restart(amc_handle* h)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_rung_window_restart: NULL handle");
+    { const int rc = window_state(h, "amc_rung_window_restart"); if (rc != AMC_OK) return rc; }
+    AMC_HIP(hipSetDevice(h->device));
+    { const int rc = zeroed_words(h, &h->d_rung_base, RUNG_BASE_BYTES); if (rc != AMC_OK) return rc; }
+    { const int rc = rung_totals_queue(h); if (rc != AMC_OK) return rc; }
+    const amc::TuneArgs a = tune_args(h);
+    hipLaunchKernelGGL(amc::rung_window_restart_kernel, dim3(1), dim3(AMC_MAX_MOVES), 0, h->stream, a);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
+int amc_rung_window_base(amc_handle* h, int64_t* accepted, int64_t* total)
+{
+    if (!h || !accepted || !total) return fail(AMC_ERR_BAD_ARG, "amc_rung_window_base: NULL argument");
+    { const int rc = window_state(h, "amc_rung_window_base"); if (rc != AMC_OK) return rc; }
+    const int n = h->K * h->n_rungs;
+    unsigned long long host[amc::RUNG_BASE_WORDS] = {0ull};
+    AMC_HIP(hipSetDevice(h->device));
+    if (h->d_rung_base) AMC_HIP(hipMemcpyAsync(host, h->d_rung_base, RUNG_BASE_BYTES, hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    for (int e = 0; e < n; ++e) {
+        accepted[e] = (int64_t)host[e];
+        total[e] = (int64_t)host[AMC_MAX_MOVES + e];
+    }
+    return AMC_OK;
+}
+
+int amc_set_rung_window_base(amc_handle* h, const int64_t* accepted, const int64_t* total)
+{
+    if (!h || !accepted || !total) return fail(AMC_ERR_BAD_ARG, "amc_set_rung_window_base: NULL argument");
+    { const int rc = window_state(h, "amc_set_rung_window_base"); if (rc != AMC_OK) return rc; }
+    const int R = h->n_rungs, n = h->K * R;
+    unsigned long long host[amc::RUNG_BASE_WORDS] = {0ull};
+    for (int e = 0; e < n; ++e) {
+        if (accepted[e] < 0 || total[e] < 0)
+            return fail(AMC_ERR_BAD_ARG, "amc_set_rung_window_base: entry %d (move %d, rung %d) is negative", e, e / R, e % R);
+        host[e] = (unsigned long long)accepted[e];
+        host[AMC_MAX_MOVES + e] = (unsigned long long)total[e];
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    { const int rc = zeroed_words(h, &h->d_rung_base, RUNG_BASE_BYTES); if (rc != AMC_OK) return rc; }
+    AMC_HIP(hipMemcpyAsync(h->d_rung_base, host, RUNG_BASE_BYTES, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
+    return AMC_OK;
+}
+
+int amc_rung_window_counts(amc_handle* h, int64_t* accepted, int64_t* total)
+{
+    if (!h || !accepted || !total) return fail(AMC_ERR_BAD_ARG, "amc_rung_window_counts: NULL argument");
+    { const int rc = window_state(h, "amc_rung_window_counts"); if (rc != AMC_OK) return rc; }
+    const int n = h->K * h->n_rungs;
+    int64_t base_acc[AMC_MAX_MOVES], base_tot[AMC_MAX_MOVES];
+    { const int rc = amc_rung_window_base(h, base_acc, base_tot); if (rc != AMC_OK) return rc; }
+    { const int rc = amc_rung_counter_totals(h, accepted, total); if (rc != AMC_OK) return rc; }
+    for (int e = 0; e < n; ++e) {
+        if (accepted[e] < base_acc[e] || total[e] < base_tot[e]) {      // counters uploaded or restored behind the base
+            accepted[e] = total[e] = -1;
+        } else {
+            accepted[e] -= base_acc[e];
+            total[e] -= base_tot[e];
+        }
+    }
     return AMC_OK;
 }
 

@@ -7,7 +7,8 @@
 //   amc_sweeps.hip      sweep launches (amc_sweep*)
 //   amc_exchange.hip    replica exchange along a temperature ladder (amc_set_ladder, amc_exchange, amc_sweep_exchange, gap counters,
 //                       the per-rung reproducible sums: amc_reduce_rungs_exact, walker tracking: amc_set_tracking ..,
-//                       proposal widths per rung: amc_set_rung_sigma / amc_get_rung_sigma, respacing: amc_respace_ladder ..)
+//                       proposal widths per rung: amc_set_rung_sigma / amc_get_rung_sigma, respacing: amc_respace_ladder ..,
+//                       tuning the widths: amc_tune_rung_sigma .., the window of the acceptance per rung: amc_rung_window_*)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -181,6 +182,11 @@ struct amc_handle {
     double rung_sigma[AMC_MAX_MOVES] = {0}; // the table as it was given (amc_get_rung_sigma)
     unsigned long long* d_rung_cnt = nullptr;   // [2][cells] accepted, total per (move, rung) (amc_rung_counter_totals; allocated at its first use,
     size_t rung_cnt_cells = 0;                  //   grown when a call needs more)
+    // Tuning the widths (amc_tune_rung_sigma .. amc_rung_window_restart): both allocated at their first use, zeroed then; a handle that
+    // never tunes and never asks for the window has neither
+    unsigned long long* d_rung_base = nullptr;  // [RUNG_BASE_WORDS] accepted, total per (move, rung) at the start of the window (zeroed by amc_set_ladder)
+    unsigned long long* d_tune = nullptr;       // [TUNE_WORDS] the record of the tunings (zeroed by amc_set_rung_sigma and amc_set_ladder)
+    bool tune_queued = false;                   // a tuning has been queued since the table was set: the device holds the table (amc_get_rung_sigma)
     double* d_x = nullptr;
     double* d_beta = nullptr;
     uint32_t* d_acc = nullptr;
@@ -299,6 +305,7 @@ AMC_INTERNAL int log_room(amc_handle* h, int* rows);
 AMC_INTERNAL int fold_log(amc_handle* h, bool with_ratio = false, int* ratio_rows = nullptr, amc::xs_word* ratio_dst = nullptr);
 AMC_INTERNAL hipError_t alloc_counters(amc_handle* h, bool narrow);
 AMC_INTERNAL int counter_room(amc_handle* h, const char* who, uint64_t steps);
+AMC_INTERNAL int rung_totals_queue(amc_handle* h);      // the totals per (move, rung) into d_rung_cnt, nothing read back
 AMC_INTERNAL amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps, int grid);        // amc_sweeps.hip
 AMC_INTERNAL int reduce_sweep_grid(const amc_handle* h);
 AMC_INTERNAL int sweep_impl(amc_handle* h, int64_t n_sweeps, bool fuse_reduce, int* grid_out);

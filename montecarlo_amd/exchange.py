@@ -188,6 +188,63 @@ class RespaceLadder(AriannaAlgorithm):
         io.write(f"\t\tUntil: {self.until}\n")
 
 
+class TuneRungSigma(AriannaAlgorithm):
+    """TuneRungSigma(chains; dependencies=(Metropolis,), target=0.44, gamma=1.0, min_calls=1000, sigma_min=1e-100, sigma_max=1e100,
+    until=None): one tuning of the Metropolis' widths per rung per scheduled time (Metropolis.tune_rung_sigma), and none after time
+    step ``until``.  The window of the acceptance it reads starts when the run starts and restarts at every tuning, so each tuning
+    measures the table in force since the one before.
+
+    A BURN-IN tool: changing sigma in the middle of a run breaks detailed balance across the change, so the samples taken while the
+    widths still move are not samples of one chain.  Schedule it over the first part of the run, or give ``until``, and measure
+    afterwards.  Scheduled behind a RespaceLadder it also answers a ladder that has moved: the widths follow the new beta at the next
+    tuning.  An algorithm of its own, so the schedule decides when it runs; a time step at which it is due ends a fused stretch of
+    ``run(fuse=True)`` like any other algorithm that is due."""
+
+    mutates_chains = True          # (as RespaceLadder: a callback due behind it at the same t is served after the tuning, not from the launch in front)
+
+    def __init__(self, chains, dependencies=None, target=0.44, gamma=1.0, min_calls=1000, sigma_min=1e-100, sigma_max=1e100, until=None,
+                 path=None, **extras):
+        assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
+        self.metropolis: Metropolis = dependencies[0]
+        if self.metropolis.rung_sigma is None:
+            raise ValueError("TuneRungSigma: the Metropolis has no widths per rung to tune (Metropolis(..., rung_sigma=...))")
+        self.target, self.gamma = float(target), float(gamma)
+        self.sigma_min, self.sigma_max = float(sigma_min), float(sigma_max)
+        if not 0.0 < self.target < 1.0:
+            raise ValueError(f"TuneRungSigma: target = {target!r} must lie in (0, 1)")
+        if not 0.0 < self.gamma <= 1.0:
+            raise ValueError(f"TuneRungSigma: gamma = {gamma!r} must lie in (0, 1]")
+        if int(min_calls) != min_calls or int(min_calls) < 1:
+            raise ValueError(f"TuneRungSigma: min_calls = {min_calls!r} must be an integer >= 1")
+        if not (1e-100 <= self.sigma_min <= self.sigma_max <= 1e100):
+            raise ValueError(f"TuneRungSigma: sigma_min = {sigma_min!r}, sigma_max = {sigma_max!r} must satisfy "
+                             "1e-100 <= sigma_min <= sigma_max <= 1e100")
+        self.min_calls = int(min_calls)
+        self.until = None if until is None else int(until)
+        self.statuses = []         # (t, status array (K, R)) of every tuning asked for
+
+    def initialise(self, simulation: Simulation) -> None:
+        if getattr(self.metropolis, "restored", False) and getattr(self.metropolis, "_rung_window_used", False):
+            return                 # (storage.restore brought the window back: the resumed run tunes as the uninterrupted one)
+        self.metropolis.restart_rung_window()
+
+    def make_step(self, simulation: Simulation) -> None:
+        if self.until is not None and simulation.t > self.until:
+            return
+        status = self.metropolis.tune_rung_sigma(self.target, self.gamma, self.min_calls, self.sigma_min, self.sigma_max)
+        self.statuses.append((simulation.t, status))
+
+    def write_algorithm(self, io, scheduler) -> None:
+        io.write("\tTuneRungSigma\n")
+        io.write(f"\t\tCalls: {_calls(scheduler)}\n")
+        io.write(f"\t\tTarget: {self.target}\n")
+        io.write(f"\t\tGamma: {self.gamma}\n")
+        io.write(f"\t\tMin calls: {self.min_calls}\n")
+        io.write(f"\t\tSigma min: {self.sigma_min}\n")
+        io.write(f"\t\tSigma max: {self.sigma_max}\n")
+        io.write(f"\t\tUntil: {self.until}\n")
+
+
 def _find_exchange(simulation: Simulation) -> ReplicaExchange:
     found = [a for a in simulation.algorithms if isinstance(a, ReplicaExchange)]
     if len(found) != 1:
@@ -258,3 +315,18 @@ def rung_energy(simulation: Simulation) -> np.ndarray:
     sums = np.array([float(np.sum(energies(met.engine.download_strided(r, R, count)))) for r in range(R)])
     tot = sharding.allreduce_sum(np.concatenate([sums, [float(count)]]), met.engine)
     return tot[:R] / tot[R]
+
+
+def callback_rung_sigma(simulation: Simulation) -> np.ndarray:
+    """The widths per (move, rung) in force, shape (K, R) (``Metropolis.rung_sigma``, which follows every tuning): with StoreCallbacks,
+    the history of a table that TuneRungSigma moves."""
+    met = _find_exchange(simulation).metropolis
+    if met.rung_sigma is None:
+        raise ValueError("callback_rung_sigma: the Metropolis has no widths per rung (Metropolis(..., rung_sigma=...))")
+    return np.array(met.rung_sigma, dtype=np.float64)
+
+
+def callback_rung_window_acceptance(simulation: Simulation) -> np.ndarray:
+    """accepted / total calls of every move per rung over the current window, shape (K, R) (Metropolis.rung_window_acceptance): the
+    acceptance of the table in force, where callback_rung_acceptance mixes every table since the counters began."""
+    return _find_exchange(simulation).metropolis.rung_window_acceptance()

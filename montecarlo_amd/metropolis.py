@@ -84,7 +84,8 @@ class Metropolis(AriannaAlgorithm):
     ``Move`` totals, and the sweep is ~20 % faster without the per-chain step log.
     ``rung_sigma``: proposal widths per (move, rung) of a temperature ladder, an array [K][R] (K = 1: a list of R will do): the chains
     at rung r propose with ``rung_sigma[k][r]`` where the others use the move's shared sigma.  Turns per-chain counters on; handed to
-    the engine when the ladder is set (ReplicaExchange); ``rung_acceptance()`` reads the acceptance it is there to tune.
+    the engine when the ladder is set (ReplicaExchange); ``rung_acceptance()`` reads the acceptance since the counters began,
+    ``rung_window_acceptance()`` the acceptance of the table in force, and ``tune_rung_sigma()`` / TuneRungSigma choose sigma_r from it.
     ``streams``: > 1 splits this rank's shard into that many sub-shards on separate HIP streams of the same GPU, so that
     the launch boundary of one overlaps the body of another (~8 % faster back-to-back single-sweep launches with 2 at
     1e7 chains -- visible only where the step loop is not host-bound, which a Python loop with a callback at every
@@ -268,6 +269,77 @@ class Metropolis(AriannaAlgorithm):
         n = acc.size
         with np.errstate(invalid="ignore", divide="ignore"):
             return (both[:n] / both[n:]).reshape(acc.shape)
+
+    # ---- tuning the widths per rung (DESIGN.md section 3.13 "Tuning the widths") ---------------
+    def _need_rung_table(self, who: str) -> None:
+        if not getattr(self, "n_rungs", 0):
+            raise ValueError(f"Metropolis.{who}: the chains have no ladder (ReplicaExchange)")
+        if self.rung_sigma is None:
+            raise ValueError(f"Metropolis.{who}: no widths per rung are set (Metropolis(..., rung_sigma=...))")
+
+    def _global_window(self):
+        """(accepted, total, inconsistent) of the current window over ALL shards, each of shape (K, R): the shards' windows added as
+        rung_acceptance() adds its totals; a cell that is inconsistent on any shard is inconsistent, and counts as (0, 0)."""
+        acc, tot = self.engine.rung_window_counts()
+        bad = (acc < 0) | (tot < 0)
+        local = np.concatenate([np.where(bad, 0, acc).reshape(-1), np.where(bad, 0, tot).reshape(-1), bad.reshape(-1)]).astype(np.float64)
+        both = np.rint(sharding.allreduce_sum(local, self.engine)).astype(np.int64)
+        n = acc.size
+        bad = both[2 * n:].reshape(acc.shape) > 0
+        return np.where(bad, 0, both[:n].reshape(acc.shape)), np.where(bad, 0, both[n:2 * n].reshape(acc.shape)), bad
+
+    def tune_rung_sigma(self, target: float = 0.44, gamma: float = 1.0, min_calls: int = 1000, sigma_min: float = 1e-100,
+                        sigma_max: float = 1e100) -> np.ndarray:
+        """One tuning of the widths per rung on the device (amc_tune_rung_sigma): every entry sigma[k][r] takes the damped step
+        sigma <- sigma a / target with a the acceptance of move k at rung r over the current window, by at most a factor of two,
+        clamped to [sigma_min, sigma_max]; an entry with fewer than ``min_calls`` calls in the window keeps its width.  With one shard
+        the engine uses its own window; with several the windows are summed over the shards as rung_acceptance() sums its totals
+        and every shard is given the sums, so all compute the same table.  The window restarts.  ``rung_sigma`` follows the device,
+        so a checkpoint written afterwards carries the tuned table.  Returns the status per entry, shape (K, R): 0 tuned, 1 too few
+        calls, 2 inconsistent window (counters replaced behind it), 3 tuned and clamped.
+        Changing sigma during a run breaks detailed balance across the change: tune during burn-in (see TuneRungSigma)."""
+        self._need_rung_table("tune_rung_sigma")
+        target, gamma, lo, hi = float(target), float(gamma), float(sigma_min), float(sigma_max)
+        if not 0.0 < target < 1.0:
+            raise ValueError(f"Metropolis.tune_rung_sigma: target = {target!r} must lie in (0, 1)")
+        if not 0.0 < gamma <= 1.0:
+            raise ValueError(f"Metropolis.tune_rung_sigma: gamma = {gamma!r} must lie in (0, 1]")
+        if int(min_calls) != min_calls or int(min_calls) < 1:
+            raise ValueError(f"Metropolis.tune_rung_sigma: min_calls = {min_calls!r} must be an integer >= 1")
+        if not (1e-100 <= lo <= 1e100 and 1e-100 <= hi <= 1e100 and lo <= hi):
+            raise ValueError(f"Metropolis.tune_rung_sigma: sigma_min = {lo!r}, sigma_max = {hi!r} must satisfy "
+                             "1e-100 <= sigma_min <= sigma_max <= 1e100")
+        eng = self.engine
+        bad = None
+        if self.world_size > 1:
+            acc, tot, bad = self._global_window()
+            eng.tune_rung_sigma(target, gamma, int(min_calls), lo, hi, counts=(acc, tot))
+        else:
+            eng.tune_rung_sigma(target, gamma, int(min_calls), lo, hi)
+        self._rung_window_used = True
+        status = np.array(eng.tune_status()[0])
+        if bad is not None:
+            status[bad] = 2                      # (given as an empty window: the width kept its bits)
+        self.rung_sigma = np.array(eng.rung_sigma(), dtype=np.float64)
+        return status
+
+    def rung_window_acceptance(self) -> np.ndarray:
+        """accepted / total calls of every move per rung over the current window and ALL shards, shape (K, R): what the next
+        tune_rung_sigma() would read.  0/0 and inconsistent cells are NaN.  The host waits for the queued steps."""
+        if not getattr(self, "n_rungs", 0):
+            raise ValueError("Metropolis.rung_window_acceptance: the chains have no ladder (ReplicaExchange)")
+        acc, tot, bad = self._global_window()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out = acc.astype(np.float64) / tot.astype(np.float64)
+        out[bad] = np.nan
+        return out
+
+    def restart_rung_window(self) -> None:
+        """The window of rung_window_acceptance() / tune_rung_sigma() starts here (stream-ordered)."""
+        if not getattr(self, "n_rungs", 0):
+            raise ValueError("Metropolis.restart_rung_window: the chains have no ladder (ReplicaExchange)")
+        self.engine.rung_window_restart()
+        self._rung_window_used = True
 
     def sweep_exchange(self, n_rounds: int, sweeps_per_round: int) -> None:
         """n_rounds x [sweeps_per_round make_step!s; one exchange step] queued by one engine call."""

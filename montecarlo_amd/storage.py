@@ -158,7 +158,14 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
         acc_x, att_x = eng.exchange_counters()
         data.update(n_rungs=metropolis.n_rungs, exchange_step=eng.exchange_step, exchange_accepted=acc_x, exchange_attempted=att_x)
         if getattr(metropolis, "rung_sigma", None) is not None:     # widths per rung: the table is state (no field without one)
+            if hasattr(eng, "rung_sigma"):          # ... as the device holds it: a tuned table is the tuned one
+                metropolis.rung_sigma = np.array(eng.rung_sigma(), dtype=np.float64)
             data["rung_sigma"] = np.asarray(metropolis.rung_sigma, dtype=np.float64)
+        if getattr(metropolis, "_rung_window_used", False):         # a tuning or a window restart has happened: the window's base and the
+            base_acc, base_tot = eng.rung_window_base()             # count of tunings are state (no field otherwise)
+            data.update(rung_window_accepted=base_acc, rung_window_total=base_tot)
+            if getattr(metropolis, "rung_sigma", None) is not None:
+                data["n_tuned"] = eng.tune_status()[1]
         if getattr(metropolis, "tracking", False):  # walker tracking is on: the labels and the trip counters are state too
             walker, direction = eng.labels()
             data.update(walker=walker, direction=direction, trips=np.array(eng.tracking_counters(), dtype=np.int64))
@@ -214,6 +221,11 @@ def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
             eng.set_labels(d["walker"], d["direction"])
             eng.set_tracking_counters(int(d["trips"][0]), int(d["trips"][1]))
             metropolis.tracking = True
+        if "rung_window_accepted" in d:             # the window of the acceptance per rung, and the count of tunings
+            eng.set_rung_window_base(d["rung_window_accepted"], d["rung_window_total"])
+            if "n_tuned" in d and tab is not None:
+                eng.set_tuned(int(d["n_tuned"]))
+            metropolis._rung_window_used = True
         if "n_respaced" in d:                       # a respaced ladder: the host copy follows the checkpoint's beta, as the engine did
             eng.set_respaced(int(d["n_respaced"]))
             metropolis.chains.beta_array[start:stop] = d["beta"]
