@@ -39,6 +39,22 @@ BETAS = (0.5, 1.0, 2.0, 4.0, 8.0)
 SIGMA0 = 0.3
 
 
+class RestartBridge(ma.AriannaAlgorithm):
+    """The bridge sums start again at the scheduled time: what was accumulated while the chains still left the right well is dropped."""
+
+    def __init__(self, chains, dependencies=None, path=None, **extras):
+        self.exchange = dependencies[0]
+
+    def make_step(self, simulation) -> None:
+        self.exchange.restart_bridge()
+
+
+def log_z_by_quadrature():
+    """log Z_r, Z_r = integral of exp(-beta_r (x^2 - 1)^2) dx, by the trapezoid rule on a fine grid (the integrand is below 1e-300 at the ends)."""
+    x = np.linspace(-6.0, 6.0, 240001)
+    return np.array([np.log(np.sum(np.exp(-b * (x * x - 1.0) ** 2)) * (x[1] - x[0])) for b in BETAS])
+
+
 def one_run(args, path, exchange: bool):
     R, L = len(BETAS), args.ladders
     x0 = 0.8 + 0.4 * ((np.arange(R * L) * 0.6180339887498949) % 1.0)          # every chain in the right well
@@ -53,7 +69,10 @@ def one_run(args, path, exchange: bool):
     callbacks = [ma.callback_energy]
     if exchange:
         track = args.track or args.adapt == "flow"
-        algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), track=track))   # every time step
+        bridge = ma.ReplicaExchange.BRIDGE_DEFAULT | 4 | 8 if args.free_energy else False          # ... and the two W columns
+        algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), track=track, bridge=bridge))   # every time step
+        if args.free_energy:                           # measure over the second half of the run
+            algorithm_list.append(dict(algorithm=RestartBridge, dependencies=(ma.ReplicaExchange,), scheduler=[max(1, args.steps // 2)]))
         callbacks.append(ma.callback_exchange_acceptance)
         if args.adapt:
             half = args.steps // 2
@@ -92,6 +111,9 @@ def main(argv=None):
     ap.add_argument("--tune-sigma", type=float, default=None, metavar="TARGET",
                     help="tune the proposal width of every rung towards this acceptance during the first half of the run; print the table and the "
                          "acceptance per rung of the second half")
+    ap.add_argument("--free-energy", action="store_true",
+                    help="accumulate the bridge sums over the second half of the run; print log(Z_(r+1) / Z_r) by three estimators beside a "
+                         "quadrature, and the heat capacity per rung")
     args = ap.parse_args(argv)
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
@@ -110,6 +132,17 @@ def main(argv=None):
         print("proposal width per rung       : " + "  ".join(f"{v:7.4f}" for v in sim.algorithms[0].rung_sigma[0]))
         print("move acceptance per rung      : " + "  ".join(f"{v:7.4f}" for v in ma.callback_rung_acceptance(sim)[0]))
     print("coldest rung, 8 bins of [-2, 2): " + " ".join(str(int(v)) for v in hist[-1][:8]))
+    if args.free_energy:
+        rx = sim.algorithms[1]
+        exact = np.diff(log_z_by_quadrature())
+        expo = rx.log_z_ratios("exponential")
+        print(f"log Z ratio per gap, {rx.bridge_sums()[1]:4d} snapshots of {args.ladders} ladders")
+        print("  quadrature                  : " + "  ".join(f"{v:7.4f}" for v in exact))
+        print("  acceptance (Bennett, C = 0) : " + "  ".join(f"{v:7.4f}" for v in rx.log_z_ratios("acceptance")))
+        print("  exponential, forward        : " + "  ".join(f"{v:7.4f}" for v in expo[0]))
+        print("  exponential, backward       : " + "  ".join(f"{v:7.4f}" for v in expo[1]))
+        print("  thermodynamic integration   : " + "  ".join(f"{v:7.4f}" for v in rx.log_z_ratios("ti")) + "   (trapezoid: coarse on this ladder)")
+        print("heat capacity per rung        : " + "  ".join(f"{v:7.4f}" for v in rx.heat_capacity()))
     if args.adapt:
         rx = sim.algorithms[1]
         print(f"ladder after {rx.metropolis.engine.respace_status()[1]} respacings   : " + "  ".join(f"{b:7.4f}" for b in rx.betas()) + "   (second half: the lines above and below)")

@@ -378,6 +378,34 @@ int  amc_histogram_rungs(amc_handle *h, double lo, double hi, int n_bins, uint64
  * Runs on the handle's stream behind whatever is queued; leaves the step indices, the step log, every counter and the reductions in
  * flight alone.  AMC_ERR_STATE without a ladder; AMC_ERR_BAD_ARG for columns == 0 or bits outside AMC_REDUCE_ALL. */
 int  amc_reduce_rungs_exact(amc_handle *h, int columns, double *records);
+/* Bridge sums (DESIGN.md section 3.13 "Bridge sums"): what free-energy differences along the ladder, log(Z_(r+1) / Z_r), and the heat
+ * capacity per rung are formed from -- per rung the reproducible sums of the energy, its square and the neighbour-reweighting factors,
+ * accumulated on the device over many snapshots.  For chain i = l R + r, e = potential(x_i) in the state type T, beta the per-chain array:
+ *   E  double(e)                                       EE  fl(double(e) * double(e))
+ *   WF exp(double((-e) * (beta_(i+1) - beta_i)))       MF  min(1, WF)      for r + 1 < R      (products and differences in T)
+ *   WB exp(double((-e) * (beta_(i-1) - beta_i)))       MB  min(1, WB)      for r >= 1         (a NaN stays a NaN)
+ * A record is the kind-R sum of one slot's summands over the local ladders and over every accumulated snapshot, its level fixed by the
+ * largest summand of that rung and column; NaN / +-Inf flag the one record they belong to (MF and MB lie in [0, 1]: no Inf flag).
+ * Integer sums: the same bits on any grid, in any order of the snapshots, and -- merged with amc_xsum_merge / amc_allreduce_xsum -- on
+ * any split into shards of whole ladders.
+ * amc_bridge_accumulate queues one snapshot of the state behind whatever is on the stream and returns at once (a pending learning
+ * step is taken first, as before an exchange step).  The first call after a reset fixes `columns`, AMC_BRIDGE_* bits, until the next
+ * reset -- amc_bridge_fetch with reset != 0, amc_set_bridge, amc_set_ladder --; another mask is AMC_ERR_STATE.
+ * amc_bridge_fetch waits and returns records[(r * 6 + c) * AMC_XSUM_WORDS ...], r < R, c in the order E, EE, WF, WB, MF, MB, of the
+ * LOCAL shard and the number of snapshots in them; reset != 0 zeroes both.  All-zero records: WF and MF at rung R - 1, WB and MB at rung
+ * 0, every column outside the mask, and everything when nothing has been accumulated (n_snapshots = 0).
+ * amc_set_bridge restores an accumulator (checkpoints); NULL or n_snapshots = 0 clears it.  The mask is read off the records: a column
+ * is in it exactly when its records are not all zero (a slot that had a summand is never an all-zero record).
+ * amc_set_ladder clears the accumulator on every call that succeeds.  A respacing that is taken (status 0) zeroes the records and the
+ * count on the device, as it zeroes the gap counters -- sums taken at other beta belong to another ladder --; the mask stays fixed.
+ * amc_upload_state and amc_tune_rung_sigma leave it alone.  None of the three touches the step indices, the step log, any counter, the
+ * reductions in flight, the labels or the widths per rung and their window; a handle that never accumulates allocates nothing for it.
+ * AMC_ERR_STATE without a ladder; AMC_ERR_BAD_ARG for columns == 0 or bits outside AMC_BRIDGE_ALL, and for records amc_set_bridge
+ * cannot have been given by amc_bridge_fetch.  A refused call leaves the handle as it was. */
+enum { AMC_BRIDGE_E = 1, AMC_BRIDGE_EE = 2, AMC_BRIDGE_WF = 4, AMC_BRIDGE_WB = 8, AMC_BRIDGE_MF = 16, AMC_BRIDGE_MB = 32, AMC_BRIDGE_ALL = 63 };
+int  amc_bridge_accumulate(amc_handle *h, int columns);
+int  amc_bridge_fetch(amc_handle *h, double *records, uint64_t *n_snapshots, int reset);
+int  amc_set_bridge(amc_handle *h, const double *records_or_null, uint64_t n_snapshots);
 /* Walker tracking (DESIGN.md section 3.13 "Walker tracking"): which replica sits at which rung, round trips and flow.  One label byte
  * per local chain, lab = w | (d << 6): w in [0, R) the walker id -- the rung the replica sat at when tracking was turned on --, d the end
  * it last visited: 0 none yet, 1 "up" (last at rung 0), 2 "down" (last at rung R - 1); d = 3 never occurs.

@@ -21,6 +21,8 @@ AMC_RED_HEADER = 4
 AMC_GD_STRIDE = 5
 AMC_XSUM_WORDS = 12      # doubles per record of a reproducible sum (include/amc.h)
 AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_REDUCE_ALL = 1, 2, 4, 7      # the sums over x a reduction forms (include/amc.h)
+# the columns of the bridge sums (include/amc.h); record order E, EE, WF, WB, MF, MB
+AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_WF, AMC_BRIDGE_WB, AMC_BRIDGE_MF, AMC_BRIDGE_MB, AMC_BRIDGE_ALL = 1, 2, 4, 8, 16, 32, 63
 AMC_RESPACE_ACCEPTANCE, AMC_RESPACE_FLOW = 1, 2      # the rules of amc_respace_ladder (include/amc.h)
 RESPACE_RULES = {"acceptance": AMC_RESPACE_ACCEPTANCE, "flow": AMC_RESPACE_FLOW}
 
@@ -166,6 +168,9 @@ def load() -> C.CDLL:
         "amc_set_exchange_step": (C.c_int, [H, C.c_uint64]),
         "amc_histogram_rungs": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64)]),
         "amc_reduce_rungs_exact": (C.c_int, [H, C.c_int, dp]),
+        "amc_bridge_accumulate": (C.c_int, [H, C.c_int]),
+        "amc_bridge_fetch": (C.c_int, [H, dp, C.POINTER(C.c_uint64), C.c_int]),
+        "amc_set_bridge": (C.c_int, [H, dp, C.c_uint64]),
         "amc_set_tracking": (C.c_int, [H, C.c_int]),
         "amc_download_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
         "amc_upload_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
@@ -704,6 +709,37 @@ class HipEngine:
         out = np.zeros((n, 3, AMC_XSUM_WORDS), dtype=np.float64)
         _check(self._lib.amc_reduce_rungs_exact(self._h, int(columns), _dptr(out)))
         return out
+
+    # -- bridge sums (include/amc.h; DESIGN.md section 3.13 "Bridge sums") ----------------
+    def bridge_accumulate(self, columns: int = AMC_BRIDGE_ALL) -> None:
+        """Queue one snapshot of the bridge sums -- per rung the reproducible sums of e, e^2 and the neighbour-reweighting factors
+        WF, WB, MF = min(1, WF), MB = min(1, WB) -- into the device-resident accumulator (amc_bridge_accumulate).  Stream-ordered,
+        nothing synchronises.  ``columns``: AMC_BRIDGE_* bits, fixed by the first call after a reset."""
+        _check(self._lib.amc_bridge_accumulate(self._h, int(columns)))
+
+    def bridge_fetch(self, reset: bool = False):
+        """(records[R][6][AMC_XSUM_WORDS], n_snapshots) of this shard's accumulator, columns in the order E, EE, WF, WB, MF, MB
+        (amc_bridge_fetch); ``reset`` zeroes both and frees the mask.  What shards exchange (sharding.allreduce_xsum); ``xsum_round``
+        yields the Float64s.  Synchronises."""
+        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        out = np.zeros((n, 6, AMC_XSUM_WORDS), dtype=np.float64)
+        count = C.c_uint64(0)
+        _check(self._lib.amc_bridge_fetch(self._h, _dptr(out), C.byref(count), int(bool(reset))))
+        return out, int(count.value)
+
+    def set_bridge(self, records=None, n_snapshots: int = 0) -> None:
+        """Restore the accumulator from ``bridge_fetch``'s records and count (amc_set_bridge); ``None`` clears it.  The mask is read off
+        the records: a column is in it exactly when its records are not all zero."""
+        if records is None:
+            _check(self._lib.amc_set_bridge(self._h, None, 0))
+            return
+        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        rec = np.ascontiguousarray(records, dtype=np.float64)
+        if rec.size != n * 6 * AMC_XSUM_WORDS:
+            raise AmcError(f"set_bridge: {rec.size} doubles, the records of {n} rungs take {n * 6 * AMC_XSUM_WORDS}")
+        if int(n_snapshots) < 0:
+            raise AmcError("set_bridge: n_snapshots < 0")
+        _check(self._lib.amc_set_bridge(self._h, _dptr(rec), int(n_snapshots)))
 
     # -- walker tracking (include/amc.h; DESIGN.md section 3.13 "Walker tracking") ----------------
     def set_tracking(self, on: bool = True) -> None:

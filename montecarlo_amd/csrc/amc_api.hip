@@ -556,6 +556,7 @@ int amc_destroy(amc_handle* h)
     (void)hipFree(h->d_xcnt);
     (void)hipFree(h->d_rung_rows);
     (void)hipFree(h->d_rung_recs);
+    (void)hipFree(h->d_bridge);
     (void)hipFree(h->d_lab);
     (void)hipFree(h->d_track);
     (void)hipFree(h->d_respace);

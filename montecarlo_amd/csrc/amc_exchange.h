@@ -4,7 +4,8 @@
 // with TRACK on -- it also moves one label byte per chain and counts trips between the ends --, rung_flow_kernel, the labels counted by
 // rung and direction, and respacing: ladder_respace_kernel, new beta values for the interior rungs from the gap or the flow counts
 // (the rule itself is amc_respace.h), and ladder_retile_kernel, which lays them over the chains; and tuning the widths per rung:
-// rung_sigma_tune_kernel (the rule itself is amc_tune.h) and rung_window_restart_kernel.
+// rung_sigma_tune_kernel (the rule itself is amc_tune.h) and rung_window_restart_kernel; and the bridge sums: bridge_sums_kernel /
+// bridge_finish_kernel, the reproducible sums of e, e^2 and the neighbour-reweighting factors by rung, accumulated over snapshots.
 // The reference has no such algorithm of its own: a user writes it as an AriannaAlgorithm whose make_step! walks simulation.chains
 // (the plugin protocol, src/algorithms.jl:6-37); with the chains in HBM the engine provides the cross-chain move.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
@@ -192,13 +193,15 @@ struct RespaceArgs {
     unsigned long long* gaps;           // d_xcnt again: zeroed with status 0
     unsigned long long* trips;          // [2] the trip counters, zeroed with status 0; nullptr without tracking
     unsigned long long* rec;            // [RESPACE_WORDS] the record above
+    unsigned long long* bridge;         // [bridge_words] the accumulator of the bridge sums, zeroed with status 0; nullptr without one
     double gamma, eps;
     int32_t rule, n_rungs, f32, counts_given;
+    int32_t bridge_words;               // words of `bridge` (BRIDGE_WORDS, amc_exchange.h "bridge sums")
 };
 
 // One block of 64 threads.  Lane r brings b[r] and its counts -- from device memory, or from the kernel argument when the call
 // brought global counts -- into LDS; lane 0 runs the rule (serial, a few hundred Float64 operations at most: microseconds); then the
-// lanes store the record and, with status 0, zero the gap and the trip counters.
+// lanes store the record and, with status 0, zero the gap and the trip counters and the accumulator of the bridge sums.
 AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void ladder_respace_kernel(const RespaceArgs a, const RespaceCounts given)
 {
     __shared__ double s_b[AMC_MAX_RUNGS], s_out[AMC_MAX_RUNGS], s_w[AMC_MAX_RUNGS], s_G[AMC_MAX_RUNGS];
@@ -231,6 +234,8 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void ladder_respace_kernel(c
         a.gaps[r] = 0ull;
         a.gaps[AMC_MAX_RUNGS + r] = 0ull;
         if (a.trips && r < 2) a.trips[r] = 0ull;
+        if (a.bridge)                   // sums taken at other beta belong to another ladder
+            for (int i = r; i < a.bridge_words; i += 64) a.bridge[i] = 0ull;
     }
 }
 
@@ -477,6 +482,179 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void rung_finish_kernel(cons
     if (threadIdx.x == 0) {
         for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
         xs::rec_from_r(rec, p);
+    }
+}
+#endif
+
+// ---- bridge sums (amc_bridge_accumulate; DESIGN.md section 3.13 "Bridge sums") ---------------------------------------------------------
+// S[r][c], c = E, EE, WF, WB, MF, MB: the kind-R sum over the ladders l -- and, through the accumulator, over the snapshots -- of one
+// chain's summand, chain i = l R + r, with e = potential_T(x_i) and beta the per-chain array, all products in T without contraction:
+//   E  double(e)          EE  fl(double(e) double(e))
+//   WF exp(double((-e) (beta_(i+1) - beta_i)))   MF min(1, WF), a NaN stays a NaN      (r + 1 < R)
+//   WB exp(double((-e) (beta_(i-1) - beta_i)))   MB min(1, WB)                         (r >= 1)
+// The slots without a summand -- WF, MF at rung R - 1, WB, MB at rung 0, every column nobody asked for -- are deposited into by nobody.
+enum { BR_E = 1, BR_EE = 2, BR_WF = 4, BR_WB = 8, BR_MF = 16, BR_MB = 32, BR_ALL = 63, BR_COLS = 6 };
+// The accumulator d_bridge: one row of XS_ROW_R words per slot s = r BR_COLS + c, AMC_MAX_RUNGS rungs of them, then the number of
+// snapshots.  Word 5 of a row is 1 once a snapshot has been merged into it: memory that was zeroed holds empty rows.
+enum { BRIDGE_COUNT = AMC_MAX_RUNGS * BR_COLS * XS_ROW_R, BRIDGE_WORDS = BRIDGE_COUNT + 1 };
+
+struct BridgeArgs {
+    const real_t* x;              // [n_ladders * n_rungs] positions of the local shard
+    const real_t* beta;           // the per-chain beta array
+    xs_word* rows;                // [gridDim.x][n_rungs][BR_COLS][XS_ROW_R]: this launch's block rows
+    int64_t l_begin, l_end;       // the ladders of this launch: at most XS_LANE_CAP - 2 trips per lane (the host splits beyond)
+    int32_t n_rungs;              // R
+    int32_t cols;                 // BR_* bits
+};
+
+// the columns that have a summand at rung r
+__host__ __device__ inline int bridge_cols_at(int cols, int r, int n_rungs)
+{
+    return cols & ~(r + 1 == n_rungs ? (BR_WF | BR_MF) : 0) & ~(r == 0 ? (BR_WB | BR_MB) : 0);
+}
+__host__ __device__ inline xs::PartR bridge_load_row(const xs_word* row) { return row[5] ? xs_load_r_row(row) : xs::part_r_empty(); }
+
+__device__ __forceinline__ double min_one(double w) { return (w != w) ? w : (w < 1.0 ? w : 1.0); }      // Julia's min(1, w)
+
+// One chain.  bn, bp: beta of the chains i + 1 and i - 1 (read only where mine names the direction).  exp once per direction, M from W.
+template <int POT>
+__device__ __forceinline__ void bridge_add(RLaneCols<BR_COLS>& L, real_t x, real_t b, real_t bn, real_t bp, const double* s_math, int mine)
+{
+    const real_t e = potential<POT>(x, s_math);
+    const real_t ne = -e;
+    const double ed = (double)e;
+    if (mine & BR_E) rl_deposit(L, 0, ed);
+    if (mine & BR_EE) rl_deposit(L, 1, ed * ed);
+    if (mine & (BR_WF | BR_MF)) {
+        const real_t d = bn - b;
+        const real_t a = ne * d;
+        const double w = exp_f64((double)a, s_math);
+        if (mine & BR_WF) rl_deposit(L, 2, w);
+        if (mine & BR_MF) rl_deposit(L, 4, min_one(w));
+    }
+    if (mine & (BR_WB | BR_MB)) {
+        const real_t d = bp - b;
+        const real_t a = ne * d;
+        const double w = exp_f64((double)a, s_math);
+        if (mine & BR_WB) rl_deposit(L, 3, w);
+        if (mine & BR_MB) rl_deposit(L, 5, min_one(w));
+    }
+    L.n += 1;
+}
+template <int POT>
+__device__ __forceinline__ void bridge_load(const BridgeArgs& a, int64_t i, bool fwd, bool bwd, real_t& x, real_t& b, real_t& bn, real_t& bp)
+{
+    x = a.x[i];
+    b = a.beta[i];
+    bn = fwd ? a.beta[i + 1] : (real_t)0;         // (fwd: r + 1 < R, so i + 1 is a chain of the same ladder; bwd likewise i - 1)
+    bp = bwd ? a.beta[i - 1] : (real_t)0;
+}
+
+// One memory-bound pass in rung_sums_kernel's form: thread id = l0 R + r, a thread keeps its rung -- and with it the set `mine` of
+// columns it deposits into -- for the whole launch, four loads of x in flight per lane; the neighbours' beta are the loads of the
+// neighbouring lanes' own beta.  RLaneCols::n counts the summands of the columns in `mine` and of no other: the top, flag and
+// multiple phases at the block's end walk `mine`, so a slot an end rung has no summand for is never fed an empty sum with n > 0.
+// Then as rung_sums_kernel: integer max / or per slot, 64-bit integer LDS adds, rows in the XS_ROW_R form.  No floating-point atomic.
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void bridge_sums_kernel(const BridgeArgs a)
+{
+    constexpr int MAX_SLOTS = AMC_MAX_RUNGS * BR_COLS;
+    __shared__ double s_math[TAB_DOUBLES];                               // exp for every potential
+    __shared__ int s_top[MAX_SLOTS];
+    __shared__ unsigned int s_flags[MAX_SLOTS];
+    __shared__ unsigned long long s_k[MAX_SLOTS][4];                    // k1.lo, k1.hi, k2.lo, k2.hi (hi: two's complement)
+    const int n_slots = a.n_rungs * BR_COLS;
+    for (int s = threadIdx.x; s < n_slots; s += AMC_BLOCK) {
+        s_top[s] = xs::XS_LMIN;
+        s_flags[s] = 0u;
+        s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
+    }
+    stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);                  // (ends in a barrier: the slots are cleared too)
+
+    const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
+    const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / a.n_rungs;
+    const int64_t l0 = tid / a.n_rungs;
+    const int r = (int)(tid - l0 * a.n_rungs);
+    int mine = bridge_cols_at(a.cols, r, a.n_rungs);
+    RLaneCols<BR_COLS> L;
+    rl_init(L);
+    if (l0 < ladders_per_trip) {
+        const bool fwd = (mine & (BR_WF | BR_MF)) != 0, bwd = (mine & (BR_WB | BR_MB)) != 0;
+        const int64_t step = ladders_per_trip * a.n_rungs;        // chains per trip
+        const int64_t end = a.l_end * a.n_rungs;                  // chain l R + r lies below it exactly when l < l_end
+        int64_t i = (a.l_begin + l0) * a.n_rungs + r;
+        real_t x0, x1, x2, x3, b0, b1, b2, b3, n0, n1, n2, n3, p0, p1, p2, p3;
+        for (; i + 3 * step < end; i += 4 * step) {
+            bridge_load<POT>(a, i, fwd, bwd, x0, b0, n0, p0);
+            bridge_load<POT>(a, i + step, fwd, bwd, x1, b1, n1, p1);
+            bridge_load<POT>(a, i + 2 * step, fwd, bwd, x2, b2, n2, p2);
+            bridge_load<POT>(a, i + 3 * step, fwd, bwd, x3, b3, n3, p3);
+            bridge_add<POT>(L, x0, b0, n0, p0, s_math, mine);
+            bridge_add<POT>(L, x1, b1, n1, p1, s_math, mine);
+            bridge_add<POT>(L, x2, b2, n2, p2, s_math, mine);
+            bridge_add<POT>(L, x3, b3, n3, p3, s_math, mine);
+        }
+        for (; i < end; i += step) {
+            bridge_load<POT>(a, i, fwd, bwd, x0, b0, n0, p0);
+            bridge_add<POT>(L, x0, b0, n0, p0, s_math, mine);
+        }
+    }
+    if (L.n == 0) mine = 0;
+#pragma unroll
+    for (int c = 0; c < BR_COLS; ++c)
+        if ((mine >> c) & 1) {
+            atomicMax(&s_top[r * BR_COLS + c], L.top[c]);
+            if (L.flags[c]) atomicOr(&s_flags[r * BR_COLS + c], L.flags[c]);
+        }
+    __syncthreads();                                              // the levels are settled
+#pragma unroll
+    for (int c = 0; c < BR_COLS; ++c)
+        if ((mine >> c) & 1) {
+            const int s = r * BR_COLS + c;
+            xs::RPair k = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n, L.top[c]);
+            const int d = s_top[s] - L.top[c];
+            if (d == 0) {
+                rung_lds_add(&s_k[s][0], k.k1);
+                rung_lds_add(&s_k[s][2], k.k2);
+            } else if (d == 1) {
+                rung_lds_add(&s_k[s][2], k.k1);
+            }
+        }
+    __syncthreads();
+    xs_word* out = a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R;
+    for (int w = threadIdx.x; w < n_slots * XS_ROW_R; w += AMC_BLOCK) {
+        const int s = w / XS_ROW_R, j = w - s * XS_ROW_R;
+        xs_word v = 0ull;
+        if (j == 0) v = (xs_word)(uint32_t)s_top[s] | ((xs_word)s_flags[s] << 32);
+        else if (j < 5) {
+            const int which = (j - 1) >> 1;                       // k1 / k2
+            const xs::i128 k = xs::i128_add(xs::i128_shl(xs::i128_of((long long)s_k[s][2 * which + 1]), 32), xs::i128{(uint64_t)s_k[s][2 * which], 0});
+            v = ((j - 1) & 1) ? (xs_word)k.hi : (xs_word)k.lo;
+        }
+        out[w] = v;                                               // (a slot nobody deposited into is an empty row: top XS_LMIN, zeros)
+    }
+}
+
+// The launches' block rows merged into the accumulator: block s = r BR_COLS + c of 64 threads, lane i merges the rows i, i + 64, ...
+// (part_r_merge: integers, so the order is immaterial), thread 0 the lanes' partials and the accumulator's own row, which it replaces.
+// A slot without a summand keeps its empty row.  Block 0 counts the snapshot.
+#if AMC_PLAIN_KERNELS
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void bridge_finish_kernel(const xs_word* rows, int n_rows, int n_rungs, int cols, xs_word* acc)
+{
+    __shared__ xs::PartR s_part[64];
+    const int s = blockIdx.x, n_slots = n_rungs * BR_COLS;
+    if (s == 0 && threadIdx.x == 0) acc[BRIDGE_COUNT] += 1ull;
+    if (!((bridge_cols_at(cols, s / BR_COLS, n_rungs) >> (s % BR_COLS)) & 1)) return;
+    xs::PartR p = xs::part_r_empty();
+    for (int b = threadIdx.x; b < n_rows; b += 64) xs::part_r_merge(p, xs_load_r_row(rows + ((int64_t)b * n_slots + s) * XS_ROW_R));
+    s_part[threadIdx.x] = p;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        xs_word* row = acc + (int64_t)s * XS_ROW_R;
+        for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
+        xs::part_r_merge(p, bridge_load_row(row));
+        xs_store_r_row(row, p);
+        row[5] = 1ull;
     }
 }
 #endif

@@ -1,10 +1,10 @@
 // amc_exchange.hip -- replica exchange along a temperature ladder: the ladder of a handle, exchange steps
 // (amc_exchange, amc_sweep_exchange), the per-gap counters and the exchange step index, the per-rung reproducible sums
-// (amc_reduce_rungs_exact), walker tracking (amc_set_tracking .. amc_set_tracking_counters), proposal widths per rung
+// (amc_reduce_rungs_exact), the bridge sums (amc_bridge_accumulate .. amc_set_bridge), walker tracking (amc_set_tracking .. amc_set_tracking_counters), proposal widths per rung
 // (amc_set_rung_sigma, amc_get_rung_sigma), respacing the ladder (amc_respace_ladder .. amc_get_ladder), tuning the widths per rung
 // (amc_tune_rung_sigma .. amc_set_tuned) and the window of the acceptance per rung (amc_rung_window_*).  amc_histogram_rungs is with the other
 // histograms in amc_state.hip.
-#define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copies of the plain kernels it launches (rung_finish_kernel, rung_flow_kernel)
+#define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copies of the plain kernels it launches (rung_finish_kernel, bridge_finish_kernel, rung_flow_kernel)
 #include "amc_internal.h"
 
 // AMC_MAX_RUNGS has two definitions, include/amc.h's (the ABI) and amc_exchange.h's (the kernel sources, which the run-time compiler
@@ -52,6 +52,29 @@ static int tracking_off(amc_handle* h)
     (void)hipFree(h->d_track);
     h->d_lab = nullptr;
     h->d_track = nullptr;
+    return AMC_OK;
+}
+
+// d_rung_rows holds at least `need` words: the block rows of the rung sums and of the bridge sums (each call's finishing kernel has
+// read them, in stream order, before the next call's launches write them).
+static int rung_rows_room(amc_handle* h, size_t need)
+{
+    if (need <= h->rung_rows_words) return AMC_OK;
+    AMC_HIP(hipStreamSynchronize(h->stream));                   // (a finishing kernel queued by a bridge snapshot may still read the old rows)
+    (void)hipFree(h->d_rung_rows);
+    h->d_rung_rows = nullptr;
+    h->rung_rows_words = 0;
+    AMC_HIP(hipMalloc(&h->d_rung_rows, need * sizeof(amc::xs_word)));
+    h->rung_rows_words = need;
+    return AMC_OK;
+}
+
+// The accumulator of the bridge sums back to "nothing accumulated", the mask free again.  Memory a handle never allocated stays unallocated.
+static const size_t BRIDGE_BYTES = amc::BRIDGE_WORDS * sizeof(amc::xs_word);      // d_bridge (amc_exchange.h BRIDGE_*)
+static int bridge_clear(amc_handle* h)
+{
+    if (h->d_bridge) AMC_HIP(hipMemsetAsync(h->d_bridge, 0, BRIDGE_BYTES, h->stream));
+    h->bridge_cols = 0;
     return AMC_OK;
 }
 
@@ -104,6 +127,7 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
         { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }
         if (h->d_respace) AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));
         { const int rc = tune_reset(h, true); if (rc != AMC_OK) return rc; }
+        { const int rc = bridge_clear(h); if (rc != AMC_OK) return rc; }
         h->rung_on = false;
         h->n_rungs = 0;
         return AMC_OK;
@@ -126,6 +150,7 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
     AMC_HIP(hipMemsetAsync(h->d_xcnt, 0, XCNT_BYTES, h->stream));      // the gaps of another ladder are other gaps
     if (h->d_respace) AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));      // ... and nobody has respaced it
     { const int rc = tune_reset(h, true); if (rc != AMC_OK) return rc; }                        // ... nor tuned its widths; another R has other cells
+    { const int rc = bridge_clear(h); if (rc != AMC_OK) return rc; }                            // ... and its bridge sums are other sums
     h->rung_on = false;                                                // ... and its rungs other rungs: no widths per rung until they are set again
     h->n_rungs = n_rungs;
     return AMC_OK;
@@ -273,14 +298,7 @@ int amc_reduce_rungs_exact(amc_handle* h, int columns, double* records)
     const int64_t n_launches = (n_ladders + per_launch - 1) / per_launch;
     const size_t slot_words = (size_t)R * amc::RED_COLS * amc::XS_ROW_R;
     const size_t need = (size_t)n_launches * (size_t)grid * slot_words;
-    if (need > h->rung_rows_words) {
-        AMC_HIP(hipStreamSynchronize(h->stream));               // (nothing queued reads the old rows after this call's predecessor returned)
-        (void)hipFree(h->d_rung_rows);
-        h->d_rung_rows = nullptr;
-        h->rung_rows_words = 0;
-        AMC_HIP(hipMalloc(&h->d_rung_rows, need * sizeof(amc::xs_word)));
-        h->rung_rows_words = need;
-    }
+    { const int rc = rung_rows_room(h, need); if (rc != AMC_OK) return rc; }
     if (!h->d_rung_recs) AMC_HIP(hipMalloc(&h->d_rung_recs, (size_t)AMC_MAX_RUNGS * amc::RED_COLS * amc::xs::XS_WORDS * sizeof(double)));
     for (int64_t i = 0; i < n_launches; ++i) {
         amc::RungSumsArgs a;
@@ -301,6 +319,119 @@ int amc_reduce_rungs_exact(amc_handle* h, int columns, double* records)
     AMC_HIP(hipGetLastError());
     AMC_HIP(hipMemcpyAsync(records, h->d_rung_recs, (size_t)n_slots * amc::xs::XS_WORDS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));
+    return AMC_OK;
+}
+
+// ---- bridge sums (DESIGN.md section 3.13 "Bridge sums") --------------------------------------------------------------------------------
+static_assert(AMC_BRIDGE_E == amc::BR_E && AMC_BRIDGE_EE == amc::BR_EE && AMC_BRIDGE_WF == amc::BR_WF && AMC_BRIDGE_WB == amc::BR_WB &&
+              AMC_BRIDGE_MF == amc::BR_MF && AMC_BRIDGE_MB == amc::BR_MB && AMC_BRIDGE_ALL == amc::BR_ALL, "the columns of include/amc.h and amc_exchange.h");
+
+int amc_bridge_accumulate(amc_handle* h, int columns)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_bridge_accumulate: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_bridge_accumulate: the handle has no ladder (amc_set_ladder)");
+    if (columns <= 0 || (columns & ~AMC_BRIDGE_ALL))
+        return fail(AMC_ERR_BAD_ARG, "amc_bridge_accumulate: columns = %d must be a non-empty combination of the AMC_BRIDGE_* bits", columns);
+    if (h->bridge_cols && h->bridge_cols != columns)
+        return fail(AMC_ERR_STATE, "amc_bridge_accumulate: columns = %d, the accumulator was begun with %d (amc_bridge_fetch with reset frees the mask)", columns,
+                    h->bridge_cols);
+    AMC_HIP(hipSetDevice(h->device));
+    // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
+    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    const int R = h->n_rungs;
+    const int64_t n_ladders = h->M / R;
+    const int grid = grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU);
+    // the lane cap, as amc_reduce_rungs_exact handles it: several launches beyond XS_LANE_CAP - 2 trips of the grid
+    const int64_t per_launch = (((int64_t)grid * AMC_BLOCK) / R) * (amc::xs::XS_LANE_CAP - 2);
+    const int64_t n_launches = (n_ladders + per_launch - 1) / per_launch;
+    const size_t slot_words = (size_t)R * amc::BR_COLS * amc::XS_ROW_R;
+    { const int rc = rung_rows_room(h, (size_t)n_launches * (size_t)grid * slot_words); if (rc != AMC_OK) return rc; }
+    if (!h->d_bridge) {
+        AMC_HIP(hipMalloc(&h->d_bridge, BRIDGE_BYTES));
+        AMC_HIP(hipMemsetAsync(h->d_bridge, 0, BRIDGE_BYTES, h->stream));
+    }
+    for (int64_t i = 0; i < n_launches; ++i) {
+        amc::BridgeArgs a;
+        a.x = h->d_x;
+        a.beta = h->d_beta;
+        a.rows = h->d_rung_rows + (size_t)i * (size_t)grid * slot_words;
+        a.l_begin = i * per_launch;
+        a.l_end = std::min(n_ladders, (i + 1) * per_launch);
+        a.n_rungs = R;
+        a.cols = columns;
+        void* params[] = {&a};
+        const int rc = launch_by_potential(h, "amc::bridge_sums_kernel", (const void*)amc::bridge_sums_kernel<amc::POT_DOUBLE_WELL>,
+                                           (const void*)amc::bridge_sums_kernel<amc::POT_HARMONIC>, grid, params);
+        if (rc != AMC_OK) return rc;
+    }
+    hipLaunchKernelGGL(amc::bridge_finish_kernel, dim3(R * amc::BR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->d_rung_rows,
+                       (int)(n_launches * grid), R, columns, h->d_bridge);
+    AMC_HIP(hipGetLastError());
+    h->bridge_cols = columns;
+    return AMC_OK;
+}
+
+int amc_bridge_fetch(amc_handle* h, double* records, uint64_t* n_snapshots, int reset)
+{
+    if (!h || !records || !n_snapshots) return fail(AMC_ERR_BAD_ARG, "amc_bridge_fetch: NULL argument");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_bridge_fetch: the handle has no ladder (amc_set_ladder)");
+    AMC_HIP(hipSetDevice(h->device));
+    const int R = h->n_rungs, n_slots = R * amc::BR_COLS;
+    std::vector<amc::xs_word> host(amc::BRIDGE_WORDS, 0ull);
+    if (h->d_bridge) AMC_HIP(hipMemcpyAsync(host.data(), h->d_bridge, BRIDGE_BYTES, hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    *n_snapshots = (uint64_t)host[amc::BRIDGE_COUNT];
+    for (int s = 0; s < n_slots; ++s) {
+        double* rec = records + (size_t)s * amc::xs::XS_WORDS;
+        const amc::xs_word* row = host.data() + (size_t)s * amc::XS_ROW_R;
+        if (row[5]) amc::xs::rec_from_r(rec, amc::xs_load_r_row(row));
+        else amc::xs::rec_clear(rec);                  // no summand: an end rung's missing slot, a column outside the mask, nothing accumulated
+    }
+    if (reset) return bridge_clear(h);
+    return AMC_OK;
+}
+
+int amc_set_bridge(amc_handle* h, const double* records, uint64_t n_snapshots)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: NULL handle");
+    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_bridge: the handle has no ladder (amc_set_ladder)");
+    AMC_HIP(hipSetDevice(h->device));
+    if (!records || n_snapshots == 0) return bridge_clear(h);
+    // The mask is read off the records: a slot that had a summand is a kind-R record, every other is all zero, and a column is in the
+    // mask exactly when its interior slots are records (E and EE have a summand at every rung, the W and M columns at all but one end).
+    const int R = h->n_rungs, n_slots = R * amc::BR_COLS;
+    std::vector<amc::xs_word> host(amc::BRIDGE_WORDS, 0ull);
+    int cols = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        const double* rec = records + (size_t)s * amc::xs::XS_WORDS;
+        const int r = s / amc::BR_COLS, c = s % amc::BR_COLS;
+        bool zero = true;
+        for (int i = 0; i < amc::xs::XS_WORDS; ++i) zero = zero && rec[i] == 0.0;
+        if (zero) continue;
+        if (rec[0] != (double)amc::xs::XS_R || !(rec[1] >= amc::xs::XS_LMIN && rec[1] <= amc::xs::XS_LMAX) || !(rec[2] >= 0.0 && rec[2] <= 7.0))
+            return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: record of rung %d, column %d is no kind-R record", r, c);
+        for (int i = 3; i < amc::xs::XS_WORDS; ++i)
+            if (!(std::fabs(rec[i]) < 9007199254740992.0) || rec[i] != std::floor(rec[i]))
+                return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: record of rung %d, column %d: word %d is no integer below 2^53", r, c, i);
+        if (!((amc::bridge_cols_at(AMC_BRIDGE_ALL, r, R) >> c) & 1))
+            return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: rung %d has no summand for column %d, its record must be all zero", r, c);
+        cols |= 1 << c;
+        amc::xs::PartR p = amc::xs::rec_to_r(rec);
+        amc::xs_word* row = host.data() + (size_t)s * amc::XS_ROW_R;
+        row[0] = (amc::xs_word)(uint32_t)p.top | ((amc::xs_word)p.flags << 32);
+        row[1] = (amc::xs_word)p.k1.lo; row[2] = (amc::xs_word)p.k1.hi;
+        row[3] = (amc::xs_word)p.k2.lo; row[4] = (amc::xs_word)p.k2.hi;
+        row[5] = 1ull;
+    }
+    if (!cols) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: n_snapshots = %llu with all-zero records", (unsigned long long)n_snapshots);
+    for (int s = 0; s < n_slots; ++s)
+        if (((amc::bridge_cols_at(cols, s / amc::BR_COLS, R) >> (s % amc::BR_COLS)) & 1) && !host[(size_t)s * amc::XS_ROW_R + 5])
+            return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: column %d has records at some rungs and none at rung %d", s % amc::BR_COLS, s / amc::BR_COLS);
+    host[amc::BRIDGE_COUNT] = (amc::xs_word)n_snapshots;
+    if (!h->d_bridge) AMC_HIP(hipMalloc(&h->d_bridge, BRIDGE_BYTES));
+    AMC_HIP(hipMemcpyAsync(h->d_bridge, host.data(), BRIDGE_BYTES, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
+    h->bridge_cols = cols;
     return AMC_OK;
 }
 
@@ -485,6 +616,8 @@ int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const 
     a.gaps = h->d_xcnt;
     a.trips = h->d_lab ? h->d_track : nullptr;
     a.rec = h->d_respace;
+    a.bridge = h->d_bridge;
+    a.bridge_words = amc::BRIDGE_WORDS;
     a.gamma = gamma;
     a.eps = eps;
     a.rule = rule;

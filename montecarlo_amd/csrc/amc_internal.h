@@ -171,6 +171,9 @@ struct amc_handle {
     amc::xs_word* d_rung_rows = nullptr;    // [launches * grid][n_rungs][RED_COLS][XS_ROW_R] block rows of the rung sums (amc_reduce_rungs_exact,
     size_t rung_rows_words = 0;             //   allocated at its first use, grown when a call needs more); the words it holds
     double* d_rung_recs = nullptr;          // [AMC_MAX_RUNGS][RED_COLS][XS_WORDS] their records (rung_finish_kernel)
+    amc::xs_word* d_bridge = nullptr;       // [BRIDGE_WORDS] the accumulator of the bridge sums: a row per slot, then the number of snapshots
+                                            //   (amc_bridge_accumulate / amc_set_bridge; allocated at its first use: a handle that never accumulates has none)
+    int bridge_cols = 0;                    // the AMC_BRIDGE_* mask the accumulator was begun with; 0: free (the next amc_bridge_accumulate fixes it)
     uint8_t* d_lab = nullptr;               // [M] walker labels, w | (d << 6) per chain; allocated exactly while tracking is on (amc_set_tracking)
     unsigned long long* d_track = nullptr;  // [2 + 3 * AMC_MAX_RUNGS] round_trips, up_trips, the cells of one flow snapshot (allocated with d_lab)
     unsigned long long* d_respace = nullptr;   // [RESPACE_WORDS] status of the last respacing, the count of status-0 ones, the ladder it computed

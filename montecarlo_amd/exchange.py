@@ -13,14 +13,18 @@ and everything else indexed by chain stay with the rung, so ``x[r::R]`` is alway
 ``track=True`` turns walker tracking on (DESIGN.md section 3.13 "Walker tracking"): the engine carries one label per chain -- which
 replica sits there and which end of the ladder it visited last -- through every accepted swap, and ``flow()`` / ``round_trips()``
 answer whether replicas actually travel between the hot and the cold end, which the acceptance per gap alone cannot.
+
+``bridge=True`` accumulates the bridge sums (DESIGN.md section 3.13 "Bridge sums") on the device while the run goes on: per rung the
+reproducible sums of the energy, its square and the neighbour-reweighting factors.  ``log_z_ratios()`` / ``log_z()`` turn them into
+free-energy differences along the ladder, ``heat_capacity()`` into the heat capacity per rung.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import sharding
-from ._capi import (AMC_MAX_MOVES, AMC_RED_HEADER, AMC_REDUCE_ALL, AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_XSUM_WORDS,
-                    xsum_round)
+from ._capi import (AMC_BRIDGE_ALL, AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_MB, AMC_BRIDGE_MF, AMC_BRIDGE_WB, AMC_BRIDGE_WF, AMC_MAX_MOVES,
+                    AMC_RED_HEADER, AMC_REDUCE_ALL, AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_XSUM_WORDS, xsum_round)
 from .metropolis import Metropolis
 from .simulation import AriannaAlgorithm, Simulation, _calls
 from .system import potential as _potential
@@ -35,11 +39,17 @@ class ReplicaExchange(AriannaAlgorithm):
     """ReplicaExchange(chains; dependencies=(Metropolis,), n_rungs=R): one exchange step of the Metropolis' engine per scheduled time.
 
     Listed behind its Metropolis, a time step at which both are due is [sweep; exchange], and ``run(fuse=True)`` queues a stretch
-    of such rounds that nothing else observes with one engine call (``sweep_exchange``): the same launches, the same results."""
+    of such rounds that nothing else observes with one engine call (``sweep_exchange``): the same launches, the same results.
+
+    ``bridge``: False, True (the acceptance set E | EE | MF | MB, what the default estimators read) or a mask of AMC_BRIDGE_* bits;
+    after every ``bridge_every``-th exchange step one snapshot of the bridge sums is queued behind it (nothing synchronises), and a
+    fused stretch is cut at those steps, so fused and stepwise runs accumulate the same records."""
+
+    BRIDGE_DEFAULT = AMC_BRIDGE_E | AMC_BRIDGE_EE | AMC_BRIDGE_MF | AMC_BRIDGE_MB
 
     mutates_chains = True          # a callback due behind it at the same t observes the state AFTER the swaps (simulation._observed_next)
 
-    def __init__(self, chains, dependencies=None, n_rungs=None, path=None, track=False, **extras):
+    def __init__(self, chains, dependencies=None, n_rungs=None, path=None, track=False, bridge=False, bridge_every=1, **extras):
         assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
         self.metropolis: Metropolis = dependencies[0]
         if n_rungs is None:
@@ -48,6 +58,18 @@ class ReplicaExchange(AriannaAlgorithm):
             raise ValueError("ReplicaExchange: n_rungs is missing (and the chains were not made by ParticleChains.ladder)")
         self.n_rungs = int(n_rungs)
         self.track = bool(track)
+        if bridge is True:
+            self.bridge = self.BRIDGE_DEFAULT
+        elif bridge is False or bridge is None:
+            self.bridge = 0
+        else:
+            self.bridge = int(bridge)
+            if self.bridge <= 0 or self.bridge & ~AMC_BRIDGE_ALL:
+                raise ValueError(f"ReplicaExchange: bridge = {bridge!r} is neither a bool nor a non-empty mask of AMC_BRIDGE_* bits")
+        if int(bridge_every) != bridge_every or int(bridge_every) < 1:
+            raise ValueError(f"ReplicaExchange: bridge_every = {bridge_every!r} must be an integer >= 1")
+        self.bridge_every = int(bridge_every)
+        self.metropolis.bridge = self.bridge           # (storage.checkpoint: the accumulator is state while the bridge is on)
         self.rank, _ = sharding.world()
 
     def initialise(self, simulation: Simulation) -> None:
@@ -56,13 +78,29 @@ class ReplicaExchange(AriannaAlgorithm):
             self.metropolis.engine.set_tracking(True)
             self.metropolis.tracking = True
 
+    def _bridge_due(self) -> bool:
+        """The exchange step just queued was a ``bridge_every``-th one (the engine's step index: a resumed run keeps the rhythm)."""
+        return self.metropolis.engine.exchange_step % self.bridge_every == 0
+
     def make_step(self, simulation: Simulation) -> None:
         self.metropolis.engine.exchange(1)
         self.metropolis.invalidate_reductions()
+        if self.bridge and self._bridge_due():
+            self.metropolis.engine.bridge_accumulate(self.bridge)
 
     def make_rounds(self, simulation: Simulation, n_rounds: int, sweeps_per_round: int) -> None:
-        """n_rounds x [sweeps_per_round x make_step!(::Metropolis); make_step!(::ReplicaExchange)] as one engine call."""
-        self.metropolis.sweep_exchange(n_rounds, sweeps_per_round)
+        """n_rounds x [sweeps_per_round x make_step!(::Metropolis); make_step!(::ReplicaExchange)] as one engine call -- with the
+        bridge on, one call up to each exchange step behind which a snapshot is due, then the snapshot."""
+        if not self.bridge:
+            self.metropolis.sweep_exchange(n_rounds, sweeps_per_round)
+            return
+        eng, left = self.metropolis.engine, int(n_rounds)
+        while left > 0:
+            n = min(left, self.bridge_every - eng.exchange_step % self.bridge_every)
+            self.metropolis.sweep_exchange(n, sweeps_per_round)
+            left -= n
+            if self._bridge_due():
+                eng.bridge_accumulate(self.bridge)
 
     def acceptance(self) -> np.ndarray:
         """Accepted / attempted swaps per gap over ALL shards, R - 1 ratios (0/0 = NaN before the first attempt)."""
@@ -107,6 +145,88 @@ class ReplicaExchange(AriannaAlgorithm):
         out = sums / float(len(self.metropolis.chains) // self.n_rungs)
         out[:, ~asked] = np.nan
         return out
+
+    # ---- bridge sums: free-energy differences along the ladder (DESIGN.md section 3.13 "Bridge sums") ----
+    def _need_bridge(self, what: str, columns: int) -> None:
+        if not self.bridge:
+            raise ValueError(f"{what} needs the bridge sums: build the ReplicaExchange with bridge=True")
+        if columns & ~self.bridge:
+            raise ValueError(f"{what} reads bridge columns {columns & ~self.bridge} that the mask bridge = {self.bridge} leaves out")
+
+    def bridge_sums(self):
+        """(sums, n_snapshots): the accumulated bridge sums over the ladders of ALL shards, an array of shape (R, 6) in the column
+        order E, EE, WF, WB, MF, MB -- NaN where a column is outside the mask or a rung has no such summand (WF, MF at rung R - 1, WB, MB
+        at rung 0) --, and the number of snapshots in them.  The shards' integer records are merged and rounded once (as rung_sums),
+        so the bits do not depend on the split into shards; a record that met a NaN or an infinity reads NaN / +-Inf.  The host
+        waits for the queued steps; the accumulator goes on."""
+        if not self.bridge:
+            raise ValueError("ReplicaExchange.bridge_sums needs the bridge sums: build the ReplicaExchange with bridge=True")
+        eng = self.metropolis.engine
+        rec, n = eng.bridge_fetch(reset=False)
+        counts = sharding.allreduce_sum(np.array([float(n), float(n) * float(n), 1.0]), eng)
+        if counts[0] != n * counts[2] or counts[1] != float(n) * float(n) * counts[2]:
+            raise RuntimeError(f"ReplicaExchange.bridge_sums: this shard holds {n} snapshots, the shards' mean is {counts[0] / counts[2]}")
+        rec = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, AMC_XSUM_WORDS)
+        merged = np.concatenate([sharding.allreduce_xsum(rec[i:i + XSUM_CHUNK], eng).reshape(-1, AMC_XSUM_WORDS)
+                                 for i in range(0, rec.shape[0], XSUM_CHUNK)])
+        empty = ~merged.any(axis=1)
+        sums = xsum_round(merged)
+        sums[empty] = np.nan
+        return sums.reshape(self.n_rungs, 6), n
+
+    def _bridge_means(self, what: str, columns: int):
+        self._need_bridge(what, columns)
+        sums, n = self.bridge_sums()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return sums, sums / (float(n) * float(len(self.metropolis.chains) // self.n_rungs))
+
+    def log_z_ratios(self, method: str = "acceptance") -> np.ndarray:
+        """log(Z_(r+1) / Z_r) for the R - 1 gaps of the ladder, Z_r = integral of exp(-beta_r U), from the accumulated bridge sums.
+
+        "acceptance" (default): Bennett's identity with the Metropolis function at C = 0, log S_MF[r] - log S_MB[r + 1] -- both
+            rungs hold the same number of samples, so the count cancels.  Its summands lie in [0, 1]: finite variance whatever the
+            ladder.  R - 1 numbers.
+        "exponential": the two one-sided exponential averages, shape (2, R - 1): row 0 log(S_WF[r] / N) (forward, samples of rung r),
+            row 1 -log(S_WB[r + 1] / N) (backward, samples of rung r + 1), N = snapshots x global ladders.  The backward average has
+            INFINITE variance once beta_(r+1) >= 2 beta_r for a harmonic well (exp((beta_(r+1) - beta_r) e) under exp(-beta_(r+1) e):
+            its second moment diverges): read it as a diagnostic, not as an estimate, on a coarse ladder.
+        "ti": thermodynamic integration by the trapezoid, -(<e>_r + <e>_(r+1)) (beta_(r+1) - beta_r) / 2, beta from betas().
+        An estimate that reads a flagged record (a NaN or an infinity among its summands) is NaN; so is every estimate before the
+        first snapshot.  The host waits for the queued steps."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            if method == "acceptance":
+                sums, _ = self._bridge_means("ReplicaExchange.log_z_ratios('acceptance')", AMC_BRIDGE_MF | AMC_BRIDGE_MB)
+                out = np.log(sums[:-1, 4]) - np.log(sums[1:, 5])
+            elif method == "exponential":
+                _, mean = self._bridge_means("ReplicaExchange.log_z_ratios('exponential')", AMC_BRIDGE_WF | AMC_BRIDGE_WB)
+                out = np.stack([np.log(mean[:-1, 2]), -np.log(mean[1:, 3])])
+            elif method == "ti":
+                _, mean = self._bridge_means("ReplicaExchange.log_z_ratios('ti')", AMC_BRIDGE_E)
+                b = self.betas()
+                out = -0.5 * (mean[:-1, 0] + mean[1:, 0]) * (b[1:] - b[:-1])
+            else:
+                raise ValueError(f"ReplicaExchange.log_z_ratios: method {method!r} is none of 'acceptance', 'exponential', 'ti'")
+        out[~np.isfinite(out)] = np.nan
+        return out
+
+    def log_z(self, method: str = "acceptance") -> np.ndarray:
+        """log(Z_r / Z_0) per rung, R values: the cumulative sum of log_z_ratios(method) with log Z_0 = 0 ("exponential": shape (2, R))."""
+        d = self.log_z_ratios(method)
+        return np.concatenate([np.zeros(d.shape[:-1] + (1,)), np.cumsum(d, axis=-1)], axis=-1)
+
+    def heat_capacity(self) -> np.ndarray:
+        """beta_r^2 (<e^2> - <e>^2) per rung, R values, from the accumulated bridge sums; beta from betas()."""
+        _, mean = self._bridge_means("ReplicaExchange.heat_capacity", AMC_BRIDGE_E | AMC_BRIDGE_EE)
+        b = self.betas()
+        out = b * b * (mean[:, 1] - mean[:, 0] * mean[:, 0])
+        out[~np.isfinite(out)] = np.nan
+        return out
+
+    def restart_bridge(self) -> None:
+        """The accumulator of the bridge sums starts again from nothing (a burn-in ends here).  The host waits for the queued steps."""
+        if not self.bridge:
+            raise ValueError("ReplicaExchange.restart_bridge needs the bridge sums: build the ReplicaExchange with bridge=True")
+        self.metropolis.engine.bridge_fetch(reset=True)
 
     def betas(self) -> np.ndarray:
         """The ladder as the device holds it now, R beta values (Float32 state: the Float32 values, widened).  The host waits for
@@ -280,6 +400,18 @@ def callback_round_trips(simulation: Simulation) -> np.ndarray:
     """(round trips, up trips) over all ladders since the start, a vector of 2 values (ReplicaExchange.round_trips).  Needs
     ReplicaExchange(..., track=True)."""
     return _find_exchange(simulation).round_trips()
+
+
+def callback_log_z(simulation: Simulation) -> np.ndarray:
+    """log(Z_r / Z_0) per rung, a vector of R values (ReplicaExchange.log_z, the acceptance estimator) from the bridge sums accumulated
+    so far; reading it does not reset the accumulator.  Needs ReplicaExchange(..., bridge=True)."""
+    return _find_exchange(simulation).log_z()
+
+
+def callback_heat_capacity(simulation: Simulation) -> np.ndarray:
+    """The heat capacity beta_r^2 (<e^2> - <e>^2) per rung, a vector of R values (ReplicaExchange.heat_capacity) from the bridge sums
+    accumulated so far; reading it does not reset the accumulator.  Needs ReplicaExchange(..., bridge=True)."""
+    return _find_exchange(simulation).heat_capacity()
 
 
 def callback_rung_energy(simulation: Simulation) -> np.ndarray:

@@ -169,6 +169,9 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
         if getattr(metropolis, "tracking", False):  # walker tracking is on: the labels and the trip counters are state too
             walker, direction = eng.labels()
             data.update(walker=walker, direction=direction, trips=np.array(eng.tracking_counters(), dtype=np.int64))
+        if getattr(metropolis, "bridge", 0):        # the bridge sums are on: the accumulator is state (no field otherwise)
+            rec, n_snap = eng.bridge_fetch(reset=False)
+            data.update(bridge_records=rec, bridge_columns=int(metropolis.bridge), bridge_snapshots=n_snap)
         n_respaced = eng.respace_status()[1] if hasattr(eng, "respace_status") else 0
         if n_respaced:                              # the ladder was respaced (ReplicaExchange.respace keeps beta_array current): no field otherwise
             data["n_respaced"] = n_respaced
@@ -226,6 +229,11 @@ def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
             if "n_tuned" in d and tab is not None:
                 eng.set_tuned(int(d["n_tuned"]))
             metropolis._rung_window_used = True
+        if "bridge_records" in d:                   # the accumulator of the bridge sums: the resumed run accumulates on to the same bits
+            if getattr(metropolis, "bridge", 0) and int(d["bridge_columns"]) != int(metropolis.bridge):
+                raise ValueError(f"checkpoint holds bridge sums of columns {int(d['bridge_columns'])}, this ReplicaExchange asks for "
+                                 f"{int(metropolis.bridge)}")
+            eng.set_bridge(d["bridge_records"], int(d["bridge_snapshots"]))
         if "n_respaced" in d:                       # a respaced ladder: the host copy follows the checkpoint's beta, as the engine did
             eng.set_respaced(int(d["n_respaced"]))
             metropolis.chains.beta_array[start:stop] = d["beta"]
