@@ -686,6 +686,9 @@ int  amc_selftest_philox(int device, uint64_t seed, const uint64_t *pair, const 
  * [8..10] values 5, 0, 2 through the three-value form, [11] value 3 alone, [12] the largest low 32-bit word of row 0;
  * totals_plain[0..5]: the six sums by plain DPP rounds.  Sums are modulo 2^64. */
 int  amc_selftest_wave_totals(int device, const int64_t *values, int64_t *totals, int64_t *totals_plain);
+/* The math tables as a block holds them in LDS: one block stages them the way every kernel does and copies its LDS out;
+ * out546: 546 doubles (the rotated layout, the LOGC entries times -2: amc_math.h).  Host buffer. */
+int  amc_selftest_staged_tables(int device, double *out546);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -159,6 +159,7 @@ def load() -> C.CDLL:
         "amc_set_reduce_columns": (C.c_int, [H, C.c_int]),
         "amc_parameters_end_all": (C.c_int, [H, dp, C.c_int]),
         "amc_selftest_wave_totals": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "amc_selftest_staged_tables": (C.c_int, [C.c_int, dp]),
         "amc_set_ladder": (C.c_int, [H, C.c_int]),
         "amc_exchange": (C.c_int, [H, C.c_int64]),
         "amc_sweep_exchange": (C.c_int, [H, C.c_int64, C.c_int64]),
@@ -1175,3 +1176,10 @@ def selftest_wave_totals(values: np.ndarray, device: int = 0):
     _check(load().amc_selftest_wave_totals(int(device), values.ctypes.data_as(i64p), out.ctypes.data_as(i64p),
                                            ref.ctypes.data_as(i64p)))
     return out, ref
+
+
+def selftest_staged_tables(device: int = 0) -> np.ndarray:
+    """The 546 doubles of the math tables as a block holds them in LDS, staged and copied out on the GPU (parity tests only)."""
+    out = np.empty(546, dtype=np.float64)
+    _check(load().amc_selftest_staged_tables(int(device), _dptr(out)))
+    return out

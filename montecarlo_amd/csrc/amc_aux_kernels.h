@@ -54,8 +54,8 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void histogram_kernel
 template <int POT>
 __global__ __launch_bounds__(AMC_BLOCK) void energy_kernel(const real_t* x, int64_t n_chains, double* e)
 {
-    __shared__ double s_math[TAB_DOUBLES];
-    stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);
     const int64_t stride = (int64_t)gridDim.x * AMC_BLOCK;
     for (int64_t c = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x; c < n_chains; c += stride)
         e[c] = (double)potential<POT>(x[c], s_math);
@@ -94,8 +94,8 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void gather_strided_k
 #if AMC_PLAIN_KERNELS
 AMC_KERNEL_LINKAGE __global__ void selftest_math_kernel(int fn, const double* a, const double* b, double* out, int64_t n)
 {
-    __shared__ double s_math[TAB_DOUBLES];
-    stage_math_tables(s_math, threadIdx.x, blockDim.x);
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double v = a[i];
@@ -135,6 +135,16 @@ AMC_KERNEL_LINKAGE __global__ void selftest_math_kernel(int fn, const double* a,
 }
 #endif
 
+// The math tables as a block holds them (amc_selftest_staged_tables): staged the way every kernel stages them, then copied out of LDS.
+#if AMC_PLAIN_KERNELS
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void selftest_staged_tables_kernel(double* out)
+{
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);
+    for (int i = threadIdx.x; i < TAB_DOUBLES; i += AMC_BLOCK) out[i] = s_math[i];
+}
+#endif
+
 // Exhaustive check of the accept filter's float estimate (accept_filter_f32) on the range where the filter relies on its
 // ACCURACY, -17 <= t <= 0: for EVERY float t with bit pattern in [bits_lo, bits_hi] the relative deviation of
 // v_exp_f32(max(t, -17) * log2e) from the spec's f64 exp(t); the maximum over the range lands in out_max_bits (bits of a
@@ -144,8 +154,8 @@ AMC_KERNEL_LINKAGE __global__ void selftest_math_kernel(int fn, const double* a,
 #if AMC_PLAIN_KERNELS
 AMC_KERNEL_LINKAGE __global__ __launch_bounds__(256) void selftest_filter_kernel(uint32_t bits_lo, uint64_t count, unsigned long long* out_max_bits)
 {
-    __shared__ double s_math[TAB_DOUBLES];
-    stage_math_tables(s_math, threadIdx.x, 256);
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);
     double worst = 0.0;
     const uint64_t stride = (uint64_t)gridDim.x * 256;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {

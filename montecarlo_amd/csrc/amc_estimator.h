@@ -339,7 +339,7 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
     } else {
         r_init(gr, s_gr[threadIdx.x >> 6]);
     }
-    stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);      // overlaps the latency of the first load
+    stage_math_tables_unrotated(s_math, threadIdx.x, AMC_BLOCK);      // overlaps the latency of the first load (why not the copy: see there)
     if (CAN_DEFER && pending) {
         auto uni = [](double v) {
             const unsigned long long b = (unsigned long long)__double_as_longlong(v);

@@ -65,13 +65,13 @@ struct ExchangeTrackArgs {
 template <int POT, bool TRACK>
 __device__ __forceinline__ void exchange_step(const ExchangeArgs& a, uint8_t* lab, unsigned long long* trips)
 {
-    __shared__ double s_math[TAB_DOUBLES];
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
     __shared__ unsigned int s_cnt[2 * AMC_MAX_RUNGS];
     __shared__ unsigned int s_trips[TRACK ? 2 : 1];
     if (threadIdx.x < 2 * AMC_MAX_RUNGS) s_cnt[threadIdx.x] = 0u;
     if constexpr (TRACK)
         if (threadIdx.x < 2) s_trips[threadIdx.x] = 0u;
-    stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);        // (ends in a barrier)
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier)
 
     const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
     const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / a.n_gaps;
@@ -393,7 +393,7 @@ template <int POT>
 __global__ __launch_bounds__(AMC_BLOCK) void rung_sums_kernel(const RungSumsArgs a)
 {
     constexpr int MAX_SLOTS = AMC_MAX_RUNGS * RED_COLS;
-    __shared__ double s_math[POT == POT_CUSTOM ? TAB_DOUBLES : 1];      // a custom potential may call amc_exp
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[POT == POT_CUSTOM ? TAB_DOUBLES : 1];      // a custom potential may call amc_exp
     __shared__ int s_top[MAX_SLOTS];
     __shared__ unsigned int s_flags[MAX_SLOTS];
     __shared__ unsigned long long s_k[MAX_SLOTS][4];                    // k1.lo, k1.hi, k2.lo, k2.hi (hi: two's complement)
@@ -403,7 +403,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void rung_sums_kernel(const RungSumsArgs
         s_flags[s] = 0u;
         s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
     }
-    if (POT == POT_CUSTOM) stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);        // (ends in a barrier)
+    if (POT == POT_CUSTOM) stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier)
 
     const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
     const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / a.n_rungs;
@@ -559,7 +559,7 @@ template <int POT>
 __global__ __launch_bounds__(AMC_BLOCK) void bridge_sums_kernel(const BridgeArgs a)
 {
     constexpr int MAX_SLOTS = AMC_MAX_RUNGS * BR_COLS;
-    __shared__ double s_math[TAB_DOUBLES];                               // exp for every potential
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];                               // exp for every potential
     __shared__ int s_top[MAX_SLOTS];
     __shared__ unsigned int s_flags[MAX_SLOTS];
     __shared__ unsigned long long s_k[MAX_SLOTS][4];                    // k1.lo, k1.hi, k2.lo, k2.hi (hi: two's complement)
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void bridge_sums_kernel(const BridgeArgs
         s_flags[s] = 0u;
         s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
     }
-    stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);                  // (ends in a barrier: the slots are cleared too)
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);                  // (ends in a barrier: the slots are cleared too)
 
     const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
     const int64_t ladders_per_trip = ((int64_t)gridDim.x * AMC_BLOCK) / a.n_rungs;

@@ -30,8 +30,8 @@ __global__ __launch_bounds__(AMC_BLOCK) void reduce_kernel(const real_t* x, cons
     // p_stride names the row's form (red_finish): the compact one for passes of at most RED_COMPACT_TRIPS trips per lane
     const bool compact = p_stride == RED_COMPACT_WORDS;
     const int64_t stride = (int64_t)gridDim.x * AMC_BLOCK;
-    __shared__ double s_math[POT == POT_CUSTOM ? TAB_DOUBLES : 1];      // a custom potential may call amc_exp
-    if (POT == POT_CUSTOM) stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[POT == POT_CUSTOM ? TAB_DOUBLES : 1];      // a custom potential may call amc_exp
+    if (POT == POT_CUSTOM) stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);
     constexpr int RNC = RedCols<POT>::NC;
     RLanes<RNC> red;
     __shared__ xs::PartR s_red[AMC_BLOCK / 64][RNC];

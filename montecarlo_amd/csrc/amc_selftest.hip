@@ -86,4 +86,17 @@ int amc_selftest_wave_totals(int device, const int64_t* values, int64_t* totals,
     return AMC_OK;
 }
 
+int amc_selftest_staged_tables(int device, double* out546)
+{
+    if (!out546) return fail(AMC_ERR_BAD_ARG, "amc_selftest_staged_tables: NULL argument");
+    AMC_HIP(hipSetDevice(device));
+    double* dout = nullptr;
+    AMC_HIP(hipMalloc(&dout, amc::TAB_DOUBLES * sizeof(double)));
+    hipLaunchKernelGGL(amc::selftest_staged_tables_kernel, dim3(1), dim3(AMC_BLOCK), 0, 0, dout);
+    AMC_HIP(hipGetLastError());
+    AMC_HIP(hipMemcpy(out546, dout, amc::TAB_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
+    (void)hipFree(dout);
+    return AMC_OK;
+}
+
 }  // extern "C"

@@ -217,11 +217,11 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     if (REDUCE) r_init(red, s_red[threadIdx.x >> 6]);
     __shared__ double s_tab[(MULTI || RUNG) ? MT_ROWS * AMC_MAX_MOVES : 1];
     __shared__ __attribute__((aligned(16))) uint8_t s_pick[MULTI ? AMC_PICK_CELLS : 16];
-    __shared__ double s_math[TAB_DOUBLES];        // exp / log / sincospi tables, 4.4 KB
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];        // exp / log / sincospi tables, 4.4 KB
 #ifdef AMC_PARAM_F32
     __shared__ float2 s_mathf_store[TABF_PAIRS];  // the Float32 log and sincospi tables of box_muller_f32, 2 KB
     const float2* s_mathf = s_mathf_store;
-    stage_math_tables_f32(s_mathf_store, threadIdx.x, AMC_BLOCK);      // visible after the barrier that ends stage_math_tables below
+    stage_math_tables_f32(s_mathf_store, threadIdx.x, AMC_BLOCK);      // visible after the barrier that ends store_math_tables below
 #else
     const float2* s_mathf = nullptr;
 #endif
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
             s_tab[MT_RDEN * AMC_MAX_MOVES + i] = a.ptab[PT_RDEN * AMC_MAX_MOVES + i];
             if (AMC_SIGMA_MEMO) mt_set_log_sigma(s_tab, i, log_f64(a.ptab[PT_SIGMA * AMC_MAX_MOVES + i]));      // (SigmaArg)
         }
-        // visible to the block after the barrier that ends stage_math_tables below
+        // visible to the block after the barrier that ends store_math_tables below
     }
     if (RUNG) {
         for (int i = threadIdx.x; i < K * a.n_rungs; i += AMC_BLOCK) {       // (<= AMC_MAX_MOVES entries: amc_set_rung_sigma)
@@ -291,6 +291,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     // (The first trip's "nothing to store yet" is still the test base_done >= 0, one v_cmp_lt_i64: as a 32-bit test of the
     // trip count or as base != first it costs the K == 1 forms 2-3 VGPRs, and the per-chain-beta and REDUCE forms a wave per SIMD.)
     const int trips = a.full_rounds + ((int)(blockIdx.x * AMC_BLOCK) < a.tail_pairs ? 1 : 0);
+    // The math tables' loads go out first: the first trip's state and its Philox rounds follow under their latency, and the writes to LDS
+    // (store_math_tables below) find them landed.
+    const MathTableLoads<AMC_BLOCK> math_loads = load_math_tables<AMC_BLOCK>(threadIdx.x);
     real2 x_nxt = {(real_t)0.0, (real_t)0.0}, b_nxt = {(real_t)a.beta, (real_t)a.beta};
     if (trips > 0) {
         x_nxt = load_x(first);
@@ -302,7 +305,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     uint64_t pair = a.pair0 + (uint64_t)(first + threadIdx.x);
     asm volatile("" : "+v"(pair));
     // SINGLE: the Philox draws of an iteration are formed one iteration ahead -- those of the first iteration
-    // right here, while the first load and the table loads are in flight (the arithmetic of ~80 VALU
+    // right here, while the table loads and the first load are in flight (the arithmetic of ~80 VALU
     // instructions per wave would otherwise start only after both have landed).
     constexpr bool AHEAD = SINGLE;
     StepDraws dr_nxt = {};
@@ -317,7 +320,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
 #ifdef AMC_USER_LOGQ
     stage_user_theta(a.ptab, MULTI);
 #endif
-    stage_math_tables(s_math, threadIdx.x, AMC_BLOCK);     // overlaps the latency of the first load; ends in a barrier
+    store_math_tables<AMC_BLOCK>(s_math, threadIdx.x, math_loads);      // behind the Philox work; ends in a barrier
     // Drain the first load HERE, once.  Otherwise the compiler must assume it is still pending inside the loop
     // and puts a counted wait before the first use of x in every iteration -- which in steady state waits for
     // the prefetch issued a few dozen instructions earlier instead of leaving it a whole iteration.

@@ -3,7 +3,8 @@
 
 Writes the SAME literal values (C99 hex floats, correctly rounded from 60-digit decimals) to
     oracle/amc_tables.inc                 (included by oracle/amc_oracle.c)
-    montecarlo_amd/csrc/amc_tables.h      (included by the HIP kernels; staged into LDS per block)
+    montecarlo_amd/csrc/amc_tables.h      (included by the HIP kernels; AMC_MATH_TABLES_STAGED, the same values in the layout
+                                           of a block's LDS, is what every block copies there)
 
   EXP2[32]      2^(j/32)
   LOG_INVC[129], LOG_LOGC[129]   indexed by idx - 53, idx = (low exponent bit : top 7 mantissa bits) of the centred
@@ -136,6 +137,13 @@ def f32_tables():
     return logf, scf
 
 
+def staged_image(e2, invc, logc, sn, cs):
+    """The 546 doubles as a block keeps them in LDS (amc_math.h, LDS_*): the order EXP2 | LOG_INVC | LOG_LOGC | SINPI | COSPI rotated by
+    the length of the cosine table, so that it comes first, and the LOGC entries times -2 (exact: a power of two)."""
+    logc2 = [(-2.0 * float.fromhex(v)).hex() for v in logc]
+    return cs + e2 + invc + logc2 + sn
+
+
 def emit(name, vals, per_line=4):
     out = [f"static const double {name}[{len(vals)}] = {{"]
     for i in range(0, len(vals), per_line):
@@ -157,6 +165,10 @@ def main():
         f.write(head + "#define AMC_TAB_LOG_IDX_MIN 53\n" + body + "\n")
     allv = e2 + invc + logc + sn + cs
     dev = emit("AMC_MATH_TABLES", allv).replace("static const double", "__device__ const double")
+    staged = staged_image(e2, invc, logc, sn, cs)
+    assert len(staged) == len(allv)
+    dev_staged = emit("AMC_MATH_TABLES_STAGED", staged).replace("static const double", "__device__ const double").replace(
+        "[546]", "[546] __attribute__((aligned(16)))")
     logf, scf = f32_tables()
     assert len(logf) == 258 and len(scf) == 256
     suffix = lambda vals: [v + "f" for v in vals]
@@ -172,6 +184,8 @@ def main():
                 "// indexed by idx - TAB_LOG_IDX_MIN (only idx in [53, 181] can occur)\n"
                 "enum { TAB_EXP2 = 0, TAB_LOG_INVC = 32, TAB_LOG_LOGC = 161, TAB_SINPI = 290, TAB_COSPI = 418,\n"
                 "       TAB_DOUBLES = 546, TAB_LOG_IDX_MIN = 53 };\n" + dev + "\n"
+                "// the same 546 doubles as a block's LDS holds them (amc_math.h, LDS_*): rotated so that COSPI comes first, the\n"
+                "// LOG_LOGC entries times -2 (exact); stage_math_tables copies this image, 273 16-byte quads\n" + dev_staged + "\n"
                 "// Float32 policy parameters (box_muller_f32): pairs -- LOGF[129] (INVC, 2 log INVC), same index as above;\n"
                 "// SINCOSF[128] (sin, cos)(pi j / 64).  TABF_* count PAIRS.\n"
                 "enum { TABF_LOG = 0, TABF_SINCOS = 129, TABF_PAIRS = 257 };\n" + devf + "\n}  // namespace amc\n")
