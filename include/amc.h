@@ -508,6 +508,52 @@ int  amc_rung_window_restart(amc_handle *h);
 int  amc_rung_window_base(amc_handle *h, int64_t *accepted, int64_t *total);
 int  amc_set_rung_window_base(amc_handle *h, const int64_t *accepted, const int64_t *total);
 
+/* Population annealing (which holds the step operation by operation): amc_anneal moves the handle's shared
+ * beta to beta_new and resamples the WHOLE ensemble in proportion to exp(-(beta_new - beta) e_c): with a_c = double((-e_c) delta),
+ * delta = T(beta_new) - T(beta) in the state's type, and a_max their maximum, chain c has the integer weight
+ * W_c = floor(2^AMC_ANNEAL_WEIGHT_BITS amc_exp(a_c - a_max)); T_w = sum W_c and the inclusive prefix C_c are exact 64-bit integers;
+ * one Philox draw per step (id 0, t = the annealing step index, draw 0, stream 4) gives the offset U = mulhi64(w.x | w.y << 32, T_w);
+ * the parent of child slot j is the unique i with C_(i-1) M <= j T_w + U < C_i M (systematic resampling, 128-bit integers), and
+ * x'_j = x_parent(j).  Chain i gets floor(M W_i / T_w) or ceil(M W_i / T_w) children, a chain with W = 0 none; beta_new == beta (no NaN
+ * energies) is the identity.  Everything is an integer or a maximum: the same bits on any grid.
+ * Asynchronous, stream-ordered behind what is queued (a pending learning step is taken first, as before an exchange step); every
+ * launch queued afterwards uses beta_new.  The Move counters, the step log, the MH and estimator step indices and reductions in flight
+ * stay with the slot.  The second position buffer and the step's scratch are allocated at the first call: a handle that never anneals
+ * has none.  Every step appends one record of AMC_ANNEAL_RECORD_WORDS 64-bit words to a log on the device: status, the bits of beta
+ * before, the bits of beta_new, the bits of a_max, T_w, U, n_parents (chains with at least one child), max_children.  Status 0: resampled;
+ * 1: every a_c was NaN; 2: a_max = +Inf; 3: a_max = -Inf (no chain has a weight).  With a status other than 0 the positions are left
+ * alone and T_w, U, n_parents, max_children read 0 (a_max reads a NaN with status 1); beta moves and the step counts in every case.
+ * log(Z(beta_new) / Z(beta)) ~ a_max + log T_w - log M - AMC_ANNEAL_WEIGHT_BITS log 2, formed by the caller from the record.
+ * AMC_ERR_STATE: a per-chain beta array, a ladder, a handle that does not hold the whole ensemble (chain_offset != 0 or
+ * n_chains != n_chains_global: resampling across devices is not done), a full log (AMC_ANNEAL_MAX_RECORDS).  AMC_ERR_BAD_ARG: beta_new
+ * not finite, n_chains >= 2^33.  A refused call leaves the handle as it was.
+ * amc_anneal_fetch: *n = records in the log; with records != NULL the records themselves (capacity in records, AMC_ERR_BAD_ARG when it
+ * is below *n), synchronises; reset empties the log.  amc_set_anneal_records puts n records back (resume; NULL or n = 0 empties it).
+ * amc_get_anneal_step / amc_set_anneal_step: annealing steps done (the step index of the offset's draw; below 2^48), settable for
+ * resume.  amc_get_beta: the shared beta as the launches queued from now on use it; amc_set_beta puts one back without resampling
+ * (resume: a fresh handle starts at the beta of its creation; AMC_ERR_BAD_ARG when it is not finite). */
+#define AMC_ANNEAL_WEIGHT_BITS 30
+#define AMC_ANNEAL_MAX_RECORDS 4096
+#define AMC_ANNEAL_RECORD_WORDS 8
+int  amc_anneal(amc_handle *h, double beta_new);
+int  amc_anneal_fetch(amc_handle *h, uint64_t *records, int capacity, int *n, int reset);
+int  amc_set_anneal_records(amc_handle *h, const uint64_t *records, int n);
+int  amc_get_anneal_step(amc_handle *h, uint64_t *t);
+int  amc_set_anneal_step(amc_handle *h, uint64_t t);
+int  amc_get_beta(amc_handle *h, double *beta);
+int  amc_set_beta(amc_handle *h, double beta);
+/* Families, population annealing's own diagnostic: amc_set_anneal_families(h, 1) gives every chain a 32-bit family id, fam[c] = c
+ * (n_chains <= 2^32 - 1; calling it again starts the families afresh), and every annealing step from then on gathers the ids along
+ * with the positions; (h, 0) frees them.  amc_anneal_family_stats synchronises and returns exact integers: the families that have a
+ * member, sum_f n_f^2 and max_f n_f (counted with atomics into a scratch array zeroed per call); rho_t = sum_sq / n_chains is what tells
+ * whether the population is large enough.  amc_download_families / amc_upload_families: the ids themselves, for checkpoints; an id
+ * >= n_chains is AMC_ERR_BAD_ARG.  All but amc_set_anneal_families need families on (AMC_ERR_STATE).  With families off nothing is
+ * allocated or gathered. */
+int  amc_set_anneal_families(amc_handle *h, int on);
+int  amc_anneal_family_stats(amc_handle *h, uint64_t *n_families, uint64_t *sum_sq, uint64_t *largest);
+int  amc_download_families(amc_handle *h, uint32_t *families);
+int  amc_upload_families(amc_handle *h, const uint32_t *families);
+
 /* MH steps done per chain so far (the Philox step index); settable for resume. */
 int  amc_get_step(amc_handle *h, uint64_t *t);
 int  amc_set_step(amc_handle *h, uint64_t t);

@@ -20,6 +20,9 @@ AMC_MAX_LEARN = 8
 AMC_RED_HEADER = 4
 AMC_GD_STRIDE = 5
 AMC_XSUM_WORDS = 12      # doubles per record of a reproducible sum (include/amc.h)
+AMC_ANNEAL_RECORD_WORDS = 8     # 64-bit words per record of an annealing step
+AMC_ANNEAL_MAX_RECORDS = 4096
+AMC_ANNEAL_WEIGHT_BITS = 30
 AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_REDUCE_ALL = 1, 2, 4, 7      # the sums over x a reduction forms (include/amc.h)
 # the columns of the bridge sums (include/amc.h); record order E, EE, WF, WB, MF, MB
 AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_WF, AMC_BRIDGE_WB, AMC_BRIDGE_MF, AMC_BRIDGE_MB, AMC_BRIDGE_ALL = 1, 2, 4, 8, 16, 32, 63
@@ -192,6 +195,17 @@ def load() -> C.CDLL:
         "amc_rung_window_restart": (C.c_int, [H]),
         "amc_rung_window_base": (C.c_int, [H, i64p, i64p]),
         "amc_set_rung_window_base": (C.c_int, [H, i64p, i64p]),
+        "amc_anneal": (C.c_int, [H, C.c_double]),
+        "amc_anneal_fetch": (C.c_int, [H, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int), C.c_int]),
+        "amc_set_anneal_records": (C.c_int, [H, C.POINTER(C.c_uint64), C.c_int]),
+        "amc_get_anneal_step": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "amc_set_anneal_step": (C.c_int, [H, C.c_uint64]),
+        "amc_get_beta": (C.c_int, [H, dp]),
+        "amc_set_beta": (C.c_int, [H, C.c_double]),
+        "amc_set_anneal_families": (C.c_int, [H, C.c_int]),
+        "amc_anneal_family_stats": (C.c_int, [H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "amc_download_families": (C.c_int, [H, C.POINTER(C.c_uint32)]),
+        "amc_upload_families": (C.c_int, [H, C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -651,6 +665,66 @@ class HipEngine:
         ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
         a = np.ascontiguousarray(rows, dtype=np.float64).reshape(n, self.gd_stride)
         _check(self._lib.amc_pg_set_accumulated(self._h, n, ids, _dptr(a)))
+
+    # -- population annealing (include/amc.h) ---------------------------------------
+    def anneal(self, beta_new: float) -> None:
+        """One annealing step (asynchronous): the shared beta moves to ``beta_new`` and the whole ensemble is resampled in proportion
+        to exp(-(beta_new - beta) e)."""
+        _check(self._lib.amc_anneal(self._h, float(beta_new)))
+
+    def anneal_records(self, reset: bool = False) -> np.ndarray:
+        """The records of the annealing steps in the log, shape (n, 8) uint64: status, bits of beta before / after, bits of a_max, T_w,
+        U, n_parents, max_children (synchronises); ``reset`` empties the log."""
+        n = C.c_int(0)
+        _check(self._lib.amc_anneal_fetch(self._h, None, 0, C.byref(n), 0))
+        out = np.zeros((n.value, AMC_ANNEAL_RECORD_WORDS), dtype=np.uint64)
+        _check(self._lib.amc_anneal_fetch(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), n.value, C.byref(n), 1 if reset else 0))
+        return out
+
+    def set_anneal_records(self, records) -> None:
+        rec = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, AMC_ANNEAL_RECORD_WORDS)
+        _check(self._lib.amc_set_anneal_records(self._h, rec.ctypes.data_as(C.POINTER(C.c_uint64)), int(rec.shape[0])))
+
+    @property
+    def anneal_step(self) -> int:
+        t = C.c_uint64(0)
+        _check(self._lib.amc_get_anneal_step(self._h, C.byref(t)))
+        return t.value
+
+    @anneal_step.setter
+    def anneal_step(self, t: int) -> None:
+        _check(self._lib.amc_set_anneal_step(self._h, int(t)))
+
+    @property
+    def beta(self) -> float:
+        """The shared beta as the launches queued from now on use it (amc_anneal moves it)."""
+        b = C.c_double(0.0)
+        _check(self._lib.amc_get_beta(self._h, C.byref(b)))
+        return b.value
+
+    @beta.setter
+    def beta(self, b: float) -> None:
+        _check(self._lib.amc_set_beta(self._h, float(b)))
+
+    def set_anneal_families(self, on: bool = True) -> None:
+        _check(self._lib.amc_set_anneal_families(self._h, 1 if on else 0))
+
+    def anneal_family_stats(self):
+        """(families with a member, sum of n_f^2, largest n_f): exact integers (synchronises)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self._lib.amc_anneal_family_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def download_families(self) -> np.ndarray:
+        out = np.empty(self.n_chains, dtype=np.uint32)
+        _check(self._lib.amc_download_families(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def upload_families(self, families) -> None:
+        fam = np.ascontiguousarray(families, dtype=np.uint32)
+        if fam.shape != (self.n_chains,):
+            raise AmcError(f"upload_families: one id per chain ({self.n_chains})")
+        _check(self._lib.amc_upload_families(self._h, fam.ctypes.data_as(C.POINTER(C.c_uint32))))
 
     # -- replica exchange along a temperature ladder (include/amc.h; DESIGN.md section 3.13) ----------------
     def set_ladder(self, n_rungs: int) -> None:

@@ -564,6 +564,14 @@ int amc_destroy(amc_handle* h)
     (void)hipFree(h->d_rung_cnt);
     (void)hipFree(h->d_rung_base);
     (void)hipFree(h->d_tune);
+    (void)hipFree(h->d_x_alt);
+    (void)hipFree(h->d_anneal_n);
+    (void)hipFree(h->d_anneal_tiles);
+    (void)hipFree(h->d_anneal_s);
+    (void)hipFree(h->d_anneal_log);
+    (void)hipFree(h->d_fam);
+    (void)hipFree(h->d_fam_alt);
+    (void)hipFree(h->d_fam_cnt);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

@@ -9,6 +9,8 @@
 //                       the per-rung reproducible sums: amc_reduce_rungs_exact, walker tracking: amc_set_tracking ..,
 //                       proposal widths per rung: amc_set_rung_sigma / amc_get_rung_sigma, respacing: amc_respace_ladder ..,
 //                       tuning the widths: amc_tune_rung_sigma .., the window of the acceptance per rung: amc_rung_window_*)
+//   amc_anneal.hip      population annealing (amc_anneal, its record log, the annealing step index, amc_get_beta, the families:
+//                       amc_set_anneal_families .. amc_upload_families)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -190,6 +192,18 @@ struct amc_handle {
     unsigned long long* d_rung_base = nullptr;  // [RUNG_BASE_WORDS] accepted, total per (move, rung) at the start of the window (zeroed by amc_set_ladder)
     unsigned long long* d_tune = nullptr;       // [TUNE_WORDS] the record of the tunings (zeroed by amc_set_rung_sigma and amc_set_ladder)
     bool tune_queued = false;                   // a tuning has been queued since the table was set: the device holds the table (amc_get_rung_sigma)
+    // Population annealing (amc_anneal.hip): all of it allocated at its first use -- a handle that never anneals
+    // has none
+    uint64_t t_a = 0;                           // annealing steps done (their own Philox step index)
+    double* d_x_alt = nullptr;                  // [M_pad] the second position buffer: a step gathers d_x into it, then the two change places
+    unsigned long long* d_anneal_n = nullptr;   // [M] one word per chain: the bits of a_i, then W_i, then N_i (amc_anneal.h)
+    unsigned long long* d_anneal_tiles = nullptr;   // [tiles] the tile sums, then their exclusive prefix
+    unsigned long long* d_anneal_s = nullptr;   // [ANNEAL_S_WORDS] the step's scratch words: maximum, T_w, U
+    unsigned long long* d_anneal_log = nullptr; // [AMC_ANNEAL_MAX_RECORDS][ANNEAL_R_WORDS] the records of the steps
+    int anneal_n = 0;                           // records in the log
+    uint32_t* d_fam = nullptr;                  // [M] family id per chain; allocated exactly while families are on (amc_set_anneal_families)
+    uint32_t* d_fam_alt = nullptr;              // [M] ... and the buffer a step gathers them into
+    unsigned int* d_fam_cnt = nullptr;          // [M] + 3 words: scratch of amc_anneal_family_stats (allocated at its first call)
     double* d_x = nullptr;
     double* d_beta = nullptr;
     uint32_t* d_acc = nullptr;

@@ -21,6 +21,7 @@
 //   amc_estimator.h    K3: pg_estimate_kernel (optionally fused with the sweep and the callback sums)
 //   amc_aux_kernels.h  histogram / energy / conversion kernels, parity-test hooks
 //   amc_exchange.h     replica exchange along a temperature ladder: exchange_kernel, the histogram by rung
+//   amc_anneal.h       population annealing: log-weights, integer weights, the three-launch prefix, the gather, the families
 #pragma once
 
 #include "amc_model.h"
@@ -32,3 +33,4 @@
 #include "amc_estimator.h"
 #include "amc_aux_kernels.h"
 #include "amc_exchange.h"
+#include "amc_anneal.h"

@@ -19,6 +19,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import sharding
+from ._capi import AMC_ANNEAL_MAX_RECORDS
 from .metropolis import Metropolis, _check_rung_sigma
 from .simulation import AriannaAlgorithm, Simulation, _calls
 
@@ -175,6 +176,13 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
         n_respaced = eng.respace_status()[1] if hasattr(eng, "respace_status") else 0
         if n_respaced:                              # the ladder was respaced (ReplicaExchange.respace keeps beta_array current): no field otherwise
             data["n_respaced"] = n_respaced
+    pa = getattr(metropolis, "annealing", None)
+    if pa is not None:                              # population annealing: beta, the step index, the records and the families are state
+        data.update(anneal_beta=float(eng.beta), anneal_step=int(eng.anneal_step), anneal_records=pa.records())
+        eng.set_anneal_records(data["anneal_records"][-AMC_ANNEAL_MAX_RECORDS:])     # (records() drained the engine's log: the run goes on with it)
+        pa._records = list(data["anneal_records"][:-AMC_ANNEAL_MAX_RECORDS])
+        if pa.families:
+            data["families"] = eng.download_families()
     if estimator is not None:
         data["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in estimator.gradients_data])
     os.makedirs(path, exist_ok=True)
@@ -237,6 +245,19 @@ def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
         if "n_respaced" in d:                       # a respaced ladder: the host copy follows the checkpoint's beta, as the engine did
             eng.set_respaced(int(d["n_respaced"]))
             metropolis.chains.beta_array[start:stop] = d["beta"]
+    if "anneal_beta" in d:                          # population annealing: the resumed run anneals on to the same bits
+        rec = np.asarray(d["anneal_records"], dtype=np.uint64).reshape(-1, 8)
+        eng.beta = float(d["anneal_beta"])
+        metropolis.chains.beta = float(d["anneal_beta"])
+        eng.anneal_step = int(d["anneal_step"])
+        eng.set_anneal_records(rec[-AMC_ANNEAL_MAX_RECORDS:])
+        pa = getattr(metropolis, "annealing", None)
+        if pa is not None:
+            pa._records = list(rec[:-AMC_ANNEAL_MAX_RECORDS])
+        if "families" in d:
+            eng.set_anneal_families(True)
+            eng.upload_families(d["families"])
+            metropolis.families_restored = True
     if estimator is not None and "gd" in d:
         from .policy_guided import GradientData
         estimator.gradients_data = [GradientData(float(r[0]), np.array([r[1]]), np.array([r[2]]), np.array([[r[3]]]), int(r[4]))
