@@ -723,6 +723,12 @@ int  amc_selftest_math(int device, int fn, const double *a, const double *b_or_n
  * (DESIGN.md section 3.6); this hook walks EVERY float t in [t_to, t_from] (t_to <= t_from <= 0) on the device and
  * returns the largest relative deviation of that estimate from the arithmetic spec's f64 exp(t). */
 int  amc_selftest_accept_filter(int device, float t_from, float t_to, double *max_rel_err);
+/* The K == 1 harmonic sweeps settle those decisions from y = an estimate of dlogp * log2(e) formed WITHOUT the exact dlogp, from
+ * -beta delta (x + xn) in Float32 under a guard that turns it into NaN where it may not be used (amc_model.h, harmonic_filter_y).
+ * y[i]: that value as a sweep lane forms it for position x[i] and displacement delta[i] in a launch of this beta and sigma
+ * (sigma bounds delta, checked once per launch).  Host buffers. */
+int  amc_selftest_filter_argument(int device, double beta, double sigma, const double *x, const double *delta, float *y,
+                                  int64_t n);
 /* out4[i] = Philox4x32-10(key = seed, counter of draw (pair[i], t[i], draw, stream)). */
 int  amc_selftest_philox(int device, uint64_t seed, const uint64_t *pair, const uint64_t *t,
                          uint32_t draw, uint32_t stream, uint32_t *out4, int64_t n);

@@ -157,6 +157,7 @@ def load() -> C.CDLL:
         "amc_runtime_info": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
         "amc_selftest_math": (C.c_int, [C.c_int, C.c_int, dp, dp, dp, C.c_int64]),
         "amc_selftest_accept_filter": (C.c_int, [C.c_int, C.c_float, C.c_float, dp]),
+        "amc_selftest_filter_argument": (C.c_int, [C.c_int, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_float), C.c_int64]),
         "amc_selftest_philox": (C.c_int, [C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                           C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64]),
         "amc_set_reduce_columns": (C.c_int, [H, C.c_int]),
@@ -1224,6 +1225,17 @@ def selftest_accept_filter(t_from: float, t_to: float, device: int = 0) -> float
     out = C.c_double(0.0)
     _check(load().amc_selftest_accept_filter(int(device), C.c_float(t_from), C.c_float(t_to), C.byref(out)))
     return out.value
+
+
+def selftest_filter_argument(beta: float, sigma: float, x: np.ndarray, delta: np.ndarray, device: int = 0) -> np.ndarray:
+    """y (Float32) of the K == 1 harmonic sweeps' filter argument for positions x and displacements delta, evaluated on the device."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    delta = np.ascontiguousarray(delta, dtype=np.float64)
+    assert x.shape == delta.shape
+    out = np.empty(x.shape, dtype=np.float32)
+    _check(load().amc_selftest_filter_argument(int(device), C.c_double(beta), C.c_double(sigma), _dptr(x), _dptr(delta),
+                                               out.ctypes.data_as(C.POINTER(C.c_float)), x.size))
+    return out
 
 
 def selftest_philox(seed: int, pair: np.ndarray, t: np.ndarray, draw: int, stream: int,

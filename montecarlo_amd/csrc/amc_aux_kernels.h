@@ -173,6 +173,23 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(256) void selftest_filter_kernel
 }
 #endif
 
+// The K == 1 harmonic forms' filter argument (harmonic_filter_y) on caller-supplied positions and displacements: y[i] as the sweep's
+// lanes form it for x[i], delta[i] under the launch constants of (beta, sigma); a lane evaluates elements i and i + 1 as its pair.
+#if AMC_PLAIN_KERNELS
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(256) void selftest_filter_argument_kernel(double beta, double sigma, const double* x, const double* delta,
+                                                                                          float* y, int64_t n)
+{
+    const HarmonicFilter hf = harmonic_filter_setup(beta, sigma);
+    const int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const int64_t j = i + 1 < n ? i + 1 : i;
+    const double x0 = x[i], x1 = x[j], d0 = delta[i], d1 = delta[j];
+    const f32x2 v = harmonic_filter_y(x0, x1, x0 + d0, x1 + d1, d0, d1, hf);
+    y[i] = v.x;
+    y[j] = v.y;
+}
+#endif
+
 // The wave-total primitives (wave_total_i64 by folding, wave_max_u32) on one wave's worth of arbitrary lane values: in is
 // [6][64] 64-bit integers; out[0..5] the six totals through wave_total_i64<6>, out[6..7] two of them through <2>, out[8..10]
 // three through <3>, out[11] one through <1>, out[12] wave_max_u32 of the low words of row 0; ref[0..5] the totals by the plain

@@ -115,6 +115,9 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
         }
     }
     unsigned long long wave_acc = 0;
+    // the fused sweep's filter constants (harmonic, one beta: product_filter), set below once sigma is final (a pending step changes it)
+    constexpr bool SW_UBETA = SWEEP != 0 && !BETA;
+    HarmonicFilter sw_hf = {0.0f, 0.0f};
     // the Box-Muller polynomials' addend coefficients as live 64-bit VGPR values (amc_math.h, MathK): this kernel has no scalar
     // registers to spare, and a literal addend costs a v_mov_b64 per fma here (18 per pair-iteration before)
     const MathK mk = math_k_pinned();
@@ -123,8 +126,9 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
         uint32_t lw = 0;
         // SWEEP == 3: K == 1 with the pool-wide counter only -- no step log
         // (no draws formed ahead; no Float32 tables: the host refuses Float32 parameters here)
-        pair_steps<POT, SWEEP == 2, (SWEEP != 3 ? AMC_LOG_PACKED : AMC_LOG_NONE), true, false>(
-            sw, xv, b0, b1, pair, p, v0, v1, s_tab, s_pick, s_math, sw_sigma1, sw_den1, sw_rden1, sw_logc1, wave_acc, lw, nullptr, mk, sw_th1, nullptr);
+        pair_steps<POT, SWEEP == 2, (SWEEP != 3 ? AMC_LOG_PACKED : AMC_LOG_NONE), true, false, false, SW_UBETA>(
+            sw, xv, b0, b1, pair, p, v0, v1, s_tab, s_pick, s_math, sw_sigma1, sw_den1, sw_rden1, sw_logc1, wave_acc, lw, nullptr, mk, sw_th1, nullptr,
+            0, 0, sw_hf);
         if (SWEEP != 3 && v0) store_log_pair<AMC_LOG_PACKED>(sw, sw.log_pos, p, lw);
     };
     const int64_t n_pairs = (a.n_chains + 1) >> 1;
@@ -358,6 +362,7 @@ void pg_estimate_kernel(const PgArgs a, const SweepArgs sw)
             }
         start_accumulators();
     }
+    if (product_filter<POT, SWEEP == 2, SW_UBETA>()) sw_hf = harmonic_filter_setup((double)a.beta, sw_sigma1);
     __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): first load drained once (see sweep_kernel)
     real2 x_done = {(real_t)0.0, (real_t)0.0};
     int64_t base_done = -1;

@@ -545,7 +545,9 @@ struct Proposal {
     real_t delta, xn, dlogp;
 };
 
-template <int POT>
+// EXACT == false (the harmonic forms whose filter takes the product form, harmonic_filter_y below): delta and xn alone; dlogp is formed
+// by delta_log_target inside the undecided arm, where accept_exact reads it.
+template <int POT, bool EXACT = true>
 __device__ __forceinline__ Proposal propose(real_t x, real_t beta, param_t sigma, param_t z, const double* T)
 {
     Proposal p;
@@ -557,11 +559,25 @@ __device__ __forceinline__ Proposal propose(real_t x, real_t beta, param_t sigma
 #else
     p.delta = (real_t)__builtin_fma(sigma, z, 0.0);
 #endif
+    if (!EXACT) {
+        p.xn = x + p.delta;
+        p.dlogp = (real_t)0.0;
+        return p;
+    }
     const real_t e1 = potential<POT>(x, T);
     p.xn = x + p.delta;
     const real_t e2 = potential<POT>(p.xn, T);
     p.dlogp = ((-e2) * beta) - ((-e1) * beta);
     return p;
+}
+
+// delta_log_target, metropolis.jl:74 + particle_1d.jl:20-22, in propose's operation order: (-e2*b) - (-e1*b)
+template <int POT>
+__device__ __forceinline__ real_t delta_log_target(real_t x, real_t xn, real_t beta, const double* T)
+{
+    const real_t e1 = potential<POT>(x, T);
+    const real_t e2 = potential<POT>(xn, T);
+    return ((-e2) * beta) - ((-e1) * beta);
 }
 
 // The reference-ordered decision.  alpha = min(1, exp(arg)); accept iff alpha > u, with u in [0, 1).  Decided
@@ -659,10 +675,115 @@ __device__ __forceinline__ void accept_filter_f32(float t0, float t1, uint32_t k
     c1.hi = hi.y < kf1;
 }
 
+// The packed form's comparisons from y = the estimate of arg * log2(e) itself: the harmonic potential's product form below arrives
+// with the factor already in its beta (one rounding less than t * LOG2E).
+__device__ __forceinline__ void accept_filter_y(f32x2 y, uint32_t k0, uint32_t k1, FilterCmp& c0, FilterCmp& c1)
+{
+    const float kf0 = (float)k0, kf1 = (float)k1;
+    constexpr float SCALE = 4096.0f, LO = (1.0f - AMC_FILTER_EPS) * SCALE, HI = (1.0f + AMC_FILTER_EPS) * SCALE;
+    const f32x2 ex = {__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
+    const f32x2 lo1 = __builtin_elementwise_fma(ex, f32x2{LO, LO}, f32x2{-1.0f, -1.0f});
+    const f32x2 hi = ex * HI;
+    c0.lo = lo1.x > kf0;
+    c0.hi = hi.x < kf0;
+    c1.lo = lo1.y > kf1;
+    c1.hi = hi.y < kf1;
+}
+
 template <bool PACKED>
 __device__ __forceinline__ void accept_filter(real_t dlogp0, real_t dlogp1, uint32_t k0, uint32_t k1, FilterCmp& c0, FilterCmp& c1)
 {
     accept_filter_f32<PACKED>((float)dlogp0, (float)dlogp1, k0, k1, c0, c1);
+}
+
+// The harmonic potential's filter argument without the exact dlogp (Float64 state and parameters, one beta for the launch).
+// e2 - e1 = xn^2 - x^2 = (xn - x)(xn + x), and xn = fl(x + delta), so dlogp ~ -beta delta (x + xn): one f64 add, two conversions and
+// Float32 products per chain instead of the five f64 operations of delta_log_target, which only the undecided arm still forms.
+//   s = fl(xn + x) (f64);  sf = RN_f32(s), df = RN_f32(delta);  w = RN(nbl df);  y = RN(w sf + g)          (one fma)
+// nbl = RN_f32(-(beta log2e)) is wave-uniform (harmonic_filter_setup: the factor log2e rides in it, so y enters accept_filter_y as it
+// is), and g is the guard: +-0 inside it, NaN outside (below).  With D = the reference-ordered dlogp that accept_exact reads and
+// t = y ln 2, the three ranges of the filter above hold with t in the place of RN_f32(dlogp) once |t - D| is accounted for:
+//
+// (a) the Float32 roundings.  nbl, df, sf, w, y: five roundings, |t - (-beta delta s)| <= 5.01 2^-24 |beta delta s| (nbl's f64
+//     product and the constant add 2^-52).  They take the place of the lines "float(dlogp)" and "* log2e" of the budget above:
+//     5.01 2^-24 * 17.01 = 5.1e-6 where there were 2.4e-6.  No product overflows inside the guard (|w| < 2^28, |w sf| is the estimate
+//     itself), and a subnormal nbl, df, sf, w or y moves t by less than 2^-34 whether the mode keeps or flushes it (each is at most
+//     2^-126 times a cofactor below 2^92, the guard's L^2).
+// (b) D against -beta delta s.  With m = max(|x|, |xn|) and the roundings e_i, |e_i| <= 2^-53, of x x, xn xn, the two products with
+//     beta and the difference:  |D + beta (xn^2 - x^2)| <= 2^-53 (2 beta x^2 + 2 beta xn^2 + |D|) (1 + 2^-51);  xn - x = delta + r,
+//     |r| <= 2^-53 |xn|, and xn + x = s (1 + e):  |beta (xn^2 - x^2) - beta delta s| <= 2^-53 beta (|xn| |s| + |delta| |s|) (1 + 2^-51).
+//     With |s| <= 2 m:  |D + beta delta s| <= 2^-53 (6.01 beta m^2 + 2.01 |D|).  Unbounded in m, so the argument is used only where
+//     beta m^2 < 2^29 (the guard):  term (b) <= 6.1 2^-24 = 3.7e-7 for |D| <= 17.01 -- measured 2.7e-8 at most
+//     (tests/test_filter_argument_bound.py: 1e6 random and the adversarial cases) -- under its share 2^-21 = 4.8e-7.
+// (|t - D| as a whole: 3.3e-6 measured there, 5.5e-6 derived.)  The budget of -17 <= D <= 0 becomes 5.1e-6 + 3.7e-7 + 4e-14 + 5e-7 + 4e-16 + 6e-8 < 6.1e-6: AMC_FILTER_EPS = 2^-16 = 1.53e-5 leaves a
+// factor 2.5 and stays as it is (so does the undecided rate, u's cell against the same interval: ~1.2e-4 per chain-step).
+// D > 0:  -beta delta s >= D - 3.7e-7 - 2^-52 D and t >= that (1 -+ 3e-7), so t > -4e-7, y > -6e-7, ex >= 1 - 6e-7 and
+//     hi >= 4096 (1 + 2^-16) (1 - 7e-7) > 4095 >= k: no reject is claimed; accept_exact accepts, so any claimed accept is right.
+// D < -17:  t <= -17 (1 - 3e-7) + 3.7e-7 < -16.99, y < -24.5: the bounds of that range hold as they stand (no accept claimed, a reject
+//     for k >= 1 only), also where the products overflow to -Inf.
+//
+// The guard.  beta m^2 < 2^29 is enforced as |s| < L and |delta| < L with L = 2^l, l = (28 - eb) >> 1, where 2^eb <= beta < 2^(eb + 1)
+// (eb taken as -64 below that, so l <= 46 and beta L^2 <= 2^29 all the same):  xn + x = s / (1 + e) and xn - x = delta + r give
+// m <= (|s| + |delta|) / 2 (1 + 2^-51) < L (1 + 2^-51), beta m^2 < 2^(eb + 1 + 2 l) (1 + 2^-50) <= 2^29 (1 + 2^-50).  At the benchmark's
+// beta = 2, L = 2^13; at beta = 2^10, L = 2^9; at beta = 2^-20, L = 2^24 -- four thousand standard deviations of the stationary law in
+// each case.  |s| < L costs two Float32 operations: q = sf 2^(128 - l) is exact and finite exactly when |sf| < 2^l (the largest Float32
+// below 2^l times a power of two is the largest finite one), which implies |s| < 2^l; g = q * 0 is then +-0, and NaN when q is +-Inf or
+// NaN.  |delta| < L: sigma is wave-uniform in these kernels (K == 1) and |delta| <= 8.6 sigma < 2^(es + 5) (2^es <= sigma < 2^(es + 1);
+// |z| < 8.6), so harmonic_filter_setup compares es + 5 with l once per launch, on the sigma the launch proposes with (the fused PGMC
+// time step: after a pending learning step has been applied).  A NaN g makes y NaN, no comparison of accept_filter_y holds, and the wave
+// takes accept_exact.  A launch whose beta or sigma is outside these bounds gets nbl = NaN: every wave of it takes accept_exact, which is
+// AMC_EXACT_ACCEPT's arithmetic -- right, and slower; it concerns pools that accept next to nothing (|delta| beyond four thousand
+// standard deviations) and beta >= 2^25.  Case by case:
+//   x = +-Inf      s = +-Inf or NaN, q = +-Inf or NaN, g = NaN                                       undecided
+//   x = NaN        s = NaN                                                                           undecided
+//   |x| >= L / 2 or so (|s| >= L)                                                                    undecided
+//   beta = Inf, NaN, negative (-0 too) or >= 2^25            nbl = NaN                               undecided (the whole launch)
+//   beta = 0       nbl = -0, w = -+0, y = +-0, ex = 1: an accept for k <= 4094; D = (-0) - (-0) = 0, accept_exact accepts       decided
+//   beta < 2^-126  nbl subnormal or zero: line (a)                                                    decided inside the budget
+//   delta = 0      xn = x, df = +-0, y = +-0: as beta = 0; D = +0                                     decided
+//   subnormal delta   df subnormal or zero, |y| < 2^-100: as delta = 0, and |D| <= beta |delta| |s| (1 + 2^-50) + (b), inside the budget  decided
+//   sigma = Inf or NaN            es = 1024: nbl = NaN                                                  undecided (the whole launch)
+//   x = +-0, subnormal x          nothing special: s = delta or next to it                             decided
+struct HarmonicFilter {
+    float nbl, cs;                // wave-uniform: RN_f32(-(beta log2e)), or NaN (the launch decides by accept_exact); 2^(128 - l)
+};
+
+// Once per launch, on wave-uniform values: the launch's beta and the sigma of its only move.
+__device__ __forceinline__ HarmonicFilter harmonic_filter_setup(double beta, double sigma)
+{
+    const uint32_t bh = (uint32_t)((uint64_t)__double_as_longlong(beta) >> 32), sh = (uint32_t)((uint64_t)__double_as_longlong(sigma) >> 32);
+    const int eb = (int)((bh >> 20) & 0x7FFu) - 1023, es = (int)((sh >> 20) & 0x7FFu) - 1023;
+    const int l = (28 - (eb < -64 ? -64 : eb)) >> 1;
+    const bool ok = (bh >> 31) == 0u && eb <= 24 && es + 5 <= l;      // 0 <= beta < 2^25 (l >= 2), |delta| < 2^l
+    const float nbl = ok ? (float)(-(beta * 0x1.71547652b82fep+0)) : __builtin_nanf("");
+    HarmonicFilter hf;
+    hf.nbl = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(nbl)));
+    hf.cs = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(255 - l) << 23)));
+    return hf;
+}
+
+// y of both chains of a pair, on packed operations as in accept_filter_f32 (K == 1 kernels).
+__device__ __forceinline__ f32x2 harmonic_filter_y(double x0, double x1, double xn0, double xn1, double d0, double d1, const HarmonicFilter& hf)
+{
+    const f32x2 sf = {(float)(xn0 + x0), (float)(xn1 + x1)};
+    const f32x2 df = {(float)d0, (float)d1};
+    const f32x2 g = (sf * hf.cs) * f32x2{0.0f, 0.0f};
+    return __builtin_elementwise_fma(df * hf.nbl, sf, g);
+}
+
+// Which forms take it: the harmonic potential with Float64 state and parameters and the built-in proposal, in K == 1 launches with one
+// beta.  Everything else keeps the exact dlogp on the hot path: the double well, script-defined potentials and proposals, Float32 state or
+// parameters, a beta array (per-chain and per-rung betas have no wave-uniform bound) -- and the K > 1 kernels, where sigma is the lane's
+// and delta needs a bound of its own: with those two more operations per chain the priced loop of the fused PGMC time step did not
+// shorten (357 -> 362 instructions, 692 -> 691 ns per wave-trip) and the K = 2 multi-step sweep went from 72 to 73 VGPRs, a wave per SIMD.
+template <int POT, bool MULTI, bool UBETA>
+constexpr bool product_filter()
+{
+#if defined(AMC_STATE_F32) || defined(AMC_PARAM_F32) || defined(AMC_USER_SCALE) || defined(AMC_USER_LOGQ)
+    return false;
+#else
+    return POT == POT_HARMONIC && UBETA && !MULTI;
+#endif
 }
 
 // The same filter for a decision whose ARGUMENT is known in full -- the script-defined proposals below form arg = (dlogp + logq_b) -
@@ -784,12 +905,14 @@ struct MoveExact {
 // to 2^-12, and the decision is settled without the second Philox call unless exp(arg) falls into u's cell (~1.2e-4
 // per chain-step, ~1.5 % of wave-steps).  `pu` / `have_pu` (wave-uniform): the accept draw, if the move pick of this
 // step already needed it (pair_steps).
-template <int POT, bool MULTI>
+// PRODUCT_FILTER (product_filter above): the filter reads harmonic_filter_y with the launch's `hf`, and dlogp is formed in the undecided arm.
+template <int POT, bool MULTI, bool PRODUCT_FILTER>
 __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t sg0, param_t sg1, int k0, int k1,
                                         const double* s_tab, MoveExact m1, param_t z0, param_t z1, u32x4 pn, u32x4 pu,
                                         bool have_pu, u32x4 accept_ctr, uint32_t key0, uint32_t key1, const double* T,
                                         unsigned long long force_mask, uint32_t& acc_bits, unsigned long long& m0,
-                                        unsigned long long& m1_out, const UserTheta& th1)
+                                        unsigned long long& m1_out, const UserTheta& th1,
+                                        const HarmonicFilter& hf)
 {
     const uint32_t a0_12 = spare_accept12(pn, 0), a1_12 = spare_accept12(pn, 1);
 #if defined(AMC_USER_SCALE) || defined(AMC_USER_LOGQ)
@@ -833,9 +956,11 @@ __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t
         return;
     }
 #endif
-    const Proposal p0 = propose<POT>(xv.x, b0, sg0, z0, T), p1 = propose<POT>(xv.y, b1, sg1, z1, T);
+    Proposal p0 = propose<POT, !PRODUCT_FILTER>(xv.x, b0, sg0, z0, T), p1 = propose<POT, !PRODUCT_FILTER>(xv.y, b1, sg1, z1, T);
+    const real_t x0 = xv.x, x1 = xv.y;
     FilterCmp c0, c1;
-    accept_filter<!MULTI>(p0.dlogp, p1.dlogp, a0_12, a1_12, c0, c1);
+    if (!PRODUCT_FILTER) accept_filter<!MULTI>(p0.dlogp, p1.dlogp, a0_12, a1_12, c0, c1);
+    else accept_filter_y(harmonic_filter_y(x0, x1, p0.xn, p1.xn, p0.delta, p1.delta, hf), a0_12, a1_12, c0, c1);
 #define AMC_B(c) __builtin_amdgcn_ballot_w64(c)
     const unsigned long long acc0 = AMC_B(c0.lo), rej0 = AMC_B(c0.hi);
     const unsigned long long acc1 = AMC_B(c1.lo), rej1 = AMC_B(c1.hi);
@@ -868,6 +993,10 @@ __device__ __forceinline__ void mh_pair(real2& xv, real_t b0, real_t b1, param_t
             // (rd: nobody reads it under AMC_PARAM_F32, whose Float32 quotient is an IEEE division -- accept_exact)
             e0.dn = mt_den(s_tab, k0); e0.lc = s_tab[MT_LOGC * AMC_MAX_MOVES + k0]; e0.rd = s_tab[MT_RDEN * AMC_MAX_MOVES + k0];
             e1.dn = mt_den(s_tab, k1); e1.lc = s_tab[MT_LOGC * AMC_MAX_MOVES + k1]; e1.rd = s_tab[MT_RDEN * AMC_MAX_MOVES + k1];
+        }
+        if (PRODUCT_FILTER) {          // delta_log_target in the reference's operation order, where it is read
+            p0.dlogp = delta_log_target<POT>(x0, p0.xn, b0, T);
+            p1.dlogp = delta_log_target<POT>(x1, p1.xn, b1, T);
         }
         const bool a0 = accept_exact(p0.delta, p0.dlogp, e0.dn, e0.rd, e0.lc, uniform_accept(a0_12, pu.x, pu.y), T);
         const bool a1 = accept_exact(p1.delta, p1.dlogp, e1.dn, e1.rd, e1.lc, uniform_accept(a1_12, pu.z, pu.w), T);

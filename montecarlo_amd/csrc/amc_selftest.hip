@@ -1,5 +1,5 @@
 // amc_selftest.hip -- parity-test hooks of the C ABI (amc_selftest_*): the device's arithmetic primitives, Philox words, the accept
-// filter's float estimate and the wave totals, evaluated on the device for the tests to compare with the oracle.
+// filter's float estimate, the harmonic forms' filter argument and the wave totals, evaluated on the device for the tests to compare with the oracle.
 #define AMC_KERNEL_LINKAGE static      // this object's own copies of the selftest kernels; none of the others is emitted
 #include "amc_internal.h"
 
@@ -46,6 +46,29 @@ int amc_selftest_accept_filter(int device, float t_from, float t_to, double* max
     (void)hipFree(d_max);
     std::memcpy(max_rel_err, &bits, sizeof(double));
     return AMC_OK;
+}
+
+int amc_selftest_filter_argument(int device, double beta, double sigma, const double* x, const double* delta, float* y, int64_t n)
+{
+    if (!x || !delta || !y || n < 0) return fail(AMC_ERR_BAD_ARG, "amc_selftest_filter_argument: bad argument");
+    if (n == 0) return AMC_OK;
+    AMC_HIP(hipSetDevice(device));
+    double *dx = nullptr, *dd = nullptr;
+    float* dy = nullptr;
+    const auto run = [&]() -> int {      // the buffers are freed below whichever call fails
+        AMC_HIP(hipMalloc(&dx, (size_t)n * sizeof(double)));
+        AMC_HIP(hipMalloc(&dd, (size_t)n * sizeof(double)));
+        AMC_HIP(hipMalloc(&dy, (size_t)n * sizeof(float)));
+        AMC_HIP(hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        AMC_HIP(hipMemcpy(dd, delta, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(amc::selftest_filter_argument_kernel, dim3((unsigned)(((n + 1) / 2 + 255) / 256)), dim3(256), 0, 0, beta, sigma, dx, dd, dy, n);
+        AMC_HIP(hipGetLastError());
+        AMC_HIP(hipMemcpy(y, dy, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        return AMC_OK;
+    };
+    const int rc = run();
+    (void)hipFree(dx); (void)hipFree(dd); (void)hipFree(dy);
+    return rc;
 }
 
 int amc_selftest_philox(int device, uint64_t seed, const uint64_t* pair, const uint64_t* t, uint32_t draw,

@@ -121,14 +121,16 @@ __device__ __forceinline__ void store_log_pair(const SweepArgs& a, int row, int6
 // with x), multi-step launches store one word per step right away.
 // RUNG: the widths come from the rung table's entry k * n_rungs + r (staged in s_tab's rows where a K > 1 sweep keeps its pool's):
 // rung0 / rung1 are the rungs of the lane's two chains.  The step log keeps the move k.
-template <int POT, bool MULTI, int LOG, bool SINGLE, bool PRE, bool RUNG = false>
+// UBETA: the launch has one beta (no beta array) and `hf` holds its harmonic_filter_setup: the K == 1 harmonic forms then settle the accept
+// decision from the product form of the filter argument (product_filter, amc_model.h).
+template <int POT, bool MULTI, int LOG, bool SINGLE, bool PRE, bool RUNG = false, bool UBETA = false>
 __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t b0, real_t b1, uint64_t pair,
                                            int64_t p, bool v0, bool v1, const double* s_tab, const uint8_t* s_pick,
                                            const double* s_math, param_t sigma1, param_t den1, double rden1, double logc1,
                                            unsigned long long& wave_acc, uint32_t& log_word,
                                            const StepDraws* pre, const MathK& mk, const UserTheta& th1,
                                            const float2* s_mathf,      // AMC_PARAM_F32: the Float32 tables (box_muller_f32), else nullptr
-                                           int rung0 = 0, int rung1 = 0)
+                                           int rung0, int rung1, const HarmonicFilter& hf)
 {
     static_assert(!PRE || SINGLE, "pre-formed draws cover exactly one step");
     const int K = a.n_moves;
@@ -178,8 +180,9 @@ __device__ __forceinline__ void pair_steps(const SweepArgs& a, real2& xv, real_t
 #endif
         unsigned long long m0, m1m;
         uint32_t acc_bits;
-        mh_pair<POT, MULTI || RUNG>(xv, b0, b1, sg0, sg1, e0, e1, s_tab, m1, z0, z1, dr.normal, pu, have_pu, accept_ctr, a.key0,
-                                    a.key1, s_math, force_mask, acc_bits, m0, m1m, th1);
+        mh_pair<POT, MULTI || RUNG, product_filter<POT, MULTI || RUNG, UBETA && !RUNG>()>(
+            xv, b0, b1, sg0, sg1, e0, e1, s_tab, m1, z0, z1, dr.normal, pu, have_pu, accept_ctr, a.key0, a.key1, s_math, force_mask, acc_bits, m0,
+            m1m, th1, hf);
         // K == 1: wavefront-ballot accept mask -> one scalar popcount per chain slot (pool-wide total)
         if (!MULTI) wave_acc += __popcll(m0 & __builtin_amdgcn_ballot_w64(v0)) + __popcll(m1m & __builtin_amdgcn_ballot_w64(v1));
         if (LOG) {
@@ -256,6 +259,10 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
     const param_t den1 = (param_t)a.ptab[PT_DEN * AMC_MAX_MOVES];
     const double logc1 = a.ptab[PT_LOGC * AMC_MAX_MOVES];
     const double rden1 = a.ptab[PT_RDEN * AMC_MAX_MOVES];
+    // the K == 1 harmonic forms' filter constants (launches with one beta): wave-uniform, from beta and the pool's only sigma
+    constexpr bool UBETA = !BETA && !RUNG;
+    HarmonicFilter hf = {0.0f, 0.0f};
+    if (product_filter<POT, MULTI, UBETA>()) hf = harmonic_filter_setup(a.beta, (double)sigma1);
     UserTheta th1 = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #ifdef AMC_USER_LOGQ
     if (!MULTI) th1 = user_theta_uniform(a.ptab, 0);
@@ -340,9 +347,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
         }
         const StepDraws dr = dr_nxt;
         uint32_t lw = 0;
-        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD, RUNG>(a, xv, b0, b1, pair, base + threadIdx.x, true, true, s_tab, s_pick, s_math,
-                                                         sigma1, den1, rden1, logc1, wave_acc, lw, &dr, math_k_literal(), th1, s_mathf,
-                                                         (int)rung, rung_next(rung));
+        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD, RUNG, UBETA>(a, xv, b0, b1, pair, base + threadIdx.x, true, true, s_tab, s_pick, s_math,
+                                                                sigma1, den1, rden1, logc1, wave_acc, lw, &dr, math_k_literal(), th1, s_mathf,
+                                                                (int)rung, rung_next(rung), hf);
         pair += (uint64_t)stride;
         if (RUNG) {
             rung += rung_step;
@@ -367,9 +374,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void sweep_kernel(const SweepArgs a)
             if (LOG && SINGLE) store_log_pair<LOG>(a, a.log_pos, base_done + threadIdx.x, lw_done);
         }
         uint32_t lw = 0;
-        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD, RUNG>(a, xv, b_nxt.x, b_nxt.y, v0 ? pair : a.pair0, p, v0, v1,
-                                                         s_tab, s_pick, s_math, sigma1, den1, rden1, logc1, wave_acc, lw, &dr_nxt, math_k_literal(), th1, s_mathf,
-                                                         (int)rung, rung_next(rung));
+        pair_steps<POT, MULTI, LOG, SINGLE, AHEAD, RUNG, UBETA>(a, xv, b_nxt.x, b_nxt.y, v0 ? pair : a.pair0, p, v0, v1,
+                                                                s_tab, s_pick, s_math, sigma1, den1, rden1, logc1, wave_acc, lw, &dr_nxt, math_k_literal(), th1, s_mathf,
+                                                                (int)rung, rung_next(rung), hf);
         // a lone last chain (odd n_chains) writes its whole pair (x and log): the odd slot is padding
         if (v0) {
             store_pair_block_writethrough(a.x + 2 * base, xv);
