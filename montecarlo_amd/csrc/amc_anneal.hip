@@ -10,42 +10,31 @@ static const size_t ANNEAL_LOG_BYTES = (size_t)AMC_ANNEAL_MAX_RECORDS * amc::ANN
 
 static int64_t anneal_tiles(const amc_handle* h) { return (h->M + amc::ANNEAL_TILE - 1) / amc::ANNEAL_TILE; }
 
-static int anneal_log_room(amc_handle* h)
-{
-    if (h->d_anneal_log) return AMC_OK;
-    AMC_HIP(hipMalloc(&h->d_anneal_log, ANNEAL_LOG_BYTES));
-    AMC_HIP(hipMemsetAsync(h->d_anneal_log, 0, ANNEAL_LOG_BYTES, h->stream));
-    return AMC_OK;
-}
-
 // The buffers of the step itself: the second position buffer (padded and zeroed like the first), the word per chain that holds a, W
 // and N in turn, the tile sums, the scratch words.
 static int anneal_room(amc_handle* h)
 {
-    if (!h->d_x_alt) {
-        AMC_HIP(hipMalloc(&h->d_x_alt, (size_t)h->M_pad * sizeof(double)));
-        AMC_HIP(hipMemsetAsync(h->d_x_alt, 0, (size_t)h->M_pad * sizeof(double), h->stream));
+    if (!h->ann.d_x_alt) {
+        AMC_HIP(hipMalloc(&h->ann.d_x_alt, (size_t)h->M_pad * sizeof(double)));
+        AMC_HIP(hipMemsetAsync(h->ann.d_x_alt, 0, (size_t)h->M_pad * sizeof(double), h->stream));
     }
-    if (!h->d_anneal_n) AMC_HIP(hipMalloc(&h->d_anneal_n, (size_t)h->M * sizeof(unsigned long long)));
-    if (!h->d_anneal_tiles) AMC_HIP(hipMalloc(&h->d_anneal_tiles, (size_t)anneal_tiles(h) * sizeof(unsigned long long)));
-    if (!h->d_anneal_s) AMC_HIP(hipMalloc(&h->d_anneal_s, amc::ANNEAL_S_WORDS * sizeof(unsigned long long)));
-    return anneal_log_room(h);
+    if (!h->ann.d_anneal_n) AMC_HIP(hipMalloc(&h->ann.d_anneal_n, (size_t)h->M * sizeof(unsigned long long)));
+    if (!h->ann.d_anneal_tiles) AMC_HIP(hipMalloc(&h->ann.d_anneal_tiles, (size_t)anneal_tiles(h) * sizeof(unsigned long long)));
+    if (!h->ann.d_anneal_s) AMC_HIP(hipMalloc(&h->ann.d_anneal_s, amc::ANNEAL_S_WORDS * sizeof(unsigned long long)));
+    return zeroed_words(h, &h->ann.d_anneal_log, ANNEAL_LOG_BYTES);
 }
 
 static int families_off(amc_handle* h)
 {
-    if (!h->d_fam) return AMC_OK;
+    if (!h->ann.d_fam) return AMC_OK;
     AMC_HIP(hipStreamSynchronize(h->stream));      // launches queued on the stream may still use them
-    (void)hipFree(h->d_fam);
-    (void)hipFree(h->d_fam_alt);
-    (void)hipFree(h->d_fam_cnt);
-    h->d_fam = h->d_fam_alt = nullptr;
-    h->d_fam_cnt = nullptr;
+    (void)hipFree(h->ann.d_fam);
+    (void)hipFree(h->ann.d_fam_alt);
+    (void)hipFree(h->ann.d_fam_cnt);
+    h->ann.d_fam = h->ann.d_fam_alt = nullptr;
+    h->ann.d_fam_cnt = nullptr;
     return AMC_OK;
 }
-
-#define AMC_NEED_FAMILIES(who)                                                                                              \
-    if (!h->d_fam) return fail(AMC_ERR_STATE, who ": families are off (amc_set_anneal_families)")
 
 extern "C" {
 
@@ -53,46 +42,45 @@ int amc_anneal(amc_handle* h, double beta_new)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_anneal: NULL handle");
     if (h->beta_arr) return fail(AMC_ERR_STATE, "amc_anneal: the handle has a per-chain beta array; population annealing cools one shared beta");
-    if (h->n_rungs) return fail(AMC_ERR_STATE, "amc_anneal: the handle has a ladder (amc_set_ladder)");
+    if (h->lad.n_rungs) return fail(AMC_ERR_STATE, "amc_anneal: the handle has a ladder (amc_set_ladder)");
     if (h->offset != 0 || h->M != h->M_global)
         return fail(AMC_ERR_STATE, "amc_anneal: the handle holds chains [%lld, %lld) of %lld; resampling needs the whole ensemble on one handle",
                     (long long)h->offset, (long long)(h->offset + h->M), (long long)h->M_global);
     if (!std::isfinite(beta_new)) return fail(AMC_ERR_BAD_ARG, "amc_anneal: beta_new = %g is not finite", beta_new);
     if (h->M >> 33) return fail(AMC_ERR_BAD_ARG, "amc_anneal: n_chains = %lld, the total weight needs n_chains < 2^33", (long long)h->M);
-    if (h->anneal_n >= AMC_ANNEAL_MAX_RECORDS)
+    if (h->ann.anneal_n >= AMC_ANNEAL_MAX_RECORDS)
         return fail(AMC_ERR_STATE, "amc_anneal: the record log is full (%d records; amc_anneal_fetch with reset empties it)", AMC_ANNEAL_MAX_RECORDS);
-    if (h->t_a >> 48) return fail(AMC_ERR_STATE, "amc_anneal: the annealing step index has reached 2^48");
+    if (h->ann.t_a >> 48) return fail(AMC_ERR_STATE, "amc_anneal: the annealing step index has reached 2^48");
     AMC_HIP(hipSetDevice(h->device));
     // (what an exchange step does before it launches: a learning step left pending by a fused time step is taken now; reductions in
     // flight were queued on the same stream and have read x before the buffers change places)
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    { const int rc = anneal_room(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
+    AMC_TRY(anneal_room(h));
     const int64_t n_tiles = anneal_tiles(h);
     const int grid_chains = grid_for(h, h->M), grid_tiles = grid_for(h, n_tiles * AMC_BLOCK);
-    unsigned long long* rec = h->d_anneal_log + (size_t)h->anneal_n * amc::ANNEAL_R_WORDS;
-    AMC_HIP(hipMemsetAsync(h->d_anneal_s, 0, amc::ANNEAL_S_WORDS * sizeof(unsigned long long), h->stream));
+    unsigned long long* rec = h->ann.d_anneal_log + (size_t)h->ann.anneal_n * amc::ANNEAL_R_WORDS;
+    AMC_HIP(hipMemsetAsync(h->ann.d_anneal_s, 0, amc::ANNEAL_S_WORDS * sizeof(unsigned long long), h->stream));
     {
         amc::AnnealLogwArgs a;
         a.x = h->d_x;
-        a.a = h->d_anneal_n;
-        a.scratch = h->d_anneal_s;
+        a.a = h->ann.d_anneal_n;
+        a.scratch = h->ann.d_anneal_s;
         a.n_chains = h->M;
         a.delta = h->f32 ? (double)((float)beta_new - (float)h->beta) : beta_new - h->beta;
         void* params[] = {&a};
-        const int rc = launch_by_potential(h, "amc::anneal_logw_kernel", (const void*)amc::anneal_logw_kernel<amc::POT_DOUBLE_WELL>,
-                                           (const void*)amc::anneal_logw_kernel<amc::POT_HARMONIC>, grid_chains, params);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(launch_by_potential(h, "amc::anneal_logw_kernel", (const void*)amc::anneal_logw_kernel<amc::POT_DOUBLE_WELL>,
+                                    (const void*)amc::anneal_logw_kernel<amc::POT_HARMONIC>, grid_chains, params));
     }
-    hipLaunchKernelGGL(amc::anneal_weights_kernel, dim3(grid_tiles), dim3(AMC_BLOCK), 0, h->stream, h->d_anneal_n, h->M, n_tiles,
-                       (const unsigned long long*)h->d_anneal_s, h->d_anneal_tiles);
+    hipLaunchKernelGGL(amc::anneal_weights_kernel, dim3(grid_tiles), dim3(AMC_BLOCK), 0, h->stream, h->ann.d_anneal_n, h->M, n_tiles,
+                       (const unsigned long long*)h->ann.d_anneal_s, h->ann.d_anneal_tiles);
     AMC_HIP(hipGetLastError());
     {
         amc::AnnealTotalArgs a;
-        a.tile_sums = h->d_anneal_tiles;
-        a.scratch = h->d_anneal_s;
+        a.tile_sums = h->ann.d_anneal_tiles;
+        a.scratch = h->ann.d_anneal_s;
         a.rec = rec;
         a.n_tiles = n_tiles;
-        a.t_a = h->t_a;
+        a.t_a = h->ann.t_a;
         std::memcpy(&a.beta_from, &h->beta, sizeof(double));
         std::memcpy(&a.beta_to, &beta_new, sizeof(double));
         a.key0 = (uint32_t)h->seed;
@@ -100,36 +88,35 @@ int amc_anneal(amc_handle* h, double beta_new)
         hipLaunchKernelGGL(amc::anneal_total_kernel, dim3(1), dim3(AMC_BLOCK), 0, h->stream, a);
         AMC_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(amc::anneal_prefix_kernel, dim3(grid_tiles), dim3(AMC_BLOCK), 0, h->stream, h->d_anneal_n, h->M, n_tiles,
-                       (const unsigned long long*)h->d_anneal_s, (const unsigned long long*)h->d_anneal_tiles, rec);
+    hipLaunchKernelGGL(amc::anneal_prefix_kernel, dim3(grid_tiles), dim3(AMC_BLOCK), 0, h->stream, h->ann.d_anneal_n, h->M, n_tiles,
+                       (const unsigned long long*)h->ann.d_anneal_s, (const unsigned long long*)h->ann.d_anneal_tiles, rec);
     AMC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(amc::anneal_gather_kernel, dim3(grid_chains), dim3(AMC_BLOCK), 0, h->stream, (const void*)h->d_x, (void*)h->d_x_alt, h->f32 ? 1 : 0,
-                       (const uint32_t*)h->d_fam, h->d_fam_alt, (const unsigned long long*)h->d_anneal_n, h->M, (const unsigned long long*)h->d_anneal_s);
+    hipLaunchKernelGGL(amc::anneal_gather_kernel, dim3(grid_chains), dim3(AMC_BLOCK), 0, h->stream, (const void*)h->d_x, (void*)h->ann.d_x_alt, h->f32 ? 1 : 0,
+                       (const uint32_t*)h->ann.d_fam, h->ann.d_fam_alt, (const unsigned long long*)h->ann.d_anneal_n, h->M, (const unsigned long long*)h->ann.d_anneal_s);
     AMC_HIP(hipGetLastError());
-    std::swap(h->d_x, h->d_x_alt);
-    if (h->d_fam) std::swap(h->d_fam, h->d_fam_alt);
+    std::swap(h->d_x, h->ann.d_x_alt);
+    if (h->ann.d_fam) std::swap(h->ann.d_fam, h->ann.d_fam_alt);
     h->beta = beta_new;          // the host field: in force for every launch queued from now on (nothing on the device is derived from it)
-    h->t_a += 1;
-    h->anneal_n += 1;
+    h->ann.t_a += 1;
+    h->ann.anneal_n += 1;
     return AMC_OK;
 }
 
 int amc_anneal_fetch(amc_handle* h, uint64_t* records, int capacity, int* n, int reset)
 {
     if (!h || !n) return fail(AMC_ERR_BAD_ARG, "amc_anneal_fetch: NULL argument");
-    *n = h->anneal_n;
+    *n = h->ann.anneal_n;
     if (!records) {              // the count alone
-        if (reset) h->anneal_n = 0;
+        if (reset) h->ann.anneal_n = 0;
         return AMC_OK;
     }
-    if (capacity < h->anneal_n)
-        return fail(AMC_ERR_BAD_ARG, "amc_anneal_fetch: capacity = %d, the log holds %d records", capacity, h->anneal_n);
+    if (capacity < h->ann.anneal_n)
+        return fail(AMC_ERR_BAD_ARG, "amc_anneal_fetch: capacity = %d, the log holds %d records", capacity, h->ann.anneal_n);
     AMC_HIP(hipSetDevice(h->device));
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "records are copied as they are");
-    if (h->anneal_n)
-        AMC_HIP(hipMemcpyAsync(records, h->d_anneal_log, (size_t)h->anneal_n * amc::ANNEAL_R_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
-    if (reset) h->anneal_n = 0;
+    // (an empty log copies nothing and still waits)
+    AMC_TRY(copy_to_host_sync(h, records, h->ann.anneal_n ? h->ann.d_anneal_log : nullptr, (size_t)h->ann.anneal_n * amc::ANNEAL_R_WORDS * sizeof(uint64_t)));
+    if (reset) h->ann.anneal_n = 0;
     return AMC_OK;
 }
 
@@ -138,21 +125,20 @@ int amc_set_anneal_records(amc_handle* h, const uint64_t* records, int n)
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_records: NULL handle");
     if (n < 0 || n > AMC_ANNEAL_MAX_RECORDS) return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_records: n = %d must lie in [0, %d]", n, AMC_ANNEAL_MAX_RECORDS);
     if (!records || n == 0) {
-        h->anneal_n = 0;
+        h->ann.anneal_n = 0;
         return AMC_OK;
     }
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = anneal_log_room(h); if (rc != AMC_OK) return rc; }
-    AMC_HIP(hipMemcpyAsync(h->d_anneal_log, records, (size_t)n * amc::ANNEAL_R_WORDS * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `records` is only valid during the call
-    h->anneal_n = n;
+    AMC_TRY(zeroed_words(h, &h->ann.d_anneal_log, ANNEAL_LOG_BYTES));
+    AMC_TRY(copy_to_device_sync(h, h->ann.d_anneal_log, records, (size_t)n * amc::ANNEAL_R_WORDS * sizeof(uint64_t)));      // `records` is only valid during the call
+    h->ann.anneal_n = n;
     return AMC_OK;
 }
 
 int amc_get_anneal_step(amc_handle* h, uint64_t* t)
 {
     if (!h || !t) return fail(AMC_ERR_BAD_ARG, "amc_get_anneal_step: NULL argument");
-    *t = h->t_a;
+    *t = h->ann.t_a;
     return AMC_OK;
 }
 
@@ -160,7 +146,7 @@ int amc_set_anneal_step(amc_handle* h, uint64_t t)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_step: NULL handle");
     if (t >> 48) return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_step: step index must fit 48 bits");
-    h->t_a = t;
+    h->ann.t_a = t;
     return AMC_OK;
 }
 
@@ -186,16 +172,16 @@ int amc_set_anneal_families(amc_handle* h, int on)
     AMC_HIP(hipSetDevice(h->device));
     if (!on) return families_off(h);
     if (h->M > 0xFFFFFFFFll) return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_families: n_chains = %lld, a family id holds 32 bits", (long long)h->M);
-    if (!h->d_fam) {
-        AMC_HIP(hipMalloc(&h->d_fam, (size_t)h->M * sizeof(uint32_t)));
-        const hipError_t e = hipMalloc(&h->d_fam_alt, (size_t)h->M * sizeof(uint32_t));
+    if (!h->ann.d_fam) {
+        AMC_HIP(hipMalloc(&h->ann.d_fam, (size_t)h->M * sizeof(uint32_t)));
+        const hipError_t e = hipMalloc(&h->ann.d_fam_alt, (size_t)h->M * sizeof(uint32_t));
         if (e != hipSuccess) {
-            (void)hipFree(h->d_fam);
-            h->d_fam = h->d_fam_alt = nullptr;
+            (void)hipFree(h->ann.d_fam);
+            h->ann.d_fam = h->ann.d_fam_alt = nullptr;
             return fail(e == hipErrorOutOfMemory ? AMC_ERR_OOM : AMC_ERR_HIP, "amc_set_anneal_families: %s", hipGetErrorString(e));
         }
     }
-    hipLaunchKernelGGL(amc::family_iota_kernel, dim3(grid_for(h, h->M)), dim3(AMC_BLOCK), 0, h->stream, h->d_fam, h->M);
+    hipLaunchKernelGGL(amc::family_iota_kernel, dim3(grid_for(h, h->M)), dim3(AMC_BLOCK), 0, h->stream, h->ann.d_fam, h->M);
     AMC_HIP(hipGetLastError());
     return AMC_OK;
 }
@@ -203,21 +189,20 @@ int amc_set_anneal_families(amc_handle* h, int on)
 int amc_anneal_family_stats(amc_handle* h, uint64_t* n_families, uint64_t* sum_sq, uint64_t* largest)
 {
     if (!h || !n_families || !sum_sq || !largest) return fail(AMC_ERR_BAD_ARG, "amc_anneal_family_stats: NULL argument");
-    AMC_NEED_FAMILIES("amc_anneal_family_stats");
+    AMC_TRY(need_families(h, "amc_anneal_family_stats"));
     AMC_HIP(hipSetDevice(h->device));
     // the scratch: a count per family id, then the three results (allocated at the first call, zeroed per call)
     const size_t cnt_bytes = (size_t)h->M * sizeof(unsigned int), bytes = cnt_bytes + (8 - cnt_bytes % 8) % 8 + 3 * sizeof(unsigned long long);
-    if (!h->d_fam_cnt) AMC_HIP(hipMalloc(&h->d_fam_cnt, bytes));
-    unsigned long long* d_out = (unsigned long long*)((char*)h->d_fam_cnt + (bytes - 3 * sizeof(unsigned long long)));
-    AMC_HIP(hipMemsetAsync(h->d_fam_cnt, 0, bytes, h->stream));
+    if (!h->ann.d_fam_cnt) AMC_HIP(hipMalloc(&h->ann.d_fam_cnt, bytes));
+    unsigned long long* d_out = (unsigned long long*)((char*)h->ann.d_fam_cnt + (bytes - 3 * sizeof(unsigned long long)));
+    AMC_HIP(hipMemsetAsync(h->ann.d_fam_cnt, 0, bytes, h->stream));
     const int grid = grid_for(h, h->M);
-    hipLaunchKernelGGL(amc::family_count_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint32_t*)h->d_fam, h->M, h->d_fam_cnt);
+    hipLaunchKernelGGL(amc::family_count_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint32_t*)h->ann.d_fam, h->M, h->ann.d_fam_cnt);
     AMC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(amc::family_stats_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const unsigned int*)h->d_fam_cnt, h->M, d_out);
+    hipLaunchKernelGGL(amc::family_stats_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const unsigned int*)h->ann.d_fam_cnt, h->M, d_out);
     AMC_HIP(hipGetLastError());
     unsigned long long host[3];
-    AMC_HIP(hipMemcpyAsync(host, d_out, sizeof host, hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    AMC_TRY(copy_to_host_sync(h, host, d_out, sizeof host));
     *n_families = (uint64_t)host[0];
     *sum_sq = (uint64_t)host[1];
     *largest = (uint64_t)host[2];
@@ -227,24 +212,20 @@ int amc_anneal_family_stats(amc_handle* h, uint64_t* n_families, uint64_t* sum_s
 int amc_download_families(amc_handle* h, uint32_t* families)
 {
     if (!h || !families) return fail(AMC_ERR_BAD_ARG, "amc_download_families: NULL argument");
-    AMC_NEED_FAMILIES("amc_download_families");
+    AMC_TRY(need_families(h, "amc_download_families"));
     AMC_HIP(hipSetDevice(h->device));
-    AMC_HIP(hipMemcpyAsync(families, h->d_fam, (size_t)h->M * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
-    return AMC_OK;
+    return copy_to_host_sync(h, families, h->ann.d_fam, (size_t)h->M * sizeof(uint32_t));
 }
 
 int amc_upload_families(amc_handle* h, const uint32_t* families)
 {
     if (!h || !families) return fail(AMC_ERR_BAD_ARG, "amc_upload_families: NULL argument");
-    AMC_NEED_FAMILIES("amc_upload_families");
+    AMC_TRY(need_families(h, "amc_upload_families"));
     for (int64_t c = 0; c < h->M; ++c)
         if ((int64_t)families[c] >= h->M)
             return fail(AMC_ERR_BAD_ARG, "amc_upload_families: chain %lld: family id %u >= n_chains = %lld", (long long)c, families[c], (long long)h->M);
     AMC_HIP(hipSetDevice(h->device));
-    AMC_HIP(hipMemcpyAsync(h->d_fam, families, (size_t)h->M * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `families` is only valid during the call
-    return AMC_OK;
+    return copy_to_device_sync(h, h->ann.d_fam, families, (size_t)h->M * sizeof(uint32_t));      // `families` is only valid during the call
 }
 
 }  // extern "C"

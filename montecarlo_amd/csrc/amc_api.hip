@@ -186,8 +186,7 @@ static int create_impl(const amc_config* cfg, const ModelSpec& spec, amc_handle*
     double wsum = 0.0;
     for (int k = 0; k < cfg->n_moves; ++k) {
         if (param_f32) {
-            const int rc_s = check_sigma_f32("amc_create", k, cfg->sigma[k]);
-            if (rc_s != AMC_OK) return rc_s;
+            AMC_TRY(check_sigma_f32("amc_create", k, cfg->sigma[k]));
         } else if (!(cfg->sigma[k] >= 1e-100) || !(cfg->sigma[k] <= 1e100))
             return fail(AMC_ERR_BAD_ARG, "amc_create: sigma[%d] must lie in [1e-100, 1e100]", k);
         if (!(cfg->weight[k] >= 0.0) || !std::isfinite(cfg->weight[k]))
@@ -269,7 +268,7 @@ static int create_impl(const amc_config* cfg, const ModelSpec& spec, amc_handle*
 
     int rc = AMC_OK;
     auto bail = [&](int code) { amc_destroy(h); return code; };
-#define AMC_TRY(call)                                                                   \
+#define CREATE_HIP(call)                                                                \
     do {                                                                                \
         hipError_t e2_ = (call);                                                        \
         if (e2_ != hipSuccess) {                                                        \
@@ -282,14 +281,14 @@ static int create_impl(const amc_config* cfg, const ModelSpec& spec, amc_handle*
     if (cfg->stream) {
         h->stream = (hipStream_t)cfg->stream;
     } else {
-        AMC_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        CREATE_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         h->own_stream = true;
     }
-    AMC_TRY(hipMalloc(&h->d_x, (size_t)h->M_pad * sizeof(double)));
-    AMC_TRY(hipMemsetAsync(h->d_x, 0, (size_t)h->M_pad * sizeof(double), h->stream));
+    CREATE_HIP(hipMalloc(&h->d_x, (size_t)h->M_pad * sizeof(double)));
+    CREATE_HIP(hipMemsetAsync(h->d_x, 0, (size_t)h->M_pad * sizeof(double), h->stream));
     if (h->counters) {
         // u16 planes suit a handle with K <= 4 (the register-resident fold); AMC_WIDE_COUNTERS keeps plain u32 arrays
-        AMC_TRY(alloc_counters(h, h->K <= 4 && !h->knobs.wide_counters));
+        CREATE_HIP(alloc_counters(h, h->K <= 4 && !h->knobs.wide_counters));
         // Half a byte (K <= 8) or one byte per chain and MH step; folding costs a read-modify-write of every counter, so a
         // deeper log amortises it over more steps: 128 rows where rows of one byte per chain fit in 2 GiB (0.64 / 1.28 GB at
         // 1e7 chains), never below 16.
@@ -300,50 +299,50 @@ static int create_impl(const amc_config* cfg, const ModelSpec& spec, amc_handle*
         if (h->knobs.log_depth) h->log_depth = h->knobs.log_depth;
         // K <= AMC_PACKED_LOG_MOVES: two chains per byte (store_log_pair)
         const size_t row_bytes = log_form(h) == AMC_LOG_PACKED ? (size_t)h->M_pad / 2 : (size_t)h->M_pad;
-        AMC_TRY(hipMalloc(&h->d_log, (size_t)h->log_depth * row_bytes));
-        AMC_TRY(hipMemsetAsync(h->d_log, 0, (size_t)h->log_depth * row_bytes, h->stream));
+        CREATE_HIP(hipMalloc(&h->d_log, (size_t)h->log_depth * row_bytes));
+        CREATE_HIP(hipMemsetAsync(h->d_log, 0, (size_t)h->log_depth * row_bytes, h->stream));
     }
-    AMC_TRY(hipMalloc(&h->d_ptab, (size_t)amc::PT_ROWS * AMC_MAX_MOVES * sizeof(double)));
-    AMC_TRY(hipMemsetAsync(h->d_ptab, 0, (size_t)amc::PT_ROWS * AMC_MAX_MOVES * sizeof(double), h->stream));
-    AMC_TRY(hipMalloc(&h->d_pick, AMC_PICK_CELLS));
-    AMC_TRY(hipMemsetAsync(h->d_pick, 0, AMC_PICK_CELLS, h->stream));
-    AMC_TRY(hipMalloc(&h->d_totals, 2 * AMC_MAX_MOVES * sizeof(unsigned long long)));
-    AMC_TRY(hipMemsetAsync(h->d_totals, 0, 2 * AMC_MAX_MOVES * sizeof(unsigned long long), h->stream));
+    CREATE_HIP(hipMalloc(&h->d_ptab, (size_t)amc::PT_ROWS * AMC_MAX_MOVES * sizeof(double)));
+    CREATE_HIP(hipMemsetAsync(h->d_ptab, 0, (size_t)amc::PT_ROWS * AMC_MAX_MOVES * sizeof(double), h->stream));
+    CREATE_HIP(hipMalloc(&h->d_pick, AMC_PICK_CELLS));
+    CREATE_HIP(hipMemsetAsync(h->d_pick, 0, AMC_PICK_CELLS, h->stream));
+    CREATE_HIP(hipMalloc(&h->d_totals, 2 * AMC_MAX_MOVES * sizeof(unsigned long long)));
+    CREATE_HIP(hipMemsetAsync(h->d_totals, 0, 2 * AMC_MAX_MOVES * sizeof(unsigned long long), h->stream));
     // room for two rounds of the estimator kernels' resident blocks (pg_plan: up to 2 x 5 per CU) beside the sweeps' 8 per CU
     const int slots_per_cu = std::max(std::max(std::max(h->blocks_per_cu, h->blocks_per_cu_single), h->blocks_per_cu_red), 10);
     h->n_slots = h->n_cu * slots_per_cu;
-    AMC_TRY(hipMalloc(&h->d_acc_slots, (size_t)h->n_slots * sizeof(unsigned long long)));
-    AMC_TRY(hipMemsetAsync(h->d_acc_slots, 0, (size_t)h->n_slots * sizeof(unsigned long long), h->stream));
+    CREATE_HIP(hipMalloc(&h->d_acc_slots, (size_t)h->n_slots * sizeof(unsigned long long)));
+    CREATE_HIP(hipMemsetAsync(h->d_acc_slots, 0, (size_t)h->n_slots * sizeof(unsigned long long), h->stream));
     h->red_blocks = grid_for(h, h->M, slots_per_cu);
-    AMC_TRY(hipMalloc(&h->d_partials, (size_t)(h->red_blocks + amc::PG_GROUP) * PG_MAX_COLS * amc::XS_ROW_R * sizeof(amc::xs_word)));   // whole groups
+    CREATE_HIP(hipMalloc(&h->d_partials, (size_t)(h->red_blocks + amc::PG_GROUP) * PG_MAX_COLS * amc::XS_ROW_R * sizeof(amc::xs_word)));   // whole groups
     for (int i = 0; i < RED_TICKETS; ++i) {
         RedTicket& t = h->red[i];
-        AMC_TRY(hipHostMalloc((void**)&t.h_rows, (size_t)h->n_slots * RED_HOST_STRIDE * sizeof(amc::xs_word), 0));
-        AMC_TRY(hipHostMalloc((void**)&t.h_ratio, (size_t)h->n_slots * RATIO_STRIDE * amc::XS_ROW_Q * sizeof(amc::xs_word), 0));
-        AMC_TRY(hipMalloc(&t.d_ratio_acc, (size_t)AMC_MAX_MOVES * 3 * sizeof(unsigned long long)));
-        AMC_TRY(hipHostMalloc((void**)&t.h_ratio_acc, (size_t)AMC_MAX_MOVES * 3 * sizeof(unsigned long long), 0));
-        AMC_TRY(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+        CREATE_HIP(hipHostMalloc((void**)&t.h_rows, (size_t)h->n_slots * RED_HOST_STRIDE * sizeof(amc::xs_word), 0));
+        CREATE_HIP(hipHostMalloc((void**)&t.h_ratio, (size_t)h->n_slots * RATIO_STRIDE * amc::XS_ROW_Q * sizeof(amc::xs_word), 0));
+        CREATE_HIP(hipMalloc(&t.d_ratio_acc, (size_t)AMC_MAX_MOVES * 3 * sizeof(unsigned long long)));
+        CREATE_HIP(hipHostMalloc((void**)&t.h_ratio_acc, (size_t)AMC_MAX_MOVES * 3 * sizeof(unsigned long long), 0));
+        CREATE_HIP(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
     }
-    AMC_TRY(hipMalloc(&h->d_out, (size_t)PG_MAX_COLS * amc::xs::XS_WORDS * sizeof(double)));
-    AMC_TRY(hipHostMalloc((void**)&h->h_pg_out, (size_t)AMC_MAX_LEARN * PG_NP_MAX_COLS * amc::xs::XS_WORDS * sizeof(double), 0));
-    AMC_TRY(hipMalloc(&h->d_gd_acc, (size_t)AMC_MAX_MOVES * AMC_GD_STRIDE_MAX * sizeof(double)));
-    AMC_TRY(hipMemsetAsync(h->d_gd_acc, 0, (size_t)AMC_MAX_MOVES * AMC_GD_STRIDE_MAX * sizeof(double), h->stream));
-    AMC_TRY(hipMalloc(&h->d_status, sizeof(int)));
-    AMC_TRY(hipMemsetAsync(h->d_status, 0, sizeof(int), h->stream));
+    CREATE_HIP(hipMalloc(&h->d_out, (size_t)PG_MAX_COLS * amc::xs::XS_WORDS * sizeof(double)));
+    CREATE_HIP(hipHostMalloc((void**)&h->h_pg_out, (size_t)AMC_MAX_LEARN * PG_NP_MAX_COLS * amc::xs::XS_WORDS * sizeof(double), 0));
+    CREATE_HIP(hipMalloc(&h->d_gd_acc, (size_t)AMC_MAX_MOVES * AMC_GD_STRIDE_MAX * sizeof(double)));
+    CREATE_HIP(hipMemsetAsync(h->d_gd_acc, 0, (size_t)AMC_MAX_MOVES * AMC_GD_STRIDE_MAX * sizeof(double), h->stream));
+    CREATE_HIP(hipMalloc(&h->d_status, sizeof(int)));
+    CREATE_HIP(hipMemsetAsync(h->d_status, 0, sizeof(int), h->stream));
     {
         const size_t groups = (size_t)(h->n_slots + amc::PG_GROUP - 1) / amc::PG_GROUP + 1;
-        AMC_TRY(hipMalloc(&h->d_pg_tickets, (groups + 1) * sizeof(uint32_t)));
-        AMC_TRY(hipMemsetAsync(h->d_pg_tickets, 0, (groups + 1) * sizeof(uint32_t), h->stream));
-        AMC_TRY(hipMalloc(&h->d_pg_groups, (size_t)2 * amc::PG_PARITY_WORDS * sizeof(amc::xs_word)));   // group rows, by the parity of the estimator step
-        AMC_TRY(hipMalloc(&h->d_theta_ring, (size_t)2 * AMC_MAX_LEARN * sizeof(double)));
-        AMC_TRY(hipMemsetAsync(h->d_theta_ring, 0, (size_t)2 * AMC_MAX_LEARN * sizeof(double), h->stream));
-        AMC_TRY(hipMalloc(&h->d_pg_tail, sizeof(amc::PgTail)));
+        CREATE_HIP(hipMalloc(&h->d_pg_tickets, (groups + 1) * sizeof(uint32_t)));
+        CREATE_HIP(hipMemsetAsync(h->d_pg_tickets, 0, (groups + 1) * sizeof(uint32_t), h->stream));
+        CREATE_HIP(hipMalloc(&h->d_pg_groups, (size_t)2 * amc::PG_PARITY_WORDS * sizeof(amc::xs_word)));   // group rows, by the parity of the estimator step
+        CREATE_HIP(hipMalloc(&h->d_theta_ring, (size_t)2 * AMC_MAX_LEARN * sizeof(double)));
+        CREATE_HIP(hipMemsetAsync(h->d_theta_ring, 0, (size_t)2 * AMC_MAX_LEARN * sizeof(double), h->stream));
+        CREATE_HIP(hipMalloc(&h->d_pg_tail, sizeof(amc::PgTail)));
     }
-    AMC_TRY(hipEventCreate(&h->ev0));
-    AMC_TRY(hipEventCreate(&h->ev1));
-    AMC_TRY(hipEventCreateWithFlags(&h->ev_params, hipEventDisableTiming));
-    AMC_TRY(hipHostMalloc((void**)&h->h_params, (size_t)AMC_MAX_NP * AMC_MAX_MOVES * sizeof(double), 0));
-#undef AMC_TRY
+    CREATE_HIP(hipEventCreate(&h->ev0));
+    CREATE_HIP(hipEventCreate(&h->ev1));
+    CREATE_HIP(hipEventCreateWithFlags(&h->ev_params, hipEventDisableTiming));
+    CREATE_HIP(hipHostMalloc((void**)&h->h_params, (size_t)AMC_MAX_NP * AMC_MAX_MOVES * sizeof(double), 0));
+#undef CREATE_HIP
     rc = push_params(h, cfg->sigma, cfg->weight);
     if (rc != AMC_OK) return bail(rc);
     if (h->n_classes > 1) {            // the moves' classes: a row of the parameter table (amc_kernels.h PT_CLASS)
@@ -387,9 +386,8 @@ static int create_model(const char* who, bool class_checks, const amc_config* cf
                         const char* const* invert_exprs, amc_handle** out)
 {
     ModelSpec spec;
-    const int rc = model_spec(class_checks ? who : nullptr, " (No sample_action! / log_proposal_density is defined)", potential_expr, reward_expr, scale_expr, n_params,
-                              n_classes, sample_exprs, logq_exprs, dlogq_exprs, perform_exprs, invert_exprs, &spec);
-    if (rc != AMC_OK) return rc;
+    AMC_TRY(model_spec(class_checks ? who : nullptr, " (No sample_action! / log_proposal_density is defined)", potential_expr, reward_expr, scale_expr, n_params,
+                       n_classes, sample_exprs, logq_exprs, dlogq_exprs, perform_exprs, invert_exprs, &spec));
     if (!potential_expr) {
         const bool f32 = cfg->struct_size == sizeof(amc_config) && cfg->state_dtype == AMC_DTYPE_F32;
         if (cfg->potential == AMC_POTENTIAL_HARMONIC) spec.potential = "x*x";
@@ -553,25 +551,8 @@ int amc_destroy(amc_handle* h)
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);
     (void)hipFree(h->d_hist);
-    (void)hipFree(h->d_xcnt);
-    (void)hipFree(h->d_rung_rows);
-    (void)hipFree(h->d_rung_recs);
-    (void)hipFree(h->d_bridge);
-    (void)hipFree(h->d_lab);
-    (void)hipFree(h->d_track);
-    (void)hipFree(h->d_respace);
-    (void)hipFree(h->d_rung_tab);
-    (void)hipFree(h->d_rung_cnt);
-    (void)hipFree(h->d_rung_base);
-    (void)hipFree(h->d_tune);
-    (void)hipFree(h->d_x_alt);
-    (void)hipFree(h->d_anneal_n);
-    (void)hipFree(h->d_anneal_tiles);
-    (void)hipFree(h->d_anneal_s);
-    (void)hipFree(h->d_anneal_log);
-    (void)hipFree(h->d_fam);
-    (void)hipFree(h->d_fam_alt);
-    (void)hipFree(h->d_fam_cnt);
+    ladder_release(h->lad);
+    anneal_release(h->ann);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

@@ -64,8 +64,7 @@ int amc_comm_unique_id(void* id128)
 {
     if (!id128) return fail(AMC_ERR_BAD_ARG, "amc_comm_unique_id: NULL argument");
     static Rccl r;
-    const int rc = load_rccl(r);
-    if (rc != AMC_OK) return rc;
+    AMC_TRY(load_rccl(r));
     const int e = r.GetUniqueId(id128);
     if (e != 0) return fail(AMC_ERR_COMM, "ncclGetUniqueId failed: %s", r.GetErrorString ? r.GetErrorString(e) : "?");
     return AMC_OK;
@@ -77,9 +76,8 @@ int amc_comm_init(amc_handle* h, int rank, int n_ranks, const void* id128)
     if (!h || !id128) return fail(AMC_ERR_BAD_ARG, "amc_comm_init: NULL argument");
     if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(AMC_ERR_BAD_ARG, "amc_comm_init: bad rank/n_ranks");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rcr = pg_resolve(h); if (rcr != AMC_OK) return rcr; }
-    const int rc = load_rccl(h->rccl);
-    if (rc != AMC_OK) return rc;
+    AMC_TRY(pg_resolve(h));
+    AMC_TRY(load_rccl(h->rccl));
     if (h->comm) return fail(AMC_ERR_STATE, "amc_comm_init: this handle already has a communicator");
     // everything the communicator's users need exists BEFORE the communicator does: a failure below leaves the handle
     // a clean single shard (amc_allreduce_sum the identity again, a later amc_comm_init welcome)
@@ -127,7 +125,7 @@ int amc_comm_destroy(amc_handle* h)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_comm_destroy: NULL handle");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rcr = pg_resolve(h); if (rcr != AMC_OK) return rcr; }
+    AMC_TRY(pg_resolve(h));
     if (h->stream) AMC_HIP(hipStreamSynchronize(h->stream));      // the estimator's collectives run there
     comm_release(h);
     return AMC_OK;
@@ -220,8 +218,7 @@ int amc_allreduce_xsum(amc_handle* h, double* records, int n_records)
         return fail(AMC_ERR_BAD_ARG, "amc_allreduce_xsum: at most %d records", h->comm_capacity / (h->comm_ranks * amc::xs::XS_WORDS));
     std::vector<double> buf(per * (size_t)h->comm_ranks, 0.0);
     std::memcpy(buf.data() + per * (size_t)h->comm_rank, records, per * sizeof(double));
-    const int rc = amc_allreduce_sum(h, buf.data(), (int)buf.size());
-    if (rc != AMC_OK) return rc;
+    AMC_TRY(amc_allreduce_sum(h, buf.data(), (int)buf.size()));
     std::memcpy(records, buf.data(), per * sizeof(double));
     for (int r = 1; r < h->comm_ranks; ++r)
         for (int i = 0; i < n_records; ++i)

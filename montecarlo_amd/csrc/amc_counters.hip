@@ -118,8 +118,7 @@ hipError_t alloc_counters(amc_handle* h, bool narrow)
 int log_room(amc_handle* h, int* rows)
 {
     if (h->log_fill == h->log_depth) {
-        const int rc = fold_log(h);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(fold_log(h));
     }
     *rows = h->log_depth - h->log_fill;
     return AMC_OK;
@@ -141,7 +140,7 @@ static int sum_acc_slots(amc_handle* h, unsigned long long* out)
 // pool totals of the counter ARRAYS (K > 1; without their 64-bit bases): host[k] accepted, host[AMC_MAX_MOVES + k] total of move k < K - 1
 static int array_totals(amc_handle* h, unsigned long long (&host)[2 * AMC_MAX_MOVES])
 {
-    { const int rc = fold_log(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(fold_log(h));
     if (h->K > 1) {
         AMC_HIP(hipMemsetAsync(h->d_totals, 0, 2 * AMC_MAX_MOVES * sizeof(unsigned long long), h->stream));
         if (h->narrow)
@@ -166,7 +165,7 @@ static int array_totals(amc_handle* h, unsigned long long (&host)[2 * AMC_MAX_MO
 static int counter_rebase(amc_handle* h)
 {
     unsigned long long host[2 * AMC_MAX_MOVES];
-    { const int rc = array_totals(h, host); if (rc != AMC_OK) return rc; }         // folds the log
+    AMC_TRY(array_totals(h, host));         // folds the log
     const size_t n = (size_t)h->K * (size_t)h->M_pad, nt = (size_t)(h->K - 1) * (size_t)h->M_pad;
     if (!h->d_acc_base) {
         AMC_HIP(hipMalloc(&h->d_acc_base, n * sizeof(unsigned long long)));
@@ -219,8 +218,7 @@ int counter_room(amc_handle* h, const char* who, uint64_t steps)
     (void)who;
     if (!h->counters) return AMC_OK;
     if (h->t_counted + steps > 0xFFFFFFFFull) {
-        const int rc = counter_rebase(h);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(counter_rebase(h));
     }
     if (h->narrow && h->t_counted + steps > 0xFFFFull) h->use_high = true;
     return AMC_OK;
@@ -231,20 +229,20 @@ int counter_room(amc_handle* h, const char* who, uint64_t steps)
 // pending log rows.  Nothing is read back.  The caller has checked the ladder and the counters and set the device.
 int rung_totals_queue(amc_handle* h)
 {
-    { const int rc = fold_log(h); if (rc != AMC_OK) return rc; }
-    const int R = h->n_rungs;
+    AMC_TRY(fold_log(h));
+    const int R = h->lad.n_rungs;
     const size_t cells = (size_t)h->K * (size_t)R;
-    if (cells > h->rung_cnt_cells) {
+    if (cells > h->lad.rung_cnt_cells) {
         AMC_HIP(hipStreamSynchronize(h->stream));               // (nothing queued reads the old cells after this call's predecessor returned)
-        (void)hipFree(h->d_rung_cnt);
-        h->d_rung_cnt = nullptr;
-        h->rung_cnt_cells = 0;
-        AMC_HIP(hipMalloc(&h->d_rung_cnt, 2 * cells * sizeof(unsigned long long)));
-        h->rung_cnt_cells = cells;
+        (void)hipFree(h->lad.d_rung_cnt);
+        h->lad.d_rung_cnt = nullptr;
+        h->lad.rung_cnt_cells = 0;
+        AMC_HIP(hipMalloc(&h->lad.d_rung_cnt, 2 * cells * sizeof(unsigned long long)));
+        h->lad.rung_cnt_cells = cells;
     }
-    unsigned long long* out_acc = h->d_rung_cnt;
-    unsigned long long* out_tot = h->d_rung_cnt + cells;
-    AMC_HIP(hipMemsetAsync(h->d_rung_cnt, 0, 2 * cells * sizeof(unsigned long long), h->stream));
+    unsigned long long* out_acc = h->lad.d_rung_cnt;
+    unsigned long long* out_tot = h->lad.d_rung_cnt + cells;
+    AMC_HIP(hipMemsetAsync(h->lad.d_rung_cnt, 0, 2 * cells * sizeof(unsigned long long), h->stream));
     const int grid = grid_for(h, h->M);
     if (h->narrow)
         hipLaunchKernelGGL(amc::rung_counter_totals_kernel<uint16_t>, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint16_t*)h->d_acc16,
@@ -267,7 +265,7 @@ int amc_download_counters(amc_handle* h, int64_t* accepted, int64_t* total)
     if (!h->counters)
         return fail(AMC_ERR_STATE, "amc_download_counters: handle was created with per_chain_counters = 0");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = fold_log(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(fold_log(h));
     std::vector<uint32_t> buf((size_t)h->M);
     // one row of counters, whatever their width on the device, as int64
     auto fetch_row = [&](const uint32_t* wide, const uint16_t* narrow, const uint16_t* high, int k, int64_t* out) -> int {
@@ -326,11 +324,10 @@ int amc_counter_totals(amc_handle* h, int64_t* accepted, int64_t* total)
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_counter_totals: NULL handle");
     AMC_HIP(hipSetDevice(h->device));
     unsigned long long host[2 * AMC_MAX_MOVES];
-    { const int rc = array_totals(h, host); if (rc != AMC_OK) return rc; }
+    AMC_TRY(array_totals(h, host));
     if (h->K == 1) {
         unsigned long long acc = 0;
-        const int rc = sum_acc_slots(h, &acc);         // (the pool-wide slots are 64-bit and never carried)
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(sum_acc_slots(h, &acc));         // (the pool-wide slots are 64-bit and never carried)
         host[0] = acc;
     }
     unsigned long long others = 0;
@@ -348,15 +345,14 @@ int amc_counter_totals(amc_handle* h, int64_t* accepted, int64_t* total)
 int amc_rung_counter_totals(amc_handle* h, int64_t* accepted, int64_t* total)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_rung_counter_totals: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_rung_counter_totals: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_rung_counter_totals"));
     if (!h->counters) return fail(AMC_ERR_STATE, "amc_rung_counter_totals: handle was created with per_chain_counters = 0");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = rung_totals_queue(h); if (rc != AMC_OK) return rc; }
-    const int R = h->n_rungs;
+    AMC_TRY(rung_totals_queue(h));
+    const int R = h->lad.n_rungs;
     const size_t cells = (size_t)h->K * (size_t)R;
     std::vector<unsigned long long> host(2 * cells);
-    AMC_HIP(hipMemcpyAsync(host.data(), h->d_rung_cnt, 2 * cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    AMC_TRY(copy_to_host_sync(h, host.data(), h->lad.d_rung_cnt, 2 * cells * sizeof(unsigned long long)));
     // the last move's total: every chain of a rung has taken all counted steps, what the other moves left is its own
     const unsigned long long steps_per_rung = (h->t_base + h->t_counted) * (uint64_t)(h->M / R);
     for (int r = 0; r < R; ++r) {
@@ -408,7 +404,7 @@ int amc_upload_counters(amc_handle* h, const int64_t* accepted, const int64_t* t
         // counts beyond 32 bits (or a handle that has carried before): everything goes into the 64-bit bases, the arrays restart
         // at zero (counter_rebase does the allocating and the switch to u32 arrays; what it carries is overwritten next)
         h->log_fill = 0;
-        { const int rc = counter_rebase(h); if (rc != AMC_OK) return rc; }
+        AMC_TRY(counter_rebase(h));
         std::vector<unsigned long long> b((size_t)h->M);
         for (int k = 0; k < h->K; ++k) {
             h->base_acc_total[k] = h->base_tot_total[k] = 0ull;

@@ -37,21 +37,21 @@ static_assert(AMC_RESPACE_ACCEPTANCE == amc::rs::RS_ACCEPTANCE && AMC_RESPACE_FL
 // Memory a handle never allocated stays unallocated.
 static int tune_reset(amc_handle* h, bool with_base)
 {
-    if (h->d_tune) AMC_HIP(hipMemsetAsync(h->d_tune, 0, TUNE_BYTES, h->stream));
-    if (with_base && h->d_rung_base) AMC_HIP(hipMemsetAsync(h->d_rung_base, 0, RUNG_BASE_BYTES, h->stream));
-    h->tune_queued = false;
+    if (h->lad.d_tune) AMC_HIP(hipMemsetAsync(h->lad.d_tune, 0, TUNE_BYTES, h->stream));
+    if (with_base && h->lad.d_rung_base) AMC_HIP(hipMemsetAsync(h->lad.d_rung_base, 0, RUNG_BASE_BYTES, h->stream));
+    h->lad.tune_queued = false;
     return AMC_OK;
 }
 
 // Tracking off: the labels and the trip counters go.  Launches queued on the stream may still use them.
 static int tracking_off(amc_handle* h)
 {
-    if (!h->d_lab) return AMC_OK;
+    if (!h->lad.d_lab) return AMC_OK;
     AMC_HIP(hipStreamSynchronize(h->stream));
-    (void)hipFree(h->d_lab);
-    (void)hipFree(h->d_track);
-    h->d_lab = nullptr;
-    h->d_track = nullptr;
+    (void)hipFree(h->lad.d_lab);
+    (void)hipFree(h->lad.d_track);
+    h->lad.d_lab = nullptr;
+    h->lad.d_track = nullptr;
     return AMC_OK;
 }
 
@@ -59,13 +59,13 @@ static int tracking_off(amc_handle* h)
 // read them, in stream order, before the next call's launches write them).
 static int rung_rows_room(amc_handle* h, size_t need)
 {
-    if (need <= h->rung_rows_words) return AMC_OK;
+    if (need <= h->lad.rung_rows_words) return AMC_OK;
     AMC_HIP(hipStreamSynchronize(h->stream));                   // (a finishing kernel queued by a bridge snapshot may still read the old rows)
-    (void)hipFree(h->d_rung_rows);
-    h->d_rung_rows = nullptr;
-    h->rung_rows_words = 0;
-    AMC_HIP(hipMalloc(&h->d_rung_rows, need * sizeof(amc::xs_word)));
-    h->rung_rows_words = need;
+    (void)hipFree(h->lad.d_rung_rows);
+    h->lad.d_rung_rows = nullptr;
+    h->lad.rung_rows_words = 0;
+    AMC_HIP(hipMalloc(&h->lad.d_rung_rows, need * sizeof(amc::xs_word)));
+    h->lad.rung_rows_words = need;
     return AMC_OK;
 }
 
@@ -73,8 +73,72 @@ static int rung_rows_room(amc_handle* h, size_t need)
 static const size_t BRIDGE_BYTES = amc::BRIDGE_WORDS * sizeof(amc::xs_word);      // d_bridge (amc_exchange.h BRIDGE_*)
 static int bridge_clear(amc_handle* h)
 {
-    if (h->d_bridge) AMC_HIP(hipMemsetAsync(h->d_bridge, 0, BRIDGE_BYTES, h->stream));
-    h->bridge_cols = 0;
+    if (h->lad.d_bridge) AMC_HIP(hipMemsetAsync(h->lad.d_bridge, 0, BRIDGE_BYTES, h->stream));
+    h->lad.bridge_cols = 0;
+    return AMC_OK;
+}
+
+// Another ladder, or none: everything the handle knew about the old one is forgotten -- its walkers, that it was respaced, the tunings of
+// its widths and the window (another R has other cells), its bridge sums, its widths per rung (none until they are set again).  Memory
+// stays, but for the labels.  The one place a feature that adds ladder state has to remember.
+static int ladder_reset(amc_handle* h)
+{
+    AMC_TRY(tracking_off(h));
+    if (h->lad.d_respace) AMC_HIP(hipMemsetAsync(h->lad.d_respace, 0, RESPACE_BYTES, h->stream));
+    AMC_TRY(tune_reset(h, true));
+    AMC_TRY(bridge_clear(h));
+    h->lad.rung_on = false;
+    return AMC_OK;
+}
+
+// The flow snapshot of this handle's labels queued into the cells behind the trip counters (tracking is on: the caller has checked).
+static int flow_snapshot_queue(amc_handle* h)
+{
+    unsigned long long* d_flow = h->lad.d_track + 2;
+    AMC_HIP(hipMemsetAsync(d_flow, 0, (size_t)(3 * h->lad.n_rungs) * sizeof(unsigned long long), h->stream));
+    const int grid = grid_for(h, (h->M + 3) / 4, h->knobs.blocks_per_cu ? 0 : EXCHANGE_BLOCKS_PER_CU);     // a thread per 4 labels; the atomics' tail again
+    hipLaunchKernelGGL(amc::rung_flow_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint8_t*)h->lad.d_lab, h->M, h->lad.n_rungs, d_flow);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
+// A pass over the ladders that ends every block with rows of its own, n_cols columns per rung, in d_rung_rows (the rung sums, the bridge
+// sums): the launches it takes and where each one's rows go.
+struct RungPass {
+    int grid = 0;
+    int64_t per_launch = 0, n_launches = 0;     // ladders per launch; launches
+    size_t slot_words = 0;                      // words of one block's rows
+    int n_blocks() const { return (int)(n_launches * grid); }      // block rows the finishing kernel reads
+};
+
+// ... planned, and room made for its rows.
+static int rung_pass_plan(amc_handle* h, int n_cols, RungPass* p)
+{
+    const int R = h->lad.n_rungs;
+    p->grid = grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU);
+    // a lane adds one summand per trip and column and holds XS_LANE_CAP of them (amc_xsum.h): ensembles beyond that many trips of the
+    // grid (2^28 chains and more) take several launches, each with block rows of its own
+    p->per_launch = (((int64_t)p->grid * AMC_BLOCK) / R) * (amc::xs::XS_LANE_CAP - 2);
+    p->n_launches = (h->M / R + p->per_launch - 1) / p->per_launch;
+    p->slot_words = (size_t)R * (size_t)n_cols * amc::XS_ROW_R;
+    return rung_rows_room(h, (size_t)p->n_launches * (size_t)p->grid * p->slot_words);
+}
+
+// ... launched: `a` comes with what only its kernel reads (the bridge sums' beta); x, the rows, the ladders, R and the columns are filled in here.
+template <class Args>
+static int rung_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
+{
+    const int64_t n_ladders = h->M / h->lad.n_rungs;
+    a.x = h->d_x;
+    a.n_rungs = h->lad.n_rungs;
+    a.cols = columns;
+    for (int64_t i = 0; i < p.n_launches; ++i) {
+        a.rows = h->lad.d_rung_rows + (size_t)i * (size_t)p.grid * p.slot_words;
+        a.l_begin = i * p.per_launch;
+        a.l_end = std::min(n_ladders, (i + 1) * p.per_launch);
+        void* params[] = {&a};
+        AMC_TRY(launch_by_potential(h, name, double_well, harmonic, p.grid, params));
+    }
     return AMC_OK;
 }
 
@@ -84,36 +148,35 @@ static int exchange_step(amc_handle* h)
 {
     // (what a sweep does before it launches: a learning step left pending by a fused time step is taken now -- it belongs in front
     // of this point of the stream; reductions in flight were queued on the same stream and have read x before this launch writes it)
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    if (h->t_x >> 48) return fail(AMC_ERR_STATE, "amc_exchange: the exchange step index has reached 2^48");
-    const int parity = (int)(h->t_x & 1u);
-    const int n_gaps = (h->n_rungs - parity) / 2;
+    AMC_TRY(pg_resolve(h));
+    if (h->lad.t_x >> 48) return fail(AMC_ERR_STATE, "amc_exchange: the exchange step index has reached 2^48");
+    const int parity = (int)(h->lad.t_x & 1u);
+    const int n_gaps = (h->lad.n_rungs - parity) / 2;
     if (n_gaps > 0) {
         amc::ExchangeArgs a;
         a.x = h->d_x;
         a.beta = h->d_beta;
-        a.counts = h->d_xcnt;
-        a.n_ladders = h->M / h->n_rungs;
+        a.counts = h->lad.d_xcnt;
+        a.n_ladders = h->M / h->lad.n_rungs;
         a.chain0 = (uint64_t)h->offset;
-        a.t_x = h->t_x;
-        a.n_rungs = h->n_rungs;
+        a.t_x = h->lad.t_x;
+        a.n_rungs = h->lad.n_rungs;
         a.n_gaps = n_gaps;
         a.key0 = (uint32_t)h->seed;
         a.key1 = (uint32_t)(h->seed >> 32);
         const int grid = grid_for(h, a.n_ladders * n_gaps, h->knobs.blocks_per_cu ? 0 : EXCHANGE_BLOCKS_PER_CU);
         amc::ExchangeTrackArgs ta;        // tracking on: the same step by the kernel that carries the labels along
         ta.step = a;
-        ta.lab = h->d_lab;
-        ta.trips = h->d_track;
-        const bool track = h->d_lab != nullptr;
+        ta.lab = h->lad.d_lab;
+        ta.trips = h->lad.d_track;
+        const bool track = h->lad.d_lab != nullptr;
         void* params[] = {track ? (void*)&ta : (void*)&a};
-        const int rc = track ? launch_by_potential(h, "amc::exchange_tracked_kernel", (const void*)amc::exchange_tracked_kernel<amc::POT_DOUBLE_WELL>,
-                                                   (const void*)amc::exchange_tracked_kernel<amc::POT_HARMONIC>, grid, params)
-                             : launch_by_potential(h, "amc::exchange_kernel", (const void*)amc::exchange_kernel<amc::POT_DOUBLE_WELL>,
-                                                   (const void*)amc::exchange_kernel<amc::POT_HARMONIC>, grid, params);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(track ? launch_by_potential(h, "amc::exchange_tracked_kernel", (const void*)amc::exchange_tracked_kernel<amc::POT_DOUBLE_WELL>,
+                                            (const void*)amc::exchange_tracked_kernel<amc::POT_HARMONIC>, grid, params)
+                      : launch_by_potential(h, "amc::exchange_kernel", (const void*)amc::exchange_kernel<amc::POT_DOUBLE_WELL>,
+                                            (const void*)amc::exchange_kernel<amc::POT_HARMONIC>, grid, params));
     }
-    h->t_x += 1;
+    h->lad.t_x += 1;
     return AMC_OK;
 }
 
@@ -124,12 +187,8 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: NULL handle");
     if (n_rungs == 0) {
         AMC_HIP(hipSetDevice(h->device));
-        { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }
-        if (h->d_respace) AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));
-        { const int rc = tune_reset(h, true); if (rc != AMC_OK) return rc; }
-        { const int rc = bridge_clear(h); if (rc != AMC_OK) return rc; }
-        h->rung_on = false;
-        h->n_rungs = 0;
+        AMC_TRY(ladder_reset(h));
+        h->lad.n_rungs = 0;
         return AMC_OK;
     }
     if (n_rungs < 2 || n_rungs > AMC_MAX_RUNGS)
@@ -145,14 +204,10 @@ int amc_set_ladder(amc_handle* h, int n_rungs)
         return fail(AMC_ERR_BAD_ARG, "amc_set_ladder: n_chains = %lld is no multiple of n_rungs = %d (no ladder may straddle a shard)",
                     (long long)h->M, n_rungs);
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = tracking_off(h); if (rc != AMC_OK) return rc; }      // another ladder has other walkers
-    if (!h->d_xcnt) AMC_HIP(hipMalloc(&h->d_xcnt, XCNT_BYTES));
-    AMC_HIP(hipMemsetAsync(h->d_xcnt, 0, XCNT_BYTES, h->stream));      // the gaps of another ladder are other gaps
-    if (h->d_respace) AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));      // ... and nobody has respaced it
-    { const int rc = tune_reset(h, true); if (rc != AMC_OK) return rc; }                        // ... nor tuned its widths; another R has other cells
-    { const int rc = bridge_clear(h); if (rc != AMC_OK) return rc; }                            // ... and its bridge sums are other sums
-    h->rung_on = false;                                                // ... and its rungs other rungs: no widths per rung until they are set again
-    h->n_rungs = n_rungs;
+    if (!h->lad.d_xcnt) AMC_HIP(hipMalloc(&h->lad.d_xcnt, XCNT_BYTES));
+    AMC_HIP(hipMemsetAsync(h->lad.d_xcnt, 0, XCNT_BYTES, h->stream));      // the gaps of another ladder are other gaps
+    AMC_TRY(ladder_reset(h));                                              // ... and the rest of what was known about the old one goes
+    h->lad.n_rungs = n_rungs;
     return AMC_OK;
 }
 
@@ -164,8 +219,8 @@ int amc_set_rung_sigma(amc_handle* h, const double* sigma, int n)
         // Host state only, so no hipSetDevice: the next sweep picks its form from this flag when it is queued, and the table's
         // memory stays for the sweeps already queued.  No pg_resolve either: every estimator entry is refused while a table is
         // set, and setting it took the step that was pending then, so none can be pending here.
-        h->rung_on = false;
-        h->tune_queued = false;          // (the record itself is zeroed when the next table is set)
+        h->lad.rung_on = false;
+        h->lad.tune_queued = false;          // (the record itself is zeroed when the next table is set)
         return AMC_OK;
     }
     if (!h->model.classes.empty() || h->script_policy || h->scaled_policy || h->n_params > 1 || h->n_classes > 1)
@@ -173,10 +228,10 @@ int amc_set_rung_sigma(amc_handle* h, const double* sigma, int n)
                                    "class or action");
     if (h->param_f32)
         return fail(AMC_ERR_STATE, "amc_set_rung_sigma: not available with param_dtype = AMC_DTYPE_F32 (the rung table holds Float64 widths)");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_rung_sigma: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_set_rung_sigma"));
     if (!h->counters)
         return fail(AMC_ERR_STATE, "amc_set_rung_sigma: handle was created with per_chain_counters = 0 (the acceptance per rung needs them)");
-    const int R = h->n_rungs;
+    const int R = h->lad.n_rungs;
     if (h->K * R > AMC_MAX_MOVES)
         return fail(AMC_ERR_BAD_ARG, "amc_set_rung_sigma: %d moves x %d rungs = %d entries, the table holds %d", h->K, R, h->K * R, AMC_MAX_MOVES);
     if (n != h->K * R)
@@ -187,33 +242,32 @@ int amc_set_rung_sigma(amc_handle* h, const double* sigma, int n)
                         sigma[e]);
     AMC_HIP(hipSetDevice(h->device));
     // (as in front of a sweep: a learning step left pending belongs in front of this point of the stream)
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    if (!h->d_rung_tab) AMC_HIP(hipMalloc(&h->d_rung_tab, (size_t)amc::RT_ROWS * AMC_MAX_MOVES * sizeof(double)));
+    AMC_TRY(pg_resolve(h));
+    if (!h->lad.d_rung_tab) AMC_HIP(hipMalloc(&h->lad.d_rung_tab, (size_t)amc::RT_ROWS * AMC_MAX_MOVES * sizeof(double)));
     amc::RungSigma s;
     for (int e = 0; e < AMC_MAX_MOVES; ++e) s.sigma[e] = e < n ? sigma[e] : 1.0;
     // on the stream, behind the sweeps that read the rows as they are
-    hipLaunchKernelGGL(amc::prepare_rung_params_kernel, dim3(1), dim3(AMC_MAX_MOVES), 0, h->stream, h->d_rung_tab, s, n);
+    hipLaunchKernelGGL(amc::prepare_rung_params_kernel, dim3(1), dim3(AMC_MAX_MOVES), 0, h->stream, h->lad.d_rung_tab, s, n);
     AMC_HIP(hipGetLastError());
-    std::memcpy(h->rung_sigma, s.sigma, sizeof(h->rung_sigma));
-    h->rung_on = true;
+    std::memcpy(h->lad.rung_sigma, s.sigma, sizeof(h->lad.rung_sigma));
+    h->lad.rung_on = true;
     return tune_reset(h, false);         // a table that was given has not been tuned; the window is left alone
 }
 
 int amc_get_rung_sigma(amc_handle* h, double* sigma, int n)
 {
     if (!h || !sigma) return fail(AMC_ERR_BAD_ARG, "amc_get_rung_sigma: NULL argument");
-    if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_get_rung_sigma: no widths per rung are set (amc_set_rung_sigma)");
-    if (n != h->K * h->n_rungs)
-        return fail(AMC_ERR_BAD_ARG, "amc_get_rung_sigma: n = %d, the table of %d moves x %d rungs has %d entries", n, h->K, h->n_rungs, h->K * h->n_rungs);
-    if (!h->tune_queued) {               // the table as it was given
-        std::memcpy(sigma, h->rung_sigma, (size_t)n * sizeof(double));
+    if (!h->lad.rung_on) return fail(AMC_ERR_STATE, "amc_get_rung_sigma: no widths per rung are set (amc_set_rung_sigma)");
+    if (n != h->K * h->lad.n_rungs)
+        return fail(AMC_ERR_BAD_ARG, "amc_get_rung_sigma: n = %d, the table of %d moves x %d rungs has %d entries", n, h->K, h->lad.n_rungs, h->K * h->lad.n_rungs);
+    if (!h->lad.tune_queued) {               // the table as it was given
+        std::memcpy(sigma, h->lad.rung_sigma, (size_t)n * sizeof(double));
         return AMC_OK;
     }
     // tuned since: the table is the device's (the record holds every entry's width as the last tuning left it)
     AMC_HIP(hipSetDevice(h->device));
     unsigned long long host[AMC_MAX_MOVES];
-    AMC_HIP(hipMemcpyAsync(host, h->d_tune + amc::TUNE_SIGMA, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    AMC_TRY(copy_to_host_sync(h, host, h->lad.d_tune + amc::TUNE_SIGMA, (size_t)n * sizeof(unsigned long long)));
     std::memcpy(sigma, host, (size_t)n * sizeof(double));
     return AMC_OK;
 }
@@ -221,12 +275,11 @@ int amc_get_rung_sigma(amc_handle* h, double* sigma, int n)
 int amc_exchange(amc_handle* h, int64_t n_steps)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_exchange: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_exchange: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_exchange"));
     if (n_steps < 0) return fail(AMC_ERR_BAD_ARG, "amc_exchange: n_steps < 0");
     AMC_HIP(hipSetDevice(h->device));
     for (int64_t i = 0; i < n_steps; ++i) {
-        const int rc = exchange_step(h);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(exchange_step(h));
     }
     return AMC_OK;
 }
@@ -234,16 +287,14 @@ int amc_exchange(amc_handle* h, int64_t n_steps)
 int amc_sweep_exchange(amc_handle* h, int64_t n_rounds, int64_t sweeps_per_round)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_sweep_exchange: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_sweep_exchange: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_sweep_exchange"));
     if (n_rounds < 0 || sweeps_per_round < 0) return fail(AMC_ERR_BAD_ARG, "amc_sweep_exchange: n_rounds < 0 or sweeps_per_round < 0");
     AMC_HIP(hipSetDevice(h->device));
     for (int64_t i = 0; i < n_rounds; ++i) {
         if (sweeps_per_round > 0) {
-            const int rc = sweep_impl(h, sweeps_per_round, false, nullptr);
-            if (rc != AMC_OK) return rc;
+            AMC_TRY(sweep_impl(h, sweeps_per_round, false, nullptr));
         }
-        const int rc = exchange_step(h);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(exchange_step(h));
     }
     return AMC_OK;
 }
@@ -251,12 +302,11 @@ int amc_sweep_exchange(amc_handle* h, int64_t n_rounds, int64_t sweeps_per_round
 int amc_exchange_counters(amc_handle* h, int64_t* accepted, int64_t* attempted)
 {
     if (!h || !accepted || !attempted) return fail(AMC_ERR_BAD_ARG, "amc_exchange_counters: NULL argument");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_exchange_counters: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_exchange_counters"));
     AMC_HIP(hipSetDevice(h->device));
     unsigned long long host[2 * AMC_MAX_RUNGS];
-    AMC_HIP(hipMemcpyAsync(host, h->d_xcnt, XCNT_BYTES, hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
-    for (int r = 0; r + 1 < h->n_rungs; ++r) {
+    AMC_TRY(copy_to_host_sync(h, host, h->lad.d_xcnt, XCNT_BYTES));
+    for (int r = 0; r + 1 < h->lad.n_rungs; ++r) {
         attempted[r] = (int64_t)host[r];
         accepted[r] = (int64_t)host[AMC_MAX_RUNGS + r];
     }
@@ -266,60 +316,37 @@ int amc_exchange_counters(amc_handle* h, int64_t* accepted, int64_t* attempted)
 int amc_set_exchange_counters(amc_handle* h, const int64_t* accepted, const int64_t* attempted)
 {
     if (!h || !accepted || !attempted) return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_counters: NULL argument");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_exchange_counters: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_set_exchange_counters"));
     unsigned long long host[2 * AMC_MAX_RUNGS] = {0};
-    for (int r = 0; r + 1 < h->n_rungs; ++r) {
+    for (int r = 0; r + 1 < h->lad.n_rungs; ++r) {
         if (accepted[r] < 0 || attempted[r] < accepted[r])
             return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_counters: gap %d: need 0 <= accepted <= attempted", r);
         host[r] = (unsigned long long)attempted[r];
         host[AMC_MAX_RUNGS + r] = (unsigned long long)accepted[r];
     }
     AMC_HIP(hipSetDevice(h->device));
-    AMC_HIP(hipMemcpyAsync(h->d_xcnt, host, XCNT_BYTES, hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
-    return AMC_OK;
+    return copy_to_device_sync(h, h->lad.d_xcnt, host, XCNT_BYTES);      // `host` is only valid during the call
 }
 
 int amc_reduce_rungs_exact(amc_handle* h, int columns, double* records)
 {
     if (!h || !records) return fail(AMC_ERR_BAD_ARG, "amc_reduce_rungs_exact: NULL argument");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_reduce_rungs_exact: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_reduce_rungs_exact"));
     if (columns <= 0 || (columns & ~AMC_REDUCE_ALL))
         return fail(AMC_ERR_BAD_ARG, "amc_reduce_rungs_exact: columns = %d must be a non-empty combination of AMC_REDUCE_E / _X / _XX", columns);
     AMC_HIP(hipSetDevice(h->device));
     // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    const int R = h->n_rungs;
-    const int64_t n_ladders = h->M / R;
-    const int grid = grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU);
-    // a lane adds one summand per trip and column and holds XS_LANE_CAP of them (amc_xsum.h): ensembles beyond that many trips of the
-    // grid (2^28 chains and more) take several launches, each with block rows of its own
-    const int64_t per_launch = (((int64_t)grid * AMC_BLOCK) / R) * (amc::xs::XS_LANE_CAP - 2);
-    const int64_t n_launches = (n_ladders + per_launch - 1) / per_launch;
-    const size_t slot_words = (size_t)R * amc::RED_COLS * amc::XS_ROW_R;
-    const size_t need = (size_t)n_launches * (size_t)grid * slot_words;
-    { const int rc = rung_rows_room(h, need); if (rc != AMC_OK) return rc; }
-    if (!h->d_rung_recs) AMC_HIP(hipMalloc(&h->d_rung_recs, (size_t)AMC_MAX_RUNGS * amc::RED_COLS * amc::xs::XS_WORDS * sizeof(double)));
-    for (int64_t i = 0; i < n_launches; ++i) {
-        amc::RungSumsArgs a;
-        a.x = h->d_x;
-        a.rows = h->d_rung_rows + (size_t)i * (size_t)grid * slot_words;
-        a.l_begin = i * per_launch;
-        a.l_end = std::min(n_ladders, (i + 1) * per_launch);
-        a.n_rungs = R;
-        a.cols = columns;
-        void* params[] = {&a};
-        const int rc = launch_by_potential(h, "amc::rung_sums_kernel", (const void*)amc::rung_sums_kernel<amc::POT_DOUBLE_WELL>,
-                                           (const void*)amc::rung_sums_kernel<amc::POT_HARMONIC>, grid, params);
-        if (rc != AMC_OK) return rc;
-    }
-    const int n_slots = R * amc::RED_COLS;
-    hipLaunchKernelGGL(amc::rung_finish_kernel, dim3(n_slots), dim3(64), 0, h->stream, (const amc::xs_word*)h->d_rung_rows,
-                       (int)(n_launches * grid), R, columns, h->d_rung_recs);
+    AMC_TRY(pg_resolve(h));
+    RungPass p;
+    AMC_TRY(rung_pass_plan(h, amc::RED_COLS, &p));
+    if (!h->lad.d_rung_recs) AMC_HIP(hipMalloc(&h->lad.d_rung_recs, (size_t)AMC_MAX_RUNGS * amc::RED_COLS * amc::xs::XS_WORDS * sizeof(double)));
+    AMC_TRY(rung_pass_launch(h, p, amc::RungSumsArgs(), columns, "amc::rung_sums_kernel", (const void*)amc::rung_sums_kernel<amc::POT_DOUBLE_WELL>,
+                             (const void*)amc::rung_sums_kernel<amc::POT_HARMONIC>));
+    const int R = h->lad.n_rungs, n_slots = R * amc::RED_COLS;
+    hipLaunchKernelGGL(amc::rung_finish_kernel, dim3(n_slots), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows, p.n_blocks(), R, columns,
+                       h->lad.d_rung_recs);
     AMC_HIP(hipGetLastError());
-    AMC_HIP(hipMemcpyAsync(records, h->d_rung_recs, (size_t)n_slots * amc::xs::XS_WORDS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
-    return AMC_OK;
+    return copy_to_host_sync(h, records, h->lad.d_rung_recs, (size_t)n_slots * amc::xs::XS_WORDS * sizeof(double));
 }
 
 // ---- bridge sums (DESIGN.md section 3.13 "Bridge sums") --------------------------------------------------------------------------------
@@ -329,57 +356,38 @@ static_assert(AMC_BRIDGE_E == amc::BR_E && AMC_BRIDGE_EE == amc::BR_EE && AMC_BR
 int amc_bridge_accumulate(amc_handle* h, int columns)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_bridge_accumulate: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_bridge_accumulate: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_bridge_accumulate"));
     if (columns <= 0 || (columns & ~AMC_BRIDGE_ALL))
         return fail(AMC_ERR_BAD_ARG, "amc_bridge_accumulate: columns = %d must be a non-empty combination of the AMC_BRIDGE_* bits", columns);
-    if (h->bridge_cols && h->bridge_cols != columns)
+    if (h->lad.bridge_cols && h->lad.bridge_cols != columns)
         return fail(AMC_ERR_STATE, "amc_bridge_accumulate: columns = %d, the accumulator was begun with %d (amc_bridge_fetch with reset frees the mask)", columns,
-                    h->bridge_cols);
+                    h->lad.bridge_cols);
     AMC_HIP(hipSetDevice(h->device));
     // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    const int R = h->n_rungs;
-    const int64_t n_ladders = h->M / R;
-    const int grid = grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU);
-    // the lane cap, as amc_reduce_rungs_exact handles it: several launches beyond XS_LANE_CAP - 2 trips of the grid
-    const int64_t per_launch = (((int64_t)grid * AMC_BLOCK) / R) * (amc::xs::XS_LANE_CAP - 2);
-    const int64_t n_launches = (n_ladders + per_launch - 1) / per_launch;
-    const size_t slot_words = (size_t)R * amc::BR_COLS * amc::XS_ROW_R;
-    { const int rc = rung_rows_room(h, (size_t)n_launches * (size_t)grid * slot_words); if (rc != AMC_OK) return rc; }
-    if (!h->d_bridge) {
-        AMC_HIP(hipMalloc(&h->d_bridge, BRIDGE_BYTES));
-        AMC_HIP(hipMemsetAsync(h->d_bridge, 0, BRIDGE_BYTES, h->stream));
-    }
-    for (int64_t i = 0; i < n_launches; ++i) {
-        amc::BridgeArgs a;
-        a.x = h->d_x;
-        a.beta = h->d_beta;
-        a.rows = h->d_rung_rows + (size_t)i * (size_t)grid * slot_words;
-        a.l_begin = i * per_launch;
-        a.l_end = std::min(n_ladders, (i + 1) * per_launch);
-        a.n_rungs = R;
-        a.cols = columns;
-        void* params[] = {&a};
-        const int rc = launch_by_potential(h, "amc::bridge_sums_kernel", (const void*)amc::bridge_sums_kernel<amc::POT_DOUBLE_WELL>,
-                                           (const void*)amc::bridge_sums_kernel<amc::POT_HARMONIC>, grid, params);
-        if (rc != AMC_OK) return rc;
-    }
-    hipLaunchKernelGGL(amc::bridge_finish_kernel, dim3(R * amc::BR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->d_rung_rows,
-                       (int)(n_launches * grid), R, columns, h->d_bridge);
+    AMC_TRY(pg_resolve(h));
+    RungPass p;
+    AMC_TRY(rung_pass_plan(h, amc::BR_COLS, &p));
+    AMC_TRY(zeroed_words(h, &h->lad.d_bridge, BRIDGE_BYTES));
+    amc::BridgeArgs a = {};
+    a.beta = h->d_beta;
+    AMC_TRY(rung_pass_launch(h, p, a, columns, "amc::bridge_sums_kernel", (const void*)amc::bridge_sums_kernel<amc::POT_DOUBLE_WELL>,
+                             (const void*)amc::bridge_sums_kernel<amc::POT_HARMONIC>));
+    const int R = h->lad.n_rungs;
+    hipLaunchKernelGGL(amc::bridge_finish_kernel, dim3(R * amc::BR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows, p.n_blocks(), R,
+                       columns, h->lad.d_bridge);
     AMC_HIP(hipGetLastError());
-    h->bridge_cols = columns;
+    h->lad.bridge_cols = columns;
     return AMC_OK;
 }
 
 int amc_bridge_fetch(amc_handle* h, double* records, uint64_t* n_snapshots, int reset)
 {
     if (!h || !records || !n_snapshots) return fail(AMC_ERR_BAD_ARG, "amc_bridge_fetch: NULL argument");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_bridge_fetch: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_bridge_fetch"));
     AMC_HIP(hipSetDevice(h->device));
-    const int R = h->n_rungs, n_slots = R * amc::BR_COLS;
+    const int R = h->lad.n_rungs, n_slots = R * amc::BR_COLS;
     std::vector<amc::xs_word> host(amc::BRIDGE_WORDS, 0ull);
-    if (h->d_bridge) AMC_HIP(hipMemcpyAsync(host.data(), h->d_bridge, BRIDGE_BYTES, hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    AMC_TRY(copy_to_host_sync(h, host.data(), h->lad.d_bridge, BRIDGE_BYTES));
     *n_snapshots = (uint64_t)host[amc::BRIDGE_COUNT];
     for (int s = 0; s < n_slots; ++s) {
         double* rec = records + (size_t)s * amc::xs::XS_WORDS;
@@ -394,12 +402,12 @@ int amc_bridge_fetch(amc_handle* h, double* records, uint64_t* n_snapshots, int 
 int amc_set_bridge(amc_handle* h, const double* records, uint64_t n_snapshots)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_bridge: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_set_bridge"));
     AMC_HIP(hipSetDevice(h->device));
     if (!records || n_snapshots == 0) return bridge_clear(h);
     // The mask is read off the records: a slot that had a summand is a kind-R record, every other is all zero, and a column is in the
     // mask exactly when its interior slots are records (E and EE have a summand at every rung, the W and M columns at all but one end).
-    const int R = h->n_rungs, n_slots = R * amc::BR_COLS;
+    const int R = h->lad.n_rungs, n_slots = R * amc::BR_COLS;
     std::vector<amc::xs_word> host(amc::BRIDGE_WORDS, 0ull);
     int cols = 0;
     for (int s = 0; s < n_slots; ++s) {
@@ -428,59 +436,54 @@ int amc_set_bridge(amc_handle* h, const double* records, uint64_t n_snapshots)
         if (((amc::bridge_cols_at(cols, s / amc::BR_COLS, R) >> (s % amc::BR_COLS)) & 1) && !host[(size_t)s * amc::XS_ROW_R + 5])
             return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: column %d has records at some rungs and none at rung %d", s % amc::BR_COLS, s / amc::BR_COLS);
     host[amc::BRIDGE_COUNT] = (amc::xs_word)n_snapshots;
-    if (!h->d_bridge) AMC_HIP(hipMalloc(&h->d_bridge, BRIDGE_BYTES));
-    AMC_HIP(hipMemcpyAsync(h->d_bridge, host.data(), BRIDGE_BYTES, hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
-    h->bridge_cols = cols;
+    if (!h->lad.d_bridge) AMC_HIP(hipMalloc(&h->lad.d_bridge, BRIDGE_BYTES));
+    AMC_TRY(copy_to_device_sync(h, h->lad.d_bridge, host.data(), BRIDGE_BYTES));      // `host` is only valid during the call
+    h->lad.bridge_cols = cols;
     return AMC_OK;
 }
 
 int amc_get_exchange_step(amc_handle* h, uint64_t* t)
 {
     if (!h || !t) return fail(AMC_ERR_BAD_ARG, "amc_get_exchange_step: NULL argument");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_get_exchange_step: the handle has no ladder (amc_set_ladder)");
-    *t = h->t_x;
+    AMC_TRY(need_ladder(h, "amc_get_exchange_step"));
+    *t = h->lad.t_x;
     return AMC_OK;
 }
 
 int amc_set_exchange_step(amc_handle* h, uint64_t t)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_step: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_exchange_step: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_set_exchange_step"));
     if (t >> 48) return fail(AMC_ERR_BAD_ARG, "amc_set_exchange_step: step index must fit 48 bits");
-    h->t_x = t;
+    h->lad.t_x = t;
     return AMC_OK;
 }
 
 // ---- walker tracking (DESIGN.md section 3.13 "Walker tracking") ---------------------------------------------------------------------
-// Tracking is on exactly while d_lab is allocated.
-#define AMC_NEED_TRACKING(who)                                                                                              \
-    if (!h->d_lab) return fail(AMC_ERR_STATE, who ": tracking is off (amc_set_tracking)")
-
 int amc_set_tracking(amc_handle* h, int on)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_tracking: NULL handle");
     AMC_HIP(hipSetDevice(h->device));
     if (!on) return tracking_off(h);
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_tracking: the handle has no ladder (amc_set_ladder)");
-    if (!h->d_lab) {
-        AMC_HIP(hipMalloc(&h->d_lab, (size_t)h->M));
-        const hipError_t e = hipMalloc(&h->d_track, TRACK_BYTES);
+    AMC_TRY(need_ladder(h, "amc_set_tracking"));
+    if (!h->lad.d_lab) {
+        AMC_HIP(hipMalloc(&h->lad.d_lab, (size_t)h->M));
+        const hipError_t e = hipMalloc(&h->lad.d_track, TRACK_BYTES);
         if (e != hipSuccess) {
-            (void)hipFree(h->d_lab);
-            h->d_lab = nullptr;
-            h->d_track = nullptr;
+            (void)hipFree(h->lad.d_lab);
+            h->lad.d_lab = nullptr;
+            h->lad.d_track = nullptr;
             return fail(e == hipErrorOutOfMemory ? AMC_ERR_OOM : AMC_ERR_HIP, "amc_set_tracking: %s", hipGetErrorString(e));
         }
     }
-    const int R = h->n_rungs;
+    const int R = h->lad.n_rungs;
     std::vector<uint8_t> lab((size_t)h->M);
     for (int64_t c = 0; c < h->M; ++c) {
         const int r = (int)(c % R);
         lab[(size_t)c] = (uint8_t)(r | (r == 0 ? amc::LAB_UP : r == R - 1 ? amc::LAB_DOWN : 0u));
     }
-    AMC_HIP(hipMemcpyAsync(h->d_lab, lab.data(), (size_t)h->M, hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipMemsetAsync(h->d_track, 0, TRACK_BYTES, h->stream));
+    AMC_HIP(hipMemcpyAsync(h->lad.d_lab, lab.data(), (size_t)h->M, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipMemsetAsync(h->lad.d_track, 0, TRACK_BYTES, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));      // `lab` is only valid during the call
     return AMC_OK;
 }
@@ -488,18 +491,16 @@ int amc_set_tracking(amc_handle* h, int on)
 int amc_download_labels(amc_handle* h, uint8_t* labels)
 {
     if (!h || !labels) return fail(AMC_ERR_BAD_ARG, "amc_download_labels: NULL argument");
-    AMC_NEED_TRACKING("amc_download_labels");
+    AMC_TRY(need_tracking(h, "amc_download_labels"));
     AMC_HIP(hipSetDevice(h->device));
-    AMC_HIP(hipMemcpyAsync(labels, h->d_lab, (size_t)h->M, hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
-    return AMC_OK;
+    return copy_to_host_sync(h, labels, h->lad.d_lab, (size_t)h->M);
 }
 
 int amc_upload_labels(amc_handle* h, const uint8_t* labels)
 {
     if (!h || !labels) return fail(AMC_ERR_BAD_ARG, "amc_upload_labels: NULL argument");
-    AMC_NEED_TRACKING("amc_upload_labels");
-    const int R = h->n_rungs;
+    AMC_TRY(need_tracking(h, "amc_upload_labels"));
+    const int R = h->lad.n_rungs;
     for (int64_t c0 = 0; c0 < h->M; c0 += R) {
         uint64_t seen = 0;
         for (int r = 0; r < R; ++r) {
@@ -516,39 +517,29 @@ int amc_upload_labels(amc_handle* h, const uint8_t* labels)
         }
     }
     AMC_HIP(hipSetDevice(h->device));
-    AMC_HIP(hipMemcpyAsync(h->d_lab, labels, (size_t)h->M, hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `labels` is only valid during the call
-    return AMC_OK;
+    return copy_to_device_sync(h, h->lad.d_lab, labels, (size_t)h->M);      // `labels` is only valid during the call
 }
 
 int amc_flow_rungs(amc_handle* h, uint64_t* counts)
 {
     if (!h || !counts) return fail(AMC_ERR_BAD_ARG, "amc_flow_rungs: NULL argument");
-    AMC_NEED_TRACKING("amc_flow_rungs");
+    AMC_TRY(need_tracking(h, "amc_flow_rungs"));
     AMC_HIP(hipSetDevice(h->device));
     // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    unsigned long long* d_flow = h->d_track + 2;
-    const size_t bytes = (size_t)(3 * h->n_rungs) * sizeof(unsigned long long);
-    AMC_HIP(hipMemsetAsync(d_flow, 0, bytes, h->stream));
-    const int grid = grid_for(h, (h->M + 3) / 4, h->knobs.blocks_per_cu ? 0 : EXCHANGE_BLOCKS_PER_CU);     // a thread per 4 labels; the atomics' tail again
-    hipLaunchKernelGGL(amc::rung_flow_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint8_t*)h->d_lab, h->M, h->n_rungs, d_flow);
-    AMC_HIP(hipGetLastError());
+    AMC_TRY(pg_resolve(h));
+    AMC_TRY(flow_snapshot_queue(h));
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "counts are copied as they are");
-    AMC_HIP(hipMemcpyAsync(counts, d_flow, bytes, hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
-    return AMC_OK;
+    return copy_to_host_sync(h, counts, h->lad.d_track + 2, (size_t)(3 * h->lad.n_rungs) * sizeof(unsigned long long));
 }
 
 int amc_tracking_counters(amc_handle* h, int64_t* round_trips, int64_t* up_trips)
 {
     if (!h || !round_trips || !up_trips) return fail(AMC_ERR_BAD_ARG, "amc_tracking_counters: NULL argument");
-    AMC_NEED_TRACKING("amc_tracking_counters");
+    AMC_TRY(need_tracking(h, "amc_tracking_counters"));
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
     unsigned long long host[2];
-    AMC_HIP(hipMemcpyAsync(host, h->d_track, sizeof host, hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    AMC_TRY(copy_to_host_sync(h, host, h->lad.d_track, sizeof host));
     *round_trips = (int64_t)host[0];
     *up_trips = (int64_t)host[1];
     return AMC_OK;
@@ -557,37 +548,27 @@ int amc_tracking_counters(amc_handle* h, int64_t* round_trips, int64_t* up_trips
 int amc_set_tracking_counters(amc_handle* h, int64_t round_trips, int64_t up_trips)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_tracking_counters: NULL handle");
-    AMC_NEED_TRACKING("amc_set_tracking_counters");
+    AMC_TRY(need_tracking(h, "amc_set_tracking_counters"));
     if (round_trips < 0 || up_trips < 0) return fail(AMC_ERR_BAD_ARG, "amc_set_tracking_counters: need round_trips >= 0 and up_trips >= 0");
     const unsigned long long host[2] = {(unsigned long long)round_trips, (unsigned long long)up_trips};
     AMC_HIP(hipSetDevice(h->device));
-    AMC_HIP(hipMemcpyAsync(h->d_track, host, sizeof host, hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
-    return AMC_OK;
+    return copy_to_device_sync(h, h->lad.d_track, host, sizeof host);      // `host` is only valid during the call
 }
 
 // ---- respacing the ladder (DESIGN.md section 3.13 "Respacing") -----------------------------------------------------------------------
-static int respace_record(amc_handle* h)
-{
-    if (h->d_respace) return AMC_OK;
-    AMC_HIP(hipMalloc(&h->d_respace, RESPACE_BYTES));
-    AMC_HIP(hipMemsetAsync(h->d_respace, 0, RESPACE_BYTES, h->stream));
-    return AMC_OK;
-}
-
 int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const uint64_t* counts)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_respace_ladder: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_respace_ladder"));
     if (rule != AMC_RESPACE_ACCEPTANCE && rule != AMC_RESPACE_FLOW)
         return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: rule = %d must be AMC_RESPACE_ACCEPTANCE (%d) or AMC_RESPACE_FLOW (%d)", rule,
                     AMC_RESPACE_ACCEPTANCE, AMC_RESPACE_FLOW);
     if (!(gamma > 0.0 && gamma <= 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: gamma = %g must lie in (0, 1]", gamma);
     if (!(eps >= 0.0 && eps < 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_respace_ladder: eps = %g must lie in [0, 1)", eps);
-    if (rule == AMC_RESPACE_FLOW && !counts && !h->d_lab)
+    if (rule == AMC_RESPACE_FLOW && !counts && !h->lad.d_lab)
         return fail(AMC_ERR_STATE, "amc_respace_ladder: rule AMC_RESPACE_FLOW with counts == NULL reads this handle's labels, and tracking is off "
                                    "(amc_set_tracking)");
-    const int R = h->n_rungs;
+    const int R = h->lad.n_rungs;
     amc::RespaceCounts given;
     std::memset(&given, 0, sizeof given);
     if (counts) {
@@ -600,23 +581,18 @@ int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const 
     }
     AMC_HIP(hipSetDevice(h->device));
     // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    { const int rc = respace_record(h); if (rc != AMC_OK) return rc; }
-    unsigned long long* d_flow = h->d_lab ? h->d_track + 2 : nullptr;
-    if (rule == AMC_RESPACE_FLOW && !counts) {      // the flow snapshot of this handle's labels, into amc_flow_rungs' scratch
-        AMC_HIP(hipMemsetAsync(d_flow, 0, (size_t)(3 * R) * sizeof(unsigned long long), h->stream));
-        const int grid = grid_for(h, (h->M + 3) / 4, h->knobs.blocks_per_cu ? 0 : EXCHANGE_BLOCKS_PER_CU);
-        hipLaunchKernelGGL(amc::rung_flow_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const uint8_t*)h->d_lab, h->M, R, d_flow);
-        AMC_HIP(hipGetLastError());
-    }
+    AMC_TRY(pg_resolve(h));
+    AMC_TRY(zeroed_words(h, &h->lad.d_respace, RESPACE_BYTES));
+    unsigned long long* d_flow = h->lad.d_lab ? h->lad.d_track + 2 : nullptr;
+    if (rule == AMC_RESPACE_FLOW && !counts) AMC_TRY(flow_snapshot_queue(h));      // of this handle's labels, into amc_flow_rungs' scratch
     amc::RespaceArgs a;
     a.beta = h->d_beta;
-    a.xcnt = h->d_xcnt;
+    a.xcnt = h->lad.d_xcnt;
     a.flow = d_flow;
-    a.gaps = h->d_xcnt;
-    a.trips = h->d_lab ? h->d_track : nullptr;
-    a.rec = h->d_respace;
-    a.bridge = h->d_bridge;
+    a.gaps = h->lad.d_xcnt;
+    a.trips = h->lad.d_lab ? h->lad.d_track : nullptr;
+    a.rec = h->lad.d_respace;
+    a.bridge = h->lad.d_bridge;
     a.bridge_words = amc::BRIDGE_WORDS;
     a.gamma = gamma;
     a.eps = eps;
@@ -626,8 +602,8 @@ int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const 
     a.counts_given = counts ? 1 : 0;
     hipLaunchKernelGGL(amc::ladder_respace_kernel, dim3(1), dim3(64), 0, h->stream, a, given);
     AMC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(amc::ladder_retile_kernel, dim3(grid_for(h, h->M)), dim3(AMC_BLOCK), 0, h->stream, (void*)h->d_beta, a.f32, h->d_lab, h->M / R, R,
-                       (const unsigned long long*)h->d_respace);
+    hipLaunchKernelGGL(amc::ladder_retile_kernel, dim3(grid_for(h, h->M)), dim3(AMC_BLOCK), 0, h->stream, (void*)h->d_beta, a.f32, h->lad.d_lab, h->M / R, R,
+                       (const unsigned long long*)h->lad.d_respace);
     AMC_HIP(hipGetLastError());
     return AMC_OK;
 }
@@ -635,11 +611,10 @@ int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const 
 int amc_respace_status(amc_handle* h, int* status, int64_t* n_respaced)
 {
     if (!h || !status || !n_respaced) return fail(AMC_ERR_BAD_ARG, "amc_respace_status: NULL argument");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_respace_status: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_respace_status"));
     unsigned long long host[2] = {0ull, 0ull};
     AMC_HIP(hipSetDevice(h->device));
-    if (h->d_respace) AMC_HIP(hipMemcpyAsync(host, h->d_respace, sizeof host, hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    AMC_TRY(copy_to_host_sync(h, host, h->lad.d_respace, sizeof host));
     *status = (int)host[amc::RESPACE_STATUS];
     *n_respaced = (int64_t)host[amc::RESPACE_COUNT];
     return AMC_OK;
@@ -648,47 +623,35 @@ int amc_respace_status(amc_handle* h, int* status, int64_t* n_respaced)
 int amc_set_respaced(amc_handle* h, int64_t n_respaced)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_respaced: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_set_respaced: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_set_respaced"));
     if (n_respaced < 0) return fail(AMC_ERR_BAD_ARG, "amc_set_respaced: n_respaced < 0");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = respace_record(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(zeroed_words(h, &h->lad.d_respace, RESPACE_BYTES));
     const unsigned long long host = (unsigned long long)n_respaced;
-    AMC_HIP(hipMemcpyAsync(h->d_respace + amc::RESPACE_COUNT, &host, sizeof host, hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
-    return AMC_OK;
+    return copy_to_device_sync(h, h->lad.d_respace + amc::RESPACE_COUNT, &host, sizeof host);      // `host` is only valid during the call
 }
 
 int amc_get_ladder(amc_handle* h, double* betas)
 {
     if (!h || !betas) return fail(AMC_ERR_BAD_ARG, "amc_get_ladder: NULL argument");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_get_ladder: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_get_ladder"));
     AMC_HIP(hipSetDevice(h->device));
     double host[AMC_MAX_RUNGS];      // the first local ladder as the device holds it
     float host32[AMC_MAX_RUNGS];
-    const int R = h->n_rungs;
-    if (h->f32) AMC_HIP(hipMemcpyAsync(host32, h->d_beta, (size_t)R * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    else AMC_HIP(hipMemcpyAsync(host, h->d_beta, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    const int R = h->lad.n_rungs;
+    AMC_TRY(h->f32 ? copy_to_host_sync(h, host32, h->d_beta, (size_t)R * sizeof(float)) : copy_to_host_sync(h, host, h->d_beta, (size_t)R * sizeof(double)));
     for (int r = 0; r < R; ++r) betas[r] = h->f32 ? (double)host32[r] : host[r];
     return AMC_OK;
 }
 
 // ---- tuning the widths per rung (DESIGN.md section 3.13 "Tuning the widths") -----------------------------------------------------------
-static int zeroed_words(amc_handle* h, unsigned long long** p, size_t bytes)
-{
-    if (*p) return AMC_OK;
-    AMC_HIP(hipMalloc(p, bytes));
-    AMC_HIP(hipMemsetAsync(*p, 0, bytes, h->stream));
-    return AMC_OK;
-}
-
 // What every entry of the window needs: a ladder, per-chain counters, cells that fit the base.
 static int window_state(amc_handle* h, const char* who)
 {
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "%s: the handle has no ladder (amc_set_ladder)", who);
+    AMC_TRY(need_ladder(h, who));
     if (!h->counters) return fail(AMC_ERR_STATE, "%s: handle was created with per_chain_counters = 0", who);
-    if (h->K * h->n_rungs > AMC_MAX_MOVES)
-        return fail(AMC_ERR_STATE, "%s: %d moves x %d rungs = %d cells, the window holds %d", who, h->K, h->n_rungs, h->K * h->n_rungs, AMC_MAX_MOVES);
+    if (h->K * h->lad.n_rungs > AMC_MAX_MOVES)
+        return fail(AMC_ERR_STATE, "%s: %d moves x %d rungs = %d cells, the window holds %d", who, h->K, h->lad.n_rungs, h->K * h->lad.n_rungs, AMC_MAX_MOVES);
     return AMC_OK;
 }
 
@@ -696,29 +659,29 @@ static amc::TuneArgs tune_args(const amc_handle* h)
 {
     amc::TuneArgs a;
     std::memset(&a, 0, sizeof a);
-    a.rung_tab = h->d_rung_tab;
-    a.cnt = h->d_rung_cnt;
-    a.base = h->d_rung_base;
-    a.rec = h->d_tune;
-    a.steps_per_rung = (h->t_base + h->t_counted) * (uint64_t)(h->M / h->n_rungs);
+    a.rung_tab = h->lad.d_rung_tab;
+    a.cnt = h->lad.d_rung_cnt;
+    a.base = h->lad.d_rung_base;
+    a.rec = h->lad.d_tune;
+    a.steps_per_rung = (h->t_base + h->t_counted) * (uint64_t)(h->M / h->lad.n_rungs);
     a.n_moves = h->K;
-    a.n_rungs = h->n_rungs;
+    a.n_rungs = h->lad.n_rungs;
     return a;
 }
 
 int amc_tune_rung_sigma(amc_handle* h, double target, double gamma, int64_t min_calls, double sigma_lo, double sigma_hi, const int64_t* counts)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: NULL handle");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_tune_rung_sigma: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_tune_rung_sigma"));
     if (!h->counters) return fail(AMC_ERR_STATE, "amc_tune_rung_sigma: handle was created with per_chain_counters = 0");
-    if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_tune_rung_sigma: no widths per rung are set (amc_set_rung_sigma)");
+    if (!h->lad.rung_on) return fail(AMC_ERR_STATE, "amc_tune_rung_sigma: no widths per rung are set (amc_set_rung_sigma)");
     if (!(target > 0.0 && target < 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: target = %g must lie in (0, 1)", target);
     if (!(gamma > 0.0 && gamma <= 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: gamma = %g must lie in (0, 1]", gamma);
     if (min_calls < 1) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: min_calls = %lld must be at least 1", (long long)min_calls);
     if (!(sigma_lo >= 1e-100 && sigma_lo <= 1e100)) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: sigma_lo = %g must lie in [1e-100, 1e100]", sigma_lo);
     if (!(sigma_hi >= 1e-100 && sigma_hi <= 1e100)) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: sigma_hi = %g must lie in [1e-100, 1e100]", sigma_hi);
     if (sigma_lo > sigma_hi) return fail(AMC_ERR_BAD_ARG, "amc_tune_rung_sigma: sigma_lo = %g is above sigma_hi = %g", sigma_lo, sigma_hi);
-    const int R = h->n_rungs, n = h->K * R;      // (n <= AMC_MAX_MOVES: amc_set_rung_sigma)
+    const int R = h->lad.n_rungs, n = h->K * R;      // (n <= AMC_MAX_MOVES: amc_set_rung_sigma)
     amc::TuneCounts given;
     std::memset(&given, 0, sizeof given);
     if (counts) {
@@ -733,10 +696,10 @@ int amc_tune_rung_sigma(amc_handle* h, double target, double gamma, int64_t min_
     }
     AMC_HIP(hipSetDevice(h->device));
     // (as in front of amc_set_rung_sigma: a learning step left pending belongs in front of this point of the stream)
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    { const int rc = zeroed_words(h, &h->d_rung_base, RUNG_BASE_BYTES); if (rc != AMC_OK) return rc; }
-    { const int rc = zeroed_words(h, &h->d_tune, TUNE_BYTES); if (rc != AMC_OK) return rc; }
-    { const int rc = rung_totals_queue(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
+    AMC_TRY(zeroed_words(h, &h->lad.d_rung_base, RUNG_BASE_BYTES));
+    AMC_TRY(zeroed_words(h, &h->lad.d_tune, TUNE_BYTES));
+    AMC_TRY(rung_totals_queue(h));
     amc::TuneArgs a = tune_args(h);
     a.min_calls = (unsigned long long)min_calls;
     a.target = target;
@@ -746,20 +709,19 @@ int amc_tune_rung_sigma(amc_handle* h, double target, double gamma, int64_t min_
     a.counts_given = counts ? 1 : 0;
     hipLaunchKernelGGL(amc::rung_sigma_tune_kernel, dim3(1), dim3(AMC_MAX_MOVES), 0, h->stream, a, given);
     AMC_HIP(hipGetLastError());
-    h->tune_queued = true;
+    h->lad.tune_queued = true;
     return AMC_OK;
 }
 
 int amc_tune_status(amc_handle* h, int* st, int n, int64_t* n_tuned)
 {
     if (!h || !st || !n_tuned) return fail(AMC_ERR_BAD_ARG, "amc_tune_status: NULL argument");
-    if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_tune_status: no widths per rung are set (amc_set_rung_sigma)");
-    if (n != h->K * h->n_rungs)
-        return fail(AMC_ERR_BAD_ARG, "amc_tune_status: n = %d, the table of %d moves x %d rungs has %d entries", n, h->K, h->n_rungs, h->K * h->n_rungs);
+    if (!h->lad.rung_on) return fail(AMC_ERR_STATE, "amc_tune_status: no widths per rung are set (amc_set_rung_sigma)");
+    if (n != h->K * h->lad.n_rungs)
+        return fail(AMC_ERR_BAD_ARG, "amc_tune_status: n = %d, the table of %d moves x %d rungs has %d entries", n, h->K, h->lad.n_rungs, h->K * h->lad.n_rungs);
     unsigned long long host[1 + AMC_MAX_MOVES] = {0ull};
     AMC_HIP(hipSetDevice(h->device));
-    if (h->d_tune) AMC_HIP(hipMemcpyAsync(host, h->d_tune, (size_t)(1 + n) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    AMC_TRY(copy_to_host_sync(h, host, h->lad.d_tune, (size_t)(1 + n) * sizeof(unsigned long long)));
     *n_tuned = (int64_t)host[amc::TUNE_COUNT];
     for (int e = 0; e < n; ++e) st[e] = (int)host[amc::TUNE_ST + e];
     return AMC_OK;
@@ -768,23 +730,21 @@ int amc_tune_status(amc_handle* h, int* st, int n, int64_t* n_tuned)
 int amc_set_tuned(amc_handle* h, int64_t n_tuned)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_tuned: NULL handle");
-    if (!h->rung_on) return fail(AMC_ERR_STATE, "amc_set_tuned: no widths per rung are set (amc_set_rung_sigma)");
+    if (!h->lad.rung_on) return fail(AMC_ERR_STATE, "amc_set_tuned: no widths per rung are set (amc_set_rung_sigma)");
     if (n_tuned < 0) return fail(AMC_ERR_BAD_ARG, "amc_set_tuned: n_tuned < 0");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = zeroed_words(h, &h->d_tune, TUNE_BYTES); if (rc != AMC_OK) return rc; }
+    AMC_TRY(zeroed_words(h, &h->lad.d_tune, TUNE_BYTES));
     const unsigned long long host = (unsigned long long)n_tuned;
-    AMC_HIP(hipMemcpyAsync(h->d_tune + amc::TUNE_COUNT, &host, sizeof host, hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
-    return AMC_OK;
+    return copy_to_device_sync(h, h->lad.d_tune + amc::TUNE_COUNT, &host, sizeof host);      // `host` is only valid during the call
 }
 
 int amc_rung_window_restart(amc_handle* h)
 {
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_rung_window_restart: NULL handle");
-    { const int rc = window_state(h, "amc_rung_window_restart"); if (rc != AMC_OK) return rc; }
+    AMC_TRY(window_state(h, "amc_rung_window_restart"));
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = zeroed_words(h, &h->d_rung_base, RUNG_BASE_BYTES); if (rc != AMC_OK) return rc; }
-    { const int rc = rung_totals_queue(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(zeroed_words(h, &h->lad.d_rung_base, RUNG_BASE_BYTES));
+    AMC_TRY(rung_totals_queue(h));
     const amc::TuneArgs a = tune_args(h);
     hipLaunchKernelGGL(amc::rung_window_restart_kernel, dim3(1), dim3(AMC_MAX_MOVES), 0, h->stream, a);
     AMC_HIP(hipGetLastError());
@@ -794,12 +754,11 @@ int amc_rung_window_restart(amc_handle* h)
 int amc_rung_window_base(amc_handle* h, int64_t* accepted, int64_t* total)
 {
     if (!h || !accepted || !total) return fail(AMC_ERR_BAD_ARG, "amc_rung_window_base: NULL argument");
-    { const int rc = window_state(h, "amc_rung_window_base"); if (rc != AMC_OK) return rc; }
-    const int n = h->K * h->n_rungs;
+    AMC_TRY(window_state(h, "amc_rung_window_base"));
+    const int n = h->K * h->lad.n_rungs;
     unsigned long long host[amc::RUNG_BASE_WORDS] = {0ull};
     AMC_HIP(hipSetDevice(h->device));
-    if (h->d_rung_base) AMC_HIP(hipMemcpyAsync(host, h->d_rung_base, RUNG_BASE_BYTES, hipMemcpyDeviceToHost, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));
+    AMC_TRY(copy_to_host_sync(h, host, h->lad.d_rung_base, RUNG_BASE_BYTES));
     for (int e = 0; e < n; ++e) {
         accepted[e] = (int64_t)host[e];
         total[e] = (int64_t)host[AMC_MAX_MOVES + e];
@@ -810,8 +769,8 @@ int amc_rung_window_base(amc_handle* h, int64_t* accepted, int64_t* total)
 int amc_set_rung_window_base(amc_handle* h, const int64_t* accepted, const int64_t* total)
 {
     if (!h || !accepted || !total) return fail(AMC_ERR_BAD_ARG, "amc_set_rung_window_base: NULL argument");
-    { const int rc = window_state(h, "amc_set_rung_window_base"); if (rc != AMC_OK) return rc; }
-    const int R = h->n_rungs, n = h->K * R;
+    AMC_TRY(window_state(h, "amc_set_rung_window_base"));
+    const int R = h->lad.n_rungs, n = h->K * R;
     unsigned long long host[amc::RUNG_BASE_WORDS] = {0ull};
     for (int e = 0; e < n; ++e) {
         if (accepted[e] < 0 || total[e] < 0)
@@ -820,20 +779,18 @@ int amc_set_rung_window_base(amc_handle* h, const int64_t* accepted, const int64
         host[AMC_MAX_MOVES + e] = (unsigned long long)total[e];
     }
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = zeroed_words(h, &h->d_rung_base, RUNG_BASE_BYTES); if (rc != AMC_OK) return rc; }
-    AMC_HIP(hipMemcpyAsync(h->d_rung_base, host, RUNG_BASE_BYTES, hipMemcpyHostToDevice, h->stream));
-    AMC_HIP(hipStreamSynchronize(h->stream));      // `host` is only valid during the call
-    return AMC_OK;
+    AMC_TRY(zeroed_words(h, &h->lad.d_rung_base, RUNG_BASE_BYTES));
+    return copy_to_device_sync(h, h->lad.d_rung_base, host, RUNG_BASE_BYTES);      // `host` is only valid during the call
 }
 
 int amc_rung_window_counts(amc_handle* h, int64_t* accepted, int64_t* total)
 {
     if (!h || !accepted || !total) return fail(AMC_ERR_BAD_ARG, "amc_rung_window_counts: NULL argument");
-    { const int rc = window_state(h, "amc_rung_window_counts"); if (rc != AMC_OK) return rc; }
-    const int n = h->K * h->n_rungs;
+    AMC_TRY(window_state(h, "amc_rung_window_counts"));
+    const int n = h->K * h->lad.n_rungs;
     int64_t base_acc[AMC_MAX_MOVES], base_tot[AMC_MAX_MOVES];
-    { const int rc = amc_rung_window_base(h, base_acc, base_tot); if (rc != AMC_OK) return rc; }
-    { const int rc = amc_rung_counter_totals(h, accepted, total); if (rc != AMC_OK) return rc; }
+    AMC_TRY(amc_rung_window_base(h, base_acc, base_tot));
+    AMC_TRY(amc_rung_counter_totals(h, accepted, total));
     for (int e = 0; e < n; ++e) {
         if (accepted[e] < base_acc[e] || total[e] < base_tot[e]) {      // counters uploaded or restored behind the base
             accepted[e] = total[e] = -1;

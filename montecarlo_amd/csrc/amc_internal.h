@@ -60,6 +60,13 @@ AMC_INTERNAL int fail(int code, const char* fmt, ...);
                         #call, hipGetErrorString(e_));                                             \
     } while (0)
 
+// A call that returns an amc_status: anything but AMC_OK is the caller's return value too (its message is already left).
+#define AMC_TRY(expr)                                                                              \
+    do {                                                                                           \
+        const int rc_ = (expr);                                                                    \
+        if (rc_ != AMC_OK) return rc_;                                                             \
+    } while (0)
+
 // ---- environment variables --------------------------------------------------------------------------------
 // Every AMC_* variable libamc.so reads is listed here and read through amc_env() (amc_api.hip), and nowhere else.  Handle knobs are
 // read by amc_knobs() in one go: amc_create copies them into the handle, which keeps them for its life; amc_model_check and
@@ -153,20 +160,13 @@ struct ModelSpec {
     std::string cache_text() const;          // the model in the code-object caches' keys (amc_rtc.hip)
 };
 
-struct amc_handle {
-    AmcKnobs knobs;             // the environment's knobs as amc_create found them
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int64_t M = 0, M_pad = 0, offset = 0, M_global = 0;
-    int potential = 0, K = 1, sweepstep = 1;
-    bool counters = false;      // per-chain counters kept
-    bool beta_arr = false;
-    double beta = 1.0;
-    uint64_t seed = 0;
-    uint64_t t = 0;             // MH steps done (Philox step index)
-    uint64_t t_counted = 0;     // MH steps counted in acc/tot since creation
-    uint64_t t_est = 0;         // estimator calls done
+// ---- state that is owned together: declared, reset and freed together -----------------------------------------------------------------
+// Two plain structs the handle holds by value.  Below each is its one release function, which frees every device pointer the struct
+// declares (tests/test_handle_state_static.py holds it to that); amc_destroy calls the two.
+
+// The temperature ladder and what belongs to it (amc_exchange.hip; the totals per rung: amc_counters.hip).  amc_set_ladder forgets all
+// of it but the memory (ladder_reset).
+struct LadderState {
     int n_rungs = 0;            // R of the temperature ladder (amc_set_ladder); 0: none
     uint64_t t_x = 0;           // exchange steps done (their own Philox step index; its parity picks the gaps)
     unsigned long long* d_xcnt = nullptr;   // [2][AMC_MAX_RUNGS] exchange attempts and accepted swaps per gap (allocated with the ladder)
@@ -192,8 +192,25 @@ struct amc_handle {
     unsigned long long* d_rung_base = nullptr;  // [RUNG_BASE_WORDS] accepted, total per (move, rung) at the start of the window (zeroed by amc_set_ladder)
     unsigned long long* d_tune = nullptr;       // [TUNE_WORDS] the record of the tunings (zeroed by amc_set_rung_sigma and amc_set_ladder)
     bool tune_queued = false;                   // a tuning has been queued since the table was set: the device holds the table (amc_get_rung_sigma)
-    // Population annealing (amc_anneal.hip): all of it allocated at its first use -- a handle that never anneals
-    // has none
+};
+static inline void ladder_release(LadderState& s)
+{
+    (void)hipFree(s.d_xcnt);
+    (void)hipFree(s.d_rung_rows);
+    (void)hipFree(s.d_rung_recs);
+    (void)hipFree(s.d_bridge);
+    (void)hipFree(s.d_lab);
+    (void)hipFree(s.d_track);
+    (void)hipFree(s.d_respace);
+    (void)hipFree(s.d_rung_tab);
+    (void)hipFree(s.d_rung_cnt);
+    (void)hipFree(s.d_rung_base);
+    (void)hipFree(s.d_tune);
+}
+
+// Population annealing (amc_anneal.hip): all of it allocated at its first use -- a handle that never anneals
+// has none
+struct AnnealState {
     uint64_t t_a = 0;                           // annealing steps done (their own Philox step index)
     double* d_x_alt = nullptr;                  // [M_pad] the second position buffer: a step gathers d_x into it, then the two change places
     unsigned long long* d_anneal_n = nullptr;   // [M] one word per chain: the bits of a_i, then W_i, then N_i (amc_anneal.h)
@@ -204,6 +221,35 @@ struct amc_handle {
     uint32_t* d_fam = nullptr;                  // [M] family id per chain; allocated exactly while families are on (amc_set_anneal_families)
     uint32_t* d_fam_alt = nullptr;              // [M] ... and the buffer a step gathers them into
     unsigned int* d_fam_cnt = nullptr;          // [M] + 3 words: scratch of amc_anneal_family_stats (allocated at its first call)
+};
+static inline void anneal_release(AnnealState& s)
+{
+    (void)hipFree(s.d_x_alt);
+    (void)hipFree(s.d_anneal_n);
+    (void)hipFree(s.d_anneal_tiles);
+    (void)hipFree(s.d_anneal_s);
+    (void)hipFree(s.d_anneal_log);
+    (void)hipFree(s.d_fam);
+    (void)hipFree(s.d_fam_alt);
+    (void)hipFree(s.d_fam_cnt);
+}
+
+struct amc_handle {
+    AmcKnobs knobs;             // the environment's knobs as amc_create found them
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int64_t M = 0, M_pad = 0, offset = 0, M_global = 0;
+    int potential = 0, K = 1, sweepstep = 1;
+    bool counters = false;      // per-chain counters kept
+    bool beta_arr = false;
+    double beta = 1.0;
+    uint64_t seed = 0;
+    uint64_t t = 0;             // MH steps done (Philox step index)
+    uint64_t t_counted = 0;     // MH steps counted in acc/tot since creation
+    uint64_t t_est = 0;         // estimator calls done
+    LadderState lad;            // the temperature ladder and what hangs on it (amc_exchange.hip)
+    AnnealState ann;            // population annealing (amc_anneal.hip)
     double* d_x = nullptr;
     double* d_beta = nullptr;
     uint32_t* d_acc = nullptr;
@@ -313,10 +359,32 @@ struct amc_handle {
     std::vector<hipModule_t> rtc_mods;
 };
 
+// What an entry needs of the handle's state before it does anything: a refusal with the entry's name, through AMC_TRY.  Tracking is on
+// exactly while d_lab is allocated, the families exactly while d_fam is.
+static inline int need_ladder(const amc_handle* h, const char* who)
+{
+    return h->lad.n_rungs ? AMC_OK : fail(AMC_ERR_STATE, "%s: the handle has no ladder (amc_set_ladder)", who);
+}
+static inline int need_tracking(const amc_handle* h, const char* who)
+{
+    return h->lad.d_lab ? AMC_OK : fail(AMC_ERR_STATE, "%s: tracking is off (amc_set_tracking)", who);
+}
+static inline int need_families(const amc_handle* h, const char* who)
+{
+    return h->ann.d_fam ? AMC_OK : fail(AMC_ERR_STATE, "%s: families are off (amc_set_anneal_families)", who);
+}
+
 // ---- shared between the translation units ----------------------------------------------------------------------------------------
 AMC_INTERNAL int grid_for(const amc_handle* h, int64_t n_items, int blocks_per_cu = 0);   // amc_api.hip
 AMC_INTERNAL hipError_t wait_stream(hipStream_t stream);                                  // amc_state.hip
 AMC_INTERNAL hipError_t wait_event(hipEvent_t ev);
+// A few words copied on the handle's stream, then hipStreamSynchronize: the caller's buffer is only valid during the call (to the device)
+// or is read right after it (to the host).  A null d_src copies nothing and still waits: the caller's zeroed words stand for a buffer
+// that was never allocated.  (The runtime's blocking wait, as these entries always used, not wait_stream's spin.)
+AMC_INTERNAL int copy_to_host_sync(amc_handle* h, void* dst, const void* d_src, size_t bytes);
+AMC_INTERNAL int copy_to_device_sync(amc_handle* h, void* d_dst, const void* src, size_t bytes);
+// *p allocated at its first use and zeroed on the stream then; nothing when it exists
+AMC_INTERNAL int zeroed_words(amc_handle* h, unsigned long long** p, size_t bytes);
 AMC_INTERNAL int log_form(const amc_handle* h);                                           // amc_counters.hip
 AMC_INTERNAL int log_room(amc_handle* h, int* rows);
 AMC_INTERNAL int fold_log(amc_handle* h, bool with_ratio = false, int* ratio_rows = nullptr, amc::xs_word* ratio_dst = nullptr);
@@ -343,7 +411,7 @@ AMC_INTERNAL int check_sigma_f32(const char* who, int k, double s);     // a sig
 // ... and it learns one sigma per move: while a table of widths per rung is set (amc_set_rung_sigma) its entries refuse the handle too.
 #define AMC_REFUSE_RUNG_SIGMA(h, who)                                                                                       \
     do {                                                                                                                    \
-        if ((h)->rung_on)                                                                                                   \
+        if ((h)->lad.rung_on)                                                                                               \
             return fail(AMC_ERR_STATE, "%s: not available while widths per rung are set (amc_set_rung_sigma): the estimator learns one sigma per move", (who)); \
     } while (0)
 AMC_INTERNAL int pg_resolve(amc_handle* h);      // takes a pending learning step now (amc_pg.hip)

@@ -25,7 +25,7 @@ static int launch_prepare_params(amc_handle* h)
 
 int push_params(amc_handle* h, const double* sigma, const double* weight)
 {
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
     std::vector<double> tab((size_t)amc::PT_ROWS * AMC_MAX_MOVES, 0.0);
     AMC_HIP(hipMemcpyAsync(tab.data(), h->d_ptab, tab.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));
@@ -35,7 +35,7 @@ int push_params(amc_handle* h, const double* sigma, const double* weight)
     }
     AMC_HIP(hipMemcpyAsync(h->d_ptab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));   // tab is a stack-scoped host buffer
-    { const int rc = launch_prepare_params(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(launch_prepare_params(h));
     if (weight && h->K > 1) {      // the cumulative weights changed: rebuild the 12-bit move-pick table from them
         hipLaunchKernelGGL(amc::prepare_pick_kernel, dim3(AMC_PICK_CELLS / AMC_BLOCK), dim3(AMC_BLOCK), 0, h->stream, h->d_ptab, h->K,
                            h->d_pick);
@@ -70,8 +70,7 @@ int amc_set_parameters(amc_handle* h, int k, const double* p, int n)
                                                      : "amc_set_parameters: this handle's policy has %d parameters", h->n_params);
     if (h->n_params == 1) {
         if (h->param_f32) {
-            const int rc = check_sigma_f32("amc_set_parameters", k, p[0]);
-            if (rc != AMC_OK) return rc;
+            AMC_TRY(check_sigma_f32("amc_set_parameters", k, p[0]));
         } else if (!(p[0] >= 1e-100) || !(p[0] <= 1e100))
             return fail(AMC_ERR_BAD_ARG, "amc_set_parameters: sigma must lie in [1e-100, 1e100] (got %.17g)", p[0]);
     } else {
@@ -79,13 +78,12 @@ int amc_set_parameters(amc_handle* h, int k, const double* p, int n)
             if (!(p[i] - p[i] == 0.0)) return fail(AMC_ERR_BAD_ARG, "amc_set_parameters: parameter %d is not finite", i);
     }
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
     for (int i = 0; i < n; ++i)
         AMC_HIP(hipMemcpyAsync(h->d_ptab + theta_row(i) * AMC_MAX_MOVES + k, p + i, sizeof(double), hipMemcpyHostToDevice, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));
     if (h->n_params == 1) {            // what derives from sigma (the script kernels of a policy with several parameters read none of it)
-        const int rc = launch_prepare_params(h);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(launch_prepare_params(h));
     }
     return AMC_OK;
 }
@@ -98,7 +96,7 @@ int amc_get_parameters(amc_handle* h, int k, double* p, int n)
         return fail(AMC_ERR_BAD_ARG, h->n_params == 1 ? "amc_get_parameters: StandardGaussian has exactly 1 parameter (sigma)"
                                                      : "amc_get_parameters: this handle's policy has %d parameters", h->n_params);
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
     for (int i = 0; i < n; ++i)
         AMC_HIP(hipMemcpyAsync(p + i, h->d_ptab + theta_row(i) * AMC_MAX_MOVES + k, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));
@@ -118,7 +116,7 @@ int amc_parameters_begin(amc_handle* h)
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_parameters_begin: NULL handle");
     if (h->params_pending) return fail(AMC_ERR_STATE, "amc_parameters_begin: a read is already in flight (call amc_parameters_end)");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
     AMC_HIP(hipMemcpyAsync(h->h_params, h->d_ptab + amc::PT_SIGMA * AMC_MAX_MOVES, (size_t)h->K * sizeof(double), hipMemcpyDeviceToHost,
                            h->stream));
     if (h->n_params > 1)         // parameters 1 .. P - 1: consecutive rows of the table

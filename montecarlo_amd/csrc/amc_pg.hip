@@ -97,7 +97,7 @@ int launch_pg_custom(amc_handle* h, amc::PgArgs& a, amc::SweepArgs& sw, int grid
                              std::to_string(sweep) + "," + std::to_string(reduce ? red_form(h) : (int)amc::RED_FORM_NONE) + "," + tf(mid) + ">";
     if (grid < 0) {            // a query: how many blocks of this form a CU holds
         hipFunction_t fn = nullptr;
-        { const int rc = rtc_function(h, inst, &fn); if (rc != AMC_OK) return rc; }
+        AMC_TRY(rtc_function(h, inst, &fn));
         int nb = 0;
         AMC_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, AMC_BLOCK, 0));
         h->occ_query = nb;
@@ -176,14 +176,14 @@ static int pg_plan(amc_handle* h, int nl, int sweep, bool reduce, int q_batch, P
     };
     auto grid_of = [&](int per_cu) { const int g = grid_for(h, pairs, per_cu); return g > limit ? limit : g; };
     int per_cu = 0;
-    { const int rc = resident(false, &per_cu); if (rc != AMC_OK) return rc; }
+    AMC_TRY(resident(false, &per_cu));
     plan->grid = grid_of(per_cu);
     plan->mid = !fits(plan->grid);
     if (plan->mid && h->blocks_per_cu_pg == 0) {
         const int two = grid_of(2 * per_cu);
         if (fits(two)) { plan->grid = two; plan->mid = false; return AMC_OK; }
         // the flushing form, on two rounds of ITS resident blocks (3 % faster than on one: q_batch 4, 143.6 -> 138.8 us)
-        { const int rc = resident(true, &per_cu); if (rc != AMC_OK) return rc; }
+        AMC_TRY(resident(true, &per_cu));
         plan->grid = grid_of(2 * per_cu);
     }
     return AMC_OK;
@@ -317,8 +317,7 @@ static int pg_launch(amc_handle* h, const char* who, int n_learn, const int* lea
                 h->pend.active = false;
                 h->pend_consumed = true;
             } else {
-                const int rcr = pg_resolve(h);
-                if (rcr != AMC_OK) return rcr;
+                AMC_TRY(pg_resolve(h));
             }
         }
         if (!h->pg_tail_valid || std::memcmp(&tl, &h->pg_tail_host, sizeof(tl)) != 0) {
@@ -333,13 +332,13 @@ static int pg_launch(amc_handle* h, const char* who, int n_learn, const int* lea
     const int nl = nl_capacity(n_learn);
     int sweep = 0;
     if (with_sweep) {
-        { const int rcc = counter_room(h, who, 1); if (rcc != AMC_OK) return rcc; }
+        AMC_TRY(counter_room(h, who, 1));
         if (h->d_log) { int room = 0; const int rcf = log_room(h, &room); if (rcf != AMC_OK) return rcf; }
         sweep = h->K > 1 ? 2 : (h->d_log ? 1 : 3);
     }
     const bool red = reduce && with_sweep;
     PgPlan plan;
-    { const int rcp = pg_plan(h, nl, sweep, red, q_batch, &plan); if (rcp != AMC_OK) return rcp; }
+    AMC_TRY(pg_plan(h, nl, sweep, red, q_batch, &plan));
     const int grid = plan.grid;
     const bool mid = plan.mid;
     if (grid_out) *grid_out = grid;
@@ -378,8 +377,8 @@ static int pg_estimate_records(amc_handle* h, const char* who, int n_learn, cons
 {
     int nl = 0;
     bool general = true;
-    { const int rcc = pg_check_call(h, who, n_learn, learn_ids, q_batch); if (rcc != AMC_OK) return rcc; }
-    { const int rcg = class_general_route(h, n_learn, false, false, q_batch, &general); if (rcg != AMC_OK) return rcg; }
+    AMC_TRY(pg_check_call(h, who, n_learn, learn_ids, q_batch));
+    AMC_TRY(class_general_route(h, n_learn, false, false, q_batch, &general));
     if (per_move_launches(h) || !general) {
         // one launch per learnable move, its 1 + 2P + P(P+1)/2 records behind those of the moves before it
         if (n_learn < 0 || n_learn > AMC_MAX_LEARN) return fail(AMC_ERR_BAD_ARG, "%s: n_learn must be in [0, %d]", who, AMC_MAX_LEARN);
@@ -388,8 +387,7 @@ static int pg_estimate_records(amc_handle* h, const char* who, int n_learn, cons
         const int slot = h->comm ? h->comm_rank : 0;
         const size_t n = (size_t)nc * amc::xs::XS_WORDS;
         for (int l = 0; l < n_learn; ++l) {
-            const int rc = pg_launch(h, who, 1, learn_ids + l, q_batch, &nl, 1, nullptr, false, false, nullptr, l, l + 1 == n_learn);
-            if (rc != AMC_OK) return rc;
+            AMC_TRY(pg_launch(h, who, 1, learn_ids + l, q_batch, &nl, 1, nullptr, false, false, nullptr, l, l + 1 == n_learn));
             AMC_HIP(hipMemcpyAsync(h->h_pg_out + (size_t)l * n, h->d_out + (size_t)slot * n, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         }
         AMC_HIP(wait_stream(h->stream));
@@ -508,8 +506,8 @@ static int pg_accumulate_impl(amc_handle* h, int n_learn, const int* learn_ids, 
 {
     int nl = 0;
     bool general = true;
-    { const int rcc = pg_check_call(h, "amc_pg_accumulate", n_learn, learn_ids, q_batch); if (rcc != AMC_OK) return rcc; }
-    { const int rcg = class_general_route(h, n_learn, with_sweep, reduce, q_batch, &general); if (rcg != AMC_OK) return rcg; }
+    AMC_TRY(pg_check_call(h, "amc_pg_accumulate", n_learn, learn_ids, q_batch));
+    AMC_TRY(class_general_route(h, n_learn, with_sweep, reduce, q_batch, &general));
     if (np_move_chain(h, n_learn)) {
         // several parameters, several learnable moves, one shard: one launch per move whose own tail folds, accumulates and (opt) takes
         // the move's learning step -- what np_single_launch does for one move, move after move.  A move's estimator reads its own
@@ -518,9 +516,8 @@ static int pg_accumulate_impl(amc_handle* h, int n_learn, const int* learn_ids, 
         uint64_t ids_mask = 0;
         for (int l = 0; l < n_learn; ++l) {
             // (with_sweep: the time step's make_step!(::Metropolis) rides in the first move's launch, as in the one-move fused step)
-            const int rc = pg_launch(h, "amc_pg_accumulate", 1, learn_ids + l, q_batch, &nl, opt ? 3 : 2, opt, with_sweep && l == 0, false, nullptr, l,
-                                     l + 1 == n_learn, learn_ids, n_learn);
-            if (rc != AMC_OK) return rc;
+            AMC_TRY(pg_launch(h, "amc_pg_accumulate", 1, learn_ids + l, q_batch, &nl, opt ? 3 : 2, opt, with_sweep && l == 0, false, nullptr, l,
+                              l + 1 == n_learn, learn_ids, n_learn));
             ids_mask |= 1ull << (learn_ids[l] & 63);
         }
         if (opt) h->gd_nonzero &= ~ids_mask;
@@ -574,7 +571,7 @@ static int pg_accumulate_impl(amc_handle* h, int n_learn, const int* learn_ids, 
     // reference's order (move-major), the draws are named by the move's index in the call (l_base): the same bits.
     if (!shards && !with_sweep && n_learn > 4 && !h->use_rtc && !h->knobs.np_small_launches) {
         PgPlan whole;
-        { const int rcp = pg_plan(h, nl_capacity(n_learn), 0, false, q_batch, &whole); if (rcp != AMC_OK) return rcp; }
+        AMC_TRY(pg_plan(h, nl_capacity(n_learn), 0, false, q_batch, &whole));
         if (whole.mid) {
             for (int base = 0; base < n_learn; base += 4) {
                 const int n = n_learn - base < 4 ? n_learn - base : 4;
@@ -583,9 +580,8 @@ static int pg_accumulate_impl(amc_handle* h, int n_learn, const int* learn_ids, 
                     sub = *opt;
                     for (int l = 0; l < n; ++l) { sub.kind[l] = opt->kind[base + l]; sub.h0[l] = opt->h0[base + l]; sub.h1[l] = opt->h1[base + l]; }
                 }
-                const int rcl = pg_launch(h, "amc_pg_accumulate", n, learn_ids + base, q_batch, &nl, opt ? 3 : 2, opt ? &sub : nullptr, false, false, nullptr,
-                                          base, base + n >= n_learn);
-                if (rcl != AMC_OK) return rcl;
+                AMC_TRY(pg_launch(h, "amc_pg_accumulate", n, learn_ids + base, q_batch, &nl, opt ? 3 : 2, opt ? &sub : nullptr, false, false, nullptr,
+                                  base, base + n >= n_learn));
             }
             if (opt) h->gd_nonzero &= ~ids_mask;
             else h->gd_nonzero |= ids_mask;
@@ -608,7 +604,7 @@ static int pg_accumulate_impl(amc_handle* h, int n_learn, const int* learn_ids, 
                 AMC_HIP(hipMemcpyAsync(h->d_theta_ring + (size_t)(t_est & 1ull) * AMC_MAX_LEARN + l, h->d_ptab + amc::PT_SIGMA * AMC_MAX_MOVES + learn_ids[l],
                                        sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         }
-        if (shards) { const int rca = pg_allreduce_records(h, n_learn * 4); if (rca != AMC_OK) return rca; }
+        if (shards) AMC_TRY(pg_allreduce_records(h, n_learn * 4));
         h->pend.active = true;
         h->pend.source = shards ? (int)amc::PG_PENDING_RECORDS : (int)amc::PG_PENDING_GROUPS;
         h->pend.groups = (grid + amc::PG_GROUP - 1) / amc::PG_GROUP;
@@ -623,7 +619,7 @@ static int pg_accumulate_impl(amc_handle* h, int n_learn, const int* learn_ids, 
     // slots, so ONE in-place all-reduce(sum) on the engine's stream is a gather -- exact whatever order RCCL adds in; the
     // kernel behind it merges the shards' integer totals and rounds once (pg_merge_slots): every shard, and a single shard
     // holding all the chains, arrive at the same bits
-    { const int rca = pg_allreduce_records(h, n_learn * 4); if (rca != AMC_OK) return rca; }
+    AMC_TRY(pg_allreduce_records(h, n_learn * 4));
     const double n_samples = (double)h->M_global * (double)q_batch;
     if (opt) {      // gradients_data += gd and the learning step in ONE launch: both sit on the critical path of the next sweep
         // (a launch that took a pending step in its prologue proposed with sigma', which block 0 left in this step's ring slot)
@@ -658,13 +654,13 @@ int amc_pg_route(amc_handle* h, int n_learn, int q_batch, int fused, char* why, 
     };
     if (fused != 0 && can_fuse) {
         bool general = true;
-        { const int rc = class_general_route(h, n_learn, true, false, q_batch, &general); if (rc != AMC_OK) return rc; }
+        AMC_TRY(class_general_route(h, n_learn, true, false, q_batch, &general));
         if (general) return 2;
         say_why();
     }
     if (per_move_launches(h)) return np_single_launch(h, n_learn) ? 1 : 0;
     bool general = true;
-    { const int rc = class_general_route(h, n_learn, false, false, q_batch, &general); if (rc != AMC_OK) return rc; }
+    AMC_TRY(class_general_route(h, n_learn, false, false, q_batch, &general));
     if (!general) say_why();
     return general ? 1 : 0;
 }
@@ -702,9 +698,9 @@ int amc_pg_update(amc_handle* h, int n_learn, const int* learn_ids, const int* o
     if (n_learn < 0 || n_learn > AMC_MAX_LEARN) return fail(AMC_ERR_BAD_ARG, "amc_pg_update: n_learn must be in [0, %d]", AMC_MAX_LEARN);
     if (n_learn == 0) return AMC_OK;
     amc::PgOpts opt;
-    { const int rc = make_opts(h, n_learn, learn_ids, optimiser, hyper0, hyper1, &opt); if (rc != AMC_OK) return rc; }
+    AMC_TRY(make_opts(h, n_learn, learn_ids, optimiser, hyper0, hyper1, &opt));
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
     for (int l = 0; l < n_learn; ++l) h->gd_nonzero &= ~(1ull << (learn_ids[l] & 63));
     if (h->n_params > 1) return pg_update_np(h, n_learn, learn_ids, opt);
     hipLaunchKernelGGL(amc::pg_update_kernel, dim3(1), dim3(64), 0, h->stream, h->d_ptab, h->d_gd_acc, n_learn,
@@ -728,8 +724,7 @@ static int pgmc_steps_impl(amc_handle* h, const char* who, int64_t n_steps, int 
     if (reduce && !red_next(h)) return fail(AMC_ERR_STATE, "%s: %d reductions are already in flight (call amc_reduce_end)", who, RED_TICKETS);
     amc::PgOpts opt;
     if (do_update && n_learn > 0) {
-        const int rc = make_opts(h, n_learn, learn_ids, optimiser, hyper0, hyper1, &opt);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(make_opts(h, n_learn, learn_ids, optimiser, hyper0, hyper1, &opt));
     }
     // the three make_step!s of one time step (src/simulation.jl:185-190), n_steps times, from one host call: two
     // launches per step on a single shard (sweep; estimator whose last block accumulates and takes the learning step)
@@ -743,19 +738,16 @@ static int pgmc_steps_impl(amc_handle* h, const char* who, int64_t n_steps, int 
     if (chain)
         fused = h->sweepstep == 1 && (h->d_log != nullptr || h->K == 1) && log_form(h) != AMC_LOG_BYTES && !h->knobs.no_sweep_estimator_fusion;
     if (fused && h->n_classes > 1) {      // a pool of several classes: the fused form where it builds (class_general_route)
-        const int rcg = class_general_route(h, n_learn, true, false, q_batch, &fused);
-        if (rcg != AMC_OK) return rcg;
+        AMC_TRY(class_general_route(h, n_learn, true, false, q_batch, &fused));
     }
     // the callback sums ride in the last fused launch (rows the host sums: K <= 4; launches that need no flush on the way)
     bool fused_reduce = reduce && fused && !chain && h->K <= 4 && !h->d_acc_base;
     if (fused_reduce && h->n_classes > 1) {
-        const int rcg = class_general_route(h, n_learn, true, true, q_batch, &fused_reduce);
-        if (rcg != AMC_OK) return rcg;
+        AMC_TRY(class_general_route(h, n_learn, true, true, q_batch, &fused_reduce));
     }
     if (fused_reduce) {            // ... and launches that need no flush on the way
         PgPlan plan;
-        const int rcp = pg_plan(h, nl_capacity(n_learn), h->K > 1 ? 2 : (h->d_log ? 1 : 3), true, q_batch, &plan);
-        if (rcp != AMC_OK) return rcp;
+        AMC_TRY(pg_plan(h, nl_capacity(n_learn), h->K > 1 ? 2 : (h->d_log ? 1 : 3), true, q_batch, &plan));
         fused_reduce = !plan.mid && reduce_fits_in_grid(h, plan.grid);
     }
     int grid = 0;
@@ -790,7 +782,7 @@ int amc_pg_get_accumulated(amc_handle* h, int n_learn, const int* learn_ids, dou
     AMC_REFUSE_PARAM_F32(h, "amc_pg_get_accumulated");
     AMC_REFUSE_RUNG_SIGMA(h, "amc_pg_get_accumulated");
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }      // (a pending step may set the status flag)
+    AMC_TRY(pg_resolve(h));      // (a pending step may set the status flag)
     const int np = h->n_params;
     const size_t dev_stride = np > 1 ? (size_t)AMC_GD_STRIDE_MAX : 5, out_stride = (size_t)amc::pg_gd_stride(np);
     std::vector<double> acc((size_t)AMC_MAX_MOVES * dev_stride);
@@ -820,7 +812,7 @@ int amc_pg_set_accumulated(amc_handle* h, int n_learn, const int* learn_ids, con
         if (!(n >= 0.0) || n != std::floor(n)) return fail(AMC_ERR_BAD_ARG, "amc_pg_set_accumulated: n of move %d is not a sample count", learn_ids[l]);
     }
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
     for (int l = 0; l < n_learn; ++l) h->gd_nonzero |= 1ull << (learn_ids[l] & 63);
     {
         const size_t dev_stride = h->n_params > 1 ? (size_t)AMC_GD_STRIDE_MAX : 5, in_stride = (size_t)amc::pg_gd_stride(h->n_params);

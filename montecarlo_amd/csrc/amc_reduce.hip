@@ -45,8 +45,7 @@ int finish_fused_reduce(amc_handle* h, int grid)
     t->ratio_rows = 0;
     t->ratio_acc = false;
     if (h->counters) {
-        const int rc2 = fold_log(h, true, &t->ratio_rows, t->h_ratio);
-        if (rc2 != AMC_OK) return rc2;
+        AMC_TRY(fold_log(h, true, &t->ratio_rows, t->h_ratio));
     }
     return red_commit(h, t, grid);
 }
@@ -135,12 +134,10 @@ int amc_reduce_begin(amc_handle* h)
     if (ratio_mode != 0 && h->K <= 4 && !h->d_acc_base) {
         // per-chain counters, few moves: the fold of the step log forms the acceptance-ratio sums while the counters
         // are in its registers (rows in h_ratio); the pass below then reads x only
-        const int rc = fold_log(h, true, &t->ratio_rows, t->h_ratio);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(fold_log(h, true, &t->ratio_rows, t->h_ratio));
         ratio_mode = 0;
     } else if (ratio_mode != 0) {
-        const int rc = fold_log(h);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(fold_log(h));
         AMC_HIP(hipMemsetAsync(t->d_ratio_acc, 0, (size_t)AMC_MAX_MOVES * 3 * sizeof(unsigned long long), h->stream));
         t->ratio_acc = true;
     }
@@ -154,9 +151,8 @@ int amc_reduce_begin(amc_handle* h)
     unsigned long long* racc = t->d_ratio_acc;
     void* params[] = {&h->d_x, &h->d_acc, &h->d_tot, &h->M, &h->M_pad, &h->K, &ratio_mode, &h->t_counted, &rows, &stride, &slots, &h->n_slots, &racc, &cols,
                       &h->d_acc_base, &h->d_tot_base, &h->t_base};
-    const int rc = launch_by_potential(h, "amc::reduce_kernel", (const void*)amc::reduce_kernel<amc::POT_DOUBLE_WELL>, (const void*)amc::reduce_kernel<amc::POT_HARMONIC>,
-                                       h->red_blocks, params);
-    if (rc != AMC_OK) return rc;
+    AMC_TRY(launch_by_potential(h, "amc::reduce_kernel", (const void*)amc::reduce_kernel<amc::POT_DOUBLE_WELL>, (const void*)amc::reduce_kernel<amc::POT_HARMONIC>,
+                                h->red_blocks, params));
     if (t->ratio_acc)
         AMC_HIP(hipMemcpyAsync(t->h_ratio_acc, t->d_ratio_acc, (size_t)h->K * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                h->stream));
@@ -172,13 +168,12 @@ int amc_sweep_reduce_begin(amc_handle* h, int64_t n_sweeps)
     // the ratio sums need the counters of every move (K > 4), or arrays plus their 64-bit bases (a handle that has counted past
     // 2^32 steps): sweep, then the reduction pass
     // (and so does a handle with widths per rung: its sweep form carries no sums -- reproducible sums, the same bits either way)
-    if (h->K > 4 || h->d_acc_base || h->rung_on || !reduce_fits_in_grid(h, reduce_sweep_grid(h))) {
+    if (h->K > 4 || h->d_acc_base || h->lad.rung_on || !reduce_fits_in_grid(h, reduce_sweep_grid(h))) {
         const int rc = sweep_impl(h, n_sweeps, false, nullptr);
         return rc != AMC_OK ? rc : amc_reduce_begin(h);
     }
     int grid = 0;
-    const int rc = sweep_impl(h, n_sweeps, true, &grid);     // the last launch wrote the sums over x to the ticket's rows
-    if (rc != AMC_OK) return rc;
+    AMC_TRY(sweep_impl(h, n_sweeps, true, &grid));     // the last launch wrote the sums over x to the ticket's rows
     return finish_fused_reduce(h, grid);
 }
 
@@ -193,8 +188,7 @@ int amc_reduce_end(amc_handle* h, double* out)
     if (!h || !out) return fail(AMC_ERR_BAD_ARG, "amc_reduce_end: NULL argument");
     double recs[(AMC_RED_HEADER + AMC_MAX_MOVES) * amc::xs::XS_WORDS];
     uint64_t steps = 0;
-    const int rc = reduce_end_records(h, "amc_reduce_end", recs, &steps);
-    if (rc != AMC_OK) return rc;
+    AMC_TRY(reduce_end_records(h, "amc_reduce_end", recs, &steps));
     for (int i = 0; i < AMC_RED_HEADER + h->K; ++i)
         out[i] = recs[(size_t)i * amc::xs::XS_WORDS] == (double)amc::xs::XS_EMPTY ? std::nan("") : amc::xs::rec_round(recs + (size_t)i * amc::xs::XS_WORDS);
     if (h->K == 1 && !h->counters) out[AMC_RED_SUM_RATIO0] = out[AMC_RED_SUM_RATIO0] / (double)steps;

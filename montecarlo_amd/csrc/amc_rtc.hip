@@ -160,7 +160,7 @@ struct Built { int stage = -1; int status = 0; std::string log, lowered; std::ve
 // then is a fatal error of the host -- which is why it is not the default (build_in_child).
 int build_in_process(const std::string& src, const std::string& inst, const std::vector<std::string>& opts, Built* out)
 {
-    { const int rc = load_hiprtc(g_hiprtc); if (rc != AMC_OK) return rc; }
+    AMC_TRY(load_hiprtc(g_hiprtc));
     void* prog = nullptr;
     int e = g_hiprtc.CreateProgram(&prog, src.c_str(), "amc_custom_potential.hip", AMC_RTC_N_SOURCES, AMC_RTC_SOURCE_TEXTS, AMC_RTC_SOURCE_NAMES);
     if (e != 0) { out->stage = 1; out->status = e; return AMC_OK; }
@@ -496,7 +496,7 @@ int rtc_compile(const ModelSpec& spec, const std::string& inst, const std::strin
         auto bk = g_rtc_broken.find(key);
         if (bk != g_rtc_broken.end()) return fail(AMC_ERR_COMPILE, "%s", bk->second.c_str());
     }
-    { const int rc = load_hiprtc(g_hiprtc); if (rc != AMC_OK) return rc; }
+    AMC_TRY(load_hiprtc(g_hiprtc));
     int rtc_major = 0, rtc_minor = 0;
     (void)g_hiprtc.Version(&rtc_major, &rtc_minor);
     const std::string cache_file = rtc_cache_path(model, inst, arch, "hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) + variant);
@@ -569,7 +569,7 @@ int rtc_function(amc_handle* h, const std::string& inst, hipFunction_t* fn)
     auto it = h->rtc_fn.find(inst);
     if (it != h->rtc_fn.end()) { *fn = it->second; return AMC_OK; }
     const RtcCode* code = nullptr;
-    { const int rc = rtc_compile(h->model, inst, h->arch, h->knobs, &code, nullptr); if (rc != AMC_OK) return rc; }
+    AMC_TRY(rtc_compile(h->model, inst, h->arch, h->knobs, &code, nullptr));
     hipModule_t mod = nullptr;
     AMC_HIP(hipModuleLoadData(&mod, code->code.data()));
     h->rtc_mods.push_back(mod);
@@ -583,7 +583,7 @@ int rtc_function(amc_handle* h, const std::string& inst, hipFunction_t* fn)
 int rtc_launch(amc_handle* h, const std::string& inst, int grid, void** params)
 {
     hipFunction_t fn = nullptr;
-    { const int rc = rtc_function(h, inst, &fn); if (rc != AMC_OK) return rc; }
+    AMC_TRY(rtc_function(h, inst, &fn));
     AMC_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, AMC_BLOCK, 1, 1, 0, h->stream, params, nullptr));
     return AMC_OK;
 }
@@ -594,7 +594,7 @@ extern "C" {
 int amc_potential_check(const char* potential_expr, char* log, int log_capacity)
 {
     if (log && log_capacity > 0) log[0] = 0;
-    { const int rc = validate_potential_expr(potential_expr); if (rc != AMC_OK) return rc; }
+    AMC_TRY(validate_potential_expr(potential_expr));
     const RtcCode* code = nullptr;
     std::string text;
     ModelSpec spec;

@@ -34,6 +34,28 @@ hipError_t wait_event(hipEvent_t ev)
     return spin_then_block([&] { return hipEventQuery(ev); }, [&] { return hipEventSynchronize(ev); });
 }
 
+int copy_to_host_sync(amc_handle* h, void* dst, const void* d_src, size_t bytes)
+{
+    if (d_src) AMC_HIP(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    return AMC_OK;
+}
+
+int copy_to_device_sync(amc_handle* h, void* d_dst, const void* src, size_t bytes)
+{
+    AMC_HIP(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, h->stream));
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    return AMC_OK;
+}
+
+int zeroed_words(amc_handle* h, unsigned long long** p, size_t bytes)
+{
+    if (*p) return AMC_OK;
+    AMC_HIP(hipMalloc(p, bytes));
+    AMC_HIP(hipMemsetAsync(*p, 0, bytes, h->stream));
+    return AMC_OK;
+}
+
 // Float32 state: d_x64 (doubles) -> dst (floats, rounded to nearest) and back, on the stream.
 static int narrow_from_x64(amc_handle* h, double* dst_as_float)
 {
@@ -100,8 +122,7 @@ int amc_upload_state(amc_handle* h, const double* x, const double* beta_or_null)
     AMC_HIP(hipSetDevice(h->device));
     if (h->f32) {
         AMC_HIP(hipMemcpyAsync(h->d_x64, x, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        const int rc = narrow_from_x64(h, h->d_x);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(narrow_from_x64(h, h->d_x));
     } else {
         AMC_HIP(hipMemcpyAsync(h->d_x, x, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
@@ -112,8 +133,7 @@ int amc_upload_state(amc_handle* h, const double* x, const double* beta_or_null)
         }
         if (h->f32) {
             AMC_HIP(hipMemcpyAsync(h->d_x64, beta_or_null, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            const int rc = narrow_from_x64(h, h->d_beta);
-            if (rc != AMC_OK) return rc;
+            AMC_TRY(narrow_from_x64(h, h->d_beta));
         } else {
             AMC_HIP(hipMemcpyAsync(h->d_beta, beta_or_null, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
         }
@@ -145,7 +165,7 @@ int amc_download_state(amc_handle* h, double* x, double* e)
     std::vector<double> tmp;
     if (!dst) { tmp.resize((size_t)h->M); dst = tmp.data(); }
     const double* d_pos = nullptr;
-    { const int rc = positions_f64(h, &d_pos); if (rc != AMC_OK) return rc; }
+    AMC_TRY(positions_f64(h, &d_pos));
     AMC_HIP(hipMemcpyAsync(dst, d_pos, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     AMC_HIP(hipStreamSynchronize(h->stream));
     if (e && h->use_rtc) {
@@ -205,15 +225,15 @@ int amc_histogram(amc_handle* h, double lo, double hi, int n_bins, uint64_t* cou
 int amc_histogram_rungs(amc_handle* h, double lo, double hi, int n_bins, uint64_t* counts)
 {
     if (!h || !counts) return fail(AMC_ERR_BAD_ARG, "amc_histogram_rungs: NULL argument");
-    if (!h->n_rungs) return fail(AMC_ERR_STATE, "amc_histogram_rungs: the handle has no ladder (amc_set_ladder)");
+    AMC_TRY(need_ladder(h, "amc_histogram_rungs"));
     if (!hist_args_ok("amc_histogram_rungs", lo, hi, n_bins)) return AMC_ERR_BAD_ARG;
     AMC_HIP(hipSetDevice(h->device));
-    const int cells = (n_bins + 3) * h->n_rungs;
+    const int cells = (n_bins + 3) * h->lad.n_rungs;
     const double inv_w = (double)n_bins / (hi - lo);
     const int lds_rows = cells <= 12288 ? 1 : 0;      // 48 KiB of u32 counters; beyond that one global atomic per position
     return hist_to_host(h, "amc_histogram_rungs", cells, counts, [&](const double* d_pos, unsigned long long* d_counts) {
         hipLaunchKernelGGL(amc::rung_histogram_kernel, dim3(hist_grid(h)), dim3(AMC_BLOCK), lds_rows ? (size_t)cells * sizeof(unsigned int) : 0,
-                           h->stream, d_pos, h->M, h->n_rungs, lo, hi, inv_w, n_bins, lds_rows, d_counts);
+                           h->stream, d_pos, h->M, h->lad.n_rungs, lo, hi, inv_w, n_bins, lds_rows, d_counts);
     });
 }
 
@@ -232,7 +252,7 @@ int amc_histogram_accumulate(amc_handle* h, double lo, double hi, int n_bins)
     }
     const double inv_w = (double)n_bins / (hi - lo);
     const double* d_pos = nullptr;
-    { const int rc = positions_f64(h, &d_pos); if (rc != AMC_OK) return rc; }
+    AMC_TRY(positions_f64(h, &d_pos));
     hipLaunchKernelGGL(amc::histogram_kernel, dim3(hist_grid(h)), dim3(AMC_BLOCK), (size_t)(n_bins + 3) * sizeof(unsigned int),
                        h->stream, d_pos, h->M, lo, hi, inv_w, n_bins, h->d_hist);
     AMC_HIP(hipGetLastError());

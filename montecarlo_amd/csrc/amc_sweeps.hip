@@ -31,7 +31,7 @@ int launch_sweep_rung(const amc::SweepArgs& a, int grid, hipStream_t stream)
 template <int POT, int FORM>
 int launch_sweep_form(amc_handle* h, const amc::SweepArgs& a, int grid, hipStream_t stream)
 {
-    if (h->rung_on) {
+    if (h->lad.rung_on) {
         // widths per rung (amc_set_rung_sigma): a ladder and per-chain counters are given; the callback sums come from a pass of their own
         if (FORM != amc::RED_FORM_NONE) return fail(AMC_ERR_STATE, "sweep: no launch forms the callback sums while widths per rung are set");
         if (h->K > 1 && log_form(h) == AMC_LOG_PACKED) return launch_sweep_rung<POT, true, AMC_LOG_PACKED>(a, grid, stream);
@@ -64,8 +64,8 @@ static int launch_sweep_custom(amc_handle* h, amc::SweepArgs& a, int grid, bool 
 {
     const bool multi = h->K > 1;
     const std::string inst = "amc::sweep_kernel<" + std::to_string(h->potential) + "," + tf(multi) + "," + std::to_string(log_form(h)) + "," + tf(h->beta_arr) + "," +
-                             tf(a.n_steps == 1) + "," + std::to_string(reduce ? red_form(h) : (int)amc::RED_FORM_NONE) + (h->rung_on ? ",true>" : ">");
-    if (h->rung_on && reduce) return fail(AMC_ERR_STATE, "sweep: no launch forms the callback sums while widths per rung are set");
+                             tf(a.n_steps == 1) + "," + std::to_string(reduce ? red_form(h) : (int)amc::RED_FORM_NONE) + (h->lad.rung_on ? ",true>" : ">");
+    if (h->lad.rung_on && reduce) return fail(AMC_ERR_STATE, "sweep: no launch forms the callback sums while widths per rung are set");
     void* params[] = {&a};
     return rtc_launch(h, inst, grid, params);
 }
@@ -96,8 +96,8 @@ amc::SweepArgs make_sweep_args(const amc_handle* h, int32_t n_steps, int grid)
     a.red_cols = h->red_cols;
     a.exact_accept = h->knobs.exact_accept ? 1 : 0;
     a.n_slots = h->n_slots;
-    if (h->rung_on) a.rung_tab = h->d_rung_tab;       // (in red_partials' place: no launch of such a handle forms the callback sums)
-    a.n_rungs = h->n_rungs;
+    if (h->lad.rung_on) a.rung_tab = h->lad.d_rung_tab;       // (in red_partials' place: no launch of such a handle forms the callback sums)
+    a.n_rungs = h->lad.n_rungs;
     a.full_rounds = a.tail_pairs = 0;
     if (grid > 0) {
         const int64_t n_pairs = (h->M + 1) / 2, round = (int64_t)grid * AMC_BLOCK;
@@ -118,7 +118,7 @@ int reduce_sweep_grid(const amc_handle* h)
 int sweep_impl(amc_handle* h, int64_t n_sweeps, bool fuse_reduce, int* grid_out)
 {
     AMC_HIP(hipSetDevice(h->device));
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }      // the sweep kernels read sigma from the parameter table
+    AMC_TRY(pg_resolve(h));      // the sweep kernels read sigma from the parameter table
     int64_t remaining = n_sweeps * (int64_t)h->sweepstep;
     // one grid for the whole call (the caller of a fused reduction sums `grid` rows)
     // (a call whose last launch also forms the callback sums: that form holds 5 blocks per CU -- 89 VGPRs -- and runs one round of
@@ -132,11 +132,10 @@ int sweep_impl(amc_handle* h, int64_t n_sweeps, bool fuse_reduce, int* grid_out)
         int32_t chunk = remaining > (1 << 20) ? (1 << 20) : (int32_t)remaining;
         if (h->d_log) {      // per-chain counters: one log row per MH step; a full log is folded before it is reused
             int room = 0;
-            const int rc = log_room(h, &room);
-            if (rc != AMC_OK) return rc;
+            AMC_TRY(log_room(h, &room));
             if (chunk > room) chunk = room;
         }
-        { const int rc = counter_room(h, "amc_sweep", (uint64_t)chunk); if (rc != AMC_OK) return rc; }      // (may carry the counters: arrays restart at zero)
+        AMC_TRY(counter_room(h, "amc_sweep", (uint64_t)chunk));      // (may carry the counters: arrays restart at zero)
         amc::SweepArgs a = make_sweep_args(h, chunk, grid);
         a.red_stride = red_row_stride(h, grid);
         const bool last = remaining == chunk;
@@ -205,8 +204,8 @@ static amc::SweepArgs slice_sweep_args(const amc::SweepArgs& whole, const amc::S
 // join per side stream at the end, so whatever is queued on the handle's stream afterwards finds every slice finished.
 static int sweep_launches_sliced(amc_handle* h, int64_t n_launches, const amc::SlicePlan& plan)
 {
-    { const int rc = pg_resolve(h); if (rc != AMC_OK) return rc; }
-    { const int rc = counter_room(h, "amc_sweep_launches", (uint64_t)n_launches); if (rc != AMC_OK) return rc; }
+    AMC_TRY(pg_resolve(h));
+    AMC_TRY(counter_room(h, "amc_sweep_launches", (uint64_t)n_launches));
     if (h->knobs.debug_plan)
         for (int s = 0; s < plan.count; ++s)
             std::fprintf(stderr, "[amc] sweep slice %d of %d: pairs from %lld, %lld chains in a grid of %d blocks\n", s, plan.count,
@@ -265,8 +264,7 @@ int amc_sweep_launches(amc_handle* h, int64_t n_launches)
         }
     }
     for (int64_t i = 0; i < n_launches; ++i) {
-        const int rc = sweep_impl(h, 1, false, nullptr);
-        if (rc != AMC_OK) return rc;
+        AMC_TRY(sweep_impl(h, 1, false, nullptr));
     }
     return AMC_OK;
 }
