@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 from typing import Optional, Sequence
 
 import numpy as np
@@ -81,25 +82,24 @@ def load() -> C.CDLL:
     H = C.c_void_p
     dp = C.POINTER(C.c_double)
     i64p = C.POINTER(C.c_int64)
+    u64p = C.POINTER(C.c_uint64)
+    ip = C.POINTER(C.c_int)
+    sp, spp = C.c_char_p, C.POINTER(C.c_char_p)          # const char *, const char *const *
+    cfgp, Hp = C.POINTER(AmcConfig), C.POINTER(H)
     sig = {
-        "amc_last_error": (C.c_char_p, []),
+        "amc_last_error": (sp, []),
         "amc_version": (C.c_int, []),
-        "amc_device_count": (C.c_int, [C.POINTER(C.c_int)]),
-        "amc_create": (C.c_int, [C.POINTER(AmcConfig), C.POINTER(H)]),
-        "amc_create_custom": (C.c_int, [C.POINTER(AmcConfig), C.c_char_p, C.POINTER(H)]),
-        "amc_create_model": (C.c_int, [C.POINTER(AmcConfig), C.c_char_p, C.c_char_p, C.POINTER(H)]),
-        "amc_create_policy_model": (C.c_int, [C.POINTER(AmcConfig), C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(H)]),
-        "amc_create_proposal_model": (C.c_int, [C.POINTER(AmcConfig), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
-                                                C.POINTER(H)]),
-        "amc_create_action_model": (C.c_int, [C.POINTER(AmcConfig), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
-                                              C.c_char_p, C.c_char_p, C.POINTER(H)]),
-        "amc_create_vector_policy_model": (C.c_int, [C.POINTER(AmcConfig), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
-                                                     C.POINTER(C.c_char_p), C.c_char_p, C.c_char_p, C.POINTER(H)]),
-        "amc_n_params": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "amc_create_mixed_model": (C.c_int, [C.POINTER(AmcConfig), C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p),
-                                             C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
-                                             C.POINTER(H)]),
-        "amc_potential_check": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
+        "amc_device_count": (C.c_int, [ip]),
+        "amc_create": (C.c_int, [cfgp, Hp]),
+        "amc_create_custom": (C.c_int, [cfgp, sp, Hp]),
+        "amc_create_model": (C.c_int, [cfgp, sp, sp, Hp]),
+        "amc_create_policy_model": (C.c_int, [cfgp, sp, sp, sp, Hp]),
+        "amc_create_proposal_model": (C.c_int, [cfgp, sp, sp, sp, sp, sp, Hp]),
+        "amc_create_action_model": (C.c_int, [cfgp, sp, sp, sp, sp, sp, sp, sp, Hp]),
+        "amc_create_vector_policy_model": (C.c_int, [cfgp, C.c_int, sp, sp, sp, sp, spp, sp, sp, Hp]),
+        "amc_n_params": (C.c_int, [H, ip, ip]),
+        "amc_create_mixed_model": (C.c_int, [cfgp, C.c_int, ip, sp, sp, spp, spp, spp, spp, spp, Hp]),
+        "amc_potential_check": (C.c_int, [sp, sp, C.c_int]),
         "amc_destroy": (C.c_int, [H]),
         "amc_upload_state": (C.c_int, [H, dp, dp]),
         "amc_init_uniform": (C.c_int, [H, C.c_double, C.c_double]),
@@ -108,42 +108,39 @@ def load() -> C.CDLL:
         "amc_counter_totals": (C.c_int, [H, i64p, i64p]),
         "amc_upload_counters": (C.c_int, [H, i64p, i64p]),
         "amc_set_counter_totals": (C.c_int, [H, i64p, C.c_uint64]),
-        "amc_histogram": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64)]),
+        "amc_histogram": (C.c_int, [H, C.c_double, C.c_double, C.c_int, u64p]),
         "amc_histogram_accumulate": (C.c_int, [H, C.c_double, C.c_double, C.c_int]),
-        "amc_histogram_fetch": (C.c_int, [H, C.POINTER(C.c_uint64), C.c_int, C.c_int]),
+        "amc_histogram_fetch": (C.c_int, [H, u64p, C.c_int, C.c_int]),
         "amc_download_strided": (C.c_int, [H, C.c_int64, C.c_int64, C.c_int64, dp]),
-        "amc_get_estimator_step": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "amc_get_estimator_step": (C.c_int, [H, u64p]),
         "amc_set_estimator_step": (C.c_int, [H, C.c_uint64]),
         "amc_sweep": (C.c_int, [H, C.c_int64]),
         "amc_sweep_launches": (C.c_int, [H, C.c_int64]),
-        "amc_get_step": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "amc_get_step": (C.c_int, [H, u64p]),
         "amc_set_step": (C.c_int, [H, C.c_uint64]),
         "amc_reduce": (C.c_int, [H, dp]),
         "amc_reduce_begin": (C.c_int, [H]),
         "amc_sweep_reduce_begin": (C.c_int, [H, C.c_int64]),
         "amc_reduce_end": (C.c_int, [H, dp]),
-        "amc_reduce_end_exact": (C.c_int, [H, dp, C.POINTER(C.c_uint64)]),
+        "amc_reduce_end_exact": (C.c_int, [H, dp, u64p]),
         "amc_xsum_merge": (C.c_int, [dp, dp, C.c_int]),
         "amc_xsum_round": (C.c_int, [dp, C.c_int, dp]),
-        "amc_pg_estimate_exact": (C.c_int, [H, C.c_int, C.POINTER(C.c_int), C.c_int, dp]),
-        "amc_pg_route": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
-        "amc_model_check": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
-                                      C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_char_p, C.c_int]),
+        "amc_pg_estimate_exact": (C.c_int, [H, C.c_int, ip, C.c_int, dp]),
+        "amc_pg_route": (C.c_int, [H, C.c_int, C.c_int, C.c_int, sp, C.c_int]),
+        "amc_model_check": (C.c_int, [C.c_int, C.c_int, sp, sp, spp, spp, spp, spp, spp, sp, C.c_int]),
         "amc_allreduce_xsum": (C.c_int, [H, dp, C.c_int]),
-        "amc_comm_library_forced": (C.c_int, [C.POINTER(C.c_int)]),
+        "amc_comm_library_forced": (C.c_int, [ip]),
         "amc_set_parameters": (C.c_int, [H, C.c_int, dp, C.c_int]),
         "amc_get_parameters": (C.c_int, [H, C.c_int, dp, C.c_int]),
         "amc_parameters_begin": (C.c_int, [H]),
         "amc_parameters_end": (C.c_int, [H, dp]),
-        "amc_pg_estimate": (C.c_int, [H, C.c_int, C.POINTER(C.c_int), C.c_int, dp]),
-        "amc_pg_accumulate": (C.c_int, [H, C.c_int, C.POINTER(C.c_int), C.c_int]),
-        "amc_pg_update": (C.c_int, [H, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp]),
-        "amc_pg_get_accumulated": (C.c_int, [H, C.c_int, C.POINTER(C.c_int), dp]),
-        "amc_pg_set_accumulated": (C.c_int, [H, C.c_int, C.POINTER(C.c_int), dp]),
-        "amc_pgmc_steps": (C.c_int, [H, C.c_int64, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
-                                     dp, dp]),
-        "amc_pgmc_steps_reduce_begin": (C.c_int, [H, C.c_int64, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
-                                                  dp, dp]),
+        "amc_pg_estimate": (C.c_int, [H, C.c_int, ip, C.c_int, dp]),
+        "amc_pg_accumulate": (C.c_int, [H, C.c_int, ip, C.c_int]),
+        "amc_pg_update": (C.c_int, [H, C.c_int, ip, ip, dp, dp]),
+        "amc_pg_get_accumulated": (C.c_int, [H, C.c_int, ip, dp]),
+        "amc_pg_set_accumulated": (C.c_int, [H, C.c_int, ip, dp]),
+        "amc_pgmc_steps": (C.c_int, [H, C.c_int64, C.c_int, ip, C.c_int, C.c_int, ip, dp, dp]),
+        "amc_pgmc_steps_reduce_begin": (C.c_int, [H, C.c_int64, C.c_int, ip, C.c_int, C.c_int, ip, dp, dp]),
         "amc_sync": (C.c_int, [H]),
         "amc_get_stream": (C.c_int, [H, C.POINTER(C.c_void_p)]),
         "amc_timing_begin": (C.c_int, [H]),
@@ -153,13 +150,12 @@ def load() -> C.CDLL:
         "amc_comm_init": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p]),
         "amc_allreduce_sum": (C.c_int, [H, dp, C.c_int]),
         "amc_comm_destroy": (C.c_int, [H]),
-        "amc_comm_info": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
-        "amc_runtime_info": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
+        "amc_comm_info": (C.c_int, [H, ip, ip, ip, sp, C.c_int]),
+        "amc_runtime_info": (C.c_int, [ip, sp, C.c_int]),
         "amc_selftest_math": (C.c_int, [C.c_int, C.c_int, dp, dp, dp, C.c_int64]),
         "amc_selftest_accept_filter": (C.c_int, [C.c_int, C.c_float, C.c_float, dp]),
         "amc_selftest_filter_argument": (C.c_int, [C.c_int, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_float), C.c_int64]),
-        "amc_selftest_philox": (C.c_int, [C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                          C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64]),
+        "amc_selftest_philox": (C.c_int, [C.c_int, C.c_uint64, u64p, u64p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int64]),
         "amc_set_reduce_columns": (C.c_int, [H, C.c_int]),
         "amc_parameters_end_all": (C.c_int, [H, dp, C.c_int]),
         "amc_selftest_wave_totals": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -169,42 +165,42 @@ def load() -> C.CDLL:
         "amc_sweep_exchange": (C.c_int, [H, C.c_int64, C.c_int64]),
         "amc_exchange_counters": (C.c_int, [H, i64p, i64p]),
         "amc_set_exchange_counters": (C.c_int, [H, i64p, i64p]),
-        "amc_get_exchange_step": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "amc_get_exchange_step": (C.c_int, [H, u64p]),
         "amc_set_exchange_step": (C.c_int, [H, C.c_uint64]),
-        "amc_histogram_rungs": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64)]),
+        "amc_histogram_rungs": (C.c_int, [H, C.c_double, C.c_double, C.c_int, u64p]),
         "amc_reduce_rungs_exact": (C.c_int, [H, C.c_int, dp]),
         "amc_bridge_accumulate": (C.c_int, [H, C.c_int]),
-        "amc_bridge_fetch": (C.c_int, [H, dp, C.POINTER(C.c_uint64), C.c_int]),
+        "amc_bridge_fetch": (C.c_int, [H, dp, u64p, C.c_int]),
         "amc_set_bridge": (C.c_int, [H, dp, C.c_uint64]),
         "amc_set_tracking": (C.c_int, [H, C.c_int]),
         "amc_download_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
         "amc_upload_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
-        "amc_flow_rungs": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "amc_flow_rungs": (C.c_int, [H, u64p]),
         "amc_tracking_counters": (C.c_int, [H, i64p, i64p]),
         "amc_set_tracking_counters": (C.c_int, [H, C.c_int64, C.c_int64]),
         "amc_set_rung_sigma": (C.c_int, [H, dp, C.c_int]),
         "amc_get_rung_sigma": (C.c_int, [H, dp, C.c_int]),
-        "amc_respace_ladder": (C.c_int, [H, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),
-        "amc_respace_status": (C.c_int, [H, C.POINTER(C.c_int), i64p]),
+        "amc_respace_ladder": (C.c_int, [H, C.c_int, C.c_double, C.c_double, u64p]),
+        "amc_respace_status": (C.c_int, [H, ip, i64p]),
         "amc_set_respaced": (C.c_int, [H, C.c_int64]),
         "amc_get_ladder": (C.c_int, [H, dp]),
         "amc_rung_counter_totals": (C.c_int, [H, i64p, i64p]),
         "amc_tune_rung_sigma": (C.c_int, [H, C.c_double, C.c_double, C.c_int64, C.c_double, C.c_double, i64p]),
-        "amc_tune_status": (C.c_int, [H, C.POINTER(C.c_int), C.c_int, i64p]),
+        "amc_tune_status": (C.c_int, [H, ip, C.c_int, i64p]),
         "amc_set_tuned": (C.c_int, [H, C.c_int64]),
         "amc_rung_window_counts": (C.c_int, [H, i64p, i64p]),
         "amc_rung_window_restart": (C.c_int, [H]),
         "amc_rung_window_base": (C.c_int, [H, i64p, i64p]),
         "amc_set_rung_window_base": (C.c_int, [H, i64p, i64p]),
         "amc_anneal": (C.c_int, [H, C.c_double]),
-        "amc_anneal_fetch": (C.c_int, [H, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int), C.c_int]),
-        "amc_set_anneal_records": (C.c_int, [H, C.POINTER(C.c_uint64), C.c_int]),
-        "amc_get_anneal_step": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "amc_anneal_fetch": (C.c_int, [H, u64p, C.c_int, ip, C.c_int]),
+        "amc_set_anneal_records": (C.c_int, [H, u64p, C.c_int]),
+        "amc_get_anneal_step": (C.c_int, [H, u64p]),
         "amc_set_anneal_step": (C.c_int, [H, C.c_uint64]),
         "amc_get_beta": (C.c_int, [H, dp]),
         "amc_set_beta": (C.c_int, [H, C.c_double]),
         "amc_set_anneal_families": (C.c_int, [H, C.c_int]),
-        "amc_anneal_family_stats": (C.c_int, [H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "amc_anneal_family_stats": (C.c_int, [H, u64p, u64p, u64p]),
         "amc_download_families": (C.c_int, [H, C.POINTER(C.c_uint32)]),
         "amc_upload_families": (C.c_int, [H, C.POINTER(C.c_uint32)]),
     }
@@ -268,8 +264,34 @@ def potential_check(expr: str) -> str:
     return buf.value.decode(errors="replace")
 
 
-def _dptr(a: Optional[np.ndarray]):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+_POINTERS = {np.dtype(t): C.POINTER(c) for t, c in (
+    (np.float64, C.c_double), (np.float32, C.c_float), (np.int64, C.c_int64), (np.uint64, C.c_uint64), (np.int32, C.c_int),
+    (np.uint32, C.c_uint32), (np.uint8, C.c_uint8))}
+
+
+def _ptr(a: Optional[np.ndarray]):
+    """The pointer to a contiguous array's data, typed after its dtype as the entry point's prototype has it (None: NULL)."""
+    return None if a is None else a.ctypes.data_as(_POINTERS[a.dtype])
+
+
+def _carray(ctype, values, n: int):
+    """``values`` as a ctypes array of at least one entry: the learn_ids / kinds (c_int) and hyperparameters (c_double) of amc_pg_*."""
+    conv = float if ctype is C.c_double else int
+    return (ctype * max(n, 1))(*[conv(v) for v in values])
+
+
+def _u64_property(name: str):
+    """The step index amc_get_<name> / amc_set_<name> as a property."""
+    getter, setter = "amc_get_" + name, "amc_set_" + name
+
+    def get(self) -> int:
+        t = C.c_uint64(0)
+        _check(getattr(self._lib, getter)(self._h, C.byref(t)))
+        return t.value
+
+    def put(self, t: int) -> None:
+        _check(getattr(self._lib, setter)(self._h, int(t)))
+    return property(get, put)
 
 
 # ---- reproducible sums (include/amc.h "Reproducible sums"): records are rows of AMC_XSUM_WORDS doubles -----------------
@@ -279,7 +301,7 @@ def xsum_merge(into: np.ndarray, other: np.ndarray) -> np.ndarray:
     b = np.ascontiguousarray(other, dtype=np.float64).reshape(-1, AMC_XSUM_WORDS)
     if a.shape != b.shape:
         raise AmcError(f"xsum_merge: record arrays of shapes {a.shape} and {b.shape}")
-    _check(load().amc_xsum_merge(_dptr(a), _dptr(b), a.shape[0]))
+    _check(load().amc_xsum_merge(_ptr(a), _ptr(b), a.shape[0]))
     return a
 
 
@@ -287,7 +309,7 @@ def xsum_round(records: np.ndarray) -> np.ndarray:
     """The Float64 of each record: the integer total rounded once."""
     a = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, AMC_XSUM_WORDS)
     out = np.empty(a.shape[0], dtype=np.float64)
-    _check(load().amc_xsum_round(_dptr(a), a.shape[0], _dptr(out)))
+    _check(load().amc_xsum_round(_ptr(a), a.shape[0], _ptr(out)))
     return out
 
 
@@ -342,6 +364,7 @@ class HipEngine:
                            "and CustomPotential(expr)")
         self.n_chains = int(n_chains)
         self.n_moves = len(sigma)
+        self.n_rungs = 0                       # rungs per ladder (set_ladder sets it; 0: no ladder)
         self.n_params = int(n_params)
         self.gd_stride = 2 + 2 * self.n_params + self.n_params ** 2          # AMC_GD_STRIDE_P
         if self.n_params != 1 and proposal is None:
@@ -439,7 +462,7 @@ class HipEngine:
             beta = np.ascontiguousarray(beta, dtype=np.float64)
             if beta.shape != (self.n_chains,):
                 raise AmcError("upload_state: beta must have one entry per chain")
-        _check(self._lib.amc_upload_state(self._h, _dptr(x), _dptr(beta)))
+        _check(self._lib.amc_upload_state(self._h, _ptr(x), _ptr(beta)))
 
     def init_uniform(self, lo: float, hi: float) -> None:
         _check(self._lib.amc_init_uniform(self._h, float(lo), float(hi)))
@@ -447,37 +470,38 @@ class HipEngine:
     def download_state(self, want_e: bool = True):
         x = np.empty(self.n_chains, dtype=np.float64)
         e = np.empty(self.n_chains, dtype=np.float64) if want_e else None
-        _check(self._lib.amc_download_state(self._h, _dptr(x), _dptr(e)))
+        _check(self._lib.amc_download_state(self._h, _ptr(x), _ptr(e)))
         return x, e
 
-    def download_counters(self):
-        acc = np.empty((self.n_moves, self.n_chains), dtype=np.int64)
-        tot = np.empty((self.n_moves, self.n_chains), dtype=np.int64)
-        p = C.POINTER(C.c_int64)
-        _check(self._lib.amc_download_counters(self._h, acc.ctypes.data_as(p), tot.ctypes.data_as(p)))
+    def _rungs(self) -> int:
+        return max(self.n_rungs, 1)                    # R as array shapes need it: at least 1, ladder or none
+
+    def _i64_pair(self, fn, shape):
+        """What an entry point ``fn(handle, int64 *, int64 *)`` writes, as two arrays of ``shape``."""
+        acc = np.zeros(shape, dtype=np.int64)
+        tot = np.zeros(shape, dtype=np.int64)
+        _check(fn(self._h, _ptr(acc), _ptr(tot)))
         return acc, tot
+
+    def download_counters(self):
+        return self._i64_pair(self._lib.amc_download_counters, (self.n_moves, self.n_chains))
 
     def counter_totals(self):
-        acc = np.zeros(self.n_moves, dtype=np.int64)
-        tot = np.zeros(self.n_moves, dtype=np.int64)
-        p = C.POINTER(C.c_int64)
-        _check(self._lib.amc_counter_totals(self._h, acc.ctypes.data_as(p), tot.ctypes.data_as(p)))
-        return acc, tot
+        return self._i64_pair(self._lib.amc_counter_totals, self.n_moves)
 
     def upload_counters(self, accepted: np.ndarray, total: Optional[np.ndarray] = None) -> None:
-        p = C.POINTER(C.c_int64)
         a = np.ascontiguousarray(accepted, dtype=np.int64).reshape(self.n_moves, self.n_chains)
         t = None if total is None else np.ascontiguousarray(total, dtype=np.int64).reshape(self.n_moves, self.n_chains)
-        _check(self._lib.amc_upload_counters(self._h, a.ctypes.data_as(p), None if t is None else t.ctypes.data_as(p)))
+        _check(self._lib.amc_upload_counters(self._h, _ptr(a), _ptr(t)))
 
     def set_counter_totals(self, accepted: int, steps_counted: int) -> None:
         a = np.array([int(accepted)], dtype=np.int64)
-        _check(self._lib.amc_set_counter_totals(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), int(steps_counted)))
+        _check(self._lib.amc_set_counter_totals(self._h, _ptr(a), int(steps_counted)))
 
     def histogram(self, lo: float, hi: float, n_bins: int) -> np.ndarray:
         """counts[n_bins + 3]: the bins of [lo, hi), then below lo, at/above hi, NaN (this shard only)."""
         out = np.zeros(int(n_bins) + 3, dtype=np.uint64)
-        _check(self._lib.amc_histogram(self._h, float(lo), float(hi), int(n_bins), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        _check(self._lib.amc_histogram(self._h, float(lo), float(hi), int(n_bins), _ptr(out)))
         return out
 
     def histogram_accumulate(self, lo: float, hi: float, n_bins: int) -> None:
@@ -486,44 +510,30 @@ class HipEngine:
 
     def histogram_fetch(self, n_bins: int, reset: bool = True) -> np.ndarray:
         out = np.zeros(int(n_bins) + 3, dtype=np.uint64)
-        _check(self._lib.amc_histogram_fetch(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_bins), 1 if reset else 0))
+        _check(self._lib.amc_histogram_fetch(self._h, _ptr(out), int(n_bins), 1 if reset else 0))
         return out
 
     def download_strided(self, first: int, stride: int, count: int) -> np.ndarray:
         out = np.empty(int(count), dtype=np.float64)
-        _check(self._lib.amc_download_strided(self._h, int(first), int(stride), int(count), _dptr(out)))
+        _check(self._lib.amc_download_strided(self._h, int(first), int(stride), int(count), _ptr(out)))
         return out
 
-    @property
-    def estimator_step(self) -> int:
-        t = C.c_uint64(0)
-        _check(self._lib.amc_get_estimator_step(self._h, C.byref(t)))
-        return t.value
-
-    @estimator_step.setter
-    def estimator_step(self, t: int) -> None:
-        _check(self._lib.amc_set_estimator_step(self._h, int(t)))
+    # the Philox step indices of the sweeps, the estimator, the exchange steps and the annealing steps
+    step = _u64_property("step")
+    estimator_step = _u64_property("estimator_step")
+    exchange_step = _u64_property("exchange_step")
+    anneal_step = _u64_property("anneal_step")
 
     # -- hot path ----------------------------------------------------------------
     def sweep(self, n_sweeps: int = 1) -> None:
         _check(self._lib.amc_sweep(self._h, int(n_sweeps)))
 
-    @property
-    def step(self) -> int:
-        t = C.c_uint64(0)
-        _check(self._lib.amc_get_step(self._h, C.byref(t)))
-        return t.value
-
-    @step.setter
-    def step(self, t: int) -> None:
-        _check(self._lib.amc_set_step(self._h, int(t)))
-
     def reduce(self) -> np.ndarray:
         out = np.empty(AMC_RED_HEADER + self.n_moves, dtype=np.float64)
-        _check(self._lib.amc_reduce(self._h, _dptr(out)))
+        _check(self._lib.amc_reduce(self._h, _ptr(out)))
         return out
 
-    REDUCE_E, REDUCE_X, REDUCE_XX, REDUCE_ALL = 1, 2, 4, 7
+    REDUCE_E, REDUCE_X, REDUCE_XX, REDUCE_ALL = AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_REDUCE_ALL
 
     def set_reduce_columns(self, columns: int) -> None:
         """Which of sum e / sum x / sum x^2 the reductions begun from now on form (amc_set_reduce_columns; REDUCE_* bits).  A
@@ -540,7 +550,7 @@ class HipEngine:
 
     def reduce_end(self) -> np.ndarray:
         out = np.empty(AMC_RED_HEADER + self.n_moves, dtype=np.float64)
-        _check(self._lib.amc_reduce_end(self._h, _dptr(out)))
+        _check(self._lib.amc_reduce_end(self._h, _ptr(out)))
         return out
 
     def reduce_end_exact(self):
@@ -549,7 +559,7 @@ class HipEngine:
         records into the numbers reduce_end() returns."""
         rec = np.zeros((AMC_RED_HEADER + self.n_moves, AMC_XSUM_WORDS), dtype=np.float64)
         steps = C.c_uint64(0)
-        _check(self._lib.amc_reduce_end_exact(self._h, _dptr(rec), C.byref(steps)))
+        _check(self._lib.amc_reduce_end_exact(self._h, _ptr(rec), C.byref(steps)))
         return rec, int(steps.value)
 
     def reduce_exact(self):
@@ -568,11 +578,11 @@ class HipEngine:
 
     def set_parameters(self, k: int, p: Sequence[float]) -> None:
         a = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
-        _check(self._lib.amc_set_parameters(self._h, int(k), _dptr(a), int(a.size)))
+        _check(self._lib.amc_set_parameters(self._h, int(k), _ptr(a), int(a.size)))
 
     def get_parameters(self, k: int) -> np.ndarray:
         a = np.empty(self.n_params, dtype=np.float64)
-        _check(self._lib.amc_get_parameters(self._h, int(k), _dptr(a), self.n_params))
+        _check(self._lib.amc_get_parameters(self._h, int(k), _ptr(a), self.n_params))
         return a
 
     def parameters_begin(self) -> None:
@@ -583,25 +593,23 @@ class HipEngine:
         """sigma[K] -- for a policy with several parameters all of them, shape (K, P)."""
         if self.n_params > 1:
             a = np.empty((self.n_moves, self.n_params), dtype=np.float64)
-            _check(self._lib.amc_parameters_end_all(self._h, _dptr(a), a.size))
+            _check(self._lib.amc_parameters_end_all(self._h, _ptr(a), a.size))
             return a
         a = np.empty(self.n_moves, dtype=np.float64)
-        _check(self._lib.amc_parameters_end(self._h, _dptr(a)))
+        _check(self._lib.amc_parameters_end(self._h, _ptr(a)))
         return a
 
     def pg_estimate(self, learn_ids: Sequence[int], q_batch: int) -> np.ndarray:
         n = len(learn_ids)
-        ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
         out = np.zeros((n, self.gd_stride), dtype=np.float64)
-        _check(self._lib.amc_pg_estimate(self._h, n, ids, int(q_batch), _dptr(out)))
+        _check(self._lib.amc_pg_estimate(self._h, n, _carray(C.c_int, learn_ids, n), int(q_batch), _ptr(out)))
         return out
 
     def pg_estimate_exact(self, learn_ids: Sequence[int], q_batch: int) -> np.ndarray:
         """The same fold as records, shape (n_learn, AMC_GD_STRIDE, AMC_XSUM_WORDS): what shards exchange."""
         n = len(learn_ids)
-        ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
         out = np.zeros((n, self.gd_stride, AMC_XSUM_WORDS), dtype=np.float64)
-        _check(self._lib.amc_pg_estimate_exact(self._h, n, ids, int(q_batch), _dptr(out)))
+        _check(self._lib.amc_pg_estimate_exact(self._h, n, _carray(C.c_int, learn_ids, n), int(q_batch), _ptr(out)))
         return out
 
     def sweep_launches(self, n_launches: int) -> None:
@@ -626,18 +634,14 @@ class HipEngine:
     def pg_accumulate(self, learn_ids: Sequence[int], q_batch: int) -> None:
         """Estimator step kept on the device: gradients_data[k] += gd (asynchronous)."""
         n = len(learn_ids)
-        ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
-        _check(self._lib.amc_pg_accumulate(self._h, n, ids, int(q_batch)))
+        _check(self._lib.amc_pg_accumulate(self._h, n, _carray(C.c_int, learn_ids, n), int(q_batch)))
 
     def pg_update(self, learn_ids: Sequence[int], kinds: Sequence[int], hyper0: Sequence[float],
                   hyper1: Sequence[float]) -> None:
         """average -> learning_step! -> reset on the device; sigma and its table are refreshed in place."""
         n = len(learn_ids)
-        ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
-        kd = (C.c_int * max(n, 1))(*[int(k) for k in kinds])
-        h0 = (C.c_double * max(n, 1))(*[float(v) for v in hyper0])
-        h1 = (C.c_double * max(n, 1))(*[float(v) for v in hyper1])
-        _check(self._lib.amc_pg_update(self._h, n, ids, kd, h0, h1))
+        _check(self._lib.amc_pg_update(self._h, n, _carray(C.c_int, learn_ids, n), _carray(C.c_int, kinds, n), _carray(C.c_double, hyper0, n),
+                                       _carray(C.c_double, hyper1, n)))
 
     def pgmc_steps(self, n_steps: int, learn_ids: Sequence[int], q_batch: int, kinds: Optional[Sequence[int]] = None,
                    hyper0: Sequence[float] = (), hyper1: Sequence[float] = (), reduce_begin: bool = False) -> None:
@@ -645,7 +649,7 @@ class HipEngine:
         ``reduce_begin``: followed by reduce_begin() of the state the last step leaves -- the callback sums then ride in that
         step's launch (amc_pgmc_steps_reduce_begin); fetch them with reduce_end()."""
         n = len(learn_ids)
-        ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
+        ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])           # (the step loop's call: _carray spelt out)
         do_update = kinds is not None
         kd = (C.c_int * max(n, 1))(*[int(k) for k in (kinds or [0] * n)])
         h0 = (C.c_double * max(n, 1))(*[float(v) for v in (hyper0 if do_update else [0.0] * n)])
@@ -655,17 +659,15 @@ class HipEngine:
 
     def pg_get_accumulated(self, learn_ids: Sequence[int]) -> np.ndarray:
         n = len(learn_ids)
-        ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
         out = np.zeros((n, self.gd_stride), dtype=np.float64)
-        _check(self._lib.amc_pg_get_accumulated(self._h, n, ids, _dptr(out)))
+        _check(self._lib.amc_pg_get_accumulated(self._h, n, _carray(C.c_int, learn_ids, n), _ptr(out)))
         return out
 
     def pg_set_accumulated(self, learn_ids: Sequence[int], rows: np.ndarray) -> None:
         """Resume: replace the device-resident gradients_data of the moves learn_ids by rows[n][5] (j, grad_j, grad_logq, g, n)."""
         n = len(learn_ids)
-        ids = (C.c_int * max(n, 1))(*[int(i) for i in learn_ids])
         a = np.ascontiguousarray(rows, dtype=np.float64).reshape(n, self.gd_stride)
-        _check(self._lib.amc_pg_set_accumulated(self._h, n, ids, _dptr(a)))
+        _check(self._lib.amc_pg_set_accumulated(self._h, n, _carray(C.c_int, learn_ids, n), _ptr(a)))
 
     # -- population annealing (include/amc.h; DESIGN.md section 3.14) ---------------------------------------
     def anneal(self, beta_new: float) -> None:
@@ -679,22 +681,12 @@ class HipEngine:
         n = C.c_int(0)
         _check(self._lib.amc_anneal_fetch(self._h, None, 0, C.byref(n), 0))
         out = np.zeros((n.value, AMC_ANNEAL_RECORD_WORDS), dtype=np.uint64)
-        _check(self._lib.amc_anneal_fetch(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), n.value, C.byref(n), 1 if reset else 0))
+        _check(self._lib.amc_anneal_fetch(self._h, _ptr(out), n.value, C.byref(n), 1 if reset else 0))
         return out
 
     def set_anneal_records(self, records) -> None:
         rec = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, AMC_ANNEAL_RECORD_WORDS)
-        _check(self._lib.amc_set_anneal_records(self._h, rec.ctypes.data_as(C.POINTER(C.c_uint64)), int(rec.shape[0])))
-
-    @property
-    def anneal_step(self) -> int:
-        t = C.c_uint64(0)
-        _check(self._lib.amc_get_anneal_step(self._h, C.byref(t)))
-        return t.value
-
-    @anneal_step.setter
-    def anneal_step(self, t: int) -> None:
-        _check(self._lib.amc_set_anneal_step(self._h, int(t)))
+        _check(self._lib.amc_set_anneal_records(self._h, _ptr(rec), int(rec.shape[0])))
 
     @property
     def beta(self) -> float:
@@ -718,14 +710,14 @@ class HipEngine:
 
     def download_families(self) -> np.ndarray:
         out = np.empty(self.n_chains, dtype=np.uint32)
-        _check(self._lib.amc_download_families(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        _check(self._lib.amc_download_families(self._h, _ptr(out)))
         return out
 
     def upload_families(self, families) -> None:
         fam = np.ascontiguousarray(families, dtype=np.uint32)
         if fam.shape != (self.n_chains,):
             raise AmcError(f"upload_families: one id per chain ({self.n_chains})")
-        _check(self._lib.amc_upload_families(self._h, fam.ctypes.data_as(C.POINTER(C.c_uint32))))
+        _check(self._lib.amc_upload_families(self._h, _ptr(fam)))
 
     # -- replica exchange along a temperature ladder (include/amc.h) ----------------
     def set_ladder(self, n_rungs: int) -> None:
@@ -744,46 +736,30 @@ class HipEngine:
 
     def exchange_counters(self):
         """(accepted, attempted), one entry per gap r < R - 1: exact counts over this shard's ladders."""
-        n = max(int(getattr(self, "n_rungs", 0)) - 1, 1)
-        acc = np.zeros(n, dtype=np.int64)
-        att = np.zeros(n, dtype=np.int64)
-        p = C.POINTER(C.c_int64)
-        _check(self._lib.amc_exchange_counters(self._h, acc.ctypes.data_as(p), att.ctypes.data_as(p)))
-        return acc, att
+        return self._i64_pair(self._lib.amc_exchange_counters, max(self.n_rungs - 1, 1))
 
     def set_exchange_counters(self, accepted, attempted) -> None:
-        n = max(int(getattr(self, "n_rungs", 0)) - 1, 1)
+        n = max(self.n_rungs - 1, 1)
         acc = np.ascontiguousarray(accepted, dtype=np.int64).reshape(-1)
         att = np.ascontiguousarray(attempted, dtype=np.int64).reshape(-1)
         if acc.size != n or att.size != n:
             raise AmcError(f"set_exchange_counters: one entry per gap ({n}) each")
-        p = C.POINTER(C.c_int64)
-        _check(self._lib.amc_set_exchange_counters(self._h, acc.ctypes.data_as(p), att.ctypes.data_as(p)))
-
-    @property
-    def exchange_step(self) -> int:
-        t = C.c_uint64(0)
-        _check(self._lib.amc_get_exchange_step(self._h, C.byref(t)))
-        return t.value
-
-    @exchange_step.setter
-    def exchange_step(self, t: int) -> None:
-        _check(self._lib.amc_set_exchange_step(self._h, int(t)))
+        _check(self._lib.amc_set_exchange_counters(self._h, _ptr(acc), _ptr(att)))
 
     def histogram_rungs(self, lo: float, hi: float, n_bins: int) -> np.ndarray:
         """counts[R][n_bins + 3]: histogram() by rung (this shard only)."""
-        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        n = self._rungs()
         out = np.zeros((n, int(n_bins) + 3), dtype=np.uint64)
-        _check(self._lib.amc_histogram_rungs(self._h, float(lo), float(hi), int(n_bins), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        _check(self._lib.amc_histogram_rungs(self._h, float(lo), float(hi), int(n_bins), _ptr(out)))
         return out
 
     def reduce_rungs(self, columns: int = AMC_REDUCE_ALL) -> np.ndarray:
         """records[R][3][AMC_XSUM_WORDS]: per rung the reproducible sums of e, x, x^2 over this shard's ladders, one chain per summand
         (amc_reduce_rungs_exact); ``columns``: AMC_REDUCE_* bits, a column not asked for is an all-zero record.  What shards exchange
         (sharding.allreduce_xsum); ``xsum_round`` yields the Float64s.  Observes the state behind everything queued; synchronises."""
-        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        n = self._rungs()
         out = np.zeros((n, 3, AMC_XSUM_WORDS), dtype=np.float64)
-        _check(self._lib.amc_reduce_rungs_exact(self._h, int(columns), _dptr(out)))
+        _check(self._lib.amc_reduce_rungs_exact(self._h, int(columns), _ptr(out)))
         return out
 
     # -- bridge sums (include/amc.h; DESIGN.md section 3.13 "Bridge sums") ----------------
@@ -797,10 +773,10 @@ class HipEngine:
         """(records[R][6][AMC_XSUM_WORDS], n_snapshots) of this shard's accumulator, columns in the order E, EE, WF, WB, MF, MB
         (amc_bridge_fetch); ``reset`` zeroes both and frees the mask.  What shards exchange (sharding.allreduce_xsum); ``xsum_round``
         yields the Float64s.  Synchronises."""
-        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        n = self._rungs()
         out = np.zeros((n, 6, AMC_XSUM_WORDS), dtype=np.float64)
         count = C.c_uint64(0)
-        _check(self._lib.amc_bridge_fetch(self._h, _dptr(out), C.byref(count), int(bool(reset))))
+        _check(self._lib.amc_bridge_fetch(self._h, _ptr(out), C.byref(count), int(bool(reset))))
         return out, int(count.value)
 
     def set_bridge(self, records=None, n_snapshots: int = 0) -> None:
@@ -809,13 +785,13 @@ class HipEngine:
         if records is None:
             _check(self._lib.amc_set_bridge(self._h, None, 0))
             return
-        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        n = self._rungs()
         rec = np.ascontiguousarray(records, dtype=np.float64)
         if rec.size != n * 6 * AMC_XSUM_WORDS:
             raise AmcError(f"set_bridge: {rec.size} doubles, the records of {n} rungs take {n * 6 * AMC_XSUM_WORDS}")
         if int(n_snapshots) < 0:
             raise AmcError("set_bridge: n_snapshots < 0")
-        _check(self._lib.amc_set_bridge(self._h, _dptr(rec), int(n_snapshots)))
+        _check(self._lib.amc_set_bridge(self._h, _ptr(rec), int(n_snapshots)))
 
     # -- walker tracking (include/amc.h; DESIGN.md section 3.13 "Walker tracking") ----------------
     def set_tracking(self, on: bool = True) -> None:
@@ -826,7 +802,7 @@ class HipEngine:
         """(walker, direction), two uint8 arrays with one entry per local chain: the walker id in [0, R) and the end the replica last
         visited (0 none yet, 1 rung 0, 2 rung R - 1).  Synchronises."""
         lab = np.zeros(self.n_chains, dtype=np.uint8)
-        _check(self._lib.amc_download_labels(self._h, lab.ctypes.data_as(C.POINTER(C.c_uint8))))
+        _check(self._lib.amc_download_labels(self._h, _ptr(lab)))
         return lab & np.uint8(63), lab >> np.uint8(6)
 
     def set_labels(self, walker, direction) -> None:
@@ -837,13 +813,13 @@ class HipEngine:
         if w.size and (w.min() < 0 or w.max() > 63 or d.min() < 0 or d.max() > 3):
             raise AmcError("set_labels: walker ids must lie in [0, 64) and directions in [0, 4)")
         lab = np.ascontiguousarray(w | (d << 6), dtype=np.uint8)
-        _check(self._lib.amc_upload_labels(self._h, lab.ctypes.data_as(C.POINTER(C.c_uint8))))
+        _check(self._lib.amc_upload_labels(self._h, _ptr(lab)))
 
     def flow_rungs(self) -> np.ndarray:
         """counts[R][3]: the local chains at rung r whose label has direction d (this shard only), int64."""
-        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        n = self._rungs()
         out = np.zeros((n, 3), dtype=np.uint64)
-        _check(self._lib.amc_flow_rungs(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        _check(self._lib.amc_flow_rungs(self._h, _ptr(out)))
         return out.astype(np.int64)
 
     def tracking_counters(self):
@@ -863,14 +839,14 @@ class HipEngine:
             _check(self._lib.amc_set_rung_sigma(self._h, None, 0))
             return
         s = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
-        _check(self._lib.amc_set_rung_sigma(self._h, _dptr(s), int(s.size)))
+        _check(self._lib.amc_set_rung_sigma(self._h, _ptr(s), int(s.size)))
 
     def rung_sigma(self) -> np.ndarray:
         """The table in force, shape (K, R): as it was set, or -- once a tuning has been queued -- as the device holds it (the host
         then waits for the queued steps)."""
-        n = max(int(getattr(self, "n_rungs", 0)), 1)
+        n = self._rungs()
         out = np.zeros((self.n_moves, n), dtype=np.float64)
-        _check(self._lib.amc_get_rung_sigma(self._h, _dptr(out), int(out.size)))
+        _check(self._lib.amc_get_rung_sigma(self._h, _ptr(out), int(out.size)))
         return out
 
     # -- respacing the ladder (include/amc.h; DESIGN.md section 3.13 "Respacing") ----------------
@@ -884,7 +860,7 @@ class HipEngine:
             raise AmcError(f"respace_ladder: rule {rule!r} is none of {sorted(RESPACE_RULES)}")
         ptr = None
         if counts is not None:
-            R = int(getattr(self, "n_rungs", 0))
+            R = self.n_rungs
             c = np.ascontiguousarray(counts).reshape(-1)
             if c.size and (not np.all(np.isfinite(c)) or c.min() < 0 or np.any(c != np.floor(c))):
                 raise AmcError("respace_ladder: counts must be non-negative integers")
@@ -892,7 +868,7 @@ class HipEngine:
             need = 2 * (R - 1) if rule_id == AMC_RESPACE_ACCEPTANCE else 3 * R
             if c.size != need:
                 raise AmcError(f"respace_ladder: counts has {c.size} entries, rule {rule!r} with {R} rungs takes {need}")
-            ptr = c.ctypes.data_as(C.POINTER(C.c_uint64))
+            ptr = _ptr(c)
         _check(self._lib.amc_respace_ladder(self._h, int(rule_id), float(gamma), float(eps), ptr))
 
     def respace_status(self):
@@ -906,13 +882,13 @@ class HipEngine:
 
     def ladder(self) -> np.ndarray:
         """The R beta values of the ladder as the device holds them (the first local ladder).  Synchronises."""
-        out = np.zeros(max(int(getattr(self, "n_rungs", 0)), 1), dtype=np.float64)
-        _check(self._lib.amc_get_ladder(self._h, _dptr(out)))
+        out = np.zeros(self._rungs(), dtype=np.float64)
+        _check(self._lib.amc_get_ladder(self._h, _ptr(out)))
         return out
 
     # -- tuning the widths per rung (include/amc.h; DESIGN.md section 3.13 "Tuning the widths") ----------------
     def _cells(self):
-        return self.n_moves, max(int(getattr(self, "n_rungs", 0)), 1)
+        return self.n_moves, self._rungs()             # the shape (K, R) of a table per (move, rung)
 
     def tune_rung_sigma(self, target: float = 0.44, gamma: float = 1.0, min_calls: int = 1000, sigma_lo: float = 1e-100,
                         sigma_hi: float = 1e100, counts=None) -> None:
@@ -931,7 +907,7 @@ class HipEngine:
             if c.dtype.kind not in "iu" and (not np.all(np.isfinite(c)) or np.any(c != np.floor(c))):
                 raise AmcError("tune_rung_sigma: counts must be integers")
             c = np.ascontiguousarray(c, dtype=np.int64)
-            ptr = c.ctypes.data_as(C.POINTER(C.c_int64))
+            ptr = _ptr(c)
         _check(self._lib.amc_tune_rung_sigma(self._h, float(target), float(gamma), int(min_calls), float(sigma_lo), float(sigma_hi), ptr))
 
     def tune_status(self):
@@ -940,24 +916,16 @@ class HipEngine:
         K, R = self._cells()
         st = np.zeros((K, R), dtype=np.int32)
         n = C.c_int64(0)
-        _check(self._lib.amc_tune_status(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), int(st.size), C.byref(n)))
+        _check(self._lib.amc_tune_status(self._h, _ptr(st), int(st.size), C.byref(n)))
         return st, n.value
 
     def set_tuned(self, n_tuned: int) -> None:
         _check(self._lib.amc_set_tuned(self._h, int(n_tuned)))
 
-    def _i64_pair(self, fn):
-        K, R = self._cells()
-        acc = np.zeros((K, R), dtype=np.int64)
-        tot = np.zeros((K, R), dtype=np.int64)
-        p = C.POINTER(C.c_int64)
-        _check(fn(self._h, acc.ctypes.data_as(p), tot.ctypes.data_as(p)))
-        return acc, tot
-
     def rung_window_counts(self):
         """(accepted, total) of this shard over the current window, each of shape (K, R); -1 in both where the counters were replaced
         behind the window's start.  Synchronises, changes nothing."""
-        return self._i64_pair(self._lib.amc_rung_window_counts)
+        return self._i64_pair(self._lib.amc_rung_window_counts, self._cells())
 
     def rung_window_restart(self) -> None:
         """The window starts here (stream-ordered, nothing is read back)."""
@@ -965,7 +933,7 @@ class HipEngine:
 
     def rung_window_base(self):
         """(accepted, total) per (move, rung) as they stood when the window began."""
-        return self._i64_pair(self._lib.amc_rung_window_base)
+        return self._i64_pair(self._lib.amc_rung_window_base, self._cells())
 
     def set_rung_window_base(self, accepted, total) -> None:
         K, R = self._cells()
@@ -973,17 +941,11 @@ class HipEngine:
         t = np.ascontiguousarray(total, dtype=np.int64).reshape(-1)
         if a.size != K * R or t.size != K * R:
             raise AmcError(f"set_rung_window_base: {a.size} and {t.size} entries, the window of {K} moves x {R} rungs has {K * R}")
-        p = C.POINTER(C.c_int64)
-        _check(self._lib.amc_set_rung_window_base(self._h, a.ctypes.data_as(p), t.ctypes.data_as(p)))
+        _check(self._lib.amc_set_rung_window_base(self._h, _ptr(a), _ptr(t)))
 
     def rung_counter_totals(self):
         """(accepted, total), each of shape (K, R): the Move counters summed over this shard's ladders per (move, rung), exact."""
-        n = max(int(getattr(self, "n_rungs", 0)), 1)
-        acc = np.zeros((self.n_moves, n), dtype=np.int64)
-        tot = np.zeros((self.n_moves, n), dtype=np.int64)
-        p = C.POINTER(C.c_int64)
-        _check(self._lib.amc_rung_counter_totals(self._h, acc.ctypes.data_as(p), tot.ctypes.data_as(p)))
-        return acc, tot
+        return self._i64_pair(self._lib.amc_rung_counter_totals, self._cells())
 
     def sync(self) -> None:
         _check(self._lib.amc_sync(self._h))
@@ -1019,13 +981,13 @@ class HipEngine:
 
     def allreduce_sum(self, a: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a, dtype=np.float64).copy()
-        _check(self._lib.amc_allreduce_sum(self._h, _dptr(a), int(a.size)))
+        _check(self._lib.amc_allreduce_sum(self._h, _ptr(a), int(a.size)))
         return a
 
     def allreduce_xsum(self, records: np.ndarray) -> np.ndarray:
         """The merged records of all shards (amc_allreduce_xsum: one RCCL all-reduce used as a gather, then the integer merge)."""
         a = np.ascontiguousarray(records, dtype=np.float64).copy()
-        _check(self._lib.amc_allreduce_xsum(self._h, _dptr(a), int(a.size // AMC_XSUM_WORDS)))
+        _check(self._lib.amc_allreduce_xsum(self._h, _ptr(a), int(a.size // AMC_XSUM_WORDS)))
         return a
 
     def comm_destroy(self) -> None:
@@ -1195,14 +1157,12 @@ class SplitEngine:
 
     def timing_begin(self) -> None:
         self.sync()
-        import time
         self._t0 = time.perf_counter()
 
     def timing_end(self) -> float:
         """Wall-clock ms between timing_begin and the completion of everything queued since (the parts run on
         different streams: there is no single pair of stream events that brackets them)."""
         self.sync()
-        import time
         return (time.perf_counter() - self._t0) * 1e3
 
 
@@ -1215,7 +1175,7 @@ def selftest_math(fn: str, a: np.ndarray, b: Optional[np.ndarray] = None, device
     if b is not None:
         b = np.ascontiguousarray(b, dtype=np.float64)
     out = np.empty_like(a)
-    _check(load().amc_selftest_math(int(device), ids[fn], _dptr(a), _dptr(b), _dptr(out), a.size))
+    _check(load().amc_selftest_math(int(device), ids[fn], _ptr(a), _ptr(b), _ptr(out), a.size))
     return out
 
 
@@ -1233,8 +1193,7 @@ def selftest_filter_argument(beta: float, sigma: float, x: np.ndarray, delta: np
     delta = np.ascontiguousarray(delta, dtype=np.float64)
     assert x.shape == delta.shape
     out = np.empty(x.shape, dtype=np.float32)
-    _check(load().amc_selftest_filter_argument(int(device), C.c_double(beta), C.c_double(sigma), _dptr(x), _dptr(delta),
-                                               out.ctypes.data_as(C.POINTER(C.c_float)), x.size))
+    _check(load().amc_selftest_filter_argument(int(device), C.c_double(beta), C.c_double(sigma), _ptr(x), _ptr(delta), _ptr(out), x.size))
     return out
 
 
@@ -1244,10 +1203,7 @@ def selftest_philox(seed: int, pair: np.ndarray, t: np.ndarray, draw: int, strea
     pair = np.ascontiguousarray(pair, dtype=np.uint64)
     t = np.ascontiguousarray(t, dtype=np.uint64)
     out = np.empty((pair.size, 4), dtype=np.uint32)
-    u64p = C.POINTER(C.c_uint64)
-    _check(load().amc_selftest_philox(int(device), C.c_uint64(int(seed)), pair.ctypes.data_as(u64p),
-                                      t.ctypes.data_as(u64p), int(draw), int(stream),
-                                      out.ctypes.data_as(C.POINTER(C.c_uint32)), pair.size))
+    _check(load().amc_selftest_philox(int(device), C.c_uint64(int(seed)), _ptr(pair), _ptr(t), int(draw), int(stream), _ptr(out), pair.size))
     return out
 
 
@@ -1258,14 +1214,12 @@ def selftest_wave_totals(values: np.ndarray, device: int = 0):
     assert values.shape == (6, 64)
     out = np.zeros(13, dtype=np.int64)
     ref = np.zeros(6, dtype=np.int64)
-    i64p = C.POINTER(C.c_int64)
-    _check(load().amc_selftest_wave_totals(int(device), values.ctypes.data_as(i64p), out.ctypes.data_as(i64p),
-                                           ref.ctypes.data_as(i64p)))
+    _check(load().amc_selftest_wave_totals(int(device), _ptr(values), _ptr(out), _ptr(ref)))
     return out, ref
 
 
 def selftest_staged_tables(device: int = 0) -> np.ndarray:
     """The 546 doubles of the math tables as a block holds them in LDS, staged and copied out on the GPU (parity tests only)."""
     out = np.empty(546, dtype=np.float64)
-    _check(load().amc_selftest_staged_tables(int(device), _dptr(out)))
+    _check(load().amc_selftest_staged_tables(int(device), _ptr(out)))
     return out

@@ -63,7 +63,7 @@ class PopulationAnnealing(AriannaAlgorithm):
         if any(isinstance(a, ReplicaExchange) for a in simulation.algorithms):
             raise ValueError("PopulationAnnealing: the algorithm list holds a ReplicaExchange; a ladder and an annealed population "
                              "exclude each other")
-        if self.families and not getattr(self.metropolis, "families_restored", False):     # (restored: storage.restore brought them back)
+        if self.families and not self.metropolis.families_restored:     # (restored: storage.restore brought them back)
             self.metropolis.engine.set_anneal_families(True)
 
     def make_step(self, simulation: Simulation) -> None:

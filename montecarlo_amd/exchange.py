@@ -74,7 +74,7 @@ class ReplicaExchange(AriannaAlgorithm):
 
     def initialise(self, simulation: Simulation) -> None:
         self.metropolis.set_ladder(self.n_rungs)       # (the per-chain beta array is on the device by now: Metropolis comes first)
-        if self.track and not getattr(self.metropolis, "tracking", False):     # (on already: storage.restore brought the labels back)
+        if self.track and not self.metropolis.tracking:     # (on already: storage.restore brought the labels back)
             self.metropolis.engine.set_tracking(True)
             self.metropolis.tracking = True
 
@@ -344,7 +344,7 @@ class TuneRungSigma(AriannaAlgorithm):
         self.statuses = []         # (t, status array (K, R)) of every tuning asked for
 
     def initialise(self, simulation: Simulation) -> None:
-        if getattr(self.metropolis, "restored", False) and getattr(self.metropolis, "_rung_window_used", False):
+        if self.metropolis.restored and self.metropolis._rung_window_used:
             return                 # (storage.restore brought the window back: the resumed run tunes as the uninterrupted one)
         self.metropolis.restart_rung_window()
 

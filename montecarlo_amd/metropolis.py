@@ -105,6 +105,19 @@ class Metropolis(AriannaAlgorithm):
         if not all(isinstance(m, Move) for m in pool):
             raise TypeError("Metropolis: pool must hold Move objects")
         self.pool = tuple(pool)
+        # ---- the state of a run that collaborators set; everything a reader may find is declared here ----
+        self.n_rungs = 0                    # rungs per ladder (set_ladder; 0: no ladder)
+        self.tracking = False               # walker tracking is on (ReplicaExchange.initialise, storage.restore; set_ladder turns it off)
+        self.bridge = 0                     # mask of the bridge sums (ReplicaExchange.__init__; 0: off)
+        self.annealing = None               # the PopulationAnnealing that cools these chains (its __init__)
+        self.restored = False               # storage.restore put the state on the device: initialise() leaves it there
+        self.families_restored = False      # storage.restore brought the annealing families back
+        self._rung_window_used = False      # a tuning or a window restart has happened (tune_rung_sigma, restart_rung_window, storage.restore)
+        self.device_params_dirty = False    # device-resident learning steps moved sigma (PolicyGradientUpdate; pull_parameters clears it)
+        self._pending_red_epoch = None      # epoch of a reduction formed inside a sweep launch that nobody has claimed (make_step)
+        self._param_ticket = None           # the one parameter read in flight (parameters_async)
+        self._red_cols = 7                  # the sums over x the reductions form (set_reduction_needs)
+        self._histogram_owner = None        # the StoreHistogram that owns the engine's running histogram (its make_step / finalise)
         # widths per (move, rung) of a temperature ladder (DESIGN.md section 3.13 "Widths per rung"): checked here, before an engine
         # exists, handed to the engine when the ladder is set (set_ladder)
         self.rung_sigma = None if rung_sigma is None else _check_rung_sigma(rung_sigma, self.pool, int(streams))
@@ -187,7 +200,7 @@ class Metropolis(AriannaAlgorithm):
 
     # ---- plugin protocol ---------------------------------------------------------------
     def initialise(self, simulation: Simulation) -> None:
-        if getattr(self, "restored", False):        # storage.restore() already put the state on the device
+        if self.restored:        # storage.restore() already put the state on the device
             self._epoch += 1
             return
         start, stop = self.shard
@@ -218,7 +231,7 @@ class Metropolis(AriannaAlgorithm):
         self._epoch += 1
 
     def _drop_pending_reduction(self) -> None:
-        if getattr(self, "_pending_red_epoch", None) is not None:
+        if self._pending_red_epoch is not None:
             self._settle_claimed()              # the engine hands reductions back oldest first: fetch what callbacks hold,
             self.engine.reduce_end_exact()      # then discard the one nobody asked for
             self._pending_red_epoch = None
@@ -248,7 +261,7 @@ class Metropolis(AriannaAlgorithm):
             raise ValueError("ReplicaExchange: the chains need a per-chain beta array (ParticleChains.ladder)")
         if not hasattr(self.engine, "set_ladder"):
             raise ValueError("ReplicaExchange: this engine has no exchange move (streams > 1 is not supported)")
-        if getattr(self, "n_rungs", 0) == R:
+        if self.n_rungs == R:
             return                              # set already (storage.restore): setting it again would zero the gap counters
         if self.rung_sigma is not None and self.rung_sigma.shape[1] != R:
             raise ValueError(f"Metropolis: rung_sigma has {self.rung_sigma.shape[1]} rungs per move, the ladder has R = {R}")
@@ -262,7 +275,7 @@ class Metropolis(AriannaAlgorithm):
         """accepted_calls / total_calls of every move per rung over ALL shards, shape (K, R): the exact integer totals of the
         per-chain counters (amc_rung_counter_totals) added across shards, then divided; 0/0 = NaN.  Needs a ladder and per-chain
         counters, with or without ``rung_sigma``.  The host waits for the queued steps."""
-        if not getattr(self, "n_rungs", 0):
+        if not self.n_rungs:
             raise ValueError("Metropolis.rung_acceptance: the chains have no ladder (ReplicaExchange)")
         acc, tot = self.engine.rung_counter_totals()
         both = sharding.allreduce_sum(np.concatenate([acc.reshape(-1), tot.reshape(-1)]).astype(np.float64), self.engine)
@@ -272,7 +285,7 @@ class Metropolis(AriannaAlgorithm):
 
     # ---- tuning the widths per rung (DESIGN.md section 3.13 "Tuning the widths") ---------------
     def _need_rung_table(self, who: str) -> None:
-        if not getattr(self, "n_rungs", 0):
+        if not self.n_rungs:
             raise ValueError(f"Metropolis.{who}: the chains have no ladder (ReplicaExchange)")
         if self.rung_sigma is None:
             raise ValueError(f"Metropolis.{who}: no widths per rung are set (Metropolis(..., rung_sigma=...))")
@@ -326,7 +339,7 @@ class Metropolis(AriannaAlgorithm):
     def rung_window_acceptance(self) -> np.ndarray:
         """accepted / total calls of every move per rung over the current window and ALL shards, shape (K, R): what the next
         tune_rung_sigma() would read.  0/0 and inconsistent cells are NaN.  The host waits for the queued steps."""
-        if not getattr(self, "n_rungs", 0):
+        if not self.n_rungs:
             raise ValueError("Metropolis.rung_window_acceptance: the chains have no ladder (ReplicaExchange)")
         acc, tot, bad = self._global_window()
         with np.errstate(invalid="ignore", divide="ignore"):
@@ -336,7 +349,7 @@ class Metropolis(AriannaAlgorithm):
 
     def restart_rung_window(self) -> None:
         """The window of rung_window_acceptance() / tune_rung_sigma() starts here (stream-ordered)."""
-        if not getattr(self, "n_rungs", 0):
+        if not self.n_rungs:
             raise ValueError("Metropolis.restart_rung_window: the chains have no ladder (ReplicaExchange)")
         self.engine.rung_window_restart()
         self._rung_window_used = True
@@ -351,7 +364,7 @@ class Metropolis(AriannaAlgorithm):
         self._drop_pending_reduction()
         self._settle_claimed()
         self.set_reduction_needs(None)          # the run's narrowing ends with the run: a caller of reductions() gets every entry
-        if getattr(self, "device_params_dirty", False):
+        if self.device_params_dirty:
             self.pull_parameters()
         if self.download_on_finalise:
             x, e = self.engine.download_state(want_e=True)
@@ -396,7 +409,7 @@ class Metropolis(AriannaAlgorithm):
         """The parameters of every move as of the steps queued so far, as a ticket (engine.parameters_begin: a copy in stream
         order; ``result()`` fetches it).  The engine keeps ONE such read in flight: algorithms that ask at the same time step
         share the ticket, and a new time step first fetches the older read -- whoever holds it gets the values all the same."""
-        tk = getattr(self, "_param_ticket", None)
+        tk = self._param_ticket
         if tk is not None and tk.t == t:
             return tk
         if tk is not None:
@@ -421,11 +434,11 @@ class Metropolis(AriannaAlgorithm):
         callback's row when the next one is due) never makes the host wait for the device, and the sweeps queued in
         between are not held back by it.  Values are those of the state at the time of this call either way."""
         key = self._epoch
-        cols = getattr(self, "_red_cols", 7)
+        cols = self._red_cols
         if self._red_key == key and self._red_val is not None and (self._red_val.cols & cols) == cols:
             return self._red_val        # (a cached reduction formed with fewer columns than are asked for now is not reused)
         ticket = Reduction(self, cols)
-        if getattr(self, "_pending_red_epoch", None) == self._epoch:
+        if self._pending_red_epoch == self._epoch:
             self._pending_red_epoch = None      # formed inside the launch (make_step(with_reductions=True)): claim it
             self._inflight.append(ticket)
         else:
@@ -453,7 +466,7 @@ class Metropolis(AriannaAlgorithm):
         cols = 7 if needs is None else ((1 if "energy" in needs else 0) | (2 if "mean_x" in needs else 0) | (4 if "mean_x2" in needs else 0))
         self._drop_pending_reduction()
         self.engine.set_reduce_columns(cols)
-        if cols != getattr(self, "_red_cols", 7):
+        if cols != self._red_cols:
             # a reduction cached for the current state was formed with the old columns: a caller who asks after the change
             # (callback_moments(simulation) after a run narrowed to energy) gets a new one, not NaN entries
             self._red_key = self._red_val = None

@@ -215,7 +215,7 @@ class PolicyGradientEstimator(AriannaAlgorithm):
         torch.distributed has loaded.  False (host path via pg_estimate + torch all-reduce) when there is no NCCL
         process group or the engine cannot do it."""
         met = self.metropolis
-        if getattr(met, "_comm_connected", False):
+        if met._comm_connected:
             return True
         met._comm_connected = sharding.connect_engine(met.engine)
         return met._comm_connected

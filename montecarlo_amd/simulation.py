@@ -30,6 +30,12 @@ from . import sharding
 class AriannaAlgorithm:
     """src/algorithms.jl:6-37: the four generic functions every algorithm implements."""
 
+    # what run() asks of an algorithm when it schedules the launches; a subclass overrides what applies to it
+    fusable = False                 # consecutive time steps that schedule nothing else go out as one make_steps(n) (Metropolis)
+    wants_reductions = False        # reads the sampler's reductions at its time steps (StoreCallbacks, StoreHistogram)
+    mutates_chains = False          # moves the chains: a reader due behind it at the same t observes the state it leaves
+    pgmc_role = None                # "estimator" / "update": the policy-gradient pair that run() may group with its Metropolis
+
     def initialise(self, simulation: "Simulation") -> None:
         return None
 
@@ -228,7 +234,7 @@ def _declare_reduction_needs(sim: Simulation) -> None:
     for alg in sim.algorithms:
         if not type(alg).__module__.startswith(__name__.rsplit(".", 1)[0] + "."):
             known = False
-        if not getattr(alg, "wants_reductions", False):
+        if not alg.wants_reductions:
             continue
         any_consumer = True
         n = alg.reduction_needs() if hasattr(alg, "reduction_needs") else None
@@ -261,13 +267,13 @@ def run(simulation: Simulation, fuse: bool = True) -> None:
             sim.t = t
             advance = 1
             due = [k for k in range(n_alg) if _due(sim, k) == t]
-            if fuse and due and getattr(sim.algorithms[due[0]], "fusable", False):
+            if fuse and due and sim.algorithms[due[0]].fusable:
                 taken = _exchange_group(sim, due, t)          # time steps, not rounds
                 if taken:
                     sim.t = t + taken - 1
                     t += taken
                     continue
-            if fuse and len(due) == 1 and getattr(sim.algorithms[due[0]], "fusable", False):
+            if fuse and len(due) == 1 and sim.algorithms[due[0]].fusable:
                 k = due[0]
                 others = [d for j in range(n_alg) if j != k for d in [_due(sim, j)] if d is not None]
                 horizon = min(others) if others else sim.steps + 1
@@ -296,7 +302,7 @@ def run(simulation: Simulation, fuse: bool = True) -> None:
                     continue
             for i, k in enumerate(due):                                             # :185-190
                 alg = sim.algorithms[k]
-                if getattr(alg, "fusable", False) and _observed_next(sim, due[i + 1:]):
+                if alg.fusable and _observed_next(sim, due[i + 1:]):
                     alg.make_step(sim, with_reductions=True)    # callbacks follow at this t: sums formed in-kernel
                 else:
                     alg.make_step(sim)
@@ -356,13 +362,13 @@ def _pgmc_group(simulation: Simulation, due: Sequence[int], t: int):
     before.  (0, 0) when the pattern does not apply."""
     sim = simulation
     algs = [sim.algorithms[k] for k in due]
-    if not getattr(algs[0], "fusable", False) or getattr(algs[1], "pgmc_role", None) != "estimator":
+    if not algs[0].fusable or algs[1].pgmc_role != "estimator":
         return 0, 0
     est = algs[1]
     if getattr(est, "metropolis", None) is not algs[0] or not hasattr(est, "make_steps_grouped"):
         return 0, 0
     m, upd = 2, None
-    if len(due) >= 3 and getattr(algs[2], "pgmc_role", None) == "update" and getattr(algs[2], "estimator", None) is est:
+    if len(due) >= 3 and algs[2].pgmc_role == "update" and getattr(algs[2], "estimator", None) is est:
         m, upd = 3, algs[2]
     head = list(due[:m])
     others = [(j, d) for j in range(len(sim.algorithms)) if j not in head for d in [_due(sim, j)] if d is not None]
@@ -382,9 +388,9 @@ def _observed_next(simulation: Simulation, later: Sequence[int]) -> bool:
     any that moves the chains (the estimator perturbs x: src/PolicyGuided/gradients.jl:98,103)."""
     for k in later:
         alg = simulation.algorithms[k]
-        if getattr(alg, "mutates_chains", False):
+        if alg.mutates_chains:
             return False
-        if getattr(alg, "wants_reductions", False):
+        if alg.wants_reductions:
             return True
     return False
 
@@ -540,7 +546,7 @@ class StoreParameters(AriannaAlgorithm):
 
     def make_step(self, simulation: Simulation) -> None:
         met = self.metropolis
-        if getattr(met, "device_params_dirty", False):
+        if met.device_params_dirty:
             if self.defer and hasattr(met.engine, "parameters_begin"):
                 self.flush()                        # the previous row first (its read was queued a period ago)
                 # sigma as of the steps queued so far; one read in flight per engine, shared by every StoreParameters of this
@@ -554,7 +560,7 @@ class StoreParameters(AriannaAlgorithm):
     def finalise(self, simulation: Simulation) -> None:
         self.flush()
         if self.store_last:
-            if getattr(self.metropolis, "device_params_dirty", False):
+            if self.metropolis.device_params_dirty:
                 self.metropolis.pull_parameters()
             self._write(simulation.t, [prm.copy() for prm in self.parameters_list])
         for f in self.files:

@@ -58,7 +58,7 @@ class StoreHistogram(AriannaAlgorithm):
         # The engine keeps ONE running histogram.  The first StoreHistogram of a Metropolis to sample owns it (its counts stay
         # on the device until finalise and its moments are read one sample late: nothing makes the host wait for the queued
         # sweeps); any other instance -- same bins or not -- fetches its counts at each sample time.
-        owner = getattr(self.metropolis, "_histogram_owner", None)
+        owner = self.metropolis._histogram_owner
         if owner is None and hasattr(eng, "histogram_accumulate"):
             owner = self.metropolis._histogram_owner = self
         on_device = owner is self
@@ -134,57 +134,190 @@ class StoreSnapshots(AriannaAlgorithm):
         io.write(f"\tStoreSnapshots\n\t\tCalls: {_calls(scheduler)}\n\t\tChains: every {self.stride}th ({self.count} on rank {self.rank})\n")
 
 
+# ---- checkpoint / restore: one pair of functions per group of state ------------------------------------------------------
+# _write_<group>(met, eng, d, est) puts the group's fields into the dict that becomes the file, _read_<group>(met, eng, d, est) puts
+# them back into the Metropolis and its engine.  A group has fields in the file only while its condition holds ("no field without
+# one"); its reader's condition is the presence of the field.  _SECTIONS lists the pairs in the order both walk them.
+def _write_core(met, eng, d, est) -> None:
+    x, _ = eng.download_state(want_e=False)
+    start, stop = met.shard
+    d.update(x=x, shard=np.array([start, stop]), n_chains_global=len(met.chains), seed=met.seed, sweepstep=met.sweepstep,
+             step=eng.step, estimator_step=eng.estimator_step, sigma=np.array([m.sigma for m in met.pool]),
+             weight=np.array([m.weight for m in met.pool]), param_dtype=met.param_dtype)
+    if met.chains.beta_array is not None:
+        d["beta"] = met.chains.beta_array[start:stop]
+
+def _read_core(met, eng, d, est) -> None:
+    if list(d["shard"]) != list(met.shard) or int(d["seed"]) != met.seed or int(d["n_chains_global"]) != len(met.chains):
+        raise ValueError("checkpoint does not match this Metropolis (shard / seed / ensemble size)")
+    saved_pd = str(d["param_dtype"]) if "param_dtype" in d else "f64"
+    if saved_pd != met.param_dtype:
+        raise ValueError(f"checkpoint was written with param_dtype {saved_pd!r}, this Metropolis has {met.param_dtype!r}: the two run "
+                         "different arithmetic (pass the moves' parameters in the checkpoint's type)")
+    eng.upload_state(d["x"], d["beta"] if "beta" in d else None)
+    for k, s in enumerate(d["sigma"]):
+        met.set_parameters(k, [float(s)])
+    eng.step = int(d["step"])
+    eng.estimator_step = int(d["estimator_step"])
+
+
+def _write_counters(met, eng, d, est) -> None:
+    acc_tot, tot_tot = eng.counter_totals()
+    d.update(accepted_total=acc_tot, total_total=tot_tot)
+    try:
+        acc, tot = eng.download_counters()
+        d.update(accepted=acc, total=tot)
+    except Exception:
+        pass                                        # pool-wide counter mode: the totals are the state
+
+def _read_counters(met, eng, d, est) -> None:
+    if "accepted" in d:
+        eng.upload_counters(d["accepted"], d["total"])
+    else:
+        eng.set_counter_totals(int(d["accepted_total"][0]), int(d["total_total"][0]) // (met.shard[1] - met.shard[0]))
+
+
+def _write_rung_sigma(met, eng, d, est) -> None:
+    if met.n_rungs and met.rung_sigma is not None:  # widths per rung: the table is state (no field without one)
+        if hasattr(eng, "rung_sigma"):              # ... as the device holds it: a tuned table is the tuned one
+            met.rung_sigma = np.array(eng.rung_sigma(), dtype=np.float64)
+        d["rung_sigma"] = np.asarray(met.rung_sigma, dtype=np.float64)
+
+def _read_rung_sigma(met, eng, d, est) -> None:
+    if "n_rungs" in d:                              # (a ladder without the field: no table)
+        tab = None
+        if "rung_sigma" in d:                       # widths per rung: checked like the constructor's against this pool and ladder
+            tab = _check_rung_sigma(d["rung_sigma"], met.pool, 1)
+            if tab.shape[1] != int(d["n_rungs"]):
+                raise ValueError(f"checkpoint holds rung_sigma of {tab.shape[1]} rungs per move for a ladder of R = {int(d['n_rungs'])}")
+        met.rung_sigma = tab                        # the checkpoint's table, or none, replaces the constructor's; _read_ladder hands it on
+
+
+def _write_ladder(met, eng, d, est) -> None:
+    if met.n_rungs:                                 # a temperature ladder: the exchange step index and the gap counters are state
+        acc_x, att_x = eng.exchange_counters()
+        d.update(n_rungs=met.n_rungs, exchange_step=eng.exchange_step, exchange_accepted=acc_x, exchange_attempted=att_x)
+
+def _read_ladder(met, eng, d, est) -> None:
+    if "n_rungs" in d:
+        met.set_ladder(int(d["n_rungs"]))
+        # set_ladder does nothing where the ladder is set already, so the table goes to the engine here: what the engine sweeps
+        # with is what the next checkpoint writes
+        if met.rung_sigma is not None or hasattr(eng, "set_rung_sigma"):
+            eng.set_rung_sigma(met.rung_sigma)
+        eng.exchange_step = int(d["exchange_step"])
+        eng.set_exchange_counters(d["exchange_accepted"], d["exchange_attempted"])
+
+
+def _write_tracking(met, eng, d, est) -> None:
+    if met.n_rungs and met.tracking:                # walker tracking is on: the labels and the trip counters are state too
+        walker, direction = eng.labels()
+        d.update(walker=walker, direction=direction, trips=np.array(eng.tracking_counters(), dtype=np.int64))
+
+def _read_tracking(met, eng, d, est) -> None:
+    if "walker" in d:
+        eng.set_tracking(True)                      # (labels start as the identity; the checkpoint's replace them)
+        eng.set_labels(d["walker"], d["direction"])
+        eng.set_tracking_counters(int(d["trips"][0]), int(d["trips"][1]))
+        met.tracking = True
+
+
+def _write_window(met, eng, d, est) -> None:
+    if met.n_rungs and met._rung_window_used:       # a tuning or a window restart has happened: the window's base and the count
+        base_acc, base_tot = eng.rung_window_base()     # of tunings are state (no field otherwise)
+        d.update(rung_window_accepted=base_acc, rung_window_total=base_tot)
+        if met.rung_sigma is not None:
+            d["n_tuned"] = eng.tune_status()[1]
+
+def _read_window(met, eng, d, est) -> None:
+    if "rung_window_accepted" in d:                 # the window of the acceptance per rung, and the count of tunings
+        eng.set_rung_window_base(d["rung_window_accepted"], d["rung_window_total"])
+        if "n_tuned" in d and met.rung_sigma is not None:
+            eng.set_tuned(int(d["n_tuned"]))
+        met._rung_window_used = True
+
+
+def _write_bridge(met, eng, d, est) -> None:
+    if met.n_rungs and met.bridge:                  # the bridge sums are on: the accumulator is state (no field otherwise)
+        rec, n_snap = eng.bridge_fetch(reset=False)
+        d.update(bridge_records=rec, bridge_columns=int(met.bridge), bridge_snapshots=n_snap)
+
+def _read_bridge(met, eng, d, est) -> None:
+    if "bridge_records" in d:                       # (read whenever it is there: the resumed run accumulates on to the same bits)
+        if met.bridge and int(d["bridge_columns"]) != int(met.bridge):
+            raise ValueError(f"checkpoint holds bridge sums of columns {int(d['bridge_columns'])}, this ReplicaExchange asks for "
+                             f"{int(met.bridge)}")
+        eng.set_bridge(d["bridge_records"], int(d["bridge_snapshots"]))
+
+
+def _write_respacing(met, eng, d, est) -> None:
+    n_respaced = eng.respace_status()[1] if met.n_rungs and hasattr(eng, "respace_status") else 0
+    if n_respaced:                                  # the ladder was respaced (ReplicaExchange.respace keeps beta_array current): no field otherwise
+        d["n_respaced"] = n_respaced
+
+def _read_respacing(met, eng, d, est) -> None:
+    if "n_respaced" in d:                           # a respaced ladder: the host copy follows the checkpoint's beta, as the engine did
+        eng.set_respaced(int(d["n_respaced"]))
+        met.chains.beta_array[met.shard[0]:met.shard[1]] = d["beta"]
+
+
+def _write_annealing(met, eng, d, est) -> None:
+    pa = met.annealing
+    if pa is not None:                              # population annealing: beta, the step index, the records and the families are state
+        d.update(anneal_beta=float(eng.beta), anneal_step=int(eng.anneal_step), anneal_records=pa.records())
+        eng.set_anneal_records(d["anneal_records"][-AMC_ANNEAL_MAX_RECORDS:])      # (records() drained the engine's log: the run goes on with it)
+        pa._records = list(d["anneal_records"][:-AMC_ANNEAL_MAX_RECORDS])
+        if pa.families:
+            d["families"] = eng.download_families()
+
+def _read_annealing(met, eng, d, est) -> None:
+    if "anneal_beta" in d:                          # population annealing: the resumed run anneals on to the same bits
+        rec = np.asarray(d["anneal_records"], dtype=np.uint64).reshape(-1, 8)
+        eng.beta = met.chains.beta = float(d["anneal_beta"])
+        eng.anneal_step = int(d["anneal_step"])
+        eng.set_anneal_records(rec[-AMC_ANNEAL_MAX_RECORDS:])
+        if met.annealing is not None:
+            met.annealing._records = list(rec[:-AMC_ANNEAL_MAX_RECORDS])
+        if "families" in d:
+            eng.set_anneal_families(True)
+            eng.upload_families(d["families"])
+            met.families_restored = True
+
+
+def _write_estimator(met, eng, d, est) -> None:
+    if est is not None:
+        d["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in est.gradients_data])
+
+def _read_estimator(met, eng, d, est) -> None:
+    if est is not None and "gd" in d:
+        from .policy_guided import GradientData
+        est.gradients_data = [GradientData(float(r[0]), np.array([r[1]]), np.array([r[2]]), np.array([[r[3]]]), int(r[4])) for r in d["gd"]]
+        if est.device_resident and est.learn_ids:
+            # the running sums live in the engine (amc_pg_accumulate adds to them there): without this the first update
+            # after the resume would average the post-resume samples only
+            if hasattr(eng, "pg_set_accumulated"):
+                eng.pg_set_accumulated(est.learn_ids, np.asarray(d["gd"], dtype=np.float64))
+            elif any(int(r[4]) != 0 for r in d["gd"]):
+                raise ValueError("restore: this engine cannot take over non-empty device-resident gradients_data")
+
+
+# The order is restore's, the engine calls depend on it: the table is checked before the ladder is set and goes to the engine behind it;
+# the ladder comes before everything kept per rung (labels, window, bridge records); the window's base before the count of tunings.
+_SECTIONS = ((_write_core, _read_core), (_write_counters, _read_counters), (_write_rung_sigma, _read_rung_sigma),
+             (_write_ladder, _read_ladder), (_write_tracking, _read_tracking), (_write_window, _read_window),
+             (_write_bridge, _read_bridge), (_write_respacing, _read_respacing), (_write_annealing, _read_annealing),
+             (_write_estimator, _read_estimator))
+
+
 def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
     """Write this rank's shard so that `restore` continues the run bit for bit."""
-    eng = metropolis.engine
-    if getattr(metropolis, "device_params_dirty", False):
+    if metropolis.device_params_dirty:
         metropolis.pull_parameters()
     if estimator is not None:
         estimator.refresh()
-    x, _ = eng.download_state(want_e=False)
-    start, stop = metropolis.shard
-    acc_tot, tot_tot = eng.counter_totals()
-    data = dict(x=x, shard=np.array([start, stop]), n_chains_global=len(metropolis.chains), seed=metropolis.seed,
-                sweepstep=metropolis.sweepstep, step=eng.step, estimator_step=eng.estimator_step,
-                sigma=np.array([m.sigma for m in metropolis.pool]), weight=np.array([m.weight for m in metropolis.pool]),
-                accepted_total=acc_tot, total_total=tot_tot, param_dtype=getattr(metropolis, "param_dtype", "f64"))
-    try:
-        acc, tot = eng.download_counters()
-        data.update(accepted=acc, total=tot)
-    except Exception:
-        pass                                       # pool-wide counter mode: totals above are the state
-    if metropolis.chains.beta_array is not None:
-        data["beta"] = metropolis.chains.beta_array[start:stop]
-    if getattr(metropolis, "n_rungs", 0):           # a temperature ladder: the exchange step index and the gap counters are state
-        acc_x, att_x = eng.exchange_counters()
-        data.update(n_rungs=metropolis.n_rungs, exchange_step=eng.exchange_step, exchange_accepted=acc_x, exchange_attempted=att_x)
-        if getattr(metropolis, "rung_sigma", None) is not None:     # widths per rung: the table is state (no field without one)
-            if hasattr(eng, "rung_sigma"):          # ... as the device holds it: a tuned table is the tuned one
-                metropolis.rung_sigma = np.array(eng.rung_sigma(), dtype=np.float64)
-            data["rung_sigma"] = np.asarray(metropolis.rung_sigma, dtype=np.float64)
-        if getattr(metropolis, "_rung_window_used", False):         # a tuning or a window restart has happened: the window's base and the
-            base_acc, base_tot = eng.rung_window_base()             # count of tunings are state (no field otherwise)
-            data.update(rung_window_accepted=base_acc, rung_window_total=base_tot)
-            if getattr(metropolis, "rung_sigma", None) is not None:
-                data["n_tuned"] = eng.tune_status()[1]
-        if getattr(metropolis, "tracking", False):  # walker tracking is on: the labels and the trip counters are state too
-            walker, direction = eng.labels()
-            data.update(walker=walker, direction=direction, trips=np.array(eng.tracking_counters(), dtype=np.int64))
-        if getattr(metropolis, "bridge", 0):        # the bridge sums are on: the accumulator is state (no field otherwise)
-            rec, n_snap = eng.bridge_fetch(reset=False)
-            data.update(bridge_records=rec, bridge_columns=int(metropolis.bridge), bridge_snapshots=n_snap)
-        n_respaced = eng.respace_status()[1] if hasattr(eng, "respace_status") else 0
-        if n_respaced:                              # the ladder was respaced (ReplicaExchange.respace keeps beta_array current): no field otherwise
-            data["n_respaced"] = n_respaced
-    pa = getattr(metropolis, "annealing", None)
-    if pa is not None:                              # population annealing: beta, the step index, the records and the families are state
-        data.update(anneal_beta=float(eng.beta), anneal_step=int(eng.anneal_step), anneal_records=pa.records())
-        eng.set_anneal_records(data["anneal_records"][-AMC_ANNEAL_MAX_RECORDS:])     # (records() drained the engine's log: the run goes on with it)
-        pa._records = list(data["anneal_records"][:-AMC_ANNEAL_MAX_RECORDS])
-        if pa.families:
-            data["families"] = eng.download_families()
-    if estimator is not None:
-        data["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in estimator.gradients_data])
+    data = {}
+    for write, _ in _SECTIONS:
+        write(metropolis, metropolis.engine, data, estimator)
     os.makedirs(path, exist_ok=True)
     fn = os.path.join(path, f"checkpoint_rank{metropolis.rank}.npz")
     np.savez(fn, **data)
@@ -194,82 +327,8 @@ def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
 def restore(metropolis: Metropolis, path: str, estimator=None) -> None:
     """Load `checkpoint`'s file into a freshly constructed Metropolis with the same pool/seed/sharding."""
     d = np.load(os.path.join(path, f"checkpoint_rank{metropolis.rank}.npz"))
-    start, stop = metropolis.shard
-    if list(d["shard"]) != [start, stop] or int(d["seed"]) != metropolis.seed or int(d["n_chains_global"]) != len(metropolis.chains):
-        raise ValueError("checkpoint does not match this Metropolis (shard / seed / ensemble size)")
-    saved_pd = str(d["param_dtype"]) if "param_dtype" in d else "f64"
-    if saved_pd != getattr(metropolis, "param_dtype", "f64"):
-        raise ValueError(f"checkpoint was written with param_dtype {saved_pd!r}, this Metropolis has "
-                         f"{getattr(metropolis, 'param_dtype', 'f64')!r}: the two run different arithmetic (pass the moves' "
-                         "parameters in the checkpoint's type)")
-    eng = metropolis.engine
-    eng.upload_state(d["x"], d["beta"] if "beta" in d else None)
-    for k, s in enumerate(d["sigma"]):
-        metropolis.set_parameters(k, [float(s)])
-    eng.step = int(d["step"])
-    eng.estimator_step = int(d["estimator_step"])
-    if "accepted" in d:
-        eng.upload_counters(d["accepted"], d["total"])
-    else:
-        eng.set_counter_totals(int(d["accepted_total"][0]), int(d["total_total"][0]) // (stop - start))
-    if "n_rungs" in d:
-        R = int(d["n_rungs"])
-        tab = None
-        if "rung_sigma" in d:                       # widths per rung: checked like the constructor's against this pool and ladder
-            tab = _check_rung_sigma(d["rung_sigma"], metropolis.pool, 1)
-            if tab.shape[1] != R:
-                raise ValueError(f"checkpoint holds rung_sigma of {tab.shape[1]} rungs per move for a ladder of R = {R}")
-        metropolis.rung_sigma = tab                 # the checkpoint's table, or none, replaces the constructor's
-        metropolis.set_ladder(R)
-        # set_ladder does nothing where the ladder is set already, so the table goes to the engine here: what the engine sweeps
-        # with is what the next checkpoint writes
-        if tab is not None or hasattr(eng, "set_rung_sigma"):
-            eng.set_rung_sigma(tab)
-        eng.exchange_step = int(d["exchange_step"])
-        eng.set_exchange_counters(d["exchange_accepted"], d["exchange_attempted"])
-        if "walker" in d:
-            eng.set_tracking(True)
-            eng.set_labels(d["walker"], d["direction"])
-            eng.set_tracking_counters(int(d["trips"][0]), int(d["trips"][1]))
-            metropolis.tracking = True
-        if "rung_window_accepted" in d:             # the window of the acceptance per rung, and the count of tunings
-            eng.set_rung_window_base(d["rung_window_accepted"], d["rung_window_total"])
-            if "n_tuned" in d and tab is not None:
-                eng.set_tuned(int(d["n_tuned"]))
-            metropolis._rung_window_used = True
-        if "bridge_records" in d:                   # the accumulator of the bridge sums: the resumed run accumulates on to the same bits
-            if getattr(metropolis, "bridge", 0) and int(d["bridge_columns"]) != int(metropolis.bridge):
-                raise ValueError(f"checkpoint holds bridge sums of columns {int(d['bridge_columns'])}, this ReplicaExchange asks for "
-                                 f"{int(metropolis.bridge)}")
-            eng.set_bridge(d["bridge_records"], int(d["bridge_snapshots"]))
-        if "n_respaced" in d:                       # a respaced ladder: the host copy follows the checkpoint's beta, as the engine did
-            eng.set_respaced(int(d["n_respaced"]))
-            metropolis.chains.beta_array[start:stop] = d["beta"]
-    if "anneal_beta" in d:                          # population annealing: the resumed run anneals on to the same bits
-        rec = np.asarray(d["anneal_records"], dtype=np.uint64).reshape(-1, 8)
-        eng.beta = float(d["anneal_beta"])
-        metropolis.chains.beta = float(d["anneal_beta"])
-        eng.anneal_step = int(d["anneal_step"])
-        eng.set_anneal_records(rec[-AMC_ANNEAL_MAX_RECORDS:])
-        pa = getattr(metropolis, "annealing", None)
-        if pa is not None:
-            pa._records = list(rec[:-AMC_ANNEAL_MAX_RECORDS])
-        if "families" in d:
-            eng.set_anneal_families(True)
-            eng.upload_families(d["families"])
-            metropolis.families_restored = True
-    if estimator is not None and "gd" in d:
-        from .policy_guided import GradientData
-        estimator.gradients_data = [GradientData(float(r[0]), np.array([r[1]]), np.array([r[2]]), np.array([[r[3]]]), int(r[4]))
-                                    for r in d["gd"]]
-        if estimator.device_resident and estimator.learn_ids:
-            # the running sums live in the engine (amc_pg_accumulate adds to them there): without this the first update
-            # after the resume would average the post-resume samples only
-            if not hasattr(eng, "pg_set_accumulated"):
-                if any(int(r[4]) != 0 for r in d["gd"]):
-                    raise ValueError("restore: this engine cannot take over non-empty device-resident gradients_data")
-            else:
-                eng.pg_set_accumulated(estimator.learn_ids, np.asarray(d["gd"], dtype=np.float64))
+    for _, read in _SECTIONS:
+        read(metropolis, metropolis.engine, d, estimator)
     metropolis.chains.x = None                      # initialise() must not overwrite the restored state
     metropolis.restored = True
     metropolis.invalidate_reductions()
