@@ -11,7 +11,12 @@ The run is repeated for --runs independent seeds; the figure printed is their me
 deviation is 8 standard errors of that mean (the spread of the runs themselves; Student's t with 7 degrees of freedom leaves less
 than 1e-4 outside 8 standard errors, and the bias of one run, of the order of its variance, is far below that).
 
-    python examples/pa_double_well.py [--chains 65536] [--stages 24] [--sweeps 10] [--runs 8] [--path data/PA/...]
+With --adaptive TARGET the list of beta values is not given: at each scheduled time the engine chooses the next beta itself, the
+largest step towards beta = 8 whose reweighting keeps the effective-sample fraction ESS / M at or above TARGET
+(PopulationAnnealing(adaptive=...), amc_anneal_next_beta), for at most --stages steps.  Every run then has its own list, so the script
+prints log(Z(8) / Z(0.5)) of the runs beside the quadrature, and the steps the last run chose.
+
+    python examples/pa_double_well.py [--chains 65536] [--stages 24] [--sweeps 10] [--runs 8] [--path data/PA/...] [--adaptive TARGET]
 """
 import argparse
 import os
@@ -40,13 +45,39 @@ def one_run(args, path, seed):
     pool = (ma.Move(ma.Displacement(0.0), ma.StandardGaussian(), [SIGMA], 1.0),)
     # BURN sweeps at the hot end, then [anneal; sweeps] per stage: the annealing step is due at BURN, BURN + sweeps, ...
     when = [BURN + i * args.sweeps for i in range(args.stages)]
+    schedule = dict(betas=list(betas[1:])) if args.adaptive is None else dict(adaptive=dict(beta_end=BETA_COLD, target=args.adaptive))
     algorithm_list = [dict(algorithm=ma.Metropolis, pool=pool, seed=seed),
-                      dict(algorithm=ma.PopulationAnnealing, dependencies=(ma.Metropolis,), scheduler=when, betas=list(betas[1:]), families=True),
+                      dict(algorithm=ma.PopulationAnnealing, dependencies=(ma.Metropolis,), scheduler=when, families=True, **schedule),
                       dict(algorithm=ma.StoreCallbacks, callbacks=(ma.callback_energy, ma.callback_anneal_beta, ma.callback_anneal_log_z, ma.callback_rho_t),
                            scheduler=when)]
     simulation = ma.Simulation(chains, algorithm_list, steps, path=path)
     ma.run(simulation)
     return simulation, betas
+
+
+def adaptive_main(args, path):
+    """--adaptive: the runs choose their own steps; log(Z(8) / Z(0.5)) of each beside the quadrature, and the last run's steps."""
+    ends, pa = [], None
+    for r in range(args.runs):
+        sim, _ = one_run(args, os.path.join(path, f"run{r}"), args.seed + r)
+        pa = sim.algorithms[1]
+        if not pa.finished:
+            raise SystemExit(f"run {r}: beta = {pa.beta} after {args.stages} steps; raise --stages or lower --adaptive")
+        ends.append(pa.log_z()[-1])
+    ends = np.array(ends)
+    done = pa.betas_done()
+    q = log_z_by_quadrature(np.concatenate([[BETA_HOT], done]))
+    exact = q[1:] - q[0]
+    tol = 8.0 * ends.std(ddof=1) / np.sqrt(args.runs) if args.runs > 1 else float("nan")
+    print(f"{args.runs} runs of {args.chains} chains, steps chosen for ESS / M >= {args.adaptive}, {args.sweeps} sweeps behind each")
+    print(f"log Z(8) / Z(0.5): mean {ends.mean():.6f}, quadrature {exact[-1]:.6f}, difference {ends.mean() - exact[-1]:+.6f}, tolerance {tol:.6f}")
+    print(f"last run, {len(done)} steps:\n   beta   log Z(beta)/Z(0.5)   quadrature   survival   ESS / M kept   search")
+    log, lz, survival = pa.search_log(), pa.log_z(), pa.survival()
+    for i in range(len(done)):
+        kept = float(np.array([log[i, 3]], dtype=np.uint64).view(np.float64)[0])
+        print(f"{done[i]:7.4f}   {lz[i]:12.6f}   {exact[i]:12.6f}   {survival[i]:7.4f}   {kept:8.4f}   {ma.ANNEAL_SEARCH_STATUS[int(log[i, 0])]}")
+    print(f"last run: rho_t = {pa.rho_t():.2f} of {args.chains} chains")
+    return ends, exact[-1], tol, done
 
 
 def main(argv=None):
@@ -57,8 +88,12 @@ def main(argv=None):
     ap.add_argument("--runs", type=int, default=8, help="independent runs (seeds); their spread is the tolerance")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--path", default=None)
+    ap.add_argument("--adaptive", type=float, default=None, metavar="TARGET",
+                    help="choose every step on the device: the largest one that keeps ESS / M >= TARGET (--stages is then the most steps a run may take)")
     args = ap.parse_args(argv)
     path = args.path or f"data/PA/particle_1d/DoubleWell/M{args.chains}/seed{args.seed}"
+    if args.adaptive is not None:
+        return adaptive_main(args, path)
     log_z, survival, rho, left = [], None, None, None
     for r in range(args.runs):
         sim, betas = one_run(args, os.path.join(path, f"run{r}"), args.seed + r)

@@ -542,6 +542,39 @@ int  amc_get_anneal_step(amc_handle *h, uint64_t *t);
 int  amc_set_anneal_step(amc_handle *h, uint64_t t);
 int  amc_get_beta(amc_handle *h, double *beta);
 int  amc_set_beta(amc_handle *h, double beta);
+/* Choosing the next beta (DESIGN.md section 3.14 "Choosing the next beta", which holds the rule operation by operation):
+ * amc_anneal_next_beta finds on the device the largest step from the shared beta towards beta_limit whose reweighting keeps the
+ * effective-sample fraction rho = (sum W)^2 / (M sum W^2) at or above `target` (strictly between 0 and 1), by `rounds` (1 .. 16) rounds
+ * of AMC_ANNEAL_SEARCH_CANDIDATES candidates over a bracket that starts at [0, T(beta_limit) - T(beta)]: the span is resolved to
+ * 8^-rounds of itself.  The weights are those of amc_anneal (the products in the state's type, the same integer W), the sums exact
+ * integers: the answer is the same on any grid and bit-exact against a host twin.  *beta_new is what to hand to amc_anneal; it never
+ * passes beta_limit and is beta_limit bit for bit when the whole span passes.  The entry changes neither beta nor the positions; it
+ * queues 2 rounds + 1 launches behind what is queued and then SYNCHRONISES once to read the answer: beta is a host field that goes into
+ * the launch arguments of the sweeps, so the host has to know it.  A pending learning step is taken first.  The energies reuse the
+ * word per chain of amc_anneal; a scratch of a few KB is allocated at the first call.
+ * diag (optional): AMC_ANNEAL_SEARCH_WORDS words: status, rounds decided, bits of the step chosen, rho at the bracket's low end (1 for
+ * a step of 0), bits of the bracket's high end, rho there, bits of the largest and of the smallest -e.  trace (optional):
+ * rounds * AMC_ANNEAL_SEARCH_CANDIDATES * 3 words, every candidate's S1 = sum W, S2h = sum (W^2 >> 30), S2l = sum (W^2 & (2^30 - 1)); rounds
+ * that were not run read 0.
+ * Status AMC_ANNEAL_SEARCH_OK: a step inside the span.  _LIMIT: every candidate passed (or the span is 0, then nothing is launched
+ * and diag reads 0 behind the status): *beta_new = beta_limit.  _BELOW_RESOLUTION: every candidate of every round failed, the step is
+ * the smallest one resolved, so that a run always advances.  _STALLED: T(beta) + T(step) == T(beta); *beta_new = beta.  _ALL_NAN,
+ * _INF, _NO_WEIGHT: no usable weights (every energy a NaN; the largest log-weight of the whole span +Inf; -Inf): *beta_new =
+ * beta_limit, and the amc_anneal that follows records its own status and leaves x alone.
+ * AMC_ERR_STATE, as amc_anneal: a per-chain beta array, a ladder, a handle that does not hold the whole ensemble.  AMC_ERR_BAD_ARG: a
+ * NULL handle or beta_new, beta_limit not finite (or a span that is not finite in the state's type), target outside (0, 1), rounds
+ * outside [1, 16], n_chains >= 2^33.  A refused call leaves the handle as it was. */
+#define AMC_ANNEAL_SEARCH_CANDIDATES 8
+#define AMC_ANNEAL_SEARCH_WORDS 8
+#define AMC_ANNEAL_SEARCH_MAX_ROUNDS 16
+#define AMC_ANNEAL_SEARCH_OK 0
+#define AMC_ANNEAL_SEARCH_LIMIT 1
+#define AMC_ANNEAL_SEARCH_BELOW_RESOLUTION 2
+#define AMC_ANNEAL_SEARCH_STALLED 3
+#define AMC_ANNEAL_SEARCH_ALL_NAN 4
+#define AMC_ANNEAL_SEARCH_INF 5
+#define AMC_ANNEAL_SEARCH_NO_WEIGHT 6
+int  amc_anneal_next_beta(amc_handle *h, double beta_limit, double target, int rounds, double *beta_new, uint64_t *diag, uint64_t *trace);
 /* Families, population annealing's own diagnostic: amc_set_anneal_families(h, 1) gives every chain a 32-bit family id, fam[c] = c
  * (n_chains <= 2^32 - 1; calling it again starts the families afresh), and every annealing step from then on gathers the ids along
  * with the positions; (h, 0) frees them.  amc_anneal_family_stats synchronises and returns exact integers: the families that have a

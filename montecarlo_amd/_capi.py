@@ -24,6 +24,12 @@ AMC_XSUM_WORDS = 12      # doubles per record of a reproducible sum (include/amc
 AMC_ANNEAL_RECORD_WORDS = 8     # 64-bit words per record of an annealing step
 AMC_ANNEAL_MAX_RECORDS = 4096
 AMC_ANNEAL_WEIGHT_BITS = 30
+AMC_ANNEAL_SEARCH_CANDIDATES = 8    # candidates per round of amc_anneal_next_beta
+AMC_ANNEAL_SEARCH_WORDS = 8         # 64-bit words of its diag
+AMC_ANNEAL_SEARCH_MAX_ROUNDS = 16
+# status of a search (diag[0])
+(AMC_ANNEAL_SEARCH_OK, AMC_ANNEAL_SEARCH_LIMIT, AMC_ANNEAL_SEARCH_BELOW_RESOLUTION, AMC_ANNEAL_SEARCH_STALLED, AMC_ANNEAL_SEARCH_ALL_NAN,
+ AMC_ANNEAL_SEARCH_INF, AMC_ANNEAL_SEARCH_NO_WEIGHT) = range(7)
 AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_REDUCE_ALL = 1, 2, 4, 7      # the sums over x a reduction forms (include/amc.h)
 # the columns of the bridge sums (include/amc.h); record order E, EE, WF, WB, MF, MB
 AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_WF, AMC_BRIDGE_WB, AMC_BRIDGE_MF, AMC_BRIDGE_MB, AMC_BRIDGE_ALL = 1, 2, 4, 8, 16, 32, 63
@@ -199,6 +205,7 @@ def load() -> C.CDLL:
         "amc_set_anneal_step": (C.c_int, [H, C.c_uint64]),
         "amc_get_beta": (C.c_int, [H, dp]),
         "amc_set_beta": (C.c_int, [H, C.c_double]),
+        "amc_anneal_next_beta": (C.c_int, [H, C.c_double, C.c_double, C.c_int, dp, u64p, u64p]),
         "amc_set_anneal_families": (C.c_int, [H, C.c_int]),
         "amc_anneal_family_stats": (C.c_int, [H, u64p, u64p, u64p]),
         "amc_download_families": (C.c_int, [H, C.POINTER(C.c_uint32)]),
@@ -698,6 +705,19 @@ class HipEngine:
     @beta.setter
     def beta(self, b: float) -> None:
         _check(self._lib.amc_set_beta(self._h, float(b)))
+
+    def anneal_next_beta(self, beta_limit: float, target: float, rounds: int = 6):
+        """(beta_new, diag, trace): the largest step from the shared beta towards ``beta_limit`` whose reweighting keeps ESS / M at or
+        above ``target``, searched on the device in ``rounds`` rounds of 8 candidates (rounds = 6 resolves 8^-6 of the span);
+        synchronises once.  Nothing moves: hand ``beta_new`` to anneal().  diag: 8 uint64 words (status, rounds decided, bits of the
+        step, rho at the low end, bits of the high end, rho there, bits of the largest / smallest -e); trace: (rounds, 8, 3) uint64, every
+        candidate's S1, S2h, S2l."""
+        b = C.c_double(0.0)
+        diag = np.zeros(AMC_ANNEAL_SEARCH_WORDS, dtype=np.uint64)
+        trace = np.zeros((max(int(rounds), 0), AMC_ANNEAL_SEARCH_CANDIDATES, 3), dtype=np.uint64)
+        _check(self._lib.amc_anneal_next_beta(self._h, float(beta_limit), float(target), int(rounds), C.byref(b), _ptr(diag),
+                                              _ptr(trace) if trace.size else None))
+        return b.value, diag, trace
 
     def set_anneal_families(self, on: bool = True) -> None:
         _check(self._lib.amc_set_anneal_families(self._h, 1 if on else 0))

@@ -19,7 +19,8 @@ import struct
 import numpy as np
 
 from . import sharding
-from ._capi import AMC_ANNEAL_MAX_RECORDS, AMC_ANNEAL_RECORD_WORDS, AMC_ANNEAL_WEIGHT_BITS
+from ._capi import (AMC_ANNEAL_MAX_RECORDS, AMC_ANNEAL_RECORD_WORDS, AMC_ANNEAL_SEARCH_MAX_ROUNDS, AMC_ANNEAL_SEARCH_STALLED,
+                    AMC_ANNEAL_SEARCH_WORDS, AMC_ANNEAL_WEIGHT_BITS)
 from .metropolis import Metropolis
 from .simulation import AriannaAlgorithm, Simulation, _calls
 
@@ -28,19 +29,54 @@ def _f64(bits) -> float:
     return struct.unpack("<d", struct.pack("<Q", int(bits)))[0]
 
 
+# the status word of a search (search_log()[:, 0]; include/amc.h AMC_ANNEAL_SEARCH_*), by value
+ANNEAL_SEARCH_STATUS = ("OK", "LIMIT", "BELOW_RESOLUTION", "STALLED", "ALL_NAN", "INF", "NO_WEIGHT")
+
+
+def _adaptive_plan(adaptive) -> dict:
+    """adaptive=dict(beta_end=..., target=..., rounds=6), checked: what PopulationAnnealing hands to anneal_next_beta."""
+    try:
+        plan = dict(adaptive)
+    except (TypeError, ValueError):
+        raise ValueError(f"PopulationAnnealing: adaptive = {adaptive!r} is not a dict(beta_end=..., target=..., rounds=6)") from None
+    unknown = sorted(set(plan) - {"beta_end", "target", "rounds"})
+    if unknown:
+        raise ValueError(f"PopulationAnnealing: adaptive has unknown keys {unknown} (beta_end, target, rounds)")
+    for key in ("beta_end", "target"):
+        if key not in plan:
+            raise ValueError(f"PopulationAnnealing: adaptive[{key!r}] is missing (it has no default)")
+    beta_end, target, rounds = float(plan["beta_end"]), float(plan["target"]), plan.get("rounds", 6)
+    if not math.isfinite(beta_end):
+        raise ValueError(f"PopulationAnnealing: adaptive['beta_end'] = {beta_end!r} is not finite")
+    if not 0.0 < target < 1.0:
+        raise ValueError(f"PopulationAnnealing: adaptive['target'] = {target!r} must lie strictly between 0 and 1 (the effective-sample "
+                         "fraction a step keeps)")
+    if int(rounds) != rounds or not 1 <= int(rounds) <= AMC_ANNEAL_SEARCH_MAX_ROUNDS:
+        raise ValueError(f"PopulationAnnealing: adaptive['rounds'] = {rounds!r} must be an integer in [1, {AMC_ANNEAL_SEARCH_MAX_ROUNDS}]")
+    return dict(beta_end=beta_end, target=target, rounds=int(rounds))
+
+
 class PopulationAnnealing(AriannaAlgorithm):
     """PopulationAnnealing(chains; dependencies=(Metropolis,), betas=[...], families=False): one annealing step of the Metropolis'
     engine per scheduled time, to the next beta of ``betas``.  Listed behind its Metropolis, a time step at which both are due is
-    [sweep; anneal].  It is an error when the list runs out."""
+    [sweep; anneal].  It is an error when the list runs out.
+
+    PopulationAnnealing(..., adaptive=dict(beta_end=..., target=..., rounds=6)) instead of ``betas``: each scheduled call is
+    [next_beta; anneal] -- the engine finds the largest step towards ``beta_end`` whose reweighting keeps the effective-sample fraction
+    ESS / M at or above ``target`` (DESIGN.md section 3.14 "Choosing the next beta") and anneals to it.  The number of steps is not
+    known in advance: once beta == beta_end, scheduled calls launch nothing and append no record (``finished``)."""
 
     mutates_chains = True          # a callback due behind it at the same t observes the state AFTER the resampling
 
-    def __init__(self, chains, dependencies=None, betas=None, families=False, path=None, **extras):
+    def __init__(self, chains, dependencies=None, betas=None, adaptive=None, families=False, path=None, **extras):
         assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
         self.metropolis: Metropolis = dependencies[0]
-        if betas is None or len(betas) == 0:
+        if adaptive is not None and betas is not None:
+            raise ValueError("PopulationAnnealing: both betas and adaptive are given; a run walks a list or chooses its steps, not both")
+        self.adaptive = None if adaptive is None else _adaptive_plan(adaptive)
+        if self.adaptive is None and (betas is None or len(betas) == 0):
             raise ValueError("PopulationAnnealing: betas is missing (the list of beta values to anneal to, one per scheduled call)")
-        self.betas = [float(b) for b in betas]
+        self.betas = [] if betas is None else [float(b) for b in betas]
         for i, b in enumerate(self.betas):
             if not math.isfinite(b):
                 raise ValueError(f"PopulationAnnealing: betas[{i}] = {b!r} is not finite")
@@ -52,9 +88,12 @@ class PopulationAnnealing(AriannaAlgorithm):
                              "device (populations that span GPUs are not supported)")
         if not hasattr(self.metropolis.engine, "anneal"):
             raise ValueError("PopulationAnnealing: this engine has no annealing step (streams > 1 is not supported)")
+        if self.adaptive is not None and not hasattr(self.metropolis.engine, "anneal_next_beta"):
+            raise ValueError("PopulationAnnealing: this engine cannot choose the next beta (adaptive needs amc_anneal_next_beta)")
         self.families = bool(families)
         self.chains = chains
         self._records = []                     # records drained from the engine's log, oldest first
+        self._search_log = []                  # adaptive: the diag of every search of this process, oldest first
         self.metropolis.annealing = self       # (storage.checkpoint: beta, the step index, the records and the families are state)
         self.rank, _ = sharding.world()
 
@@ -69,13 +108,38 @@ class PopulationAnnealing(AriannaAlgorithm):
     def make_step(self, simulation: Simulation) -> None:
         eng = self.metropolis.engine
         i = eng.anneal_step
-        if i >= len(self.betas):
-            raise ValueError(f"PopulationAnnealing: annealing step {i + 1} is due and betas holds {len(self.betas)} values")
+        if self.adaptive is None:
+            if i >= len(self.betas):
+                raise ValueError(f"PopulationAnnealing: annealing step {i + 1} is due and betas holds {len(self.betas)} values")
+            beta_new = self.betas[i]
+        else:
+            if self.finished:                   # at beta_end: nothing is launched, no record is appended
+                return
+            plan = self.adaptive
+            beta_new, diag, _ = eng.anneal_next_beta(plan["beta_end"], plan["target"], plan["rounds"])
+            if int(diag[0]) == AMC_ANNEAL_SEARCH_STALLED:
+                raise ValueError(f"PopulationAnnealing: the search stalled at beta = {eng.beta!r}: the smallest step it resolves towards "
+                                 f"beta_end = {plan['beta_end']!r} does not change beta in the state's type (more rounds, or a beta_end "
+                                 "closer by)")
+            self._search_log.append(np.array(diag, dtype=np.uint64))
         if i - len(self._records) >= AMC_ANNEAL_MAX_RECORDS:
             self._drain()
-        eng.anneal(self.betas[i])
-        self.chains.beta = self.betas[i]
+        eng.anneal(beta_new)
+        self.chains.beta = beta_new
         self.metropolis.invalidate_reductions()
+
+    @property
+    def finished(self) -> bool:
+        """No annealing step is left: beta has reached beta_end (adaptive), or the list has been walked."""
+        if self.adaptive is not None:
+            return float(self.metropolis.engine.beta) == self.adaptive["beta_end"]
+        return self.metropolis.engine.anneal_step >= len(self.betas)
+
+    def search_log(self) -> np.ndarray:
+        """adaptive: one row of 8 unsigned 64-bit words per search of this process (a resumed run starts an empty log): status, rounds
+        decided, bits of the step chosen, rho at the bracket's low end, bits of its high end, rho there, bits of the largest and of the
+        smallest -e."""
+        return np.array(self._search_log, dtype=np.uint64).reshape(-1, AMC_ANNEAL_SEARCH_WORDS)
 
     def _drain(self) -> None:
         rec = np.asarray(self.metropolis.engine.anneal_records(reset=True), dtype=np.uint64).reshape(-1, AMC_ANNEAL_RECORD_WORDS)
@@ -123,8 +187,12 @@ class PopulationAnnealing(AriannaAlgorithm):
         return self.family_stats()[1] / float(len(self.chains))
 
     def write_algorithm(self, io, scheduler) -> None:
-        io.write(f"\tPopulationAnnealing\n\t\tCalls: {_calls(scheduler)}\n\t\tBetas: {len(self.betas)} from {self.betas[0]} to {self.betas[-1]}\n"
-                 f"\t\tFamilies: {str(self.families).lower()}\n")
+        if self.adaptive is None:
+            betas = f"\t\tBetas: {len(self.betas)} from {self.betas[0]} to {self.betas[-1]}\n"
+        else:
+            betas = (f"\t\tBetas: adaptive, ESS / M >= {self.adaptive['target']} per step, to {self.adaptive['beta_end']} "
+                     f"({self.adaptive['rounds']} rounds)\n")
+        io.write(f"\tPopulationAnnealing\n\t\tCalls: {_calls(scheduler)}\n{betas}\t\tFamilies: {str(self.families).lower()}\n")
 
 
 def _find_annealing(simulation: Simulation) -> PopulationAnnealing:

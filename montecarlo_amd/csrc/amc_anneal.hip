@@ -1,10 +1,15 @@
 // amc_anneal.hip -- population annealing: the annealing step (amc_anneal), its record log (amc_anneal_fetch,
-// amc_set_anneal_records), the annealing step index, the shared beta (amc_get_beta, amc_set_beta) and the families (amc_set_anneal_families ..
-// amc_upload_families).  Everything here is allocated at its first use: a handle that never anneals has none of it.
+// amc_set_anneal_records), the annealing step index, the shared beta (amc_get_beta, amc_set_beta), the choice of the next beta
+// (amc_anneal_next_beta) and the families (amc_set_anneal_families .. amc_upload_families).  Everything here is allocated at its first use: a handle that never anneals has none of it.
 #define AMC_KERNEL_LINKAGE static      // the template instantiations, and this object's own copies of the plain kernels it launches
 #include "amc_internal.h"
 
 static_assert(AMC_ANNEAL_RECORD_WORDS == amc::ANNEAL_R_WORDS, "the record of include/amc.h and amc_anneal.h");
+static_assert(AMC_ANNEAL_SEARCH_MAX_ROUNDS == amc::SEARCH_MAX_ROUNDS && AMC_ANNEAL_SEARCH_OK == amc::SEARCH_OK && AMC_ANNEAL_SEARCH_LIMIT == amc::SEARCH_LIMIT &&
+                  AMC_ANNEAL_SEARCH_BELOW_RESOLUTION == amc::SEARCH_BELOW_RESOLUTION && AMC_ANNEAL_SEARCH_STALLED == amc::SEARCH_STALLED &&
+                  AMC_ANNEAL_SEARCH_ALL_NAN == amc::SEARCH_ALL_NAN && AMC_ANNEAL_SEARCH_INF == amc::SEARCH_INF &&
+                  AMC_ANNEAL_SEARCH_NO_WEIGHT == amc::SEARCH_NO_WEIGHT,
+              "the search of include/amc.h and amc_anneal_search.h");
 
 static const size_t ANNEAL_LOG_BYTES = (size_t)AMC_ANNEAL_MAX_RECORDS * amc::ANNEAL_R_WORDS * sizeof(unsigned long long);
 
@@ -99,6 +104,82 @@ int amc_anneal(amc_handle* h, double beta_new)
     h->beta = beta_new;          // the host field: in force for every launch queued from now on (nothing on the device is derived from it)
     h->ann.t_a += 1;
     h->ann.anneal_n += 1;
+    return AMC_OK;
+}
+
+// Choosing the next beta (DESIGN.md section 3.14 "Choosing the next beta"; the kernels are amc_anneal_search.h's).
+int amc_anneal_next_beta(amc_handle* h, double beta_limit, double target, int rounds, double* beta_new, uint64_t* diag, uint64_t* trace)
+{
+    if (!h || !beta_new) return fail(AMC_ERR_BAD_ARG, "amc_anneal_next_beta: NULL argument");
+    if (h->beta_arr)
+        return fail(AMC_ERR_STATE, "amc_anneal_next_beta: the handle has a per-chain beta array; population annealing cools one shared beta");
+    if (h->lad.n_rungs) return fail(AMC_ERR_STATE, "amc_anneal_next_beta: the handle has a ladder (amc_set_ladder)");
+    if (h->offset != 0 || h->M != h->M_global)
+        return fail(AMC_ERR_STATE, "amc_anneal_next_beta: the handle holds chains [%lld, %lld) of %lld; the weights need the whole ensemble on one handle",
+                    (long long)h->offset, (long long)(h->offset + h->M), (long long)h->M_global);
+    if (!std::isfinite(beta_limit)) return fail(AMC_ERR_BAD_ARG, "amc_anneal_next_beta: beta_limit = %g is not finite", beta_limit);
+    if (!(target > 0.0 && target < 1.0)) return fail(AMC_ERR_BAD_ARG, "amc_anneal_next_beta: target = %g must lie strictly between 0 and 1", target);
+    if (rounds < 1 || rounds > AMC_ANNEAL_SEARCH_MAX_ROUNDS)
+        return fail(AMC_ERR_BAD_ARG, "amc_anneal_next_beta: rounds = %d must lie in [1, %d]", rounds, AMC_ANNEAL_SEARCH_MAX_ROUNDS);
+    if (h->M >> 33) return fail(AMC_ERR_BAD_ARG, "amc_anneal_next_beta: n_chains = %lld, the sums need n_chains < 2^33", (long long)h->M);
+    const double span = h->f32 ? (double)((float)beta_limit - (float)h->beta) : beta_limit - h->beta;
+    if (!std::isfinite(span)) return fail(AMC_ERR_BAD_ARG, "amc_anneal_next_beta: the span from beta = %g to beta_limit = %g is not finite", h->beta, beta_limit);
+    const size_t n_trace = (size_t)rounds * amc::SEARCH_SUMS;
+    if (span == 0.0) {                                         // nothing to search and nothing launched
+        *beta_new = beta_limit;
+        if (diag) {
+            std::memset(diag, 0, AMC_ANNEAL_SEARCH_WORDS * sizeof(uint64_t));
+            diag[0] = AMC_ANNEAL_SEARCH_LIMIT;
+        }
+        if (trace) std::memset(trace, 0, n_trace * sizeof(uint64_t));
+        return AMC_OK;
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_TRY(pg_resolve(h));                                    // (as amc_anneal: a learning step left pending is taken now)
+    if (!h->ann.d_anneal_n) AMC_HIP(hipMalloc(&h->ann.d_anneal_n, (size_t)h->M * sizeof(unsigned long long)));
+    if (!h->ann.d_anneal_search) AMC_HIP(hipMalloc(&h->ann.d_anneal_search, amc::SEARCH_S_WORDS * sizeof(unsigned long long)));
+    unsigned long long* s = h->ann.d_anneal_search;
+    AMC_HIP(hipMemsetAsync(s, 0, amc::SEARCH_S_WORDS * sizeof(unsigned long long), h->stream));      // the keys, the bracket, every round's sums
+    const int grid = grid_for(h, h->M);
+    {
+        amc::AnnealEnergyArgs a;
+        a.x = h->d_x;
+        a.ne = h->ann.d_anneal_n;
+        a.scratch = s;
+        a.n_chains = h->M;
+        a.span = span;
+        void* params[] = {&a};
+        AMC_TRY(launch_by_potential(h, "amc::anneal_energy_kernel", (const void*)amc::anneal_energy_kernel<amc::POT_DOUBLE_WELL>,
+                                    (const void*)amc::anneal_energy_kernel<amc::POT_HARMONIC>, grid, params));
+    }
+    amc::AnnealDecideArgs d;
+    d.scratch = s;
+    d.n_chains = h->M;
+    d.rounds = rounds;
+    d.f32 = h->f32 ? 1 : 0;
+    d.span = span;
+    d.beta = h->beta;
+    d.beta_limit = beta_limit;
+    d.target = target;
+    for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(amc::anneal_search_sums_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, (const unsigned long long*)h->ann.d_anneal_n, h->M,
+                           d.f32, r, s);
+        AMC_HIP(hipGetLastError());
+        d.round = r;
+        hipLaunchKernelGGL(amc::anneal_search_decide_kernel, dim3(1), dim3(64), 0, h->stream, d);
+        AMC_HIP(hipGetLastError());
+    }
+    // the one synchronisation: beta is a host field (it goes into the sweeps' launch arguments), so the host must know the answer
+    unsigned long long host[amc::SEARCH_S_WORDS];
+    AMC_TRY(copy_to_host_sync(h, host, s, (amc::SEARCH_S_HEAD + n_trace) * sizeof(unsigned long long)));
+    std::memcpy(beta_new, &host[amc::SEARCH_S_BETA], sizeof(double));
+    if (diag) {
+        static const int words[AMC_ANNEAL_SEARCH_WORDS] = {amc::SEARCH_S_STATUS, amc::SEARCH_S_ROUNDS, amc::SEARCH_S_STEP,  amc::SEARCH_S_RHO_LO,
+                                                            amc::SEARCH_S_HI,     amc::SEARCH_S_RHO_HI, amc::SEARCH_S_NE_HI, amc::SEARCH_S_NE_LO};
+        for (int i = 0; i < AMC_ANNEAL_SEARCH_WORDS; ++i) diag[i] = (uint64_t)host[words[i]];
+    }
+    if (trace)
+        for (size_t i = 0; i < n_trace; ++i) trace[i] = (uint64_t)host[amc::SEARCH_S_HEAD + i];
     return AMC_OK;
 }
 

@@ -10,7 +10,7 @@
 //                       proposal widths per rung: amc_set_rung_sigma / amc_get_rung_sigma, respacing: amc_respace_ladder ..,
 //                       tuning the widths: amc_tune_rung_sigma .., the window of the acceptance per rung: amc_rung_window_*)
 //   amc_anneal.hip      population annealing (amc_anneal, its record log, the annealing step index, amc_get_beta, the families:
-//                       amc_set_anneal_families .. amc_upload_families)
+//                       amc_set_anneal_families .. amc_upload_families; amc_anneal_next_beta)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -221,6 +221,8 @@ struct AnnealState {
     uint32_t* d_fam = nullptr;                  // [M] family id per chain; allocated exactly while families are on (amc_set_anneal_families)
     uint32_t* d_fam_alt = nullptr;              // [M] ... and the buffer a step gathers them into
     unsigned int* d_fam_cnt = nullptr;          // [M] + 3 words: scratch of amc_anneal_family_stats (allocated at its first call)
+    unsigned long long* d_anneal_search = nullptr;   // [SEARCH_S_WORDS] the words of amc_anneal_next_beta (allocated at its first call;
+                                                     //   its energies go into d_anneal_n)
 };
 static inline void anneal_release(AnnealState& s)
 {
@@ -232,6 +234,7 @@ static inline void anneal_release(AnnealState& s)
     (void)hipFree(s.d_fam);
     (void)hipFree(s.d_fam_alt);
     (void)hipFree(s.d_fam_cnt);
+    (void)hipFree(s.d_anneal_search);
 }
 
 struct amc_handle {

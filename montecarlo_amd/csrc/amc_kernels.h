@@ -22,6 +22,7 @@
 //   amc_aux_kernels.h  histogram / energy / conversion kernels, parity-test hooks
 //   amc_exchange.h     replica exchange along a temperature ladder: exchange_kernel, the histogram by rung
 //   amc_anneal.h       population annealing: log-weights, integer weights, the three-launch prefix, the gather, the families
+//   amc_anneal_search.h  population annealing: the next beta from a target on the effective-sample fraction (energies, sums, decision)
 #pragma once
 
 #include "amc_model.h"
@@ -34,3 +35,4 @@
 #include "amc_aux_kernels.h"
 #include "amc_exchange.h"
 #include "amc_anneal.h"
+#include "amc_anneal_search.h"
