@@ -701,6 +701,44 @@ int  amc_pgmc_steps(amc_handle *h, int64_t n_steps, int n_learn, const int *lear
 int  amc_pgmc_steps_reduce_begin(amc_handle *h, int64_t n_steps, int n_learn, const int *learn_ids, int q_batch,
                                  int do_update, const int *optimiser, const double *hyper0, const double *hyper1);
 
+/* Time correlation: how fast an observable of the chains decorrelates, from ONE time origin and the M chains
+ * as independent series.  With a_i = O(x_i) at the mark and O_i = O(x_i) at a later sample, per group g and slot s the reproducible
+ * (kind-R) sums of   O: O_i   OO: fl(O_i O_i)   AO: fl(a_i O_i)   -- Float64 products, one multiplication each, no fma -- give
+ *   C_g(k) = <a O_k> - <a><O_k>.   O(x) = double(potential_T(x)) for AMC_CORR_E, double(x) for AMC_CORR_X (both conversions exact).
+ * Groups: a handle with a ladder has G = R of them, group r the chains l R + r (the series of RUNG r, whatever replicas pass through
+ * it); a handle without a ladder has one, g = 0, over all local chains.  Every record's level is fixed by the largest summand of its
+ * own group, column and slot; NaN and +-Inf flag their own record and no other.  The same bits on any grid and any split into shards.
+ * amc_corr_mark queues one pass behind whatever is on the stream and returns at once (a pending learning step is taken first, as
+ * before amc_bridge_accumulate): it stores a_i for every local chain (a buffer of n_chains doubles, allocated at its first use),
+ * forgets the samples of an earlier mark and takes sample 0 of the new origin in the same launch -- there O = a, so slot 0 holds
+ * sum a, sum a^2, sum a a --, steps[0] = amc_get_step's value.  amc_corr_sample queues one pass over x and the origin into the next
+ * free slot s, steps[s] = the MH step index at the call (two samples at one index are allowed); with sliced sweep launches it runs
+ * behind their join, where a bridge snapshot runs.
+ * amc_corr_fetch waits and returns records[((s * G + g) * AMC_CORR_COLS + c) * AMC_XSUM_WORDS ...] of the LOCAL shard (merge across
+ * shards with amc_xsum_merge / amc_allreduce_xsum), s < *n_samples (slot 0 included), and steps[s]; capacity counts the slots the
+ * caller's arrays hold; *observable = 0 and *n_samples = 0 when nothing is marked.  Fetch resets nothing.
+ * amc_corr_download_origin (n_chains doubles) and amc_set_corr serve checkpoints: amc_set_corr restores a mark with its samples,
+ * the records checked as amc_set_bridge checks them -- kind-R records, every word an integer below 2^53 --, steps non-decreasing.
+ * amc_corr_clear drops the mark and keeps the memory.
+ * The mark is CLEARED by every call that reassigns chain slots -- amc_upload_state, amc_init_uniform, amc_set_ladder, an amc_anneal
+ * that was queued (resampling moves positions between slots: a product across it has no meaning) -- and KEPT by amc_exchange (the
+ * series is that of rung r, the thing a ladder is meant to shorten), by sweeps, reductions and the estimator, and by
+ * amc_respace_ladder and amc_tune_rung_sigma: those two are burn-in tools whose status the host does not know without a
+ * synchronisation, so they cannot clear it; a series marked across one of them mixes two ladders / widths and is the caller's to discard.
+ * None of these entries touches the step indices, the step log, a counter, reductions in flight, labels, widths or the bridge sums.
+ * AMC_ERR_STATE: amc_corr_sample / amc_corr_download_origin without a mark, amc_corr_sample with all AMC_CORR_MAX_LAGS slots used.
+ * AMC_ERR_BAD_ARG: an observable outside {E, X}; capacity < *n_samples; amc_set_corr with records amc_corr_fetch cannot have given,
+ * n_samples outside [1, AMC_CORR_MAX_LAGS] or decreasing steps.  A refused call leaves the handle as it was. */
+enum { AMC_CORR_E = 1, AMC_CORR_X = 2 };
+#define AMC_CORR_MAX_LAGS 256
+enum { AMC_CORR_O = 0, AMC_CORR_OO = 1, AMC_CORR_AO = 2, AMC_CORR_COLS = 3 };
+int  amc_corr_mark(amc_handle *h, int observable);
+int  amc_corr_sample(amc_handle *h);
+int  amc_corr_fetch(amc_handle *h, double *records, uint64_t *steps, int capacity, int *n_samples, int *observable);
+int  amc_corr_download_origin(amc_handle *h, double *origin);
+int  amc_set_corr(amc_handle *h, int observable, const double *origin, const double *records, const uint64_t *steps, int n_samples);
+int  amc_corr_clear(amc_handle *h);
+
 int  amc_sync(amc_handle *h);
 /* hipStream_t the handle launches on (for event timing / graph capture by the host). */
 int  amc_get_stream(amc_handle *h, void **stream);

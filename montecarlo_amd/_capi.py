@@ -33,6 +33,11 @@ AMC_ANNEAL_SEARCH_MAX_ROUNDS = 16
 AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_REDUCE_ALL = 1, 2, 4, 7      # the sums over x a reduction forms (include/amc.h)
 # the columns of the bridge sums (include/amc.h); record order E, EE, WF, WB, MF, MB
 AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_WF, AMC_BRIDGE_WB, AMC_BRIDGE_MF, AMC_BRIDGE_MB, AMC_BRIDGE_ALL = 1, 2, 4, 8, 16, 32, 63
+# time correlation (include/amc.h): the observables, the slots of one mark, the columns of a record in their order
+AMC_CORR_E, AMC_CORR_X = 1, 2
+AMC_CORR_MAX_LAGS = 256
+AMC_CORR_O, AMC_CORR_OO, AMC_CORR_AO, AMC_CORR_COLS = 0, 1, 2, 3
+CORR_OBSERVABLES = {"energy": AMC_CORR_E, "x": AMC_CORR_X}
 AMC_RESPACE_ACCEPTANCE, AMC_RESPACE_FLOW = 1, 2      # the rules of amc_respace_ladder (include/amc.h)
 RESPACE_RULES = {"acceptance": AMC_RESPACE_ACCEPTANCE, "flow": AMC_RESPACE_FLOW}
 
@@ -178,6 +183,12 @@ def load() -> C.CDLL:
         "amc_bridge_accumulate": (C.c_int, [H, C.c_int]),
         "amc_bridge_fetch": (C.c_int, [H, dp, u64p, C.c_int]),
         "amc_set_bridge": (C.c_int, [H, dp, C.c_uint64]),
+        "amc_corr_mark": (C.c_int, [H, C.c_int]),
+        "amc_corr_sample": (C.c_int, [H]),
+        "amc_corr_fetch": (C.c_int, [H, dp, u64p, C.c_int, ip, ip]),
+        "amc_corr_download_origin": (C.c_int, [H, dp]),
+        "amc_set_corr": (C.c_int, [H, C.c_int, dp, dp, u64p, C.c_int]),
+        "amc_corr_clear": (C.c_int, [H]),
         "amc_set_tracking": (C.c_int, [H, C.c_int]),
         "amc_download_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
         "amc_upload_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
@@ -812,6 +823,48 @@ class HipEngine:
         if int(n_snapshots) < 0:
             raise AmcError("set_bridge: n_snapshots < 0")
         _check(self._lib.amc_set_bridge(self._h, _ptr(rec), int(n_snapshots)))
+
+    # -- time correlation (include/amc.h) ----------------
+    def corr_mark(self, observable="energy") -> None:
+        """Mark a time origin (amc_corr_mark): a_i = O(x_i) of every local chain is kept on the device, and sample 0 is taken in the
+        same launch.  ``observable``: "energy" / "x" or AMC_CORR_E / AMC_CORR_X.  Stream-ordered, nothing synchronises."""
+        _check(self._lib.amc_corr_mark(self._h, int(CORR_OBSERVABLES.get(observable, observable))))
+
+    def corr_sample(self) -> None:
+        """Queue the sums of O, O^2 and a O by group into the next slot of the mark (amc_corr_sample).  Stream-ordered."""
+        _check(self._lib.amc_corr_sample(self._h))
+
+    def corr_fetch(self):
+        """(records[n_samples][G][3][AMC_XSUM_WORDS], steps[n_samples], observable) of this shard's mark, columns O, OO, AO
+        (amc_corr_fetch); G = R with a ladder, else 1; observable 0 and no samples when nothing is marked.  What shards exchange
+        (sharding.allreduce_xsum); ``xsum_round`` yields the Float64s.  Synchronises, resets nothing."""
+        g = self._rungs()
+        out = np.zeros((AMC_CORR_MAX_LAGS, g, AMC_CORR_COLS, AMC_XSUM_WORDS), dtype=np.float64)
+        steps = np.zeros(AMC_CORR_MAX_LAGS, dtype=np.uint64)
+        n, obs = C.c_int(0), C.c_int(0)
+        _check(self._lib.amc_corr_fetch(self._h, _ptr(out), _ptr(steps), AMC_CORR_MAX_LAGS, C.byref(n), C.byref(obs)))
+        return out[:n.value].copy(), steps[:n.value].copy(), int(obs.value)
+
+    def corr_origin(self) -> np.ndarray:
+        """a_i of every local chain as the mark stored it (amc_corr_download_origin; checkpoints).  Synchronises."""
+        out = np.zeros(self.n_chains, dtype=np.float64)
+        _check(self._lib.amc_corr_download_origin(self._h, _ptr(out)))
+        return out
+
+    def set_corr(self, observable, origin, records, steps) -> None:
+        """Restore a mark with its samples from ``corr_origin`` and ``corr_fetch`` (amc_set_corr; checkpoints)."""
+        g = self._rungs()
+        st = np.ascontiguousarray(steps, dtype=np.uint64)
+        rec = np.ascontiguousarray(records, dtype=np.float64)
+        org = np.ascontiguousarray(origin, dtype=np.float64)
+        if org.size != self.n_chains or rec.size != st.size * g * AMC_CORR_COLS * AMC_XSUM_WORDS:
+            raise AmcError(f"set_corr: {org.size} origin values and {rec.size} doubles for {st.size} samples of {g} groups on {self.n_chains} chains")
+        _check(self._lib.amc_set_corr(self._h, int(CORR_OBSERVABLES.get(observable, observable)), _ptr(org), _ptr(rec), _ptr(st),
+                                      int(st.size)))
+
+    def corr_clear(self) -> None:
+        """Drop the mark (amc_corr_clear); the memory stays."""
+        _check(self._lib.amc_corr_clear(self._h))
 
     # -- walker tracking (include/amc.h; DESIGN.md section 3.13 "Walker tracking") ----------------
     def set_tracking(self, on: bool = True) -> None:

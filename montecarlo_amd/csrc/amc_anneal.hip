@@ -104,6 +104,7 @@ int amc_anneal(amc_handle* h, double beta_new)
     h->beta = beta_new;          // the host field: in force for every launch queued from now on (nothing on the device is derived from it)
     h->ann.t_a += 1;
     h->ann.anneal_n += 1;
+    corr_forget(h);              // the copies have changed slots: the mark of the time correlation goes (include/amc.h "Time correlation")
     return AMC_OK;
 }
 

@@ -553,6 +553,7 @@ int amc_destroy(amc_handle* h)
     (void)hipFree(h->d_hist);
     ladder_release(h->lad);
     anneal_release(h->ann);
+    corr_release(h->corr);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

@@ -87,6 +87,7 @@ static int ladder_reset(amc_handle* h)
     if (h->lad.d_respace) AMC_HIP(hipMemsetAsync(h->lad.d_respace, 0, RESPACE_BYTES, h->stream));
     AMC_TRY(tune_reset(h, true));
     AMC_TRY(bridge_clear(h));
+    corr_forget(h);                 // (no ladder state, but its groups are the rungs: the chains' slots mean something else now)
     h->lad.rung_on = false;
     return AMC_OK;
 }
@@ -102,19 +103,11 @@ static int flow_snapshot_queue(amc_handle* h)
     return AMC_OK;
 }
 
-// A pass over the ladders that ends every block with rows of its own, n_cols columns per rung, in d_rung_rows (the rung sums, the bridge
-// sums): the launches it takes and where each one's rows go.
-struct RungPass {
-    int grid = 0;
-    int64_t per_launch = 0, n_launches = 0;     // ladders per launch; launches
-    size_t slot_words = 0;                      // words of one block's rows
-    int n_blocks() const { return (int)(n_launches * grid); }      // block rows the finishing kernel reads
-};
-
-// ... planned, and room made for its rows.
-static int rung_pass_plan(amc_handle* h, int n_cols, RungPass* p)
+// A pass over the groups (RungPass, amc_internal.h) planned, and room made for its rows.
+int rung_pass_plan(amc_handle* h, int n_cols, RungPass* p)
 {
-    const int R = h->lad.n_rungs;
+    const int R = h->lad.n_rungs ? h->lad.n_rungs : 1;
+    p->groups = R;
     p->grid = grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU);
     // a lane adds one summand per trip and column and holds XS_LANE_CAP of them (amc_xsum.h): ensembles beyond that many trips of the
     // grid (2^28 chains and more) take several launches, each with block rows of its own
@@ -122,24 +115,6 @@ static int rung_pass_plan(amc_handle* h, int n_cols, RungPass* p)
     p->n_launches = (h->M / R + p->per_launch - 1) / p->per_launch;
     p->slot_words = (size_t)R * (size_t)n_cols * amc::XS_ROW_R;
     return rung_rows_room(h, (size_t)p->n_launches * (size_t)p->grid * p->slot_words);
-}
-
-// ... launched: `a` comes with what only its kernel reads (the bridge sums' beta); x, the rows, the ladders, R and the columns are filled in here.
-template <class Args>
-static int rung_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
-{
-    const int64_t n_ladders = h->M / h->lad.n_rungs;
-    a.x = h->d_x;
-    a.n_rungs = h->lad.n_rungs;
-    a.cols = columns;
-    for (int64_t i = 0; i < p.n_launches; ++i) {
-        a.rows = h->lad.d_rung_rows + (size_t)i * (size_t)p.grid * p.slot_words;
-        a.l_begin = i * p.per_launch;
-        a.l_end = std::min(n_ladders, (i + 1) * p.per_launch);
-        void* params[] = {&a};
-        AMC_TRY(launch_by_potential(h, name, double_well, harmonic, p.grid, params));
-    }
-    return AMC_OK;
 }
 
 // One exchange step on the stream: the gaps r with r mod 2 == t_x mod 2 of every local ladder.  A parity without gaps (R = 2, odd

@@ -11,6 +11,7 @@
 //                       tuning the widths: amc_tune_rung_sigma .., the window of the acceptance per rung: amc_rung_window_*)
 //   amc_anneal.hip      population annealing (amc_anneal, its record log, the annealing step index, amc_get_beta, the families:
 //                       amc_set_anneal_families .. amc_upload_families; amc_anneal_next_beta)
+//   amc_corr.hip        time correlation from one time origin (amc_corr_mark .. amc_corr_clear)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -161,8 +162,8 @@ struct ModelSpec {
 };
 
 // ---- state that is owned together: declared, reset and freed together -----------------------------------------------------------------
-// Two plain structs the handle holds by value.  Below each is its one release function, which frees every device pointer the struct
-// declares (tests/test_handle_state_static.py holds it to that); amc_destroy calls the two.
+// Plain structs the handle holds by value.  Below each is its one release function, which frees every device pointer the struct
+// declares (tests/test_handle_state_static.py holds it to that); amc_destroy calls them all.
 
 // The temperature ladder and what belongs to it (amc_exchange.hip; the totals per rung: amc_counters.hip).  amc_set_ladder forgets all
 // of it but the memory (ladder_reset).
@@ -237,6 +238,22 @@ static inline void anneal_release(AnnealState& s)
     (void)hipFree(s.d_anneal_search);
 }
 
+// Time correlation (amc_corr.hip): both buffers allocated at their first use -- a handle that never marks has
+// neither.  A mark stands exactly while observable != 0.
+struct CorrState {
+    int observable = 0;                         // AMC_CORR_E / AMC_CORR_X of the mark; 0: nothing is marked
+    int n_samples = 0;                          // slots taken since the mark, slot 0 (the mark's own) included
+    int groups = 0;                             // G at the mark (amc_set_ladder clears the mark, so it is the handle's G while the mark stands)
+    uint64_t steps[AMC_CORR_MAX_LAGS] = {0};    // the MH step index at each sample
+    double* d_origin = nullptr;                 // [M_pad] a_i = O(x_i) at the mark
+    amc::xs_word* d_corr = nullptr;             // [CORR_ACC_WORDS] a row per (sample, group, column): the records' layout (amc_corr.h)
+};
+static inline void corr_release(CorrState& s)
+{
+    (void)hipFree(s.d_origin);
+    (void)hipFree(s.d_corr);
+}
+
 struct amc_handle {
     AmcKnobs knobs;             // the environment's knobs as amc_create found them
     int device = 0;
@@ -253,6 +270,7 @@ struct amc_handle {
     uint64_t t_est = 0;         // estimator calls done
     LadderState lad;            // the temperature ladder and what hangs on it (amc_exchange.hip)
     AnnealState ann;            // population annealing (amc_anneal.hip)
+    CorrState corr;             // time correlation (amc_corr.hip)
     double* d_x = nullptr;
     double* d_beta = nullptr;
     uint32_t* d_acc = nullptr;
@@ -377,6 +395,15 @@ static inline int need_families(const amc_handle* h, const char* who)
     return h->ann.d_fam ? AMC_OK : fail(AMC_ERR_STATE, "%s: families are off (amc_set_anneal_families)", who);
 }
 
+// The chains have changed slots (an upload, a new initial ensemble, another ladder, a resampling): a product of the origin values with
+// what the slots hold now has no meaning, so the mark of the time correlation goes.  Host fields only; the memory stays.
+static inline void corr_forget(amc_handle* h)
+{
+    h->corr.observable = 0;
+    h->corr.n_samples = 0;
+    h->corr.groups = 0;
+}
+
 // ---- shared between the translation units ----------------------------------------------------------------------------------------
 AMC_INTERNAL int grid_for(const amc_handle* h, int64_t n_items, int blocks_per_cu = 0);   // amc_api.hip
 AMC_INTERNAL hipError_t wait_stream(hipStream_t stream);                                  // amc_state.hip
@@ -418,6 +445,17 @@ AMC_INTERNAL int check_sigma_f32(const char* who, int k, double s);     // a sig
             return fail(AMC_ERR_STATE, "%s: not available while widths per rung are set (amc_set_rung_sigma): the estimator learns one sigma per move", (who)); \
     } while (0)
 AMC_INTERNAL int pg_resolve(amc_handle* h);      // takes a pending learning step now (amc_pg.hip)
+// A pass over the groups of chains -- the rungs of the ladder; ONE group of all local chains without a ladder -- that ends every block
+// with rows of its own, n_cols columns per group, in lad.d_rung_rows (the rung sums, the bridge sums, the time correlation): the
+// launches it takes and where each one's rows go (amc_exchange.hip).
+struct RungPass {
+    int grid = 0;
+    int groups = 1;                             // G: R of the ladder, 1 without one (a "ladder" of the pass is then a single chain)
+    int64_t per_launch = 0, n_launches = 0;     // ladders per launch; launches
+    size_t slot_words = 0;                      // words of one block's rows
+    int n_blocks() const { return (int)(n_launches * grid); }      // block rows the finishing kernel reads
+};
+AMC_INTERNAL int rung_pass_plan(amc_handle* h, int n_cols, RungPass* p);      // ... planned, and room made for its rows
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };
@@ -435,5 +473,24 @@ static inline int launch_by_potential(amc_handle* h, const char* name, const voi
     if (h->use_rtc) return rtc_launch(h, std::string(name) + "<" + std::to_string(h->potential) + ">", grid, params);
     (void)hipLaunchKernel(h->potential == AMC_POTENTIAL_DOUBLE_WELL ? double_well : harmonic, dim3(grid), dim3(AMC_BLOCK), params, 0, h->stream);
     AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
+// A planned pass launched: `a` comes with what only its kernel reads (the bridge sums' beta, the origin of the time correlation); x, the
+// rows, the ladders, G and the columns are filled in here.
+template <class Args>
+static inline int rung_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
+{
+    const int64_t n_ladders = h->M / p.groups;
+    a.x = h->d_x;
+    a.n_rungs = p.groups;
+    a.cols = columns;
+    for (int64_t i = 0; i < p.n_launches; ++i) {
+        a.rows = h->lad.d_rung_rows + (size_t)i * (size_t)p.grid * p.slot_words;
+        a.l_begin = i * p.per_launch;
+        a.l_end = std::min(n_ladders, (i + 1) * p.per_launch);
+        void* params[] = {&a};
+        AMC_TRY(launch_by_potential(h, name, double_well, harmonic, p.grid, params));
+    }
     return AMC_OK;
 }

@@ -23,6 +23,7 @@
 //   amc_exchange.h     replica exchange along a temperature ladder: exchange_kernel, the histogram by rung
 //   amc_anneal.h       population annealing: log-weights, integer weights, the three-launch prefix, the gather, the families
 //   amc_anneal_search.h  population annealing: the next beta from a target on the effective-sample fraction (energies, sums, decision)
+//   amc_corr.h         time correlation from one time origin: the sums of O, O^2, a O by group, one slot per lag
 #pragma once
 
 #include "amc_model.h"
@@ -36,3 +37,4 @@
 #include "amc_exchange.h"
 #include "amc_anneal.h"
 #include "amc_anneal_search.h"
+#include "amc_corr.h"

@@ -110,6 +110,7 @@ class Metropolis(AriannaAlgorithm):
         self.tracking = False               # walker tracking is on (ReplicaExchange.initialise, storage.restore; set_ladder turns it off)
         self.bridge = 0                     # mask of the bridge sums (ReplicaExchange.__init__; 0: off)
         self.annealing = None               # the PopulationAnnealing that cools these chains (its __init__)
+        self.autocorrelation = None         # the Autocorrelation that measures these chains (its __init__)
         self.restored = False               # storage.restore put the state on the device: initialise() leaves it there
         self.families_restored = False      # storage.restore brought the annealing families back
         self._rung_window_used = False      # a tuning or a window restart has happened (tune_rung_sigma, restart_rung_window, storage.restore)

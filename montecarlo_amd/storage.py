@@ -284,6 +284,16 @@ def _read_annealing(met, eng, d, est) -> None:
             met.families_restored = True
 
 
+def _write_correlation(met, eng, d, est) -> None:
+    ac = met.autocorrelation
+    if ac is not None:                              # a time correlation: the observable, the mark with its origin values, records and steps,
+        d.update(ac.state())                        # and the host accumulator with its origin count are state (no field otherwise)
+
+def _read_correlation(met, eng, d, est) -> None:
+    if "corr_observable" in d and met.autocorrelation is not None:      # behind the core: upload_state has cleared the engine's mark
+        met.autocorrelation.set_state(d)
+
+
 def _write_estimator(met, eng, d, est) -> None:
     if est is not None:
         d["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in est.gradients_data])
@@ -302,11 +312,12 @@ def _read_estimator(met, eng, d, est) -> None:
 
 
 # The order is restore's, the engine calls depend on it: the table is checked before the ladder is set and goes to the engine behind it;
-# the ladder comes before everything kept per rung (labels, window, bridge records); the window's base before the count of tunings.
+# the ladder comes before everything kept per rung (labels, window, bridge records, the time correlation's groups); the window's base
+# before the count of tunings.
 _SECTIONS = ((_write_core, _read_core), (_write_counters, _read_counters), (_write_rung_sigma, _read_rung_sigma),
              (_write_ladder, _read_ladder), (_write_tracking, _read_tracking), (_write_window, _read_window),
              (_write_bridge, _read_bridge), (_write_respacing, _read_respacing), (_write_annealing, _read_annealing),
-             (_write_estimator, _read_estimator))
+             (_write_correlation, _read_correlation), (_write_estimator, _read_estimator))
 
 
 def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
