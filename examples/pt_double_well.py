@@ -7,7 +7,7 @@ down.  Every chain starts in the right well; the script runs the same schedule w
 rung, the fraction of chains left of the barrier, the mean energy and the swap acceptance of every gap.
 
     python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track] [--rung-sigma] [--adapt flow|acceptance]
-                                          [--tune-sigma TARGET]
+                                          [--tune-sigma TARGET] [--free-energy [--blocks 32]]
 
 --track also follows every replica through the swaps and prints, at the end, the flow fraction f(r) -- of the replicas at rung r that
 have been to an end of the ladder, the share that came from the hot end (rung 0) last -- and the round trips per ladder.
@@ -25,6 +25,10 @@ the end are those of the second half, on the final ladder, which is printed too.
 and leaves the widths alone afterwards -- changing sigma breaks detailed balance across the change, so the first half is burn-in.  The
 table starts from sigma_0 at every rung, or from the table of --rung-sigma.  The tuned table is printed, and beside it the acceptance
 per rung over the window since the last tuning: the second half, under the final table.
+
+--free-energy accumulates the bridge sums over the second half of the run and prints log(Z_(r+1) / Z_r) by three estimators beside a
+quadrature, and the heat capacity per rung.  With --blocks B the sums are kept per block of ladders (ReplicaExchange(..., blocks=B)) and
+every estimate comes with the standard error of a delete-one-block jackknife over the B blocks, value +- se.
 """
 import argparse
 import os
@@ -70,7 +74,8 @@ def one_run(args, path, exchange: bool):
     if exchange:
         track = args.track or args.adapt == "flow"
         bridge = ma.ReplicaExchange.BRIDGE_DEFAULT | 4 | 8 if args.free_energy else False          # ... and the two W columns
-        algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), track=track, bridge=bridge))   # every time step
+        blocks = args.blocks if args.free_energy else None
+        algorithm_list.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), track=track, bridge=bridge, blocks=blocks))   # every time step
         if args.free_energy:                           # measure over the second half of the run
             algorithm_list.append(dict(algorithm=RestartBridge, dependencies=(ma.ReplicaExchange,), scheduler=[max(1, args.steps // 2)]))
         callbacks.append(ma.callback_exchange_acceptance)
@@ -114,7 +119,11 @@ def main(argv=None):
     ap.add_argument("--free-energy", action="store_true",
                     help="accumulate the bridge sums over the second half of the run; print log(Z_(r+1) / Z_r) by three estimators beside a "
                          "quadrature, and the heat capacity per rung")
+    ap.add_argument("--blocks", type=int, default=None, metavar="B",
+                    help="with --free-energy: keep the bridge sums per block of ladders and print every estimate +- its jackknife standard error")
     args = ap.parse_args(argv)
+    if args.blocks is not None and not args.free_energy:
+        ap.error("--blocks needs --free-energy")
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
     _, left_plain, energy_plain, _, _ = one_run(args, os.path.join(path, "plain"), False)
@@ -135,14 +144,28 @@ def main(argv=None):
     if args.free_energy:
         rx = sim.algorithms[1]
         exact = np.diff(log_z_by_quadrature())
-        expo = rx.log_z_ratios("exponential")
-        print(f"log Z ratio per gap, {rx.bridge_sums()[1]:4d} snapshots of {args.ladders} ladders")
-        print("  quadrature                  : " + "  ".join(f"{v:7.4f}" for v in exact))
-        print("  acceptance (Bennett, C = 0) : " + "  ".join(f"{v:7.4f}" for v in rx.log_z_ratios("acceptance")))
-        print("  exponential, forward        : " + "  ".join(f"{v:7.4f}" for v in expo[0]))
-        print("  exponential, backward       : " + "  ".join(f"{v:7.4f}" for v in expo[1]))
-        print("  thermodynamic integration   : " + "  ".join(f"{v:7.4f}" for v in rx.log_z_ratios("ti")) + "   (trapezoid: coarse on this ladder)")
-        print("heat capacity per rung        : " + "  ".join(f"{v:7.4f}" for v in rx.heat_capacity()))
+        if args.blocks:                                 # (value, se) per estimate: the jackknife over the blocks of ladders
+            def row(pair, i=None):
+                value, se = pair if i is None else (pair[0][i], pair[1][i])
+                return "  ".join(f"{v:7.4f} +- {s:6.4f}" for v, s in zip(value, se))
+            expo = rx.log_z_ratios("exponential", error=True)
+            print(f"log Z ratio per gap, {rx.bridge_sums()[1]:4d} snapshots of {args.ladders} ladders, +- jackknife se over {args.blocks} blocks")
+            print("  quadrature                  : " + "  ".join(f"{v:7.4f}          " for v in exact))
+            print("  acceptance (Bennett, C = 0) : " + row(rx.log_z_ratios("acceptance", error=True)))
+            print("  exponential, forward        : " + row(expo, 0))
+            print("  exponential, backward       : " + row(expo, 1))
+            print("  thermodynamic integration   : " + row(rx.log_z_ratios("ti", error=True)) + "   (trapezoid: coarse on this ladder)")
+            print("log(Z_r / Z_0), acceptance    : " + row(rx.log_z(error=True)))
+            print("heat capacity per rung        : " + row(rx.heat_capacity(error=True)))
+        else:
+            expo = rx.log_z_ratios("exponential")
+            print(f"log Z ratio per gap, {rx.bridge_sums()[1]:4d} snapshots of {args.ladders} ladders")
+            print("  quadrature                  : " + "  ".join(f"{v:7.4f}" for v in exact))
+            print("  acceptance (Bennett, C = 0) : " + "  ".join(f"{v:7.4f}" for v in rx.log_z_ratios("acceptance")))
+            print("  exponential, forward        : " + "  ".join(f"{v:7.4f}" for v in expo[0]))
+            print("  exponential, backward       : " + "  ".join(f"{v:7.4f}" for v in expo[1]))
+            print("  thermodynamic integration   : " + "  ".join(f"{v:7.4f}" for v in rx.log_z_ratios("ti")) + "   (trapezoid: coarse on this ladder)")
+            print("heat capacity per rung        : " + "  ".join(f"{v:7.4f}" for v in rx.heat_capacity()))
     if args.adapt:
         rx = sim.algorithms[1]
         print(f"ladder after {rx.metropolis.engine.respace_status()[1]} respacings   : " + "  ".join(f"{b:7.4f}" for b in rx.betas()) + "   (second half: the lines above and below)")

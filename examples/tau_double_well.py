@@ -8,10 +8,15 @@ schedule runs with and without exchange steps: the series of RUNG r decorrelates
 it, and tau_int -- the number of MH steps between two samples that count as independent -- says by how much.
 
     python examples/tau_double_well.py [--ladders 16384] [--burn 500] [--every 2] [--lags 100] [--origins 2] [--path data/TAU/...]
+                                       [--blocks 32]
     python examples/tau_double_well.py --anneal
 
 --anneal: population annealing instead (examples/pa_double_well.py's schedule): the population is cooled to the last beta, then an
 origin is marked and tau_int of the energy at that beta is printed -- what the sweeps between two annealing steps have to cover.
+
+--blocks B keeps the sums per block of ladders (Autocorrelation(..., blocks=B)) and prints the standard error of every tau_int from a
+delete-one-block jackknife over the B blocks, each replicate with its own automatic window.  Not with --anneal: resampling makes
+copies of one parent share blocks.
 """
 import argparse
 import os
@@ -43,7 +48,7 @@ def ladder_run(args, path, exchange: bool):
     x_sched = range(1, sched[-1] + 1) if exchange else range(1, args.burn + 1)
     al.append(dict(algorithm=ma.ReplicaExchange, dependencies=(ma.Metropolis,), scheduler=list(x_sched)))
     al.append(dict(algorithm=ma.Autocorrelation, dependencies=(ma.Metropolis,), scheduler=sched, observable="energy", n_lags=args.lags,
-                   origins=args.origins))
+                   origins=args.origins, blocks=args.blocks))
     sim = ma.Simulation(chains, al, sched[-1], path=path)
     ma.run(sim)
     return sim.algorithms[2]
@@ -79,7 +84,10 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--path", default=None)
     ap.add_argument("--anneal", action="store_true", help="tau_int at the final beta of a population-annealing run instead")
+    ap.add_argument("--blocks", type=int, default=None, metavar="B", help="print tau_int +- its jackknife standard error over B blocks of ladders")
     args = ap.parse_args(argv)
+    if args.blocks is not None and args.anneal:
+        ap.error("--blocks does not go with --anneal: resampling makes copies of one parent share blocks")
     path = args.path or f"data/TAU/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     if args.anneal:
         ac, beta = anneal_run(args, os.path.join(path, "anneal"))
@@ -89,11 +97,19 @@ def main(argv=None):
         return tau
     with_x = ladder_run(args, os.path.join(path, "exchange"), True)
     without = ladder_run(args, os.path.join(path, "plain"), False)
-    tau_x, win_x, ok_x = with_x.tau_int()
-    tau_p, win_p, ok_p = without.tau_int()
     row("beta", BETAS)
-    row("tau_int(energy), with exchange", tau_x)
-    row("tau_int(energy), without", tau_p)
+    if args.blocks:
+        tau_x, se_x, win_x, ok_x = with_x.tau_int(error=True)
+        tau_p, se_p, win_p, ok_p = without.tau_int(error=True)
+        row("tau_int(energy), with exchange", tau_x)
+        row(f"  +- se ({args.blocks} blocks)", se_x)
+        row("tau_int(energy), without", tau_p)
+        row(f"  +- se ({args.blocks} blocks)", se_p)
+    else:
+        tau_x, win_x, ok_x = with_x.tau_int()
+        tau_p, win_p, ok_p = without.tau_int()
+        row("tau_int(energy), with exchange", tau_x)
+        row("tau_int(energy), without", tau_p)
     row("window (lags), with / without", [f"{a}/{b}" for a, b in zip(win_x, win_p)], "{:>9s}")
     if not (ok_x.all() and ok_p.all()):
         print("(a window reached the last lag: that tau_int is a lower bound; run with more --lags or a larger --every)")

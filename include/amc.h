@@ -739,6 +739,47 @@ int  amc_corr_download_origin(amc_handle *h, double *origin);
 int  amc_set_corr(amc_handle *h, int observable, const double *origin, const double *records, const uint64_t *steps, int n_samples);
 int  amc_corr_clear(amc_handle *h);
 
+/* Jackknife blocks: the bridge sums and the time correlation kept per BLOCK of ladders, so that a
+ * delete-one-block jackknife over the B blocks gives an error bar for any function of the sums -- the ladders (the chains, without a
+ * ladder) are independent systems, whatever the correlation in time or between the rungs of one ladder.
+ * The partition is the pair (B, C), 2 <= B <= AMC_MAX_JK_BLOCKS blocks and a chunk of C >= 1 ladders: the block of a ladder is
+ *   b(l) = (l_global div C) mod B,   l_global = chain_offset / G + l_local   (64-bit; G = R of the ladder, 1 without one: a "ladder"
+ * is then one chain).  It depends on nothing else -- not the grid, not the launch split, not the split into shards --, and a ladder
+ * stays in its block for the whole run: exchange steps move positions within a ladder only.
+ * amc_set_blocks(h, n_blocks, chunk): n_blocks = 0 turns the partition off (the state of every handle that never called it); chunk = 0
+ * asks for the default, max(1, 256 div G) ladders.  On success it clears the bridge accumulator and forgets the mark of the time
+ * correlation, as amc_set_ladder does; amc_set_ladder turns the partition off on every call that succeeds.
+ * While a partition is set, amc_bridge_accumulate, amc_corr_mark and amc_corr_sample keep one row per (block, group, column) --
+ * allocated at their first use, sized by B and G --, and amc_bridge_fetch / amc_corr_fetch return the merge over the blocks: bit for
+ * bit the records of a handle without a partition (kind-R merges are integer additions, their order is immaterial).
+ * amc_bridge_fetch_blocks: records[((b * R + r) * 6 + c) * AMC_XSUM_WORDS ...], b < *n_blocks, capacity_blocks >= B; a block without
+ * a local ladder gives all-zero records.  amc_corr_fetch_blocks: records[(((b * S + s) * G + g) * AMC_CORR_COLS + c) * AMC_XSUM_WORDS
+ * ...] with S = *n_samples <= capacity: B * S * G * 3 records are written, densely (the caller's array holds B * capacity * G * 3), and
+ * steps[s] as amc_corr_fetch gives them; with records = NULL or steps = NULL it returns *n_blocks, *n_samples and *observable alone,
+ * without waiting for the stream (what a caller sizes its arrays by).  Both are AMC_ERR_STATE without a partition.
+ * A respacing that is taken zeroes every block's rows; amc_upload_state, amc_init_uniform forget the blocked mark as they forget the
+ * plain one.  amc_anneal is AMC_ERR_STATE while a partition is set: resampling makes copies of one parent share blocks, so the blocks
+ * stop being independent and a jackknife over them has no meaning.
+ * amc_set_bridge_blocks / amc_set_corr_blocks serve checkpoints: they restore the blocked accumulators from what the _blocks fetches
+ * gave (n_blocks = B of the partition, set beforehand with the same chunk), every block's records checked as amc_set_bridge /
+ * amc_set_corr check theirs and refused the same way; besides, a block without a local ladder must be all zero and the blocks with one
+ * share one column mask.  amc_set_bridge_blocks with records = NULL or n_snapshots = 0 clears.  Both are AMC_ERR_STATE without a
+ * partition; amc_set_bridge (with records) and amc_set_corr are AMC_ERR_STATE WITH one: the accumulator in use is then the blocked
+ * one, merged records cannot be split into its blocks, and taking them into the plain accumulator would drop them silently.
+ * Synchronisation: the calls above stay stream-ordered, with one exception -- when a blocked accumulator is (re)allocated the call
+ * waits for the stream first: amc_bridge_accumulate at its first use under a partition and after a change of B, amc_corr_mark /
+ * amc_corr_sample at the first mark and whenever the samples outgrow the room (slot 16, 32, 64, 128).  A graph capture or a timing
+ * loop should take one snapshot and as many samples as it will use beforehand.
+ * AMC_ERR_BAD_ARG: n_blocks outside {0} and [2, AMC_MAX_JK_BLOCKS], chunk < 0 or above AMC_MAX_JK_CHUNK, a capacity too small, a NULL argument. */
+#define AMC_MAX_JK_BLOCKS 64
+#define AMC_MAX_JK_CHUNK (1ll << 40)
+int  amc_set_blocks(amc_handle *h, int n_blocks, int64_t chunk);
+int  amc_bridge_fetch_blocks(amc_handle *h, double *records, int capacity_blocks, int *n_blocks, uint64_t *n_snapshots, int reset);
+int  amc_corr_fetch_blocks(amc_handle *h, double *records, uint64_t *steps, int capacity, int *n_blocks, int *n_samples, int *observable);
+int  amc_set_bridge_blocks(amc_handle *h, const double *records, int n_blocks, uint64_t n_snapshots);
+int  amc_set_corr_blocks(amc_handle *h, int observable, const double *origin, const double *records, const uint64_t *steps, int n_blocks,
+                         int n_samples);
+
 int  amc_sync(amc_handle *h);
 /* hipStream_t the handle launches on (for event timing / graph capture by the host). */
 int  amc_get_stream(amc_handle *h, void **stream);

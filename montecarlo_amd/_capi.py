@@ -36,6 +36,7 @@ AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_WF, AMC_BRIDGE_WB, AMC_BRIDGE_MF, AMC_BR
 # time correlation (include/amc.h): the observables, the slots of one mark, the columns of a record in their order
 AMC_CORR_E, AMC_CORR_X = 1, 2
 AMC_CORR_MAX_LAGS = 256
+AMC_MAX_JK_BLOCKS = 64          # blocks of a jackknife partition (amc_set_blocks)
 AMC_CORR_O, AMC_CORR_OO, AMC_CORR_AO, AMC_CORR_COLS = 0, 1, 2, 3
 CORR_OBSERVABLES = {"energy": AMC_CORR_E, "x": AMC_CORR_X}
 AMC_RESPACE_ACCEPTANCE, AMC_RESPACE_FLOW = 1, 2      # the rules of amc_respace_ladder (include/amc.h)
@@ -189,6 +190,11 @@ def load() -> C.CDLL:
         "amc_corr_download_origin": (C.c_int, [H, dp]),
         "amc_set_corr": (C.c_int, [H, C.c_int, dp, dp, u64p, C.c_int]),
         "amc_corr_clear": (C.c_int, [H]),
+        "amc_set_blocks": (C.c_int, [H, C.c_int, C.c_int64]),
+        "amc_bridge_fetch_blocks": (C.c_int, [H, dp, C.c_int, ip, u64p, C.c_int]),
+        "amc_corr_fetch_blocks": (C.c_int, [H, dp, u64p, C.c_int, ip, ip, ip]),
+        "amc_set_bridge_blocks": (C.c_int, [H, dp, C.c_int, C.c_uint64]),
+        "amc_set_corr_blocks": (C.c_int, [H, C.c_int, dp, dp, u64p, C.c_int, C.c_int]),
         "amc_set_tracking": (C.c_int, [H, C.c_int]),
         "amc_download_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
         "amc_upload_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
@@ -865,6 +871,58 @@ class HipEngine:
     def corr_clear(self) -> None:
         """Drop the mark (amc_corr_clear); the memory stays."""
         _check(self._lib.amc_corr_clear(self._h))
+
+    # -- jackknife blocks (include/amc.h; DESIGN.md section 3.16) ----------------
+    def set_blocks(self, n_blocks: int, chunk: int = 0) -> None:
+        """Keep the bridge sums and the time correlation per block of ladders, block of ladder l = (l_global div chunk) mod n_blocks
+        (amc_set_blocks); ``n_blocks`` 0 turns the partition off, ``chunk`` 0 asks for the default.  Clears the bridge accumulator and
+        the mark.  ``bridge_fetch`` / ``corr_fetch`` go on returning the merged records, bit for bit those of a handle without one."""
+        _check(self._lib.amc_set_blocks(self._h, int(n_blocks), int(chunk)))
+
+    def bridge_fetch_blocks(self, reset: bool = False):
+        """(records[B][R][6][AMC_XSUM_WORDS], n_snapshots) of this shard's blocked accumulator (amc_bridge_fetch_blocks); a block
+        without a local ladder is all zero.  Shards merge block by block (sharding.allreduce_xsum).  Synchronises."""
+        out = np.zeros((AMC_MAX_JK_BLOCKS, self._rungs(), 6, AMC_XSUM_WORDS), dtype=np.float64)
+        nb, count = C.c_int(0), C.c_uint64(0)
+        _check(self._lib.amc_bridge_fetch_blocks(self._h, _ptr(out), AMC_MAX_JK_BLOCKS, C.byref(nb), C.byref(count), int(bool(reset))))
+        return out[:nb.value].copy(), int(count.value)
+
+    def corr_fetch_blocks(self):
+        """(records[B][n_samples][G][3][AMC_XSUM_WORDS], steps[n_samples], observable) of this shard's blocked mark
+        (amc_corr_fetch_blocks).  Synchronises, resets nothing."""
+        nb, n, obs = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(self._lib.amc_corr_fetch_blocks(self._h, None, None, 0, C.byref(nb), C.byref(n), C.byref(obs)))      # the sizes alone
+        b, s = nb.value, n.value
+        out = np.zeros((b, max(s, 1), self._rungs(), AMC_CORR_COLS, AMC_XSUM_WORDS), dtype=np.float64)
+        steps = np.zeros(max(s, 1), dtype=np.uint64)
+        _check(self._lib.amc_corr_fetch_blocks(self._h, _ptr(out), _ptr(steps), s, C.byref(nb), C.byref(n), C.byref(obs)))
+        return out[:, :s].copy(), steps[:s].copy(), int(obs.value)
+
+    def set_bridge_blocks(self, records=None, n_snapshots: int = 0) -> None:
+        """Restore the blocked accumulator from ``bridge_fetch_blocks``'s records and count (amc_set_bridge_blocks; checkpoints);
+        ``None`` clears it.  The partition is set beforehand."""
+        if records is None:
+            _check(self._lib.amc_set_bridge_blocks(self._h, None, 0, 0))
+            return
+        rec = np.ascontiguousarray(records, dtype=np.float64)
+        per_block = self._rungs() * 6 * AMC_XSUM_WORDS
+        if rec.ndim < 1 or rec.shape[0] < 1 or rec.size != rec.shape[0] * per_block:
+            raise AmcError(f"set_bridge_blocks: {rec.size} doubles, the records of a block of {self._rungs()} rungs take {per_block}")
+        if int(n_snapshots) < 0:
+            raise AmcError("set_bridge_blocks: n_snapshots < 0")
+        _check(self._lib.amc_set_bridge_blocks(self._h, _ptr(rec), int(rec.shape[0]), int(n_snapshots)))
+
+    def set_corr_blocks(self, observable, origin, records, steps) -> None:
+        """Restore a blocked mark with its samples from ``corr_origin`` and ``corr_fetch_blocks`` (amc_set_corr_blocks; checkpoints)."""
+        g = self._rungs()
+        st = np.ascontiguousarray(steps, dtype=np.uint64)
+        rec = np.ascontiguousarray(records, dtype=np.float64)
+        org = np.ascontiguousarray(origin, dtype=np.float64)
+        if rec.ndim < 1 or rec.shape[0] < 1 or org.size != self.n_chains or rec.size != rec.shape[0] * st.size * g * AMC_CORR_COLS * AMC_XSUM_WORDS:
+            raise AmcError(f"set_corr_blocks: {org.size} origin values and {rec.size} doubles for {st.size} samples of {g} groups on "
+                           f"{self.n_chains} chains")
+        _check(self._lib.amc_set_corr_blocks(self._h, int(CORR_OBSERVABLES.get(observable, observable)), _ptr(org), _ptr(rec), _ptr(st),
+                                             int(rec.shape[0]), int(st.size)))
 
     # -- walker tracking (include/amc.h; DESIGN.md section 3.13 "Walker tracking") ----------------
     def set_tracking(self, on: bool = True) -> None:

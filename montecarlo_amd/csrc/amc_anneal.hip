@@ -48,6 +48,8 @@ int amc_anneal(amc_handle* h, double beta_new)
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_anneal: NULL handle");
     if (h->beta_arr) return fail(AMC_ERR_STATE, "amc_anneal: the handle has a per-chain beta array; population annealing cools one shared beta");
     if (h->lad.n_rungs) return fail(AMC_ERR_STATE, "amc_anneal: the handle has a ladder (amc_set_ladder)");
+    if (h->blocks.n_blocks)
+        return fail(AMC_ERR_STATE, "amc_anneal: a partition is set (amc_set_blocks); resampling makes copies of one parent share blocks, which are then not independent");
     if (h->offset != 0 || h->M != h->M_global)
         return fail(AMC_ERR_STATE, "amc_anneal: the handle holds chains [%lld, %lld) of %lld; resampling needs the whole ensemble on one handle",
                     (long long)h->offset, (long long)(h->offset + h->M), (long long)h->M_global);

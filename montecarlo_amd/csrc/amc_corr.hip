@@ -24,6 +24,26 @@ static int corr_room(amc_handle* h)
     return zeroed_words(h, &h->corr.d_corr, CORR_BYTES);
 }
 
+// The blocked accumulator (a partition is set): rows [sample][b][g][c], room for slot `slot` -- 16 samples at a mark, doubled when a
+// sample needs more (what the slots below it hold is kept), so that its size follows B, G and the lags in use.
+static inline size_t corr_block_sample_words(const amc_handle* h) { return (size_t)h->blocks.n_blocks * corr_sample_words(corr_groups(h)); }
+static int corr_blocks_room(amc_handle* h, int slot)
+{
+    const size_t spw = corr_block_sample_words(h);
+    if ((size_t)(slot + 1) * spw <= h->blocks.corr_blk_words) return AMC_OK;
+    const size_t need = (size_t)std::min<int>(AMC_CORR_MAX_LAGS, std::max(16, 2 * slot)) * spw;
+    amc::xs_word* grown = nullptr;
+    AMC_HIP(hipMalloc(&grown, need * sizeof(amc::xs_word)));
+    if (slot && h->blocks.d_corr_blk)
+        (void)hipMemcpyAsync(grown, h->blocks.d_corr_blk, (size_t)slot * spw * sizeof(amc::xs_word), hipMemcpyDeviceToDevice, h->stream);
+    const hipError_t e = hipStreamSynchronize(h->stream);      // (a finishing kernel queued earlier may still write the old rows)
+    (void)hipFree(h->blocks.d_corr_blk);
+    h->blocks.d_corr_blk = grown;
+    h->blocks.corr_blk_words = need;
+    AMC_HIP(e);
+    return AMC_OK;
+}
+
 // One pass into slot `slot`: the sums of the sample, and with `mark` the origin values too.
 static int corr_pass(amc_handle* h, int observable, int slot, bool mark)
 {
@@ -31,11 +51,24 @@ static int corr_pass(amc_handle* h, int observable, int slot, bool mark)
     // (as in front of a bridge snapshot: a learning step left pending belongs in front of this point of the stream)
     AMC_TRY(pg_resolve(h));
     RungPass p;
+    amc::CorrArgs a = {};
+    a.mark = mark ? 1 : 0;
+    if (h->blocks.n_blocks) {           // a row per (block, group, column): the traversal and the finishing kernel of amc_blocks.h
+        const int B = h->blocks.n_blocks;
+        AMC_TRY(blocks_pass_plan(h, amc::CORR_COLS, &p));
+        AMC_TRY(corr_room(h));
+        AMC_TRY(corr_blocks_room(h, slot));
+        a.origin = h->corr.d_origin;
+        AMC_TRY(blocks_pass_launch(h, p, a, observable, "amc::corr_sums_blocks_kernel", (const void*)amc::corr_sums_blocks_kernel<amc::POT_DOUBLE_WELL>,
+                                   (const void*)amc::corr_sums_blocks_kernel<amc::POT_HARMONIC>));
+        hipLaunchKernelGGL(amc::corr_finish_blocks_kernel, dim3(B * p.groups * amc::CORR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows,
+                           p.n_blocks(), p.groups, B, h->blocks.d_corr_blk + (size_t)slot * corr_block_sample_words(h));
+        AMC_HIP(hipGetLastError());
+        return AMC_OK;
+    }
     AMC_TRY(rung_pass_plan(h, amc::CORR_COLS, &p));
     AMC_TRY(corr_room(h));
-    amc::CorrArgs a = {};
     a.origin = h->corr.d_origin;
-    a.mark = mark ? 1 : 0;
     AMC_TRY(rung_pass_launch(h, p, a, observable, "amc::corr_sums_kernel", (const void*)amc::corr_sums_kernel<amc::POT_DOUBLE_WELL>,
                              (const void*)amc::corr_sums_kernel<amc::POT_HARMONIC>));
     hipLaunchKernelGGL(amc::corr_finish_kernel, dim3(p.groups * amc::CORR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows, p.n_blocks(),
@@ -78,10 +111,58 @@ int amc_corr_fetch(amc_handle* h, double* records, uint64_t* steps, int capacity
     if (capacity < n) return fail(AMC_ERR_BAD_ARG, "amc_corr_fetch: capacity = %d, the mark has %d samples", capacity, n);
     AMC_HIP(hipSetDevice(h->device));
     const size_t n_rows = (size_t)n * h->corr.groups * amc::CORR_COLS;
-    std::vector<amc::xs_word> host(n_rows * amc::XS_ROW_R + 1, 0ull);
-    AMC_TRY(copy_to_host_sync(h, host.data(), n ? h->corr.d_corr : nullptr, n_rows * amc::XS_ROW_R * sizeof(amc::xs_word)));
-    for (size_t s = 0; s < n_rows; ++s) amc::xs::rec_from_r(records + s * amc::xs::XS_WORDS, amc::xs_load_r_row(host.data() + s * amc::XS_ROW_R));
+    if (h->blocks.n_blocks && n) {      // the merge over the blocks: integers, the records of a handle without a partition
+        const int B = h->blocks.n_blocks;
+        const size_t per_sample = (size_t)h->corr.groups * amc::CORR_COLS;
+        std::vector<amc::xs_word> host(n_rows * B * amc::XS_ROW_R, 0ull);
+        AMC_TRY(copy_to_host_sync(h, host.data(), h->blocks.d_corr_blk, host.size() * sizeof(amc::xs_word)));
+        for (size_t s = 0; s < n_rows; ++s) {
+            const size_t slot = s / per_sample, gc = s % per_sample;
+            amc::xs::PartR p = amc::xs::part_r_empty();
+            for (int b = 0; b < B; ++b) amc::xs::part_r_merge(p, amc::xs_load_r_row(host.data() + ((slot * B + b) * per_sample + gc) * amc::XS_ROW_R));
+            amc::xs::rec_from_r(records + s * amc::xs::XS_WORDS, p);
+        }
+    } else {
+        std::vector<amc::xs_word> host(n_rows * amc::XS_ROW_R + 1, 0ull);
+        AMC_TRY(copy_to_host_sync(h, host.data(), n ? h->corr.d_corr : nullptr, n_rows * amc::XS_ROW_R * sizeof(amc::xs_word)));
+        for (size_t s = 0; s < n_rows; ++s) amc::xs::rec_from_r(records + s * amc::xs::XS_WORDS, amc::xs_load_r_row(host.data() + s * amc::XS_ROW_R));
+    }
     for (int s = 0; s < n; ++s) steps[s] = h->corr.steps[s];
+    *n_samples = n;
+    *observable = h->corr.observable;
+    return AMC_OK;
+}
+
+int amc_corr_fetch_blocks(amc_handle* h, double* records, uint64_t* steps, int capacity, int* n_blocks, int* n_samples, int* observable)
+{
+    if (!h || !n_blocks || !n_samples || !observable) return fail(AMC_ERR_BAD_ARG, "amc_corr_fetch_blocks: NULL argument");
+    const int B = h->blocks.n_blocks;
+    if (!B) return fail(AMC_ERR_STATE, "amc_corr_fetch_blocks: no partition is set (amc_set_blocks)");
+    const int n = h->corr.observable ? h->corr.n_samples : 0;
+    if (!records || !steps) {           // the sizes alone, for a caller about to allocate: nothing waits, nothing is copied
+        *n_blocks = B;
+        *n_samples = n;
+        *observable = h->corr.observable;
+        return AMC_OK;
+    }
+    if (capacity < n) return fail(AMC_ERR_BAD_ARG, "amc_corr_fetch_blocks: capacity = %d, the mark has %d samples", capacity, n);
+    AMC_HIP(hipSetDevice(h->device));
+    const int G = corr_groups(h);
+    const size_t per_sample = (size_t)G * amc::CORR_COLS;
+    std::vector<amc::xs_word> host((size_t)n * B * per_sample * amc::XS_ROW_R + 1, 0ull);
+    AMC_TRY(copy_to_host_sync(h, host.data(), n ? h->blocks.d_corr_blk : nullptr, (host.size() - 1) * sizeof(amc::xs_word)));
+    const amc::blk::Part part = blocks_part(h);
+    for (int b = 0; b < B; ++b) {
+        const bool empty = amc::blk::ladders_in_block(part, b, h->M / G) == 0;      // a block without a local ladder: all-zero records
+        for (int s = 0; s < n; ++s)
+            for (size_t gc = 0; gc < per_sample; ++gc) {
+                double* rec = records + (((size_t)b * n + s) * per_sample + gc) * amc::xs::XS_WORDS;
+                if (empty) amc::xs::rec_clear(rec);
+                else amc::xs::rec_from_r(rec, amc::xs_load_r_row(host.data() + (((size_t)s * B + b) * per_sample + gc) * amc::XS_ROW_R));
+            }
+    }
+    for (int s = 0; s < n; ++s) steps[s] = h->corr.steps[s];
+    *n_blocks = B;
     *n_samples = n;
     *observable = h->corr.observable;
     return AMC_OK;
@@ -95,40 +176,101 @@ int amc_corr_download_origin(amc_handle* h, double* origin)
     return copy_to_host_sync(h, origin, h->corr.d_origin, (size_t)h->M * sizeof(double));
 }
 
+// What amc_set_corr and amc_set_corr_blocks refuse alike: the observable, the number of samples, the steps.
+static int corr_set_check(const char* who, int observable, const uint64_t* steps, int n_samples)
+{
+    if (observable != AMC_CORR_E && observable != AMC_CORR_X)
+        return fail(AMC_ERR_BAD_ARG, "%s: observable = %d must be AMC_CORR_E or AMC_CORR_X", who, observable);
+    if (n_samples < 1 || n_samples > AMC_CORR_MAX_LAGS)
+        return fail(AMC_ERR_BAD_ARG, "%s: n_samples = %d must lie in [1, %d]", who, n_samples, AMC_CORR_MAX_LAGS);
+    for (int s = 0; s < n_samples; ++s) {
+        if (steps[s] >> 48) return fail(AMC_ERR_BAD_ARG, "%s: steps[%d] must fit 48 bits", who, s);
+        if (s && steps[s] < steps[s - 1]) return fail(AMC_ERR_BAD_ARG, "%s: steps[%d] = %llu lies before steps[%d]", who, s, (unsigned long long)steps[s], s - 1);
+    }
+    return AMC_OK;
+}
+
+// One record of a sample into its row: every (sample, group, column) had a summand, so each is a kind-R record, as amc_corr_fetch gave it.
+static int corr_row_from_record(const char* who, const double* rec, int slot, int g, int c, amc::xs_word* row)
+{
+    if (rec[0] != (double)amc::xs::XS_R || !(rec[1] >= amc::xs::XS_LMIN && rec[1] <= amc::xs::XS_LMAX) || rec[1] != std::floor(rec[1]) ||
+        !(rec[2] >= 0.0 && rec[2] <= 7.0) || rec[2] != std::floor(rec[2]))
+        return fail(AMC_ERR_BAD_ARG, "%s: record of sample %d, group %d, column %d is no kind-R record", who, slot, g, c);
+    for (int i = 3; i < amc::xs::XS_WORDS; ++i)
+        if (!(std::fabs(rec[i]) < 9007199254740992.0) || rec[i] != std::floor(rec[i]))
+            return fail(AMC_ERR_BAD_ARG, "%s: record of sample %d, group %d, column %d: word %d is no integer below 2^53", who, slot, g, c, i);
+    const amc::xs::PartR p = amc::xs::rec_to_r(rec);
+    row[0] = (amc::xs_word)(uint32_t)p.top | ((amc::xs_word)p.flags << 32);
+    row[1] = (amc::xs_word)p.k1.lo; row[2] = (amc::xs_word)p.k1.hi;
+    row[3] = (amc::xs_word)p.k2.lo; row[4] = (amc::xs_word)p.k2.hi;
+    return AMC_OK;
+}
+
 int amc_set_corr(amc_handle* h, int observable, const double* origin, const double* records, const uint64_t* steps, int n_samples)
 {
     if (!h || !origin || !records || !steps) return fail(AMC_ERR_BAD_ARG, "amc_set_corr: NULL argument");
-    if (observable != AMC_CORR_E && observable != AMC_CORR_X)
-        return fail(AMC_ERR_BAD_ARG, "amc_set_corr: observable = %d must be AMC_CORR_E or AMC_CORR_X", observable);
-    if (n_samples < 1 || n_samples > AMC_CORR_MAX_LAGS)
-        return fail(AMC_ERR_BAD_ARG, "amc_set_corr: n_samples = %d must lie in [1, %d]", n_samples, AMC_CORR_MAX_LAGS);
-    for (int s = 0; s < n_samples; ++s) {
-        if (steps[s] >> 48) return fail(AMC_ERR_BAD_ARG, "amc_set_corr: steps[%d] must fit 48 bits", s);
-        if (s && steps[s] < steps[s - 1]) return fail(AMC_ERR_BAD_ARG, "amc_set_corr: steps[%d] = %llu lies before steps[%d]", s, (unsigned long long)steps[s], s - 1);
-    }
-    // every (sample, group, column) had a summand: each record is a kind-R record, as amc_corr_fetch gave it
+    // (the accumulator in use is the blocked one, which merged records cannot fill: taking them would drop them silently)
+    if (h->blocks.n_blocks)
+        return fail(AMC_ERR_STATE, "amc_set_corr: a partition is set (amc_set_blocks): merged records cannot be split into its blocks, "
+                                   "amc_set_corr_blocks restores them");
+    AMC_TRY(corr_set_check("amc_set_corr", observable, steps, n_samples));
     const int G = corr_groups(h);
     const size_t n_rows = (size_t)n_samples * G * amc::CORR_COLS;
     std::vector<amc::xs_word> host(n_rows * amc::XS_ROW_R, 0ull);
-    for (size_t s = 0; s < n_rows; ++s) {
-        const double* rec = records + s * amc::xs::XS_WORDS;
-        const int slot = (int)(s / ((size_t)G * amc::CORR_COLS)), g = (int)(s / amc::CORR_COLS % G), c = (int)(s % amc::CORR_COLS);
-        if (rec[0] != (double)amc::xs::XS_R || !(rec[1] >= amc::xs::XS_LMIN && rec[1] <= amc::xs::XS_LMAX) || rec[1] != std::floor(rec[1]) ||
-            !(rec[2] >= 0.0 && rec[2] <= 7.0) || rec[2] != std::floor(rec[2]))
-            return fail(AMC_ERR_BAD_ARG, "amc_set_corr: record of sample %d, group %d, column %d is no kind-R record", slot, g, c);
-        for (int i = 3; i < amc::xs::XS_WORDS; ++i)
-            if (!(std::fabs(rec[i]) < 9007199254740992.0) || rec[i] != std::floor(rec[i]))
-                return fail(AMC_ERR_BAD_ARG, "amc_set_corr: record of sample %d, group %d, column %d: word %d is no integer below 2^53", slot, g, c, i);
-        const amc::xs::PartR p = amc::xs::rec_to_r(rec);
-        amc::xs_word* row = host.data() + s * amc::XS_ROW_R;
-        row[0] = (amc::xs_word)(uint32_t)p.top | ((amc::xs_word)p.flags << 32);
-        row[1] = (amc::xs_word)p.k1.lo; row[2] = (amc::xs_word)p.k1.hi;
-        row[3] = (amc::xs_word)p.k2.lo; row[4] = (amc::xs_word)p.k2.hi;
-    }
+    for (size_t s = 0; s < n_rows; ++s)
+        AMC_TRY(corr_row_from_record("amc_set_corr", records + s * amc::xs::XS_WORDS, (int)(s / ((size_t)G * amc::CORR_COLS)), (int)(s / amc::CORR_COLS % G),
+                                     (int)(s % amc::CORR_COLS), host.data() + s * amc::XS_ROW_R));
     AMC_HIP(hipSetDevice(h->device));
     AMC_TRY(corr_room(h));
     AMC_HIP(hipMemcpyAsync(h->corr.d_origin, origin, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
     AMC_TRY(copy_to_device_sync(h, h->corr.d_corr, host.data(), host.size() * sizeof(amc::xs_word)));      // the caller's buffers are only valid during the call
+    h->corr.observable = observable;
+    h->corr.groups = G;
+    h->corr.n_samples = n_samples;
+    for (int s = 0; s < n_samples; ++s) h->corr.steps[s] = steps[s];
+    return AMC_OK;
+}
+
+int amc_set_corr_blocks(amc_handle* h, int observable, const double* origin, const double* records, const uint64_t* steps, int n_blocks, int n_samples)
+{
+    if (!h || !origin || !records || !steps) return fail(AMC_ERR_BAD_ARG, "amc_set_corr_blocks: NULL argument");
+    const int B = h->blocks.n_blocks;
+    if (!B) return fail(AMC_ERR_STATE, "amc_set_corr_blocks: no partition is set (amc_set_blocks)");
+    if (n_blocks != B) return fail(AMC_ERR_BAD_ARG, "amc_set_corr_blocks: n_blocks = %d, the partition has %d blocks", n_blocks, B);
+    AMC_TRY(corr_set_check("amc_set_corr_blocks", observable, steps, n_samples));
+    // records[b][s][g][c] as amc_corr_fetch_blocks gave them, into the rows [s][b][g][c]; a block without a local ladder is all zero
+    const int G = corr_groups(h);
+    const size_t per_sample = (size_t)G * amc::CORR_COLS;
+    std::vector<amc::xs_word> host((size_t)n_samples * B * per_sample * amc::XS_ROW_R, 0ull);
+    const amc::blk::Part part = blocks_part(h);
+    for (int b = 0; b < B; ++b) {
+        const bool empty = amc::blk::ladders_in_block(part, b, h->M / G) == 0;
+        for (int s = 0; s < n_samples; ++s)
+            for (size_t gc = 0; gc < per_sample; ++gc) {
+                const double* rec = records + (((size_t)b * n_samples + s) * per_sample + gc) * amc::xs::XS_WORDS;
+                if (empty) {
+                    for (int i = 0; i < amc::xs::XS_WORDS; ++i)
+                        if (rec[i] != 0.0) return fail(AMC_ERR_BAD_ARG, "amc_set_corr_blocks: block %d has no local ladder, its records must be all zero", b);
+                    continue;
+                }
+                AMC_TRY(corr_row_from_record("amc_set_corr_blocks", rec, s, (int)(gc / amc::CORR_COLS), (int)(gc % amc::CORR_COLS),
+                                             host.data() + (((size_t)s * B + b) * per_sample + gc) * amc::XS_ROW_R));
+            }
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_TRY(corr_room(h));
+    if (host.size() > h->blocks.corr_blk_words) {       // (nothing the old rows hold is kept: corr_blocks_room would copy them)
+        const size_t need = (size_t)std::max(16, n_samples) * corr_block_sample_words(h);
+        amc::xs_word* rows = nullptr;
+        AMC_HIP(hipMalloc(&rows, need * sizeof(amc::xs_word)));
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        (void)hipFree(h->blocks.d_corr_blk);
+        h->blocks.d_corr_blk = rows;
+        h->blocks.corr_blk_words = need;
+        AMC_HIP(e);
+    }
+    AMC_HIP(hipMemcpyAsync(h->corr.d_origin, origin, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    AMC_TRY(copy_to_device_sync(h, h->blocks.d_corr_blk, host.data(), host.size() * sizeof(amc::xs_word)));      // the caller's buffers are only valid during the call
     h->corr.observable = observable;
     h->corr.groups = G;
     h->corr.n_samples = n_samples;

@@ -74,6 +74,7 @@ static const size_t BRIDGE_BYTES = amc::BRIDGE_WORDS * sizeof(amc::xs_word);    
 static int bridge_clear(amc_handle* h)
 {
     if (h->lad.d_bridge) AMC_HIP(hipMemsetAsync(h->lad.d_bridge, 0, BRIDGE_BYTES, h->stream));
+    if (h->blocks.d_bridge_blk) AMC_HIP(hipMemsetAsync(h->blocks.d_bridge_blk, 0, h->blocks.bridge_blk_words * sizeof(amc::xs_word), h->stream));
     h->lad.bridge_cols = 0;
     return AMC_OK;
 }
@@ -88,6 +89,8 @@ static int ladder_reset(amc_handle* h)
     AMC_TRY(tune_reset(h, true));
     AMC_TRY(bridge_clear(h));
     corr_forget(h);                 // (no ladder state, but its groups are the rungs: the chains' slots mean something else now)
+    h->blocks.n_blocks = 0;         // (the jackknife partition counts ladders: another R has other ladders)
+    h->blocks.chunk = 0;
     h->lad.rung_on = false;
     return AMC_OK;
 }
@@ -115,6 +118,28 @@ int rung_pass_plan(amc_handle* h, int n_cols, RungPass* p)
     p->n_launches = (h->M / R + p->per_launch - 1) / p->per_launch;
     p->slot_words = (size_t)R * (size_t)n_cols * amc::XS_ROW_R;
     return rung_rows_room(h, (size_t)p->n_launches * (size_t)p->grid * p->slot_words);
+}
+
+// ... of a handle with a partition (blocks_pass_launch, amc_internal.h): the same grid rounded up to a multiple of B.
+int blocks_pass_plan(amc_handle* h, int n_cols, RungPass* p)
+{
+    const int R = blocks_groups(h);
+    p->groups = R;
+    p->grid = amc::blk::grid_round(grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU), h->blocks.n_blocks);
+    p->per_launch = amc::blk::ladders_per_launch(h->M / R, h->blocks.n_blocks, h->blocks.chunk, R, p->grid, AMC_BLOCK, amc::xs::XS_LANE_CAP - 2);
+    p->n_launches = (h->M / R + p->per_launch - 1) / p->per_launch;
+    p->slot_words = (size_t)R * (size_t)n_cols * amc::XS_ROW_R;
+    return rung_rows_room(h, (size_t)p->n_launches * (size_t)p->grid * p->slot_words);
+}
+
+// The blocked accumulator of the bridge sums on the host: the rows [b][r][c], then the number of snapshots (all zero while nothing has
+// been accumulated since the partition was set).  Waits for the stream.
+static int bridge_blocks_host(amc_handle* h, std::vector<amc::xs_word>* rows)
+{
+    const size_t words = (size_t)h->blocks.n_blocks * h->lad.n_rungs * amc::BR_COLS * amc::XS_ROW_R + 1;
+    rows->assign(words, 0ull);
+    const bool have = h->blocks.d_bridge_blk && h->blocks.bridge_blk_words == words;
+    return copy_to_host_sync(h, rows->data(), have ? h->blocks.d_bridge_blk : nullptr, words * sizeof(amc::xs_word));
 }
 
 // One exchange step on the stream: the gaps r with r mod 2 == t_x mod 2 of every local ladder.  A parity without gaps (R = 2, odd
@@ -341,10 +366,22 @@ int amc_bridge_accumulate(amc_handle* h, int columns)
     // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
     AMC_TRY(pg_resolve(h));
     RungPass p;
-    AMC_TRY(rung_pass_plan(h, amc::BR_COLS, &p));
-    AMC_TRY(zeroed_words(h, &h->lad.d_bridge, BRIDGE_BYTES));
     amc::BridgeArgs a = {};
     a.beta = h->d_beta;
+    if (h->blocks.n_blocks) {           // a row per (block, rung, column): the traversal and the finishing kernel of amc_blocks.h
+        const int B = h->blocks.n_blocks, n_slots = h->lad.n_rungs * amc::BR_COLS;
+        AMC_TRY(blocks_pass_plan(h, amc::BR_COLS, &p));
+        AMC_TRY(blocks_words(h, &h->blocks.d_bridge_blk, &h->blocks.bridge_blk_words, (size_t)B * n_slots * amc::XS_ROW_R + 1));
+        AMC_TRY(blocks_pass_launch(h, p, a, columns, "amc::bridge_sums_blocks_kernel", (const void*)amc::bridge_sums_blocks_kernel<amc::POT_DOUBLE_WELL>,
+                                   (const void*)amc::bridge_sums_blocks_kernel<amc::POT_HARMONIC>));
+        hipLaunchKernelGGL(amc::bridge_finish_blocks_kernel, dim3(B * n_slots), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows, p.n_blocks(),
+                           h->lad.n_rungs, columns, B, h->blocks.d_bridge_blk);
+        AMC_HIP(hipGetLastError());
+        h->lad.bridge_cols = columns;
+        return AMC_OK;
+    }
+    AMC_TRY(rung_pass_plan(h, amc::BR_COLS, &p));
+    AMC_TRY(zeroed_words(h, &h->lad.d_bridge, BRIDGE_BYTES));
     AMC_TRY(rung_pass_launch(h, p, a, columns, "amc::bridge_sums_kernel", (const void*)amc::bridge_sums_kernel<amc::POT_DOUBLE_WELL>,
                              (const void*)amc::bridge_sums_kernel<amc::POT_HARMONIC>));
     const int R = h->lad.n_rungs;
@@ -361,6 +398,26 @@ int amc_bridge_fetch(amc_handle* h, double* records, uint64_t* n_snapshots, int 
     AMC_TRY(need_ladder(h, "amc_bridge_fetch"));
     AMC_HIP(hipSetDevice(h->device));
     const int R = h->lad.n_rungs, n_slots = R * amc::BR_COLS;
+    if (h->blocks.n_blocks) {           // the merge over the blocks: integers, the records of a handle without a partition
+        std::vector<amc::xs_word> rows;
+        AMC_TRY(bridge_blocks_host(h, &rows));
+        *n_snapshots = (uint64_t)rows.back();
+        for (int s = 0; s < n_slots; ++s) {
+            amc::xs::PartR p = amc::xs::part_r_empty();
+            bool any = false;
+            for (int b = 0; b < h->blocks.n_blocks; ++b) {
+                const amc::xs_word* row = rows.data() + ((size_t)b * n_slots + s) * amc::XS_ROW_R;
+                if (!row[5]) continue;
+                any = true;
+                amc::xs::part_r_merge(p, amc::xs_load_r_row(row));
+            }
+            double* rec = records + (size_t)s * amc::xs::XS_WORDS;
+            if (any) amc::xs::rec_from_r(rec, p);
+            else amc::xs::rec_clear(rec);
+        }
+        if (reset) return bridge_clear(h);
+        return AMC_OK;
+    }
     std::vector<amc::xs_word> host(amc::BRIDGE_WORDS, 0ull);
     AMC_TRY(copy_to_host_sync(h, host.data(), h->lad.d_bridge, BRIDGE_BYTES));
     *n_snapshots = (uint64_t)host[amc::BRIDGE_COUNT];
@@ -374,16 +431,13 @@ int amc_bridge_fetch(amc_handle* h, double* records, uint64_t* n_snapshots, int 
     return AMC_OK;
 }
 
-int amc_set_bridge(amc_handle* h, const double* records, uint64_t n_snapshots)
+// The rows of one accumulator's records (amc_bridge_fetch's layout, R x BR_COLS of them) as amc_set_bridge checks them; *cols: the mask
+// read off them, 0 when every record is all zero.  The mask is read off the records: a slot that had a summand is a kind-R record, every
+// other is all zero, and a column is in the mask exactly when its interior slots are records (E and EE have a summand at every rung, the
+// W and M columns at all but one end).
+static int bridge_rows_from_records(const char* who, const double* records, int R, amc::xs_word* rows, int* cols_out)
 {
-    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: NULL handle");
-    AMC_TRY(need_ladder(h, "amc_set_bridge"));
-    AMC_HIP(hipSetDevice(h->device));
-    if (!records || n_snapshots == 0) return bridge_clear(h);
-    // The mask is read off the records: a slot that had a summand is a kind-R record, every other is all zero, and a column is in the
-    // mask exactly when its interior slots are records (E and EE have a summand at every rung, the W and M columns at all but one end).
-    const int R = h->lad.n_rungs, n_slots = R * amc::BR_COLS;
-    std::vector<amc::xs_word> host(amc::BRIDGE_WORDS, 0ull);
+    const int n_slots = R * amc::BR_COLS;
     int cols = 0;
     for (int s = 0; s < n_slots; ++s) {
         const double* rec = records + (size_t)s * amc::xs::XS_WORDS;
@@ -392,27 +446,126 @@ int amc_set_bridge(amc_handle* h, const double* records, uint64_t n_snapshots)
         for (int i = 0; i < amc::xs::XS_WORDS; ++i) zero = zero && rec[i] == 0.0;
         if (zero) continue;
         if (rec[0] != (double)amc::xs::XS_R || !(rec[1] >= amc::xs::XS_LMIN && rec[1] <= amc::xs::XS_LMAX) || !(rec[2] >= 0.0 && rec[2] <= 7.0))
-            return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: record of rung %d, column %d is no kind-R record", r, c);
+            return fail(AMC_ERR_BAD_ARG, "%s: record of rung %d, column %d is no kind-R record", who, r, c);
         for (int i = 3; i < amc::xs::XS_WORDS; ++i)
             if (!(std::fabs(rec[i]) < 9007199254740992.0) || rec[i] != std::floor(rec[i]))
-                return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: record of rung %d, column %d: word %d is no integer below 2^53", r, c, i);
+                return fail(AMC_ERR_BAD_ARG, "%s: record of rung %d, column %d: word %d is no integer below 2^53", who, r, c, i);
         if (!((amc::bridge_cols_at(AMC_BRIDGE_ALL, r, R) >> c) & 1))
-            return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: rung %d has no summand for column %d, its record must be all zero", r, c);
+            return fail(AMC_ERR_BAD_ARG, "%s: rung %d has no summand for column %d, its record must be all zero", who, r, c);
         cols |= 1 << c;
         amc::xs::PartR p = amc::xs::rec_to_r(rec);
-        amc::xs_word* row = host.data() + (size_t)s * amc::XS_ROW_R;
+        amc::xs_word* row = rows + (size_t)s * amc::XS_ROW_R;
         row[0] = (amc::xs_word)(uint32_t)p.top | ((amc::xs_word)p.flags << 32);
         row[1] = (amc::xs_word)p.k1.lo; row[2] = (amc::xs_word)p.k1.hi;
         row[3] = (amc::xs_word)p.k2.lo; row[4] = (amc::xs_word)p.k2.hi;
         row[5] = 1ull;
     }
+    for (int s = 0; cols && s < n_slots; ++s)
+        if (((amc::bridge_cols_at(cols, s / amc::BR_COLS, R) >> (s % amc::BR_COLS)) & 1) && !rows[(size_t)s * amc::XS_ROW_R + 5])
+            return fail(AMC_ERR_BAD_ARG, "%s: column %d has records at some rungs and none at rung %d", who, s % amc::BR_COLS, s / amc::BR_COLS);
+    *cols_out = cols;
+    return AMC_OK;
+}
+
+int amc_set_bridge(amc_handle* h, const double* records, uint64_t n_snapshots)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: NULL handle");
+    AMC_TRY(need_ladder(h, "amc_set_bridge"));
+    AMC_HIP(hipSetDevice(h->device));
+    if (!records || n_snapshots == 0) return bridge_clear(h);
+    // (the accumulator in use is the blocked one, which merged records cannot fill: taking them would drop them silently)
+    if (h->blocks.n_blocks)
+        return fail(AMC_ERR_STATE, "amc_set_bridge: a partition is set (amc_set_blocks): merged records cannot be split into its blocks, "
+                                   "amc_set_bridge_blocks restores them");
+    std::vector<amc::xs_word> host(amc::BRIDGE_WORDS, 0ull);
+    int cols = 0;
+    AMC_TRY(bridge_rows_from_records("amc_set_bridge", records, h->lad.n_rungs, host.data(), &cols));
     if (!cols) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: n_snapshots = %llu with all-zero records", (unsigned long long)n_snapshots);
-    for (int s = 0; s < n_slots; ++s)
-        if (((amc::bridge_cols_at(cols, s / amc::BR_COLS, R) >> (s % amc::BR_COLS)) & 1) && !host[(size_t)s * amc::XS_ROW_R + 5])
-            return fail(AMC_ERR_BAD_ARG, "amc_set_bridge: column %d has records at some rungs and none at rung %d", s % amc::BR_COLS, s / amc::BR_COLS);
     host[amc::BRIDGE_COUNT] = (amc::xs_word)n_snapshots;
     if (!h->lad.d_bridge) AMC_HIP(hipMalloc(&h->lad.d_bridge, BRIDGE_BYTES));
     AMC_TRY(copy_to_device_sync(h, h->lad.d_bridge, host.data(), BRIDGE_BYTES));      // `host` is only valid during the call
+    h->lad.bridge_cols = cols;
+    return AMC_OK;
+}
+
+// ---- jackknife blocks --------------------------------------------------------------------------------------
+static_assert(AMC_MAX_JK_BLOCKS == amc::blk::BLK_MAX_BLOCKS, "the blocks of include/amc.h and amc_blocks.h");
+
+int amc_set_blocks(amc_handle* h, int n_blocks, int64_t chunk)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_blocks: NULL handle");
+    if (n_blocks != 0 && (n_blocks < 2 || n_blocks > AMC_MAX_JK_BLOCKS))
+        return fail(AMC_ERR_BAD_ARG, "amc_set_blocks: n_blocks = %d must be 0 (no partition) or lie in [2, %d]", n_blocks, AMC_MAX_JK_BLOCKS);
+    if (chunk < 0 || chunk > AMC_MAX_JK_CHUNK)      // (the traversal adds a chunk to a global ladder index: both stay far from 2^63)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_blocks: chunk = %lld must lie in [1, 2^40], or be 0 for the default", (long long)chunk);
+    AMC_HIP(hipSetDevice(h->device));
+    // one full block-width of contiguous chains: every lane of a HIP block has a ladder of the chunk, in one trip
+    if (n_blocks && chunk == 0) chunk = std::max(1, AMC_BLOCK / blocks_groups(h));
+    h->blocks.n_blocks = n_blocks;
+    h->blocks.chunk = n_blocks ? chunk : 0;
+    // sums kept under another partition (or under none) are not sums of these blocks
+    AMC_TRY(bridge_clear(h));
+    corr_forget(h);
+    return AMC_OK;
+}
+
+int amc_bridge_fetch_blocks(amc_handle* h, double* records, int capacity_blocks, int* n_blocks, uint64_t* n_snapshots, int reset)
+{
+    if (!h || !records || !n_blocks || !n_snapshots) return fail(AMC_ERR_BAD_ARG, "amc_bridge_fetch_blocks: NULL argument");
+    AMC_TRY(need_ladder(h, "amc_bridge_fetch_blocks"));
+    const int B = h->blocks.n_blocks;
+    if (!B) return fail(AMC_ERR_STATE, "amc_bridge_fetch_blocks: no partition is set (amc_set_blocks)");
+    if (capacity_blocks < B) return fail(AMC_ERR_BAD_ARG, "amc_bridge_fetch_blocks: capacity_blocks = %d, the partition has %d blocks", capacity_blocks, B);
+    AMC_HIP(hipSetDevice(h->device));
+    const int R = h->lad.n_rungs, n_slots = R * amc::BR_COLS;
+    std::vector<amc::xs_word> rows;
+    AMC_TRY(bridge_blocks_host(h, &rows));
+    const amc::blk::Part part = blocks_part(h);
+    for (int b = 0; b < B; ++b) {
+        const bool empty = amc::blk::ladders_in_block(part, b, h->M / R) == 0;      // a block without a local ladder: all-zero records
+        for (int s = 0; s < n_slots; ++s) {
+            double* rec = records + ((size_t)b * n_slots + s) * amc::xs::XS_WORDS;
+            const amc::xs_word* row = rows.data() + ((size_t)b * n_slots + s) * amc::XS_ROW_R;
+            if (!empty && row[5]) amc::xs::rec_from_r(rec, amc::xs_load_r_row(row));
+            else amc::xs::rec_clear(rec);
+        }
+    }
+    *n_blocks = B;
+    *n_snapshots = (uint64_t)rows.back();
+    if (reset) return bridge_clear(h);
+    return AMC_OK;
+}
+
+int amc_set_bridge_blocks(amc_handle* h, const double* records, int n_blocks, uint64_t n_snapshots)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge_blocks: NULL handle");
+    AMC_TRY(need_ladder(h, "amc_set_bridge_blocks"));
+    const int B = h->blocks.n_blocks;
+    if (!B) return fail(AMC_ERR_STATE, "amc_set_bridge_blocks: no partition is set (amc_set_blocks)");
+    AMC_HIP(hipSetDevice(h->device));
+    if (!records || n_snapshots == 0) return bridge_clear(h);
+    if (n_blocks != B) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge_blocks: n_blocks = %d, the partition has %d blocks", n_blocks, B);
+    // every block's records as amc_set_bridge checks one accumulator's; the blocks with a local ladder share one mask, the others are all zero
+    const int R = h->lad.n_rungs, n_slots = R * amc::BR_COLS;
+    const size_t words = (size_t)B * n_slots * amc::XS_ROW_R + 1;
+    std::vector<amc::xs_word> host(words, 0ull);
+    const amc::blk::Part part = blocks_part(h);
+    int cols = 0;
+    for (int b = 0; b < B; ++b) {
+        int cols_b = 0;
+        AMC_TRY(bridge_rows_from_records("amc_set_bridge_blocks", records + (size_t)b * n_slots * amc::xs::XS_WORDS, R,
+                                         host.data() + (size_t)b * n_slots * amc::XS_ROW_R, &cols_b));
+        if (amc::blk::ladders_in_block(part, b, h->M / R) == 0) {
+            if (cols_b) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge_blocks: block %d has no local ladder, its records must be all zero", b);
+            continue;
+        }
+        if (!cols_b) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge_blocks: n_snapshots = %llu with all-zero records in block %d", (unsigned long long)n_snapshots, b);
+        if (cols && cols_b != cols) return fail(AMC_ERR_BAD_ARG, "amc_set_bridge_blocks: block %d holds the columns %d, the blocks below it %d", b, cols_b, cols);
+        cols = cols_b;
+    }
+    host[words - 1] = (amc::xs_word)n_snapshots;
+    AMC_TRY(blocks_words(h, &h->blocks.d_bridge_blk, &h->blocks.bridge_blk_words, words));
+    AMC_TRY(copy_to_device_sync(h, h->blocks.d_bridge_blk, host.data(), words * sizeof(amc::xs_word)));      // `host` is only valid during the call
     h->lad.bridge_cols = cols;
     return AMC_OK;
 }
@@ -569,6 +722,10 @@ int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const 
     a.rec = h->lad.d_respace;
     a.bridge = h->lad.d_bridge;
     a.bridge_words = amc::BRIDGE_WORDS;
+    if (h->blocks.n_blocks) {           // the accumulator in use is the blocked one: every block's rows go
+        a.bridge = h->blocks.d_bridge_blk;
+        a.bridge_words = (int32_t)h->blocks.bridge_blk_words;
+    }
     a.gamma = gamma;
     a.eps = eps;
     a.rule = rule;

@@ -11,7 +11,8 @@
 //                       tuning the widths: amc_tune_rung_sigma .., the window of the acceptance per rung: amc_rung_window_*)
 //   amc_anneal.hip      population annealing (amc_anneal, its record log, the annealing step index, amc_get_beta, the families:
 //                       amc_set_anneal_families .. amc_upload_families; amc_anneal_next_beta)
-//   amc_corr.hip        time correlation from one time origin (amc_corr_mark .. amc_corr_clear)
+//   amc_corr.hip        time correlation from one time origin (amc_corr_mark .. amc_corr_clear; per jackknife block: amc_corr_fetch_blocks;
+//                       the partition itself, amc_set_blocks, and amc_bridge_fetch_blocks are with the bridge sums in amc_exchange.hip)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -254,6 +255,23 @@ static inline void corr_release(CorrState& s)
     (void)hipFree(s.d_corr);
 }
 
+// Jackknife blocks (amc_set_blocks): the partition and the blocked accumulators of the bridge sums and of the
+// time correlation, each allocated at its first use for the B and G at hand -- a handle that never sets a partition has neither and
+// launches what it always did.  A partition is set exactly while n_blocks != 0.
+struct BlocksState {
+    int n_blocks = 0;                           // B; 0: no partition
+    int64_t chunk = 0;                          // C
+    amc::xs_word* d_bridge_blk = nullptr;       // [B][R][BR_COLS][XS_ROW_R] rows, then the number of snapshots (amc_blocks.h)
+    size_t bridge_blk_words = 0;                //   the words it holds
+    amc::xs_word* d_corr_blk = nullptr;         // [samples][B][G][CORR_COLS][XS_ROW_R]
+    size_t corr_blk_words = 0;
+};
+static inline void blocks_release(BlocksState& s)
+{
+    (void)hipFree(s.d_bridge_blk);
+    (void)hipFree(s.d_corr_blk);
+}
+
 struct amc_handle {
     AmcKnobs knobs;             // the environment's knobs as amc_create found them
     int device = 0;
@@ -271,6 +289,7 @@ struct amc_handle {
     LadderState lad;            // the temperature ladder and what hangs on it (amc_exchange.hip)
     AnnealState ann;            // population annealing (amc_anneal.hip)
     CorrState corr;             // time correlation (amc_corr.hip)
+    BlocksState blocks;         // jackknife blocks of the bridge sums and the time correlation (amc_exchange.hip, amc_corr.hip)
     double* d_x = nullptr;
     double* d_beta = nullptr;
     uint32_t* d_acc = nullptr;
@@ -492,5 +511,49 @@ static inline int rung_pass_launch(amc_handle* h, const RungPass& p, Args a, int
         void* params[] = {&a};
         AMC_TRY(launch_by_potential(h, name, double_well, harmonic, p.grid, params));
     }
+    return AMC_OK;
+}
+
+// The same for a handle with a partition (amc_set_blocks): the pass in the traversal of amc_blocks.h -- a grid that is a multiple of B,
+// HIP block k serving jackknife block k mod B --, split into launches by ladder ranges that keep every lane within XS_LANE_CAP - 2
+// summands (blk::ladders_per_launch).  The kernels take the partition as their second argument.
+static inline int blocks_groups(const amc_handle* h) { return h->lad.n_rungs ? h->lad.n_rungs : 1; }
+static inline amc::blk::Part blocks_part(const amc_handle* h)
+{
+    amc::blk::Part part = {};
+    part.l_first = h->offset / blocks_groups(h);
+    part.chunk = h->blocks.chunk;
+    part.n_blocks = h->blocks.n_blocks;
+    return part;
+}
+AMC_INTERNAL int blocks_pass_plan(amc_handle* h, int n_cols, RungPass* p);      // amc_exchange.hip
+template <class Args>
+static inline int blocks_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
+{
+    const int64_t n_ladders = h->M / p.groups;
+    amc::blk::Part part = blocks_part(h);
+    a.x = h->d_x;
+    a.n_rungs = p.groups;
+    a.cols = columns;
+    for (int64_t i = 0; i < p.n_launches; ++i) {
+        a.rows = h->lad.d_rung_rows + (size_t)i * (size_t)p.grid * p.slot_words;
+        a.l_begin = i * p.per_launch;
+        a.l_end = std::min(n_ladders, (i + 1) * p.per_launch);
+        void* params[] = {&a, &part};
+        AMC_TRY(launch_by_potential(h, name, double_well, harmonic, p.grid, params));
+    }
+    return AMC_OK;
+}
+// *p holds exactly `need` words, zeroed on the stream when it is (re)allocated: the blocked accumulators follow B and G at their first use
+static inline int blocks_words(amc_handle* h, amc::xs_word** p, size_t* have, size_t need)
+{
+    if (*p && *have == need) return AMC_OK;
+    AMC_HIP(hipStreamSynchronize(h->stream));
+    (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    AMC_HIP(hipMalloc(p, need * sizeof(amc::xs_word)));
+    *have = need;
+    AMC_HIP(hipMemsetAsync(*p, 0, need * sizeof(amc::xs_word), h->stream));
     return AMC_OK;
 }

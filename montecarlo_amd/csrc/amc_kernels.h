@@ -24,6 +24,7 @@
 //   amc_anneal.h       population annealing: log-weights, integer weights, the three-launch prefix, the gather, the families
 //   amc_anneal_search.h  population annealing: the next beta from a target on the effective-sample fraction (energies, sums, decision)
 //   amc_corr.h         time correlation from one time origin: the sums of O, O^2, a O by group, one slot per lag
+//   amc_blocks.h       jackknife blocks: the bridge sums and the time correlation per block of ladders, the traversal's index arithmetic
 #pragma once
 
 #include "amc_model.h"
@@ -38,3 +39,4 @@
 #include "amc_anneal.h"
 #include "amc_anneal_search.h"
 #include "amc_corr.h"
+#include "amc_blocks.h"

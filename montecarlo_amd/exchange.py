@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import sharding
+from . import jackknife, sharding
 from ._capi import (AMC_BRIDGE_ALL, AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_MB, AMC_BRIDGE_MF, AMC_BRIDGE_WB, AMC_BRIDGE_WF, AMC_MAX_MOVES,
                     AMC_RED_HEADER, AMC_REDUCE_ALL, AMC_REDUCE_E, AMC_REDUCE_X, AMC_REDUCE_XX, AMC_XSUM_WORDS, xsum_round)
 from .metropolis import Metropolis
@@ -43,13 +43,18 @@ class ReplicaExchange(AriannaAlgorithm):
 
     ``bridge``: False, True (the acceptance set E | EE | MF | MB, what the default estimators read) or a mask of AMC_BRIDGE_* bits;
     after every ``bridge_every``-th exchange step one snapshot of the bridge sums is queued behind it (nothing synchronises), and a
-    fused stretch is cut at those steps, so fused and stepwise runs accumulate the same records."""
+    fused stretch is cut at those steps, so fused and stepwise runs accumulate the same records.
+
+    ``blocks=B`` (2..64) keeps the bridge sums per block of ladders, block of ladder l = (l div block_chunk) mod B (DESIGN.md section
+    3.16; ``block_chunk`` None: max(1, 256 div R) ladders), and ``log_z_ratios`` / ``log_z`` / ``heat_capacity`` take ``error=True``:
+    (value, se), se from the delete-one-block jackknife over the B blocks.  The values themselves do not change by a bit."""
 
     BRIDGE_DEFAULT = AMC_BRIDGE_E | AMC_BRIDGE_EE | AMC_BRIDGE_MF | AMC_BRIDGE_MB
 
     mutates_chains = True          # a callback due behind it at the same t observes the state AFTER the swaps (simulation._observed_next)
 
-    def __init__(self, chains, dependencies=None, n_rungs=None, path=None, track=False, bridge=False, bridge_every=1, **extras):
+    def __init__(self, chains, dependencies=None, n_rungs=None, path=None, track=False, bridge=False, bridge_every=1, blocks=None,
+                 block_chunk=None, **extras):
         assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
         self.metropolis: Metropolis = dependencies[0]
         if n_rungs is None:
@@ -70,10 +75,16 @@ class ReplicaExchange(AriannaAlgorithm):
             raise ValueError(f"ReplicaExchange: bridge_every = {bridge_every!r} must be an integer >= 1")
         self.bridge_every = int(bridge_every)
         self.metropolis.bridge = self.bridge           # (storage.checkpoint: the accumulator is state while the bridge is on)
+        self.blocks = jackknife.check_blocks("ReplicaExchange", blocks, block_chunk, len(chains) // self.n_rungs, self.n_rungs)
+        if self.blocks:                                # (storage.checkpoint: the records per block are state; an Autocorrelation shares them)
+            jackknife.ask_blocks("ReplicaExchange", self.metropolis, self.blocks)
         self.rank, _ = sharding.world()
 
     def initialise(self, simulation: Simulation) -> None:
         self.metropolis.set_ladder(self.n_rungs)       # (the per-chain beta array is on the device by now: Metropolis comes first)
+        if self.blocks:
+            jackknife.refuse_annealing("ReplicaExchange", simulation)
+            jackknife.use_blocks(self.metropolis, self.blocks)
         if self.track and not self.metropolis.tracking:     # (on already: storage.restore brought the labels back)
             self.metropolis.engine.set_tracking(True)
             self.metropolis.tracking = True
@@ -153,6 +164,12 @@ class ReplicaExchange(AriannaAlgorithm):
         if columns & ~self.bridge:
             raise ValueError(f"{what} reads bridge columns {columns & ~self.bridge} that the mask bridge = {self.bridge} leaves out")
 
+    def _same_snapshots(self, what: str, n: int) -> None:
+        """Every shard holds ``n`` snapshots: the means divide by n times the global ladders."""
+        counts = sharding.allreduce_sum(np.array([float(n), float(n) * float(n), 1.0]), self.metropolis.engine)
+        if counts[0] != n * counts[2] or counts[1] != float(n) * float(n) * counts[2]:
+            raise RuntimeError(f"{what}: this shard holds {n} snapshots, the shards' mean is {counts[0] / counts[2]}")
+
     def bridge_sums(self):
         """(sums, n_snapshots): the accumulated bridge sums over the ladders of ALL shards, an array of shape (R, 6) in the column
         order E, EE, WF, WB, MF, MB -- NaN where a column is outside the mask or a rung has no such summand (WF, MF at rung R - 1, WB, MB
@@ -163,9 +180,7 @@ class ReplicaExchange(AriannaAlgorithm):
             raise ValueError("ReplicaExchange.bridge_sums needs the bridge sums: build the ReplicaExchange with bridge=True")
         eng = self.metropolis.engine
         rec, n = eng.bridge_fetch(reset=False)
-        counts = sharding.allreduce_sum(np.array([float(n), float(n) * float(n), 1.0]), eng)
-        if counts[0] != n * counts[2] or counts[1] != float(n) * float(n) * counts[2]:
-            raise RuntimeError(f"ReplicaExchange.bridge_sums: this shard holds {n} snapshots, the shards' mean is {counts[0] / counts[2]}")
+        self._same_snapshots("ReplicaExchange.bridge_sums", n)
         rec = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, AMC_XSUM_WORDS)
         merged = np.concatenate([sharding.allreduce_xsum(rec[i:i + XSUM_CHUNK], eng).reshape(-1, AMC_XSUM_WORDS)
                                  for i in range(0, rec.shape[0], XSUM_CHUNK)])
@@ -180,7 +195,39 @@ class ReplicaExchange(AriannaAlgorithm):
         with np.errstate(invalid="ignore", divide="ignore"):
             return sums, sums / (float(n) * float(len(self.metropolis.chains) // self.n_rungs))
 
-    def log_z_ratios(self, method: str = "acceptance") -> np.ndarray:
+    def _merged(self, rec) -> np.ndarray:
+        """Records merged over the shards, XSUM_CHUNK of them per all-reduce (rung_sums)."""
+        eng = self.metropolis.engine
+        flat = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, AMC_XSUM_WORDS)
+        return np.concatenate([sharding.allreduce_xsum(flat[i:i + XSUM_CHUNK], eng).reshape(-1, AMC_XSUM_WORDS)
+                               for i in range(0, flat.shape[0], XSUM_CHUNK)]).reshape(np.shape(rec))
+
+    def bridge_blocks(self):
+        """(records[B][R][6][AMC_XSUM_WORDS], n_snapshots, ladders[B]): the accumulated bridge sums per jackknife block over ALL
+        shards -- the shards' records merged block by block -- and the ladders of every block.  Needs ``blocks``.  The host waits."""
+        if not self.bridge or not self.blocks:
+            raise ValueError("ReplicaExchange.bridge_blocks needs bridge=True and blocks=B")
+        rec, n = self.metropolis.engine.bridge_fetch_blocks(reset=False)
+        self._same_snapshots("ReplicaExchange.bridge_blocks", n)
+        return self._merged(rec), n, jackknife.block_counts(len(self.metropolis.chains) // self.n_rungs, *self.blocks)
+
+    def _estimate(self, what: str, columns: int, fn, error: bool):
+        """fn(sums[R][6], means[R][6]) of the accumulated bridge sums; with ``error`` (value, se), the same fn on every leave-one-out
+        merge of the blocks (jackknife.jackknife)."""
+        if not error:
+            return fn(*self._bridge_means(what, columns))
+        self._need_bridge(what, columns)
+        if not self.blocks:
+            raise ValueError(f"{what}: error=True needs the sums per block: build the ReplicaExchange with blocks=B")
+        rec, n, ladders = self.bridge_blocks()
+
+        def of_merge(values, n_ladders):
+            sums = np.where(values == 0.0, np.nan, values)      # (an all-zero record: a column outside the mask, an end rung's missing slot)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return fn(sums, sums / (float(n) * float(n_ladders)))
+        return jackknife.jackknife(rec, ladders, of_merge)
+
+    def log_z_ratios(self, method: str = "acceptance", error: bool = False):
         """log(Z_(r+1) / Z_r) for the R - 1 gaps of the ladder, Z_r = integral of exp(-beta_r U), from the accumulated bridge sums.
 
         "acceptance" (default): Bennett's identity with the Metropolis function at C = 0, log S_MF[r] - log S_MB[r + 1] -- both
@@ -192,35 +239,58 @@ class ReplicaExchange(AriannaAlgorithm):
             its second moment diverges): read it as a diagnostic, not as an estimate, on a coarse ladder.
         "ti": thermodynamic integration by the trapezoid, -(<e>_r + <e>_(r+1)) (beta_(r+1) - beta_r) / 2, beta from betas().
         An estimate that reads a flagged record (a NaN or an infinity among its summands) is NaN; so is every estimate before the
-        first snapshot.  The host waits for the queued steps."""
-        with np.errstate(invalid="ignore", divide="ignore"):
-            if method == "acceptance":
-                sums, _ = self._bridge_means("ReplicaExchange.log_z_ratios('acceptance')", AMC_BRIDGE_MF | AMC_BRIDGE_MB)
-                out = np.log(sums[:-1, 4]) - np.log(sums[1:, 5])
-            elif method == "exponential":
-                _, mean = self._bridge_means("ReplicaExchange.log_z_ratios('exponential')", AMC_BRIDGE_WF | AMC_BRIDGE_WB)
-                out = np.stack([np.log(mean[:-1, 2]), -np.log(mean[1:, 3])])
-            elif method == "ti":
-                _, mean = self._bridge_means("ReplicaExchange.log_z_ratios('ti')", AMC_BRIDGE_E)
-                b = self.betas()
-                out = -0.5 * (mean[:-1, 0] + mean[1:, 0]) * (b[1:] - b[:-1])
-            else:
-                raise ValueError(f"ReplicaExchange.log_z_ratios: method {method!r} is none of 'acceptance', 'exponential', 'ti'")
-        out[~np.isfinite(out)] = np.nan
-        return out
+        first snapshot.  ``error=True`` (needs ``blocks``): (estimates, their jackknife standard errors).  The host waits for the
+        queued steps."""
+        return self._estimate(*self._ratios_of(method), error)
 
-    def log_z(self, method: str = "acceptance") -> np.ndarray:
-        """log(Z_r / Z_0) per rung, R values: the cumulative sum of log_z_ratios(method) with log Z_0 = 0 ("exponential": shape (2, R))."""
-        d = self.log_z_ratios(method)
-        return np.concatenate([np.zeros(d.shape[:-1] + (1,)), np.cumsum(d, axis=-1)], axis=-1)
+    def _ratios_of(self, method: str):
+        """(what, columns, fn) of log_z_ratios(method)."""
+        what = f"ReplicaExchange.log_z_ratios({method!r})"
+        if method == "acceptance":
+            def fn(sums, mean):
+                return np.log(sums[:-1, 4]) - np.log(sums[1:, 5])
+            columns = AMC_BRIDGE_MF | AMC_BRIDGE_MB
+        elif method == "exponential":
+            def fn(sums, mean):
+                return np.stack([np.log(mean[:-1, 2]), -np.log(mean[1:, 3])])
+            columns = AMC_BRIDGE_WF | AMC_BRIDGE_WB
+        elif method == "ti":
+            b = self.betas()
 
-    def heat_capacity(self) -> np.ndarray:
-        """beta_r^2 (<e^2> - <e>^2) per rung, R values, from the accumulated bridge sums; beta from betas()."""
-        _, mean = self._bridge_means("ReplicaExchange.heat_capacity", AMC_BRIDGE_E | AMC_BRIDGE_EE)
+            def fn(sums, mean):
+                return -0.5 * (mean[:-1, 0] + mean[1:, 0]) * (b[1:] - b[:-1])
+            columns = AMC_BRIDGE_E
+        else:
+            raise ValueError(f"ReplicaExchange.log_z_ratios: method {method!r} is none of 'acceptance', 'exponential', 'ti'")
+
+        def finite(sums, mean):
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out = fn(sums, mean)
+            out[~np.isfinite(out)] = np.nan
+            return out
+        return what, columns, finite
+
+    def log_z(self, method: str = "acceptance", error: bool = False):
+        """log(Z_r / Z_0) per rung, R values: the cumulative sum of log_z_ratios(method) with log Z_0 = 0 ("exponential": shape (2, R)).
+        ``error=True``: (values, se), the jackknife of the cumulative sum itself -- the gaps of one ladder are correlated, so their
+        errors do not add."""
+        what, columns, ratios = self._ratios_of(method)
+
+        def fn(sums, mean):
+            d = ratios(sums, mean)
+            return np.concatenate([np.zeros(d.shape[:-1] + (1,)), np.cumsum(d, axis=-1)], axis=-1)
+        return self._estimate(what.replace("log_z_ratios", "log_z"), columns, fn, error)
+
+    def heat_capacity(self, error: bool = False):
+        """beta_r^2 (<e^2> - <e>^2) per rung, R values, from the accumulated bridge sums; beta from betas().  ``error=True``: (values,
+        se)."""
         b = self.betas()
-        out = b * b * (mean[:, 1] - mean[:, 0] * mean[:, 0])
-        out[~np.isfinite(out)] = np.nan
-        return out
+
+        def fn(sums, mean):
+            out = b * b * (mean[:, 1] - mean[:, 0] * mean[:, 0])
+            out[~np.isfinite(out)] = np.nan
+            return out
+        return self._estimate("ReplicaExchange.heat_capacity", AMC_BRIDGE_E | AMC_BRIDGE_EE, fn, error)
 
     def restart_bridge(self) -> None:
         """The accumulator of the bridge sums starts again from nothing (a burn-in ends here).  The host waits for the queued steps."""
@@ -406,6 +476,16 @@ def callback_log_z(simulation: Simulation) -> np.ndarray:
     """log(Z_r / Z_0) per rung, a vector of R values (ReplicaExchange.log_z, the acceptance estimator) from the bridge sums accumulated
     so far; reading it does not reset the accumulator.  Needs ReplicaExchange(..., bridge=True)."""
     return _find_exchange(simulation).log_z()
+
+
+def callback_log_z_error(simulation: Simulation) -> np.ndarray:
+    """The jackknife standard error of callback_log_z's values (ReplicaExchange.log_z(error=True)[1]; needs blocks=B)."""
+    return _find_exchange(simulation).log_z(error=True)[1]
+
+
+def callback_heat_capacity_error(simulation: Simulation) -> np.ndarray:
+    """The jackknife standard error of callback_heat_capacity's values (ReplicaExchange.heat_capacity(error=True)[1])."""
+    return _find_exchange(simulation).heat_capacity(error=True)[1]
 
 
 def callback_heat_capacity(simulation: Simulation) -> np.ndarray:

@@ -1,0 +1,144 @@
+"""Delete-one-block jackknife over the blocks of a partition (HipEngine.set_blocks).
+
+The ladders of an ensemble -- the chains, where there is no ladder -- are independent systems, so the B blocks of a partition are
+independent too, whatever the correlation in time or between the rungs of one ladder.  For any function theta = fn(sums) of the
+reproducible sums the engine keeps per block, the jackknife gives a standard error from the B leave-one-out replicates
+
+    theta_(b) = fn(total without block b),     se^2 = (B - 1) / B * sum_b (theta_(b) - mean_b theta_(b))^2.
+
+The leave-one-out totals are exact: records are merged as integers (xsum_merge), never subtracted as Float64s.
+"""
+import numpy as np
+
+from ._capi import AMC_MAX_JK_BLOCKS, AMC_XSUM_WORDS, xsum_merge, xsum_round
+
+__all__ = ["block_counts", "check_blocks", "default_chunk", "jackknife", "leave_one_out", "use_blocks"]
+
+
+def default_chunk(n_groups: int) -> int:
+    """The chunk amc_set_blocks takes for chunk = 0: one block-width of contiguous chains."""
+    return max(1, 256 // max(int(n_groups), 1))
+
+
+def block_counts(n_ladders: int, n_blocks: int, chunk: int, first: int = 0) -> np.ndarray:
+    """Ladders per block of the ``n_ladders`` ladders that begin at global ladder ``first``, block of ladder l = (l div chunk) mod
+    n_blocks, in closed form: a whole period of n_blocks * chunk ladders gives every block ``chunk``, the cut periods the rest."""
+    B, C = int(n_blocks), int(chunk)
+    if B < 1 or C < 1 or n_ladders < 0 or first < 0:
+        raise ValueError(f"block_counts: n_ladders = {n_ladders}, n_blocks = {n_blocks}, chunk = {chunk}, first = {first}")
+
+    def below(g):                                    # ladders of each block among the global ladders [0, g)
+        whole, rest = divmod(int(g), B * C)
+        return whole * C + np.clip(rest - np.arange(B, dtype=np.int64) * C, 0, C)
+
+    return below(int(first) + int(n_ladders)) - below(first)
+
+
+def check_blocks(who: str, blocks, chunk, n_ladders: int, n_groups: int):
+    """``blocks=`` / ``block_chunk=`` of an algorithm as the partition (B, C), None without one.  A ValueError where B lies outside
+    [2, AMC_MAX_JK_BLOCKS], C < 1, or the ``n_ladders`` ladders make fewer chunks than blocks (a block would be empty)."""
+    if blocks is None or blocks is False:
+        if chunk is not None:
+            raise ValueError(f"{who}: block_chunk = {chunk!r} without blocks")
+        return None
+    if int(blocks) != blocks or not 2 <= int(blocks) <= AMC_MAX_JK_BLOCKS:
+        raise ValueError(f"{who}: blocks = {blocks!r} must be an integer in [2, {AMC_MAX_JK_BLOCKS}]")
+    C = default_chunk(n_groups) if chunk is None else chunk
+    if int(C) != C or int(C) < 1:
+        raise ValueError(f"{who}: block_chunk = {chunk!r} must be an integer >= 1")
+    B, C = int(blocks), int(C)
+    n_chunks = -(-int(n_ladders) // C)
+    if B > n_chunks:
+        raise ValueError(f"{who}: blocks = {B} is larger than the {n_chunks} chunks that {n_ladders} ladders make in chunks of {C}: "
+                         "a block would be empty (fewer blocks, or a smaller block_chunk)")
+    return B, C
+
+
+def ask_blocks(who: str, metropolis, partition) -> None:
+    """``metropolis.blocks`` = the partition an algorithm asks for; the engine keeps one, so a second algorithm asks for the same."""
+    if metropolis.blocks is not None and tuple(metropolis.blocks) != tuple(partition):
+        raise ValueError(f"{who}: blocks and chunk {tuple(partition)}, another algorithm of this Metropolis asks for {tuple(metropolis.blocks)}: "
+                         "the engine keeps its sums under one partition")
+    metropolis.blocks = tuple(partition)
+
+
+def refuse_annealing(who: str, simulation) -> None:
+    """Blocks of ladders stop being independent once a resampling lets copies of one parent share them."""
+    from .annealing import PopulationAnnealing
+    if any(isinstance(a, PopulationAnnealing) for a in simulation.algorithms):
+        raise ValueError(f"{who}: blocks together with a PopulationAnnealing in the algorithm list: resampling makes copies of one parent "
+                         "share blocks, so a jackknife over them has no meaning")
+
+
+def use_blocks(metropolis, partition) -> None:
+    """The partition (B, C) on the Metropolis' engine, once: setting it again would clear the sums (storage.restore sets it first, two
+    algorithms may share it).  Behind set_ladder, which turns a partition off."""
+    if metropolis.blocks_on == tuple(partition):
+        return
+    if metropolis.blocks_on is not None:
+        raise ValueError(f"blocks: the engine keeps its sums under the partition {metropolis.blocks_on}, {tuple(partition)} is asked for "
+                         "(one partition per Metropolis: give every algorithm and the checkpoint the same blocks and chunk)")
+    if not hasattr(metropolis.engine, "set_blocks"):
+        raise ValueError("blocks: this engine keeps no sums per block (streams > 1 is not supported)")
+    metropolis.engine.set_blocks(*partition)
+    metropolis.blocks_on = tuple(partition)
+
+
+def _merge(a, b):
+    """Records merged record by record; an all-zero record (a slot without a summand) merges as nothing."""
+    if a is None:
+        return b.copy()
+    out = a.copy()
+    za, zb = ~a.any(axis=1), ~b.any(axis=1)
+    both = ~za & ~zb
+    if both.any():
+        out[both] = xsum_merge(a[both], b[both])
+    out[za] = b[za]
+    return out
+
+
+def leave_one_out(block_records):
+    """(total, [total without block b for every b]) of ``block_records[B][...][AMC_XSUM_WORDS]``, every one an exact merge (prefix and
+    suffix merges: 3 B of them)."""
+    rec = np.ascontiguousarray(block_records, dtype=np.float64)
+    B, shape = rec.shape[0], rec.shape[1:]
+    flat = rec.reshape(B, -1, AMC_XSUM_WORDS)
+    prefix, suffix = [None] * (B + 1), [None] * (B + 1)       # prefix[b]: blocks < b; suffix[b]: blocks >= b
+    for b in range(B):
+        prefix[b + 1] = _merge(prefix[b], flat[b])
+    for b in range(B - 1, -1, -1):
+        suffix[b] = _merge(suffix[b + 1], flat[b])
+    loo = []
+    for b in range(B):
+        if prefix[b] is None:
+            loo.append(suffix[b + 1].copy())
+        elif suffix[b + 1] is None:
+            loo.append(prefix[b].copy())
+        else:
+            loo.append(_merge(prefix[b], suffix[b + 1]))
+    return prefix[B].reshape(shape), [r.reshape(shape) for r in loo]
+
+
+def jackknife(block_records, counts, fn):
+    """(theta, se) of ``theta = fn(values, n)``: ``values`` the Float64s of merged records, shaped as one block's records without
+    the last axis, ``n`` the ladders merged.  ``block_records[B][...][AMC_XSUM_WORDS]``: the records per block (bridge_fetch_blocks,
+    one sample or all of corr_fetch_blocks); ``counts[B]``: the ladders of each block (block_counts) -- they may differ.  theta comes
+    from the full merge, se from the B leave-one-out replicates, each the whole of ``fn``.  An empty block is a ValueError."""
+    rec = np.ascontiguousarray(block_records, dtype=np.float64)
+    counts = np.asarray(counts, dtype=np.int64)
+    if rec.ndim < 2 or rec.shape[-1] != AMC_XSUM_WORDS or rec.shape[0] != counts.size:
+        raise ValueError(f"jackknife: records of shape {rec.shape} for {counts.size} blocks")
+    B = counts.size
+    if B < 2:
+        raise ValueError(f"jackknife: {B} block(s); a jackknife needs at least 2")
+    for b in range(B):
+        if counts[b] <= 0:
+            raise ValueError(f"jackknife: block {b} is empty (fewer chunks of ladders than blocks?)")
+    total, loo = leave_one_out(rec)
+    n = int(counts.sum())
+    shape = rec.shape[1:-1]
+    theta = np.asarray(fn(xsum_round(total).reshape(shape), n), dtype=np.float64)
+    reps = np.stack([np.asarray(fn(xsum_round(loo[b]).reshape(shape), n - int(counts[b])), dtype=np.float64) for b in range(B)])
+    dev = reps - reps.mean(axis=0)
+    se = np.sqrt((B - 1) / B * (dev * dev).sum(axis=0))
+    return theta, se

@@ -109,6 +109,8 @@ class Metropolis(AriannaAlgorithm):
         self.n_rungs = 0                    # rungs per ladder (set_ladder; 0: no ladder)
         self.tracking = False               # walker tracking is on (ReplicaExchange.initialise, storage.restore; set_ladder turns it off)
         self.bridge = 0                     # mask of the bridge sums (ReplicaExchange.__init__; 0: off)
+        self.blocks = None                  # the jackknife partition (B, C) an algorithm asks for (ReplicaExchange / Autocorrelation.__init__)
+        self.blocks_on = None               # ... and the one set on the engine (jackknife.use_blocks; set_ladder turns it off)
         self.annealing = None               # the PopulationAnnealing that cools these chains (its __init__)
         self.autocorrelation = None         # the Autocorrelation that measures these chains (its __init__)
         self.restored = False               # storage.restore put the state on the device: initialise() leaves it there
@@ -269,6 +271,7 @@ class Metropolis(AriannaAlgorithm):
         self.engine.set_ladder(R)
         self.n_rungs = R
         self.tracking = False                   # (amc_set_ladder turns walker tracking off; ReplicaExchange(track=True) and restore turn it on)
+        self.blocks_on = None                   # (... and the jackknife partition: jackknife.use_blocks sets it again)
         if self.rung_sigma is not None:         # (amc_set_ladder clears the table too)
             self.engine.set_rung_sigma(self.rung_sigma)
 

@@ -250,6 +250,24 @@ def _read_bridge(met, eng, d, est) -> None:
         eng.set_bridge(d["bridge_records"], int(d["bridge_snapshots"]))
 
 
+def _write_bridge_blocks(met, eng, d, est) -> None:
+    if met.n_rungs and met.bridge and met.blocks_on:    # a jackknife partition: the records per block are the state the run goes on from
+        rec, n_snap = eng.bridge_fetch_blocks(reset=False)
+        d.update(bridge_blocks=np.array(met.blocks_on, dtype=np.int64), bridge_block_records=rec, bridge_block_snapshots=n_snap)
+
+def _read_bridge_blocks(met, eng, d, est) -> None:
+    # behind _read_bridge: setting the partition clears the plain accumulator that section filled, and this one fills the blocks
+    if "bridge_block_records" in d and met.blocks:
+        from . import jackknife
+        if tuple(int(v) for v in d["bridge_blocks"]) != tuple(met.blocks):
+            raise ValueError(f"checkpoint holds bridge sums under the partition {tuple(int(v) for v in d['bridge_blocks'])}, this run asks "
+                             f"for {tuple(met.blocks)}")
+        jackknife.use_blocks(met, met.blocks)
+        eng.set_bridge_blocks(d["bridge_block_records"], int(d["bridge_block_snapshots"]))
+    elif "bridge_records" in d and met.bridge and met.blocks and int(d["bridge_snapshots"]):
+        raise ValueError("checkpoint holds bridge sums without sums per block, this ReplicaExchange asks for blocks")
+
+
 def _write_respacing(met, eng, d, est) -> None:
     n_respaced = eng.respace_status()[1] if met.n_rungs and hasattr(eng, "respace_status") else 0
     if n_respaced:                                  # the ladder was respaced (ReplicaExchange.respace keeps beta_array current): no field otherwise
@@ -294,6 +312,15 @@ def _read_correlation(met, eng, d, est) -> None:
         met.autocorrelation.set_state(d)
 
 
+def _write_correlation_blocks(met, eng, d, est) -> None:
+    if met.autocorrelation is not None:
+        d.update(met.autocorrelation.state_blocks())
+
+def _read_correlation_blocks(met, eng, d, est) -> None:
+    if met.autocorrelation is not None:
+        met.autocorrelation.set_state_blocks(d)
+
+
 def _write_estimator(met, eng, d, est) -> None:
     if est is not None:
         d["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in est.gradients_data])
@@ -316,8 +343,9 @@ def _read_estimator(met, eng, d, est) -> None:
 # before the count of tunings.
 _SECTIONS = ((_write_core, _read_core), (_write_counters, _read_counters), (_write_rung_sigma, _read_rung_sigma),
              (_write_ladder, _read_ladder), (_write_tracking, _read_tracking), (_write_window, _read_window),
-             (_write_bridge, _read_bridge), (_write_respacing, _read_respacing), (_write_annealing, _read_annealing),
-             (_write_correlation, _read_correlation), (_write_estimator, _read_estimator))
+             (_write_bridge, _read_bridge), (_write_bridge_blocks, _read_bridge_blocks), (_write_respacing, _read_respacing),
+             (_write_annealing, _read_annealing), (_write_correlation, _read_correlation),
+             (_write_correlation_blocks, _read_correlation_blocks), (_write_estimator, _read_estimator))
 
 
 def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
