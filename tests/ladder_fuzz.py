@@ -9,7 +9,13 @@ sequence.  This module draws the configuration and the sequence:
                       above, rung_sums_twin.records, track_twin.flow_counts, numpy for the bin rule and the strided counter sums.  What
                       set_ladder, set_rung_sigma(None), set_tracking and the setters reset or keep follows the text of DESIGN.md
                       section 3.13 and include/amc.h.  It shares no code with the product.
-    draw_case         one configuration (a plain dict; x0 and beta are functions of it: make_state)
+                      The ladder tools on top: respace_twin.RespaceTwin (the ladder class), tune_twin.tune_rule with the window and
+                      its base, bridge_twin.records / merge, corr_twin.observable / sample_records with one group per rung,
+                      blocks_twin with first = chain_offset // R -- and, from the header's text alone, what a respacing that is
+                      taken, set_rung_sigma, set_ladder, set_blocks and upload_state zero or keep, and which calls are refused with
+                      AMC_ERR_STATE (Refused).  HipEngine has no read of the per-chain beta but ladder(): that is the "get_ladder"
+                      observer.
+    draw_case        one configuration (a plain dict; x0 and beta are functions of it: make_state)
     run_walk          the operations, drawn one by one; both sides take each, the observers compare bit for bit / integer for integer
     run_case          engine and reference of a case, the walk, the comparison at the end
 
@@ -20,18 +26,32 @@ import os
 import numpy as np
 import pytest
 
+import blocks_twin as BL
+import bridge_twin as BT
+import corr_twin as CT
 import exchange_twin as X
 import f32_param_twin as F
 import oracle_lib as O
+import respace_twin as RP
 import rung_sigma_twin as RT
 import rung_sums_twin as RS
 import track_twin as T
+import tune_twin as TU
 
 DEFAULT_CASES, DEFAULT_SEED = 40, 20261019       # drawn cases behind the pinned ones (AMC_LADDER_FUZZ_CASES, AMC_LADDER_FUZZ_SEED)
 MAX_CHAINS = 6200
 MAX_EXCHANGE_STEPS = 40          # per walk: the twin's exchange step is a Python loop over the gaps
 T_X_LIMIT = 1 << 48              # amc_exchange refuses a step index that has reached 2^48
 TWO32 = 1 << 32
+MAX_SNAPSHOTS, MAX_SAMPLES = 12, 20      # per walk: below the second reallocation of a blocked accumulator (slot 16, then 32)
+ERR_STATE = -5                   # AMC_ERR_STATE
+
+
+class Refused(RuntimeError):
+    """What the reference raises where the header says AMC_ERR_STATE; worded as _capi._check words an AmcError."""
+
+    def __init__(self, what):
+        super().__init__(f"amc error {ERR_STATE}: {what}")
 
 
 # ---- the reference ---------------------------------------------------------------------------------------------------------------------
@@ -52,7 +72,7 @@ def hist_row(x, lo, hi, n_bins):
 class LadderReference:
     """HipEngine's surface for a handle with a ladder, from the twins.  Constructor arguments as HipEngine's."""
 
-    ladder_class = T.TrackTwin       # (the host tests put a defective subclass here)
+    ladder_class = RP.RespaceTwin    # (the host tests put a defective subclass here)
 
     def __init__(self, *, n_chains, chain_offset=0, n_chains_global=None, potential="harmonic", beta=1.0, sigma=(1.0,), weight=(1.0,),
                  seed=1, sweepstep=1, per_chain_counters=True, dtype="f64", param_dtype="f64"):
@@ -70,6 +90,9 @@ class LadderReference:
         self.n_rungs = 0
         self.tw = None
         self._t_x = 0                                        # a property of the handle: survives clearing and re-setting the ladder
+        self.partition = None                                # (B, C) while a partition is set
+        self.corr = None                                     # the mark: dict(observable, origin, records, steps, series)
+        self._bridge_clear()
 
     # -- the simulation underneath -------------------------------------------------------------------------------------------------------
     def _plain_sim(self):
@@ -111,8 +134,11 @@ class LadderReference:
     # -- state ----------------------------------------------------------------------------------------------------------------------------
     def upload_state(self, x, beta=None):
         x = np.ascontiguousarray(x, dtype=np.float64)
+        self.corr = None                                     # chain slots are reassigned: the mark is forgotten
         if beta is not None:
             self.beta = np.array(beta, dtype=np.float64)
+            if self.tw is not None:
+                self.tw.beta = self.beta.astype(np.float32).astype(np.float64) if self.dtype == "f32" else self.beta.copy()
         if isinstance(self.sim, F.TwinSim):
             X._State(self.sim).put(x, self.sim.pot)
             self.sim.beta[:] = self.beta.astype(np.float32)
@@ -159,7 +185,8 @@ class LadderReference:
 
     # -- the ladder -----------------------------------------------------------------------------------------------------------------------
     def set_ladder(self, n_rungs):
-        """Zeroes the gap counters, turns tracking off, clears the table; t_x stays."""
+        """Zeroes the gap counters, turns tracking off, clears the table, the bridge accumulator, the mark, the partition, the window
+        base and the records of respacing and tuning; t_x stays."""
         R = int(n_rungs)
         assert 2 <= R <= 64 and self.n_chains % R == 0 and self.offset % R == 0 and self.n_global % R == 0
         if self.tw is not None:
@@ -169,6 +196,10 @@ class LadderReference:
                                     f32=self.dtype == "f32")
         self.tw.t_x = self._t_x
         self.n_rungs = R
+        self.partition, self.corr = None, None
+        self._bridge_clear()
+        self.base = np.zeros((2, self.n_moves, R), dtype=np.int64)
+        self._tune_reset()
 
     def exchange(self, n=1):
         self.tw.exchange(int(n))
@@ -247,6 +278,8 @@ class LadderReference:
 
     # -- widths per rung ------------------------------------------------------------------------------------------------------------------
     def set_rung_sigma(self, sigma):
+        """(the tuning record starts afresh; the window base stays)"""
+        self._tune_reset()
         if sigma is None:
             if self.table is not None:                       # the sweeps read the pool's sigma_k again, as it is now
                 self.table = None
@@ -268,6 +301,203 @@ class LadderReference:
         acc, tot = self.sim.counters()
         R = self.n_rungs
         return (np.stack([acc[:, r::R].sum(axis=1) for r in range(R)], axis=1), np.stack([tot[:, r::R].sum(axis=1) for r in range(R)], axis=1))
+
+    # -- the window and the tuning (tune_twin.tune_rule; the bookkeeping as tune_twin.TuneTwin keeps it) --------------------------------
+    def _tune_reset(self):
+        self.tune_st = np.zeros((self.n_moves, max(self.n_rungs, 1)), dtype=np.int64)
+        self.n_tuned = 0
+
+    def _window(self):
+        acc, tot = self.rung_counter_totals()
+        bad = (acc < self.base[0]) | (tot < self.base[1])
+        return np.where(bad, -1, acc - self.base[0]), np.where(bad, -1, tot - self.base[1]), bad
+
+    def rung_window_counts(self):
+        a, t, _ = self._window()
+        return a, t
+
+    def rung_window_restart(self):
+        self.base[0], self.base[1] = self.rung_counter_totals()
+
+    def rung_window_base(self):
+        return self.base[0].copy(), self.base[1].copy()
+
+    def set_rung_window_base(self, accepted, total):
+        K, R = self.n_moves, self.n_rungs
+        self.base = np.stack([np.asarray(accepted, dtype=np.int64).reshape(K, R), np.asarray(total, dtype=np.int64).reshape(K, R)])
+
+    def window_base_for_tuning(self):
+        """(the host tests put a defect here)"""
+        return self.base
+
+    def tune_rung_sigma(self, target=0.44, gamma=1.0, min_calls=1000, sigma_lo=1e-100, sigma_hi=1e100, counts=None):
+        if self.table is None:
+            raise Refused("no table set")
+        K, R = self.table.shape
+        if counts is None:
+            saved, self.base = self.base, self.window_base_for_tuning()
+            A, Tt, bad = self._window()
+            self.base = saved
+        else:
+            A, Tt = np.asarray(counts[0]).reshape(K, R), np.asarray(counts[1]).reshape(K, R)
+            bad = np.zeros((K, R), dtype=bool)
+        new = self.table.copy()
+        for k in range(K):
+            for r in range(R):
+                self.tune_st[k, r], new[k, r] = TU.tune_rule(self.table[k, r], A[k, r], Tt[k, r], target, gamma, min_calls, sigma_lo, sigma_hi,
+                                                             bool(bad[k, r]))
+        if np.any((self.tune_st == TU.OK) | (self.tune_st == TU.CLAMPED)):
+            self.n_tuned += 1
+        self.rung_window_restart()                           # a tuning ends the window in every case
+        if not np.array_equal(new.view(np.uint64), self.table.view(np.uint64)):
+            self.table = new
+            self._switch(self._rung_sim(self.table_as_read()))
+
+    def tune_status(self):
+        assert self.table is not None
+        return self.tune_st.copy(), self.n_tuned
+
+    # -- respacing (respace_twin) -------------------------------------------------------------------------------------------------------------
+    def respace_ladder(self, rule, gamma=1.0, eps=0.0, counts=None):
+        R = self.n_rungs
+        if rule == RP.FLOW and counts is None and not self.tracking:
+            raise Refused("rule flow with the handle's own counts while tracking is off")
+        if counts is not None:
+            c = np.asarray(counts, dtype=np.int64).reshape(-1)
+            counts = (c[:R - 1], c[R - 1:]) if rule == RP.ACCEPTANCE else c.reshape(R, 3)
+        if self.tw.respace(rule, gamma, eps, counts) == 0:
+            self.beta = self.tw.beta.copy()
+            self._respaced()
+
+    def _respaced(self):
+        """A respacing that is taken zeroes the bridge records and the count, every block's rows too; the mask stays."""
+        self.bridge_rec, self.bridge_n = np.zeros((self.n_rungs, BT.COLS, BT.WORDS)), 0
+        self.bridge_blk = None
+
+    def respace_status(self):
+        return self.tw.status, self.tw.n_respaced
+
+    def ladder(self):
+        return self.tw.ladder()
+
+    # -- bridge sums (bridge_twin; per block blocks_twin) -----------------------------------------------------------------------------------
+    def _bridge_clear(self):
+        self.bridge_mask, self.bridge_n = 0, 0
+        self.bridge_rec = np.zeros((max(self.n_rungs, 1), BT.COLS, BT.WORDS))
+        self.bridge_blk = None                               # records[B][R][6][12] while a partition is set and a snapshot is in
+
+    def _f32(self):
+        return self.dtype == "f32"
+
+    def _first_ladder(self):
+        return self.offset // self.n_rungs
+
+    def bridge_accumulate(self, columns=BT.ALL):
+        columns, R = int(columns), self.n_rungs
+        assert 0 < columns <= BT.ALL
+        if self.bridge_mask and columns != self.bridge_mask:
+            raise Refused("another column mask while one is fixed")
+        self.bridge_mask = columns
+        e = self.sim.state()[1]
+        self.bridge_rec = BT.merge([self.bridge_rec, BT.records(e, self.tw.beta, R, columns, self._f32())])
+        if self.partition is not None:
+            B, C = self.partition
+            blk = BL.bridge_records(e, self.tw.beta, R, B, C, columns, self._f32(), first=self.block_first())
+            self.bridge_blk = blk if self.bridge_blk is None else BT.merge([self.bridge_blk, blk])
+        self.bridge_n += 1
+
+    def bridge_fetch(self, reset=False):
+        out = self.bridge_rec.copy(), self.bridge_n
+        if reset:
+            self._bridge_clear()
+        return out
+
+    def set_bridge(self, records=None, n_snapshots=0):
+        if records is not None and self.partition is not None:
+            raise Refused("merged records while a partition is set")
+        self._bridge_clear()
+        if records is None or int(n_snapshots) == 0:
+            return
+        self.bridge_rec = np.array(records, dtype=np.float64).reshape(self.n_rungs, BT.COLS, BT.WORDS)
+        self.bridge_n = int(n_snapshots)
+        self.bridge_mask = sum(1 << c for c in range(BT.COLS) if self.bridge_rec[:, c].any())
+
+    # -- time correlation, one group per rung (corr_twin; per block blocks_twin) ------------------------------------------------------------
+    def _observe(self, kind):
+        return CT.observable(kind, self.potential, self.sim.state()[0], self._f32())
+
+    def corr_steps_entry(self):
+        """steps[s]: the MH step index at the call (the host tests put a defect here)."""
+        return self.step
+
+    def corr_mark(self, observable="energy"):
+        a = self._observe(observable)
+        self.corr = dict(observable=CT.OBSERVABLES[observable], origin=a, records=[self.corr_sample_records(a, a)],
+                         steps=[self.corr_steps_entry()], series=[a])
+
+    def corr_sample_records(self, origin, values):
+        return CT.sample_records(origin, values, self.n_rungs)
+
+    def corr_sample(self):
+        if self.corr is None:
+            raise Refused("no mark")
+        o = self._observe(self.corr["observable"])
+        self.corr["records"].append(self.corr_sample_records(self.corr["origin"], o))
+        self.corr["steps"].append(self.corr_steps_entry())
+        if self.corr["series"] is not None:
+            self.corr["series"].append(o)
+
+    def corr_fetch(self):
+        if self.corr is None:
+            return np.zeros((0, self.n_rungs, CT.COLS, CT.WORDS)), np.zeros(0, dtype=np.uint64), 0
+        return np.stack(self.corr["records"]), np.array(self.corr["steps"], dtype=np.uint64), self.corr["observable"]
+
+    def corr_origin(self):
+        if self.corr is None:
+            raise Refused("no mark")
+        return self.corr["origin"].copy()
+
+    def set_corr(self, observable, origin, records, steps):
+        if self.partition is not None:
+            raise Refused("a plain mark while a partition is set")
+        rec = np.array(records, dtype=np.float64).reshape(-1, self.n_rungs, CT.COLS, CT.WORDS)
+        self.corr = dict(observable=CT.OBSERVABLES[observable], origin=np.array(origin, dtype=np.float64), records=list(rec),
+                         steps=[int(s) for s in steps], series=None)
+
+    def corr_clear(self):
+        self.corr = None
+
+    # -- jackknife blocks -----------------------------------------------------------------------------------------------------------------
+    def set_blocks(self, n_blocks, chunk=0):
+        """Clears the bridge accumulator and forgets the mark on every call that succeeds."""
+        B = int(n_blocks)
+        assert B == 0 or 2 <= B <= 64
+        self.partition = None if B == 0 else (B, int(chunk) if int(chunk) else max(1, 256 // self.n_rungs))
+        self._bridge_clear()
+        self.corr = None
+
+    def block_first(self):
+        """The global index of local ladder 0 (the host tests put a defect here)."""
+        return self._first_ladder()
+
+    def bridge_fetch_blocks(self, reset=False):
+        if self.partition is None:
+            raise Refused("no partition")
+        B = self.partition[0]
+        rec = np.zeros((B, self.n_rungs, BT.COLS, BT.WORDS)) if self.bridge_blk is None else self.bridge_blk.copy()
+        out = rec, self.bridge_n
+        if reset:
+            self._bridge_clear()
+        return out
+
+    def corr_fetch_blocks(self):
+        if self.partition is None:
+            raise Refused("no partition")
+        B, C = self.partition
+        if self.corr is None:
+            return np.zeros((B, 0, self.n_rungs, CT.COLS, CT.WORDS)), np.zeros(0, dtype=np.uint64), 0
+        rec = BL.corr_records(self.corr["series"], self.n_rungs, B, C, first=self.block_first())
+        return rec, np.array(self.corr["steps"], dtype=np.uint64), self.corr["observable"]
 
 
 # ---- cases -----------------------------------------------------------------------------------------------------------------------------
@@ -412,6 +642,35 @@ PINNED = [
     # Float32 state with the slice knobs set: its kernels are compiled at run time, so its launches stay whole
     pinned_case(7, 171, [("launches", 3), ("exchange", 2), ("launches", 2), ("state",), ("rung_sums", 5), ("counters",)],
                 dtype="f32", per_chain_counters=False, slices=2, plant=True),
+    # -- the ladder tools ------------------------------------------------------------------------------------------------------------
+    # a flow respacing that is taken, with a bridge mask fixed, a partition set and a mark standing: the block rows and the count are
+    # zeroed, the mask, the mark and its samples stay, the labels and the gap counters start afresh
+    pinned_case(4, 85, [("track",), ("blocks", 3, 5), ("exchange", 8), ("single", 2), ("bridge", BT.ACCEPTANCE_SET), ("mark", "energy"),
+                        ("exchange", 6), ("sample",), ("bridge", BT.ACCEPTANCE_SET), ("bridge_blocks",),
+                        ("respace", RP.FLOW, 1.0, 0.01, "own"), ("respace_status",), ("bridge_blocks",), ("corr_blocks",), ("walkers",),
+                        ("gaps",), ("refused", "mask"), ("sample",), ("bridge", BT.ACCEPTANCE_SET), ("bridge_blocks",), ("corr_blocks",),
+                        ("get_ladder",)],
+                beta_ratio=1.15, chain_offset=8 * 2 ** 19),
+    # Move counters uploaded behind the window base: status 2 and a new window; a table written then resets the record and keeps the
+    # base; the tuning after it reads the window from that base
+    pinned_case(3, 85, [("table",), ("single", 4), ("window_restart",), ("recount", 0), ("window",),
+                        ("tune", 0.44, 1.0, 1, 1e-100, 1e100, False), ("tune_status",), ("window",), ("multi", 3), ("table",),
+                        ("tune_status",), ("window",), ("multi", 5), ("tune", 0.44, 0.5, 1, 0.05, 0.5, False), ("tune_status",), ("window",),
+                        ("state",), ("mark", "x"), ("corr_fetch",), ("mark", "energy"), ("corr_put",), ("corr_fetch",)],
+                sigma=[0.8, 0.11], weight=[0.625, 0.375]),
+    # a partition with a chunk of one ladder on a shard that holds chain id 2^32, R = 3
+    pinned_case(3, 171, [("blocks", 64, 1), ("bridge", BT.ALL), ("mark", "x"), ("single", 2), ("exchange", 2), ("sample",), ("bridge", BT.ALL),
+                         ("bridge_blocks",), ("corr_blocks",), ("bridge_fetch",), ("corr_fetch",), ("blocks_off",), ("refused", "fetch_blocks"),
+                         ("bridge_fetch",), ("corr_fetch",), ("mark", "x"), ("single", 1), ("sample",), ("corr_fetch",), ("corr_clear",),
+                         ("corr_put",), ("sample",), ("corr_fetch",), ("bridge", BT.E), ("bridge_fetch",), ("bridge_reset",),
+                         ("bridge_put", True), ("bridge", BT.E), ("bridge_fetch",)],
+                potential="double_well", chain_offset=((TWO32 - 256) // 18) * 18),
+    # Float32 state: the respacing rounds the ladder once, the bridge differences are formed in Float32 from the rounded values
+    pinned_case(5, 85, [("exchange", 8), ("respace", RP.ACCEPTANCE, 0.7, 0.01, "own"), ("respace_status",), ("get_ladder",), ("bridge", BT.ALL),
+                        ("bridge_fetch",), ("single", 2), ("bridge", BT.ALL), ("bridge_fetch",), ("get_ladder",), ("upload", True), ("get_ladder",),
+                        ("bridge", BT.ALL), ("bridge_fetch",), ("mark", "energy"), ("exchange", 1), ("sample",), ("corr_fetch",),
+                        ("upload", False), ("corr_fetch",), ("corr_put",), ("sample",), ("corr_fetch",)],
+                dtype="f32", sigma=[0.5]),
 ]
 
 
@@ -437,11 +696,23 @@ def same_ints(a, b):
 
 
 MUTATORS = ["single", "single", "multi", "launches", "launches", "exchange", "exchange", "exchange", "sweep_exchange", "sweep_exchange",
-            "table", "table", "clear", "sigma", "track", "track", "untrack", "labels", "xcounters", "tx", "ladder", "recount"]
-OBSERVERS = ["state", "counters", "gaps", "walkers", "rung_sums", "rung_hist", "rung_totals", "reduce"]
+            "table", "table", "clear", "sigma", "track", "track", "untrack", "labels", "xcounters", "tx", "ladder", "recount",
+            # the ladder tools
+            "bridge", "bridge", "bridge", "bridge_reset", "bridge_put", "respace", "respace", "respace", "tune", "tune", "tune",
+            "window_restart", "window_base", "mark", "mark", "sample", "sample", "sample", "corr_clear", "corr_put", "corr_put", "corr_put", "blocks", "blocks",
+            "blocks_off", "upload", "refused", "refused"]
+OLD_OBSERVERS = ["state", "counters", "gaps", "walkers", "rung_sums", "rung_hist", "rung_totals", "reduce"]
+NEW_OBSERVERS = ["get_ladder", "respace_status", "tune_status", "window", "bridge_fetch", "corr_fetch", "bridge_blocks", "corr_blocks"]
+OBSERVERS = OLD_OBSERVERS + NEW_OBSERVERS
+OBSERVER_DRAW = OBSERVERS + ["bridge_fetch", "corr_fetch"]      # the two whose records the walk hands back later
+NEW_OPERATIONS = ["bridge", "bridge_reset", "bridge_put", "respace", "tune", "window_restart", "window_base", "mark", "sample", "corr_clear",
+                  "corr_put", "blocks", "blocks_off", "upload", "refused"] + NEW_OBSERVERS
 OPERATIONS = sorted(set(MUTATORS)) + OBSERVERS
+OBSERVER_SHARE = 0.36            # of the draws; the host test holds the walks to at most 40 % observers
+MIN_MUTATORS = 8                 # mutating operations taken by every walk
 T_X_VALUES = [0, 1, TWO32 - 1, TWO32, 1 << 47, T_X_LIMIT - 3]
 RECOUNT_STEPS = [0, 17, 65_530, 65_535, 65_536, 70_000]
+REFUSALS = ["mask", "sample", "put_bridge", "put_corr", "fetch_blocks", "tune", "flow"]
 
 
 def other_ladders(ref):
@@ -449,8 +720,44 @@ def other_ladders(ref):
     return [r for r in range(2, 65) if r != ref.n_rungs and ref.n_chains % r == 0 and ref.offset % r == 0]
 
 
-def possible(ref, name):
+def new_context():
+    """What a walk keeps beside the two sides: snapshots and samples taken, and what the fetch observers have returned (the records that
+    bridge_put, corr_put and the refused restores hand back)."""
+    return dict(snapshots=0, samples=0, bridge=None, corr=None)
+
+
+def windowed(ref):
+    """The amc_rung_window_* entries: a ladder, per-chain counters, K R <= 64."""
+    return ref.per_chain_counters and ref.n_moves * ref.n_rungs <= 64
+
+
+def stash_fits(ref, stash):
+    return stash is not None and stash["R"] == ref.n_rungs
+
+
+def refusals(ref, ctx):
+    """The calls of the fixed list that the handle, as it is now, must refuse with AMC_ERR_STATE."""
+    out = []
+    if ref.bridge_mask:
+        out.append("mask")
+    if ref.corr is None:
+        out.append("sample")
+    if ref.partition is not None and stash_fits(ref, ctx["bridge"]):
+        out.append("put_bridge")
+    if ref.partition is not None and stash_fits(ref, ctx["corr"]):
+        out.append("put_corr")
+    if ref.partition is None:
+        out.append("fetch_blocks")
+    if ref.table is None:
+        out.append("tune")
+    if not ref.tracking:
+        out.append("flow")
+    return out
+
+
+def possible(ref, name, ctx=None):
     """Whether the handle, as it is now, takes operation `name`."""
+    ctx = ctx if ctx is not None else new_context()
     if name == "table":
         return ref.per_chain_counters and ref.param_dtype == "f64" and ref.n_moves * ref.n_rungs <= 64
     if name == "clear":
@@ -461,14 +768,34 @@ def possible(ref, name):
         return bool(other_ladders(ref))
     if name in ("recount", "rung_totals"):
         return ref.per_chain_counters
+    if name == "bridge":
+        return ctx["snapshots"] < MAX_SNAPSHOTS
+    if name == "bridge_put":
+        return ref.partition is None
+    if name in ("tune", "tune_status"):
+        return ref.table is not None
+    if name in ("window_restart", "window_base", "window"):
+        return windowed(ref)
+    if name == "sample":
+        return ref.corr is not None and ctx["samples"] < MAX_SAMPLES
+    if name == "mark":
+        return ctx["samples"] < MAX_SAMPLES
+    if name == "corr_put":
+        return ref.partition is None and stash_fits(ref, ctx["corr"])
+    if name in ("blocks_off", "bridge_blocks", "corr_blocks"):
+        return ref.partition is not None
+    if name == "refused":
+        return bool(refusals(ref, ctx))
     return True
 
 
-def draw_op(rng, ref, steps_left):
-    """One operation the handle can take, with its scalar arguments: a tuple (name, ...).  Arrays are drawn when it is applied."""
+def draw_op(rng, ref, steps_left, ctx=None, mutator=False):
+    """One operation the handle can take, with its scalar arguments: a tuple (name, ...).  Arrays are drawn when it is applied.
+    `mutator`: no observer."""
+    ctx = ctx if ctx is not None else new_context()
     for _ in range(64):
-        name = str(rng.choice(OBSERVERS if rng.random() < 0.4 else MUTATORS))
-        if not possible(ref, name):
+        name = str(rng.choice(OBSERVER_DRAW if not mutator and rng.random() < OBSERVER_SHARE else MUTATORS))
+        if not possible(ref, name, ctx):
             continue
         if name == "single":
             return (name, int(rng.integers(1, 6)))
@@ -489,7 +816,7 @@ def draw_op(rng, ref, steps_left):
         if name == "tx":
             return (name, int(rng.choice(T_X_VALUES)))
         if name == "ladder":                # seldom: it turns tracking off and clears the table
-            if rng.random() < 0.7:
+            if rng.random() < 0.4:
                 continue
             return (name, int(rng.choice(other_ladders(ref))))
         if name == "recount":
@@ -498,8 +825,33 @@ def draw_op(rng, ref, steps_left):
             return (name, int(rng.integers(1, 8)))
         if name == "rung_hist":
             return (name, int(rng.choice([7, 200, 4000])), bool(rng.random() < 0.5))
+        if name == "bridge":                # the first one after a reset draws the mask
+            if ref.bridge_mask:
+                return (name, ref.bridge_mask)
+            return (name, int(rng.choice([BT.ACCEPTANCE_SET, BT.ALL, BT.E, int(rng.integers(1, BT.ALL + 1))])))
+        if name == "bridge_put":
+            return (name, bool(stash_fits(ref, ctx["bridge"]) and rng.random() < 0.7))
+        if name == "respace":
+            rule = RP.FLOW if rng.random() < 0.5 else RP.ACCEPTANCE
+            counts = str(rng.choice(["own", "own", "explicit", "explicit", "zero", "flat"]))
+            if rule == RP.FLOW and counts == "own" and not ref.tracking:
+                rule = RP.ACCEPTANCE
+            gamma = 1.0 if rng.random() < 0.5 else float(1.0 - rng.random())         # (0, 1]
+            return (name, rule, gamma, float(rng.choice([0.0, 0.01, 0.5])), counts)
+        if name == "tune":
+            lo, hi = [(1e-100, 1e100), (1e-100, 1e100), (0.05, 0.5), (0.9, 1.1)][int(rng.integers(0, 4))]
+            gamma = 1.0 if rng.random() < 0.5 else float(1.0 - rng.random())
+            return (name, float(rng.choice([0.2, 0.44, 0.7])), gamma, int(rng.choice([1, 50, 10 ** 6])), lo, hi, bool(rng.random() < 0.4))
+        if name == "mark":
+            return (name, str(rng.choice(["energy", "x"])))
+        if name == "blocks":
+            return (name, int(rng.choice([2, 3, 32, 64])), int(rng.choice([0, 1, 5, ref.n_chains // ref.n_rungs])))
+        if name == "upload":
+            return (name, bool(rng.random() < 0.5))
+        if name == "refused":
+            return (name, str(rng.choice(refusals(ref, ctx))))
         return (name,)
-    return ("state",)
+    return ("single", 1) if mutator else ("state",)
 
 
 def histogram_range(rng, ref, n_bins, at_edge):
@@ -521,8 +873,9 @@ def histogram_range(rng, ref, n_bins, at_edge):
     return lo, hi
 
 
-def apply_op(op, sides, rng, ref):
-    """`sides` take a mutating operation of a handle in the state `ref` is in; its arrays are drawn here from rng."""
+def apply_op(op, sides, rng, ref, ctx=None):
+    """`sides` take a mutating operation of a handle in the state `ref` is in; its arrays are drawn here from rng.  `ctx`: the walk's
+    context (new_context), for the operations that hand earlier fetches back."""
     name = op[0]
     K, M, R = ref.n_moves, ref.n_chains, ref.n_rungs
     if name == "single":
@@ -582,11 +935,130 @@ def apply_op(op, sides, rng, ref):
         acc = (tot * rng.uniform(0, 1, tot.shape)).astype(np.int64)
         for s in sides:
             s.upload_counters(acc, tot)
+    elif name == "bridge":
+        for s in sides:
+            s.bridge_accumulate(op[1])
+    elif name == "bridge_reset":
+        for s in sides:
+            s.bridge_fetch(reset=True)
+    elif name == "bridge_put":
+        stash = ctx["bridge"] if op[1] else None
+        for s in sides:
+            s.set_bridge(*((stash["records"], stash["n"]) if stash else (None, 0)))
+    elif name == "respace":
+        counts = respace_counts(rng, op[1], op[4], R, M // R)
+        for s in sides:
+            s.respace_ladder(op[1], op[2], op[3], counts)
+    elif name == "tune":
+        counts = None
+        if op[6]:                           # a global window: a few thousand calls per cell, or none at all in some
+            tot = rng.integers(0, 5000, (K, R))
+            if rng.random() < 0.3:
+                tot = tot * rng.integers(0, 2, (K, R))
+            counts = ((tot * rng.uniform(0, 1, (K, R))).astype(np.int64), tot.astype(np.int64))
+        for s in sides:
+            s.tune_rung_sigma(op[1], op[2], op[3], op[4], op[5], counts)
+    elif name == "window_restart":
+        for s in sides:
+            s.rung_window_restart()
+    elif name == "window_base":             # around the counters as they stand: some cells end up ahead of them
+        acc, tot = ref.rung_counter_totals()
+        bt = np.maximum(0, tot + rng.integers(-40, 8, tot.shape))
+        ba = np.minimum(bt, np.maximum(0, acc + rng.integers(-40, 3, acc.shape)))
+        for s in sides:
+            s.set_rung_window_base(ba, bt)
+    elif name == "mark":
+        for s in sides:
+            s.corr_mark(op[1])
+    elif name == "sample":
+        for s in sides:
+            s.corr_sample()
+    elif name == "corr_clear":
+        for s in sides:
+            s.corr_clear()
+    elif name == "corr_put":
+        c = ctx["corr"]
+        for s in sides:
+            s.set_corr(c["observable"], c["origin"], c["records"], c["steps"])
+    elif name == "blocks":
+        for s in sides:
+            s.set_blocks(op[1], op[2])
+    elif name == "blocks_off":
+        for s in sides:
+            s.set_blocks(0, 0)
+    elif name == "upload":
+        x = rng.normal(0.0, 1.5, M)
+        if ref.dtype == "f32":
+            x = x.astype(np.float32).astype(np.float64)
+        beta = None
+        if op[1]:                           # a geometric ladder of another ratio, or per-chain values that no ladder repeats
+            beta = (0.4 * rng.uniform(1.05, 2.0) ** np.arange(R))[np.arange(M) % R] if rng.random() < 0.7 else rng.uniform(0.2, 3.0, M)
+        for s in sides:
+            s.upload_state(x, beta)
     else:
         raise ValueError(op)
 
 
-def observe(op, eng, ref, rng, fail):
+def respace_counts(rng, rule, kind, R, L):
+    """The GLOBAL counts of a respacing: None (the handle's own); "explicit" ones that the rule can use; "zero": a count the rule
+    divides by is zero (status 2); "flat": no weight to spread (status 1)."""
+    if kind == "own":
+        return None
+    if rule == RP.ACCEPTANCE:
+        att = rng.integers(1, 50 * L + 2, R - 1)
+        acc = (att * rng.uniform(0, 1, R - 1)).astype(np.int64)
+        if kind == "zero":
+            j = int(rng.integers(0, R - 1))
+            att[j] = acc[j] = 0
+        if kind == "flat":
+            acc = att.copy()
+        return np.concatenate([att, acc]).astype(np.uint64)
+    n = np.zeros((R, 3), dtype=np.int64)
+    f = np.sort(rng.uniform(0, 1, R))[::-1]
+    if kind == "flat":
+        f[:] = 0.5
+    tot = rng.integers(1, 50 * L + 2, R)
+    n[:, 1] = np.round(f * tot).astype(np.int64)
+    n[:, 2] = tot - n[:, 1]
+    n[:, 0] = rng.integers(0, L + 1, R)
+    if kind == "zero":
+        n[int(rng.integers(0, R)), 1:] = 0
+    return n.astype(np.uint64)
+
+
+def refuse(which, side, ref, ctx):
+    """The call `which` of the fixed list on `side`: the exception it raised, or None when the side took it."""
+    try:
+        if which == "mask":
+            side.bridge_accumulate(BT.ALL if ref.bridge_mask != BT.ALL else BT.E)
+        elif which == "sample":
+            side.corr_sample()
+        elif which == "put_bridge":
+            side.set_bridge(ctx["bridge"]["records"], ctx["bridge"]["n"])
+        elif which == "put_corr":
+            c = ctx["corr"]
+            side.set_corr(c["observable"], c["origin"], c["records"], c["steps"])
+        elif which == "fetch_blocks":
+            side.bridge_fetch_blocks()
+        elif which == "tune":
+            side.tune_rung_sigma(0.44, 1.0, 1, 1e-100, 1e100, None)
+        elif which == "flow":
+            side.respace_ladder(RP.FLOW, 1.0, 0.0, None)
+        else:
+            raise ValueError(which)
+    except (AssertionError, ValueError):
+        raise
+    except Exception as exc:
+        return exc
+    return None
+
+
+def is_state_error(exc):
+    """An AmcError (the engine) or a Refused (the reference) that carries AMC_ERR_STATE."""
+    return type(exc).__name__ in ("AmcError", "Refused") and str(exc).startswith(f"amc error {ERR_STATE}:")
+
+
+def observe(op, eng, ref, rng, fail, ctx=None):
     name = op[0]
     if name == "state":
         (x, e), (xo, eo) = eng.download_state(), ref.download_state()
@@ -633,8 +1105,60 @@ def observe(op, eng, ref, rng, fail):
         want = ref.reduce_state_records()
         if not np.array_equal(fbits(got), fbits(want)):
             fail("records of sum e, sum x, sum x^2 differ", np.argwhere(fbits(got) != fbits(want))[:4])
+    elif name == "get_ladder":             # (the mutator "ladder" is set_ladder)
+        got, want = eng.ladder(), ref.ladder()
+        if not same_floats(got, want):
+            fail("the ladder differs", (got, want))
+    elif name == "respace_status":
+        if tuple(eng.respace_status()) != tuple(ref.respace_status()):
+            fail("respacing status differs", (eng.respace_status(), ref.respace_status()))
+    elif name == "tune_status":
+        (st, n), (sto, no) = eng.tune_status(), ref.tune_status()
+        if not same_ints(st, sto) or n != no:
+            fail("tuning status differs", (st, n, sto, no))
+        if not same_words(eng.rung_sigma(), ref.rung_sigma()):
+            fail("the table differs", (eng.rung_sigma(), ref.rung_sigma()))
+    elif name == "window":
+        for what, (a, t), (ao, to) in (("counts", eng.rung_window_counts(), ref.rung_window_counts()),
+                                       ("base", eng.rung_window_base(), ref.rung_window_base())):
+            if not (same_ints(a, ao) and same_ints(t, to)):
+                fail(f"window {what} differ", (a, ao, t, to))
+    elif name == "bridge_fetch":
+        (rec, n), (reco, no) = eng.bridge_fetch(), ref.bridge_fetch()
+        if n != no or not same_words(rec, reco):
+            fail("bridge records differ", (n, no, np.argwhere(fbits(rec) != fbits(reco))[:4] if np.shape(rec) == np.shape(reco) else None))
+        if ctx is not None and no > 0:
+            ctx["bridge"] = dict(R=ref.n_rungs, records=reco, n=no)
+    elif name == "corr_fetch":
+        (rec, st, ob), (reco, sto, obo) = eng.corr_fetch(), ref.corr_fetch()
+        if ob != obo or not same_ints(st, sto) or not same_words(rec, reco):
+            fail("correlation records differ", (ob, obo, st, sto))
+        if obo:
+            org, orgo = eng.corr_origin(), ref.corr_origin()
+            if not same_floats(org, orgo):
+                fail("the origin differs", np.flatnonzero(fbits(org) != fbits(orgo))[:8])
+            if ctx is not None:
+                ctx["corr"] = dict(R=ref.n_rungs, observable=obo, origin=orgo, records=reco, steps=sto)
+    elif name == "bridge_blocks":
+        (blk, n), (blko, no) = eng.bridge_fetch_blocks(), ref.bridge_fetch_blocks()
+        if n != no or not same_words(blk, blko):
+            fail("bridge records per block differ", (n, no, np.shape(blk), np.shape(blko)))
+        if not same_words(BL.merge_blocks(blk), eng.bridge_fetch()[0]):
+            fail("the merge over the blocks is not the merged bridge fetch")
+    elif name == "corr_blocks":
+        (blk, st, ob), (blko, sto, obo) = eng.corr_fetch_blocks(), ref.corr_fetch_blocks()
+        if ob != obo or not same_ints(st, sto) or not same_words(blk, blko):
+            fail("correlation records per block differ", (ob, obo, st, sto, np.shape(blk), np.shape(blko)))
+        if len(sto) and not same_words(BL.merge_blocks(blk), eng.corr_fetch()[0]):
+            fail("the merge over the blocks is not the merged correlation fetch")
     else:
         raise ValueError(op)
+
+
+def same_words(a, b):
+    """Records word for word (every word of a record is an integer held in a Float64: no NaN)."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(fbits(a), fbits(b))
 
 
 def run_walk(engine, reference, rng, n_ops, case=None, script=(), after_op=None):
@@ -658,17 +1182,31 @@ def run_walk(engine, reference, rng, n_ops, case=None, script=(), after_op=None)
     queue = [tuple(op) for op in script]
     if not queue:                           # most walks start with tracking on, and with a table where the handle takes one
         queue += [("track",)] * bool(rng.random() < 0.6) + [("table",)] * bool(rng.random() < 0.6 and possible(ref, "table"))
-    while len(ops) < max(n_ops, len(script)):
-        op = queue.pop(0) if queue else draw_op(rng, ref, steps_left)
+    ctx = new_context()
+    taken = 0                    # mutating operations taken
+    respaced_under_mark = tuned = retabled = False
+    wanted = 0 if script else MIN_MUTATORS      # (a pinned case runs its script and n_ops operations, no more)
+    while len(ops) < max(n_ops, len(script)) or taken < wanted:
+        op = queue.pop(0) if queue else draw_op(rng, ref, steps_left, ctx, mutator=len(ops) >= max(n_ops, len(script)))
         name = op[0]
         ops.append(op)
         if name in OBSERVERS:
-            observe(op, engine, ref, rng, fail)
+            if not possible(ref, name, ctx):
+                fail("the script asks for an observation the handle cannot give")
+            observe(op, engine, ref, rng, fail, ctx)
             if name == "walkers" and case.get("beta_kind") == "equal" and min(ref.tracking_counters()) >= 1:
                 events.add("equal beta with tracking: a round trip and an up trip")
             continue
-        if not possible(ref, name):
+        if not possible(ref, name, ctx) or (name == "refused" and op[1] not in refusals(ref, ctx)):
             fail("the script asks for an operation the handle cannot take")
+        if name == "refused":                  # both sides refuse with AMC_ERR_STATE; the observers that follow show nothing moved
+            for side, who in ((engine, "the engine"), (ref, "the reference")):
+                exc = refuse(op[1], side, ref, ctx)
+                if exc is None or not is_state_error(exc):
+                    fail(f"{who} did not refuse with AMC_ERR_STATE: {exc!r}")
+            continue
+        taken += 1
+        before = dict(n=ref.bridge_n, marked=ref.corr is not None, respaced=ref.respace_status()[1])
         n_x = op[1] if name in ("exchange", "sweep_exchange") else 0
         if n_x:
             t0, R = ref.exchange_step, ref.n_rungs
@@ -716,20 +1254,66 @@ def run_walk(engine, reference, rng, n_ops, case=None, script=(), after_op=None)
             cross_in = None
         arrays = int(rng.integers(0, 2 ** 62))     # both sides draw the operation's arrays from generators with this one seed
         try:
-            apply_op(op, (engine,), np.random.default_rng(arrays), ref)
+            apply_op(op, (engine,), np.random.default_rng(arrays), ref, ctx)
         except AssertionError:
             raise
         except Exception as exc:               # a refusal by the engine of something the reference takes
             fail(f"the engine refused: {exc!r}")
         if after_op is not None:
             after_op(op)
-        apply_op(op, (ref,), np.random.default_rng(arrays), ref)
+        apply_op(op, (ref,), np.random.default_rng(arrays), ref, ctx)
+        # the combinations of the ladder tools that the host test counts
+        if name == "bridge":
+            ctx["snapshots"] += 1
+            if crossing and ref.partition is not None:
+                events.add("partition on a shard across 2^32")
+        elif name in ("mark", "sample"):
+            ctx["samples"] += 1
+            if name == "sample" and respaced_under_mark:
+                events.add("respacing with a mark standing, then a sample")
+            if name == "mark":
+                respaced_under_mark = False
+                if crossing and ref.partition is not None:
+                    events.add("partition on a shard across 2^32")
+        elif name == "respace":
+            took = ref.respace_status()[1] > before["respaced"]
+            if before["n"]:
+                events.add("respacing taken with snapshots accumulated" if took else
+                           "respacing not taken (status != 0) with snapshots accumulated")
+            if took and ref.partition is not None:
+                events.add("respacing taken under a partition")
+            if took and ref.dtype == "f32":
+                events.add("Float32 ladder respaced")
+            respaced_under_mark = respaced_under_mark or before["marked"]
+            if op[4] != "own" and ref.offset > 0:
+                events.add("explicit counts on a shard that does not start at 0")
+        elif name == "tune":
+            st = ref.tune_status()[0]
+            if np.any(st == TU.INCONSISTENT):
+                events.add("tuning with an inconsistent window")
+            if np.any(st == TU.CLAMPED):
+                events.add("tuning that clamps")
+            if tuned and retabled:
+                events.add("table rewritten between two tunings")
+            tuned, retabled = True, False
+            if op[6] and ref.offset > 0:
+                events.add("explicit counts on a shard that does not start at 0")
+        elif name == "table":
+            retabled = tuned
+        elif name in ("clear", "ladder"):
+            tuned = retabled = False
+        elif name == "upload" and before["marked"]:
+            events.add("upload with a mark standing")
+        elif name == "blocks" and before["n"]:
+            events.add("set_blocks with snapshots accumulated")
+        if ref.corr is None:
+            respaced_under_mark = False
     if case.get("plant"):
         events.add("non-finite positions")
     # the end: everything
     ops.append(("end",))
     for name in OBSERVERS:
-        if possible(ref, name):
+        if possible(ref, name, ctx):
             observe((name, 7) if name == "rung_sums" else (name, 200, False) if name == "rung_hist" else (name,), engine, ref, rng, fail)
     if engine.step != ref.step:
         fail("step index differs", (engine.step, ref.step))
@@ -737,7 +1321,7 @@ def run_walk(engine, reference, rng, n_ops, case=None, script=(), after_op=None)
         fail("exchange step index differs", (engine.exchange_step, ref.exchange_step))
     if engine.estimator_step != ref.estimator_step:
         fail("estimator step index differs", (engine.estimator_step, ref.estimator_step))
-    return dict(ops=ops[:-1], events=events)
+    return dict(ops=ops[:-1], events=events, taken=taken)
 
 
 def run_case(factory, case, reference_factory=LadderReference, after_op=None):

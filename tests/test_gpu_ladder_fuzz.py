@@ -5,9 +5,19 @@ steps, widths per rung set, rewritten and cleared behind queued sweeps, tracking
 counters, exchange step indices up to 2^48, another ladder in the middle -- and the observers in between: state, counters, labels,
 flow, trips, per-rung sums, histograms and counter totals, the callback records.  Everything bit for bit or integer for integer.
 
+The same walk draws the ladder tools among them, so that they meet on one handle in an order nobody wrote down: bridge snapshots
+under a drawn mask, reset and put back; respacings by acceptance and by flow, with the handle's own counts and with explicit global
+ones, taken and not; tunings with their window restarted, its base set and Move counters uploaded behind it; marks, samples and
+set_corr; partitions of 2 to 64 blocks at chunks of 0, 1, 5 and every ladder; upload_state in the middle; the calls that must be
+refused with AMC_ERR_STATE -- observed through the ladder, the two status records and the table, the window, the bridge and
+correlation records word for word, merged and per block (whose merge must be the merged fetch).  What each call zeroes, keeps or
+refuses is the text of include/amc.h, held in ladder_fuzz.LadderReference.
+
 The pinned cases (ladder_fuzz.PINNED) come first; AMC_LADDER_FUZZ_CASES (default 40 drawn cases) and AMC_LADDER_FUZZ_SEED widen or
-move the sample.  Measured on an MI355X: the file at its defaults (6 pinned + 40 drawn cases) takes 16.3 s, most of it the host twins
-and the run-time compilation of the Float32-state kernels; 300 drawn cases of another seed take 44 s.
+move the sample.  Measured on an MI355X, one box, one session: the file at its defaults (10 pinned + 40 drawn cases) takes 20.0 s
+the first time and 4.8 s run again at once (the Float32-state kernels are compiled at run time and kept: the difference is theirs);
+300 drawn cases of another seed take 39.0 s.  The file as it was before the ladder tools (6 pinned + 40 drawn cases; 16.3 s on
+record) takes 6.6 s in that same warm state: the twins' extra Python is not what the time goes to, the slowest single walk is 3.2 s.
 Custom (run-time compiled) potentials stay out: each costs seconds of compile time, and the exchange files cover them.
 """
 import os

@@ -1,6 +1,7 @@
 """The random ladder walks (tests/ladder_fuzz.py) on the host: that the cases are well formed and repeat, that the default case list
 meets the combinations it is there for, and that the walk notices a reference with one deliberate defect -- the evidence that
-tests/test_gpu_ladder_fuzz.py would notice the same kinds of error in a kernel.  No GPU: both sides of the walk are reference objects."""
+tests/test_gpu_ladder_fuzz.py would notice the same kinds of error in a kernel, or in the host code that decides what a call resets
+and what it leaves alone.  No GPU: both sides of the walk are reference objects."""
 import collections
 
 import numpy as np
@@ -8,6 +9,7 @@ import pytest
 
 import exchange_twin as X
 import ladder_fuzz as LF
+import respace_twin as RP
 import track_twin as T
 
 N_CASES, SEED = LF.DEFAULT_CASES, LF.DEFAULT_SEED       # the list tests/test_gpu_ladder_fuzz.py walks on the device by default
@@ -25,6 +27,19 @@ EVENTS = [
     "Float32 state on a handle with the slice knobs",
     "Float32 parameters with tracking",
     "counts cross 65 536 after an upload while a table is set",
+    # the ladder tools: bridge sums, respacing, tuning and its window, time correlation, jackknife blocks
+    "respacing taken with snapshots accumulated",
+    "respacing not taken (status != 0) with snapshots accumulated",
+    "respacing taken under a partition",
+    "respacing with a mark standing, then a sample",
+    "tuning with an inconsistent window",
+    "tuning that clamps",
+    "table rewritten between two tunings",
+    "explicit counts on a shard that does not start at 0",
+    "upload with a mark standing",
+    "set_blocks with snapshots accumulated",
+    "partition on a shard across 2^32",
+    "Float32 ladder respaced",
 ]
 
 
@@ -68,6 +83,15 @@ def test_default_list_meets_every_combination(default_walks):
     assert not [name for name in LF.OPERATIONS if ops[name] < 3], dict(ops)
     assert not [name for name in EVENTS if events[name] < 1], dict(events)
     # both forms of the per-rung histogram: LDS rows while R (bins + 3) <= 12 288 counters, one global atomic per chain beyond
+    assert set(LF.NEW_OPERATIONS) <= set(LF.OPERATIONS)
+    # at most 40 % of the operations observe, and every drawn walk takes at least 8 mutating operations
+    n_observers = sum(ops[name] for name in LF.OBSERVERS)
+    assert n_observers <= 0.4 * sum(ops.values()), (n_observers, sum(ops.values()))
+    assert not [info["taken"] for _, info in default_walks[len(LF.PINNED):] if info["taken"] < LF.MIN_MUTATORS]
+    # no walk goes past the room a blocked accumulator starts with more than once
+    for _, info in default_walks:
+        names = [op[0] for op in info["ops"]]
+        assert names.count("bridge") <= LF.MAX_SNAPSHOTS and names.count("mark") + names.count("sample") <= LF.MAX_SAMPLES
     forms = {case["R"] * (op[1] + 3) <= 12_288 for case, info in default_walks for op in info["ops"] if op[0] == "rung_hist"}
     assert forms == {True, False}
 
@@ -114,7 +138,7 @@ class TableReadTransposed(LF.LadderReference):
         return np.array([[flat[r * K + k] for r in range(R)] for k in range(K)])
 
 
-class _EndRuleOnTheLeavingLabel(T.TrackTwin):
+class _EndRuleOnTheLeavingLabel(RP.RespaceTwin):
     def _swapped(self, a, r):
         lab = self.lab
         if lab is None:
@@ -168,8 +192,98 @@ class HistogramSpillsTheLastBin(LF.LadderReference):
     hist_row = staticmethod(_row_with_the_last_bin_open)
 
 
+class RespacingLeavesTheBridgeRecords(LF.LadderReference):
+    """8: a respacing that is taken leaves the bridge records and their count."""
+
+    def _respaced(self):
+        pass
+
+
+class RespacingClearsTheMask(LF.LadderReference):
+    """9: a respacing that is taken frees the column mask along with the records."""
+
+    def _respaced(self):
+        super()._respaced()
+        self.bridge_mask = 0
+
+
+class RefusedRespacingZeroesTheGaps(LF.LadderReference):
+    """10: a respacing that is not taken (status != 0) zeroes the gap counters."""
+
+    def respace_ladder(self, *a, **k):
+        super().respace_ladder(*a, **k)
+        if self.tw.status != 0:
+            self.tw.accepted[:] = 0
+            self.tw.attempted[:] = 0
+
+
+class BlockRowsSurviveARespacing(LF.LadderReference):
+    """11: a respacing that is taken zeroes the merged records and leaves the rows per block."""
+
+    def _respaced(self):
+        rows = self.bridge_blk
+        super()._respaced()
+        self.bridge_blk = rows
+
+
+class BlockOfTheLocalLadder(LF.LadderReference):
+    """12: the block of a ladder is formed from its local index."""
+
+    def block_first(self):
+        return 0
+
+
+class WindowIgnoresTheBase(LF.LadderReference):
+    """13: the tuning reads the counters since they began, not since the window's base."""
+
+    def window_base_for_tuning(self):
+        return np.zeros_like(self.base)
+
+
+class TableDropsTheBase(LF.LadderReference):
+    """14: set_rung_sigma drops the window base."""
+
+    def set_rung_sigma(self, sigma):
+        super().set_rung_sigma(sigma)
+        if sigma is not None and self.n_rungs:
+            self.base[:] = 0
+
+
+class UploadKeepsTheMark(LF.LadderReference):
+    """15: upload_state keeps the mark."""
+
+    def upload_state(self, x, beta=None):
+        mark = self.corr
+        super().upload_state(x, beta)
+        self.corr = mark
+
+
+class StepsHoldTheExchangeIndex(LF.LadderReference):
+    """16: steps[s] records the exchange step index."""
+
+    def corr_steps_entry(self):
+        return self.exchange_step
+
+
+class GroupsFollowTheWalker(LF.LadderReference):
+    """17: the correlation groups follow the walker, not the rung."""
+
+    def _observe(self, kind):
+        o = super()._observe(kind)
+        if not self.tracking:
+            return o
+        R = self.n_rungs
+        walker = (self.tw.lab & np.uint8(63)).astype(np.int64)
+        out = o.copy()
+        out[(np.arange(o.size) // R) * R + walker] = o
+        return out
+
+
 DEFECTS = [ParityFromTheNextStep, DrawKeyedByLocalId, TableReadTransposed, EndRuleOnTheLeavingLabel, LadderKeepsGapCounters,
-           StepIndexOf32Bits, HistogramSpillsTheLastBin]
+           StepIndexOf32Bits, HistogramSpillsTheLastBin,
+           RespacingLeavesTheBridgeRecords, RespacingClearsTheMask, RefusedRespacingZeroesTheGaps, BlockRowsSurviveARespacing,
+           BlockOfTheLocalLadder, WindowIgnoresTheBase, TableDropsTheBase, UploadKeepsTheMark, StepsHoldTheExchangeIndex,
+           GroupsFollowTheWalker]
 
 
 @pytest.mark.parametrize("defect", DEFECTS, ids=[d.__name__ for d in DEFECTS])
