@@ -1,7 +1,8 @@
 // amc_blocks.h -- the bridge sums and the time correlation kept per jackknife block of ladders (amc_set_blocks):
 // the partition's index arithmetic -- which launch, HIP block, thread and trip visits which local ladder -- as host-and-device inline
-// functions, then bridge_sums_blocks_kernel / corr_sums_blocks_kernel, in which every HIP block serves ONE jackknife block, and the two
-// finishing kernels that merge the rows of the HIP blocks of each jackknife block.
+// functions, then bridge_sums_blocks_kernel / corr_sums_blocks_kernel, in which every HIP block serves ONE jackknife block.  Prologue
+// and block end are the frame's (amc_exchange.h "the frame of the sums by group"); bridge_finish_kernel and corr_finish_kernel merge the
+// rows of the HIP blocks of each jackknife block.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
 // With AMC_BLOCKS_INDEX_ONLY defined the file is its index arithmetic alone, plain host C++ once __host__ and __device__ are empty: the
 // same text then runs on the CPU under the sanitizers (tests/aux/blocks_plan_host.cpp).
@@ -136,47 +137,6 @@ AMC_BLK_HD int grid_round(int grid, int n_blocks) { return (grid + n_blocks - 1)
 
 namespace amc {
 
-// The end of a block of rung_sums_kernel / bridge_sums_kernel / corr_sums_kernel for a lane with the columns `mine` of group r on its
-// books (0: none): integer max / or per slot, barrier, 64-bit integer LDS adds of the lane's multiples at the settled level, barrier,
-// the block's rows in the XS_ROW_R form by consecutive threads.  The slots are cleared and a barrier has passed.
-template <int NC>
-__device__ __forceinline__ void blocks_rows_end(const RLaneCols<NC>& L, int r, int mine, int n_slots, int* s_top, unsigned int* s_flags,
-                                                unsigned long long (*s_k)[4], xs_word* out)
-{
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if ((mine >> c) & 1) {
-            atomicMax(&s_top[r * NC + c], L.top[c]);
-            if (L.flags[c]) atomicOr(&s_flags[r * NC + c], L.flags[c]);
-        }
-    __syncthreads();                                              // the levels are settled
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if ((mine >> c) & 1) {
-            const int s = r * NC + c;
-            xs::RPair k = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n, L.top[c]);
-            const int d = s_top[s] - L.top[c];
-            if (d == 0) {
-                rung_lds_add(&s_k[s][0], k.k1);
-                rung_lds_add(&s_k[s][2], k.k2);
-            } else if (d == 1) {
-                rung_lds_add(&s_k[s][2], k.k1);
-            }
-        }
-    __syncthreads();
-    for (int w = threadIdx.x; w < n_slots * XS_ROW_R; w += AMC_BLOCK) {
-        const int s = w / XS_ROW_R, j = w - s * XS_ROW_R;
-        xs_word v = 0ull;
-        if (j == 0) v = (xs_word)(uint32_t)s_top[s] | ((xs_word)s_flags[s] << 32);
-        else if (j < 5) {
-            const int which = (j - 1) >> 1;                       // k1 / k2
-            const xs::i128 k = xs::i128_add(xs::i128_shl(xs::i128_of((long long)s_k[s][2 * which + 1]), 32), xs::i128{(uint64_t)s_k[s][2 * which], 0});
-            v = ((j - 1) & 1) ? (xs_word)k.hi : (xs_word)k.lo;
-        }
-        out[w] = v;                                               // (a slot nobody deposited into is an empty row: top XS_LMIN, zeros)
-    }
-}
-
 // bridge_sums_kernel with the traversal of blk::Walk: HIP block k sums the ladders of jackknife block k mod B alone, so its rows are
 // rows of that block; the summands (bridge_add), the lane arithmetic and the end of the block are the unpartitioned pass's own.  Four
 // ladders' loads in flight per lane across the flattened (chunk, trip) sequence.
@@ -187,13 +147,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void bridge_sums_blocks_kernel(const Bri
     __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];                               // exp for every potential
     __shared__ int s_top[MAX_SLOTS];
     __shared__ unsigned int s_flags[MAX_SLOTS];
-    __shared__ unsigned long long s_k[MAX_SLOTS][4];                    // k1.lo, k1.hi, k2.lo, k2.hi (hi: two's complement)
+    __shared__ unsigned long long s_k[MAX_SLOTS][4];
     const int n_slots = a.n_rungs * BR_COLS;
-    for (int s = threadIdx.x; s < n_slots; s += AMC_BLOCK) {
-        s_top[s] = xs::XS_LMIN;
-        s_flags[s] = 0u;
-        s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
-    }
+    group_slots_clear(n_slots, s_top, s_flags, s_k);
     stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);                  // (ends in a barrier: the slots are cleared too)
 
     blk::Walk w;
@@ -225,7 +181,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void bridge_sums_blocks_kernel(const Bri
         bridge_add<POT>(L, x3, b3, n3, p3, s_math, mine);
     }
     if (L.n == 0) mine = 0;
-    blocks_rows_end<BR_COLS>(L, r, mine, n_slots, s_top, s_flags, s_k, a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R);
+    group_rows_end<BR_COLS>(L, r, mine, n_slots, s_top, s_flags, s_k, a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R);
 }
 
 // corr_sums_kernel with the same traversal (a mark stores the origin values of the ladders it visits: every local ladder, once).
@@ -238,11 +194,7 @@ __global__ __launch_bounds__(AMC_BLOCK) void corr_sums_blocks_kernel(const CorrA
     __shared__ unsigned int s_flags[MAX_SLOTS];
     __shared__ unsigned long long s_k[MAX_SLOTS][4];
     const int n_slots = a.n_rungs * CORR_COLS;
-    for (int s = threadIdx.x; s < n_slots; s += AMC_BLOCK) {
-        s_top[s] = xs::XS_LMIN;
-        s_flags[s] = 0u;
-        s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
-    }
+    group_slots_clear(n_slots, s_top, s_flags, s_k);
     if (POT == POT_CUSTOM) stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier)
 
     blk::Walk w;
@@ -276,53 +228,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void corr_sums_blocks_kernel(const CorrA
         corr_add<POT>(L, x3, a3, a, i3, s_math);
     }
     __syncthreads();                                              // the slots are cleared
-    blocks_rows_end<CORR_COLS>(L, r, L.n > 0 ? (1 << CORR_COLS) - 1 : 0, n_slots, s_top, s_flags, s_k,
+    group_rows_end<CORR_COLS>(L, r, L.n > 0 ? (1 << CORR_COLS) - 1 : 0, n_slots, s_top, s_flags, s_k,
                                a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R);
 }
-
-// The accumulator of the blocked bridge sums: rows [b][r][c] of XS_ROW_R words in bridge_finish_kernel's form (word 5 of a row is 1
-// once a snapshot has been merged into it), then the number of snapshots at word B R BR_COLS XS_ROW_R.
-// Block (b, s) of 64 threads, s = r BR_COLS + c: lane i merges the rows of the HIP blocks b + i B, b + (i + 64) B, ... of every launch
-// (the grids are multiples of B, so those are the rows k with k mod B == b), thread 0 the lanes' partials and the accumulator's own
-// row, which it replaces.  Block 0 counts the snapshot, once.
-#if AMC_PLAIN_KERNELS
-AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void bridge_finish_blocks_kernel(const xs_word* rows, int n_rows, int n_rungs, int cols, int n_blocks,
-                                                                                      xs_word* acc)
-{
-    __shared__ xs::PartR s_part[64];
-    const int n_slots = n_rungs * BR_COLS, b = blockIdx.x / n_slots, s = blockIdx.x - b * n_slots;
-    if (blockIdx.x == 0 && threadIdx.x == 0) acc[(int64_t)n_blocks * n_slots * XS_ROW_R] += 1ull;
-    if (!((bridge_cols_at(cols, s / BR_COLS, n_rungs) >> (s % BR_COLS)) & 1)) return;
-    xs::PartR p = xs::part_r_empty();
-    for (int k = b + (int)threadIdx.x * n_blocks; k < n_rows; k += 64 * n_blocks)
-        xs::part_r_merge(p, xs_load_r_row(rows + ((int64_t)k * n_slots + s) * XS_ROW_R));
-    s_part[threadIdx.x] = p;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        xs_word* row = acc + ((int64_t)b * n_slots + s) * XS_ROW_R;
-        for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
-        xs::part_r_merge(p, bridge_load_row(row));
-        xs_store_r_row(row, p);
-        row[5] = 1ull;
-    }
-}
-
-// ... and of the time correlation: `acc` points at the rows [b][g][c] of ONE sample, which are written once.
-AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void corr_finish_blocks_kernel(const xs_word* rows, int n_rows, int n_groups, int n_blocks, xs_word* acc)
-{
-    __shared__ xs::PartR s_part[64];
-    const int n_slots = n_groups * CORR_COLS, b = blockIdx.x / n_slots, s = blockIdx.x - b * n_slots;
-    xs::PartR p = xs::part_r_empty();
-    for (int k = b + (int)threadIdx.x * n_blocks; k < n_rows; k += 64 * n_blocks)
-        xs::part_r_merge(p, xs_load_r_row(rows + ((int64_t)k * n_slots + s) * XS_ROW_R));
-    s_part[threadIdx.x] = p;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
-        xs_store_r_row(acc + ((int64_t)b * n_slots + s) * XS_ROW_R, p);
-    }
-}
-#endif
 
 }  // namespace amc
 

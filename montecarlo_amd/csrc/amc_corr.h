@@ -1,6 +1,6 @@
 // amc_corr.h -- time correlation from one time origin (amc_corr_mark .. amc_corr_fetch): corr_sums_kernel, the
 // reproducible sums of O, O^2 and a O by group, a = the observable at the mark, and corr_finish_kernel, which leaves them in the
-// slot of their lag.
+// slot of their lag -- with a partition (amc_blocks.h) per jackknife block.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
 #pragma once
 
@@ -44,9 +44,9 @@ __device__ __forceinline__ void corr_add(RLaneCols<CORR_COLS>& L, real_t x, doub
 
 // One memory-bound pass in the form of rung_sums_kernel / bridge_sums_kernel (amc_exchange.h): thread id = l0 G + g, a thread keeps
 // its group for the whole launch and advances by (threads / G) ladders per trip, four loads of x -- and, in a sample, of a -- in
-// flight per lane; a mark reads 8 B and writes 8 B per chain, a sample reads 16 B (Float64 state).  End of block as there: integer
-// max / or per slot, barrier, 64-bit integer LDS adds of the lanes' multiples at the settled level, barrier, rows in the XS_ROW_R
-// form by consecutive threads.  No floating-point atomic, no block waits on another, plain vector stores only.
+// flight per lane; a mark reads 8 B and writes 8 B per chain, a sample reads 16 B (Float64 state).  Prologue and block end are the
+// frame's (amc_exchange.h "the frame of the sums by group"): no floating-point atomic, no block waits on another, plain vector stores
+// only.  A block without a chain of a group leaves that group's rows empty.
 template <int POT>
 __global__ __launch_bounds__(AMC_BLOCK) void corr_sums_kernel(const CorrArgs a)
 {
@@ -54,13 +54,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void corr_sums_kernel(const CorrArgs a)
     __shared__ AMC_MATH_LDS_ALIGN double s_math[POT == POT_CUSTOM ? TAB_DOUBLES : 1];      // a custom potential may call amc_exp
     __shared__ int s_top[MAX_SLOTS];
     __shared__ unsigned int s_flags[MAX_SLOTS];
-    __shared__ unsigned long long s_k[MAX_SLOTS][4];                    // k1.lo, k1.hi, k2.lo, k2.hi (hi: two's complement)
+    __shared__ unsigned long long s_k[MAX_SLOTS][4];
     const int n_slots = a.n_rungs * CORR_COLS;
-    for (int s = threadIdx.x; s < n_slots; s += AMC_BLOCK) {
-        s_top[s] = xs::XS_LMIN;
-        s_flags[s] = 0u;
-        s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
-    }
+    group_slots_clear(n_slots, s_top, s_flags, s_k);
     if (POT == POT_CUSTOM) stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier)
 
     const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
@@ -90,58 +86,18 @@ __global__ __launch_bounds__(AMC_BLOCK) void corr_sums_kernel(const CorrArgs a)
         for (; i < end; i += step) corr_add<POT>(L, a.x[i], a.mark ? 0.0 : a.origin[i], a, i, s_math);
     }
     __syncthreads();                                              // the slots are cleared
-    const bool mine = L.n > 0;
-#pragma unroll
-    for (int c = 0; c < CORR_COLS; ++c)
-        if (mine) {
-            atomicMax(&s_top[r * CORR_COLS + c], L.top[c]);
-            if (L.flags[c]) atomicOr(&s_flags[r * CORR_COLS + c], L.flags[c]);
-        }
-    __syncthreads();                                              // the levels are settled
-#pragma unroll
-    for (int c = 0; c < CORR_COLS; ++c)
-        if (mine) {
-            const int s = r * CORR_COLS + c;
-            xs::RPair k = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n, L.top[c]);
-            const int d = s_top[s] - L.top[c];
-            if (d == 0) {
-                rung_lds_add(&s_k[s][0], k.k1);
-                rung_lds_add(&s_k[s][2], k.k2);
-            } else if (d == 1) {
-                rung_lds_add(&s_k[s][2], k.k1);
-            }
-        }
-    __syncthreads();
-    xs_word* out = a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R;
-    for (int w = threadIdx.x; w < n_slots * XS_ROW_R; w += AMC_BLOCK) {
-        const int s = w / XS_ROW_R, j = w - s * XS_ROW_R;
-        xs_word v = 0ull;
-        if (j == 0) v = (xs_word)(uint32_t)s_top[s] | ((xs_word)s_flags[s] << 32);
-        else if (j < 5) {
-            const int which = (j - 1) >> 1;                       // k1 / k2
-            const xs::i128 k = xs::i128_add(xs::i128_shl(xs::i128_of((long long)s_k[s][2 * which + 1]), 32), xs::i128{(uint64_t)s_k[s][2 * which], 0});
-            v = ((j - 1) & 1) ? (xs_word)k.hi : (xs_word)k.lo;
-        }
-        out[w] = v;                                               // (a block without a chain of the group leaves an empty row: top XS_LMIN, zeros)
-    }
+    group_rows_end<CORR_COLS>(L, r, L.n > 0 ? (1 << CORR_COLS) - 1 : 0, n_slots, s_top, s_flags, s_k, a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R);
 }
 
-// The launches' block rows merged into the rows of ONE sample: bridge_finish_kernel with a slot offset -- `acc` points at the sample's
-// rows --, block s = g CORR_COLS + c of 64 threads, lane i merges the rows i, i + 64, ... (part_r_merge: integers, so the order is
-// immaterial), thread 0 the lanes' partials.  A sample's rows are written once: whatever an earlier mark left there is replaced.
+// The launches' block rows merged into the rows [b][g][c] of ONE sample, at which `acc` points: bridge_finish_kernel's blocks and
+// strides (n_blocks = 1 without a partition) without an accumulator to add to -- a sample's rows are written once, whatever an
+// earlier mark left there is replaced.
 #if AMC_PLAIN_KERNELS
-AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void corr_finish_kernel(const xs_word* rows, int n_rows, int n_groups, xs_word* acc)
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void corr_finish_kernel(const xs_word* rows, int n_rows, int n_groups, int n_blocks, xs_word* acc)
 {
-    __shared__ xs::PartR s_part[64];
-    const int s = blockIdx.x, n_slots = n_groups * CORR_COLS;
-    xs::PartR p = xs::part_r_empty();
-    for (int b = threadIdx.x; b < n_rows; b += 64) xs::part_r_merge(p, xs_load_r_row(rows + ((int64_t)b * n_slots + s) * XS_ROW_R));
-    s_part[threadIdx.x] = p;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
-        xs_store_r_row(acc + (int64_t)s * XS_ROW_R, p);
-    }
+    const int n_slots = n_groups * CORR_COLS, b = blockIdx.x / n_slots, s = blockIdx.x - b * n_slots;
+    const xs::PartR p = group_rows_merge(rows, n_rows, n_slots, s, b, n_blocks);
+    if (threadIdx.x == 0) xs_store_r_row(acc + ((int64_t)b * n_slots + s) * XS_ROW_R, p);
 }
 #endif
 

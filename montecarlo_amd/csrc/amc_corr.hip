@@ -11,9 +11,11 @@ static_assert(AMC_CORR_E == amc::CORR_E && AMC_CORR_X == amc::CORR_X && AMC_CORR
 
 static const size_t CORR_BYTES = (size_t)amc::CORR_ACC_WORDS * sizeof(amc::xs_word);      // d_corr (amc_corr.h CORR_ACC_WORDS)
 
-static inline int corr_groups(const amc_handle* h) { return h->lad.n_rungs ? h->lad.n_rungs : 1; }
-// words of one sample's rows
-static inline size_t corr_sample_words(int groups) { return (size_t)groups * amc::CORR_COLS * amc::XS_ROW_R; }
+// words of one sample's rows: with a partition a row per (block, group, column)
+static inline size_t corr_sample_words(const amc_handle* h)
+{
+    return (size_t)std::max(1, h->blocks.n_blocks) * pass_groups(h) * amc::CORR_COLS * amc::XS_ROW_R;
+}
 
 static int corr_room(amc_handle* h)
 {
@@ -24,17 +26,17 @@ static int corr_room(amc_handle* h)
     return zeroed_words(h, &h->corr.d_corr, CORR_BYTES);
 }
 
-// The blocked accumulator (a partition is set): rows [sample][b][g][c], room for slot `slot` -- 16 samples at a mark, doubled when a
-// sample needs more (what the slots below it hold is kept), so that its size follows B, G and the lags in use.
-static inline size_t corr_block_sample_words(const amc_handle* h) { return (size_t)h->blocks.n_blocks * corr_sample_words(corr_groups(h)); }
-static int corr_blocks_room(amc_handle* h, int slot)
+// The blocked accumulator (a partition is set): rows [sample][b][g][c], room for slot `slot`, so that its size follows B, G and the
+// lags in use.  keep: what the slots below it hold is kept, and the room doubles (16 samples at a mark); otherwise a restore is
+// about to write slots 0 .. slot, and the room is theirs (16 at least).
+static int corr_blocks_room(amc_handle* h, int slot, bool keep)
 {
-    const size_t spw = corr_block_sample_words(h);
+    const size_t spw = corr_sample_words(h);
     if ((size_t)(slot + 1) * spw <= h->blocks.corr_blk_words) return AMC_OK;
-    const size_t need = (size_t)std::min<int>(AMC_CORR_MAX_LAGS, std::max(16, 2 * slot)) * spw;
+    const size_t need = (size_t)(keep ? std::min<int>(AMC_CORR_MAX_LAGS, std::max(16, 2 * slot)) : std::max(16, slot + 1)) * spw;
     amc::xs_word* grown = nullptr;
     AMC_HIP(hipMalloc(&grown, need * sizeof(amc::xs_word)));
-    if (slot && h->blocks.d_corr_blk)
+    if (keep && slot && h->blocks.d_corr_blk)
         (void)hipMemcpyAsync(grown, h->blocks.d_corr_blk, (size_t)slot * spw * sizeof(amc::xs_word), hipMemcpyDeviceToDevice, h->stream);
     const hipError_t e = hipStreamSynchronize(h->stream);      // (a finishing kernel queued earlier may still write the old rows)
     (void)hipFree(h->blocks.d_corr_blk);
@@ -44,37 +46,46 @@ static int corr_blocks_room(amc_handle* h, int slot)
     return AMC_OK;
 }
 
-// One pass into slot `slot`: the sums of the sample, and with `mark` the origin values too.
+// One pass into slot `slot`: the sums of the sample, and with `mark` the origin values too.  With a partition the traversal of
+// amc_blocks.h into the blocked accumulator.
 static int corr_pass(amc_handle* h, int observable, int slot, bool mark)
 {
     AMC_HIP(hipSetDevice(h->device));
     // (as in front of a bridge snapshot: a learning step left pending belongs in front of this point of the stream)
     AMC_TRY(pg_resolve(h));
+    const int B = h->blocks.n_blocks;
     RungPass p;
     amc::CorrArgs a = {};
     a.mark = mark ? 1 : 0;
-    if (h->blocks.n_blocks) {           // a row per (block, group, column): the traversal and the finishing kernel of amc_blocks.h
-        const int B = h->blocks.n_blocks;
-        AMC_TRY(blocks_pass_plan(h, amc::CORR_COLS, &p));
-        AMC_TRY(corr_room(h));
-        AMC_TRY(corr_blocks_room(h, slot));
-        a.origin = h->corr.d_origin;
-        AMC_TRY(blocks_pass_launch(h, p, a, observable, "amc::corr_sums_blocks_kernel", (const void*)amc::corr_sums_blocks_kernel<amc::POT_DOUBLE_WELL>,
-                                   (const void*)amc::corr_sums_blocks_kernel<amc::POT_HARMONIC>));
-        hipLaunchKernelGGL(amc::corr_finish_blocks_kernel, dim3(B * p.groups * amc::CORR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows,
-                           p.n_blocks(), p.groups, B, h->blocks.d_corr_blk + (size_t)slot * corr_block_sample_words(h));
-        AMC_HIP(hipGetLastError());
-        return AMC_OK;
-    }
-    AMC_TRY(rung_pass_plan(h, amc::CORR_COLS, &p));
+    AMC_TRY(rung_pass_plan(h, amc::CORR_COLS, B != 0, &p));
     AMC_TRY(corr_room(h));
+    if (B) AMC_TRY(corr_blocks_room(h, slot, true));
     a.origin = h->corr.d_origin;
-    AMC_TRY(rung_pass_launch(h, p, a, observable, "amc::corr_sums_kernel", (const void*)amc::corr_sums_kernel<amc::POT_DOUBLE_WELL>,
-                             (const void*)amc::corr_sums_kernel<amc::POT_HARMONIC>));
-    hipLaunchKernelGGL(amc::corr_finish_kernel, dim3(p.groups * amc::CORR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows, p.n_blocks(),
-                       p.groups, h->corr.d_corr + (size_t)slot * corr_sample_words(p.groups));
+    if (B)
+        AMC_TRY(rung_pass_launch(h, p, a, observable, "amc::corr_sums_blocks_kernel", (const void*)amc::corr_sums_blocks_kernel<amc::POT_DOUBLE_WELL>,
+                                 (const void*)amc::corr_sums_blocks_kernel<amc::POT_HARMONIC>));
+    else
+        AMC_TRY(rung_pass_launch(h, p, a, observable, "amc::corr_sums_kernel", (const void*)amc::corr_sums_kernel<amc::POT_DOUBLE_WELL>,
+                                 (const void*)amc::corr_sums_kernel<amc::POT_HARMONIC>));
+    hipLaunchKernelGGL(amc::corr_finish_kernel, dim3((B ? B : 1) * p.groups * amc::CORR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows,
+                       p.n_blocks(), p.groups, B ? B : 1, (B ? h->blocks.d_corr_blk : h->corr.d_corr) + (size_t)slot * corr_sample_words(h));
     AMC_HIP(hipGetLastError());
     return AMC_OK;
+}
+
+// A mark adopted (amc_corr_mark, the setters), and reported (the fetches).
+static void corr_adopt(amc_handle* h, int observable, const uint64_t* steps, int n_samples)
+{
+    h->corr.observable = observable;
+    h->corr.groups = pass_groups(h);
+    h->corr.n_samples = n_samples;
+    for (int s = 0; s < n_samples; ++s) h->corr.steps[s] = steps[s];
+}
+static void corr_report(const amc_handle* h, int n, uint64_t* steps, int* n_samples, int* observable)
+{
+    for (int s = 0; steps && s < n; ++s) steps[s] = h->corr.steps[s];
+    *n_samples = n;
+    *observable = h->corr.observable;
 }
 
 extern "C" {
@@ -85,10 +96,7 @@ int amc_corr_mark(amc_handle* h, int observable)
     if (observable != AMC_CORR_E && observable != AMC_CORR_X)
         return fail(AMC_ERR_BAD_ARG, "amc_corr_mark: observable = %d must be AMC_CORR_E or AMC_CORR_X", observable);
     AMC_TRY(corr_pass(h, observable, 0, true));
-    h->corr.observable = observable;
-    h->corr.groups = corr_groups(h);
-    h->corr.n_samples = 1;
-    h->corr.steps[0] = h->t;
+    corr_adopt(h, observable, &h->t, 1);
     return AMC_OK;
 }
 
@@ -127,9 +135,7 @@ int amc_corr_fetch(amc_handle* h, double* records, uint64_t* steps, int capacity
         AMC_TRY(copy_to_host_sync(h, host.data(), n ? h->corr.d_corr : nullptr, n_rows * amc::XS_ROW_R * sizeof(amc::xs_word)));
         for (size_t s = 0; s < n_rows; ++s) amc::xs::rec_from_r(records + s * amc::xs::XS_WORDS, amc::xs_load_r_row(host.data() + s * amc::XS_ROW_R));
     }
-    for (int s = 0; s < n; ++s) steps[s] = h->corr.steps[s];
-    *n_samples = n;
-    *observable = h->corr.observable;
+    corr_report(h, n, steps, n_samples, observable);
     return AMC_OK;
 }
 
@@ -141,13 +147,12 @@ int amc_corr_fetch_blocks(amc_handle* h, double* records, uint64_t* steps, int c
     const int n = h->corr.observable ? h->corr.n_samples : 0;
     if (!records || !steps) {           // the sizes alone, for a caller about to allocate: nothing waits, nothing is copied
         *n_blocks = B;
-        *n_samples = n;
-        *observable = h->corr.observable;
+        corr_report(h, n, nullptr, n_samples, observable);
         return AMC_OK;
     }
     if (capacity < n) return fail(AMC_ERR_BAD_ARG, "amc_corr_fetch_blocks: capacity = %d, the mark has %d samples", capacity, n);
     AMC_HIP(hipSetDevice(h->device));
-    const int G = corr_groups(h);
+    const int G = pass_groups(h);
     const size_t per_sample = (size_t)G * amc::CORR_COLS;
     std::vector<amc::xs_word> host((size_t)n * B * per_sample * amc::XS_ROW_R + 1, 0ull);
     AMC_TRY(copy_to_host_sync(h, host.data(), n ? h->blocks.d_corr_blk : nullptr, (host.size() - 1) * sizeof(amc::xs_word)));
@@ -161,10 +166,8 @@ int amc_corr_fetch_blocks(amc_handle* h, double* records, uint64_t* steps, int c
                 else amc::xs::rec_from_r(rec, amc::xs_load_r_row(host.data() + (((size_t)s * B + b) * per_sample + gc) * amc::XS_ROW_R));
             }
     }
-    for (int s = 0; s < n; ++s) steps[s] = h->corr.steps[s];
     *n_blocks = B;
-    *n_samples = n;
-    *observable = h->corr.observable;
+    corr_report(h, n, steps, n_samples, observable);
     return AMC_OK;
 }
 
@@ -193,17 +196,9 @@ static int corr_set_check(const char* who, int observable, const uint64_t* steps
 // One record of a sample into its row: every (sample, group, column) had a summand, so each is a kind-R record, as amc_corr_fetch gave it.
 static int corr_row_from_record(const char* who, const double* rec, int slot, int g, int c, amc::xs_word* row)
 {
-    if (rec[0] != (double)amc::xs::XS_R || !(rec[1] >= amc::xs::XS_LMIN && rec[1] <= amc::xs::XS_LMAX) || rec[1] != std::floor(rec[1]) ||
-        !(rec[2] >= 0.0 && rec[2] <= 7.0) || rec[2] != std::floor(rec[2]))
-        return fail(AMC_ERR_BAD_ARG, "%s: record of sample %d, group %d, column %d is no kind-R record", who, slot, g, c);
-    for (int i = 3; i < amc::xs::XS_WORDS; ++i)
-        if (!(std::fabs(rec[i]) < 9007199254740992.0) || rec[i] != std::floor(rec[i]))
-            return fail(AMC_ERR_BAD_ARG, "%s: record of sample %d, group %d, column %d: word %d is no integer below 2^53", who, slot, g, c, i);
-    const amc::xs::PartR p = amc::xs::rec_to_r(rec);
-    row[0] = (amc::xs_word)(uint32_t)p.top | ((amc::xs_word)p.flags << 32);
-    row[1] = (amc::xs_word)p.k1.lo; row[2] = (amc::xs_word)p.k1.hi;
-    row[3] = (amc::xs_word)p.k2.lo; row[4] = (amc::xs_word)p.k2.hi;
-    return AMC_OK;
+    char where[64];
+    std::snprintf(where, sizeof where, "sample %d, group %d, column %d", slot, g, c);
+    return r_row_from_record(who, where, rec, row);
 }
 
 int amc_set_corr(amc_handle* h, int observable, const double* origin, const double* records, const uint64_t* steps, int n_samples)
@@ -214,7 +209,7 @@ int amc_set_corr(amc_handle* h, int observable, const double* origin, const doub
         return fail(AMC_ERR_STATE, "amc_set_corr: a partition is set (amc_set_blocks): merged records cannot be split into its blocks, "
                                    "amc_set_corr_blocks restores them");
     AMC_TRY(corr_set_check("amc_set_corr", observable, steps, n_samples));
-    const int G = corr_groups(h);
+    const int G = pass_groups(h);
     const size_t n_rows = (size_t)n_samples * G * amc::CORR_COLS;
     std::vector<amc::xs_word> host(n_rows * amc::XS_ROW_R, 0ull);
     for (size_t s = 0; s < n_rows; ++s)
@@ -224,10 +219,7 @@ int amc_set_corr(amc_handle* h, int observable, const double* origin, const doub
     AMC_TRY(corr_room(h));
     AMC_HIP(hipMemcpyAsync(h->corr.d_origin, origin, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
     AMC_TRY(copy_to_device_sync(h, h->corr.d_corr, host.data(), host.size() * sizeof(amc::xs_word)));      // the caller's buffers are only valid during the call
-    h->corr.observable = observable;
-    h->corr.groups = G;
-    h->corr.n_samples = n_samples;
-    for (int s = 0; s < n_samples; ++s) h->corr.steps[s] = steps[s];
+    corr_adopt(h, observable, steps, n_samples);
     return AMC_OK;
 }
 
@@ -239,7 +231,7 @@ int amc_set_corr_blocks(amc_handle* h, int observable, const double* origin, con
     if (n_blocks != B) return fail(AMC_ERR_BAD_ARG, "amc_set_corr_blocks: n_blocks = %d, the partition has %d blocks", n_blocks, B);
     AMC_TRY(corr_set_check("amc_set_corr_blocks", observable, steps, n_samples));
     // records[b][s][g][c] as amc_corr_fetch_blocks gave them, into the rows [s][b][g][c]; a block without a local ladder is all zero
-    const int G = corr_groups(h);
+    const int G = pass_groups(h);
     const size_t per_sample = (size_t)G * amc::CORR_COLS;
     std::vector<amc::xs_word> host((size_t)n_samples * B * per_sample * amc::XS_ROW_R, 0ull);
     const amc::blk::Part part = blocks_part(h);
@@ -259,22 +251,10 @@ int amc_set_corr_blocks(amc_handle* h, int observable, const double* origin, con
     }
     AMC_HIP(hipSetDevice(h->device));
     AMC_TRY(corr_room(h));
-    if (host.size() > h->blocks.corr_blk_words) {       // (nothing the old rows hold is kept: corr_blocks_room would copy them)
-        const size_t need = (size_t)std::max(16, n_samples) * corr_block_sample_words(h);
-        amc::xs_word* rows = nullptr;
-        AMC_HIP(hipMalloc(&rows, need * sizeof(amc::xs_word)));
-        const hipError_t e = hipStreamSynchronize(h->stream);
-        (void)hipFree(h->blocks.d_corr_blk);
-        h->blocks.d_corr_blk = rows;
-        h->blocks.corr_blk_words = need;
-        AMC_HIP(e);
-    }
+    AMC_TRY(corr_blocks_room(h, n_samples - 1, false));      // (nothing the old rows hold is kept)
     AMC_HIP(hipMemcpyAsync(h->corr.d_origin, origin, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
     AMC_TRY(copy_to_device_sync(h, h->blocks.d_corr_blk, host.data(), host.size() * sizeof(amc::xs_word)));      // the caller's buffers are only valid during the call
-    h->corr.observable = observable;
-    h->corr.groups = G;
-    h->corr.n_samples = n_samples;
-    for (int s = 0; s < n_samples; ++s) h->corr.steps[s] = steps[s];
+    corr_adopt(h, observable, steps, n_samples);
     return AMC_OK;
 }
 

@@ -367,13 +367,7 @@ struct RungSumsArgs {
 // One memory-bound pass, 8 B per chain (4 B for Float32 state).  Work items as in exchange_kernel: thread id = l0 R + r, a thread keeps
 // its rung for the whole launch and advances by (threads / R) ladders per trip, so neighbouring lanes read neighbouring chains and the
 // loop divides nothing; four loads are in flight per lane.  The lanes of a wave hold DIFFERENT rungs, so each lane keeps its own
-// running top (RLaneCols, amc_wave_sums.h) where the whole-ensemble sums keep a wave-uniform one.
-// End of block, per slot s = r RED_COLS + c in LDS: (1) the slot's top = max of its lanes' tops and the OR of their flags -- integer
-// max / or, order-free --, barrier; (2) the level is settled: every lane brings its two integers (xs_r_multiples) to
-// it (xs_r_settle's rule as the choice of the slot: at the top k1, k2 add; one level below k1 adds to k2; further below nothing is
-// left) and adds them with 64-bit integer LDS atomics, low 32 bits and
-// high parts apart (128 lanes x 2^62 do not fit 64 bits; k = hi 2^32 + lo), barrier; (3) the block stores its rows, consecutive words
-// by consecutive threads.  No floating-point atomic anywhere; rung_finish_kernel merges the blocks' rows (integers: any order).
+// running top (RLaneCols, amc_wave_sums.h) where the whole-ensemble sums keep a wave-uniform one.  Then the frame below.
 template <int POT>
 __device__ __forceinline__ void rung_add(RLaneCols<RED_COLS>& L, real_t x, const double* s_math, int cols)
 {
@@ -383,12 +377,91 @@ __device__ __forceinline__ void rung_add(RLaneCols<RED_COLS>& L, real_t x, const
     if (cols & RED_WANT_XX) rl_deposit(L, 2, xd * xd);
     L.n += 1;
 }
+
+// ---- the frame of the sums by group (DESIGN.md section 3.13 "Per-rung sums") -----------------------------------------------------------
+// The five sums kernels -- rung_sums_kernel, bridge_sums_kernel, corr_sums_kernel (amc_corr.h) and the two blocked forms (amc_blocks.h)
+// -- are each: the slot prologue, a loop of their own, the block end; their rows go through ONE finishing merge.  A slot is
+// s = g NC + c in LDS, g the lane's group (its rung), c one of the kernel's NC columns: s_top, s_flags and s_k[s] = k1.lo, k1.hi,
+// k2.lo, k2.hi (hi: two's complement).
+//
+// The slot prologue clears them.  THE BARRIER RULE: exactly one barrier lies between this clearing and the first LDS atomic of the
+// block end.  A kernel that stages the math tables behind the prologue has it there (stage_math_tables ends in a barrier); every
+// other has one __syncthreads() behind its loop, and no kernel has both.
+__device__ __forceinline__ void group_slots_clear(int n_slots, int* s_top, unsigned int* s_flags, unsigned long long (*s_k)[4])
+{
+    for (int s = threadIdx.x; s < n_slots; s += AMC_BLOCK) {
+        s_top[s] = xs::XS_LMIN;
+        s_flags[s] = 0u;
+        s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
+    }
+}
 __device__ __forceinline__ void rung_lds_add(unsigned long long* lo_hi, long long k)
 {
     if (k == 0) return;
     atomicAdd(lo_hi, (unsigned long long)(k & 0xFFFFFFFFll));
     atomicAdd(lo_hi + 1, (unsigned long long)(k >> 32));
 }
+// The block end for a lane with the columns `mine` of group r on its books (0: none, as for a lane that took no summand): (1) the
+// slot's top = max of its lanes' tops and the OR of their flags -- integer max / or, order-free --, barrier; (2) the level is settled:
+// every lane brings its two integers (xs_r_multiples) to it (xs_r_settle's rule as the choice of the slot: at the top k1, k2 add; one
+// level below k1 adds to k2; further below nothing is left) and adds them with 64-bit integer LDS atomics, low 32 bits and high parts
+// apart (128 lanes x 2^62 do not fit 64 bits; k = hi 2^32 + lo), barrier; (3) the block stores its rows in the XS_ROW_R form,
+// consecutive words by consecutive threads -- those of the columns in `stored` (a slot nobody deposited into is an empty row: top
+// XS_LMIN, zeros).  No floating-point atomic anywhere; the rows are integers, so the finishing merge may take them in any order.
+template <int NC>
+__device__ __forceinline__ void group_rows_end(const RLaneCols<NC>& L, int r, int mine, int n_slots, int* s_top, unsigned int* s_flags,
+                                               unsigned long long (*s_k)[4], xs_word* out, int stored = -1)
+{
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if ((mine >> c) & 1) {
+            atomicMax(&s_top[r * NC + c], L.top[c]);
+            if (L.flags[c]) atomicOr(&s_flags[r * NC + c], L.flags[c]);
+        }
+    __syncthreads();                                              // the levels are settled
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if ((mine >> c) & 1) {
+            const int s = r * NC + c;
+            xs::RPair k = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n, L.top[c]);
+            const int d = s_top[s] - L.top[c];
+            if (d == 0) {
+                rung_lds_add(&s_k[s][0], k.k1);
+                rung_lds_add(&s_k[s][2], k.k2);
+            } else if (d == 1) {
+                rung_lds_add(&s_k[s][2], k.k1);
+            }
+        }
+    __syncthreads();
+    for (int w = threadIdx.x; w < n_slots * XS_ROW_R; w += AMC_BLOCK) {
+        const int s = w / XS_ROW_R, j = w - s * XS_ROW_R;
+        if (stored != -1 && !((stored >> (s % NC)) & 1)) continue;
+        xs_word v = 0ull;
+        if (j == 0) v = (xs_word)(uint32_t)s_top[s] | ((xs_word)s_flags[s] << 32);
+        else if (j < 5) {
+            const int which = (j - 1) >> 1;                       // k1 / k2
+            const xs::i128 k = xs::i128_add(xs::i128_shl(xs::i128_of((long long)s_k[s][2 * which + 1]), 32), xs::i128{(uint64_t)s_k[s][2 * which], 0});
+            v = ((j - 1) & 1) ? (xs_word)k.hi : (xs_word)k.lo;
+        }
+        out[w] = v;
+    }
+}
+// The finishing merge of slot s by one block of 64 threads: lane i merges the rows first + i stride, first + (i + 64) stride, ... of
+// the launches' block rows (part_r_merge: integers, so the order is immaterial), thread 0 the lanes' partials; its return value is
+// the slot's sum, every other thread's a partial.
+__device__ __forceinline__ xs::PartR group_rows_merge(const xs_word* rows, int n_rows, int n_slots, int s, int first, int stride)
+{
+    __shared__ xs::PartR s_part[64];
+    xs::PartR p = xs::part_r_empty();
+    for (int k = first + (int)threadIdx.x * stride; k < n_rows; k += 64 * stride)
+        xs::part_r_merge(p, xs_load_r_row(rows + ((int64_t)k * n_slots + s) * XS_ROW_R));
+    s_part[threadIdx.x] = p;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
+    return p;
+}
+
 template <int POT>
 __global__ __launch_bounds__(AMC_BLOCK) void rung_sums_kernel(const RungSumsArgs a)
 {
@@ -396,13 +469,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void rung_sums_kernel(const RungSumsArgs
     __shared__ AMC_MATH_LDS_ALIGN double s_math[POT == POT_CUSTOM ? TAB_DOUBLES : 1];      // a custom potential may call amc_exp
     __shared__ int s_top[MAX_SLOTS];
     __shared__ unsigned int s_flags[MAX_SLOTS];
-    __shared__ unsigned long long s_k[MAX_SLOTS][4];                    // k1.lo, k1.hi, k2.lo, k2.hi (hi: two's complement)
+    __shared__ unsigned long long s_k[MAX_SLOTS][4];
     const int n_slots = a.n_rungs * RED_COLS;
-    for (int s = threadIdx.x; s < n_slots; s += AMC_BLOCK) {
-        s_top[s] = xs::XS_LMIN;
-        s_flags[s] = 0u;
-        s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
-    }
+    group_slots_clear(n_slots, s_top, s_flags, s_k);
     if (POT == POT_CUSTOM) stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier)
 
     const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
@@ -425,64 +494,23 @@ __global__ __launch_bounds__(AMC_BLOCK) void rung_sums_kernel(const RungSumsArgs
         for (; i < end; i += step) rung_add<POT>(L, a.x[i], s_math, a.cols);
     }
     __syncthreads();                                              // the slots are cleared
-    const bool mine = L.n > 0;
-#pragma unroll
-    for (int c = 0; c < RED_COLS; ++c)
-        if (mine && ((a.cols >> c) & 1)) {
-            atomicMax(&s_top[r * RED_COLS + c], L.top[c]);
-            if (L.flags[c]) atomicOr(&s_flags[r * RED_COLS + c], L.flags[c]);
-        }
-    __syncthreads();                                              // the levels are settled
-#pragma unroll
-    for (int c = 0; c < RED_COLS; ++c)
-        if (mine && ((a.cols >> c) & 1)) {
-            const int s = r * RED_COLS + c;
-            xs::RPair k = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n, L.top[c]);
-            const int d = s_top[s] - L.top[c];
-            if (d == 0) {
-                rung_lds_add(&s_k[s][0], k.k1);
-                rung_lds_add(&s_k[s][2], k.k2);
-            } else if (d == 1) {
-                rung_lds_add(&s_k[s][2], k.k1);
-            }
-        }
-    __syncthreads();
-    xs_word* out = a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R;
-    for (int w = threadIdx.x; w < n_slots * XS_ROW_R; w += AMC_BLOCK) {
-        const int s = w / XS_ROW_R, j = w - s * XS_ROW_R;
-        if (!((a.cols >> (s % RED_COLS)) & 1)) continue;
-        xs_word v = 0ull;
-        if (j == 0) v = (xs_word)(uint32_t)s_top[s] | ((xs_word)s_flags[s] << 32);
-        else if (j < 5) {
-            const int which = (j - 1) >> 1;                       // k1 / k2
-            const xs::i128 k = xs::i128_add(xs::i128_shl(xs::i128_of((long long)s_k[s][2 * which + 1]), 32), xs::i128{(uint64_t)s_k[s][2 * which], 0});
-            v = ((j - 1) & 1) ? (xs_word)k.hi : (xs_word)k.lo;
-        }
-        out[w] = v;
-    }
+    // (the rows of a column nobody asked for are not written: rung_finish_kernel does not read them)
+    group_rows_end<RED_COLS>(L, r, L.n > 0 ? a.cols : 0, n_slots, s_top, s_flags, s_k, a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R, a.cols);
 }
 
-// The records of the rung sums from the block rows of the launches: block s = r RED_COLS + c of 64 threads, lane i merges the rows
-// i, i + 64, ... (part_r_merge: integers, so the order is immaterial), thread 0 the lanes' partials, and leaves one record of
+// The records of the rung sums from the block rows of the launches: block s = r RED_COLS + c merges slot s and leaves one record of
 // XS_WORDS doubles -- all zero for a column nobody asked for.
 #if AMC_PLAIN_KERNELS
 AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void rung_finish_kernel(const xs_word* rows, int n_rows, int n_rungs, int cols, double* recs)
 {
-    __shared__ xs::PartR s_part[64];
-    const int s = blockIdx.x, n_slots = n_rungs * RED_COLS;
+    const int s = blockIdx.x;
     double* rec = recs + (int64_t)s * xs::XS_WORDS;
     if (!((cols >> (s % RED_COLS)) & 1)) {
         if (threadIdx.x < xs::XS_WORDS) rec[threadIdx.x] = 0.0;
         return;
     }
-    xs::PartR p = xs::part_r_empty();
-    for (int b = threadIdx.x; b < n_rows; b += 64) xs::part_r_merge(p, xs_load_r_row(rows + ((int64_t)b * n_slots + s) * XS_ROW_R));
-    s_part[threadIdx.x] = p;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
-        xs::rec_from_r(rec, p);
-    }
+    const xs::PartR p = group_rows_merge(rows, n_rows, n_rungs * RED_COLS, s, 0, 1);
+    if (threadIdx.x == 0) xs::rec_from_r(rec, p);
 }
 #endif
 
@@ -552,9 +580,8 @@ __device__ __forceinline__ void bridge_load(const BridgeArgs& a, int64_t i, bool
 
 // One memory-bound pass in rung_sums_kernel's form: thread id = l0 R + r, a thread keeps its rung -- and with it the set `mine` of
 // columns it deposits into -- for the whole launch, four loads of x in flight per lane; the neighbours' beta are the loads of the
-// neighbouring lanes' own beta.  RLaneCols::n counts the summands of the columns in `mine` and of no other: the top, flag and
-// multiple phases at the block's end walk `mine`, so a slot an end rung has no summand for is never fed an empty sum with n > 0.
-// Then as rung_sums_kernel: integer max / or per slot, 64-bit integer LDS adds, rows in the XS_ROW_R form.  No floating-point atomic.
+// neighbouring lanes' own beta.  RLaneCols::n counts the summands of the columns in `mine` and of no other: the block end walks
+// `mine`, so a slot an end rung has no summand for is never fed an empty sum with n > 0.
 template <int POT>
 __global__ __launch_bounds__(AMC_BLOCK) void bridge_sums_kernel(const BridgeArgs a)
 {
@@ -562,13 +589,9 @@ __global__ __launch_bounds__(AMC_BLOCK) void bridge_sums_kernel(const BridgeArgs
     __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];                               // exp for every potential
     __shared__ int s_top[MAX_SLOTS];
     __shared__ unsigned int s_flags[MAX_SLOTS];
-    __shared__ unsigned long long s_k[MAX_SLOTS][4];                    // k1.lo, k1.hi, k2.lo, k2.hi (hi: two's complement)
+    __shared__ unsigned long long s_k[MAX_SLOTS][4];
     const int n_slots = a.n_rungs * BR_COLS;
-    for (int s = threadIdx.x; s < n_slots; s += AMC_BLOCK) {
-        s_top[s] = xs::XS_LMIN;
-        s_flags[s] = 0u;
-        s_k[s][0] = s_k[s][1] = s_k[s][2] = s_k[s][3] = 0ull;
-    }
+    group_slots_clear(n_slots, s_top, s_flags, s_k);
     stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);                  // (ends in a barrier: the slots are cleared too)
 
     const int64_t tid = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
@@ -600,58 +623,24 @@ __global__ __launch_bounds__(AMC_BLOCK) void bridge_sums_kernel(const BridgeArgs
         }
     }
     if (L.n == 0) mine = 0;
-#pragma unroll
-    for (int c = 0; c < BR_COLS; ++c)
-        if ((mine >> c) & 1) {
-            atomicMax(&s_top[r * BR_COLS + c], L.top[c]);
-            if (L.flags[c]) atomicOr(&s_flags[r * BR_COLS + c], L.flags[c]);
-        }
-    __syncthreads();                                              // the levels are settled
-#pragma unroll
-    for (int c = 0; c < BR_COLS; ++c)
-        if ((mine >> c) & 1) {
-            const int s = r * BR_COLS + c;
-            xs::RPair k = xs::xs_r_multiples(L.a1[c], L.a2[c], (uint64_t)(unsigned)L.n, L.top[c]);
-            const int d = s_top[s] - L.top[c];
-            if (d == 0) {
-                rung_lds_add(&s_k[s][0], k.k1);
-                rung_lds_add(&s_k[s][2], k.k2);
-            } else if (d == 1) {
-                rung_lds_add(&s_k[s][2], k.k1);
-            }
-        }
-    __syncthreads();
-    xs_word* out = a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R;
-    for (int w = threadIdx.x; w < n_slots * XS_ROW_R; w += AMC_BLOCK) {
-        const int s = w / XS_ROW_R, j = w - s * XS_ROW_R;
-        xs_word v = 0ull;
-        if (j == 0) v = (xs_word)(uint32_t)s_top[s] | ((xs_word)s_flags[s] << 32);
-        else if (j < 5) {
-            const int which = (j - 1) >> 1;                       // k1 / k2
-            const xs::i128 k = xs::i128_add(xs::i128_shl(xs::i128_of((long long)s_k[s][2 * which + 1]), 32), xs::i128{(uint64_t)s_k[s][2 * which], 0});
-            v = ((j - 1) & 1) ? (xs_word)k.hi : (xs_word)k.lo;
-        }
-        out[w] = v;                                               // (a slot nobody deposited into is an empty row: top XS_LMIN, zeros)
-    }
+    group_rows_end<BR_COLS>(L, r, mine, n_slots, s_top, s_flags, s_k, a.rows + (int64_t)blockIdx.x * n_slots * XS_ROW_R);
 }
 
-// The launches' block rows merged into the accumulator: block s = r BR_COLS + c of 64 threads, lane i merges the rows i, i + 64, ...
-// (part_r_merge: integers, so the order is immaterial), thread 0 the lanes' partials and the accumulator's own row, which it replaces.
-// A slot without a summand keeps its empty row.  Block 0 counts the snapshot.
+// The launches' block rows merged into an accumulator of n_blocks x R x BR_COLS rows [b][r][c]: block (b, s), s = r BR_COLS + c,
+// merges slot s of the HIP blocks b, b + B, ... (a blocked pass has grids that are multiples of B, so those are the rows k with
+// k mod B == b; the unpartitioned pass is B = 1, b = 0), then the accumulator's own row, which it replaces.  A slot without a summand
+// keeps its empty row.  Block 0 counts the snapshot in *count, once: the word BRIDGE_COUNT of d_bridge, the word behind the rows of
+// the blocked accumulator.
 #if AMC_PLAIN_KERNELS
-AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void bridge_finish_kernel(const xs_word* rows, int n_rows, int n_rungs, int cols, xs_word* acc)
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(64) void bridge_finish_kernel(const xs_word* rows, int n_rows, int n_rungs, int cols, int n_blocks, xs_word* acc,
+                                                                               xs_word* count)
 {
-    __shared__ xs::PartR s_part[64];
-    const int s = blockIdx.x, n_slots = n_rungs * BR_COLS;
-    if (s == 0 && threadIdx.x == 0) acc[BRIDGE_COUNT] += 1ull;
+    const int n_slots = n_rungs * BR_COLS, b = blockIdx.x / n_slots, s = blockIdx.x - b * n_slots;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count += 1ull;
     if (!((bridge_cols_at(cols, s / BR_COLS, n_rungs) >> (s % BR_COLS)) & 1)) return;
-    xs::PartR p = xs::part_r_empty();
-    for (int b = threadIdx.x; b < n_rows; b += 64) xs::part_r_merge(p, xs_load_r_row(rows + ((int64_t)b * n_slots + s) * XS_ROW_R));
-    s_part[threadIdx.x] = p;
-    __syncthreads();
+    xs::PartR p = group_rows_merge(rows, n_rows, n_slots, s, b, n_blocks);
     if (threadIdx.x == 0) {
-        xs_word* row = acc + (int64_t)s * XS_ROW_R;
-        for (int i = 1; i < 64; ++i) xs::part_r_merge(p, s_part[i]);
+        xs_word* row = acc + ((int64_t)b * n_slots + s) * XS_ROW_R;
         xs::part_r_merge(p, bridge_load_row(row));
         xs_store_r_row(row, p);
         row[5] = 1ull;

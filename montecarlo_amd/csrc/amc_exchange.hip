@@ -106,30 +106,40 @@ static int flow_snapshot_queue(amc_handle* h)
     return AMC_OK;
 }
 
-// A pass over the groups (RungPass, amc_internal.h) planned, and room made for its rows.
-int rung_pass_plan(amc_handle* h, int n_cols, RungPass* p)
+// A pass over the groups (RungPass, amc_internal.h) planned, and room made for its rows.  Blocked: the same grid rounded up to a
+// multiple of B, and the ladders per launch by the traversal's own bound.
+int rung_pass_plan(amc_handle* h, int n_cols, bool blocked, RungPass* p)
 {
-    const int R = h->lad.n_rungs ? h->lad.n_rungs : 1;
+    const int R = pass_groups(h);
     p->groups = R;
+    p->blocked = blocked;
     p->grid = grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU);
+    if (blocked) p->grid = amc::blk::grid_round(p->grid, h->blocks.n_blocks);
     // a lane adds one summand per trip and column and holds XS_LANE_CAP of them (amc_xsum.h): ensembles beyond that many trips of the
     // grid (2^28 chains and more) take several launches, each with block rows of its own
-    p->per_launch = (((int64_t)p->grid * AMC_BLOCK) / R) * (amc::xs::XS_LANE_CAP - 2);
+    const int64_t cap = amc::xs::XS_LANE_CAP - 2;
+    p->per_launch = blocked ? amc::blk::ladders_per_launch(h->M / R, h->blocks.n_blocks, h->blocks.chunk, R, p->grid, AMC_BLOCK, cap)
+                            : (((int64_t)p->grid * AMC_BLOCK) / R) * cap;
     p->n_launches = (h->M / R + p->per_launch - 1) / p->per_launch;
     p->slot_words = (size_t)R * (size_t)n_cols * amc::XS_ROW_R;
     return rung_rows_room(h, (size_t)p->n_launches * (size_t)p->grid * p->slot_words);
 }
 
-// ... of a handle with a partition (blocks_pass_launch, amc_internal.h): the same grid rounded up to a multiple of B.
-int blocks_pass_plan(amc_handle* h, int n_cols, RungPass* p)
+// A kind-R record, as a fetch gives it, into words 0 .. 4 of a row of XS_ROW_R words (word 5 is the caller's): the kind, an integer
+// level within the levels, an integer flag word within the flags, integers below 2^53.  Anything else is refused, named by who / where.
+int r_row_from_record(const char* who, const char* where, const double* rec, amc::xs_word* row)
 {
-    const int R = blocks_groups(h);
-    p->groups = R;
-    p->grid = amc::blk::grid_round(grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU), h->blocks.n_blocks);
-    p->per_launch = amc::blk::ladders_per_launch(h->M / R, h->blocks.n_blocks, h->blocks.chunk, R, p->grid, AMC_BLOCK, amc::xs::XS_LANE_CAP - 2);
-    p->n_launches = (h->M / R + p->per_launch - 1) / p->per_launch;
-    p->slot_words = (size_t)R * (size_t)n_cols * amc::XS_ROW_R;
-    return rung_rows_room(h, (size_t)p->n_launches * (size_t)p->grid * p->slot_words);
+    if (rec[0] != (double)amc::xs::XS_R || !(rec[1] >= amc::xs::XS_LMIN && rec[1] <= amc::xs::XS_LMAX) || rec[1] != std::floor(rec[1]) ||
+        !(rec[2] >= 0.0 && rec[2] <= 7.0) || rec[2] != std::floor(rec[2]))
+        return fail(AMC_ERR_BAD_ARG, "%s: record of %s is no kind-R record", who, where);
+    for (int i = 3; i < amc::xs::XS_WORDS; ++i)
+        if (!(std::fabs(rec[i]) < 9007199254740992.0) || rec[i] != std::floor(rec[i]))
+            return fail(AMC_ERR_BAD_ARG, "%s: record of %s: word %d is no integer below 2^53", who, where, i);
+    const amc::xs::PartR p = amc::xs::rec_to_r(rec);
+    row[0] = (amc::xs_word)(uint32_t)p.top | ((amc::xs_word)p.flags << 32);
+    row[1] = (amc::xs_word)p.k1.lo; row[2] = (amc::xs_word)p.k1.hi;
+    row[3] = (amc::xs_word)p.k2.lo; row[4] = (amc::xs_word)p.k2.hi;
+    return AMC_OK;
 }
 
 // The blocked accumulator of the bridge sums on the host: the rows [b][r][c], then the number of snapshots (all zero while nothing has
@@ -338,7 +348,7 @@ int amc_reduce_rungs_exact(amc_handle* h, int columns, double* records)
     // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
     AMC_TRY(pg_resolve(h));
     RungPass p;
-    AMC_TRY(rung_pass_plan(h, amc::RED_COLS, &p));
+    AMC_TRY(rung_pass_plan(h, amc::RED_COLS, false, &p));      // (unpartitioned under a partition too)
     if (!h->lad.d_rung_recs) AMC_HIP(hipMalloc(&h->lad.d_rung_recs, (size_t)AMC_MAX_RUNGS * amc::RED_COLS * amc::xs::XS_WORDS * sizeof(double)));
     AMC_TRY(rung_pass_launch(h, p, amc::RungSumsArgs(), columns, "amc::rung_sums_kernel", (const void*)amc::rung_sums_kernel<amc::POT_DOUBLE_WELL>,
                              (const void*)amc::rung_sums_kernel<amc::POT_HARMONIC>));
@@ -365,28 +375,24 @@ int amc_bridge_accumulate(amc_handle* h, int columns)
     AMC_HIP(hipSetDevice(h->device));
     // (as in front of an exchange step: a learning step left pending belongs in front of this point of the stream)
     AMC_TRY(pg_resolve(h));
+    // with a partition a row per (block, rung, column), the number of snapshots behind them: the traversal of amc_blocks.h
+    const int B = h->blocks.n_blocks, R = h->lad.n_rungs, n_slots = R * amc::BR_COLS;
     RungPass p;
     amc::BridgeArgs a = {};
     a.beta = h->d_beta;
-    if (h->blocks.n_blocks) {           // a row per (block, rung, column): the traversal and the finishing kernel of amc_blocks.h
-        const int B = h->blocks.n_blocks, n_slots = h->lad.n_rungs * amc::BR_COLS;
-        AMC_TRY(blocks_pass_plan(h, amc::BR_COLS, &p));
+    AMC_TRY(rung_pass_plan(h, amc::BR_COLS, B != 0, &p));
+    if (B) {
         AMC_TRY(blocks_words(h, &h->blocks.d_bridge_blk, &h->blocks.bridge_blk_words, (size_t)B * n_slots * amc::XS_ROW_R + 1));
-        AMC_TRY(blocks_pass_launch(h, p, a, columns, "amc::bridge_sums_blocks_kernel", (const void*)amc::bridge_sums_blocks_kernel<amc::POT_DOUBLE_WELL>,
-                                   (const void*)amc::bridge_sums_blocks_kernel<amc::POT_HARMONIC>));
-        hipLaunchKernelGGL(amc::bridge_finish_blocks_kernel, dim3(B * n_slots), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows, p.n_blocks(),
-                           h->lad.n_rungs, columns, B, h->blocks.d_bridge_blk);
-        AMC_HIP(hipGetLastError());
-        h->lad.bridge_cols = columns;
-        return AMC_OK;
+        AMC_TRY(rung_pass_launch(h, p, a, columns, "amc::bridge_sums_blocks_kernel", (const void*)amc::bridge_sums_blocks_kernel<amc::POT_DOUBLE_WELL>,
+                                 (const void*)amc::bridge_sums_blocks_kernel<amc::POT_HARMONIC>));
+    } else {
+        AMC_TRY(zeroed_words(h, &h->lad.d_bridge, BRIDGE_BYTES));
+        AMC_TRY(rung_pass_launch(h, p, a, columns, "amc::bridge_sums_kernel", (const void*)amc::bridge_sums_kernel<amc::POT_DOUBLE_WELL>,
+                                 (const void*)amc::bridge_sums_kernel<amc::POT_HARMONIC>));
     }
-    AMC_TRY(rung_pass_plan(h, amc::BR_COLS, &p));
-    AMC_TRY(zeroed_words(h, &h->lad.d_bridge, BRIDGE_BYTES));
-    AMC_TRY(rung_pass_launch(h, p, a, columns, "amc::bridge_sums_kernel", (const void*)amc::bridge_sums_kernel<amc::POT_DOUBLE_WELL>,
-                             (const void*)amc::bridge_sums_kernel<amc::POT_HARMONIC>));
-    const int R = h->lad.n_rungs;
-    hipLaunchKernelGGL(amc::bridge_finish_kernel, dim3(R * amc::BR_COLS), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows, p.n_blocks(), R,
-                       columns, h->lad.d_bridge);
+    amc::xs_word* acc = B ? h->blocks.d_bridge_blk : h->lad.d_bridge;
+    hipLaunchKernelGGL(amc::bridge_finish_kernel, dim3((B ? B : 1) * n_slots), dim3(64), 0, h->stream, (const amc::xs_word*)h->lad.d_rung_rows, p.n_blocks(), R,
+                       columns, B ? B : 1, acc, acc + (B ? (size_t)B * n_slots * amc::XS_ROW_R : (size_t)amc::BRIDGE_COUNT));
     AMC_HIP(hipGetLastError());
     h->lad.bridge_cols = columns;
     return AMC_OK;
@@ -445,19 +451,13 @@ static int bridge_rows_from_records(const char* who, const double* records, int 
         bool zero = true;
         for (int i = 0; i < amc::xs::XS_WORDS; ++i) zero = zero && rec[i] == 0.0;
         if (zero) continue;
-        if (rec[0] != (double)amc::xs::XS_R || !(rec[1] >= amc::xs::XS_LMIN && rec[1] <= amc::xs::XS_LMAX) || !(rec[2] >= 0.0 && rec[2] <= 7.0))
-            return fail(AMC_ERR_BAD_ARG, "%s: record of rung %d, column %d is no kind-R record", who, r, c);
-        for (int i = 3; i < amc::xs::XS_WORDS; ++i)
-            if (!(std::fabs(rec[i]) < 9007199254740992.0) || rec[i] != std::floor(rec[i]))
-                return fail(AMC_ERR_BAD_ARG, "%s: record of rung %d, column %d: word %d is no integer below 2^53", who, r, c, i);
+        char where[48];
+        std::snprintf(where, sizeof where, "rung %d, column %d", r, c);
+        amc::xs_word* row = rows + (size_t)s * amc::XS_ROW_R;
+        AMC_TRY(r_row_from_record(who, where, rec, row));
         if (!((amc::bridge_cols_at(AMC_BRIDGE_ALL, r, R) >> c) & 1))
             return fail(AMC_ERR_BAD_ARG, "%s: rung %d has no summand for column %d, its record must be all zero", who, r, c);
         cols |= 1 << c;
-        amc::xs::PartR p = amc::xs::rec_to_r(rec);
-        amc::xs_word* row = rows + (size_t)s * amc::XS_ROW_R;
-        row[0] = (amc::xs_word)(uint32_t)p.top | ((amc::xs_word)p.flags << 32);
-        row[1] = (amc::xs_word)p.k1.lo; row[2] = (amc::xs_word)p.k1.hi;
-        row[3] = (amc::xs_word)p.k2.lo; row[4] = (amc::xs_word)p.k2.hi;
         row[5] = 1ull;
     }
     for (int s = 0; cols && s < n_slots; ++s)
@@ -500,7 +500,7 @@ int amc_set_blocks(amc_handle* h, int n_blocks, int64_t chunk)
         return fail(AMC_ERR_BAD_ARG, "amc_set_blocks: chunk = %lld must lie in [1, 2^40], or be 0 for the default", (long long)chunk);
     AMC_HIP(hipSetDevice(h->device));
     // one full block-width of contiguous chains: every lane of a HIP block has a ladder of the chunk, in one trip
-    if (n_blocks && chunk == 0) chunk = std::max(1, AMC_BLOCK / blocks_groups(h));
+    if (n_blocks && chunk == 0) chunk = std::max(1, AMC_BLOCK / pass_groups(h));
     h->blocks.n_blocks = n_blocks;
     h->blocks.chunk = n_blocks ? chunk : 0;
     // sums kept under another partition (or under none) are not sums of these blocks

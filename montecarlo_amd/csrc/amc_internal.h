@@ -466,15 +466,22 @@ AMC_INTERNAL int check_sigma_f32(const char* who, int k, double s);     // a sig
 AMC_INTERNAL int pg_resolve(amc_handle* h);      // takes a pending learning step now (amc_pg.hip)
 // A pass over the groups of chains -- the rungs of the ladder; ONE group of all local chains without a ladder -- that ends every block
 // with rows of its own, n_cols columns per group, in lad.d_rung_rows (the rung sums, the bridge sums, the time correlation): the
-// launches it takes and where each one's rows go (amc_exchange.hip).
+// launches it takes and where each one's rows go (amc_exchange.hip).  A BLOCKED pass (the caller's choice, under a partition:
+// amc_set_blocks) takes the traversal of amc_blocks.h -- a grid that is a multiple of B, HIP block k serving jackknife block k mod B,
+// launches split by ladder ranges that keep every lane within XS_LANE_CAP - 2 summands -- and its kernels the partition as their
+// second argument.
+static inline int pass_groups(const amc_handle* h) { return h->lad.n_rungs ? h->lad.n_rungs : 1; }
 struct RungPass {
     int grid = 0;
     int groups = 1;                             // G: R of the ladder, 1 without one (a "ladder" of the pass is then a single chain)
+    bool blocked = false;
     int64_t per_launch = 0, n_launches = 0;     // ladders per launch; launches
     size_t slot_words = 0;                      // words of one block's rows
     int n_blocks() const { return (int)(n_launches * grid); }      // block rows the finishing kernel reads
 };
-AMC_INTERNAL int rung_pass_plan(amc_handle* h, int n_cols, RungPass* p);      // ... planned, and room made for its rows
+AMC_INTERNAL int rung_pass_plan(amc_handle* h, int n_cols, bool blocked, RungPass* p);      // ... planned, and room made for its rows
+// a kind-R record into words 0 .. 4 of an XS_ROW_R row, or a refusal naming who / where (amc_exchange.hip; amc_set_bridge*, amc_set_corr*)
+AMC_INTERNAL int r_row_from_record(const char* who, const char* where, const double* rec, amc::xs_word* row);
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };
@@ -495,40 +502,18 @@ static inline int launch_by_potential(amc_handle* h, const char* name, const voi
     return AMC_OK;
 }
 
-// A planned pass launched: `a` comes with what only its kernel reads (the bridge sums' beta, the origin of the time correlation); x, the
-// rows, the ladders, G and the columns are filled in here.
-template <class Args>
-static inline int rung_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
-{
-    const int64_t n_ladders = h->M / p.groups;
-    a.x = h->d_x;
-    a.n_rungs = p.groups;
-    a.cols = columns;
-    for (int64_t i = 0; i < p.n_launches; ++i) {
-        a.rows = h->lad.d_rung_rows + (size_t)i * (size_t)p.grid * p.slot_words;
-        a.l_begin = i * p.per_launch;
-        a.l_end = std::min(n_ladders, (i + 1) * p.per_launch);
-        void* params[] = {&a};
-        AMC_TRY(launch_by_potential(h, name, double_well, harmonic, p.grid, params));
-    }
-    return AMC_OK;
-}
-
-// The same for a handle with a partition (amc_set_blocks): the pass in the traversal of amc_blocks.h -- a grid that is a multiple of B,
-// HIP block k serving jackknife block k mod B --, split into launches by ladder ranges that keep every lane within XS_LANE_CAP - 2
-// summands (blk::ladders_per_launch).  The kernels take the partition as their second argument.
-static inline int blocks_groups(const amc_handle* h) { return h->lad.n_rungs ? h->lad.n_rungs : 1; }
 static inline amc::blk::Part blocks_part(const amc_handle* h)
 {
     amc::blk::Part part = {};
-    part.l_first = h->offset / blocks_groups(h);
+    part.l_first = h->offset / pass_groups(h);
     part.chunk = h->blocks.chunk;
     part.n_blocks = h->blocks.n_blocks;
     return part;
 }
-AMC_INTERNAL int blocks_pass_plan(amc_handle* h, int n_cols, RungPass* p);      // amc_exchange.hip
+// A planned pass launched: `a` comes with what only its kernel reads (the bridge sums' beta, the origin of the time correlation); x, the
+// rows, the ladders, G and the columns are filled in here, and behind `a` the partition when the pass is blocked.
 template <class Args>
-static inline int blocks_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
+static inline int rung_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
 {
     const int64_t n_ladders = h->M / p.groups;
     amc::blk::Part part = blocks_part(h);
@@ -539,11 +524,12 @@ static inline int blocks_pass_launch(amc_handle* h, const RungPass& p, Args a, i
         a.rows = h->lad.d_rung_rows + (size_t)i * (size_t)p.grid * p.slot_words;
         a.l_begin = i * p.per_launch;
         a.l_end = std::min(n_ladders, (i + 1) * p.per_launch);
-        void* params[] = {&a, &part};
+        void* params[] = {&a, p.blocked ? &part : nullptr};      // (a kernel reads as many as it has arguments)
         AMC_TRY(launch_by_potential(h, name, double_well, harmonic, p.grid, params));
     }
     return AMC_OK;
 }
+
 // *p holds exactly `need` words, zeroed on the stream when it is (re)allocated: the blocked accumulators follow B and G at their first use
 static inline int blocks_words(amc_handle* h, amc::xs_word** p, size_t* have, size_t need)
 {

@@ -20,11 +20,12 @@
 //   amc_pg_tail.h      estimator launch records, GradientData samples, accumulate / update kernels, pending learning steps
 //   amc_estimator.h    K3: pg_estimate_kernel (optionally fused with the sweep and the callback sums)
 //   amc_aux_kernels.h  histogram / energy / conversion kernels, parity-test hooks
-//   amc_exchange.h     replica exchange along a temperature ladder: exchange_kernel, the histogram by rung
+//   amc_exchange.h     replica exchange along a temperature ladder: exchange_kernel, the histogram by rung; the rung and bridge sums and
+//                      the frame of every sum by group (slot prologue, block end, finishing merge)
 //   amc_anneal.h       population annealing: log-weights, integer weights, the three-launch prefix, the gather, the families
 //   amc_anneal_search.h  population annealing: the next beta from a target on the effective-sample fraction (energies, sums, decision)
 //   amc_corr.h         time correlation from one time origin: the sums of O, O^2, a O by group, one slot per lag
-//   amc_blocks.h       jackknife blocks: the bridge sums and the time correlation per block of ladders, the traversal's index arithmetic
+//   amc_blocks.h       jackknife blocks: the traversal's index arithmetic, the bridge sums and the time correlation per block of ladders
 #pragma once
 
 #include "amc_model.h"

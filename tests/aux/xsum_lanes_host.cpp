@@ -3,7 +3,7 @@
 //   xsum_lanes_host <file of raw Float64s> <L> [<blocks>]
 // The values are cut into <blocks> contiguous pieces (default 1); a piece is one "block" of L lanes.  Summand i of a block goes to
 // lane i mod L, which runs the per-lane sequence of rl_deposit (amc_wave_sums.h): the special-flag check, xs_r_rebase when its top
-// cannot take the value, xs_r_split, ++n.  Then the end-of-block sequence of rung_sums_kernel (amc_exchange.h): the maximum of the
+// cannot take the value, xs_r_split, ++n.  Then the block end of the sums by group (group_rows_end, amc_exchange.h): the maximum of the
 // lanes' tops and the OR of their flags, every lane's xs_r_multiples brought to that top by xs_r_settle, integer addition,
 // rec_from_r.  Prints the XS_WORDS words of each block's record on one line.
 // Build: c++ -O2 -std=c++17 -ffp-contract=off (tests/test_xsum.py); the header is plain host C++ once the two qualifiers are empty.

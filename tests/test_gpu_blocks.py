@@ -289,6 +289,30 @@ def test_a_planted_value_flags_its_own_block_rung_and_columns_on_a_ladder(gpu):
     assert not got[:3, :, :, 2].any() and got[3, 1, :, 2].all()
 
 
+# ---- 5c. levels: every branch of the block end in one slot of one HIP block ----------------------------------------------------------------
+@pytest.mark.parametrize("sums", ["bridge", "corr"])
+def test_levels_differ_among_the_lanes_of_one_slot_of_one_block(gpu, sums):
+    """R = 3, L = 64, B = 2, C = 32: two HIP blocks, each with the one chunk of its jackknife block, a chain per lane.  The ladders of
+    rung 1 hold |x| near 1, 2^-20, 2^-40, 2^-90 in turn, so every chunk holds all four and neighbouring lanes of that rung sit 0, 1
+    and >= 2 levels of 50 bits below the slot's top: O = x at the levels 0, -1, -1, -2; the harmonic e = x^2 at 0, -1, -2, -4."""
+    R, L, n_blocks, chunk = 3, 64, 2, 32
+    eng, beta = ladder_engine(gpu, R, L)
+    l = np.arange(L)
+    x = eng.download_state()[0].reshape(L, R)
+    x[:, 1] = np.where(l % 3 == 0, -1.0, 1.0) * (1.0 + 0.37 * np.sin(l)) * np.array([1.0, 2.0 ** -20, 2.0 ** -40, 2.0 ** -90])[l % 4]
+    eng.upload_state(x.reshape(-1), beta)
+    eng.set_ladder(R)
+    eng.set_blocks(n_blocks, chunk)
+    if sums == "bridge":
+        eng.bridge_accumulate()
+        same(eng.bridge_fetch_blocks()[0], bridge_twin_now(eng, beta, R, n_blocks, chunk), "levels in one slot of one block, bridge")
+    else:
+        eng.corr_mark("x")
+        series = [eng.download_state()[0]]
+        same(eng.corr_fetch_blocks()[0], K.corr_records(series, R, n_blocks, chunk), "levels in one slot of one block, corr")
+    eng.close()
+
+
 # ---- 8. the setters and a resume -----------------------------------------------------------------------------------------------------------
 def test_setters_refuse_what_their_twins_refuse_and_a_resumed_handle_ends_on_the_same_bits(gpu):
     R, L, n_blocks, chunk = 3, 211, 8, 5
@@ -322,6 +346,8 @@ def test_setters_refuse_what_their_twins_refuse_and_a_resumed_handle_ends_on_the
     refused(part.set_bridge_blocks, rec[:4], n)                                      # another number of blocks
     refused(part.set_bridge_blocks, changed(rec, (2, 1, 0, 0), 5.0), n)              # no kind-R record
     refused(part.set_bridge_blocks, changed(rec, (2, 1, 0, 1), 1e9), n)              # a level outside the range
+    refused(part.set_bridge_blocks, changed(rec, (2, 1, 0, 1), 0.5), n)              # a level that is no integer
+    refused(part.set_bridge_blocks, changed(rec, (2, 1, 0, 2), 0.5), n)              # flags that are no integer
     refused(part.set_bridge_blocks, changed(rec, (2, 1, 0, 5), 0.5), n)              # a word that is no integer
     refused(part.set_bridge_blocks, changed(rec, (2, 1, 0, 5), 2.0 ** 53), n)        # ... not below 2^53
     refused(part.set_bridge_blocks, changed(rec, (2, R - 1, 2), rec[2, 0, 2]), n)    # WF at the last rung has no summand

@@ -413,6 +413,14 @@ def test_set_bridge_restores_the_accumulator(gpu):
         eng.sweep(2); eng.exchange(1); eng.bridge_accumulate(B.ACCEPTANCE_SET)
     ra, rb = a.bridge_fetch(), b.bridge_fetch()
     assert ra[1] == rb[1] == 3 and np.array_equal(bits(ra[0]), bits(rb[0]))
+    # a level word or a flag word that is no integer is refused, as amc_set_corr refuses it, and the accumulator stays as it was
+    for word, value in ((1, 0.5), (2, 0.5)):
+        bad = rb[0].copy()
+        bad[1, 0, word] = value
+        with pytest.raises(gpu.AmcError, match=r"amc error -1.*amc_set_bridge.*rung 1, column 0 is no kind-R record"):
+            b.set_bridge(bad, 3)
+    after = b.bridge_fetch()
+    assert after[1] == 3 and np.array_equal(bits(after[0]), bits(rb[0]))
     a.close(); b.close()
 
 

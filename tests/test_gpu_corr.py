@@ -184,6 +184,33 @@ def test_flags_touch_their_own_records_only(gpu):
     eng.close()
 
 
+@pytest.mark.parametrize("kind", ["x", "energy"])
+def test_levels_differ_among_the_lanes_of_one_slot(gpu, kind):
+    """Every branch of the block end in ONE slot of one block.  R = 3, L = 64: 192 lanes of one block with one chain each (the 64
+    lanes behind them have none), and the ladders of rung 1 hold |x| near 1, 2^-20, 2^-40, 2^-90 in turn, so neighbouring lanes of
+    that rung sit 0, 1 and >= 2 levels of 50 bits below the slot's top: in O = x at the levels 0, -1, -1, -2, in O = e = x^2 at
+    0, -1, -2, -4.  The mark, then a sample whose values are the neighbouring ladder's (a O mixes the magnitudes)."""
+    R, L = 3, 64
+    x, beta = start_state(R * L, R)
+    l = np.arange(L)
+    a = x.copy().reshape(L, R)
+    a[:, 1] = np.where(l % 3 == 0, -1.0, 1.0) * (1.0 + 0.37 * np.sin(l)) * np.array([1.0, 2.0 ** -20, 2.0 ** -40, 2.0 ** -90])[l % 4]
+    eng = gpu.HipEngine(n_chains=R * L, potential="harmonic", beta=1.0, sigma=[0.5], weight=[1.0], seed=5)
+    eng.upload_state(a.reshape(-1), beta)
+    eng.set_ladder(R)
+    eng.corr_mark(kind)
+    series = [observe(eng, kind)]
+    rec0, steps0, _ = eng.corr_fetch()
+    same_records(rec0, T.records(series, R), f"levels in one slot, the mark, {kind}")
+    origin = eng.corr_origin()
+    eng.upload_state(np.roll(a, 1, axis=0).reshape(-1), beta)         # (through the checkpoint route: an upload clears the mark)
+    eng.set_corr(kind, origin, rec0, steps0)
+    eng.corr_sample()
+    series.append(observe(eng, kind))
+    same_records(eng.corr_fetch()[0], T.records(series, R), f"levels in one slot, a sample, {kind}")
+    eng.close()
+
+
 # ---- 4. shards ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("R", [0, 6])
 def test_shard_invariance(gpu, R):

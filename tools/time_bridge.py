@@ -9,7 +9,11 @@ alternating REPEATS times (median and range of the windows); prints the markdown
 the bridge sums did, so the same command on an older checkout gives the figure to compare with (the bridge-off path launches nothing
 new) -- and, beside it, per round with a snapshot behind every round.
 
-    python tools/time_bridge.py [--chains 10000000] [--rungs 8] [--launches 300] [--repeats 7] [--rounds]
+--blocks B [--chunk C]: the same figures with a jackknife partition set (amc_set_blocks; C = 0: the default chunk), the rows of
+profiles/jackknife_blocks.md; amc_reduce_rungs_exact stays unpartitioned under a partition, so its row is the same yardstick.  Every
+window begins with five untimed calls: the first snapshot allocates its accumulator, and an allocation waits for the stream.
+
+    python tools/time_bridge.py [--chains 10000000] [--rungs 8] [--launches 300] [--repeats 7] [--potential harmonic] [--blocks 0] [--chunk 0] [--rounds]
 """
 import argparse
 import os
@@ -24,6 +28,8 @@ MASKS = (("E", 1), ("E | EE | MF | MB", 1 | 2 | 16 | 32), ("all six", 63))
 
 
 def device_us(eng, call, n):
+    for _ in range(5):
+        call()
     eng.sync()
     eng.timing_begin()
     for _ in range(n):
@@ -31,12 +37,14 @@ def device_us(eng, call, n):
     return eng.timing_end() * 1e3 / n
 
 
-def make_engine(M, R):
+def make_engine(M, R, potential="harmonic", blocks=0, chunk=0):
     betas = 0.5 * 1.3 ** np.arange(R)
-    eng = _capi.HipEngine(n_chains=M, potential="harmonic", beta=1.0, sigma=[0.5], weight=[1.0], seed=1, per_chain_counters=False)
+    eng = _capi.HipEngine(n_chains=M, potential=potential, beta=1.0, sigma=[0.5], weight=[1.0], seed=1, per_chain_counters=False)
     eng.upload_state(np.zeros(M), np.tile(betas, M // R))
     eng.init_uniform(-2.0, 2.0)
     eng.set_ladder(R)
+    if blocks:
+        eng.set_blocks(blocks, chunk)
     for _ in range(3):                                   # ramp: clocks up, state equilibrated
         eng.sweep_exchange(200, 1)
     eng.sync()
@@ -53,12 +61,16 @@ def main(argv=None):
     ap.add_argument("--rungs", type=int, default=8)
     ap.add_argument("--launches", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--potential", default="harmonic", choices=("harmonic", "double_well"))
+    ap.add_argument("--blocks", type=int, default=0, help="jackknife blocks B (0: no partition)")
+    ap.add_argument("--chunk", type=int, default=0, help="ladders per chunk C (0: the default chunk)")
     ap.add_argument("--rounds", action="store_true", help="[sweep; exchange] rounds with the bridge off (and on)")
     args = ap.parse_args(argv)
     R, n = args.rungs, args.launches
     M = (args.chains // R) * R
-    eng = make_engine(M, R)
-    print(f"M = {M}, R = {R}, harmonic, Float64, K = 1; {args.repeats} alternating windows of {n} calls per figure (median, min .. max)\n")
+    eng = make_engine(M, R, args.potential, args.blocks, args.chunk)
+    part = f", B = {args.blocks}, C = {args.chunk or 'default'}" if args.blocks else ""
+    print(f"M = {M}, R = {R}, {args.potential}, Float64, K = 1{part}; {args.repeats} alternating windows of {n} calls per figure (median, min .. max)\n")
     if args.rounds:
         off, on = [], []
         has_bridge = hasattr(eng, "bridge_accumulate")
