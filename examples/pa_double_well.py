@@ -16,7 +16,12 @@ largest step towards beta = 8 whose reweighting keeps the effective-sample fract
 (PopulationAnnealing(adaptive=...), amc_anneal_next_beta), for at most --stages steps.  Every run then has its own list, so the script
 prints log(Z(8) / Z(0.5)) of the runs beside the quadrature, and the steps the last run chose.
 
+With --reweight N the energy histogram of the population is taken on the device in front of every annealing step and at the end
+(PopulationAnnealing(energy_histogram=...)), and the last run prints <e>(beta), C(beta) and log(Z(beta) / Z(0.5)) by multiple-histogram
+reweighting over the temperatures of the schedule on an N-point grid from 0.5 to the last beta, each beside the quadrature.
+
     python examples/pa_double_well.py [--chains 65536] [--stages 24] [--sweeps 10] [--runs 8] [--path data/PA/...] [--adaptive TARGET]
+                                      [--reweight N]
 """
 import argparse
 import os
@@ -38,6 +43,36 @@ def log_z_by_quadrature(betas):
     return np.array([np.log(np.sum(np.exp(-b * (x * x - 1.0) ** 2)) * (x[1] - x[0])) for b in betas])
 
 
+# the chance of e >= 60 at beta = 0.5 is below 1e-14: no sample of any run lands outside; one row of 6003 cells.  Energies sit at the bin centres, and
+# the density of states diverges at e -> 0: at the cold end, where <e> ~ 1 / (2 beta) is a few bins wide, the curve shows that bias
+HIST = dict(lo=0.0, hi=60.0, n_bins=6000)
+
+
+def curve_by_quadrature(betas):
+    """(log Z, <e>, C) at every beta of `betas` by the trapezoid rule on the same grid."""
+    x = np.linspace(-8.0, 8.0, 320001)
+    u = (x * x - 1.0) ** 2
+    out = []
+    for b in betas:
+        w = np.exp(-b * u)
+        z, m1, m2 = np.sum(w), np.sum(w * u), np.sum(w * u * u)
+        out.append((np.log(z * (x[1] - x[0])), m1 / z, b * b * (m2 / z - (m1 / z) ** 2)))
+    return tuple(np.array(v) for v in zip(*out))
+
+
+def print_reweighted(args, pa):
+    """--reweight: the curve along the schedule from the last run's histograms, beside the quadrature."""
+    taken, _ = pa.histograms()
+    grid = np.exp(np.linspace(np.log(taken[0]), np.log(taken[-1]), max(2, args.reweight)))
+    log_z, m1, _, c = pa.reweight(grid)
+    q_log_z, q_m1, q_c = curve_by_quadrature(grid)
+    q0 = curve_by_quadrature(taken[:1])[0][0]
+    print(f"last run, reweighted over {len(taken)} temperatures, {HIST['n_bins']} bins of [{HIST['lo']:g}, {HIST['hi']:g}): WHAM | quadrature")
+    print("     beta       <e>               C                 log(Z / Z(0.5))")
+    for b, e1, e2, c1, c2, z1, z2 in zip(grid, m1, q_m1, c, q_c, log_z, q_log_z - q0):
+        print(f"  {b:7.4f}   {e1:7.4f} | {e2:7.4f}   {c1:7.4f} | {c2:7.4f}   {z1:8.4f} | {z2:8.4f}")
+
+
 def one_run(args, path, seed):
     betas = BETA_HOT * (BETA_COLD / BETA_HOT) ** (np.arange(args.stages + 1) / args.stages)
     steps = BURN + args.stages * args.sweeps
@@ -46,6 +81,8 @@ def one_run(args, path, seed):
     # BURN sweeps at the hot end, then [anneal; sweeps] per stage: the annealing step is due at BURN, BURN + sweeps, ...
     when = [BURN + i * args.sweeps for i in range(args.stages)]
     schedule = dict(betas=list(betas[1:])) if args.adaptive is None else dict(adaptive=dict(beta_end=BETA_COLD, target=args.adaptive))
+    if args.reweight:
+        schedule["energy_histogram"] = HIST
     algorithm_list = [dict(algorithm=ma.Metropolis, pool=pool, seed=seed),
                       dict(algorithm=ma.PopulationAnnealing, dependencies=(ma.Metropolis,), scheduler=when, families=True, **schedule),
                       dict(algorithm=ma.StoreCallbacks, callbacks=(ma.callback_energy, ma.callback_anneal_beta, ma.callback_anneal_log_z, ma.callback_rho_t),
@@ -77,6 +114,8 @@ def adaptive_main(args, path):
         kept = float(np.array([log[i, 3]], dtype=np.uint64).view(np.float64)[0])
         print(f"{done[i]:7.4f}   {lz[i]:12.6f}   {exact[i]:12.6f}   {survival[i]:7.4f}   {kept:8.4f}   {ma.ANNEAL_SEARCH_STATUS[int(log[i, 0])]}")
     print(f"last run: rho_t = {pa.rho_t():.2f} of {args.chains} chains")
+    if args.reweight:
+        print_reweighted(args, pa)
     return ends, exact[-1], tol, done
 
 
@@ -90,6 +129,9 @@ def main(argv=None):
     ap.add_argument("--path", default=None)
     ap.add_argument("--adaptive", type=float, default=None, metavar="TARGET",
                     help="choose every step on the device: the largest one that keeps ESS / M >= TARGET (--stages is then the most steps a run may take)")
+    ap.add_argument("--reweight", type=int, default=0, metavar="N",
+                    help="take the energy histogram at every annealing temperature; print <e>, C and log Z on an N-point grid of beta along "
+                         "the schedule by multiple-histogram reweighting, beside the quadrature")
     args = ap.parse_args(argv)
     path = args.path or f"data/PA/particle_1d/DoubleWell/M{args.chains}/seed{args.seed}"
     if args.adaptive is not None:
@@ -113,6 +155,8 @@ def main(argv=None):
     worst = int(np.argmax(np.abs(mean - exact) / tol)) if args.runs > 1 else args.stages - 1
     print(f"largest deviation in units of its tolerance: {abs(mean[worst] - exact[worst]) / tol[worst]:.3f} at beta = {betas[worst + 1]:.4f}")
     print(f"last run: rho_t = {rho:.2f} of {args.chains} chains, fraction x < 0 at beta = {betas[-1]:.1f}: {left:.4f}")
+    if args.reweight:
+        print_reweighted(args, pa)
     return mean, exact, tol, survival, rho, left
 
 

@@ -7,7 +7,7 @@ down.  Every chain starts in the right well; the script runs the same schedule w
 rung, the fraction of chains left of the barrier, the mean energy and the swap acceptance of every gap.
 
     python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track] [--rung-sigma] [--adapt flow|acceptance]
-                                          [--tune-sigma TARGET] [--free-energy [--blocks 32]]
+                                          [--tune-sigma TARGET] [--free-energy [--blocks 32]] [--reweight N]
 
 --track also follows every replica through the swaps and prints, at the end, the flow fraction f(r) -- of the replicas at rung r that
 have been to an end of the ladder, the share that came from the hot end (rung 0) last -- and the round trips per ladder.
@@ -29,6 +29,11 @@ per rung over the window since the last tuning: the second half, under the final
 --free-energy accumulates the bridge sums over the second half of the run and prints log(Z_(r+1) / Z_r) by three estimators beside a
 quadrature, and the heat capacity per rung.  With --blocks B the sums are kept per block of ladders (ReplicaExchange(..., blocks=B)) and
 every estimate comes with the standard error of a delete-one-block jackknife over the B blocks, value +- se.
+
+--reweight N accumulates an energy histogram per rung on the device over the second half of the run (EnergyHistogram, 100 snapshots)
+and prints <e>(beta), C(beta) and log(Z(beta) / Z(beta_0)) by multiple-histogram reweighting (WHAM) on an N-point grid between the end
+rungs, each beside the quadrature -- the curve BETWEEN the simulated temperatures.  With --free-energy the WHAM free energies per rung
+are printed beside the bridge estimates.
 """
 import argparse
 import os
@@ -57,6 +62,23 @@ def log_z_by_quadrature():
     """log Z_r, Z_r = integral of exp(-beta_r (x^2 - 1)^2) dx, by the trapezoid rule on a fine grid (the integrand is below 1e-300 at the ends)."""
     x = np.linspace(-6.0, 6.0, 240001)
     return np.array([np.log(np.sum(np.exp(-b * (x * x - 1.0) ** 2)) * (x[1] - x[0])) for b in BETAS])
+
+
+# the chance of e >= 60 at beta = 0.5 is below 1e-14: no sample of any run lands outside; 5 x 2403 cells: the per-block LDS path.  Energies sit at the bin centres, and
+# the density of states diverges at e -> 0: at the cold end, where <e> ~ 1 / (2 beta) is a few bins wide, the curve shows that bias
+HIST = dict(lo=0.0, hi=60.0, n_bins=2400)
+
+
+def curve_by_quadrature(betas):
+    """(log Z, <e>, C) at every beta of `betas` by the trapezoid rule on the same grid."""
+    x = np.linspace(-6.0, 6.0, 240001)
+    u = (x * x - 1.0) ** 2
+    out = []
+    for b in betas:
+        w = np.exp(-b * u)
+        z, m1, m2 = np.sum(w), np.sum(w * u), np.sum(w * u * u)
+        out.append((np.log(z * (x[1] - x[0])), m1 / z, b * b * (m2 / z - (m1 / z) ** 2)))
+    return tuple(np.array(v) for v in zip(*out))
 
 
 def one_run(args, path, exchange: bool):
@@ -91,6 +113,11 @@ def one_run(args, path, exchange: bool):
             algorithm_list.append(dict(algorithm=ma.TuneRungSigma, dependencies=(ma.Metropolis,), target=args.tune_sigma, gamma=1.0, min_calls=1000,
                                        scheduler=list(range(half - 9 * every, half + 1, every)), until=half))
             callbacks.append(ma.callback_rung_sigma)
+        if args.reweight:                              # measure over the second half of the run, behind every respacing and tuning
+            half = args.steps // 2
+            every = max(1, (args.steps - half) // 100)
+            algorithm_list.append(dict(algorithm=ma.EnergyHistogram, dependencies=(ma.Metropolis,),
+                                       scheduler=list(range(half + every, args.steps + 1, every)), **HIST))
     algorithm_list.append(dict(algorithm=ma.StoreCallbacks, callbacks=tuple(callbacks),
                                scheduler=ma.build_schedule(args.steps, 0, max(1, args.steps // 10))))
     simulation = ma.Simulation(chains, algorithm_list, args.steps, path=path)
@@ -119,6 +146,9 @@ def main(argv=None):
     ap.add_argument("--free-energy", action="store_true",
                     help="accumulate the bridge sums over the second half of the run; print log(Z_(r+1) / Z_r) by three estimators beside a "
                          "quadrature, and the heat capacity per rung")
+    ap.add_argument("--reweight", type=int, default=0, metavar="N",
+                    help="accumulate an energy histogram per rung over the second half of the run; print <e>, C and log Z on an N-point grid "
+                         "of beta between the end rungs by multiple-histogram reweighting, beside the quadrature")
     ap.add_argument("--blocks", type=int, default=None, metavar="B",
                     help="with --free-energy: keep the bridge sums per block of ladders and print every estimate +- its jackknife standard error")
     args = ap.parse_args(argv)
@@ -166,6 +196,22 @@ def main(argv=None):
             print("  exponential, backward       : " + "  ".join(f"{v:7.4f}" for v in expo[1]))
             print("  thermodynamic integration   : " + "  ".join(f"{v:7.4f}" for v in rx.log_z_ratios("ti")) + "   (trapezoid: coarse on this ladder)")
             print("heat capacity per rung        : " + "  ".join(f"{v:7.4f}" for v in rx.heat_capacity()))
+    if args.reweight:
+        eh = next(a for a in sim.algorithms if isinstance(a, ma.EnergyHistogram))
+        ladder = eh.betas()
+        grid = np.exp(np.linspace(np.log(ladder[0]), np.log(ladder[-1]), max(2, args.reweight)))
+        log_z, m1, _, c = eh.reweight(grid)
+        q_log_z, q_m1, q_c = curve_by_quadrature(grid)
+        q_log_z0 = curve_by_quadrature(ladder[:1])[0][0]
+        print(f"reweighted curve, {eh.n_snapshots} snapshots of {args.ladders} ladders, {HIST['n_bins']} bins of [{HIST['lo']:g}, {HIST['hi']:g}): WHAM | quadrature")
+        print("     beta       <e>               C                 log(Z / Z_0)")
+        for b, e1, e2, c1, c2, z1, z2 in zip(grid, m1, q_m1, c, q_c, log_z, q_log_z - q_log_z0):
+            print(f"  {b:7.4f}   {e1:7.4f} | {e2:7.4f}   {c1:7.4f} | {c2:7.4f}   {z1:8.4f} | {z2:8.4f}")
+        if args.free_energy:
+            rx = sim.algorithms[1]
+            print("log(Z_r / Z_0), WHAM (-f_r)   : " + "  ".join(f"{v:7.4f}" for v in -eh.free_energies()))
+            print("log(Z_r / Z_0), bridge sums   : " + "  ".join(f"{v:7.4f}" for v in rx.log_z("acceptance")))
+            print("log(Z_r / Z_0), quadrature    : " + "  ".join(f"{v:7.4f}" for v in curve_by_quadrature(ladder)[0] - q_log_z0))
     if args.adapt:
         rx = sim.algorithms[1]
         print(f"ladder after {rx.metropolis.engine.respace_status()[1]} respacings   : " + "  ".join(f"{b:7.4f}" for b in rx.betas()) + "   (second half: the lines above and below)")

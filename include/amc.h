@@ -739,6 +739,43 @@ int  amc_corr_download_origin(amc_handle *h, double *origin);
 int  amc_set_corr(amc_handle *h, int observable, const double *origin, const double *records, const uint64_t *steps, int n_samples);
 int  amc_corr_clear(amc_handle *h);
 
+/* Energy histograms: per group a histogram of the chains' energies, accumulated on the device over as many
+ * snapshots as the caller queues -- all that multiple-histogram reweighting (Ferrenberg-Swendsen / WHAM) needs to give <e>, C and
+ * log Z BETWEEN the simulated temperatures.  Counts are integers: the same on any grid, in any snapshot order and on any split into
+ * shards.  Groups are those of the time correlation: G = R with a ladder (group r = the chains l R + r), G = 1 without one, over all
+ * local chains.
+ * Binning rule: for chain i, e = potential_T(x_i) in the state type T, read from the state buffer itself (Float32 state: the Float32 x),
+ * as the bridge sums form it; v = double(e) (exact); with inv_w = (double)n_bins / (hi - lo) the cell is
+ *   n_bins + 2  if v is NaN,   n_bins  if v < lo,   n_bins + 1  if v >= hi,   otherwise  min((int)((v - lo) * inv_w), n_bins - 1)
+ * -- Float64 subtraction and product, truncation; the clamp serves (hi - ulp - lo) * inv_w rounding up to n_bins --, amc_histogram's
+ * rule applied to e.  Row layout per group is n_bins + 3 cells: counts[g * (n_bins + 3) + cell].  Arguments as amc_histogram takes
+ * them: 1 <= n_bins <= 8192, finite lo < hi.
+ * amc_energy_histogram_accumulate queues one pass behind whatever is on the stream and returns at once (a pending learning step is
+ * taken first, as before amc_bridge_accumulate; with sliced sweep launches it runs behind their join, where a bridge snapshot runs).
+ * The first call after a reset allocates and zeroes G * (n_bins + 3) 64-bit counters on the device and fixes (lo, hi, n_bins); a later
+ * call with other values is AMC_ERR_STATE.
+ * amc_energy_histogram_fetch waits and returns the LOCAL shard's counts (counts add across shards), *n_groups = G, *n_bins, *lo, *hi,
+ * and *n_snapshots = (sum of row 0) / (n_chains / G): every chain lands in exactly one of the n_bins + 3 cells of its group, so EVERY
+ * row sums to n_snapshots * n_chains / G exactly.  With nothing accumulated it writes no counts, sets *n_bins = 0 and
+ * *n_snapshots = 0 and returns AMC_OK.  capacity_cells counts the 64-bit cells the caller's array holds; fewer than G * (n_bins + 3)
+ * is AMC_ERR_BAD_ARG.  counts = NULL is allowed: the call then returns the sizes and the bins alone (*n_snapshots = 0), without waiting
+ * for the stream, copying or resetting -- what a caller sizes its array by.  reset != 0 frees the accumulator: the next accumulate may
+ * bring other bins.
+ * amc_set_energy_histogram restores the accumulator (checkpoints): counts = NULL or n_snapshots = 0 clears it; otherwise
+ * counts[G * (n_bins + 3)] whose rows do not ALL sum to n_snapshots * n_chains / G are AMC_ERR_BAD_ARG.
+ * CLEARED by amc_set_ladder on success (the groups change).  A respacing that is taken (status 0) ZEROES the cells on the device, in
+ * stream order, exactly as it zeroes the bridge records -- counts taken at other beta belong to another ladder --; the bins stay
+ * fixed, and one that is not taken leaves the cells alone.
+ * KEPT by sweeps, exchange steps, reductions, the estimator, tuning, amc_upload_state, amc_init_uniform, amc_set_blocks (a histogram
+ * is not kept per jackknife block), and -- on purpose -- by amc_anneal and amc_set_beta: a histogram belongs to ONE beta per group,
+ * so the caller fetches with reset before beta moves (the Python layer does); the engine cannot know whether the caller is done.
+ * None of the three entries touches a step index, the step log, a counter, reductions in flight, labels, widths, the bridge sums or
+ * the mark of the time correlation.  A refused call leaves the handle as it was. */
+int  amc_energy_histogram_accumulate(amc_handle *h, double lo, double hi, int n_bins);
+int  amc_energy_histogram_fetch(amc_handle *h, uint64_t *counts, int64_t capacity_cells, int *n_groups, int *n_bins,
+                                double *lo, double *hi, uint64_t *n_snapshots, int reset);
+int  amc_set_energy_histogram(amc_handle *h, double lo, double hi, int n_bins, const uint64_t *counts_or_null, uint64_t n_snapshots);
+
 /* Jackknife blocks: the bridge sums and the time correlation kept per BLOCK of ladders, so that a
  * delete-one-block jackknife over the B blocks gives an error bar for any function of the sums -- the ladders (the chains, without a
  * ladder) are independent systems, whatever the correlation in time or between the rungs of one ladder.

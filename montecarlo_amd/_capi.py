@@ -37,6 +37,7 @@ AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_WF, AMC_BRIDGE_WB, AMC_BRIDGE_MF, AMC_BR
 AMC_CORR_E, AMC_CORR_X = 1, 2
 AMC_CORR_MAX_LAGS = 256
 AMC_MAX_JK_BLOCKS = 64          # blocks of a jackknife partition (amc_set_blocks)
+AMC_EHIST_MAX_BINS = 8192       # bins of any histogram entry (amc_histogram, amc_energy_histogram_accumulate)
 AMC_CORR_O, AMC_CORR_OO, AMC_CORR_AO, AMC_CORR_COLS = 0, 1, 2, 3
 CORR_OBSERVABLES = {"energy": AMC_CORR_E, "x": AMC_CORR_X}
 AMC_RESPACE_ACCEPTANCE, AMC_RESPACE_FLOW = 1, 2      # the rules of amc_respace_ladder (include/amc.h)
@@ -190,6 +191,9 @@ def load() -> C.CDLL:
         "amc_corr_download_origin": (C.c_int, [H, dp]),
         "amc_set_corr": (C.c_int, [H, C.c_int, dp, dp, u64p, C.c_int]),
         "amc_corr_clear": (C.c_int, [H]),
+        "amc_energy_histogram_accumulate": (C.c_int, [H, C.c_double, C.c_double, C.c_int]),
+        "amc_energy_histogram_fetch": (C.c_int, [H, u64p, C.c_int64, ip, ip, dp, dp, u64p, C.c_int]),
+        "amc_set_energy_histogram": (C.c_int, [H, C.c_double, C.c_double, C.c_int, u64p, C.c_uint64]),
         "amc_set_blocks": (C.c_int, [H, C.c_int, C.c_int64]),
         "amc_bridge_fetch_blocks": (C.c_int, [H, dp, C.c_int, ip, u64p, C.c_int]),
         "amc_corr_fetch_blocks": (C.c_int, [H, dp, u64p, C.c_int, ip, ip, ip]),
@@ -871,6 +875,41 @@ class HipEngine:
     def corr_clear(self) -> None:
         """Drop the mark (amc_corr_clear); the memory stays."""
         _check(self._lib.amc_corr_clear(self._h))
+
+    # -- energy histograms (include/amc.h; DESIGN.md section 3.17) ----------------
+    # (Not offered on a SplitEngine, as bridge_accumulate is not: the sub-shards of one GPU keep no ladder state.)
+    def energy_histogram_accumulate(self, lo: float, hi: float, n_bins: int) -> None:
+        """Queue one snapshot of the energy histograms -- per group (rung; one group without a ladder) the counts of
+        e = potential(x) over ``n_bins`` half-open bins of [lo, hi) and the three cells below / at or above / NaN -- into the
+        device-resident accumulator (amc_energy_histogram_accumulate).  Stream-ordered, nothing synchronises.  The bins are fixed by
+        the first call after a reset."""
+        _check(self._lib.amc_energy_histogram_accumulate(self._h, float(lo), float(hi), int(n_bins)))
+
+    def energy_histogram_fetch(self, reset: bool = False):
+        """(counts[G, n_bins + 3] uint64, n_snapshots, (lo, hi, n_bins)) of this shard's accumulator (amc_energy_histogram_fetch);
+        counts add across shards.  With nothing accumulated: counts of shape (G, 0), 0 snapshots, (0.0, 0.0, 0).  ``reset`` frees
+        the accumulator and its bins.  Synchronises."""
+        ng, nb, lo, hi, count = C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_double(0.0), C.c_uint64(0)
+        sizes = (C.byref(ng), C.byref(nb), C.byref(lo), C.byref(hi), C.byref(count))
+        _check(self._lib.amc_energy_histogram_fetch(self._h, None, 0, *sizes, 0))      # the sizes alone: nothing waits
+        if nb.value == 0:
+            return np.zeros((ng.value, 0), dtype=np.uint64), 0, (0.0, 0.0, 0)
+        out = np.empty(ng.value * (nb.value + 3), dtype=np.uint64)
+        _check(self._lib.amc_energy_histogram_fetch(self._h, _ptr(out), int(out.size), *sizes, int(bool(reset))))
+        return out[:ng.value * (nb.value + 3)].reshape(ng.value, nb.value + 3).copy(), int(count.value), (lo.value, hi.value, nb.value)
+
+    def set_energy_histogram(self, lo: float = 0.0, hi: float = 0.0, n_bins: int = 0, counts=None, n_snapshots: int = 0) -> None:
+        """Restore the accumulator from ``energy_histogram_fetch``'s counts, count and bins (amc_set_energy_histogram; checkpoints);
+        ``counts=None`` or ``n_snapshots=0`` clears it."""
+        if counts is None or int(n_snapshots) == 0:
+            _check(self._lib.amc_set_energy_histogram(self._h, 0.0, 0.0, 0, None, 0))
+            return
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        if c.size != self._rungs() * (int(n_bins) + 3):
+            raise AmcError(f"set_energy_histogram: {c.size} counts, {self._rungs()} rows of {int(n_bins)} bins take {self._rungs() * (int(n_bins) + 3)}")
+        if int(n_snapshots) < 0:
+            raise AmcError("set_energy_histogram: n_snapshots < 0")
+        _check(self._lib.amc_set_energy_histogram(self._h, float(lo), float(hi), int(n_bins), _ptr(c), int(n_snapshots)))
 
     # -- jackknife blocks (include/amc.h; DESIGN.md section 3.16) ----------------
     def set_blocks(self, n_blocks: int, chunk: int = 0) -> None:

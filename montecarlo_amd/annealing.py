@@ -20,7 +20,7 @@ import numpy as np
 
 from . import sharding
 from ._capi import (AMC_ANNEAL_MAX_RECORDS, AMC_ANNEAL_RECORD_WORDS, AMC_ANNEAL_SEARCH_MAX_ROUNDS, AMC_ANNEAL_SEARCH_STALLED,
-                    AMC_ANNEAL_SEARCH_WORDS, AMC_ANNEAL_WEIGHT_BITS)
+                    AMC_ANNEAL_SEARCH_WORDS, AMC_ANNEAL_WEIGHT_BITS, AMC_EHIST_MAX_BINS)
 from .metropolis import Metropolis
 from .simulation import AriannaAlgorithm, Simulation, _calls
 
@@ -56,6 +56,26 @@ def _adaptive_plan(adaptive) -> dict:
     return dict(beta_end=beta_end, target=target, rounds=int(rounds))
 
 
+def _histogram_plan(energy_histogram) -> dict:
+    """energy_histogram=dict(lo=..., hi=..., n_bins=..., max_outside=0.0), checked."""
+    try:
+        plan = dict(energy_histogram)
+    except (TypeError, ValueError):
+        raise ValueError(f"PopulationAnnealing: energy_histogram = {energy_histogram!r} is not a dict(lo=..., hi=..., n_bins=...)") from None
+    unknown = sorted(set(plan) - {"lo", "hi", "n_bins", "max_outside"})
+    if unknown:
+        raise ValueError(f"PopulationAnnealing: energy_histogram has unknown keys {unknown} (lo, hi, n_bins, max_outside)")
+    for key in ("lo", "hi", "n_bins"):
+        if key not in plan:
+            raise ValueError(f"PopulationAnnealing: energy_histogram[{key!r}] is missing (it has no default)")
+    lo, hi, n_bins, max_outside = float(plan["lo"]), float(plan["hi"]), plan["n_bins"], float(plan.get("max_outside", 0.0))
+    if int(n_bins) != n_bins or not 1 <= int(n_bins) <= AMC_EHIST_MAX_BINS or not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        raise ValueError(f"PopulationAnnealing: energy_histogram needs an integer 1 <= n_bins <= {AMC_EHIST_MAX_BINS} and finite lo < hi, got {plan!r}")
+    if not 0.0 <= max_outside <= 1.0:
+        raise ValueError(f"PopulationAnnealing: energy_histogram['max_outside'] = {max_outside!r} must lie in [0, 1]")
+    return dict(lo=lo, hi=hi, n_bins=int(n_bins), max_outside=max_outside)
+
+
 class PopulationAnnealing(AriannaAlgorithm):
     """PopulationAnnealing(chains; dependencies=(Metropolis,), betas=[...], families=False): one annealing step of the Metropolis'
     engine per scheduled time, to the next beta of ``betas``.  Listed behind its Metropolis, a time step at which both are due is
@@ -64,11 +84,16 @@ class PopulationAnnealing(AriannaAlgorithm):
     PopulationAnnealing(..., adaptive=dict(beta_end=..., target=..., rounds=6)) instead of ``betas``: each scheduled call is
     [next_beta; anneal] -- the engine finds the largest step towards ``beta_end`` whose reweighting keeps the effective-sample fraction
     ESS / M at or above ``target`` (DESIGN.md section 3.14 "Choosing the next beta") and anneals to it.  The number of steps is not
-    known in advance: once beta == beta_end, scheduled calls launch nothing and append no record (``finished``)."""
+    known in advance: once beta == beta_end, scheduled calls launch nothing and append no record (``finished``).
+
+    PopulationAnnealing(..., energy_histogram=dict(lo=..., hi=..., n_bins=..., max_outside=0.0)): before each annealing step, and once
+    at ``finalise``, the energy histogram of the population at the beta in force is taken on the device (DESIGN.md section 3.17:
+    [accumulate; fetch with reset]) and kept with its beta; ``histograms()`` returns them, ``reweight(betas)`` applies
+    multiple-histogram reweighting over the temperatures of the schedule.  Without the option nothing new is launched."""
 
     mutates_chains = True          # a callback due behind it at the same t observes the state AFTER the resampling
 
-    def __init__(self, chains, dependencies=None, betas=None, adaptive=None, families=False, path=None, **extras):
+    def __init__(self, chains, dependencies=None, betas=None, adaptive=None, families=False, energy_histogram=None, path=None, **extras):
         assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
         self.metropolis: Metropolis = dependencies[0]
         if adaptive is not None and betas is not None:
@@ -91,6 +116,12 @@ class PopulationAnnealing(AriannaAlgorithm):
         if self.adaptive is not None and not hasattr(self.metropolis.engine, "anneal_next_beta"):
             raise ValueError("PopulationAnnealing: this engine cannot choose the next beta (adaptive needs amc_anneal_next_beta)")
         self.families = bool(families)
+        self.hist_plan = None if energy_histogram is None else _histogram_plan(energy_histogram)
+        if self.hist_plan is not None and not hasattr(self.metropolis.engine, "energy_histogram_accumulate"):
+            raise ValueError("PopulationAnnealing: this engine has no energy histograms (energy_histogram needs amc_energy_histogram_accumulate)")
+        self._hist = []                        # energy_histogram: (beta, row[n_bins + 3]) per temperature, oldest first
+        self._hist_final = False               # ... the last one was taken by finalise (a checkpoint leaves it out: the resumed run takes
+                                               # the histogram of that beta itself, in front of its next step or at its own finalise)
         self.chains = chains
         self._records = []                     # records drained from the engine's log, oldest first
         self._search_log = []                  # adaptive: the diag of every search of this process, oldest first
@@ -124,9 +155,77 @@ class PopulationAnnealing(AriannaAlgorithm):
             self._search_log.append(np.array(diag, dtype=np.uint64))
         if i - len(self._records) >= AMC_ANNEAL_MAX_RECORDS:
             self._drain()
+        if self.hist_plan is not None:
+            self._take_histogram(final=False)
         eng.anneal(beta_new)
         self.chains.beta = beta_new
         self.metropolis.invalidate_reductions()
+
+    def finalise(self, simulation: Simulation) -> None:
+        if self.hist_plan is not None and not self._hist_final:
+            self._take_histogram(final=True)
+
+    def _take_histogram(self, final: bool) -> None:
+        """[accumulate; fetch with reset] at the beta in force: one row, kept with its beta.  The histogram finalise took is replaced
+        when the run goes on (the population has been swept since)."""
+        eng, plan = self.metropolis.engine, self.hist_plan
+        if self._hist_final:
+            self._hist.pop()
+        eng.energy_histogram_accumulate(plan["lo"], plan["hi"], plan["n_bins"])
+        counts, _, _ = eng.energy_histogram_fetch(reset=True)
+        self._hist.append((float(eng.beta), np.array(counts[0], dtype=np.uint64)))
+        self._hist_final = bool(final)
+
+    def histograms(self):
+        """(betas[S], counts[S, n_bins + 3]): the energy histogram taken at every temperature so far, the bins, then below lo, at or
+        above hi, NaN.  Needs energy_histogram=..."""
+        if self.hist_plan is None:
+            raise ValueError("PopulationAnnealing.histograms needs the histograms: build the PopulationAnnealing with energy_histogram=dict(...)")
+        n = self.hist_plan["n_bins"] + 3
+        return (np.array([b for b, _ in self._hist], dtype=np.float64),
+                np.array([c for _, c in self._hist], dtype=np.uint64).reshape(-1, n))
+
+    def reweight(self, betas, **kw):
+        """(log Z, <e>, <e^2>, C) at every beta of ``betas`` by multiple-histogram reweighting over the temperatures of the schedule
+        (reweighting.wham / reweight); log Z is 0 at the first temperature.  Raises, naming the temperature and the cell, when a
+        histogram's share outside the bins exceeds ``max_outside``."""
+        from . import reweighting
+        b, counts = self.histograms()
+        if not len(b):
+            raise ValueError("PopulationAnnealing.reweight: no histogram has been taken yet")
+        plan = self.hist_plan
+        share = reweighting.outside_share(counts)
+        bad = np.argwhere(share > plan["max_outside"])
+        if bad.size:
+            s, c = int(bad[0][0]), int(bad[0][1])
+            raise ValueError(f"PopulationAnnealing: the histogram at beta = {b[s]!r} (temperature {s}) has a share of {share[s, c]:.3e} of its "
+                             f"samples in the cell '{('below lo', 'at or above hi', 'NaN')[c]}' (max_outside = {plan['max_outside']:g}): "
+                             f"widen [lo, hi) = [{plan['lo']:g}, {plan['hi']:g})")
+        energies = reweighting.bin_centres(plan["lo"], plan["hi"], plan["n_bins"])
+        log_g = reweighting.wham(counts[:, :plan["n_bins"]], b, energies, **kw)[0]
+        return reweighting.reweight(log_g, energies, betas)
+
+    def histogram_state(self) -> dict:
+        """The section of a checkpoint: the bins and the list, without the histogram finalise took."""
+        if self.hist_plan is None:
+            return {}
+        b, counts = self.histograms()
+        keep = len(b) - (1 if self._hist_final else 0)
+        plan = self.hist_plan
+        return dict(anneal_hist_bins=np.array([plan["lo"], plan["hi"], float(plan["n_bins"])]), anneal_hist_betas=b[:keep],
+                    anneal_hist_counts=counts[:keep])
+
+    def set_histogram_state(self, d) -> None:
+        if self.hist_plan is None or "anneal_hist_bins" not in d:
+            return
+        lo, hi, n_bins = (float(v) for v in d["anneal_hist_bins"])
+        plan = self.hist_plan
+        if (lo, hi, int(n_bins)) != (plan["lo"], plan["hi"], plan["n_bins"]):
+            raise ValueError(f"checkpoint holds annealing histograms with the bins {(lo, hi, int(n_bins))}, this PopulationAnnealing asks "
+                             f"for {(plan['lo'], plan['hi'], plan['n_bins'])}")
+        counts = np.asarray(d["anneal_hist_counts"], dtype=np.uint64).reshape(-1, plan["n_bins"] + 3)
+        self._hist = [(float(b), c.copy()) for b, c in zip(d["anneal_hist_betas"], counts)]
+        self._hist_final = False
 
     @property
     def finished(self) -> bool:

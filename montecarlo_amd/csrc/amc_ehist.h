@@ -1,0 +1,83 @@
+// amc_ehist.h -- energy histograms per group: energy_histogram_kernel<POT>, one pass that bins
+// e = potential_T(x) of every local chain into the row of its group (its rung; ONE group without a ladder), and the plain kernel that
+// zeroes the cells behind a respacing that was taken.  Counts are integers: the same on any grid, in any order, on any split.
+// Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
+#pragma once
+
+#include "amc_blocks.h"
+
+namespace amc {
+
+// The per-block histogram is a STATIC LDS array (launch_by_potential and rtc_launch pass no dynamic LDS): 12288 u32 cells = 48 KiB,
+// beside the 4.4 KiB of math tables 52.4 KiB per block.  That stays below the 64 KiB a workgroup's static LDS may take without special
+// options, and three such blocks fit the 160 KiB of a CU -- the pass runs two per CU (hist_grid: the flush, not the occupancy, sets
+// its grid), so LDS never lowers what is resident.  It is amc_histogram_rungs' threshold too: R = 64 rungs of 189 bins fit.  Beyond
+// it every chain is one 64-bit global atomic, as in rung_histogram_kernel.  A u32 cell holds a block's share of ONE pass, at most
+// ceil(M / gridDim.x) chains: the host refuses a launch whose grid would let that reach 2^32 (amc_energy_histogram_accumulate).
+enum { EHIST_LDS_CELLS = 12288 };
+
+struct EhistArgs {
+    const real_t* x;              // [n_chains] positions of the local shard
+    unsigned long long* counts;   // [n_groups][n_bins + 3] the accumulator
+    int64_t n_chains;
+    double lo, hi, inv_w;         // inv_w = (double)n_bins / (hi - lo), formed by the host
+    int32_t n_groups, n_bins;     // G (the shard starts at a multiple of it); bins
+};
+
+// One chain into its cell: e in T as the bridge sums form it, widened exactly, binned by hist_bin.
+template <int POT>
+__device__ __forceinline__ void ehist_count(const EhistArgs& a, real_t x, const double* s_math, bool lds, unsigned int* s_cells, int base)
+{
+    const int cell = base + hist_bin((double)potential<POT>(x, s_math), a.lo, a.hi, a.inv_w, a.n_bins);
+    if (lds) atomicAdd(&s_cells[cell], 1u);
+    else atomicAdd(&a.counts[cell], 1ull);
+}
+
+// Memory-bound, one read of x.  Work items as in the sums by group: thread id = l0 G + r, a thread keeps its group -- the base of its
+// row is formed once, no modulo per chain -- and advances by (threads / G) ladders per trip, so neighbouring lanes read neighbouring
+// chains; four loads in flight per lane (one load per trip leaves the pass waiting for latency: histogram_kernel).  Float32 state
+// halves the bytes.  The grid is hist_grid's: the flush ends every block with atomics on the same few addresses.
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void energy_histogram_kernel(const EhistArgs a)
+{
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
+    __shared__ unsigned int s_cells[EHIST_LDS_CELLS];
+    const int row = a.n_bins + 3, cells = a.n_groups * row;
+    const bool lds = cells <= EHIST_LDS_CELLS;
+    if (lds)
+        for (int i = threadIdx.x; i < cells; i += AMC_BLOCK) s_cells[i] = 0u;
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier: the cells are cleared too)
+
+    const uint32_t tid = blockIdx.x * AMC_BLOCK + threadIdx.x;      // (a grid of hist_grid: far below 2^32 threads)
+    const uint32_t ladders_per_trip = (gridDim.x * AMC_BLOCK) / (uint32_t)a.n_groups;
+    const uint32_t l0 = tid / (uint32_t)a.n_groups;
+    if (l0 < ladders_per_trip) {
+        const int base = (int)(tid - l0 * (uint32_t)a.n_groups) * row;
+        const int64_t step = (int64_t)ladders_per_trip * a.n_groups;      // chains per trip
+        int64_t i = tid;                                                  // chain l0 G + r
+        for (; i + 3 * step < a.n_chains; i += 4 * step) {
+            const real_t x0 = a.x[i], x1 = a.x[i + step], x2 = a.x[i + 2 * step], x3 = a.x[i + 3 * step];
+            ehist_count<POT>(a, x0, s_math, lds, s_cells, base);
+            ehist_count<POT>(a, x1, s_math, lds, s_cells, base);
+            ehist_count<POT>(a, x2, s_math, lds, s_cells, base);
+            ehist_count<POT>(a, x3, s_math, lds, s_cells, base);
+        }
+        for (; i < a.n_chains; i += step) ehist_count<POT>(a, a.x[i], s_math, lds, s_cells, base);
+    }
+    if (lds) {
+        __syncthreads();
+        flush_cells(s_cells, a.counts, cells);
+    }
+}
+
+// Behind ladder_respace_kernel on the stream: a respacing that was taken zeroes the cells, as it zeroes the bridge records -- counts
+// taken at other beta belong to another ladder.  Any other status leaves them.
+#if AMC_PLAIN_KERNELS
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void ehist_respaced_kernel(unsigned long long* counts, int cells, const unsigned long long* rec)
+{
+    if (rec[RESPACE_STATUS] != 0ull) return;
+    for (int i = blockIdx.x * AMC_BLOCK + threadIdx.x; i < cells; i += gridDim.x * AMC_BLOCK) counts[i] = 0ull;
+}
+#endif
+
+}  // namespace amc

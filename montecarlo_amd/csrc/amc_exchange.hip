@@ -88,6 +88,7 @@ static int ladder_reset(amc_handle* h)
     if (h->lad.d_respace) AMC_HIP(hipMemsetAsync(h->lad.d_respace, 0, RESPACE_BYTES, h->stream));
     AMC_TRY(tune_reset(h, true));
     AMC_TRY(bridge_clear(h));
+    AMC_TRY(ehist_clear(h));        // (the energy histograms' groups are the rungs)
     corr_forget(h);                 // (no ladder state, but its groups are the rungs: the chains' slots mean something else now)
     h->blocks.n_blocks = 0;         // (the jackknife partition counts ladders: another R has other ladders)
     h->blocks.chunk = 0;
@@ -734,6 +735,7 @@ int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const 
     a.counts_given = counts ? 1 : 0;
     hipLaunchKernelGGL(amc::ladder_respace_kernel, dim3(1), dim3(64), 0, h->stream, a, given);
     AMC_HIP(hipGetLastError());
+    AMC_TRY(ehist_respaced(h));         // the energy histograms' cells go with status 0, as the bridge records do
     hipLaunchKernelGGL(amc::ladder_retile_kernel, dim3(grid_for(h, h->M)), dim3(AMC_BLOCK), 0, h->stream, (void*)h->d_beta, a.f32, h->lad.d_lab, h->M / R, R,
                        (const unsigned long long*)h->lad.d_respace);
     AMC_HIP(hipGetLastError());

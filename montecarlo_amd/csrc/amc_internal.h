@@ -13,6 +13,7 @@
 //                       amc_set_anneal_families .. amc_upload_families; amc_anneal_next_beta)
 //   amc_corr.hip        time correlation from one time origin (amc_corr_mark .. amc_corr_clear; per jackknife block: amc_corr_fetch_blocks;
 //                       the partition itself, amc_set_blocks, and amc_bridge_fetch_blocks are with the bridge sums in amc_exchange.hip)
+//   amc_ehist.hip       energy histograms per group (amc_energy_histogram_accumulate / _fetch, amc_set_energy_histogram)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -272,6 +273,19 @@ static inline void blocks_release(BlocksState& s)
     (void)hipFree(s.d_corr_blk);
 }
 
+// Energy histograms per group (amc_ehist.hip): the accumulator is allocated by the first
+// amc_energy_histogram_accumulate after a reset -- a handle that never accumulates has none.  It stands exactly while d_ehist != nullptr.
+struct EhistState {
+    unsigned long long* d_ehist = nullptr;      // [groups][n_bins + 3] counts; the bins are fixed while it stands
+    int n_bins = 0;
+    int groups = 0;                             // G when it was begun (amc_set_ladder clears it, so it is the handle's G while it stands)
+    double lo = 0.0, hi = 0.0;
+};
+static inline void ehist_release(EhistState& s)
+{
+    (void)hipFree(s.d_ehist);
+}
+
 struct amc_handle {
     AmcKnobs knobs;             // the environment's knobs as amc_create found them
     int device = 0;
@@ -289,6 +303,7 @@ struct amc_handle {
     LadderState lad;            // the temperature ladder and what hangs on it (amc_exchange.hip)
     AnnealState ann;            // population annealing (amc_anneal.hip)
     CorrState corr;             // time correlation (amc_corr.hip)
+    EhistState ehist;           // energy histograms per group (amc_ehist.hip)
     BlocksState blocks;         // jackknife blocks of the bridge sums and the time correlation (amc_exchange.hip, amc_corr.hip)
     double* d_x = nullptr;
     double* d_beta = nullptr;
@@ -434,6 +449,8 @@ AMC_INTERNAL int copy_to_host_sync(amc_handle* h, void* dst, const void* d_src, 
 AMC_INTERNAL int copy_to_device_sync(amc_handle* h, void* d_dst, const void* src, size_t bytes);
 // *p allocated at its first use and zeroed on the stream then; nothing when it exists
 AMC_INTERNAL int zeroed_words(amc_handle* h, unsigned long long** p, size_t bytes);
+AMC_INTERNAL bool hist_args_ok(const char* who, double lo, double hi, int n_bins);         // what every histogram entry asks of its bins
+AMC_INTERNAL int hist_grid(const amc_handle* h);                                          // the grid of every histogram pass
 AMC_INTERNAL int log_form(const amc_handle* h);                                           // amc_counters.hip
 AMC_INTERNAL int log_room(amc_handle* h, int* rows);
 AMC_INTERNAL int fold_log(amc_handle* h, bool with_ratio = false, int* ratio_rows = nullptr, amc::xs_word* ratio_dst = nullptr);
@@ -482,6 +499,10 @@ struct RungPass {
 AMC_INTERNAL int rung_pass_plan(amc_handle* h, int n_cols, bool blocked, RungPass* p);      // ... planned, and room made for its rows
 // a kind-R record into words 0 .. 4 of an XS_ROW_R row, or a refusal naming who / where (amc_exchange.hip; amc_set_bridge*, amc_set_corr*)
 AMC_INTERNAL int r_row_from_record(const char* who, const char* where, const double* rec, amc::xs_word* row);
+// the energy histograms (amc_ehist.hip): the accumulator freed, no bins fixed (amc_set_ladder; waits for what still writes it); its cells
+// zeroed on the stream when the respacing just queued is taken (amc_respace_ladder).  Nothing happens on a handle without one.
+AMC_INTERNAL int ehist_clear(amc_handle* h);
+AMC_INTERNAL int ehist_respaced(amc_handle* h);
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };

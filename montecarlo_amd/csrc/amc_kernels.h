@@ -26,6 +26,7 @@
 //   amc_anneal_search.h  population annealing: the next beta from a target on the effective-sample fraction (energies, sums, decision)
 //   amc_corr.h         time correlation from one time origin: the sums of O, O^2, a O by group, one slot per lag
 //   amc_blocks.h       jackknife blocks: the traversal's index arithmetic, the bridge sums and the time correlation per block of ladders
+//   amc_ehist.h        energy histograms per group: energy_histogram_kernel, the cells zeroed behind a respacing
 #pragma once
 
 #include "amc_model.h"
@@ -41,3 +42,4 @@
 #include "amc_anneal_search.h"
 #include "amc_corr.h"
 #include "amc_blocks.h"
+#include "amc_ehist.h"

@@ -84,11 +84,20 @@ static int positions_f64(amc_handle* h, const double** out)
 }
 
 // What every histogram entry asks of its bins; the message is left for amc_last_error().
-static bool hist_args_ok(const char* who, double lo, double hi, int n_bins)
+bool hist_args_ok(const char* who, double lo, double hi, int n_bins)
 {
     if (n_bins >= 1 && n_bins <= 8192 && hi > lo && std::isfinite(lo) && std::isfinite(hi)) return true;
     fail(AMC_ERR_BAD_ARG, "%s: need 1 <= n_bins <= 8192 and finite lo < hi", who);
     return false;
+}
+
+// Every block ends with one 64-bit atomic per non-empty bin on the SAME few hundred addresses, and those serialise (~13 ns
+// each per address): a full grid of 2048 blocks spends 27 us there.  Two blocks per CU keep enough loads in flight and the
+// flush short (1e7 chains, 200 bins: 53.1 us with 2048 blocks, 32.2 with 1024, 23.4 with 512, 27.0 with 256, 43.5 with 128).
+int hist_grid(const amc_handle* h)
+{
+    const int g = 2 * h->n_cu;
+    return g < h->red_blocks ? g : h->red_blocks;
 }
 
 // A histogram launch into a scratch buffer of `cells` cleared counters, copied to the caller's `counts`: launch(d_pos, d_counts) queues
@@ -201,15 +210,6 @@ int amc_download_state(amc_handle* h, double* x, double* e)
         }
     }
     return AMC_OK;
-}
-
-// Every block ends with one 64-bit atomic per non-empty bin on the SAME few hundred addresses, and those serialise (~13 ns
-// each per address): a full grid of 2048 blocks spends 27 us there.  Two blocks per CU keep enough loads in flight and the
-// flush short (1e7 chains, 200 bins: 53.1 us with 2048 blocks, 32.2 with 1024, 23.4 with 512, 27.0 with 256, 43.5 with 128).
-static int hist_grid(const amc_handle* h)
-{
-    const int g = 2 * h->n_cu;
-    return g < h->red_blocks ? g : h->red_blocks;
 }
 
 int amc_histogram(amc_handle* h, double lo, double hi, int n_bins, uint64_t* counts)

@@ -1,0 +1,146 @@
+"""``EnergyHistogram``: per rung a histogram of the chains' energies, accumulated on the device, and the curve between the
+simulated temperatures from it.
+
+An extension over the reference, like ``ReplicaExchange`` and ``Autocorrelation``.  The engine bins e = potential(x) of every chain
+into the row of its group -- the rungs of the ladder, ONE group without a ladder -- in one memory-bound pass per scheduled call
+(include/amc.h amc_energy_histogram_accumulate); the counts are integers, the same on any grid, in any
+snapshot order and on any split into shards.  Multiple-histogram reweighting (``reweighting.wham``) turns the rows into the density
+of states log g(E), the free energy per rung and <e>(beta), C(beta), log Z(beta) at any beta between the rungs; with one group it
+is single-histogram reweighting around the shared beta.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import reweighting, sharding
+from ._capi import AMC_EHIST_MAX_BINS
+from .metropolis import Metropolis
+from .simulation import AriannaAlgorithm, Simulation, _calls
+
+_CELLS = ("below lo", "at or above hi", "NaN")
+
+
+class EnergyHistogram(AriannaAlgorithm):
+    """EnergyHistogram(chains; dependencies=(Metropolis,), scheduler=..., lo=..., hi=..., n_bins=..., max_outside=0.0): one snapshot of
+    the energy histograms per scheduled time, on the Metropolis' engine.  It observes only: listed behind its Metropolis (and its
+    ReplicaExchange), a time step at which all are due is [sweep; exchange; snapshot].
+
+    ``counts()`` are the counts of ALL ranks, ``reweight(betas)`` the curve.  ``max_outside``: the largest share of a row that may lie
+    in one of the three cells outside the bins (below lo, at or above hi, NaN) before ``reweight`` / ``density_of_states`` /
+    ``free_energies`` refuse: what lies outside is missing from the reweighted sums, so the default tolerates nothing."""
+
+    def __init__(self, chains, dependencies=None, lo=None, hi=None, n_bins=None, max_outside=0.0, path=None, **extras):
+        assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
+        self.metropolis: Metropolis = dependencies[0]
+        if lo is None or hi is None or n_bins is None:
+            raise ValueError("EnergyHistogram: lo, hi and n_bins are required")
+        if int(n_bins) != n_bins or not 1 <= int(n_bins) <= AMC_EHIST_MAX_BINS or not (np.isfinite(lo) and np.isfinite(hi) and float(lo) < float(hi)):
+            raise ValueError(f"EnergyHistogram: need an integer 1 <= n_bins <= {AMC_EHIST_MAX_BINS} and finite lo < hi, got lo = {lo!r}, hi = {hi!r}, n_bins = {n_bins!r}")
+        if not 0.0 <= float(max_outside) <= 1.0:
+            raise ValueError(f"EnergyHistogram: max_outside = {max_outside!r} must lie in [0, 1]")
+        if not hasattr(self.metropolis.engine, "energy_histogram_accumulate"):
+            raise ValueError("EnergyHistogram: this engine has no energy histograms (streams > 1 is not supported)")
+        self.chains = chains
+        self.lo, self.hi, self.n_bins, self.max_outside = float(lo), float(hi), int(n_bins), float(max_outside)
+        self.metropolis.energy_histogram = self     # (storage.checkpoint: the accumulator is state)
+
+    # -- scheduling -----------------------------------------------------------------------------------------------------------------
+    def initialise(self, simulation: Simulation) -> None:
+        from .annealing import PopulationAnnealing
+        if any(isinstance(a, PopulationAnnealing) for a in simulation.algorithms):
+            raise ValueError("EnergyHistogram beside a PopulationAnnealing: a histogram belongs to one beta, and annealing moves it; "
+                             "PopulationAnnealing(..., energy_histogram=dict(lo=..., hi=..., n_bins=...)) keeps one histogram per temperature")
+
+    def make_step(self, simulation: Simulation) -> None:
+        self.metropolis.engine.energy_histogram_accumulate(self.lo, self.hi, self.n_bins)
+
+    def restart(self) -> None:
+        """Drop what has been accumulated (fetch with reset); the next scheduled call begins anew."""
+        self.metropolis.engine.energy_histogram_fetch(reset=True)
+
+    # -- results --------------------------------------------------------------------------------------------------------------------
+    def _groups(self) -> int:
+        return max(int(self.metropolis.n_rungs), 1)
+
+    def _local(self):
+        """(counts[G, n_bins + 3], n_snapshots) of this shard; zeros while nothing has been accumulated."""
+        counts, n_snap, (lo, hi, n_bins) = self.metropolis.engine.energy_histogram_fetch(reset=False)
+        if n_bins == 0:
+            return np.zeros((self._groups(), self.n_bins + 3), dtype=np.uint64), 0
+        if (lo, hi, n_bins) != (self.lo, self.hi, self.n_bins):
+            raise ValueError(f"EnergyHistogram: the engine's accumulator has the bins {(lo, hi, n_bins)}, this algorithm asks for "
+                             f"{(self.lo, self.hi, self.n_bins)}")
+        return counts, n_snap
+
+    def counts(self) -> np.ndarray:
+        """counts[G, n_bins + 3] (uint64) of ALL ranks: the bins, then below lo, at or above hi, NaN.  Summed exactly: a 64-bit count
+        travels as two halves below 2^32, so the Float64 sum over the ranks rounds nothing.  The host waits for the queued
+        snapshots."""
+        local = self._local()[0]
+        if self.metropolis.world_size <= 1:
+            return local
+        halves = np.concatenate([(local & np.uint64(0xFFFFFFFF)).ravel(), (local >> np.uint64(32)).ravel()]).astype(np.float64)
+        total = sharding.allreduce_sum(halves, self.metropolis.engine)
+        lo_half, hi_half = total[:local.size].astype(np.uint64), total[local.size:].astype(np.uint64)
+        return (lo_half + (hi_half << np.uint64(32))).reshape(local.shape)
+
+    @property
+    def n_snapshots(self) -> int:
+        """Snapshots in the accumulator (every rank takes the same number)."""
+        return self._local()[1]
+
+    def betas(self) -> np.ndarray:
+        """beta per group as it stands now: the ladder on the device (``ReplicaExchange.betas()``), the shared beta without one."""
+        eng = self.metropolis.engine
+        if self.metropolis.n_rungs:
+            return np.asarray(eng.ladder(), dtype=np.float64)
+        return np.array([float(eng.beta)], dtype=np.float64)
+
+    def energies(self) -> np.ndarray:
+        return reweighting.bin_centres(self.lo, self.hi, self.n_bins)
+
+    def _checked_counts(self) -> np.ndarray:
+        counts = self.counts()
+        if not counts[:, :self.n_bins].sum():
+            raise ValueError("EnergyHistogram: nothing has been accumulated yet")
+        share = reweighting.outside_share(counts)
+        bad = np.argwhere(share > self.max_outside)
+        if bad.size:
+            g, c = int(bad[0][0]), int(bad[0][1])
+            raise ValueError(f"EnergyHistogram: rung {g} has a share of {share[g, c]:.3e} of its samples in the cell '{_CELLS[c]}' "
+                             f"(max_outside = {self.max_outside:g}): widen [lo, hi) = [{self.lo:g}, {self.hi:g})")
+        return counts
+
+    def _wham(self, tol=1e-12, max_iter=100000):
+        counts = self._checked_counts()
+        return reweighting.wham(counts[:, :self.n_bins], self.betas(), self.energies(), tol=tol, max_iter=max_iter)
+
+    def density_of_states(self, **kw):
+        """(energies[n_bins], log_g[n_bins]): the bin centres and the WHAM density of states (-inf where no rung has a count), on the
+        normalisation log Z(beta_0) = 0."""
+        return self.energies(), self._wham(**kw)[0]
+
+    def free_energies(self, **kw) -> np.ndarray:
+        """f_r = -log Z(beta_r) + log Z(beta_0) per rung (f_0 = 0)."""
+        return self._wham(**kw)[1]
+
+    def reweight(self, betas, **kw):
+        """(log Z, <e>, <e^2>, C) at every beta of ``betas`` (reweighting.reweight), from the ladder as it stands at fetch time."""
+        return reweighting.reweight(self._wham(**kw)[0], self.energies(), betas)
+
+    # -- checkpoints (storage.py's section) -------------------------------------------------------------------------------------------
+    def state(self) -> dict:
+        counts, n_snap = self._local()
+        return dict(ehist_bins=np.array([self.lo, self.hi, float(self.n_bins)], dtype=np.float64), ehist_counts=counts,
+                    ehist_snapshots=np.uint64(n_snap))
+
+    def set_state(self, d) -> None:
+        lo, hi, n_bins = (float(v) for v in d["ehist_bins"])
+        if (lo, hi, int(n_bins)) != (self.lo, self.hi, self.n_bins):
+            raise ValueError(f"checkpoint holds energy histograms with the bins {(lo, hi, int(n_bins))}, this EnergyHistogram asks for "
+                             f"{(self.lo, self.hi, self.n_bins)}")
+        self.metropolis.engine.set_energy_histogram(self.lo, self.hi, self.n_bins, np.asarray(d["ehist_counts"], dtype=np.uint64),
+                                                    int(d["ehist_snapshots"]))
+
+    def write_algorithm(self, io, scheduler) -> None:
+        io.write(f"\tEnergyHistogram\n\t\tCalls: {_calls(scheduler)}\n\t\tBins: {self.n_bins} in [{self.lo}, {self.hi})\n")

@@ -287,6 +287,7 @@ def _write_annealing(met, eng, d, est) -> None:
         pa._records = list(d["anneal_records"][:-AMC_ANNEAL_MAX_RECORDS])
         if pa.families:
             d["families"] = eng.download_families()
+        d.update(pa.histogram_state())              # energy_histogram=...: a histogram per temperature so far (no field otherwise)
 
 def _read_annealing(met, eng, d, est) -> None:
     if "anneal_beta" in d:                          # population annealing: the resumed run anneals on to the same bits
@@ -296,6 +297,7 @@ def _read_annealing(met, eng, d, est) -> None:
         eng.set_anneal_records(rec[-AMC_ANNEAL_MAX_RECORDS:])
         if met.annealing is not None:
             met.annealing._records = list(rec[:-AMC_ANNEAL_MAX_RECORDS])
+            met.annealing.set_histogram_state(d)
         if "families" in d:
             eng.set_anneal_families(True)
             eng.upload_families(d["families"])
@@ -319,6 +321,16 @@ def _write_correlation_blocks(met, eng, d, est) -> None:
 def _read_correlation_blocks(met, eng, d, est) -> None:
     if met.autocorrelation is not None:
         met.autocorrelation.set_state_blocks(d)
+
+
+def _write_energy_histogram(met, eng, d, est) -> None:
+    eh = met.energy_histogram
+    if eh is not None:                              # energy histograms: the bins, the counts and the snapshot count are state (no field otherwise)
+        d.update(eh.state())
+
+def _read_energy_histogram(met, eng, d, est) -> None:
+    if "ehist_counts" in d and met.energy_histogram is not None:      # behind the ladder: set_ladder clears the engine's accumulator
+        met.energy_histogram.set_state(d)
 
 
 def _write_estimator(met, eng, d, est) -> None:
@@ -345,7 +357,8 @@ _SECTIONS = ((_write_core, _read_core), (_write_counters, _read_counters), (_wri
              (_write_ladder, _read_ladder), (_write_tracking, _read_tracking), (_write_window, _read_window),
              (_write_bridge, _read_bridge), (_write_bridge_blocks, _read_bridge_blocks), (_write_respacing, _read_respacing),
              (_write_annealing, _read_annealing), (_write_correlation, _read_correlation),
-             (_write_correlation_blocks, _read_correlation_blocks), (_write_estimator, _read_estimator))
+             (_write_correlation_blocks, _read_correlation_blocks), (_write_energy_histogram, _read_energy_histogram),
+             (_write_estimator, _read_estimator))
 
 
 def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:
