@@ -195,8 +195,9 @@ __device__ __forceinline__ void pg_sample_script(real_t& x, real_t beta, double 
 // x = (x + delta) + (-delta) in the reference's operations, and (b) four SUMMANDS of GradientData (j, grad j, grad logq, g:
 // gradients.jl:104-108), which the reference folds with `+` over all chains in whatever order its reducer takes (foldxl /
 // foldxt, estimator.jl:94,113).  The summands follow the ARITHMETIC SPEC of DESIGN.md section 3.6b, which the oracle restates
-// operation for operation (its spec-form sample) next to the reference-ordered form (a few ulp apart,
-// test_pg_sample_summands_within_ulps): two parts of the reference's rounding sequence that cost 19 of its 46 f64 operations
+// operation for operation (its spec-form sample) next to the reference-ordered form; test_gpu_pg_exact.py pins this form to
+// that twin bit for bit and, like test_pg_exact_host.py, to the exact value (<= 2 ulp of j; the reference-ordered form is the
+// looser of the two): two parts of the reference's rounding sequence that cost 19 of its 46 f64 operations
 // per sample are replaced --
 //   * alpha = min(1, exp((dlogp + logq_b) - logq_f)) with logq_b == logq_f bit for bit: the detour through logq moves
 //     the argument by at most 2^-53 (2|dlogp| + |logq|) -- alpha = exp(min(dlogp, 0)), and log_proposal_density itself (a

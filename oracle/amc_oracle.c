@@ -1402,8 +1402,10 @@ static void pgmc_sample_f32(particle_t *p, move_t *m, double sigma, int pot, dou
  * (amc_kernels.h pg_sample): alpha = exp(min(dlogp, 0)) without the detour through logq_b - logq_f (which cancels bit
  * for bit), and d logq / d sigma = d^2 c3 - 1/sigma as one fma chain with c3 = dden / den^2 split hi + lo.  For the fold
  * to be bit-reproducible against the engine the oracle restates THAT arithmetic here, operation for operation;
- * pgmc_sample above is the reference-ordered form (gradients.jl:93-109), and the tests pin the two within a few ulp per
- * sample (test_pg_sample_summands_within_ulps).  The position update is the reference's in both. */
+ * pgmc_sample above is the reference-ordered form (gradients.jl:93-109).  tests/test_pg_exact_host.py pins BOTH to the exact
+ * value per sample (this form within 2 / 4 / 2 / 4 units of j, grad j, d logq / d sigma, g; the reference-ordered one within
+ * (2 + |dlogp| + |logq|) 2^-52 relative in j), tests/test_gpu_pg_exact.py pins the kernels to this form bit for bit.  The
+ * position update is the reference's in both. */
 typedef struct { double sigma, c3hi, c3lo, c1; } spec_consts_t;
 static spec_consts_t spec_consts(double sigma)
 {
@@ -1473,6 +1475,24 @@ void amo_pg_summands_reference(int pot, double beta, double sigma, double z, dou
     particle_t p = { *x, beta, amo_potential(pot, *x) };
     move_t m = { 0.0, 0, 0 };
     pgmc_sample(&p, &m, sigma, pot, z, out);
+    *x = p.x;
+}
+/* the same two with Float32 state: *x holds a Float32 value before and after; beta is converted as the chain's field is */
+void amo_pg_summands_spec_f32(int pot, double beta, double sigma, double z, double *x, double out[4])
+{
+    particle_t p = { *x, beta, (double)amo_potential_f32(pot, (float)*x) };
+    move_t m = { 0.0, 0, 0 };
+    spec_consts_t k = spec_consts(sigma);
+    double j, d;
+    pgmc_sample_spec_f32(&p, &m, &k, pot, z, &j, &d);
+    out[0] = j; out[1] = j * d; out[2] = d; out[3] = d * d;
+    *x = p.x;
+}
+void amo_pg_summands_reference_f32(int pot, double beta, double sigma, double z, double *x, double out[4])
+{
+    particle_t p = { *x, beta, (double)amo_potential_f32(pot, (float)*x) };
+    move_t m = { 0.0, 0, 0 };
+    pgmc_sample_f32(&p, &m, sigma, pot, z, out);
     *x = p.x;
 }
 

@@ -134,6 +134,8 @@ void   amo_pg_estimate_plain(amo_sim *s, int n_learn, const int *learn_ids, int 
  *  and in the reference's operation order (gradients.jl:93-109); *x is updated like the chain's */
 void   amo_pg_summands_spec(int pot, double beta, double sigma, double z, double *x, double out[4]);
 void   amo_pg_summands_reference(int pot, double beta, double sigma, double z, double *x, double out[4]);
+void   amo_pg_summands_spec_f32(int pot, double beta, double sigma, double z, double *x, double out[4]);      /* Float32 state */
+void   amo_pg_summands_reference_f32(int pot, double beta, double sigma, double z, double *x, double out[4]);
 
 /* ---- reproducible sums: the definition applied to explicit operands, records of 12 doubles (include/amc.h) ---- */
 void   amo_xsum_q(const double *v, int64_t n, int e, double *rec);

@@ -98,6 +98,8 @@ def load() -> C.CDLL:
         "amo_pg_estimate_plain": (None, [S, C.c_int, C.POINTER(C.c_int), C.c_int, dp]),
         "amo_pg_summands_spec": (None, [C.c_int, C.c_double, C.c_double, C.c_double, dp, dp]),
         "amo_pg_summands_reference": (None, [C.c_int, C.c_double, C.c_double, C.c_double, dp, dp]),
+        "amo_pg_summands_spec_f32": (None, [C.c_int, C.c_double, C.c_double, C.c_double, dp, dp]),
+        "amo_pg_summands_reference_f32": (None, [C.c_int, C.c_double, C.c_double, C.c_double, dp, dp]),
         "amo_xsum_q": (None, [dp, C.c_int64, C.c_int, dp]),
         "amo_xsum_q_product": (None, [dp, dp, C.c_int64, C.c_int, dp]),
         "amo_xsum_r": (None, [dp, C.c_int64, dp]),
@@ -174,11 +176,12 @@ def gd_exponents(sigma):
     return list(e)
 
 
-def pg_summands(pot, beta, sigma, z, x, form="spec"):
-    """One estimator sample of the Gaussian policy: (summands[4], new x); form 'spec'  or 'reference'."""
+def pg_summands(pot, beta, sigma, z, x, form="spec", dtype="f64"):
+    """One estimator sample of the Gaussian policy: (summands[4], new x); form 'spec' (DESIGN.md 3.6b) or 'reference';
+    dtype 'f32': Float32 state (x holds a Float32 value)."""
     xx = np.array([float(x)])
     out = np.zeros(4)
-    fn = load().amo_pg_summands_spec if form == "spec" else load().amo_pg_summands_reference
+    fn = getattr(load(), "amo_pg_summands_" + ("spec" if form == "spec" else "reference") + ("_f32" if dtype == "f32" else ""))
     fn(POTENTIALS[pot] if isinstance(pot, str) else int(pot), float(beta), float(sigma), float(z), _dptr(xx), _dptr(out))
     return out, float(xx[0])
 
