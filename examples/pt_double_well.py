@@ -7,7 +7,7 @@ down.  Every chain starts in the right well; the script runs the same schedule w
 rung, the fraction of chains left of the barrier, the mean energy and the swap acceptance of every gap.
 
     python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track] [--rung-sigma] [--adapt flow|acceptance]
-                                          [--tune-sigma TARGET] [--free-energy [--blocks 32]] [--reweight N]
+                                          [--tune-sigma TARGET] [--free-energy] [--reweight N] [--blocks 32]
 
 --track also follows every replica through the swaps and prints, at the end, the flow fraction f(r) -- of the replicas at rung r that
 have been to an end of the ladder, the share that came from the hot end (rung 0) last -- and the round trips per ladder.
@@ -28,7 +28,8 @@ per rung over the window since the last tuning: the second half, under the final
 
 --free-energy accumulates the bridge sums over the second half of the run and prints log(Z_(r+1) / Z_r) by three estimators beside a
 quadrature, and the heat capacity per rung.  With --blocks B the sums are kept per block of ladders (ReplicaExchange(..., blocks=B)) and
-every estimate comes with the standard error of a delete-one-block jackknife over the B blocks, value +- se.
+every estimate comes with the standard error of a delete-one-block jackknife over the B blocks, value +- se; with --reweight N the
+energy histograms are kept per block too (EnergyHistogram(..., blocks=B)) and every point of the curve is printed +- se.
 
 --reweight N accumulates an energy histogram per rung on the device over the second half of the run (EnergyHistogram, 100 snapshots)
 and prints <e>(beta), C(beta) and log(Z(beta) / Z(beta_0)) by multiple-histogram reweighting (WHAM) on an N-point grid between the end
@@ -116,7 +117,7 @@ def one_run(args, path, exchange: bool):
         if args.reweight:                              # measure over the second half of the run, behind every respacing and tuning
             half = args.steps // 2
             every = max(1, (args.steps - half) // 100)
-            algorithm_list.append(dict(algorithm=ma.EnergyHistogram, dependencies=(ma.Metropolis,),
+            algorithm_list.append(dict(algorithm=ma.EnergyHistogram, dependencies=(ma.Metropolis,), blocks=args.blocks,
                                        scheduler=list(range(half + every, args.steps + 1, every)), **HIST))
     algorithm_list.append(dict(algorithm=ma.StoreCallbacks, callbacks=tuple(callbacks),
                                scheduler=ma.build_schedule(args.steps, 0, max(1, args.steps // 10))))
@@ -150,10 +151,11 @@ def main(argv=None):
                     help="accumulate an energy histogram per rung over the second half of the run; print <e>, C and log Z on an N-point grid "
                          "of beta between the end rungs by multiple-histogram reweighting, beside the quadrature")
     ap.add_argument("--blocks", type=int, default=None, metavar="B",
-                    help="with --free-energy: keep the bridge sums per block of ladders and print every estimate +- its jackknife standard error")
+                    help="with --free-energy and / or --reweight: keep the bridge sums and the energy histograms per block of ladders and print "
+                         "every estimate +- its jackknife standard error")
     args = ap.parse_args(argv)
-    if args.blocks is not None and not args.free_energy:
-        ap.error("--blocks needs --free-energy")
+    if args.blocks is not None and not (args.free_energy or args.reweight):
+        ap.error("--blocks needs --free-energy or --reweight")
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
     _, left_plain, energy_plain, _, _ = one_run(args, os.path.join(path, "plain"), False)
@@ -200,13 +202,22 @@ def main(argv=None):
         eh = next(a for a in sim.algorithms if isinstance(a, ma.EnergyHistogram))
         ladder = eh.betas()
         grid = np.exp(np.linspace(np.log(ladder[0]), np.log(ladder[-1]), max(2, args.reweight)))
-        log_z, m1, _, c = eh.reweight(grid)
         q_log_z, q_m1, q_c = curve_by_quadrature(grid)
         q_log_z0 = curve_by_quadrature(ladder[:1])[0][0]
-        print(f"reweighted curve, {eh.n_snapshots} snapshots of {args.ladders} ladders, {HIST['n_bins']} bins of [{HIST['lo']:g}, {HIST['hi']:g}): WHAM | quadrature")
-        print("     beta       <e>               C                 log(Z / Z_0)")
-        for b, e1, e2, c1, c2, z1, z2 in zip(grid, m1, q_m1, c, q_c, log_z, q_log_z - q_log_z0):
-            print(f"  {b:7.4f}   {e1:7.4f} | {e2:7.4f}   {c1:7.4f} | {c2:7.4f}   {z1:8.4f} | {z2:8.4f}")
+        head = f"reweighted curve, {eh.n_snapshots} snapshots of {args.ladders} ladders, {HIST['n_bins']} bins of [{HIST['lo']:g}, {HIST['hi']:g})"
+        if args.blocks:                                 # every point of the curve +- the jackknife over the blocks of ladders
+            (log_z, z_se), (m1, m1_se), _, (c, c_se) = eh.reweight(grid, error=True)
+            print(f"{head}: WHAM +- jackknife se over {args.blocks} blocks | quadrature")
+            print("     beta       <e>                           C                             log(Z / Z_0)")
+            for i, b in enumerate(grid):
+                print(f"  {b:7.4f}   {m1[i]:7.4f} +- {m1_se[i]:6.4f} | {q_m1[i]:7.4f}   {c[i]:7.4f} +- {c_se[i]:6.4f} | {q_c[i]:7.4f}   "
+                      f"{log_z[i]:8.4f} +- {z_se[i]:6.4f} | {q_log_z[i] - q_log_z0:8.4f}")
+        else:
+            log_z, m1, _, c = eh.reweight(grid)
+            print(f"{head}: WHAM | quadrature")
+            print("     beta       <e>               C                 log(Z / Z_0)")
+            for b, e1, e2, c1, c2, z1, z2 in zip(grid, m1, q_m1, c, q_c, log_z, q_log_z - q_log_z0):
+                print(f"  {b:7.4f}   {e1:7.4f} | {e2:7.4f}   {c1:7.4f} | {c2:7.4f}   {z1:8.4f} | {z2:8.4f}")
         if args.free_energy:
             rx = sim.algorithms[1]
             print("log(Z_r / Z_0), WHAM (-f_r)   : " + "  ".join(f"{v:7.4f}" for v in -eh.free_energies()))

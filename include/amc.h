@@ -767,7 +767,7 @@ int  amc_corr_clear(amc_handle *h);
  * stream order, exactly as it zeroes the bridge records -- counts taken at other beta belong to another ladder --; the bins stay
  * fixed, and one that is not taken leaves the cells alone.
  * KEPT by sweeps, exchange steps, reductions, the estimator, tuning, amc_upload_state, amc_init_uniform, amc_set_blocks (a histogram
- * is not kept per jackknife block), and -- on purpose -- by amc_anneal and amc_set_beta: a histogram belongs to ONE beta per group,
+ * kept per jackknife block is folded into a plain one, see "Energy histograms per jackknife block" below), and -- on purpose -- by amc_anneal and amc_set_beta: a histogram belongs to ONE beta per group,
  * so the caller fetches with reset before beta moves (the Python layer does); the engine cannot know whether the caller is done.
  * None of the three entries touches a step index, the step log, a counter, reductions in flight, labels, widths, the bridge sums or
  * the mark of the time correlation.  A refused call leaves the handle as it was. */
@@ -816,6 +816,41 @@ int  amc_corr_fetch_blocks(amc_handle *h, double *records, uint64_t *steps, int 
 int  amc_set_bridge_blocks(amc_handle *h, const double *records, int n_blocks, uint64_t n_snapshots);
 int  amc_set_corr_blocks(amc_handle *h, int observable, const double *origin, const double *records, const uint64_t *steps, int n_blocks,
                          int n_samples);
+
+/* Energy histograms per jackknife block (DESIGN.md section 3.17 "Per block"): the energy histograms with a set of rows per block of
+ * the partition (amc_set_blocks), so that a delete-one-block jackknife gives an error bar for anything formed from the counts -- the
+ * reweighted curve log Z(beta), <e>(beta), C(beta), log g(E), f_r.  The form is opt-in: amc_energy_histogram_accumulate, _fetch and
+ * amc_set_energy_histogram do what they always did, and a handle that never calls the entries below allocates and launches what it
+ * always did, with or without a partition.
+ * amc_energy_histogram_accumulate_blocks queues one pass, as amc_energy_histogram_accumulate does, in which chain i of local ladder l
+ * is counted by the same binning rule into the row of (b(l), group): counts[(b * G + g) * (n_bins + 3) + cell].  It needs a partition
+ * (AMC_ERR_STATE without one).  The first call after a reset allocates and zeroes B * G * (n_bins + 3) 64-bit counters, fixes
+ * (lo, hi, n_bins) and the accumulator's FORM, "blocked under (B, C)"; it waits for the stream at that allocation, as the other
+ * blocked accumulators do, and is stream-ordered otherwise.  More than AMC_EHIST_BLK_MAX_CELLS = 2^22 cells (32 MiB) are
+ * AMC_ERR_BAD_ARG.  An accumulator's form is fixed while it stands: amc_energy_histogram_accumulate on a blocked accumulator and
+ * amc_energy_histogram_accumulate_blocks on a plain one are AMC_ERR_STATE (amc_energy_histogram_fetch with reset frees either), as
+ * are other bins.
+ * amc_energy_histogram_fetch_blocks waits and returns the LOCAL shard's counts, *n_blocks = B, *n_groups = G, the bins and
+ * *n_snapshots; a block without a local ladder is all zero, and every (b, g) row sums to n_snapshots * (local ladders of block b).
+ * Blocks are functions of the global ladder index, so shards add cell by cell.  capacity_cells below B * G * (n_bins + 3) is
+ * AMC_ERR_BAD_ARG; counts = NULL returns the sizes and the bins alone (*n_snapshots = 0) without waiting; reset != 0 frees the
+ * accumulator.  AMC_ERR_STATE unless a blocked accumulator stands.
+ * amc_energy_histogram_fetch on a blocked accumulator returns the sum over the blocks (formed on the host behind the copy): the bits
+ * a plain accumulator would hold, capacity_cells and the row-sum identity as documented there.
+ * amc_set_energy_histogram_blocks restores a blocked accumulator (checkpoints) under the partition set beforehand: n_blocks = B;
+ * counts = NULL or n_snapshots = 0 clears; rows that do not ALL sum to n_snapshots * (local ladders of their block) -- an empty
+ * block's rows to zero -- are AMC_ERR_BAD_ARG, as are n_blocks != B and too many cells; AMC_ERR_STATE without a partition.
+ * amc_set_energy_histogram replaces an accumulator of either form by a plain one.
+ * Lifetimes: CLEARED by amc_set_ladder; a respacing that is taken zeroes the rows of EVERY block, one that is not leaves them; a
+ * successful amc_set_blocks, with any arguments, FOLDS a standing blocked accumulator into a plain one -- exact integer sums on the
+ * device, in stream order: nothing is lost, the bins stay, the form becomes plain --; kept by everything that keeps a plain one.
+ * A refused call leaves the handle as it was. */
+#define AMC_EHIST_BLK_MAX_CELLS 4194304
+int  amc_energy_histogram_accumulate_blocks(amc_handle *h, double lo, double hi, int n_bins);
+int  amc_energy_histogram_fetch_blocks(amc_handle *h, uint64_t *counts, int64_t capacity_cells, int *n_blocks, int *n_groups, int *n_bins,
+                                       double *lo, double *hi, uint64_t *n_snapshots, int reset);
+int  amc_set_energy_histogram_blocks(amc_handle *h, double lo, double hi, int n_bins, const uint64_t *counts_or_null, int n_blocks,
+                                     uint64_t n_snapshots);
 
 int  amc_sync(amc_handle *h);
 /* hipStream_t the handle launches on (for event timing / graph capture by the host). */

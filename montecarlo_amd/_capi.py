@@ -199,6 +199,9 @@ def load() -> C.CDLL:
         "amc_corr_fetch_blocks": (C.c_int, [H, dp, u64p, C.c_int, ip, ip, ip]),
         "amc_set_bridge_blocks": (C.c_int, [H, dp, C.c_int, C.c_uint64]),
         "amc_set_corr_blocks": (C.c_int, [H, C.c_int, dp, dp, u64p, C.c_int, C.c_int]),
+        "amc_energy_histogram_accumulate_blocks": (C.c_int, [H, C.c_double, C.c_double, C.c_int]),
+        "amc_energy_histogram_fetch_blocks": (C.c_int, [H, u64p, C.c_int64, ip, ip, ip, dp, dp, u64p, C.c_int]),
+        "amc_set_energy_histogram_blocks": (C.c_int, [H, C.c_double, C.c_double, C.c_int, u64p, C.c_int, C.c_uint64]),
         "amc_set_tracking": (C.c_int, [H, C.c_int]),
         "amc_download_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
         "amc_upload_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
@@ -962,6 +965,39 @@ class HipEngine:
                            f"{self.n_chains} chains")
         _check(self._lib.amc_set_corr_blocks(self._h, int(CORR_OBSERVABLES.get(observable, observable)), _ptr(org), _ptr(rec), _ptr(st),
                                              int(rec.shape[0]), int(st.size)))
+
+    # -- energy histograms per jackknife block (include/amc.h; DESIGN.md section 3.17 "Per block") ----------------
+    def energy_histogram_accumulate_blocks(self, lo: float, hi: float, n_bins: int) -> None:
+        """``energy_histogram_accumulate`` with a set of rows per block of the partition (amc_energy_histogram_accumulate_blocks):
+        needs ``set_blocks``; the first call after a reset fixes the bins and the accumulator's form and waits for the stream once."""
+        _check(self._lib.amc_energy_histogram_accumulate_blocks(self._h, float(lo), float(hi), int(n_bins)))
+
+    def energy_histogram_fetch_blocks(self, reset: bool = False):
+        """(counts[B, G, n_bins + 3] uint64, n_snapshots, (lo, hi, n_bins)) of this shard's blocked accumulator
+        (amc_energy_histogram_fetch_blocks); a block without a local ladder is all zero, shards add cell by cell.  An AmcError unless
+        a blocked accumulator stands.  ``reset`` frees the accumulator.  Synchronises."""
+        nk, ng, nb, lo, hi, count = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_double(0.0), C.c_uint64(0)
+        sizes = (C.byref(nk), C.byref(ng), C.byref(nb), C.byref(lo), C.byref(hi), C.byref(count))
+        _check(self._lib.amc_energy_histogram_fetch_blocks(self._h, None, 0, *sizes, 0))      # the sizes alone: nothing waits
+        shape = (nk.value, ng.value, nb.value + 3)
+        out = np.empty(shape[0] * shape[1] * shape[2], dtype=np.uint64)
+        _check(self._lib.amc_energy_histogram_fetch_blocks(self._h, _ptr(out), int(out.size), *sizes, int(bool(reset))))
+        return out.reshape(shape), int(count.value), (lo.value, hi.value, nb.value)
+
+    def set_energy_histogram_blocks(self, lo: float = 0.0, hi: float = 0.0, n_bins: int = 0, counts=None, n_snapshots: int = 0) -> None:
+        """Restore the blocked accumulator from ``energy_histogram_fetch_blocks``'s counts, count and bins
+        (amc_set_energy_histogram_blocks; checkpoints); ``counts=None`` or ``n_snapshots=0`` clears it.  The partition is set
+        beforehand."""
+        if counts is None or int(n_snapshots) == 0:
+            _check(self._lib.amc_set_energy_histogram_blocks(self._h, 0.0, 0.0, 0, None, 0, 0))
+            return
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        per_block = self._rungs() * (int(n_bins) + 3)
+        if c.ndim < 1 or c.shape[0] < 1 or c.size != c.shape[0] * per_block:
+            raise AmcError(f"set_energy_histogram_blocks: {c.size} counts, a block of {self._rungs()} rows of {int(n_bins)} bins takes {per_block}")
+        if int(n_snapshots) < 0:
+            raise AmcError("set_energy_histogram_blocks: n_snapshots < 0")
+        _check(self._lib.amc_set_energy_histogram_blocks(self._h, float(lo), float(hi), int(n_bins), _ptr(c), int(c.shape[0]), int(n_snapshots)))
 
     # -- walker tracking (include/amc.h; DESIGN.md section 3.13 "Walker tracking") ----------------
     def set_tracking(self, on: bool = True) -> None:

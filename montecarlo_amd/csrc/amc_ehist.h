@@ -1,6 +1,7 @@
 // amc_ehist.h -- energy histograms per group: energy_histogram_kernel<POT>, one pass that bins
-// e = potential_T(x) of every local chain into the row of its group (its rung; ONE group without a ladder), and the plain kernel that
-// zeroes the cells behind a respacing that was taken.  Counts are integers: the same on any grid, in any order, on any split.
+// e = potential_T(x) of every local chain into the row of its group (its rung; ONE group without a ladder),
+// energy_histogram_blocks_kernel<POT>, the same pass with a set of rows per jackknife block, and the plain kernels that zero the cells
+// behind a respacing that was taken and fold the blocks' rows into one set.  Counts are integers: the same on any grid, in any order, on any split.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
 #pragma once
 
@@ -70,9 +71,64 @@ __global__ __launch_bounds__(AMC_BLOCK) void energy_histogram_kernel(const Ehist
     }
 }
 
-// Behind ladder_respace_kernel on the stream: a respacing that was taken zeroes the cells, as it zeroes the bridge records -- counts
-// taken at other beta belong to another ladder.  Any other status leaves them.
+// Per jackknife block (amc_energy_histogram_accumulate_blocks): energy_histogram_kernel's body on the traversal of
+// bridge_sums_blocks_kernel.  The grid is a multiple of B and HIP block k serves jackknife block b = k mod B alone, over ALL local
+// ladders in one launch (a count has no lane cap), so the LDS array stays G rows for ONE jackknife block -- the same cells, the same
+// threshold, the same occupancy -- and is flushed into that block's rows, counts + b G (n_bins + 3); beyond the threshold every chain
+// is one 64-bit global atomic into its block's row.  A thread keeps its group (blk::walk_begin), so the row base is formed once; four
+// loads in flight per lane over the flattened (chunk, trip) sequence.  A u32 cell holds at most blk::lane_bound x AMC_BLOCK chains of
+// one pass: the host refuses a launch that could reach 2^32.
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void energy_histogram_blocks_kernel(const EhistArgs a, const blk::Part part)
+{
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
+    __shared__ unsigned int s_cells[EHIST_LDS_CELLS];
+    const int row = a.n_bins + 3, cells = a.n_groups * row;
+    const bool lds = cells <= EHIST_LDS_CELLS;
+    if (lds)
+        for (int i = threadIdx.x; i < cells; i += AMC_BLOCK) s_cells[i] = 0u;
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier: the cells are cleared too)
+
+    EhistArgs mine = a;                                        // ... with the rows of this HIP block's jackknife block
+    mine.counts = a.counts + (int64_t)((int)blockIdx.x % part.n_blocks) * cells;
+    blk::Walk w;
+    const int g = blk::walk_begin(w, part, a.n_groups, (int)gridDim.x, AMC_BLOCK, (int)blockIdx.x, (int)threadIdx.x, 0, a.n_chains / a.n_groups);
+    const int base = g * row;
+    for (;;) {
+        const int64_t l0 = blk::walk_next(w), l1 = blk::walk_next(w), l2 = blk::walk_next(w), l3 = blk::walk_next(w);
+        if (l3 < 0) {                                             // fewer than four are left: one by one
+            const int64_t rest[3] = {l0, l1, l2};
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (rest[j] >= 0) ehist_count<POT>(mine, a.x[rest[j] * a.n_groups + g], s_math, lds, s_cells, base);
+            break;
+        }
+        const real_t x0 = a.x[l0 * a.n_groups + g], x1 = a.x[l1 * a.n_groups + g], x2 = a.x[l2 * a.n_groups + g], x3 = a.x[l3 * a.n_groups + g];
+        ehist_count<POT>(mine, x0, s_math, lds, s_cells, base);
+        ehist_count<POT>(mine, x1, s_math, lds, s_cells, base);
+        ehist_count<POT>(mine, x2, s_math, lds, s_cells, base);
+        ehist_count<POT>(mine, x3, s_math, lds, s_cells, base);
+    }
+    if (lds) {
+        __syncthreads();
+        flush_cells(s_cells, mine.counts, cells);
+    }
+}
+
 #if AMC_PLAIN_KERNELS
+// amc_set_blocks on a blocked accumulator: the B blocks' rows added into the first, in place (thread i reads cell i of every block and
+// writes cell i of block 0 alone) -- what a plain accumulator would hold, integer for integer.
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void ehist_fold_kernel(unsigned long long* counts, int cells, int n_blocks)
+{
+    for (int i = blockIdx.x * AMC_BLOCK + threadIdx.x; i < cells; i += gridDim.x * AMC_BLOCK) {
+        unsigned long long s = counts[i];
+        for (int b = 1; b < n_blocks; ++b) s += counts[(int64_t)b * cells + i];
+        counts[i] = s;
+    }
+}
+
+// Behind ladder_respace_kernel on the stream: a respacing that was taken zeroes the cells (every block's, of a blocked accumulator), as
+// it zeroes the bridge records -- counts taken at other beta belong to another ladder.  Any other status leaves them.
 AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void ehist_respaced_kernel(unsigned long long* counts, int cells, const unsigned long long* rec)
 {
     if (rec[RESPACE_STATUS] != 0ull) return;

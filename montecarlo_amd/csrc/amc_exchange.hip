@@ -500,6 +500,8 @@ int amc_set_blocks(amc_handle* h, int n_blocks, int64_t chunk)
     if (chunk < 0 || chunk > AMC_MAX_JK_CHUNK)      // (the traversal adds a chunk to a global ladder index: both stay far from 2^63)
         return fail(AMC_ERR_BAD_ARG, "amc_set_blocks: chunk = %lld must lie in [1, 2^40], or be 0 for the default", (long long)chunk);
     AMC_HIP(hipSetDevice(h->device));
+    // energy histograms kept under the partition that goes: their blocks' rows are added up on the stream, nothing is lost
+    AMC_TRY(ehist_fold(h));
     // one full block-width of contiguous chains: every lane of a HIP block has a ladder of the chunk, in one trip
     if (n_blocks && chunk == 0) chunk = std::max(1, AMC_BLOCK / pass_groups(h));
     h->blocks.n_blocks = n_blocks;

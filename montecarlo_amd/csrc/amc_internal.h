@@ -13,7 +13,8 @@
 //                       amc_set_anneal_families .. amc_upload_families; amc_anneal_next_beta)
 //   amc_corr.hip        time correlation from one time origin (amc_corr_mark .. amc_corr_clear; per jackknife block: amc_corr_fetch_blocks;
 //                       the partition itself, amc_set_blocks, and amc_bridge_fetch_blocks are with the bridge sums in amc_exchange.hip)
-//   amc_ehist.hip       energy histograms per group (amc_energy_histogram_accumulate / _fetch, amc_set_energy_histogram)
+//   amc_ehist.hip       energy histograms per group (amc_energy_histogram_accumulate / _fetch, amc_set_energy_histogram; per jackknife
+//                       block: amc_energy_histogram_accumulate_blocks / _fetch_blocks, amc_set_energy_histogram_blocks)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -275,10 +276,13 @@ static inline void blocks_release(BlocksState& s)
 
 // Energy histograms per group (amc_ehist.hip): the accumulator is allocated by the first
 // amc_energy_histogram_accumulate after a reset -- a handle that never accumulates has none.  It stands exactly while d_ehist != nullptr.
+// Its FORM is fixed while it stands too: plain (blocks == 0), or blocked under the partition it was begun with
+// (amc_energy_histogram_accumulate_blocks: a set of rows per jackknife block); amc_set_blocks folds a blocked one into a plain one.
 struct EhistState {
-    unsigned long long* d_ehist = nullptr;      // [groups][n_bins + 3] counts; the bins are fixed while it stands
+    unsigned long long* d_ehist = nullptr;      // [blocks or 1][groups][n_bins + 3] counts; the bins are fixed while it stands
     int n_bins = 0;
     int groups = 0;                             // G when it was begun (amc_set_ladder clears it, so it is the handle's G while it stands)
+    int blocks = 0;                             // B of a blocked accumulator (the handle's partition while it stands); 0: plain
     double lo = 0.0, hi = 0.0;
 };
 static inline void ehist_release(EhistState& s)
@@ -500,9 +504,11 @@ AMC_INTERNAL int rung_pass_plan(amc_handle* h, int n_cols, bool blocked, RungPas
 // a kind-R record into words 0 .. 4 of an XS_ROW_R row, or a refusal naming who / where (amc_exchange.hip; amc_set_bridge*, amc_set_corr*)
 AMC_INTERNAL int r_row_from_record(const char* who, const char* where, const double* rec, amc::xs_word* row);
 // the energy histograms (amc_ehist.hip): the accumulator freed, no bins fixed (amc_set_ladder; waits for what still writes it); its cells
-// zeroed on the stream when the respacing just queued is taken (amc_respace_ladder).  Nothing happens on a handle without one.
+// zeroed on the stream when the respacing just queued is taken (amc_respace_ladder); a blocked accumulator folded into a plain one on
+// the stream (amc_set_blocks).  Nothing happens on a handle without one.
 AMC_INTERNAL int ehist_clear(amc_handle* h);
 AMC_INTERNAL int ehist_respaced(amc_handle* h);
+AMC_INTERNAL int ehist_fold(amc_handle* h);
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };

@@ -26,7 +26,8 @@
 //   amc_anneal_search.h  population annealing: the next beta from a target on the effective-sample fraction (energies, sums, decision)
 //   amc_corr.h         time correlation from one time origin: the sums of O, O^2, a O by group, one slot per lag
 //   amc_blocks.h       jackknife blocks: the traversal's index arithmetic, the bridge sums and the time correlation per block of ladders
-//   amc_ehist.h        energy histograms per group: energy_histogram_kernel, the cells zeroed behind a respacing
+//   amc_ehist.h        energy histograms per group: energy_histogram_kernel, energy_histogram_blocks_kernel (a set of rows per
+//                      jackknife block), the cells zeroed behind a respacing, the blocks' rows folded into one set
 #pragma once
 
 #include "amc_model.h"

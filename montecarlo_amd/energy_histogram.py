@@ -7,12 +7,16 @@ into the row of its group -- the rungs of the ladder, ONE group without a ladder
 snapshot order and on any split into shards.  Multiple-histogram reweighting (``reweighting.wham``) turns the rows into the density
 of states log g(E), the free energy per rung and <e>(beta), C(beta), log Z(beta) at any beta between the rungs; with one group it
 is single-histogram reweighting around the shared beta.
+
+With ``blocks=B`` the engine keeps the counts per jackknife block of ladders (DESIGN.md section 3.17 "Per block"), and every result
+comes with a delete-one-block standard error (``error=True``): each replicate is the whole of WHAM and the reweighting on its
+leave-one-out counts.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from . import reweighting, sharding
+from . import jackknife, reweighting, sharding
 from ._capi import AMC_EHIST_MAX_BINS
 from .metropolis import Metropolis
 from .simulation import AriannaAlgorithm, Simulation, _calls
@@ -27,9 +31,15 @@ class EnergyHistogram(AriannaAlgorithm):
 
     ``counts()`` are the counts of ALL ranks, ``reweight(betas)`` the curve.  ``max_outside``: the largest share of a row that may lie
     in one of the three cells outside the bins (below lo, at or above hi, NaN) before ``reweight`` / ``density_of_states`` /
-    ``free_energies`` refuse: what lies outside is missing from the reweighted sums, so the default tolerates nothing."""
+    ``free_energies`` refuse: what lies outside is missing from the reweighted sums, so the default tolerates nothing.
 
-    def __init__(self, chains, dependencies=None, lo=None, hi=None, n_bins=None, max_outside=0.0, path=None, **extras):
+    ``blocks=B`` (``block_chunk=C``, default ``jackknife.default_chunk``): the counts are kept per block of the jackknife partition
+    (B, C) -- one partition per Metropolis, shared with a ReplicaExchange / Autocorrelation that asks for blocks --;
+    ``counts_blocks()`` returns them, ``counts()`` their sum, and ``reweight`` / ``free_energies`` / ``density_of_states`` take
+    ``error=True``."""
+
+    def __init__(self, chains, dependencies=None, lo=None, hi=None, n_bins=None, max_outside=0.0, blocks=None, block_chunk=None, path=None,
+                 **extras):
         assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
         self.metropolis: Metropolis = dependencies[0]
         if lo is None or hi is None or n_bins is None:
@@ -43,6 +53,14 @@ class EnergyHistogram(AriannaAlgorithm):
         self.chains = chains
         self.lo, self.hi, self.n_bins, self.max_outside = float(lo), float(hi), int(n_bins), float(max_outside)
         self.metropolis.energy_histogram = self     # (storage.checkpoint: the accumulator is state)
+        groups = int(getattr(chains, "n_rungs", None) or 1)
+        if blocks is not None and block_chunk is None and self.metropolis.blocks and self.metropolis.blocks[0] == int(blocks):
+            block_chunk = self.metropolis.blocks[1]      # (another algorithm of these chains set the chunk: one partition per engine)
+        self.blocks = jackknife.check_blocks("EnergyHistogram", blocks, block_chunk, len(chains) // groups, groups)
+        if self.blocks:
+            if not hasattr(self.metropolis.engine, "energy_histogram_accumulate_blocks"):
+                raise ValueError("EnergyHistogram: this engine keeps no energy histograms per block (streams > 1 is not supported)")
+            jackknife.ask_blocks("EnergyHistogram", self.metropolis, self.blocks)
 
     # -- scheduling -----------------------------------------------------------------------------------------------------------------
     def initialise(self, simulation: Simulation) -> None:
@@ -50,9 +68,19 @@ class EnergyHistogram(AriannaAlgorithm):
         if any(isinstance(a, PopulationAnnealing) for a in simulation.algorithms):
             raise ValueError("EnergyHistogram beside a PopulationAnnealing: a histogram belongs to one beta, and annealing moves it; "
                              "PopulationAnnealing(..., energy_histogram=dict(lo=..., hi=..., n_bins=...)) keeps one histogram per temperature")
+        if self.blocks:
+            jackknife.refuse_annealing("EnergyHistogram", simulation)
+            from .exchange import ReplicaExchange
+            if any(isinstance(a, ReplicaExchange) and a.bridge and not a.blocks for a in simulation.algorithms):
+                raise ValueError("EnergyHistogram: blocks beside a ReplicaExchange(bridge=...) without blocks: setting the partition at the "
+                                 "first snapshot would clear the bridge sums accumulated so far; give the ReplicaExchange the same blocks")
 
     def make_step(self, simulation: Simulation) -> None:
-        self.metropolis.engine.energy_histogram_accumulate(self.lo, self.hi, self.n_bins)
+        if self.blocks:                         # (here and not in initialise: every algorithm's set_ladder lies behind us by now)
+            jackknife.use_blocks(self.metropolis, self.blocks)
+            self.metropolis.engine.energy_histogram_accumulate_blocks(self.lo, self.hi, self.n_bins)
+        else:
+            self.metropolis.engine.energy_histogram_accumulate(self.lo, self.hi, self.n_bins)
 
     def restart(self) -> None:
         """Drop what has been accumulated (fetch with reset); the next scheduled call begins anew."""
@@ -76,13 +104,29 @@ class EnergyHistogram(AriannaAlgorithm):
         """counts[G, n_bins + 3] (uint64) of ALL ranks: the bins, then below lo, at or above hi, NaN.  Summed exactly: a 64-bit count
         travels as two halves below 2^32, so the Float64 sum over the ranks rounds nothing.  The host waits for the queued
         snapshots."""
-        local = self._local()[0]
+        return self._all_ranks(self._local()[0])
+
+    def _all_ranks(self, local: np.ndarray) -> np.ndarray:
         if self.metropolis.world_size <= 1:
             return local
         halves = np.concatenate([(local & np.uint64(0xFFFFFFFF)).ravel(), (local >> np.uint64(32)).ravel()]).astype(np.float64)
         total = sharding.allreduce_sum(halves, self.metropolis.engine)
         lo_half, hi_half = total[:local.size].astype(np.uint64), total[local.size:].astype(np.uint64)
         return (lo_half + (hi_half << np.uint64(32))).reshape(local.shape)
+
+    def _local_blocks(self):
+        """(counts[B, G, n_bins + 3], n_snapshots) of this shard; zeros while nothing has been accumulated."""
+        if not self.blocks:
+            raise ValueError("EnergyHistogram: counts per block need blocks=B")
+        if self._local()[1] == 0:               # (nothing stands, or other bins: _local has said so)
+            return np.zeros((self.blocks[0], self._groups(), self.n_bins + 3), dtype=np.uint64), 0
+        counts, n_snap, _ = self.metropolis.engine.energy_histogram_fetch_blocks(reset=False)
+        return counts, n_snap
+
+    def counts_blocks(self) -> np.ndarray:
+        """counts[B, G, n_bins + 3] (uint64) of ALL ranks per jackknife block: blocks are functions of the global ladder index, so the
+        shards add cell by cell (the two halves of ``counts()``).  Needs ``blocks=B``; their sum over B is ``counts()``."""
+        return self._all_ranks(self._local_blocks()[0])
 
     @property
     def n_snapshots(self) -> int:
@@ -115,18 +159,55 @@ class EnergyHistogram(AriannaAlgorithm):
         counts = self._checked_counts()
         return reweighting.wham(counts[:, :self.n_bins], self.betas(), self.energies(), tol=tol, max_iter=max_iter)
 
-    def density_of_states(self, **kw):
+    def _jackknife(self, pick, tol=1e-12, max_iter=100000):
+        """(theta, se) of ``pick(log_g, f)`` (a flat Float64 array): theta from the counts of all blocks -- the bits the call without
+        ``error`` gives --, se from the B leave-one-out replicates, each the whole of WHAM on its own counts, started from the full
+        solution.  The ``max_outside`` check is the total's; a replicate that WHAM cannot solve raises, naming the block."""
+        if not self.blocks:
+            raise ValueError("EnergyHistogram: error=True needs blocks=B (the counts per jackknife block)")
+        self._checked_counts()                                          # (the total: the same refusals as without error)
+        blocks = self.counts_blocks()
+        betas, energies, n = self.betas(), self.energies(), self.n_bins
+        total = blocks.sum(axis=0, dtype=np.uint64)
+        log_g, f, _ = reweighting.wham(total[:, :n], betas, energies, tol=tol, max_iter=max_iter)
+        for b in range(blocks.shape[0]):
+            if not blocks[b].any():
+                raise ValueError(f"EnergyHistogram: block {b} is empty (fewer chunks of ladders than blocks?)")
+            rest = (total - blocks[b])[:, :n]
+            if np.any(rest.sum(axis=1) == 0) or not reweighting._connected(rest > 0):
+                raise ValueError(f"EnergyHistogram: without block {b} the rungs' histograms no longer connect (a row is empty or shares no "
+                                 "bin with the others): the replicate's free energies are undetermined; more snapshots or fewer blocks")
+
+        def fn(counts):
+            if counts is total or np.array_equal(counts, total):
+                return pick(log_g, f)
+            lg, fr, _ = reweighting.wham(counts[:, :n], betas, energies, tol=tol, max_iter=max_iter, f0=f)
+            return pick(lg, fr)
+
+        return jackknife.jackknife_counts(blocks, fn)
+
+    def density_of_states(self, error=False, **kw):
         """(energies[n_bins], log_g[n_bins]): the bin centres and the WHAM density of states (-inf where no rung has a count), on the
-        normalisation log Z(beta_0) = 0."""
+        normalisation log Z(beta_0) = 0.  ``error=True``: (energies, (log_g, se)), se NaN where a replicate has -inf."""
+        if error:
+            return self.energies(), self._jackknife(lambda lg, f: lg, **kw)
         return self.energies(), self._wham(**kw)[0]
 
-    def free_energies(self, **kw) -> np.ndarray:
-        """f_r = -log Z(beta_r) + log Z(beta_0) per rung (f_0 = 0)."""
+    def free_energies(self, error=False, **kw):
+        """f_r = -log Z(beta_r) + log Z(beta_0) per rung (f_0 = 0).  ``error=True``: (f, se)."""
+        if error:
+            return self._jackknife(lambda lg, f: f, **kw)
         return self._wham(**kw)[1]
 
-    def reweight(self, betas, **kw):
-        """(log Z, <e>, <e^2>, C) at every beta of ``betas`` (reweighting.reweight), from the ladder as it stands at fetch time."""
-        return reweighting.reweight(self._wham(**kw)[0], self.energies(), betas)
+    def reweight(self, betas, error=False, **kw):
+        """(log Z, <e>, <e^2>, C) at every beta of ``betas`` (reweighting.reweight), from the ladder as it stands at fetch time.
+        ``error=True``: the four as (value, se) pairs, ((log Z, se), (<e>, se), (<e^2>, se), (C, se))."""
+        if not error:
+            return reweighting.reweight(self._wham(**kw)[0], self.energies(), betas)
+        b = np.asarray(betas, dtype=np.float64)
+        energies = self.energies()
+        theta, se = self._jackknife(lambda lg, f: np.concatenate([np.ravel(v) for v in reweighting.reweight(lg, energies, b)]), **kw)
+        return tuple((t.reshape(b.shape), s.reshape(b.shape)) for t, s in zip(np.split(theta, 4), np.split(se, 4)))
 
     # -- checkpoints (storage.py's section) -------------------------------------------------------------------------------------------
     def state(self) -> dict:
@@ -142,5 +223,44 @@ class EnergyHistogram(AriannaAlgorithm):
         self.metropolis.engine.set_energy_histogram(self.lo, self.hi, self.n_bins, np.asarray(d["ehist_counts"], dtype=np.uint64),
                                                     int(d["ehist_snapshots"]))
 
+    def state_blocks(self) -> dict:
+        """The counts per block (storage.py's section behind the ladder and the partition); nothing without blocks or snapshots."""
+        if not self.blocks or self.metropolis.blocks_on != self.blocks:
+            return {}
+        counts, n_snap = self._local_blocks()
+        if not n_snap:
+            return {}
+        return dict(ehist_blocks=np.array(self.blocks, dtype=np.int64), ehist_block_counts=counts, ehist_block_snapshots=np.uint64(n_snap))
+
+    def set_state_blocks(self, d) -> None:
+        if "ehist_block_counts" not in d:
+            if self.blocks and "ehist_counts" in d and int(d["ehist_snapshots"]):
+                raise ValueError("checkpoint holds energy histograms without counts per block, this EnergyHistogram asks for blocks")
+            return
+        if not self.blocks:                     # (set_state has restored their sum: the run goes on with a plain accumulator)
+            return
+        if tuple(int(v) for v in d["ehist_blocks"]) != tuple(self.blocks):
+            raise ValueError(f"checkpoint holds energy histograms under the partition {tuple(int(v) for v in d['ehist_blocks'])}, this run asks "
+                             f"for {tuple(self.blocks)}")
+        jackknife.use_blocks(self.metropolis, self.blocks)
+        self.metropolis.engine.set_energy_histogram_blocks(self.lo, self.hi, self.n_bins, np.asarray(d["ehist_block_counts"], dtype=np.uint64),
+                                                           int(d["ehist_block_snapshots"]))
+
     def write_algorithm(self, io, scheduler) -> None:
         io.write(f"\tEnergyHistogram\n\t\tCalls: {_calls(scheduler)}\n\t\tBins: {self.n_bins} in [{self.lo}, {self.hi})\n")
+        if self.blocks:
+            io.write(f"\t\tBlocks: {self.blocks[0]} of chunk {self.blocks[1]}\n")
+
+
+def _find_energy_histogram(simulation: Simulation) -> EnergyHistogram:
+    found = [a for a in simulation.algorithms if isinstance(a, EnergyHistogram)]
+    if len(found) != 1:
+        raise ValueError(f"this callback needs exactly one EnergyHistogram in the algorithm list, found {len(found)}")
+    return found[0]
+
+
+def callback_reweight_error(simulation: Simulation) -> np.ndarray:
+    """The jackknife standard errors [4, G] of (log Z, <e>, <e^2>, C) reweighted to the ladder's own betas
+    (EnergyHistogram.reweight(betas(), error=True); needs blocks=B).  The host waits for the queued snapshots."""
+    eh = _find_energy_histogram(simulation)
+    return np.stack([se for _, se in eh.reweight(eh.betas(), error=True)])

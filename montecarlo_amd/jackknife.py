@@ -12,7 +12,7 @@ import numpy as np
 
 from ._capi import AMC_MAX_JK_BLOCKS, AMC_XSUM_WORDS, xsum_merge, xsum_round
 
-__all__ = ["block_counts", "check_blocks", "default_chunk", "jackknife", "leave_one_out", "use_blocks"]
+__all__ = ["block_counts", "check_blocks", "default_chunk", "jackknife", "jackknife_counts", "leave_one_out", "use_blocks"]
 
 
 def default_chunk(n_groups: int) -> int:
@@ -141,4 +141,30 @@ def jackknife(block_records, counts, fn):
     reps = np.stack([np.asarray(fn(xsum_round(loo[b]).reshape(shape), n - int(counts[b])), dtype=np.float64) for b in range(B)])
     dev = reps - reps.mean(axis=0)
     se = np.sqrt((B - 1) / B * (dev * dev).sum(axis=0))
+    return theta, se
+
+
+def jackknife_counts(block_counts, fn):
+    """(theta, se) of ``theta = fn(counts)`` for integer counts kept per block: ``block_counts[B, ...]`` uint64 (the energy histograms
+    of energy_histogram_fetch_blocks).  theta comes from the exact uint64 total, the B replicates from total - block b -- exact too: a
+    block's counts are part of the total, so the difference neither wraps nor rounds --, each the whole of ``fn``; se by the formula
+    of ``jackknife``.  A ValueError for B < 2 and for a block whose counts are all zero."""
+    c = np.ascontiguousarray(block_counts)
+    if c.dtype != np.uint64:
+        raise ValueError(f"jackknife_counts: counts of dtype {c.dtype}; the exact leave-one-out totals need uint64")
+    if c.ndim < 1:
+        raise ValueError(f"jackknife_counts: counts of shape {c.shape}; need [B, ...]")
+    B = c.shape[0]
+    if B < 2:
+        raise ValueError(f"jackknife_counts: {B} block(s); a jackknife needs at least 2")
+    for b in range(B):
+        if not c[b].any():
+            raise ValueError(f"jackknife_counts: block {b} is empty (fewer chunks of ladders than blocks?)")
+    total = c.sum(axis=0, dtype=np.uint64)
+    theta = np.asarray(fn(total), dtype=np.float64)
+    reps = np.stack([np.asarray(fn(total - c[b]), dtype=np.float64) for b in range(B)])
+    # (an entry that is not finite in some replicate -- log g of a bin only one block filled -- has the se NaN, and no other entry)
+    with np.errstate(invalid="ignore"):
+        dev = reps - reps.mean(axis=0)
+        se = np.sqrt((B - 1) / B * (dev * dev).sum(axis=0))
     return theta, se

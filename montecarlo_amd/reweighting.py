@@ -42,10 +42,11 @@ def _connected(support):
     return bool(np.all(seen))
 
 
-def wham(counts, betas, energies, tol=1e-12, max_iter=100000):
+def wham(counts, betas, energies, tol=1e-12, max_iter=100000, f0=None):
     """(log_g[n_bins], f[K], n_iter) from counts[K, n_bins] (integers or reals: expected counts are accepted), betas[K] and the
     bin energies.  f_0 = 0.  Bins empty in every row have log g = -inf and take no part.  ValueError: a row without an in-range
-    count, rows whose supports are not connected, no convergence within `max_iter`."""
+    count, rows whose supports are not connected, no convergence within `max_iter`.  ``f0``: the f[K] the iteration starts from
+    instead of zeros (a jackknife's replicates start from the full solution); the fixed point is the same."""
     n = np.asarray(counts, dtype=np.float64)
     b = np.asarray(betas, dtype=np.float64).reshape(-1)
     e = np.asarray(energies, dtype=np.float64).reshape(-1)
@@ -65,6 +66,11 @@ def wham(counts, betas, energies, tol=1e-12, max_iter=100000):
     log_n = np.log(totals)
     be = np.outer(b, e[live])                                   # beta_k E_b
     f = np.zeros(b.size)
+    if f0 is not None:
+        f = np.array(f0, dtype=np.float64).reshape(-1)
+        if f.shape != b.shape or not np.all(np.isfinite(f)):
+            raise ValueError(f"wham: f0 of shape {f.shape} for {b.size} betas, or not finite")
+        f = f - f[0]
     for it in range(1, int(max_iter) + 1):
         log_g = log_num - _logsumexp((log_n + f)[:, None] - be, axis=0)
         f_new = -_logsumexp(log_g[None, :] - be, axis=1)
