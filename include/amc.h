@@ -776,6 +776,38 @@ int  amc_energy_histogram_fetch(amc_handle *h, uint64_t *counts, int64_t capacit
                                 double *lo, double *hi, uint64_t *n_snapshots, int reset);
 int  amc_set_energy_histogram(amc_handle *h, double lo, double hi, int n_bins, const uint64_t *counts_or_null, uint64_t n_snapshots);
 
+/* Convergence per group: running sums PER CHAIN over time, and their reproducible sums over the chains of a
+ * group -- what the Gelman-Rubin potential scale reduction (split or not) and a batch-means tau_int are formed from on the host.
+ * Groups and observable are those of the time correlation: G = R with a ladder (group r = the slots l R + r), G = 1 without one;
+ * O(x) = double(potential_T(x)) for AMC_CORR_E, double(x) for AMC_CORR_X.
+ * Per local chain i and part p in {0, 1} (the two halves of the caller's window) the device keeps S[p][i] and Q[p][i], Float64: a
+ * sample into part p does S[p][i] <- S[p][i] + o_i, Q[p][i] <- Q[p][i] + fl(o_i o_i), one rounding per operation, nothing
+ * contracted; sequential in time per chain, so independent of grid, slices and shards.
+ * amc_chain_stats_accumulate queues one pass behind whatever is on the stream and returns at once (a pending learning step is taken
+ * first; with sliced sweep launches it runs behind their join, where a sample of the time correlation runs).  The first call after a
+ * clear allocates (once) and zeroes 4 * n_chains doubles and fixes the observable; a later call with another one is AMC_ERR_STATE.
+ * amc_chain_stats_fetch queues the sums by group, waits, and returns records[(g * AMC_CHAIN_STATS_COLS + c) * AMC_XSUM_WORDS ...] of
+ * the LOCAL shard (kind R; merge across shards with amc_xsum_merge), columns S0, S0S0, Q0, S1, S1S1, Q1, S0S1 with the summands
+ * S[0][i], fl(S[0][i] S[0][i]), Q[0][i], the same three of part 1, fl(S[0][i] S[1][i]); n[p] = the samples part p holds, *groups = G.
+ * The device divides nothing.  A non-finite summand flags the sums it belongs to, as in the time correlation.  records = NULL returns
+ * *groups, *observable and n alone, without waiting.  capacity_words counts the doubles the caller's array holds; fewer than
+ * G * AMC_CHAIN_STATS_COLS * AMC_XSUM_WORDS is AMC_ERR_BAD_ARG.  With nothing accumulated it writes no records, sets *observable = 0
+ * and n = {0, 0} and returns AMC_OK.  It never changes the accumulators.
+ * amc_chain_stats_download (sums[(p * 2 + k) * n_chains + i], k = 0: S, 1: Q; AMC_ERR_STATE with nothing accumulated) and
+ * amc_set_chain_stats serve checkpoints; amc_set_chain_stats with sums = NULL, n = NULL or n = {0, 0} clears, as amc_chain_stats_clear does
+ * (the memory stays).
+ * CLEARED by amc_set_ladder on success, amc_upload_state and amc_init_uniform.  KEPT by sweeps, exchange steps, reductions, the
+ * estimator, tuning, amc_set_blocks (the sums are not kept per jackknife block), the bridge sums, the time correlation, the energy
+ * histograms -- none of which they touch either -- and, on purpose, by amc_anneal, amc_set_beta and amc_respace_ladder: the caller clears
+ * when beta moves (the Python layer refuses such a schedule).
+ * AMC_ERR_BAD_ARG: part outside {0, 1}, an observable outside {E, X}.  A refused call leaves the handle as it was. */
+enum { AMC_CHAIN_STATS_PARTS = 2, AMC_CHAIN_STATS_COLS = 7 };
+int  amc_chain_stats_accumulate(amc_handle *h, int observable, int part);
+int  amc_chain_stats_fetch(amc_handle *h, double *records, int capacity_words, uint64_t *n, int *groups, int *observable);   /* n[2] */
+int  amc_chain_stats_download(amc_handle *h, double *sums);
+int  amc_set_chain_stats(amc_handle *h, int observable, const uint64_t *n, const double *sums);   /* n[2] */
+int  amc_chain_stats_clear(amc_handle *h);
+
 /* Jackknife blocks: the bridge sums and the time correlation kept per BLOCK of ladders, so that a
  * delete-one-block jackknife over the B blocks gives an error bar for any function of the sums -- the ladders (the chains, without a
  * ladder) are independent systems, whatever the correlation in time or between the rungs of one ladder.

@@ -40,6 +40,10 @@ AMC_MAX_JK_BLOCKS = 64          # blocks of a jackknife partition (amc_set_block
 AMC_EHIST_MAX_BINS = 8192       # bins of any histogram entry (amc_histogram, amc_energy_histogram_accumulate)
 AMC_CORR_O, AMC_CORR_OO, AMC_CORR_AO, AMC_CORR_COLS = 0, 1, 2, 3
 CORR_OBSERVABLES = {"energy": AMC_CORR_E, "x": AMC_CORR_X}
+# convergence per group (include/amc.h): the parts of the window, the columns of a fetch in their order
+AMC_CHAIN_STATS_PARTS, AMC_CHAIN_STATS_COLS = 2, 7
+(AMC_CHAIN_STATS_S0, AMC_CHAIN_STATS_S0S0, AMC_CHAIN_STATS_Q0, AMC_CHAIN_STATS_S1, AMC_CHAIN_STATS_S1S1, AMC_CHAIN_STATS_Q1,
+ AMC_CHAIN_STATS_S0S1) = range(7)
 AMC_RESPACE_ACCEPTANCE, AMC_RESPACE_FLOW = 1, 2      # the rules of amc_respace_ladder (include/amc.h)
 RESPACE_RULES = {"acceptance": AMC_RESPACE_ACCEPTANCE, "flow": AMC_RESPACE_FLOW}
 
@@ -194,6 +198,11 @@ def load() -> C.CDLL:
         "amc_energy_histogram_accumulate": (C.c_int, [H, C.c_double, C.c_double, C.c_int]),
         "amc_energy_histogram_fetch": (C.c_int, [H, u64p, C.c_int64, ip, ip, dp, dp, u64p, C.c_int]),
         "amc_set_energy_histogram": (C.c_int, [H, C.c_double, C.c_double, C.c_int, u64p, C.c_uint64]),
+        "amc_chain_stats_accumulate": (C.c_int, [H, C.c_int, C.c_int]),
+        "amc_chain_stats_fetch": (C.c_int, [H, dp, C.c_int, u64p, ip, ip]),
+        "amc_chain_stats_download": (C.c_int, [H, dp]),
+        "amc_set_chain_stats": (C.c_int, [H, C.c_int, u64p, dp]),
+        "amc_chain_stats_clear": (C.c_int, [H]),
         "amc_set_blocks": (C.c_int, [H, C.c_int, C.c_int64]),
         "amc_bridge_fetch_blocks": (C.c_int, [H, dp, C.c_int, ip, u64p, C.c_int]),
         "amc_corr_fetch_blocks": (C.c_int, [H, dp, u64p, C.c_int, ip, ip, ip]),
@@ -878,6 +887,60 @@ class HipEngine:
     def corr_clear(self) -> None:
         """Drop the mark (amc_corr_clear); the memory stays."""
         _check(self._lib.amc_corr_clear(self._h))
+
+    # -- convergence per group (include/amc.h; DESIGN.md section 3.18) ----------------
+    # (Not offered on a SplitEngine, as corr_mark is not.)
+    def chain_stats_accumulate(self, observable="energy", part: int = 0) -> None:
+        """Queue one sample of the observable into every local chain's running sums S and Q of ``part`` (0 or 1: the halves of the
+        window; amc_chain_stats_accumulate).  ``observable``: "energy" / "x" or AMC_CORR_E / AMC_CORR_X, fixed by the first call
+        after a clear.  Stream-ordered, nothing synchronises."""
+        _check(self._lib.amc_chain_stats_accumulate(self._h, int(CORR_OBSERVABLES.get(observable, observable)), int(part)))
+
+    def chain_stats_counts(self):
+        """((n0, n1), observable): the samples each part holds and the observable the sums were begun with, 0 when nothing is
+        accumulated (amc_chain_stats_fetch without records).  Host state: nothing is queued, nothing waits."""
+        n = np.zeros(2, dtype=np.uint64)
+        g, obs = C.c_int(0), C.c_int(0)
+        _check(self._lib.amc_chain_stats_fetch(self._h, None, 0, _ptr(n), C.byref(g), C.byref(obs)))
+        return (int(n[0]), int(n[1])), int(obs.value)
+
+    def chain_stats_fetch(self):
+        """(records[G][7][AMC_XSUM_WORDS], n[2], observable) of this shard: the sums over the chains of a group of S0, S0 S0, Q0, S1,
+        S1 S1, Q1, S0 S1 and the samples each part holds (amc_chain_stats_fetch); G = R with a ladder, else 1; records of shape
+        (G, 0, AMC_XSUM_WORDS), n = (0, 0) and observable 0 when nothing is accumulated.  What shards exchange
+        (sharding.allreduce_xsum).  Synchronises, changes nothing."""
+        n = np.zeros(2, dtype=np.uint64)
+        g, obs = C.c_int(0), C.c_int(0)
+        _check(self._lib.amc_chain_stats_fetch(self._h, None, 0, _ptr(n), C.byref(g), C.byref(obs)))      # the sizes alone: nothing waits
+        if obs.value == 0:
+            return np.zeros((g.value, 0, AMC_XSUM_WORDS)), (0, 0), 0
+        out = np.zeros((g.value, AMC_CHAIN_STATS_COLS, AMC_XSUM_WORDS), dtype=np.float64)
+        _check(self._lib.amc_chain_stats_fetch(self._h, _ptr(out), int(out.size), _ptr(n), C.byref(g), C.byref(obs)))
+        return out, (int(n[0]), int(n[1])), int(obs.value)
+
+    def chain_stats_sums(self) -> np.ndarray:
+        """sums[2 parts][S, Q][n_chains] of every local chain (amc_chain_stats_download; checkpoints).  Synchronises."""
+        out = np.zeros((AMC_CHAIN_STATS_PARTS, 2, self.n_chains), dtype=np.float64)
+        _check(self._lib.amc_chain_stats_download(self._h, _ptr(out)))
+        return out
+
+    def set_chain_stats(self, observable=0, n=(0, 0), sums=None) -> None:
+        """Restore the running sums from ``chain_stats_sums`` and ``chain_stats_fetch``'s n (amc_set_chain_stats; checkpoints);
+        ``sums=None`` or n = (0, 0) clears."""
+        cnt = np.ascontiguousarray(n, dtype=np.uint64)
+        if cnt.size != AMC_CHAIN_STATS_PARTS:
+            raise AmcError(f"set_chain_stats: n = {n!r} must hold the two counts")
+        if sums is None or not cnt.any():
+            _check(self._lib.amc_set_chain_stats(self._h, 0, None, None))
+            return
+        s = np.ascontiguousarray(sums, dtype=np.float64)
+        if s.size != AMC_CHAIN_STATS_PARTS * 2 * self.n_chains:
+            raise AmcError(f"set_chain_stats: {s.size} doubles, 2 parts of S and Q on {self.n_chains} chains take {4 * self.n_chains}")
+        _check(self._lib.amc_set_chain_stats(self._h, int(CORR_OBSERVABLES.get(observable, observable)), _ptr(cnt), _ptr(s)))
+
+    def chain_stats_clear(self) -> None:
+        """Forget the running sums (amc_chain_stats_clear); the memory stays."""
+        _check(self._lib.amc_chain_stats_clear(self._h))
 
     # -- energy histograms (include/amc.h; DESIGN.md section 3.17) ----------------
     # (Not offered on a SplitEngine, as bridge_accumulate is not: the sub-shards of one GPU keep no ladder state.)

@@ -379,8 +379,8 @@ __device__ __forceinline__ void rung_add(RLaneCols<RED_COLS>& L, real_t x, const
 }
 
 // ---- the frame of the sums by group (DESIGN.md section 3.13 "Per-rung sums") -----------------------------------------------------------
-// The five sums kernels -- rung_sums_kernel, bridge_sums_kernel, corr_sums_kernel (amc_corr.h) and the two blocked forms (amc_blocks.h)
-// -- are each: the slot prologue, a loop of their own, the block end; their rows go through ONE finishing merge.  A slot is
+// The six sums kernels -- rung_sums_kernel, bridge_sums_kernel, corr_sums_kernel (amc_corr.h), the two blocked forms (amc_blocks.h) and
+// chain_stats_sums_kernel (amc_chainstats.h) -- are each: the slot prologue, a loop of their own, the block end; their rows go through ONE finishing merge.  A slot is
 // s = g NC + c in LDS, g the lane's group (its rung), c one of the kernel's NC columns: s_top, s_flags and s_k[s] = k1.lo, k1.hi,
 // k2.lo, k2.hi (hi: two's complement).
 //

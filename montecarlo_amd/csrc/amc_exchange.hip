@@ -90,6 +90,7 @@ static int ladder_reset(amc_handle* h)
     AMC_TRY(bridge_clear(h));
     AMC_TRY(ehist_clear(h));        // (the energy histograms' groups are the rungs)
     corr_forget(h);                 // (no ladder state, but its groups are the rungs: the chains' slots mean something else now)
+    chain_stats_forget(h);          // (likewise the running sums per chain)
     h->blocks.n_blocks = 0;         // (the jackknife partition counts ladders: another R has other ladders)
     h->blocks.chunk = 0;
     h->lad.rung_on = false;
@@ -109,12 +110,14 @@ static int flow_snapshot_queue(amc_handle* h)
 
 // A pass over the groups (RungPass, amc_internal.h) planned, and room made for its rows.  Blocked: the same grid rounded up to a
 // multiple of B, and the ladders per launch by the traversal's own bound.
+int rung_pass_grid(const amc_handle* h) { return grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU); }
+
 int rung_pass_plan(amc_handle* h, int n_cols, bool blocked, RungPass* p)
 {
     const int R = pass_groups(h);
     p->groups = R;
     p->blocked = blocked;
-    p->grid = grid_for(h, h->M, h->knobs.blocks_per_cu ? 0 : RUNG_SUMS_BLOCKS_PER_CU);
+    p->grid = rung_pass_grid(h);
     if (blocked) p->grid = amc::blk::grid_round(p->grid, h->blocks.n_blocks);
     // a lane adds one summand per trip and column and holds XS_LANE_CAP of them (amc_xsum.h): ensembles beyond that many trips of the
     // grid (2^28 chains and more) take several launches, each with block rows of its own

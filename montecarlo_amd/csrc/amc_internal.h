@@ -15,6 +15,8 @@
 //                       the partition itself, amc_set_blocks, and amc_bridge_fetch_blocks are with the bridge sums in amc_exchange.hip)
 //   amc_ehist.hip       energy histograms per group (amc_energy_histogram_accumulate / _fetch, amc_set_energy_histogram; per jackknife
 //                       block: amc_energy_histogram_accumulate_blocks / _fetch_blocks, amc_set_energy_histogram_blocks)
+//   amc_chainstats.hip  convergence per group: running sums per chain and their sums by group (amc_chain_stats_accumulate ..
+//                       amc_chain_stats_clear)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
 //   amc_parameters.hip  the parameter table (amc_set / get_parameters, amc_parameters_begin / _end)
 //   amc_pg.hip          the estimator's host side (amc_pg_*, amc_pgmc_steps*)
@@ -290,6 +292,20 @@ static inline void ehist_release(EhistState& s)
     (void)hipFree(s.d_ehist);
 }
 
+// Convergence per group (amc_chainstats.hip): running sums per chain, both buffers allocated at their first
+// use -- a handle that never accumulates has neither.  The accumulators stand exactly while observable != 0.
+struct ChainStatsState {
+    int observable = 0;                         // AMC_CORR_E / AMC_CORR_X the accumulators were begun with; 0: nothing accumulated
+    uint64_t n[2] = {0, 0};                     // samples each part holds
+    double* d_sums = nullptr;                   // [2 parts][S, Q][M] (amc_chainstats.h)
+    amc::xs_word* d_stat_rows = nullptr;        // [AMC_MAX_RUNGS][CS_COLS][XS_ROW_R] the rows of the last fetch (chain_stats_finish_kernel)
+};
+static inline void chain_stats_release(ChainStatsState& s)
+{
+    (void)hipFree(s.d_sums);
+    (void)hipFree(s.d_stat_rows);
+}
+
 struct amc_handle {
     AmcKnobs knobs;             // the environment's knobs as amc_create found them
     int device = 0;
@@ -308,6 +324,7 @@ struct amc_handle {
     AnnealState ann;            // population annealing (amc_anneal.hip)
     CorrState corr;             // time correlation (amc_corr.hip)
     EhistState ehist;           // energy histograms per group (amc_ehist.hip)
+    ChainStatsState cstat;      // running sums per chain for the convergence diagnostics (amc_chainstats.hip)
     BlocksState blocks;         // jackknife blocks of the bridge sums and the time correlation (amc_exchange.hip, amc_corr.hip)
     double* d_x = nullptr;
     double* d_beta = nullptr;
@@ -442,6 +459,15 @@ static inline void corr_forget(amc_handle* h)
     h->corr.groups = 0;
 }
 
+// ... and so go the running sums per chain of the convergence diagnostics (an upload, a new initial ensemble, another ladder; NOT a
+// resampling, an annealing step or a respacing: the caller clears when beta moves).  Host fields only; the
+// memory stays and is zeroed by the next first sample.
+static inline void chain_stats_forget(amc_handle* h)
+{
+    h->cstat.observable = 0;
+    h->cstat.n[0] = h->cstat.n[1] = 0;
+}
+
 // ---- shared between the translation units ----------------------------------------------------------------------------------------
 AMC_INTERNAL int grid_for(const amc_handle* h, int64_t n_items, int blocks_per_cu = 0);   // amc_api.hip
 AMC_INTERNAL hipError_t wait_stream(hipStream_t stream);                                  // amc_state.hip
@@ -501,6 +527,7 @@ struct RungPass {
     int n_blocks() const { return (int)(n_launches * grid); }      // block rows the finishing kernel reads
 };
 AMC_INTERNAL int rung_pass_plan(amc_handle* h, int n_cols, bool blocked, RungPass* p);      // ... planned, and room made for its rows
+AMC_INTERNAL int rung_pass_grid(const amc_handle* h);      // the grid of an unblocked pass: what a memory-bound pass over the chains takes
 // a kind-R record into words 0 .. 4 of an XS_ROW_R row, or a refusal naming who / where (amc_exchange.hip; amc_set_bridge*, amc_set_corr*)
 AMC_INTERNAL int r_row_from_record(const char* who, const char* where, const double* rec, amc::xs_word* row);
 // the energy histograms (amc_ehist.hip): the accumulator freed, no bins fixed (amc_set_ladder; waits for what still writes it); its cells
@@ -539,22 +566,31 @@ static inline amc::blk::Part blocks_part(const amc_handle* h)
 }
 // A planned pass launched: `a` comes with what only its kernel reads (the bridge sums' beta, the origin of the time correlation); x, the
 // rows, the ladders, G and the columns are filled in here, and behind `a` the partition when the pass is blocked.
-template <class Args>
-static inline int rung_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
+// (rung_pass_each: the launches of the plan one by one -- G, each launch's rows and ladders filled in, then launch(a); the sums of the
+// chain statistics, whose kernel has no potential to be launched by, take it directly)
+template <class Args, class Launch>
+static inline int rung_pass_each(amc_handle* h, const RungPass& p, Args a, Launch launch)
 {
     const int64_t n_ladders = h->M / p.groups;
-    amc::blk::Part part = blocks_part(h);
-    a.x = h->d_x;
     a.n_rungs = p.groups;
-    a.cols = columns;
     for (int64_t i = 0; i < p.n_launches; ++i) {
         a.rows = h->lad.d_rung_rows + (size_t)i * (size_t)p.grid * p.slot_words;
         a.l_begin = i * p.per_launch;
         a.l_end = std::min(n_ladders, (i + 1) * p.per_launch);
-        void* params[] = {&a, p.blocked ? &part : nullptr};      // (a kernel reads as many as it has arguments)
-        AMC_TRY(launch_by_potential(h, name, double_well, harmonic, p.grid, params));
+        AMC_TRY(launch(a));
     }
     return AMC_OK;
+}
+template <class Args>
+static inline int rung_pass_launch(amc_handle* h, const RungPass& p, Args a, int columns, const char* name, const void* double_well, const void* harmonic)
+{
+    amc::blk::Part part = blocks_part(h);
+    a.x = h->d_x;
+    a.cols = columns;
+    return rung_pass_each(h, p, a, [&](Args& one) {
+        void* params[] = {&one, p.blocked ? &part : nullptr};      // (a kernel reads as many as it has arguments)
+        return launch_by_potential(h, name, double_well, harmonic, p.grid, params);
+    });
 }
 
 // *p holds exactly `need` words, zeroed on the stream when it is (re)allocated: the blocked accumulators follow B and G at their first use

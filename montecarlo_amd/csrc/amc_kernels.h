@@ -28,6 +28,7 @@
 //   amc_blocks.h       jackknife blocks: the traversal's index arithmetic, the bridge sums and the time correlation per block of ladders
 //   amc_ehist.h        energy histograms per group: energy_histogram_kernel, energy_histogram_blocks_kernel (a set of rows per
 //                      jackknife block), the cells zeroed behind a respacing, the blocks' rows folded into one set
+//   amc_chainstats.h   convergence per group: running sums per chain (chain_stats_add_kernel) and their sums by group
 #pragma once
 
 #include "amc_model.h"
@@ -44,3 +45,4 @@
 #include "amc_corr.h"
 #include "amc_blocks.h"
 #include "amc_ehist.h"
+#include "amc_chainstats.h"

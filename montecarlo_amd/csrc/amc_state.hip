@@ -130,6 +130,7 @@ int amc_upload_state(amc_handle* h, const double* x, const double* beta_or_null)
     if (!h || !x) return fail(AMC_ERR_BAD_ARG, "amc_upload_state: NULL argument");
     AMC_HIP(hipSetDevice(h->device));
     corr_forget(h);              // other positions in the slots: the mark of the time correlation goes
+    chain_stats_forget(h);       // ... and the running sums per chain
     if (h->f32) {
         AMC_HIP(hipMemcpyAsync(h->d_x64, x, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice, h->stream));
         AMC_TRY(narrow_from_x64(h, h->d_x));
@@ -158,6 +159,7 @@ int amc_init_uniform(amc_handle* h, double lo, double hi)
     if (!h) return fail(AMC_ERR_BAD_ARG, "amc_init_uniform: NULL handle");
     AMC_HIP(hipSetDevice(h->device));
     corr_forget(h);
+    chain_stats_forget(h);
     const int grid = grid_for(h, (h->M + 1) / 2);
     // Float32 state: System(Float32(lo + (hi - lo) u), beta) -- the Float64 ensemble, rounded
     hipLaunchKernelGGL(amc::init_uniform_kernel, dim3(grid), dim3(AMC_BLOCK), 0, h->stream, h->f32 ? h->d_x64 : h->d_x, h->M,

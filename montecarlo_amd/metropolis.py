@@ -114,6 +114,7 @@ class Metropolis(AriannaAlgorithm):
         self.annealing = None               # the PopulationAnnealing that cools these chains (its __init__)
         self.autocorrelation = None         # the Autocorrelation that measures these chains (its __init__)
         self.energy_histogram = None        # the EnergyHistogram that bins these chains' energies (its __init__)
+        self.convergence = None             # the Convergence that keeps these chains' running sums (its __init__)
         self.restored = False               # storage.restore put the state on the device: initialise() leaves it there
         self.families_restored = False      # storage.restore brought the annealing families back
         self._rung_window_used = False      # a tuning or a window restart has happened (tune_rung_sigma, restart_rung_window, storage.restore)

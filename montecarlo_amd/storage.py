@@ -323,6 +323,16 @@ def _read_correlation_blocks(met, eng, d, est) -> None:
         met.autocorrelation.set_state_blocks(d)
 
 
+def _write_convergence(met, eng, d, est) -> None:
+    cv = met.convergence
+    if cv is not None:                              # convergence per group: the observable, the counts, the sums per chain and the
+        d.update(cv.state())                        # algorithm's phase are state (no field otherwise)
+
+def _read_convergence(met, eng, d, est) -> None:
+    if "conv_observable" in d and met.convergence is not None:      # behind the core and the ladder: both clear the engine's sums
+        met.convergence.set_state(d)
+
+
 def _write_energy_histogram(met, eng, d, est) -> None:
     eh = met.energy_histogram
     if eh is not None:                              # energy histograms: the bins, the counts and the snapshot count are state (no field otherwise)
@@ -367,7 +377,8 @@ _SECTIONS = ((_write_core, _read_core), (_write_counters, _read_counters), (_wri
              (_write_ladder, _read_ladder), (_write_tracking, _read_tracking), (_write_window, _read_window),
              (_write_bridge, _read_bridge), (_write_bridge_blocks, _read_bridge_blocks), (_write_respacing, _read_respacing),
              (_write_annealing, _read_annealing), (_write_correlation, _read_correlation),
-             (_write_correlation_blocks, _read_correlation_blocks), (_write_energy_histogram, _read_energy_histogram),
+             (_write_correlation_blocks, _read_correlation_blocks), (_write_convergence, _read_convergence),
+             (_write_energy_histogram, _read_energy_histogram),
              (_write_energy_histogram_blocks, _read_energy_histogram_blocks), (_write_estimator, _read_estimator))
 
 
