@@ -7,7 +7,7 @@ down.  Every chain starts in the right well; the script runs the same schedule w
 rung, the fraction of chains left of the barrier, the mean energy and the swap acceptance of every gap.
 
     python examples/pt_double_well.py [--ladders 16384] [--steps 2000] [--path data/PT/...] [--track] [--rung-sigma] [--adapt flow|acceptance]
-                                          [--tune-sigma TARGET] [--free-energy] [--reweight N] [--blocks 32]
+                                          [--tune-sigma TARGET] [--free-energy] [--reweight N] [--moments] [--blocks 32]
 
 --track also follows every replica through the swaps and prints, at the end, the flow fraction f(r) -- of the replicas at rung r that
 have been to an end of the ladder, the share that came from the hot end (rung 0) last -- and the round trips per ladder.
@@ -35,6 +35,11 @@ energy histograms are kept per block too (EnergyHistogram(..., blocks=B)) and ev
 and prints <e>(beta), C(beta) and log(Z(beta) / Z(beta_0)) by multiple-histogram reweighting (WHAM) on an N-point grid between the end
 rungs, each beside the quadrature -- the curve BETWEEN the simulated temperatures.  With --free-energy the WHAM free energies per rung
 are printed beside the bridge estimates.
+
+--moments (with --reweight N) runs the TILTED well x^4 - 2 x^2 + x / 4 instead (a potential compiled at run time), whose wells are
+not equally deep, keeps the sums of x, x^2 and [x > 0] per energy bin on the device beside the counts
+(EnergyHistogram(..., moments=("x", "x2", "pos"), x_bound=4)) and prints <x>(beta), <x^2>(beta) and the occupancy of the right-hand
+well P(x > 0)(beta) on the same grid, each beside the quadrature: functions of the POSITION between the simulated temperatures.
 """
 import argparse
 import os
@@ -47,6 +52,13 @@ import montecarlo_amd as ma   # noqa: E402
 
 BETAS = (0.5, 1.0, 2.0, 4.0, 8.0)
 SIGMA0 = 0.3
+TILTED = "x*x*x*x - 2.0*x*x + 0.25*x"                  # --moments: the left well (x ~ -1.03, U ~ -1.26) lies 0.5 below the right one
+X_BOUND = 4.0                                          # |x| <= 4 for every binned chain: U(4) = 225 is far beyond the bins
+
+
+def well(tilted: bool):
+    """U(x) of the run as a numpy function."""
+    return (lambda x: x * x * x * x - 2.0 * x * x + 0.25 * x) if tilted else (lambda x: (x * x - 1.0) ** 2)
 
 
 class RestartBridge(ma.AriannaAlgorithm):
@@ -70,10 +82,10 @@ def log_z_by_quadrature():
 HIST = dict(lo=0.0, hi=60.0, n_bins=2400)
 
 
-def curve_by_quadrature(betas):
+def curve_by_quadrature(betas, tilted=False):
     """(log Z, <e>, C) at every beta of `betas` by the trapezoid rule on the same grid."""
     x = np.linspace(-6.0, 6.0, 240001)
-    u = (x * x - 1.0) ** 2
+    u = well(tilted)(x)
     out = []
     for b in betas:
         w = np.exp(-b * u)
@@ -82,10 +94,21 @@ def curve_by_quadrature(betas):
     return tuple(np.array(v) for v in zip(*out))
 
 
+def moments_by_quadrature(betas):
+    """(<x>, <x^2>, P(x > 0)) of the tilted well at every beta of `betas`, by the trapezoid rule on the same grid."""
+    x = np.linspace(-6.0, 6.0, 240001)
+    u = well(True)(x)
+    out = []
+    for b in betas:
+        w = np.exp(-b * (u - u.min()))
+        out.append((np.sum(w * x) / np.sum(w), np.sum(w * x * x) / np.sum(w), np.sum(w[x > 0]) / np.sum(w)))
+    return tuple(np.array(v) for v in zip(*out))
+
+
 def one_run(args, path, exchange: bool):
     R, L = len(BETAS), args.ladders
     x0 = 0.8 + 0.4 * ((np.arange(R * L) * 0.6180339887498949) % 1.0)          # every chain in the right well
-    chains = ma.ParticleChains.ladder(L, BETAS, potential="double_well", x=x0)
+    chains = ma.ParticleChains.ladder(L, BETAS, potential=ma.CustomPotential(TILTED) if args.moments else "double_well", x=x0)
     pool = (ma.Move(ma.Displacement(0.0), ma.StandardGaussian(), [SIGMA0], 1.0),)
     algorithm_list = [dict(algorithm=ma.Metropolis, pool=pool, seed=args.seed)]
     if exchange and args.rung_sigma:
@@ -117,15 +140,16 @@ def one_run(args, path, exchange: bool):
         if args.reweight:                              # measure over the second half of the run, behind every respacing and tuning
             half = args.steps // 2
             every = max(1, (args.steps - half) // 100)
+            hist = dict(HIST, lo=-1.5, hi=58.5, moments=("x", "x2", "pos"), x_bound=X_BOUND) if args.moments else HIST      # (the tilted well reaches -1.26)
             algorithm_list.append(dict(algorithm=ma.EnergyHistogram, dependencies=(ma.Metropolis,), blocks=args.blocks,
-                                       scheduler=list(range(half + every, args.steps + 1, every)), **HIST))
+                                       scheduler=list(range(half + every, args.steps + 1, every)), **hist))
     algorithm_list.append(dict(algorithm=ma.StoreCallbacks, callbacks=tuple(callbacks),
                                scheduler=ma.build_schedule(args.steps, 0, max(1, args.steps // 10))))
     simulation = ma.Simulation(chains, algorithm_list, args.steps, path=path)
     ma.run(simulation)
     x = simulation.chains.x.reshape(L, R)
     left = (x < 0.0).mean(axis=0)
-    energy = ma.potential("double_well", x).mean(axis=0)
+    energy = well(args.moments)(x).mean(axis=0)
     accept = simulation.algorithms[1].acceptance() if exchange else None
     hist = simulation.algorithms[0].engine.histogram_rungs(-2.0, 2.0, 8) if exchange else None
     return simulation, left, energy, accept, hist
@@ -150,12 +174,19 @@ def main(argv=None):
     ap.add_argument("--reweight", type=int, default=0, metavar="N",
                     help="accumulate an energy histogram per rung over the second half of the run; print <e>, C and log Z on an N-point grid "
                          "of beta between the end rungs by multiple-histogram reweighting, beside the quadrature")
+    ap.add_argument("--moments", action="store_true",
+                    help="with --reweight: run the tilted well x^4 - 2 x^2 + x / 4, keep the sums of x, x^2 and [x > 0] per energy bin and print "
+                         "<x>, <x^2> and P(x > 0) on the grid beside the quadrature")
     ap.add_argument("--blocks", type=int, default=None, metavar="B",
                     help="with --free-energy and / or --reweight: keep the bridge sums and the energy histograms per block of ladders and print "
                          "every estimate +- its jackknife standard error")
     args = ap.parse_args(argv)
     if args.blocks is not None and not (args.free_energy or args.reweight):
         ap.error("--blocks needs --free-energy or --reweight")
+    if args.moments and not args.reweight:
+        ap.error("--moments needs --reweight N")
+    if args.moments and (args.blocks is not None or args.free_energy):
+        ap.error("--moments: the moments per bin are not kept per jackknife block, and the quadrature beside --free-energy is the symmetric well's")
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
     _, left_plain, energy_plain, _, _ = one_run(args, os.path.join(path, "plain"), False)
@@ -202,9 +233,9 @@ def main(argv=None):
         eh = next(a for a in sim.algorithms if isinstance(a, ma.EnergyHistogram))
         ladder = eh.betas()
         grid = np.exp(np.linspace(np.log(ladder[0]), np.log(ladder[-1]), max(2, args.reweight)))
-        q_log_z, q_m1, q_c = curve_by_quadrature(grid)
-        q_log_z0 = curve_by_quadrature(ladder[:1])[0][0]
-        head = f"reweighted curve, {eh.n_snapshots} snapshots of {args.ladders} ladders, {HIST['n_bins']} bins of [{HIST['lo']:g}, {HIST['hi']:g})"
+        q_log_z, q_m1, q_c = curve_by_quadrature(grid, args.moments)
+        q_log_z0 = curve_by_quadrature(ladder[:1], args.moments)[0][0]
+        head = f"reweighted curve, {eh.n_snapshots} snapshots of {args.ladders} ladders, {eh.n_bins} bins of [{eh.lo:g}, {eh.hi:g})"
         if args.blocks:                                 # every point of the curve +- the jackknife over the blocks of ladders
             (log_z, z_se), (m1, m1_se), _, (c, c_se) = eh.reweight(grid, error=True)
             print(f"{head}: WHAM +- jackknife se over {args.blocks} blocks | quadrature")
@@ -218,6 +249,13 @@ def main(argv=None):
             print("     beta       <e>               C                 log(Z / Z_0)")
             for b, e1, e2, c1, c2, z1, z2 in zip(grid, m1, q_m1, c, q_c, log_z, q_log_z - q_log_z0):
                 print(f"  {b:7.4f}   {e1:7.4f} | {e2:7.4f}   {c1:7.4f} | {c2:7.4f}   {z1:8.4f} | {z2:8.4f}")
+        if args.moments:
+            mom = eh.reweight_moments(grid)
+            q_x, q_x2, q_pos = moments_by_quadrature(grid)
+            print(f"reweighted moments of the position, |x| <= {X_BOUND:g} ({int(eh.beyond_bound().sum())} binned samples beyond it): WHAM | quadrature")
+            print("     beta       <x>               <x^2>             P(x > 0)")
+            for b, x1, x2, s1, s2, p1, p2 in zip(grid, mom["x"], q_x, mom["x2"], q_x2, mom["pos"], q_pos):
+                print(f"  {b:7.4f}   {x1:7.4f} | {x2:7.4f}   {s1:7.4f} | {s2:7.4f}   {p1:7.4f} | {p2:7.4f}")
         if args.free_energy:
             rx = sim.algorithms[1]
             print("log(Z_r / Z_0), WHAM (-f_r)   : " + "  ".join(f"{v:7.4f}" for v in -eh.free_energies()))

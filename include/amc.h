@@ -884,6 +884,47 @@ int  amc_energy_histogram_fetch_blocks(amc_handle *h, uint64_t *counts, int64_t 
 int  amc_set_energy_histogram_blocks(amc_handle *h, double lo, double hi, int n_bins, const uint64_t *counts_or_null, int n_blocks,
                                      uint64_t n_snapshots);
 
+/* Moments per energy bin (DESIGN.md section 3.17 "Moments per bin"): the energy histograms' pass with, beside the count of every
+ * cell, the sums of x, x^2 and [x > 0] over the chains of every bin -- S_gb = sum of o over the samples of group g that fell into bin b.
+ * With the density of states g_b of WHAM they give a function of the POSITION at any beta: o_b = sum_g S_gb / sum_g n_gb and
+ * <o>(beta) = sum_b g_b exp(-beta E_b) o_b / sum_b g_b exp(-beta E_b).  An accumulator of its own, independent of the energy
+ * histograms': both may stand, and a handle that never calls these entries allocates and launches what it always did.
+ * Rule per chain, in this order: e = potential_T(x), v = double(e) and the cell by the binning rule above; xd = double(x) (exact).
+ * A chain whose cell is a bin but for which !(fabs(xd) <= x_bound) -- NaN included -- goes into a FOURTH tail cell, n_bins + 3
+ * ("x beyond x_bound"), and into no sum, so S_gb / n_gb stays a mean over the same samples.  A row has n_bins + 4 count cells; with no
+ * chain beyond x_bound the first n_bins + 3 are bit for bit those of amc_energy_histogram_accumulate.  A chain of bin b adds, to the
+ * columns that `mask` selects, the integer
+ *   AMC_EMOM_X    k = RN(lsb1(xd) * 2^-E_X)
+ *   AMC_EMOM_XX   k = RN(lsb1(v) * 2^-E_XX), v = xd * xd rounded to Float64 once (exact for Float32 state)
+ *   AMC_EMOM_POS  1 if xd > 0
+ * with eb = ilogb(x_bound) + 1, E_X = eb - 32, E_XX = 2 eb - 32, so |k| <= 2^32: kind Q of section 3.8 (lsb1 sets the last bit of
+ * the significand: no tie exists), added as signed 64-bit integers -- the same on any grid, in any order, on any split.  A sum cell
+ * times its quantum 2^E is the sum.  Layout: counts[g * (n_bins + 4) + cell] (unsigned), sums[(g * C + c) * n_bins + b] (signed),
+ * C = popcount(mask), columns in mask-bit order.
+ * amc_energy_moments_accumulate queues one pass and returns at once (stream-ordered; a pending learning step is taken first).  The
+ * first call after a reset allocates and zeroes the cells and fixes the FORM (lo, hi, n_bins, mask, x_bound); a later call with
+ * another form is AMC_ERR_STATE.  AMC_ERR_BAD_ARG: bins as amc_histogram refuses them, mask == 0 or bits outside AMC_EMOM_ALL,
+ * x_bound not finite and positive or outside [2^-500, 2^500).  Capacity: a cell holds fewer than 2^31 deposits of at most 2^32
+ * quanta; the handle counts the snapshots, and a call that would make n_snapshots * (n_chains / G) reach 2^31 is AMC_ERR_STATE before
+ * anything is launched (fetch with reset).  A refused first call leaves nothing allocated.
+ * amc_energy_moments_fetch waits and returns the LOCAL shard's cells (they add across shards), the form, *n_cols = C and
+ * *n_snapshots = (sum of row 0) / (n_chains / G): every row of counts sums to n_snapshots * n_chains / G.  The capacities count
+ * cells; too few are AMC_ERR_BAD_ARG.  counts = sums = NULL returns the sizes and the form alone (*n_snapshots = 0) without waiting;
+ * with nothing accumulated it writes no cells, *n_bins = 0, *n_cols = 0, *mask = 0 and returns AMC_OK.  reset != 0 frees the accumulator.
+ * amc_set_energy_moments restores it (checkpoints): counts = NULL, sums = NULL or n_snapshots = 0 clears; AMC_ERR_BAD_ARG for rows of
+ * counts that do not ALL sum to n_snapshots * n_chains / G, for n_snapshots * n_chains / G >= 2^31, for a sum cell whose magnitude
+ * exceeds (count of its bin) * 2^32, and for a POS cell that is negative or exceeds its count.
+ * Lifetimes are the energy histograms': CLEARED by amc_set_ladder; ZEROED on the device, in stream order, by a respacing that is taken
+ * (one that is not leaves the cells); kept by everything else, amc_anneal and amc_set_beta included.  amc_set_blocks does not touch
+ * it: a form per jackknife block does not exist yet, and neither does one per temperature of a population annealing. */
+enum { AMC_EMOM_X = 1, AMC_EMOM_XX = 2, AMC_EMOM_POS = 4, AMC_EMOM_ALL = 7 };
+int  amc_energy_moments_accumulate(amc_handle *h, double lo, double hi, int n_bins, int mask, double x_bound);
+int  amc_energy_moments_fetch(amc_handle *h, uint64_t *counts, int64_t *sums, int64_t capacity_counts, int64_t capacity_sums,
+                              int *n_groups, int *n_bins, int *n_cols, double *lo, double *hi, int *mask, double *x_bound,
+                              uint64_t *n_snapshots, int reset);
+int  amc_set_energy_moments(amc_handle *h, double lo, double hi, int n_bins, int mask, double x_bound, const uint64_t *counts_or_null,
+                            const int64_t *sums_or_null, uint64_t n_snapshots);
+
 int  amc_sync(amc_handle *h);
 /* hipStream_t the handle launches on (for event timing / graph capture by the host). */
 int  amc_get_stream(amc_handle *h, void **stream);

@@ -37,6 +37,7 @@ AMC_BRIDGE_E, AMC_BRIDGE_EE, AMC_BRIDGE_WF, AMC_BRIDGE_WB, AMC_BRIDGE_MF, AMC_BR
 AMC_CORR_E, AMC_CORR_X = 1, 2
 AMC_CORR_MAX_LAGS = 256
 AMC_MAX_JK_BLOCKS = 64          # blocks of a jackknife partition (amc_set_blocks)
+AMC_EMOM_X, AMC_EMOM_XX, AMC_EMOM_POS, AMC_EMOM_ALL = 1, 2, 4, 7      # columns of amc_energy_moments_accumulate, in mask-bit order
 AMC_EHIST_MAX_BINS = 8192       # bins of any histogram entry (amc_histogram, amc_energy_histogram_accumulate)
 AMC_CORR_O, AMC_CORR_OO, AMC_CORR_AO, AMC_CORR_COLS = 0, 1, 2, 3
 CORR_OBSERVABLES = {"energy": AMC_CORR_E, "x": AMC_CORR_X}
@@ -211,6 +212,9 @@ def load() -> C.CDLL:
         "amc_energy_histogram_accumulate_blocks": (C.c_int, [H, C.c_double, C.c_double, C.c_int]),
         "amc_energy_histogram_fetch_blocks": (C.c_int, [H, u64p, C.c_int64, ip, ip, ip, dp, dp, u64p, C.c_int]),
         "amc_set_energy_histogram_blocks": (C.c_int, [H, C.c_double, C.c_double, C.c_int, u64p, C.c_int, C.c_uint64]),
+        "amc_energy_moments_accumulate": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double]),
+        "amc_energy_moments_fetch": (C.c_int, [H, u64p, i64p, C.c_int64, C.c_int64, ip, ip, ip, dp, dp, ip, dp, u64p, C.c_int]),
+        "amc_set_energy_moments": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, u64p, i64p, C.c_uint64]),
         "amc_set_tracking": (C.c_int, [H, C.c_int]),
         "amc_download_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
         "amc_upload_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
@@ -976,6 +980,45 @@ class HipEngine:
         if int(n_snapshots) < 0:
             raise AmcError("set_energy_histogram: n_snapshots < 0")
         _check(self._lib.amc_set_energy_histogram(self._h, float(lo), float(hi), int(n_bins), _ptr(c), int(n_snapshots)))
+
+    # -- moments per energy bin (include/amc.h; DESIGN.md section 3.17 "Moments per bin") ----------------
+    def energy_moments_accumulate(self, lo: float, hi: float, n_bins: int, mask: int, x_bound: float) -> None:
+        """Queue one snapshot of the energy histograms WITH the sums of x, x^2 and [x > 0] per bin that ``mask`` selects
+        (AMC_EMOM_X | AMC_EMOM_XX | AMC_EMOM_POS) into their own device-resident accumulator (amc_energy_moments_accumulate).
+        Stream-ordered.  The form (bins, mask, ``x_bound``) is fixed by the first call after a reset."""
+        _check(self._lib.amc_energy_moments_accumulate(self._h, float(lo), float(hi), int(n_bins), int(mask), float(x_bound)))
+
+    def energy_moments_fetch(self, reset: bool = False):
+        """(counts[G, n_bins + 4] uint64, sums[G, C, n_bins] int64, n_snapshots, (lo, hi, n_bins, mask, x_bound)) of this shard's
+        accumulator (amc_energy_moments_fetch); both add across shards, and a sum cell times its quantum (``emom_quanta``) is the
+        sum.  With nothing accumulated: shapes (G, 0) and (G, 0, 0), 0 snapshots, (0.0, 0.0, 0, 0, 0.0).  ``reset`` frees the
+        accumulator and its form.  Synchronises."""
+        ng, nb, nc, lo, hi = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        mask, bound, count = C.c_int(0), C.c_double(0.0), C.c_uint64(0)
+        sizes = (C.byref(ng), C.byref(nb), C.byref(nc), C.byref(lo), C.byref(hi), C.byref(mask), C.byref(bound), C.byref(count))
+        _check(self._lib.amc_energy_moments_fetch(self._h, None, None, 0, 0, *sizes, 0))      # the sizes alone: nothing waits
+        if nb.value == 0:
+            return np.zeros((ng.value, 0), dtype=np.uint64), np.zeros((ng.value, 0, 0), dtype=np.int64), 0, (0.0, 0.0, 0, 0, 0.0)
+        counts = np.empty((ng.value, nb.value + 4), dtype=np.uint64)
+        sums = np.empty((ng.value, nc.value, nb.value), dtype=np.int64)
+        _check(self._lib.amc_energy_moments_fetch(self._h, _ptr(counts), _ptr(sums), int(counts.size), int(sums.size), *sizes, int(bool(reset))))
+        return counts, sums, int(count.value), (lo.value, hi.value, nb.value, mask.value, bound.value)
+
+    def set_energy_moments(self, lo: float = 0.0, hi: float = 0.0, n_bins: int = 0, mask: int = 0, x_bound: float = 0.0, counts=None, sums=None,
+                           n_snapshots: int = 0) -> None:
+        """Restore the accumulator from ``energy_moments_fetch``'s cells, count and form (amc_set_energy_moments; checkpoints);
+        ``counts=None``, ``sums=None`` or ``n_snapshots=0`` clears it."""
+        if counts is None or sums is None or int(n_snapshots) == 0:
+            _check(self._lib.amc_set_energy_moments(self._h, 0.0, 0.0, 0, 0, 0.0, None, None, 0))
+            return
+        c, s = np.ascontiguousarray(counts, dtype=np.uint64), np.ascontiguousarray(sums, dtype=np.int64)
+        G, cols = self._rungs(), bin(int(mask) & 0xFFFFFFFF).count("1")
+        if c.size != G * (int(n_bins) + 4) or s.size != G * cols * int(n_bins):
+            raise AmcError(f"set_energy_moments: {c.size} counts and {s.size} sums, {G} rows of {int(n_bins)} bins and {cols} columns take "
+                           f"{G * (int(n_bins) + 4)} and {G * cols * int(n_bins)}")
+        if int(n_snapshots) < 0:
+            raise AmcError("set_energy_moments: n_snapshots < 0")
+        _check(self._lib.amc_set_energy_moments(self._h, float(lo), float(hi), int(n_bins), int(mask), float(x_bound), _ptr(c), _ptr(s), int(n_snapshots)))
 
     # -- jackknife blocks (include/amc.h; DESIGN.md section 3.16) ----------------
     def set_blocks(self, n_blocks: int, chunk: int = 0) -> None:

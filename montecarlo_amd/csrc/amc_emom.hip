@@ -1,0 +1,210 @@
+// amc_emom.hip -- moments per energy bin (DESIGN.md section 3.17 "Moments per bin"): one pass per snapshot into a device-resident
+// accumulator of 64-bit counts and signed 64-bit sums of x, x^2 and [x > 0] per (group, bin) (amc_energy_moments_accumulate), its fetch
+// (amc_energy_moments_fetch) and the checkpoint entry (amc_set_energy_moments).  Independent of the energy histograms' accumulator
+// (amc_ehist.hip): both may stand.  Allocated at its first use: a handle that never accumulates has none and launches what it always did.
+#define AMC_KERNEL_LINKAGE static      // template instantiations, and this object's own copy of the plain kernel it launches (emom_respaced_kernel)
+#include "amc_internal.h"
+
+static_assert(AMC_EMOM_X == amc::EMOM_X && AMC_EMOM_XX == amc::EMOM_XX && AMC_EMOM_POS == amc::EMOM_POS && AMC_EMOM_ALL == amc::EMOM_ALL,
+              "the columns of include/amc.h and amc_emom.h");
+
+// G rows of n_bins + 4 count cells; G x C rows of n_bins sum cells behind them.
+static inline size_t emom_count_cells(int G, int n_bins) { return (size_t)G * (size_t)(n_bins + 4); }
+static inline size_t emom_sum_cells(int G, int cols, int n_bins) { return (size_t)G * (size_t)cols * (size_t)n_bins; }
+static inline size_t emom_words(const amc_handle* h)
+{
+    return emom_count_cells(h->emom.groups, h->emom.n_bins) + emom_sum_cells(h->emom.groups, h->emom.cols, h->emom.n_bins);
+}
+
+// The accumulator gone, no form fixed.  hipFree waits for whatever still writes the memory.
+int emom_clear(amc_handle* h)
+{
+    if (!h->emom.d_emom) return AMC_OK;
+    (void)hipFree(h->emom.d_emom);
+    h->emom = EmomState();
+    return AMC_OK;
+}
+
+int emom_respaced(amc_handle* h)
+{
+    if (!h->emom.d_emom) return AMC_OK;
+    const int words = (int)emom_words(h);       // (at most 64 rows of 8196 + 64 x 3 rows of 8192 cells)
+    hipLaunchKernelGGL(amc::emom_respaced_kernel, dim3(grid_for(h, words)), dim3(AMC_BLOCK), 0, h->stream, h->emom.d_emom, words,
+                       (const unsigned long long*)h->lad.d_respace);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
+// What every entry asks of a form: the bins as every histogram entry, a mask of known columns, a bound whose quanta exist.
+// (2^-500 <= x_bound < 2^500 keeps 1.5 * 2^(E + 52) a normal number for both quanta)
+static int emom_form_ok(const char* who, double lo, double hi, int n_bins, int mask, double x_bound)
+{
+    if (!hist_args_ok(who, lo, hi, n_bins)) return AMC_ERR_BAD_ARG;
+    if (mask == 0 || (mask & ~AMC_EMOM_ALL)) return fail(AMC_ERR_BAD_ARG, "%s: mask = %d: need at least one of AMC_EMOM_X, AMC_EMOM_XX, AMC_EMOM_POS and no other bit", who, mask);
+    if (!(std::isfinite(x_bound) && x_bound > 0.0)) return fail(AMC_ERR_BAD_ARG, "%s: x_bound = %g must be finite and positive", who, x_bound);
+    if (!(x_bound >= 0x1p-500 && x_bound < 0x1p500)) return fail(AMC_ERR_BAD_ARG, "%s: x_bound = %g lies outside [2^-500, 2^500)", who, x_bound);
+    return AMC_OK;
+}
+
+// Room for G rows of counts and G x C rows of sums under the form; the caller fills or zeroes it.
+static int emom_begin(amc_handle* h, double lo, double hi, int n_bins, int mask, double x_bound)
+{
+    const int G = pass_groups(h), cols = __builtin_popcount((unsigned)mask);
+    unsigned long long* d = nullptr;
+    AMC_HIP(hipMalloc(&d, (emom_count_cells(G, n_bins) + emom_sum_cells(G, cols, n_bins)) * sizeof(unsigned long long)));
+    h->emom = EmomState();
+    h->emom.d_emom = d;
+    h->emom.groups = G;
+    h->emom.n_bins = n_bins;
+    h->emom.mask = mask;
+    h->emom.cols = cols;
+    h->emom.lo = lo;
+    h->emom.hi = hi;
+    h->emom.x_bound = x_bound;
+    return AMC_OK;
+}
+
+// A cell holds fewer than 2^31 deposits: n_snapshots * (n_chains / G) stays below 2^31.
+static inline bool emom_fits(const amc_handle* h, uint64_t n_snapshots)
+{
+    const uint64_t per_group = (uint64_t)(h->M / pass_groups(h));
+    return n_snapshots < ((uint64_t)1 << 31) && n_snapshots * per_group < ((uint64_t)1 << 31);
+}
+
+extern "C" {
+
+int amc_energy_moments_accumulate(amc_handle* h, double lo, double hi, int n_bins, int mask, double x_bound)
+{
+    static const char* who = "amc_energy_moments_accumulate";
+    if (!h) return fail(AMC_ERR_BAD_ARG, "%s: NULL handle", who);
+    AMC_TRY(emom_form_ok(who, lo, hi, n_bins, mask, x_bound));
+    const EmomState& s = h->emom;
+    if (s.d_emom && (n_bins != s.n_bins || lo != s.lo || hi != s.hi || mask != s.mask || x_bound != s.x_bound))
+        return fail(AMC_ERR_STATE, "%s: the accumulator has another form: [%g, %g) in %d bins, mask %d, x_bound %g (amc_energy_moments_fetch with reset frees it)",
+                    who, s.lo, s.hi, s.n_bins, s.mask, s.x_bound);
+    // before anything is allocated or launched: the pass that would let a cell reach 2^31 deposits
+    if (!emom_fits(h, s.n_snapshots + 1))
+        return fail(AMC_ERR_STATE, "%s: %llu snapshots of %lld chains per group are all a cell holds (n_snapshots * n_chains / G < 2^31): fetch with reset", who,
+                    (unsigned long long)s.n_snapshots, (long long)(h->M / pass_groups(h)));
+    AMC_HIP(hipSetDevice(h->device));
+    // (as in front of an energy-histogram snapshot: a learning step left pending belongs in front of this point of the stream)
+    AMC_TRY(pg_resolve(h));
+    const bool first = !h->emom.d_emom;
+    if (first) {
+        AMC_TRY(emom_begin(h, lo, hi, n_bins, mask, x_bound));
+        if (hipMemsetAsync(h->emom.d_emom, 0, emom_words(h) * sizeof(unsigned long long), h->stream) != hipSuccess) {
+            (void)emom_clear(h);
+            return fail(AMC_ERR_HIP, "%s: clearing the accumulator failed", who);
+        }
+    }
+    amc::EmomArgs a = {};
+    a.x = h->d_x;
+    a.counts = h->emom.d_emom;
+    a.sums = h->emom.d_emom + emom_count_cells(h->emom.groups, n_bins);
+    a.n_chains = h->M;
+    a.lo = lo;
+    a.hi = hi;
+    a.inv_w = (double)n_bins / (hi - lo);
+    a.x_bound = x_bound;
+    a.n_groups = h->emom.groups;
+    a.n_bins = n_bins;
+    a.mask = mask;
+    a.n_cols = h->emom.cols;
+    a.e_x = amc::emom_e_x(x_bound);
+    a.e_xx = amc::emom_e_xx(x_bound);
+    void* params[] = {&a};
+    const int rc = launch_by_potential(h, "amc::energy_moments_kernel", (const void*)amc::energy_moments_kernel<amc::POT_DOUBLE_WELL>,
+                                       (const void*)amc::energy_moments_kernel<amc::POT_HARMONIC>, hist_grid(h), params);
+    // a first call that is refused (a run-time build that fails, say) leaves no accumulator and no form behind
+    if (rc != AMC_OK) {
+        if (first) (void)emom_clear(h);
+        return rc;
+    }
+    h->emom.n_snapshots += 1;
+    return AMC_OK;
+}
+
+int amc_energy_moments_fetch(amc_handle* h, uint64_t* counts, int64_t* sums, int64_t capacity_counts, int64_t capacity_sums, int* n_groups, int* n_bins,
+                             int* n_cols, double* lo, double* hi, int* mask, double* x_bound, uint64_t* n_snapshots, int reset)
+{
+    static const char* who = "amc_energy_moments_fetch";
+    if (!h || !n_groups || !n_bins || !n_cols || !lo || !hi || !mask || !x_bound || !n_snapshots) return fail(AMC_ERR_BAD_ARG, "%s: NULL argument", who);
+    const EmomState& s = h->emom;
+    *n_groups = s.d_emom ? s.groups : pass_groups(h);
+    *n_bins = s.n_bins;
+    *n_cols = s.cols;
+    *lo = s.lo;
+    *hi = s.hi;
+    *mask = s.mask;
+    *x_bound = s.x_bound;
+    *n_snapshots = 0;
+    if (!s.d_emom) return AMC_OK;       // nothing accumulated: no cells (the arrays may be NULL), no form
+    if (!counts && !sums) return AMC_OK;        // the sizes alone, for a caller about to allocate: nothing waits, nothing is copied, nothing is reset
+    if (!counts || !sums) return fail(AMC_ERR_BAD_ARG, "%s: counts and sums are given together, or neither", who);
+    const size_t n_counts = emom_count_cells(s.groups, s.n_bins), n_sums = emom_sum_cells(s.groups, s.cols, s.n_bins);
+    if (capacity_counts < (int64_t)n_counts || capacity_sums < (int64_t)n_sums)
+        return fail(AMC_ERR_BAD_ARG, "%s: capacities %lld and %lld, the accumulator has %d rows of %d count cells and %d x %d rows of %d sum cells", who,
+                    (long long)capacity_counts, (long long)capacity_sums, s.groups, s.n_bins + 4, s.groups, s.cols, s.n_bins);
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_HIP(hipMemcpyAsync(sums, s.d_emom + n_counts, n_sums * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    AMC_TRY(copy_to_host_sync(h, counts, s.d_emom, n_counts * sizeof(unsigned long long)));
+    uint64_t row0 = 0;
+    for (int i = 0; i < s.n_bins + 4; ++i) row0 += counts[i];
+    *n_snapshots = row0 / (uint64_t)(h->M / s.groups);      // every chain of a group lands in exactly one cell of its row
+    h->emom.n_snapshots = *n_snapshots;                     // (a respacing that was taken has zeroed the cells: the count follows them)
+    if (reset) return emom_clear(h);
+    return AMC_OK;
+}
+
+int amc_set_energy_moments(amc_handle* h, double lo, double hi, int n_bins, int mask, double x_bound, const uint64_t* counts_or_null,
+                           const int64_t* sums_or_null, uint64_t n_snapshots)
+{
+    static const char* who = "amc_set_energy_moments";
+    if (!h) return fail(AMC_ERR_BAD_ARG, "%s: NULL handle", who);
+    if (!counts_or_null || !sums_or_null || n_snapshots == 0) {
+        AMC_HIP(hipSetDevice(h->device));
+        return emom_clear(h);
+    }
+    AMC_TRY(emom_form_ok(who, lo, hi, n_bins, mask, x_bound));
+    const int G = pass_groups(h), cols = __builtin_popcount((unsigned)mask);
+    const uint64_t per_group = (uint64_t)(h->M / G);
+    if (!emom_fits(h, n_snapshots))
+        return fail(AMC_ERR_BAD_ARG, "%s: n_snapshots * n_chains / G = %llu * %llu is not below 2^31, all a cell holds", who, (unsigned long long)n_snapshots,
+                    (unsigned long long)per_group);
+    const uint64_t want = n_snapshots * per_group;
+    const int pos_col = (mask & AMC_EMOM_POS) ? cols - 1 : -1;
+    for (int g = 0; g < G; ++g) {
+        const uint64_t* row = counts_or_null + (size_t)g * (n_bins + 4);
+        uint64_t sum = 0;
+        bool over = false;
+        for (int i = 0; i < n_bins + 4 && !over; ++i) {     // (a sum that wraps cannot pass: every partial sum is held to `want`)
+            over = row[i] > want - sum;
+            if (!over) sum += row[i];
+        }
+        if (over || sum != want) return fail(AMC_ERR_BAD_ARG, "%s: row %d does not sum to n_snapshots * n_chains / G = %llu", who, g, (unsigned long long)want);
+        for (int c = 0; c < cols; ++c)
+            for (int b = 0; b < n_bins; ++b) {
+                const int64_t v = sums_or_null[((size_t)g * cols + c) * n_bins + b];
+                const uint64_t n = row[b];                  // (< 2^31: n << 32 cannot wrap)
+                const uint64_t mag = v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;
+                if (c == pos_col ? (v < 0 || mag > n) : mag > (n << 32))
+                    return fail(AMC_ERR_BAD_ARG, "%s: sum cell (group %d, column %d, bin %d) = %lld is more than the %llu chains of its bin can hold", who, g, c, b,
+                                (long long)v, (unsigned long long)n);
+            }
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_TRY(emom_clear(h));
+    AMC_TRY(emom_begin(h, lo, hi, n_bins, mask, x_bound));
+    const size_t n_counts = emom_count_cells(G, n_bins), n_sums = emom_sum_cells(G, cols, n_bins);
+    // (the caller's buffers are only valid during the call)
+    int rc = copy_to_device_sync(h, h->emom.d_emom, counts_or_null, n_counts * sizeof(unsigned long long));
+    if (rc == AMC_OK) rc = copy_to_device_sync(h, h->emom.d_emom + n_counts, sums_or_null, n_sums * sizeof(unsigned long long));
+    if (rc != AMC_OK) {
+        (void)emom_clear(h);
+        return rc;
+    }
+    h->emom.n_snapshots = n_snapshots;
+    return AMC_OK;
+}
+
+}  // extern "C"

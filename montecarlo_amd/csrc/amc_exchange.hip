@@ -89,6 +89,7 @@ static int ladder_reset(amc_handle* h)
     AMC_TRY(tune_reset(h, true));
     AMC_TRY(bridge_clear(h));
     AMC_TRY(ehist_clear(h));        // (the energy histograms' groups are the rungs)
+    AMC_TRY(emom_clear(h));         // (... and the moments per bin's)
     corr_forget(h);                 // (no ladder state, but its groups are the rungs: the chains' slots mean something else now)
     chain_stats_forget(h);          // (likewise the running sums per chain)
     h->blocks.n_blocks = 0;         // (the jackknife partition counts ladders: another R has other ladders)
@@ -741,6 +742,7 @@ int amc_respace_ladder(amc_handle* h, int rule, double gamma, double eps, const 
     hipLaunchKernelGGL(amc::ladder_respace_kernel, dim3(1), dim3(64), 0, h->stream, a, given);
     AMC_HIP(hipGetLastError());
     AMC_TRY(ehist_respaced(h));         // the energy histograms' cells go with status 0, as the bridge records do
+    AMC_TRY(emom_respaced(h));          // ... and the moments per bin's
     hipLaunchKernelGGL(amc::ladder_retile_kernel, dim3(grid_for(h, h->M)), dim3(AMC_BLOCK), 0, h->stream, (void*)h->d_beta, a.f32, h->lad.d_lab, h->M / R, R,
                        (const unsigned long long*)h->lad.d_respace);
     AMC_HIP(hipGetLastError());

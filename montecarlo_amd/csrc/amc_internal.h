@@ -15,6 +15,7 @@
 //                       the partition itself, amc_set_blocks, and amc_bridge_fetch_blocks are with the bridge sums in amc_exchange.hip)
 //   amc_ehist.hip       energy histograms per group (amc_energy_histogram_accumulate / _fetch, amc_set_energy_histogram; per jackknife
 //                       block: amc_energy_histogram_accumulate_blocks / _fetch_blocks, amc_set_energy_histogram_blocks)
+//   amc_emom.hip        moments per energy bin (amc_energy_moments_accumulate / _fetch, amc_set_energy_moments)
 //   amc_chainstats.hip  convergence per group: running sums per chain and their sums by group (amc_chain_stats_accumulate ..
 //                       amc_chain_stats_clear)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
@@ -292,6 +293,24 @@ static inline void ehist_release(EhistState& s)
     (void)hipFree(s.d_ehist);
 }
 
+// Moments per energy bin (amc_emom.hip; DESIGN.md section 3.17 "Moments per bin"): an accumulator of its own beside the energy
+// histograms', allocated by the first amc_energy_moments_accumulate after a reset -- a handle that never calls it has none.  It stands
+// exactly while d_emom != nullptr, and its form (bins, mask, bound) is fixed while it stands.
+struct EmomState {
+    unsigned long long* d_emom = nullptr;       // [groups][n_bins + 4] counts, then [groups][cols][n_bins] signed 64-bit sums: one allocation
+    int n_bins = 0;
+    int groups = 0;                             // G when it was begun (amc_set_ladder clears it)
+    int mask = 0, cols = 0;                     // the columns kept (AMC_EMOM_*), C = popcount(mask)
+    double lo = 0.0, hi = 0.0, x_bound = 0.0;
+    uint64_t n_snapshots = 0;                   // passes queued since the cells were last known to be zero: the capacity check's count (a
+                                                // respacing taken on the device zeroes the cells without the host knowing: amc_energy_moments_fetch
+                                                // brings the count back to what the rows hold)
+};
+static inline void emom_release(EmomState& s)
+{
+    (void)hipFree(s.d_emom);
+}
+
 // Convergence per group (amc_chainstats.hip): running sums per chain, both buffers allocated at their first
 // use -- a handle that never accumulates has neither.  The accumulators stand exactly while observable != 0.
 struct ChainStatsState {
@@ -324,6 +343,7 @@ struct amc_handle {
     AnnealState ann;            // population annealing (amc_anneal.hip)
     CorrState corr;             // time correlation (amc_corr.hip)
     EhistState ehist;           // energy histograms per group (amc_ehist.hip)
+    EmomState emom;             // moments per energy bin (amc_emom.hip)
     ChainStatsState cstat;      // running sums per chain for the convergence diagnostics (amc_chainstats.hip)
     BlocksState blocks;         // jackknife blocks of the bridge sums and the time correlation (amc_exchange.hip, amc_corr.hip)
     double* d_x = nullptr;
@@ -536,6 +556,9 @@ AMC_INTERNAL int r_row_from_record(const char* who, const char* where, const dou
 AMC_INTERNAL int ehist_clear(amc_handle* h);
 AMC_INTERNAL int ehist_respaced(amc_handle* h);
 AMC_INTERNAL int ehist_fold(amc_handle* h);
+// the moments per energy bin (amc_emom.hip): freed with the ladder, zeroed on the stream behind a respacing that is taken, as above
+AMC_INTERNAL int emom_clear(amc_handle* h);
+AMC_INTERNAL int emom_respaced(amc_handle* h);
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };

@@ -28,6 +28,8 @@
 //   amc_blocks.h       jackknife blocks: the traversal's index arithmetic, the bridge sums and the time correlation per block of ladders
 //   amc_ehist.h        energy histograms per group: energy_histogram_kernel, energy_histogram_blocks_kernel (a set of rows per
 //                      jackknife block), the cells zeroed behind a respacing, the blocks' rows folded into one set
+//   amc_emom.h         moments per energy bin: energy_moments_kernel (the energy histograms' pass with integer sums of x, x^2 and
+//                      [x > 0] per bin beside the counts), the deposit rule the host compiles too
 //   amc_chainstats.h   convergence per group: running sums per chain (chain_stats_add_kernel) and their sums by group
 #pragma once
 
@@ -45,4 +47,5 @@
 #include "amc_corr.h"
 #include "amc_blocks.h"
 #include "amc_ehist.h"
+#include "amc_emom.h"
 #include "amc_chainstats.h"

@@ -11,17 +11,31 @@ is single-histogram reweighting around the shared beta.
 With ``blocks=B`` the engine keeps the counts per jackknife block of ladders (DESIGN.md section 3.17 "Per block"), and every result
 comes with a delete-one-block standard error (``error=True``): each replicate is the whole of WHAM and the reweighting on its
 leave-one-out counts.
+
+With ``moments=("x", "x2", "pos")`` and ``x_bound=...`` the pass also adds x, x^2 and [x > 0] of the chains of every bin into integer
+sums on the device (DESIGN.md section 3.17 "Moments per bin"; include/amc.h amc_energy_moments_accumulate), and
+``reweight_moments(betas)`` gives <x>, <x^2> and the occupancy of the right-hand well at any beta: functions of the position, which
+the counts alone cannot give.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import jackknife, reweighting, sharding
-from ._capi import AMC_EHIST_MAX_BINS
+from ._capi import AMC_EHIST_MAX_BINS, AMC_EMOM_POS, AMC_EMOM_X, AMC_EMOM_XX
 from .metropolis import Metropolis
 from .simulation import AriannaAlgorithm, Simulation, _calls
 
-_CELLS = ("below lo", "at or above hi", "NaN")
+_CELLS = ("below lo", "at or above hi", "NaN", "x beyond x_bound")
+MOMENTS = {"x": AMC_EMOM_X, "x2": AMC_EMOM_XX, "pos": AMC_EMOM_POS}      # name -> column bit; the columns stand in bit order
+
+
+def emom_quanta(x_bound: float):
+    """(2^E_X, 2^E_XX, 1): the quantum of every column under ``x_bound`` -- eb = ilogb(x_bound) + 1, E_X = eb - 32, E_XX = 2 eb - 32."""
+    eb = int(np.floor(np.log2(float(x_bound)))) + 1
+    if not 2.0 ** (eb - 1) <= float(x_bound) < 2.0 ** eb:      # (log2 rounded across a power of two)
+        eb += 1 if float(x_bound) >= 2.0 ** eb else -1
+    return {AMC_EMOM_X: 2.0 ** (eb - 32), AMC_EMOM_XX: 2.0 ** (2 * eb - 32), AMC_EMOM_POS: 1.0}
 
 
 class EnergyHistogram(AriannaAlgorithm):
@@ -36,10 +50,15 @@ class EnergyHistogram(AriannaAlgorithm):
     ``blocks=B`` (``block_chunk=C``, default ``jackknife.default_chunk``): the counts are kept per block of the jackknife partition
     (B, C) -- one partition per Metropolis, shared with a ReplicaExchange / Autocorrelation that asks for blocks --;
     ``counts_blocks()`` returns them, ``counts()`` their sum, and ``reweight`` / ``free_energies`` / ``density_of_states`` take
-    ``error=True``."""
+    ``error=True``.
+
+    ``moments=("x", "x2", "pos")`` (any of the three) with ``x_bound=...``: the pass keeps, per bin, the sums of x, x^2 and [x > 0]
+    beside the counts, in an accumulator of their own; ``moment_sums()``, ``microcanonical()``, ``reweight_moments(betas)`` return
+    them.  A chain of a bin with |x| > x_bound (or NaN) is counted in a fourth cell outside the bins, "x beyond x_bound", which
+    ``max_outside`` covers too.  Not available together with ``blocks``: the moments are not kept per jackknife block yet."""
 
     def __init__(self, chains, dependencies=None, lo=None, hi=None, n_bins=None, max_outside=0.0, blocks=None, block_chunk=None, path=None,
-                 **extras):
+                 moments=None, x_bound=None, **extras):
         assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
         self.metropolis: Metropolis = dependencies[0]
         if lo is None or hi is None or n_bins is None:
@@ -50,6 +69,25 @@ class EnergyHistogram(AriannaAlgorithm):
             raise ValueError(f"EnergyHistogram: max_outside = {max_outside!r} must lie in [0, 1]")
         if not hasattr(self.metropolis.engine, "energy_histogram_accumulate"):
             raise ValueError("EnergyHistogram: this engine has no energy histograms (streams > 1 is not supported)")
+        self.mask, self.moments, self.x_bound = 0, (), None
+        if moments is not None:
+            names = (moments,) if isinstance(moments, str) else tuple(moments)
+            if not names or any(n not in MOMENTS for n in names) or len(set(names)) != len(names):
+                raise ValueError(f"EnergyHistogram: moments = {moments!r}: need one or more of {tuple(MOMENTS)}, each once")
+            if blocks is not None:
+                raise ValueError("EnergyHistogram: moments together with blocks: the moments per bin are not kept per jackknife block yet "
+                                 "(no error bars for reweight_moments); give one of the two")
+            if x_bound is None:
+                raise ValueError("EnergyHistogram: moments need x_bound, the largest |x| a binned chain may have (it fixes the sums' quanta)")
+            if not (np.isfinite(x_bound) and 2.0 ** -500 <= float(x_bound) < 2.0 ** 500):
+                raise ValueError(f"EnergyHistogram: x_bound = {x_bound!r} must be finite, positive and within [2^-500, 2^500)")
+            if not hasattr(self.metropolis.engine, "energy_moments_accumulate"):
+                raise ValueError("EnergyHistogram: this engine keeps no moments per energy bin (streams > 1 is not supported)")
+            self.moments = tuple(n for n in MOMENTS if n in names)      # (in column order)
+            self.mask = sum(MOMENTS[n] for n in self.moments)
+            self.x_bound = float(x_bound)
+        elif x_bound is not None:
+            raise ValueError("EnergyHistogram: x_bound without moments")
         self.chains = chains
         self.lo, self.hi, self.n_bins, self.max_outside = float(lo), float(hi), int(n_bins), float(max_outside)
         self.metropolis.energy_histogram = self     # (storage.checkpoint: the accumulator is state)
@@ -79,12 +117,17 @@ class EnergyHistogram(AriannaAlgorithm):
         if self.blocks:                         # (here and not in initialise: every algorithm's set_ladder lies behind us by now)
             jackknife.use_blocks(self.metropolis, self.blocks)
             self.metropolis.engine.energy_histogram_accumulate_blocks(self.lo, self.hi, self.n_bins)
+        elif self.mask:
+            self.metropolis.engine.energy_moments_accumulate(self.lo, self.hi, self.n_bins, self.mask, self.x_bound)
         else:
             self.metropolis.engine.energy_histogram_accumulate(self.lo, self.hi, self.n_bins)
 
     def restart(self) -> None:
         """Drop what has been accumulated (fetch with reset); the next scheduled call begins anew."""
-        self.metropolis.engine.energy_histogram_fetch(reset=True)
+        if self.mask:
+            self.metropolis.engine.energy_moments_fetch(reset=True)
+        else:
+            self.metropolis.engine.energy_histogram_fetch(reset=True)
 
     # -- results --------------------------------------------------------------------------------------------------------------------
     def _groups(self) -> int:
@@ -92,6 +135,9 @@ class EnergyHistogram(AriannaAlgorithm):
 
     def _local(self):
         """(counts[G, n_bins + 3], n_snapshots) of this shard; zeros while nothing has been accumulated."""
+        if self.mask:                           # (the moments' pass counts too: its first n_bins + 3 cells)
+            counts, _, n_snap = self._local_moments()
+            return np.ascontiguousarray(counts[:, :self.n_bins + 3]), n_snap
         counts, n_snap, (lo, hi, n_bins) = self.metropolis.engine.energy_histogram_fetch(reset=False)
         if n_bins == 0:
             return np.zeros((self._groups(), self.n_bins + 3), dtype=np.uint64), 0
@@ -99,6 +145,20 @@ class EnergyHistogram(AriannaAlgorithm):
             raise ValueError(f"EnergyHistogram: the engine's accumulator has the bins {(lo, hi, n_bins)}, this algorithm asks for "
                              f"{(self.lo, self.hi, self.n_bins)}")
         return counts, n_snap
+
+    def _local_moments(self):
+        """(counts[G, n_bins + 4], sums[G, C, n_bins] int64, n_snapshots) of this shard; zeros while nothing has been accumulated."""
+        if not self.mask:
+            raise ValueError("EnergyHistogram: the moments per bin need moments=(...) and x_bound")
+        counts, sums, n_snap, form = self.metropolis.engine.energy_moments_fetch(reset=False)
+        if form[2] == 0:
+            G = self._groups()
+            return np.zeros((G, self.n_bins + 4), dtype=np.uint64), np.zeros((G, len(self.moments), self.n_bins), dtype=np.int64), 0
+        mine = (self.lo, self.hi, self.n_bins, self.mask, self.x_bound)
+        if form != mine:
+            raise ValueError(f"EnergyHistogram: the engine's accumulator has the form (lo, hi, n_bins, mask, x_bound) = {form}, this algorithm "
+                             f"asks for {mine}")
+        return counts, sums, n_snap
 
     def counts(self) -> np.ndarray:
         """counts[G, n_bins + 3] (uint64) of ALL ranks: the bins, then below lo, at or above hi, NaN.  Summed exactly: a 64-bit count
@@ -148,11 +208,17 @@ class EnergyHistogram(AriannaAlgorithm):
         if not counts[:, :self.n_bins].sum():
             raise ValueError("EnergyHistogram: nothing has been accumulated yet")
         share = reweighting.outside_share(counts)
+        if self.mask:                           # the fourth cell, "x beyond x_bound", belongs to the same total
+            beyond = self.beyond_bound().astype(np.float64)
+            total = counts.sum(axis=1).astype(np.float64) + beyond
+            with np.errstate(invalid="ignore", divide="ignore"):
+                share = np.where(total[:, None] > 0, np.concatenate([counts[:, -3:], beyond[:, None]], axis=1) / total[:, None], 0.0)
         bad = np.argwhere(share > self.max_outside)
         if bad.size:
             g, c = int(bad[0][0]), int(bad[0][1])
             raise ValueError(f"EnergyHistogram: rung {g} has a share of {share[g, c]:.3e} of its samples in the cell '{_CELLS[c]}' "
-                             f"(max_outside = {self.max_outside:g}): widen [lo, hi) = [{self.lo:g}, {self.hi:g})")
+                             f"(max_outside = {self.max_outside:g}): " +
+                             (f"raise x_bound = {self.x_bound:g}" if c == 3 else f"widen [lo, hi) = [{self.lo:g}, {self.hi:g})"))
         return counts
 
     def _wham(self, tol=1e-12, max_iter=100000):
@@ -209,8 +275,41 @@ class EnergyHistogram(AriannaAlgorithm):
         theta, se = self._jackknife(lambda lg, f: np.concatenate([np.ravel(v) for v in reweighting.reweight(lg, energies, b)]), **kw)
         return tuple((t.reshape(b.shape), s.reshape(b.shape)) for t, s in zip(np.split(theta, 4), np.split(se, 4)))
 
+    # -- moments per bin ---------------------------------------------------------------------------------------------------------------
+    def beyond_bound(self) -> np.ndarray:
+        """Per group the chains of ALL ranks that fell into a bin with |x| > x_bound or NaN (uint64[G]): the fourth tail cell."""
+        return self._all_ranks(np.ascontiguousarray(self._local_moments()[0][:, self.n_bins + 3]))
+
+    def moment_sums(self) -> np.ndarray:
+        """S[G, C, n_bins] (Float64) of ALL ranks: per group, column (``self.moments``, in that order) and bin the sum of the observable
+        over the samples of the bin -- the device's integer times the column's quantum.  The signed 64-bit integers travel as the
+        two halves of their two's complement, like the counts, and are put together modulo 2^64: exact.  The host waits for the
+        queued snapshots."""
+        k = self._all_ranks(self._local_moments()[1].view(np.uint64)).view(np.int64)
+        quanta = emom_quanta(self.x_bound)
+        q = np.array([quanta[MOMENTS[n]] for n in self.moments], dtype=np.float64)
+        return k.astype(np.float64) * q[None, :, None]
+
+    def microcanonical(self):
+        """(energies[n_bins], o[C, n_bins]): the mean of every observable over all samples of a bin, sum_g S_gb / sum_g n_gb; NaN where
+        no group has a count."""
+        n = self.counts()[:, :self.n_bins].sum(axis=0).astype(np.float64)
+        s = self.moment_sums().sum(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.energies(), np.where(n[None, :] > 0, s / n[None, :], np.nan)
+
+    def reweight_moments(self, betas, **kw) -> dict:
+        """{name: <o>(beta)} for every kept moment ("x", "x2", "pos") at every beta of ``betas`` (reweighting.reweight_observable with
+        WHAM's density of states), from the ladder as it stands at fetch time."""
+        counts = self._checked_counts()[:, :self.n_bins]
+        log_g = reweighting.wham(counts, self.betas(), self.energies(), **kw)[0]
+        sums = self.moment_sums()
+        return {name: reweighting.reweight_observable(log_g, self.energies(), betas, sums[:, c, :], counts) for c, name in enumerate(self.moments)}
+
     # -- checkpoints (storage.py's section) -------------------------------------------------------------------------------------------
     def state(self) -> dict:
+        if self.mask:                           # (the moments' accumulator holds the counts: state_moments)
+            return {}
         counts, n_snap = self._local()
         return dict(ehist_bins=np.array([self.lo, self.hi, float(self.n_bins)], dtype=np.float64), ehist_counts=counts,
                     ehist_snapshots=np.uint64(n_snap))
@@ -222,6 +321,25 @@ class EnergyHistogram(AriannaAlgorithm):
                              f"{(self.lo, self.hi, self.n_bins)}")
         self.metropolis.engine.set_energy_histogram(self.lo, self.hi, self.n_bins, np.asarray(d["ehist_counts"], dtype=np.uint64),
                                                     int(d["ehist_snapshots"]))
+
+    def state_moments(self) -> dict:
+        """The moments' accumulator (storage.py's section): the form, the cells and the snapshot count; nothing without moments."""
+        if not self.mask:
+            return {}
+        counts, sums, n_snap = self._local_moments()
+        return dict(emom_form=np.array([self.lo, self.hi, float(self.n_bins), float(self.mask), self.x_bound], dtype=np.float64),
+                    emom_counts=counts, emom_sums=sums, emom_snapshots=np.uint64(n_snap))
+
+    def set_state_moments(self, d) -> None:
+        if "emom_counts" not in d or not self.mask:
+            return
+        lo, hi, n_bins, mask, x_bound = (float(v) for v in d["emom_form"])
+        form, mine = (lo, hi, int(n_bins), int(mask), x_bound), (self.lo, self.hi, self.n_bins, self.mask, self.x_bound)
+        if form != mine:
+            raise ValueError(f"checkpoint holds moments per bin of the form (lo, hi, n_bins, mask, x_bound) = {form}, this EnergyHistogram "
+                             f"asks for {mine}")
+        self.metropolis.engine.set_energy_moments(*mine, np.asarray(d["emom_counts"], dtype=np.uint64), np.asarray(d["emom_sums"], dtype=np.int64),
+                                                  int(d["emom_snapshots"]))
 
     def state_blocks(self) -> dict:
         """The counts per block (storage.py's section behind the ladder and the partition); nothing without blocks or snapshots."""
@@ -250,6 +368,8 @@ class EnergyHistogram(AriannaAlgorithm):
         io.write(f"\tEnergyHistogram\n\t\tCalls: {_calls(scheduler)}\n\t\tBins: {self.n_bins} in [{self.lo}, {self.hi})\n")
         if self.blocks:
             io.write(f"\t\tBlocks: {self.blocks[0]} of chunk {self.blocks[1]}\n")
+        if self.mask:
+            io.write(f"\t\tMoments: {', '.join(self.moments)} within |x| <= {self.x_bound}\n")
 
 
 def _find_energy_histogram(simulation: Simulation) -> EnergyHistogram:
@@ -264,3 +384,11 @@ def callback_reweight_error(simulation: Simulation) -> np.ndarray:
     (EnergyHistogram.reweight(betas(), error=True); needs blocks=B).  The host waits for the queued snapshots."""
     eh = _find_energy_histogram(simulation)
     return np.stack([se for _, se in eh.reweight(eh.betas(), error=True)])
+
+
+def callback_reweight_moments(simulation: Simulation) -> np.ndarray:
+    """The kept moments [C, G] (rows in the order of ``EnergyHistogram.moments``) reweighted to the ladder's own betas
+    (EnergyHistogram.reweight_moments(betas())).  The host waits for the queued snapshots."""
+    eh = _find_energy_histogram(simulation)
+    out = eh.reweight_moments(eh.betas())
+    return np.stack([out[name] for name in eh.moments])

@@ -11,7 +11,7 @@ states g_b and the free energies f_k = -log Z_k solve
 which `wham` iterates in log space from f = 0, normalised to f_0 = 0, until max |delta f| < tol."""
 import numpy as np
 
-__all__ = ["bin_centres", "wham", "reweight", "outside_share"]
+__all__ = ["bin_centres", "wham", "reweight", "reweight_observable", "outside_share"]
 
 
 def bin_centres(lo, hi, n_bins):
@@ -102,6 +102,34 @@ def reweight(log_g, energies, betas):
     m2 = var + m1 * m1
     c = b.reshape(-1) ** 2 * var
     return tuple(v.reshape(b.shape) for v in (log_z, m1, m2, c))
+
+
+def reweight_observable(log_g, energies, betas, sums, counts):
+    """<o>(beta) at every beta of `betas` (a scalar or an array) of an observable that is no function of the energy, from its sums per
+    bin: sums[K, n_bins] = S_kb, the sum of o over the samples of row k that fell into bin b, and counts[K, n_bins] = n_kb.  The
+    microcanonical mean o_b = sum_k S_kb / sum_k n_kb is weighted with the density of states `wham` returns,
+
+        <o>(beta) = sum_b g_b exp(-beta E_b) o_b / sum_b g_b exp(-beta E_b),
+
+    the weights formed in log space.  Bins with sum_k n_kb = 0 (log g = -inf) take no part, in the numerator or the denominator; NaN
+    where no bin is left."""
+    lg = np.asarray(log_g, dtype=np.float64).reshape(-1)
+    e = np.asarray(energies, dtype=np.float64).reshape(-1)
+    b = np.asarray(betas, dtype=np.float64)
+    s = np.asarray(sums, dtype=np.float64)
+    n = np.asarray(counts, dtype=np.float64)
+    if s.ndim == 1:
+        s, n = s[None, :], n.reshape(1, -1)
+    if s.shape != n.shape or s.ndim != 2 or s.shape[1] != e.size or lg.size != e.size:
+        raise ValueError(f"reweight_observable: sums of shape {s.shape}, counts of shape {n.shape} for {e.size} energies and {lg.size} log g")
+    total = n.sum(axis=0)
+    live = (total > 0) & (lg > -np.inf)
+    if not np.any(live):
+        return np.full(b.shape, np.nan)
+    mean = s[:, live].sum(axis=0) / total[live]
+    a = lg[live][None, :] - np.outer(b.reshape(-1), e[live])
+    p = np.exp(a - _logsumexp(a, axis=1)[:, None])
+    return (p @ mean).reshape(b.shape)
 
 
 def outside_share(counts_with_tail_cells):

@@ -343,6 +343,15 @@ def _read_energy_histogram(met, eng, d, est) -> None:
         met.energy_histogram.set_state(d)
 
 
+def _write_energy_moments(met, eng, d, est) -> None:
+    if met.energy_histogram is not None:            # moments=...: the form, the counts, the sums per bin and the snapshot count (no field otherwise)
+        d.update(met.energy_histogram.state_moments())
+
+def _read_energy_moments(met, eng, d, est) -> None:
+    if "emom_counts" in d and met.energy_histogram is not None:      # behind the ladder: set_ladder clears the engine's accumulator
+        met.energy_histogram.set_state_moments(d)
+
+
 def _write_energy_histogram_blocks(met, eng, d, est) -> None:
     if met.energy_histogram is not None:            # blocks=B: the counts per jackknife block are the state the run goes on from
         d.update(met.energy_histogram.state_blocks())
@@ -378,7 +387,7 @@ _SECTIONS = ((_write_core, _read_core), (_write_counters, _read_counters), (_wri
              (_write_bridge, _read_bridge), (_write_bridge_blocks, _read_bridge_blocks), (_write_respacing, _read_respacing),
              (_write_annealing, _read_annealing), (_write_correlation, _read_correlation),
              (_write_correlation_blocks, _read_correlation_blocks), (_write_convergence, _read_convergence),
-             (_write_energy_histogram, _read_energy_histogram),
+             (_write_energy_histogram, _read_energy_histogram), (_write_energy_moments, _read_energy_moments),
              (_write_energy_histogram_blocks, _read_energy_histogram_blocks), (_write_estimator, _read_estimator))
 
 
