@@ -39,7 +39,8 @@ are printed beside the bridge estimates.
 --moments (with --reweight N) runs the TILTED well x^4 - 2 x^2 + x / 4 instead (a potential compiled at run time), whose wells are
 not equally deep, keeps the sums of x, x^2 and [x > 0] per energy bin on the device beside the counts
 (EnergyHistogram(..., moments=("x", "x2", "pos"), x_bound=4)) and prints <x>(beta), <x^2>(beta) and the occupancy of the right-hand
-well P(x > 0)(beta) on the same grid, each beside the quadrature: functions of the POSITION between the simulated temperatures.
+well P(x > 0)(beta) on the same grid, each beside the quadrature: functions of the POSITION between the simulated temperatures.  With
+--blocks B the sums per bin are kept per block of ladders as well, and the three curves are printed +- their jackknife standard error.
 """
 import argparse
 import os
@@ -185,8 +186,8 @@ def main(argv=None):
         ap.error("--blocks needs --free-energy or --reweight")
     if args.moments and not args.reweight:
         ap.error("--moments needs --reweight N")
-    if args.moments and (args.blocks is not None or args.free_energy):
-        ap.error("--moments: the moments per bin are not kept per jackknife block, and the quadrature beside --free-energy is the symmetric well's")
+    if args.moments and args.free_energy:
+        ap.error("--moments: the quadrature beside --free-energy is the symmetric well's")
     path = args.path or f"data/PT/particle_1d/DoubleWell/L{args.ladders}/seed{args.seed}"
     sim, left, energy, accept, hist = one_run(args, os.path.join(path, "exchange"), True)
     _, left_plain, energy_plain, _, _ = one_run(args, os.path.join(path, "plain"), False)
@@ -249,7 +250,15 @@ def main(argv=None):
             print("     beta       <e>               C                 log(Z / Z_0)")
             for b, e1, e2, c1, c2, z1, z2 in zip(grid, m1, q_m1, c, q_c, log_z, q_log_z - q_log_z0):
                 print(f"  {b:7.4f}   {e1:7.4f} | {e2:7.4f}   {c1:7.4f} | {c2:7.4f}   {z1:8.4f} | {z2:8.4f}")
-        if args.moments:
+        if args.moments and args.blocks:               # the sums per bin are kept per block too: every moment +- its jackknife se
+            mom = eh.reweight_moments(grid, error=True)
+            q_x, q_x2, q_pos = moments_by_quadrature(grid)
+            print(f"reweighted moments of the position, |x| <= {X_BOUND:g} ({int(eh.beyond_bound().sum())} binned samples beyond it): "
+                  f"WHAM +- jackknife se over {args.blocks} blocks | quadrature")
+            print("     beta       <x>                           <x^2>                         P(x > 0)")
+            for i, b in enumerate(grid):
+                print(f"  {b:7.4f}   " + "   ".join(f"{mom[k][0][i]:7.4f} +- {mom[k][1][i]:6.4f} | {q[i]:7.4f}" for k, q in (("x", q_x), ("x2", q_x2), ("pos", q_pos))))
+        elif args.moments:
             mom = eh.reweight_moments(grid)
             q_x, q_x2, q_pos = moments_by_quadrature(grid)
             print(f"reweighted moments of the position, |x| <= {X_BOUND:g} ({int(eh.beyond_bound().sum())} binned samples beyond it): WHAM | quadrature")

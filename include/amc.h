@@ -915,8 +915,8 @@ int  amc_set_energy_histogram_blocks(amc_handle *h, double lo, double hi, int n_
  * counts that do not ALL sum to n_snapshots * n_chains / G, for n_snapshots * n_chains / G >= 2^31, for a sum cell whose magnitude
  * exceeds (count of its bin) * 2^32, and for a POS cell that is negative or exceeds its count.
  * Lifetimes are the energy histograms': CLEARED by amc_set_ladder; ZEROED on the device, in stream order, by a respacing that is taken
- * (one that is not leaves the cells); kept by everything else, amc_anneal and amc_set_beta included.  amc_set_blocks does not touch
- * it: a form per jackknife block does not exist yet, and neither does one per temperature of a population annealing. */
+ * (one that is not leaves the cells); kept by everything else, amc_anneal and amc_set_beta included.  amc_set_blocks leaves a plain
+ * accumulator alone (a blocked one: "Moments per block" below); a form per temperature of a population annealing does not exist. */
 enum { AMC_EMOM_X = 1, AMC_EMOM_XX = 2, AMC_EMOM_POS = 4, AMC_EMOM_ALL = 7 };
 int  amc_energy_moments_accumulate(amc_handle *h, double lo, double hi, int n_bins, int mask, double x_bound);
 int  amc_energy_moments_fetch(amc_handle *h, uint64_t *counts, int64_t *sums, int64_t capacity_counts, int64_t capacity_sums,
@@ -924,6 +924,39 @@ int  amc_energy_moments_fetch(amc_handle *h, uint64_t *counts, int64_t *sums, in
                               uint64_t *n_snapshots, int reset);
 int  amc_set_energy_moments(amc_handle *h, double lo, double hi, int n_bins, int mask, double x_bound, const uint64_t *counts_or_null,
                             const int64_t *sums_or_null, uint64_t n_snapshots);
+
+/* Moments per energy bin per jackknife block (DESIGN.md section 3.17 "Moments per block"): the moments per bin with a set of cells per
+ * block of the partition (amc_set_blocks), so that a delete-one-block jackknife gives an error bar for <x>(beta), <x^2>(beta) and
+ * P(x > 0)(beta).  The form is opt-in: the three entries above do what they always did, and a handle that never calls the entries
+ * below allocates and launches what it always did, with or without a partition.
+ * amc_energy_moments_accumulate_blocks queues one pass in which chain i of local ladder l is counted and summed by the rule above into
+ * the set of block b(l).  It needs a partition (AMC_ERR_STATE without one).  The first call after a reset allocates and zeroes B sets of
+ * G * (n_bins + 4) + G * C * n_bins 64-bit words and fixes the form, "blocked under (B, C)"; it waits for the stream at that
+ * allocation and is stream-ordered otherwise.  More than AMC_EMOM_BLK_MAX_WORDS = 2^22 words (32 MiB) are AMC_ERR_BAD_ARG, as is all
+ * that amc_energy_moments_accumulate refuses.  The capacity rule is the plain one, (n_snapshots + 1) * (n_chains / G) < 2^31: it is
+ * conservative per block and keeps a later fold valid.  An accumulator's form is fixed while it stands: the plain entry on a blocked
+ * accumulator and the blocked entry on a plain one are AMC_ERR_STATE (amc_energy_moments_fetch with reset frees either), as is
+ * another (lo, hi, n_bins, mask, x_bound).  A refused first call leaves nothing allocated.
+ * amc_energy_moments_fetch_blocks waits and returns the LOCAL shard's cells, counts[(b * G + g) * (n_bins + 4) + cell] and
+ * sums[((b * G + g) * C + c) * n_bins + bin], *n_blocks = B, the form and *n_snapshots (from the first block that has a local
+ * ladder); a block without a local ladder is all zero, and every (b, g) row of counts sums to n_snapshots * (local ladders of block b).
+ * Shards add cell by cell.  The capacities count cells of all blocks; counts = sums = NULL returns the sizes and the form alone
+ * without waiting; reset != 0 frees the accumulator.  AMC_ERR_STATE unless a blocked accumulator stands.
+ * amc_energy_moments_fetch on a blocked accumulator returns the sum over its blocks: the integers a plain accumulator would hold.
+ * amc_set_energy_moments_blocks restores a blocked accumulator (checkpoints) under the partition set beforehand: n_blocks = B;
+ * counts = NULL, sums = NULL or n_snapshots = 0 clears; AMC_ERR_BAD_ARG for rows that do not ALL sum to n_snapshots * (local ladders
+ * of their block), for a sum cell its bin's count cannot hold (as amc_set_energy_moments), for n_blocks != B and for too many words;
+ * AMC_ERR_STATE without a partition.  amc_set_energy_moments replaces an accumulator of either form by a plain one.
+ * Lifetimes: CLEARED by amc_set_ladder; a respacing that is taken zeroes the words of EVERY block; a successful amc_set_blocks, with
+ * any arguments, FOLDS a standing blocked accumulator into a plain one -- exact integer sums on the device, in stream order (signed
+ * sums add as unsigned words modulo 2^64): nothing is lost, the form becomes plain. */
+#define AMC_EMOM_BLK_MAX_WORDS 4194304
+int  amc_energy_moments_accumulate_blocks(amc_handle *h, double lo, double hi, int n_bins, int mask, double x_bound);
+int  amc_energy_moments_fetch_blocks(amc_handle *h, uint64_t *counts, int64_t *sums, int64_t capacity_counts, int64_t capacity_sums,
+                                     int *n_blocks, int *n_groups, int *n_bins, int *n_cols, double *lo, double *hi, int *mask,
+                                     double *x_bound, uint64_t *n_snapshots, int reset);
+int  amc_set_energy_moments_blocks(amc_handle *h, double lo, double hi, int n_bins, int mask, double x_bound, const uint64_t *counts_or_null,
+                                   const int64_t *sums_or_null, int n_blocks, uint64_t n_snapshots);
 
 int  amc_sync(amc_handle *h);
 /* hipStream_t the handle launches on (for event timing / graph capture by the host). */

@@ -21,7 +21,8 @@ from .exchange import (ReplicaExchange, callback_exchange_acceptance, callback_r
                        callback_heat_capacity_error)
 from .correlation import Autocorrelation, callback_rho, callback_tau_int, callback_tau_int_error, rho_from_records, tau_from_rho
 from .convergence import Convergence, callback_rhat, rhat_from_records, tau_batch_from_records, variances_from_records
-from .energy_histogram import EnergyHistogram, callback_reweight_error, callback_reweight_moments
+from .energy_histogram import (EnergyHistogram, callback_reweight_error, callback_reweight_moments,
+                               callback_reweight_moments_error)
 from . import reweighting
 from .annealing import ANNEAL_SEARCH_STATUS, PopulationAnnealing, callback_anneal_beta, callback_anneal_log_z, callback_rho_t
 from .storage import StoreHistogram, StoreSnapshots, checkpoint, restore
@@ -44,7 +45,7 @@ __all__ = [
     "callback_rung_window_acceptance", "callback_log_z", "callback_heat_capacity", "callback_log_z_error", "callback_heat_capacity_error",
     "Autocorrelation", "callback_rho", "callback_tau_int", "callback_tau_int_error", "rho_from_records", "tau_from_rho",
     "Convergence", "callback_rhat", "rhat_from_records", "tau_batch_from_records", "variances_from_records",
-    "EnergyHistogram", "callback_reweight_error", "callback_reweight_moments", "reweighting",
+    "EnergyHistogram", "callback_reweight_error", "callback_reweight_moments", "callback_reweight_moments_error", "reweighting",
     "ANNEAL_SEARCH_STATUS", "PopulationAnnealing", "callback_anneal_beta", "callback_anneal_log_z", "callback_rho_t",
     "DAT", "TXT", "StoreBackups", "StoreLastFrames", "StoreTrajectories",
     "Action", "AriannaSystem", "Policy", "CustomPotential", "Displacement", "Move", "ParticleChains", "ScaledGaussian", "ScriptAction", "ScriptPolicy", "StandardGaussian", "potential",

@@ -215,6 +215,9 @@ def load() -> C.CDLL:
         "amc_energy_moments_accumulate": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double]),
         "amc_energy_moments_fetch": (C.c_int, [H, u64p, i64p, C.c_int64, C.c_int64, ip, ip, ip, dp, dp, ip, dp, u64p, C.c_int]),
         "amc_set_energy_moments": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, u64p, i64p, C.c_uint64]),
+        "amc_energy_moments_accumulate_blocks": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double]),
+        "amc_energy_moments_fetch_blocks": (C.c_int, [H, u64p, i64p, C.c_int64, C.c_int64, ip, ip, ip, ip, dp, dp, ip, dp, u64p, C.c_int]),
+        "amc_set_energy_moments_blocks": (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, u64p, i64p, C.c_int, C.c_uint64]),
         "amc_set_tracking": (C.c_int, [H, C.c_int]),
         "amc_download_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
         "amc_upload_labels": (C.c_int, [H, C.POINTER(C.c_uint8)]),
@@ -1024,7 +1027,8 @@ class HipEngine:
     def set_blocks(self, n_blocks: int, chunk: int = 0) -> None:
         """Keep the bridge sums and the time correlation per block of ladders, block of ladder l = (l_global div chunk) mod n_blocks
         (amc_set_blocks); ``n_blocks`` 0 turns the partition off, ``chunk`` 0 asks for the default.  Clears the bridge accumulator and
-        the mark.  ``bridge_fetch`` / ``corr_fetch`` go on returning the merged records, bit for bit those of a handle without one."""
+        the mark; energy histograms and moments per bin kept per block are folded into plain accumulators, nothing is lost.
+        ``bridge_fetch`` / ``corr_fetch`` go on returning the merged records, bit for bit those of a handle without one."""
         _check(self._lib.amc_set_blocks(self._h, int(n_blocks), int(chunk)))
 
     def bridge_fetch_blocks(self, reset: bool = False):
@@ -1104,6 +1108,43 @@ class HipEngine:
         if int(n_snapshots) < 0:
             raise AmcError("set_energy_histogram_blocks: n_snapshots < 0")
         _check(self._lib.amc_set_energy_histogram_blocks(self._h, float(lo), float(hi), int(n_bins), _ptr(c), int(c.shape[0]), int(n_snapshots)))
+
+    # -- moments per energy bin per jackknife block (include/amc.h; DESIGN.md section 3.17 "Moments per block") ----------------
+    def energy_moments_accumulate_blocks(self, lo: float, hi: float, n_bins: int, mask: int, x_bound: float) -> None:
+        """``energy_moments_accumulate`` with a set of cells per block of the partition (amc_energy_moments_accumulate_blocks): needs
+        ``set_blocks``; the first call after a reset fixes the form and waits for the stream once."""
+        _check(self._lib.amc_energy_moments_accumulate_blocks(self._h, float(lo), float(hi), int(n_bins), int(mask), float(x_bound)))
+
+    def energy_moments_fetch_blocks(self, reset: bool = False):
+        """(counts[B, G, n_bins + 4] uint64, sums[B, G, C, n_bins] int64, n_snapshots, (lo, hi, n_bins, mask, x_bound)) of this shard's
+        blocked accumulator (amc_energy_moments_fetch_blocks); a block without a local ladder is all zero, shards add cell by cell.
+        An AmcError unless a blocked accumulator stands.  ``reset`` frees the accumulator.  Synchronises."""
+        nk, ng, nb, nc, lo, hi = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        mask, bound, count = C.c_int(0), C.c_double(0.0), C.c_uint64(0)
+        sizes = (C.byref(nk), C.byref(ng), C.byref(nb), C.byref(nc), C.byref(lo), C.byref(hi), C.byref(mask), C.byref(bound), C.byref(count))
+        _check(self._lib.amc_energy_moments_fetch_blocks(self._h, None, None, 0, 0, *sizes, 0))      # the sizes alone: nothing waits
+        counts = np.empty((nk.value, ng.value, nb.value + 4), dtype=np.uint64)
+        sums = np.empty((nk.value, ng.value, nc.value, nb.value), dtype=np.int64)
+        _check(self._lib.amc_energy_moments_fetch_blocks(self._h, _ptr(counts), _ptr(sums), int(counts.size), int(sums.size), *sizes, int(bool(reset))))
+        return counts, sums, int(count.value), (lo.value, hi.value, nb.value, mask.value, bound.value)
+
+    def set_energy_moments_blocks(self, lo: float = 0.0, hi: float = 0.0, n_bins: int = 0, mask: int = 0, x_bound: float = 0.0, counts=None,
+                                  sums=None, n_snapshots: int = 0) -> None:
+        """Restore the blocked accumulator from ``energy_moments_fetch_blocks``'s cells, count and form (amc_set_energy_moments_blocks;
+        checkpoints); ``counts=None``, ``sums=None`` or ``n_snapshots=0`` clears it.  The partition is set beforehand."""
+        if counts is None or sums is None or int(n_snapshots) == 0:
+            _check(self._lib.amc_set_energy_moments_blocks(self._h, 0.0, 0.0, 0, 0, 0.0, None, None, 0, 0))
+            return
+        c, s = np.ascontiguousarray(counts, dtype=np.uint64), np.ascontiguousarray(sums, dtype=np.int64)
+        G, cols = self._rungs(), bin(int(mask) & 0xFFFFFFFF).count("1")
+        per_c, per_s = G * (int(n_bins) + 4), G * cols * int(n_bins)
+        if c.ndim < 1 or c.shape[0] < 1 or s.ndim < 1 or s.shape[0] != c.shape[0] or c.size != c.shape[0] * per_c or s.size != c.shape[0] * per_s:
+            raise AmcError(f"set_energy_moments_blocks: {c.size} counts and {s.size} sums, a block of {G} rows of {int(n_bins)} bins and {cols} "
+                           f"columns takes {per_c} and {per_s}")
+        if int(n_snapshots) < 0:
+            raise AmcError("set_energy_moments_blocks: n_snapshots < 0")
+        _check(self._lib.amc_set_energy_moments_blocks(self._h, float(lo), float(hi), int(n_bins), int(mask), float(x_bound), _ptr(c), _ptr(s),
+                                                       int(c.shape[0]), int(n_snapshots)))
 
     # -- walker tracking (include/amc.h; DESIGN.md section 3.13 "Walker tracking") ----------------
     def set_tracking(self, on: bool = True) -> None:

@@ -2,7 +2,8 @@
 // energy_histogram_kernel that, beside the count of every cell, adds x, x^2 and [x > 0] of the chains of a bin into integer sums per
 // (group, column, bin) -- the microcanonical means that multiple-histogram reweighting needs for <x>, <x^2> and the occupancy of a well
 // at any beta.  Every summand is an integer multiple of a quantum fixed by x_bound (kind Q of section 3.8), added as a signed 64-bit
-// integer: the same on any grid, in any order, on any split.  The plain kernel zeroes the cells behind a respacing that was taken.
+// integer: the same on any grid, in any order, on any split.  energy_moments_blocks_kernel<POT> is the same pass with a set of cells
+// per jackknife block ("Moments per block").  The plain kernel zeroes the cells behind a respacing that was taken.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
 #pragma once
 
@@ -133,9 +134,62 @@ __global__ __launch_bounds__(AMC_BLOCK) void energy_moments_kernel(const EmomArg
     }
 }
 
+// Per jackknife block (amc_energy_moments_accumulate_blocks): energy_moments_kernel's body on the traversal of
+// energy_histogram_blocks_kernel.  The grid is a multiple of B and HIP block k serves jackknife block b = k mod B alone, over ALL local
+// ladders in one launch, so the LDS array stays the cells of ONE jackknife block -- the same words, the same threshold, the same
+// occupancy -- and is flushed into that block's set; beyond the threshold every deposit is a 64-bit global atomic into the block's
+// set.  The accumulator is B sets of the plain layout, a.counts = set 0: set b begins b (count_cells + sum_cells) words behind it, its
+// sums count_cells words further.  A thread keeps its group (blk::walk_begin), so both bases are formed once; four loads in flight per
+// lane over the flattened (chunk, trip) sequence.  A u32 count cell holds at most blk::lane_bound x AMC_BLOCK chains of one pass: the
+// host refuses a launch that could reach 2^32.
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void energy_moments_blocks_kernel(const EmomArgs a, const blk::Part part)
+{
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
+    __shared__ unsigned long long s_words[EHIST_LDS_CELLS / 2];
+    const int row = a.n_bins + 4, count_cells = a.n_groups * row, sum_cells = a.n_groups * a.n_cols * a.n_bins;
+    const bool lds = (int64_t)count_cells + 2 * (int64_t)sum_cells <= EHIST_LDS_CELLS;
+    unsigned long long* s_sums = s_words;
+    unsigned int* s_counts = reinterpret_cast<unsigned int*>(s_words + (lds ? sum_cells : 0));
+    if (lds) {
+        for (int i = threadIdx.x; i < sum_cells; i += AMC_BLOCK) s_sums[i] = 0ull;
+        for (int i = threadIdx.x; i < count_cells; i += AMC_BLOCK) s_counts[i] = 0u;
+    }
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier: the cells are cleared too)
+
+    EmomArgs mine = a;                                         // ... with the set of this HIP block's jackknife block
+    mine.counts = a.counts + (int64_t)((int)blockIdx.x % part.n_blocks) * ((int64_t)count_cells + sum_cells);
+    mine.sums = mine.counts + count_cells;
+    blk::Walk w;
+    const int g = blk::walk_begin(w, part, a.n_groups, (int)gridDim.x, AMC_BLOCK, (int)blockIdx.x, (int)threadIdx.x, 0, a.n_chains / a.n_groups);
+    const int count_base = g * row, sum_base = g * a.n_cols * a.n_bins;
+    for (;;) {
+        const int64_t l0 = blk::walk_next(w), l1 = blk::walk_next(w), l2 = blk::walk_next(w), l3 = blk::walk_next(w);
+        if (l3 < 0) {                                             // fewer than four are left: one by one
+            const int64_t rest[3] = {l0, l1, l2};
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (rest[j] >= 0) emom_count<POT>(mine, a.x[rest[j] * a.n_groups + g], s_math, lds, s_counts, s_sums, count_base, sum_base);
+            break;
+        }
+        const real_t x0 = a.x[l0 * a.n_groups + g], x1 = a.x[l1 * a.n_groups + g], x2 = a.x[l2 * a.n_groups + g], x3 = a.x[l3 * a.n_groups + g];
+        emom_count<POT>(mine, x0, s_math, lds, s_counts, s_sums, count_base, sum_base);
+        emom_count<POT>(mine, x1, s_math, lds, s_counts, s_sums, count_base, sum_base);
+        emom_count<POT>(mine, x2, s_math, lds, s_counts, s_sums, count_base, sum_base);
+        emom_count<POT>(mine, x3, s_math, lds, s_counts, s_sums, count_base, sum_base);
+    }
+    if (lds) {
+        __syncthreads();
+        flush_cells(s_counts, mine.counts, count_cells);
+        for (int i = threadIdx.x; i < sum_cells; i += AMC_BLOCK)
+            if (s_sums[i]) atomicAdd(&mine.sums[i], s_sums[i]);
+    }
+}
+
 #if AMC_PLAIN_KERNELS
 // Behind ladder_respace_kernel on the stream, beside ehist_respaced_kernel: a respacing that was taken zeroes the count cells and the sum
-// cells (one allocation, `words` 64-bit words) -- sums taken at other beta belong to another ladder.  Any other status leaves them.
+// cells (one allocation, `words` 64-bit words; every block's set, of a blocked accumulator) -- sums taken at other beta belong to another
+// ladder.  Any other status leaves them.
 AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void emom_respaced_kernel(unsigned long long* words_ptr, int words, const unsigned long long* rec)
 {
     if (rec[RESPACE_STATUS] != 0ull) return;

@@ -506,6 +506,7 @@ int amc_set_blocks(amc_handle* h, int n_blocks, int64_t chunk)
     AMC_HIP(hipSetDevice(h->device));
     // energy histograms kept under the partition that goes: their blocks' rows are added up on the stream, nothing is lost
     AMC_TRY(ehist_fold(h));
+    AMC_TRY(emom_fold(h));          // ... and the moments per bin's sets
     // one full block-width of contiguous chains: every lane of a HIP block has a ladder of the chunk, in one trip
     if (n_blocks && chunk == 0) chunk = std::max(1, AMC_BLOCK / pass_groups(h));
     h->blocks.n_blocks = n_blocks;

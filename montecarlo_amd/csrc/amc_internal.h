@@ -15,7 +15,8 @@
 //                       the partition itself, amc_set_blocks, and amc_bridge_fetch_blocks are with the bridge sums in amc_exchange.hip)
 //   amc_ehist.hip       energy histograms per group (amc_energy_histogram_accumulate / _fetch, amc_set_energy_histogram; per jackknife
 //                       block: amc_energy_histogram_accumulate_blocks / _fetch_blocks, amc_set_energy_histogram_blocks)
-//   amc_emom.hip        moments per energy bin (amc_energy_moments_accumulate / _fetch, amc_set_energy_moments)
+//   amc_emom.hip        moments per energy bin (amc_energy_moments_accumulate / _fetch, amc_set_energy_moments; per jackknife block:
+//                       amc_energy_moments_accumulate_blocks / _fetch_blocks, amc_set_energy_moments_blocks)
 //   amc_chainstats.hip  convergence per group: running sums per chain and their sums by group (amc_chain_stats_accumulate ..
 //                       amc_chain_stats_clear)
 //   amc_reduce.hip      callback reductions (tickets, amc_reduce*, amc_sweep_reduce_begin) and record arithmetic
@@ -295,11 +296,15 @@ static inline void ehist_release(EhistState& s)
 
 // Moments per energy bin (amc_emom.hip; DESIGN.md section 3.17 "Moments per bin"): an accumulator of its own beside the energy
 // histograms', allocated by the first amc_energy_moments_accumulate after a reset -- a handle that never calls it has none.  It stands
-// exactly while d_emom != nullptr, and its form (bins, mask, bound) is fixed while it stands.
+// exactly while d_emom != nullptr, and its form (bins, mask, bound) is fixed while it stands: plain (blocks == 0), or blocked under the
+// partition it was begun with (amc_energy_moments_accumulate_blocks: a set per jackknife block); amc_set_blocks folds a blocked one
+// into a plain one.
 struct EmomState {
-    unsigned long long* d_emom = nullptr;       // [groups][n_bins + 4] counts, then [groups][cols][n_bins] signed 64-bit sums: one allocation
+    unsigned long long* d_emom = nullptr;       // one set: [groups][n_bins + 4] counts, then [groups][cols][n_bins] signed 64-bit sums; one
+                                                // allocation of `blocks or 1` sets
     int n_bins = 0;
     int groups = 0;                             // G when it was begun (amc_set_ladder clears it)
+    int blocks = 0;                             // B of a blocked accumulator (the handle's partition while it stands); 0: plain
     int mask = 0, cols = 0;                     // the columns kept (AMC_EMOM_*), C = popcount(mask)
     double lo = 0.0, hi = 0.0, x_bound = 0.0;
     uint64_t n_snapshots = 0;                   // passes queued since the cells were last known to be zero: the capacity check's count (a
@@ -559,6 +564,7 @@ AMC_INTERNAL int ehist_fold(amc_handle* h);
 // the moments per energy bin (amc_emom.hip): freed with the ladder, zeroed on the stream behind a respacing that is taken, as above
 AMC_INTERNAL int emom_clear(amc_handle* h);
 AMC_INTERNAL int emom_respaced(amc_handle* h);
+AMC_INTERNAL int emom_fold(amc_handle* h);
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };

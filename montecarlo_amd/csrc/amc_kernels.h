@@ -29,7 +29,8 @@
 //   amc_ehist.h        energy histograms per group: energy_histogram_kernel, energy_histogram_blocks_kernel (a set of rows per
 //                      jackknife block), the cells zeroed behind a respacing, the blocks' rows folded into one set
 //   amc_emom.h         moments per energy bin: energy_moments_kernel (the energy histograms' pass with integer sums of x, x^2 and
-//                      [x > 0] per bin beside the counts), the deposit rule the host compiles too
+//                      [x > 0] per bin beside the counts), energy_moments_blocks_kernel (a set of cells per jackknife block), the
+//                      deposit rule the host compiles too
 //   amc_chainstats.h   convergence per group: running sums per chain (chain_stats_add_kernel) and their sums by group
 #pragma once
 

@@ -15,7 +15,8 @@ leave-one-out counts.
 With ``moments=("x", "x2", "pos")`` and ``x_bound=...`` the pass also adds x, x^2 and [x > 0] of the chains of every bin into integer
 sums on the device (DESIGN.md section 3.17 "Moments per bin"; include/amc.h amc_energy_moments_accumulate), and
 ``reweight_moments(betas)`` gives <x>, <x^2> and the occupancy of the right-hand well at any beta: functions of the position, which
-the counts alone cannot give.
+the counts alone cannot give.  Together with ``blocks=B`` the sums are kept per jackknife block too (DESIGN.md section 3.17 "Moments
+per block"), and ``reweight_moments(betas, error=True)`` returns every value with its standard error.
 """
 from __future__ import annotations
 
@@ -55,7 +56,8 @@ class EnergyHistogram(AriannaAlgorithm):
     ``moments=("x", "x2", "pos")`` (any of the three) with ``x_bound=...``: the pass keeps, per bin, the sums of x, x^2 and [x > 0]
     beside the counts, in an accumulator of their own; ``moment_sums()``, ``microcanonical()``, ``reweight_moments(betas)`` return
     them.  A chain of a bin with |x| > x_bound (or NaN) is counted in a fourth cell outside the bins, "x beyond x_bound", which
-    ``max_outside`` covers too.  Not available together with ``blocks``: the moments are not kept per jackknife block yet."""
+    ``max_outside`` covers too.  Together with ``blocks=B`` counts and sums are kept per jackknife block (``counts_blocks()``,
+    ``moment_sums_blocks()``), and ``reweight_moments(betas, error=True)`` gives {name: (value, se)}."""
 
     def __init__(self, chains, dependencies=None, lo=None, hi=None, n_bins=None, max_outside=0.0, blocks=None, block_chunk=None, path=None,
                  moments=None, x_bound=None, **extras):
@@ -74,9 +76,6 @@ class EnergyHistogram(AriannaAlgorithm):
             names = (moments,) if isinstance(moments, str) else tuple(moments)
             if not names or any(n not in MOMENTS for n in names) or len(set(names)) != len(names):
                 raise ValueError(f"EnergyHistogram: moments = {moments!r}: need one or more of {tuple(MOMENTS)}, each once")
-            if blocks is not None:
-                raise ValueError("EnergyHistogram: moments together with blocks: the moments per bin are not kept per jackknife block yet "
-                                 "(no error bars for reweight_moments); give one of the two")
             if x_bound is None:
                 raise ValueError("EnergyHistogram: moments need x_bound, the largest |x| a binned chain may have (it fixes the sums' quanta)")
             if not (np.isfinite(x_bound) and 2.0 ** -500 <= float(x_bound) < 2.0 ** 500):
@@ -96,7 +95,7 @@ class EnergyHistogram(AriannaAlgorithm):
             block_chunk = self.metropolis.blocks[1]      # (another algorithm of these chains set the chunk: one partition per engine)
         self.blocks = jackknife.check_blocks("EnergyHistogram", blocks, block_chunk, len(chains) // groups, groups)
         if self.blocks:
-            if not hasattr(self.metropolis.engine, "energy_histogram_accumulate_blocks"):
+            if not hasattr(self.metropolis.engine, "energy_moments_accumulate_blocks" if self.mask else "energy_histogram_accumulate_blocks"):
                 raise ValueError("EnergyHistogram: this engine keeps no energy histograms per block (streams > 1 is not supported)")
             jackknife.ask_blocks("EnergyHistogram", self.metropolis, self.blocks)
 
@@ -116,7 +115,10 @@ class EnergyHistogram(AriannaAlgorithm):
     def make_step(self, simulation: Simulation) -> None:
         if self.blocks:                         # (here and not in initialise: every algorithm's set_ladder lies behind us by now)
             jackknife.use_blocks(self.metropolis, self.blocks)
-            self.metropolis.engine.energy_histogram_accumulate_blocks(self.lo, self.hi, self.n_bins)
+            if self.mask:
+                self.metropolis.engine.energy_moments_accumulate_blocks(self.lo, self.hi, self.n_bins, self.mask, self.x_bound)
+            else:
+                self.metropolis.engine.energy_histogram_accumulate_blocks(self.lo, self.hi, self.n_bins)
         elif self.mask:
             self.metropolis.engine.energy_moments_accumulate(self.lo, self.hi, self.n_bins, self.mask, self.x_bound)
         else:
@@ -178,10 +180,23 @@ class EnergyHistogram(AriannaAlgorithm):
         """(counts[B, G, n_bins + 3], n_snapshots) of this shard; zeros while nothing has been accumulated."""
         if not self.blocks:
             raise ValueError("EnergyHistogram: counts per block need blocks=B")
+        if self.mask:                           # (the moments' pass counts too: the first n_bins + 3 cells of every row)
+            counts, _, n_snap = self._local_moments_blocks()
+            return np.ascontiguousarray(counts[:, :, :self.n_bins + 3]), n_snap
         if self._local()[1] == 0:               # (nothing stands, or other bins: _local has said so)
             return np.zeros((self.blocks[0], self._groups(), self.n_bins + 3), dtype=np.uint64), 0
         counts, n_snap, _ = self.metropolis.engine.energy_histogram_fetch_blocks(reset=False)
         return counts, n_snap
+
+    def _local_moments_blocks(self):
+        """(counts[B, G, n_bins + 4], sums[B, G, C, n_bins] int64, n_snapshots) of this shard; zeros while nothing has been accumulated."""
+        if not self.blocks:
+            raise ValueError("EnergyHistogram: moments per block need blocks=B")
+        if self._local_moments()[2] == 0:       # (nothing stands, or another form: _local_moments has said so)
+            B, G = self.blocks[0], self._groups()
+            return np.zeros((B, G, self.n_bins + 4), dtype=np.uint64), np.zeros((B, G, len(self.moments), self.n_bins), dtype=np.int64), 0
+        counts, sums, n_snap, _ = self.metropolis.engine.energy_moments_fetch_blocks(reset=False)
+        return counts, sums, n_snap
 
     def counts_blocks(self) -> np.ndarray:
         """counts[B, G, n_bins + 3] (uint64) of ALL ranks per jackknife block: blocks are functions of the global ladder index, so the
@@ -225,10 +240,12 @@ class EnergyHistogram(AriannaAlgorithm):
         counts = self._checked_counts()
         return reweighting.wham(counts[:, :self.n_bins], self.betas(), self.energies(), tol=tol, max_iter=max_iter)
 
-    def _jackknife(self, pick, tol=1e-12, max_iter=100000):
+    def _jackknife(self, pick, tol=1e-12, max_iter=100000, with_sums=False):
         """(theta, se) of ``pick(log_g, f)`` (a flat Float64 array): theta from the counts of all blocks -- the bits the call without
         ``error`` gives --, se from the B leave-one-out replicates, each the whole of WHAM on its own counts, started from the full
-        solution.  The ``max_outside`` check is the total's; a replicate that WHAM cannot solve raises, naming the block."""
+        solution.  ``with_sums``: ``pick(log_g, f, counts[G, n_bins], sums[G, C, n_bins])`` with the replicate's own counts and moment
+        sums (Float64, in the columns' quanta), exact leave-one-out integers both.  The ``max_outside`` check is the total's; a
+        replicate that WHAM cannot solve raises, naming the block."""
         if not self.blocks:
             raise ValueError("EnergyHistogram: error=True needs blocks=B (the counts per jackknife block)")
         self._checked_counts()                                          # (the total: the same refusals as without error)
@@ -243,14 +260,21 @@ class EnergyHistogram(AriannaAlgorithm):
             if np.any(rest.sum(axis=1) == 0) or not reweighting._connected(rest > 0):
                 raise ValueError(f"EnergyHistogram: without block {b} the rungs' histograms no longer connect (a row is empty or shares no "
                                  "bin with the others): the replicate's free energies are undetermined; more snapshots or fewer blocks")
+        arrays = [blocks]
+        if with_sums:
+            arrays.append(self._moment_integers_blocks())
+            q = self._quanta()
+        first = [True]
 
-        def fn(counts):
-            if counts is total or np.array_equal(counts, total):
-                return pick(log_g, f)
+        def fn(counts, sums=None):
+            more = () if sums is None else (counts[:, :n], sums.astype(np.float64) * q[None, :, None])
+            if first[0]:                        # (jackknife_integers gives the total first: the full solution, solved above)
+                first[0] = False
+                return pick(log_g, f, *more)
             lg, fr, _ = reweighting.wham(counts[:, :n], betas, energies, tol=tol, max_iter=max_iter, f0=f)
-            return pick(lg, fr)
+            return pick(lg, fr, *more)
 
-        return jackknife.jackknife_counts(blocks, fn)
+        return jackknife.jackknife_integers(arrays, fn)
 
     def density_of_states(self, error=False, **kw):
         """(energies[n_bins], log_g[n_bins]): the bin centres and the WHAM density of states (-inf where no rung has a count), on the
@@ -286,9 +310,22 @@ class EnergyHistogram(AriannaAlgorithm):
         two halves of their two's complement, like the counts, and are put together modulo 2^64: exact.  The host waits for the
         queued snapshots."""
         k = self._all_ranks(self._local_moments()[1].view(np.uint64)).view(np.int64)
+        return k.astype(np.float64) * self._quanta()[None, :, None]
+
+    def _quanta(self) -> np.ndarray:
+        """The quantum of every kept column, in column order."""
         quanta = emom_quanta(self.x_bound)
-        q = np.array([quanta[MOMENTS[n]] for n in self.moments], dtype=np.float64)
-        return k.astype(np.float64) * q[None, :, None]
+        return np.array([quanta[MOMENTS[n]] for n in self.moments], dtype=np.float64)
+
+    def _moment_integers_blocks(self) -> np.ndarray:
+        """k[B, G, C, n_bins] (int64) of ALL ranks: the device's integer sums per jackknife block, the halves of ``moment_sums``."""
+        return self._all_ranks(np.ascontiguousarray(self._local_moments_blocks()[1]).view(np.uint64)).view(np.int64)
+
+    def moment_sums_blocks(self) -> np.ndarray:
+        """S[B, G, C, n_bins] (Float64) of ALL ranks per jackknife block: ``moment_sums()`` of the ladders of every block (blocks are
+        functions of the global ladder index, so the shards add cell by cell).  Needs ``blocks=B``; the integers behind it sum over B
+        to those behind ``moment_sums()``."""
+        return self._moment_integers_blocks().astype(np.float64) * self._quanta()[None, None, :, None]
 
     def microcanonical(self):
         """(energies[n_bins], o[C, n_bins]): the mean of every observable over all samples of a bin, sum_g S_gb / sum_g n_gb; NaN where
@@ -298,9 +335,22 @@ class EnergyHistogram(AriannaAlgorithm):
         with np.errstate(invalid="ignore", divide="ignore"):
             return self.energies(), np.where(n[None, :] > 0, s / n[None, :], np.nan)
 
-    def reweight_moments(self, betas, **kw) -> dict:
+    def reweight_moments(self, betas, error=False, **kw) -> dict:
         """{name: <o>(beta)} for every kept moment ("x", "x2", "pos") at every beta of ``betas`` (reweighting.reweight_observable with
-        WHAM's density of states), from the ladder as it stands at fetch time."""
+        WHAM's density of states), from the ladder as it stands at fetch time.  ``error=True`` (needs ``blocks=B``): {name: (value,
+        se)}, the values those of ``error=False``, se the delete-one-block jackknife: every replicate is the whole of WHAM on its
+        leave-one-out counts, followed by reweight_observable with its leave-one-out sums and counts."""
+        if not self.mask:
+            raise ValueError("EnergyHistogram: the moments per bin need moments=(...) and x_bound")
+        if error:
+            b = np.asarray(betas, dtype=np.float64)
+            energies, C = self.energies(), len(self.moments)
+
+            def pick(lg, f, counts, sums):
+                return np.concatenate([np.ravel(reweighting.reweight_observable(lg, energies, b, sums[:, c, :], counts)) for c in range(C)])
+
+            theta, se = self._jackknife(pick, with_sums=True, **kw)
+            return {name: (t.reshape(b.shape), e.reshape(b.shape)) for name, t, e in zip(self.moments, np.split(theta, C), np.split(se, C))}
         counts = self._checked_counts()[:, :self.n_bins]
         log_g = reweighting.wham(counts, self.betas(), self.energies(), **kw)[0]
         sums = self.moment_sums()
@@ -343,7 +393,7 @@ class EnergyHistogram(AriannaAlgorithm):
 
     def state_blocks(self) -> dict:
         """The counts per block (storage.py's section behind the ladder and the partition); nothing without blocks or snapshots."""
-        if not self.blocks or self.metropolis.blocks_on != self.blocks:
+        if self.mask or not self.blocks or self.metropolis.blocks_on != self.blocks:      # (with moments: state_moments_blocks)
             return {}
         counts, n_snap = self._local_blocks()
         if not n_snap:
@@ -351,6 +401,8 @@ class EnergyHistogram(AriannaAlgorithm):
         return dict(ehist_blocks=np.array(self.blocks, dtype=np.int64), ehist_block_counts=counts, ehist_block_snapshots=np.uint64(n_snap))
 
     def set_state_blocks(self, d) -> None:
+        if self.mask:                           # (the moments' accumulator holds the counts: set_state_moments_blocks)
+            return
         if "ehist_block_counts" not in d:
             if self.blocks and "ehist_counts" in d and int(d["ehist_snapshots"]):
                 raise ValueError("checkpoint holds energy histograms without counts per block, this EnergyHistogram asks for blocks")
@@ -363,6 +415,34 @@ class EnergyHistogram(AriannaAlgorithm):
         jackknife.use_blocks(self.metropolis, self.blocks)
         self.metropolis.engine.set_energy_histogram_blocks(self.lo, self.hi, self.n_bins, np.asarray(d["ehist_block_counts"], dtype=np.uint64),
                                                            int(d["ehist_block_snapshots"]))
+
+    def state_moments_blocks(self) -> dict:
+        """The moments per block (storage.py's section behind the ladder and the partition): the partition, counts and sums per block
+        and the snapshot count; nothing without moments, blocks or snapshots."""
+        if not self.mask or not self.blocks or self.metropolis.blocks_on != self.blocks:
+            return {}
+        counts, sums, n_snap = self._local_moments_blocks()
+        if not n_snap:
+            return {}
+        return dict(emom_blocks=np.array(self.blocks, dtype=np.int64), emom_block_counts=counts, emom_block_sums=sums,
+                    emom_block_snapshots=np.uint64(n_snap))
+
+    def set_state_moments_blocks(self, d) -> None:
+        if not self.mask:
+            return
+        if "emom_block_counts" not in d:
+            if self.blocks and "emom_counts" in d and int(d["emom_snapshots"]):
+                raise ValueError("checkpoint holds moments per bin without cells per block, this EnergyHistogram asks for blocks")
+            return
+        if not self.blocks:                     # (set_state_moments has restored their sum: the run goes on with a plain accumulator)
+            return
+        if tuple(int(v) for v in d["emom_blocks"]) != tuple(self.blocks):
+            raise ValueError(f"checkpoint holds moments per bin under the partition {tuple(int(v) for v in d['emom_blocks'])}, this run asks "
+                             f"for {tuple(self.blocks)}")
+        jackknife.use_blocks(self.metropolis, self.blocks)
+        self.metropolis.engine.set_energy_moments_blocks(self.lo, self.hi, self.n_bins, self.mask, self.x_bound,
+                                                         np.asarray(d["emom_block_counts"], dtype=np.uint64),
+                                                         np.asarray(d["emom_block_sums"], dtype=np.int64), int(d["emom_block_snapshots"]))
 
     def write_algorithm(self, io, scheduler) -> None:
         io.write(f"\tEnergyHistogram\n\t\tCalls: {_calls(scheduler)}\n\t\tBins: {self.n_bins} in [{self.lo}, {self.hi})\n")
@@ -392,3 +472,12 @@ def callback_reweight_moments(simulation: Simulation) -> np.ndarray:
     eh = _find_energy_histogram(simulation)
     out = eh.reweight_moments(eh.betas())
     return np.stack([out[name] for name in eh.moments])
+
+
+def callback_reweight_moments_error(simulation: Simulation) -> np.ndarray:
+    """The jackknife standard errors [C, G] of the kept moments (rows in the order of ``EnergyHistogram.moments``) reweighted to the
+    ladder's own betas (EnergyHistogram.reweight_moments(betas(), error=True); needs blocks=B).  The host waits for the queued
+    snapshots."""
+    eh = _find_energy_histogram(simulation)
+    out = eh.reweight_moments(eh.betas(), error=True)
+    return np.stack([out[name][1] for name in eh.moments])

@@ -12,7 +12,8 @@ import numpy as np
 
 from ._capi import AMC_MAX_JK_BLOCKS, AMC_XSUM_WORDS, xsum_merge, xsum_round
 
-__all__ = ["block_counts", "check_blocks", "default_chunk", "jackknife", "jackknife_counts", "leave_one_out", "use_blocks"]
+__all__ = ["block_counts", "check_blocks", "default_chunk", "jackknife", "jackknife_counts", "jackknife_integers", "leave_one_out",
+           "leave_one_out_integers", "use_blocks"]
 
 
 def default_chunk(n_groups: int) -> int:
@@ -50,7 +51,7 @@ def check_blocks(who: str, blocks, chunk, n_ladders: int, n_groups: int):
     n_chunks = -(-int(n_ladders) // C)
     if B > n_chunks:
         raise ValueError(f"{who}: blocks = {B} is larger than the {n_chunks} chunks that {n_ladders} ladders make in chunks of {C}: "
-                         "a block would be empty (fewer blocks, or a smaller block_chunk)")
+                         "a jackknife block would be empty (fewer blocks, or a smaller block_chunk)")
     return B, C
 
 
@@ -164,6 +165,47 @@ def jackknife_counts(block_counts, fn):
     theta = np.asarray(fn(total), dtype=np.float64)
     reps = np.stack([np.asarray(fn(total - c[b]), dtype=np.float64) for b in range(B)])
     # (an entry that is not finite in some replicate -- log g of a bin only one block filled -- has the se NaN, and no other entry)
+    with np.errstate(invalid="ignore"):
+        dev = reps - reps.mean(axis=0)
+        se = np.sqrt((B - 1) / B * (dev * dev).sum(axis=0))
+    return theta, se
+
+
+def leave_one_out_integers(block_arrays):
+    """(totals, [totals without block b for every b]) of several integer arrays kept per block at once: ``block_arrays`` is a sequence
+    of arrays [B, ...], each uint64 (counts) or int64 (signed sums), all with the same B.  Every total and every difference is an
+    exact integer: a uint64 block is part of its total, so the difference neither wraps nor rounds; int64 sums are added and
+    subtracted modulo 2^64, which is exact wherever the true results fit 64 bits, as the engine's cells do.  A ValueError for another
+    dtype, for B < 2 and for a block in which every array is zero."""
+    arrays = [np.ascontiguousarray(a) for a in block_arrays]
+    if not arrays:
+        raise ValueError("leave_one_out_integers: no arrays")
+    for a in arrays:
+        if a.dtype not in (np.uint64, np.int64):
+            raise ValueError(f"leave_one_out_integers: an array of dtype {a.dtype}; the exact leave-one-out totals need uint64 or int64")
+        if a.ndim < 1 or a.shape[0] != arrays[0].shape[0]:
+            raise ValueError(f"leave_one_out_integers: arrays of shapes {[x.shape for x in arrays]}; need [B, ...] with one B")
+    B = arrays[0].shape[0]
+    if B < 2:
+        raise ValueError(f"leave_one_out_integers: {B} block(s); a jackknife needs at least 2")
+    for b in range(B):
+        if not any(a[b].any() for a in arrays):
+            raise ValueError(f"leave_one_out_integers: block {b} is empty (fewer chunks of ladders than blocks?)")
+    with np.errstate(over="ignore"):
+        totals = tuple(a.sum(axis=0, dtype=a.dtype) for a in arrays)
+        loo = [tuple(t - a[b] for t, a in zip(totals, arrays)) for b in range(B)]
+    return totals, loo
+
+
+def jackknife_integers(block_arrays, fn):
+    """(theta, se) of ``theta = fn(*totals)`` for several integer arrays kept per block that belong together -- the counts (uint64) and
+    the sums per bin (int64) of energy_moments_fetch_blocks: ``jackknife_counts`` for more than one array.  theta comes from the exact
+    totals (``fn`` sees them first), the B replicates from ``leave_one_out_integers``, each the whole of ``fn``; se by the formula of
+    ``jackknife``, NaN where a replicate is not finite."""
+    totals, loo = leave_one_out_integers(block_arrays)
+    B = len(loo)
+    theta = np.asarray(fn(*totals), dtype=np.float64)
+    reps = np.stack([np.asarray(fn(*loo[b]), dtype=np.float64) for b in range(B)])
     with np.errstate(invalid="ignore"):
         dev = reps - reps.mean(axis=0)
         se = np.sqrt((B - 1) / B * (dev * dev).sum(axis=0))

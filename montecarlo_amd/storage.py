@@ -362,6 +362,16 @@ def _read_energy_histogram_blocks(met, eng, d, est) -> None:
         met.energy_histogram.set_state_blocks(d)
 
 
+def _write_energy_moments_blocks(met, eng, d, est) -> None:
+    if met.energy_histogram is not None:            # moments=... with blocks=B: the cells per jackknife block (no field otherwise)
+        d.update(met.energy_histogram.state_moments_blocks())
+
+def _read_energy_moments_blocks(met, eng, d, est) -> None:
+    # behind _read_energy_moments (which restored the sum over the blocks), the ladder and the sections that set the partition
+    if met.energy_histogram is not None:
+        met.energy_histogram.set_state_moments_blocks(d)
+
+
 def _write_estimator(met, eng, d, est) -> None:
     if est is not None:
         d["gd"] = np.array([[g.j, g.grad_j[0], g.grad_logq_forward[0], g.g[0, 0], g.n] for g in est.gradients_data])
@@ -388,7 +398,8 @@ _SECTIONS = ((_write_core, _read_core), (_write_counters, _read_counters), (_wri
              (_write_annealing, _read_annealing), (_write_correlation, _read_correlation),
              (_write_correlation_blocks, _read_correlation_blocks), (_write_convergence, _read_convergence),
              (_write_energy_histogram, _read_energy_histogram), (_write_energy_moments, _read_energy_moments),
-             (_write_energy_histogram_blocks, _read_energy_histogram_blocks), (_write_estimator, _read_estimator))
+             (_write_energy_histogram_blocks, _read_energy_histogram_blocks), (_write_energy_moments_blocks, _read_energy_moments_blocks),
+             (_write_estimator, _read_estimator))
 
 
 def checkpoint(metropolis: Metropolis, path: str, estimator=None) -> str:

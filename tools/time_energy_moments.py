@@ -10,7 +10,12 @@ A moments accumulator holds fewer than 2^31 / (M / R) snapshots (1717 at 1e7 cha
 window begins with a fetch with reset and one call that allocates the new accumulator, both outside the timed region.
 amc_reduce_rungs_exact copies its records to the host and synchronises in every call, so its figure includes that round trip.
 
-    python tools/time_energy_moments.py [--chains 10000000] [--launches 50] [--repeats 5]
+With --blocks B the tool times the pass per jackknife block instead (amc_energy_moments_accumulate_blocks; DESIGN.md section 3.17
+"Moments per block") beside the plain moments pass of the same handle in the same run: one, two and three columns under the
+partition (B, default chunk), and all three columns under chunks of ONE ladder, the bad case (every chunk is a trip of its own for
+G lanes of a HIP block).  It prints the markdown table of profiles/energy_moments_blocks.md.
+
+    python tools/time_energy_moments.py [--chains 10000000] [--launches 50] [--repeats 5] [--blocks 32]
 """
 import argparse
 import os
@@ -46,15 +51,56 @@ def make_engine(M, betas):
     return eng
 
 
+def blocked_table(args, M, n):
+    """The pass per jackknife block beside the plain moments pass, windows alternating."""
+    B = args.blocks
+    eng = make_engine(M, 0.5 * 1.5 ** np.arange(R))
+    plain = lambda mask: (lambda: eng.energy_moments_accumulate(*BINS, mask, X_BOUND))
+    blocked = lambda mask: (lambda: eng.energy_moments_accumulate_blocks(*BINS, mask, X_BOUND))
+    default = max(1, 256 // R)
+    figures = [("ehist", "the plain energy-histogram snapshot", None, lambda: eng.energy_histogram_accumulate(*BINS), None)]
+    for key, text, mask in (("x", "mask X", X), ("x_xx", "mask X + XX", X | XX), ("all", "mask X + XX + POS", X | XX | POS)):
+        figures.append((key, f"moments, {text}", (0, 0), plain(mask), None))
+        figures.append((f"blk_{key}", f"moments per block, {text}, B = {B}, chunk {default}", (B, 0), blocked(mask), key))
+    figures.append(("blk_all_1", f"moments per block, mask X + XX + POS, B = {B}, chunk 1", (B, 1), blocked(X | XX | POS), "all"))
+    us = {f[0]: [] for f in figures}
+    for _ in range(args.repeats):
+        for key, _, part, call, _ in figures:
+            eng.energy_moments_fetch(reset=True)         # (another mask or form is another accumulator; outside the timed region ...
+            if part is not None:
+                eng.set_blocks(*part)
+            call()                                       #  ... as is the call that allocates and zeroes the new accumulator)
+            us[key].append(device_us(eng, call, n))
+    med = {k: float(np.median(v)) for k, v in us.items()}
+    print(f"M = {M}, R = {R}, double well, K = 1, {BINS[2]} bins of [{BINS[0]:g}, {BINS[1]:g}), x_bound = {X_BOUND:g}; {args.repeats} alternating "
+          f"windows of {n} queued calls per figure (median, min .. max)\n")
+    print("| figure | us | vs the plain moments pass of the same mask |")
+    print("|---|---|---|")
+    for key, text, _, _, base in figures:
+        ratio = f"{med[key] / med[base]:.2f}" if base else ""
+        print(f"| {text} | {med[key]:.1f} ({min(us[key]):.1f} .. {max(us[key]):.1f}) | {ratio} |")
+    # what the last window left: the identities of the contract
+    counts, sums, n_snap, _ = eng.energy_moments_fetch_blocks()
+    per_block = counts.sum(axis=2)[:, 0]
+    merged = eng.energy_moments_fetch()
+    print(f"\n{n_snap} snapshots in the accumulator; ladders per block {int(per_block.min()) // max(n_snap, 1)} .. {int(per_block.max()) // max(n_snap, 1)}; "
+          f"the merged fetch is the sum over the blocks: {bool(np.array_equal(merged[0], counts.sum(axis=0, dtype=np.uint64)) and np.array_equal(merged[1], sums.sum(axis=0)))}; "
+          f"beyond x_bound: {int(counts[:, :, -1].sum())}")
+    eng.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--chains", type=int, default=10_000_000)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--blocks", type=int, default=0, metavar="B", help="time the pass per jackknife block beside the plain moments pass")
     args = ap.parse_args(argv)
     M, n = args.chains - args.chains % (2 * R), args.launches
     if n + 1 >= 2 ** 31 // (M // R):
         ap.error(f"--launches {n}: a moments accumulator of {M // R} chains per rung holds fewer than {2 ** 31 // (M // R)} snapshots")
+    if args.blocks:
+        return blocked_table(args, M, n)
     ladder = make_engine(M, 0.5 * 1.5 ** np.arange(R))
     cold = make_engine(M, [0.5, 1.0, 2.0, 4.0, 8.0, 16.0, 64.0, 4000.0])      # the cold rung: e of order 1 / 4000, bin width 0.08
     mom = lambda eng, mask: (lambda: eng.energy_moments_accumulate(*BINS, mask, X_BOUND))
