@@ -20,8 +20,13 @@ With --reweight N the energy histogram of the population is taken on the device 
 (PopulationAnnealing(energy_histogram=...)), and the last run prints <e>(beta), C(beta) and log(Z(beta) / Z(0.5)) by multiple-histogram
 reweighting over the temperatures of the schedule on an N-point grid from 0.5 to the last beta, each beside the quadrature.
 
+With --blocks B the families are partitioned into B blocks and the engine keeps the weight sums of every step per block
+(PopulationAnnealing(blocks=B), amc_set_anneal_blocks): the last run prints log(Z(beta) / Z(0.5)) +- its own delete-one-block jackknife
+standard error beside the quadrature -- an error bar from ONE run, where the tolerance above needs several.  Together with
+--reweight N the histograms are kept per block of families and every point of the reweighted curve is printed +- its standard error.
+
     python examples/pa_double_well.py [--chains 65536] [--stages 24] [--sweeps 10] [--runs 8] [--path data/PA/...] [--adaptive TARGET]
-                                      [--reweight N]
+                                      [--reweight N] [--blocks B]
 """
 import argparse
 import os
@@ -64,13 +69,29 @@ def print_reweighted(args, pa):
     """--reweight: the curve along the schedule from the last run's histograms, beside the quadrature."""
     taken, _ = pa.histograms()
     grid = np.exp(np.linspace(np.log(taken[0]), np.log(taken[-1]), max(2, args.reweight)))
-    log_z, m1, _, c = pa.reweight(grid)
+    if pa.blocks is not None:              # --blocks: every point with its jackknife standard error over the blocks of families
+        (log_z, m1, _, c), (log_z_se, m1_se, _, c_se) = pa.reweight(grid, error=True)
+    else:
+        log_z, m1, _, c = pa.reweight(grid)
     q_log_z, q_m1, q_c = curve_by_quadrature(grid)
     q0 = curve_by_quadrature(taken[:1])[0][0]
     print(f"last run, reweighted over {len(taken)} temperatures, {HIST['n_bins']} bins of [{HIST['lo']:g}, {HIST['hi']:g}): WHAM | quadrature")
     print("     beta       <e>               C                 log(Z / Z(0.5))")
+    if pa.blocks is not None:
+        for b, e1, s1, e2, c1, s2, c2, z1, s3, z2 in zip(grid, m1, m1_se, q_m1, c, c_se, q_c, log_z, log_z_se, q_log_z - q0):
+            print(f"  {b:7.4f}   {e1:7.4f} +- {s1:.4f} | {e2:7.4f}   {c1:7.4f} +- {s2:.4f} | {c2:7.4f}   {z1:8.4f} +- {s3:.4f} | {z2:8.4f}")
+        return
     for b, e1, e2, c1, c2, z1, z2 in zip(grid, m1, q_m1, c, q_c, log_z, q_log_z - q0):
         print(f"  {b:7.4f}   {e1:7.4f} | {e2:7.4f}   {c1:7.4f} | {c2:7.4f}   {z1:8.4f} | {z2:8.4f}")
+
+
+def print_error_bars(pa, exact):
+    """--blocks: the last run's log Z with its jackknife standard error over the blocks of families, beside the quadrature."""
+    value, se = pa.log_z(error=True)
+    done = pa.betas_done()
+    print(f"last run, jackknife over {pa.blocks[0]} blocks of families:\n   beta   log Z(beta)/Z(0.5) +- se          quadrature   difference / se")
+    for b, v, s, q in zip(done, value, se, exact):
+        print(f"{b:7.4f}   {v:12.6f} +- {s:.6f}   {q:12.6f}   {(v - q) / s:+8.2f}")
 
 
 def one_run(args, path, seed):
@@ -83,6 +104,8 @@ def one_run(args, path, seed):
     schedule = dict(betas=list(betas[1:])) if args.adaptive is None else dict(adaptive=dict(beta_end=BETA_COLD, target=args.adaptive))
     if args.reweight:
         schedule["energy_histogram"] = HIST
+    if args.blocks:
+        schedule["blocks"] = args.blocks
     algorithm_list = [dict(algorithm=ma.Metropolis, pool=pool, seed=seed),
                       dict(algorithm=ma.PopulationAnnealing, dependencies=(ma.Metropolis,), scheduler=when, families=True, **schedule),
                       dict(algorithm=ma.StoreCallbacks, callbacks=(ma.callback_energy, ma.callback_anneal_beta, ma.callback_anneal_log_z, ma.callback_rho_t),
@@ -114,6 +137,8 @@ def adaptive_main(args, path):
         kept = float(np.array([log[i, 3]], dtype=np.uint64).view(np.float64)[0])
         print(f"{done[i]:7.4f}   {lz[i]:12.6f}   {exact[i]:12.6f}   {survival[i]:7.4f}   {kept:8.4f}   {ma.ANNEAL_SEARCH_STATUS[int(log[i, 0])]}")
     print(f"last run: rho_t = {pa.rho_t():.2f} of {args.chains} chains")
+    if args.blocks:
+        print_error_bars(pa, exact)
     if args.reweight:
         print_reweighted(args, pa)
     return ends, exact[-1], tol, done
@@ -132,6 +157,8 @@ def main(argv=None):
     ap.add_argument("--reweight", type=int, default=0, metavar="N",
                     help="take the energy histogram at every annealing temperature; print <e>, C and log Z on an N-point grid of beta along "
                          "the schedule by multiple-histogram reweighting, beside the quadrature")
+    ap.add_argument("--blocks", type=int, default=0, metavar="B",
+                    help="partition the families into B blocks; print the last run's log Z +- its jackknife standard error beside the quadrature")
     args = ap.parse_args(argv)
     path = args.path or f"data/PA/particle_1d/DoubleWell/M{args.chains}/seed{args.seed}"
     if args.adaptive is not None:
@@ -155,6 +182,8 @@ def main(argv=None):
     worst = int(np.argmax(np.abs(mean - exact) / tol)) if args.runs > 1 else args.stages - 1
     print(f"largest deviation in units of its tolerance: {abs(mean[worst] - exact[worst]) / tol[worst]:.3f} at beta = {betas[worst + 1]:.4f}")
     print(f"last run: rho_t = {rho:.2f} of {args.chains} chains, fraction x < 0 at beta = {betas[-1]:.1f}: {left:.4f}")
+    if args.blocks:
+        print_error_bars(pa, exact)
     if args.reweight:
         print_reweighted(args, pa)
     return mean, exact, tol, survival, rho, left

@@ -586,6 +586,34 @@ int  amc_set_anneal_families(amc_handle *h, int on);
 int  amc_anneal_family_stats(amc_handle *h, uint64_t *n_families, uint64_t *sum_sq, uint64_t *largest);
 int  amc_download_families(amc_handle *h, uint32_t *families);
 int  amc_upload_families(amc_handle *h, const uint32_t *families);
+/* Error bars for population annealing (DESIGN.md section 3.14 "Error bars"): blocks of slots stop being independent at the first
+ * resampling (see amc_set_blocks below, which keeps refusing amc_anneal), blocks of FAMILIES do not -- descendants of different
+ * ancestors never share a parent.  amc_set_anneal_blocks(h, n_blocks, chunk) sets the partition "block of chain c =
+ * (fam[c] div chunk) mod n_blocks", a function of the family id and nothing else: n_blocks = 0 turns it off, otherwise
+ * 2 <= n_blocks <= AMC_MAX_JK_BLOCKS; chunk = 0 asks for ceil(n_chains / n_blocks), every block one contiguous range of ancestors.  It
+ * needs families on and excludes amc_set_blocks, in either order (AMC_ERR_STATE); every successful call empties the log below, and so do
+ * amc_set_anneal_families(h, 0) and amc_set_anneal_families(h, 1), which turn the partition off.
+ * While it is set, every amc_anneal appends a BLOCK RECORD of 2 n_blocks 64-bit words to a second log, aligned with the records' log:
+ * n_b, the chains of block b before the resampling, then T_b, the sum of W_c over them -- the integer weights the step resamples by, so
+ * sum_b T_b = T_w and sum_b n_b = n_chains exactly, on any grid.  With a status other than 0, n_b is still counted and T_b reads 0.  One
+ * more launch per step (and one memset); a handle without the partition launches and allocates what it always did.  A full log
+ * (AMC_ANNEAL_MAX_RECORDS block records) makes amc_anneal AMC_ERR_STATE.
+ * amc_anneal_fetch_blocks: *n = block records in the log, *n_blocks = B; with records == NULL the sizes alone, without waiting and
+ * without resetting; otherwise records[(s * 2 + k) * B + b], k = 0: n_b, k = 1: T_b (capacity in block records), synchronises, reset
+ * empties this log -- amc_anneal_fetch and its reset do not touch it: a caller drains both in one place to keep them aligned.
+ * amc_set_anneal_block_records puts n block records back (resume; n_blocks must be B; NULL or n = 0 empties the log).
+ * amc_anneal_block_counts: counts[b] = the n_b of the chains as they stand (one launch; synchronises).
+ * All but amc_set_anneal_blocks are AMC_ERR_STATE without the partition.
+ * Energy histograms per block of families: while this partition is set (and amc_set_blocks, which excludes it, is not),
+ * amc_energy_histogram_accumulate_blocks / _fetch_blocks / amc_set_energy_histogram_blocks (below) work under IT: counts[b][n_bins + 3],
+ * ONE group (a ladder is AMC_ERR_STATE), chain c counted in the row of its family's block; LDS cells while n_blocks (n_bins + 3) <= 12288,
+ * one global atomic per chain beyond.  The sum over the blocks is the plain histogram cell for cell; *n_snapshots = (sum of all
+ * cells) / n_chains, and amc_set_energy_histogram_blocks checks that total instead of every row (a block's share of the chains changes
+ * with every resampling).  Turning the partition off, or setting another, folds a standing accumulator of this form into a plain one. */
+int  amc_set_anneal_blocks(amc_handle *h, int n_blocks, int64_t chunk);
+int  amc_anneal_fetch_blocks(amc_handle *h, uint64_t *records, int capacity, int *n, int *n_blocks, int reset);
+int  amc_set_anneal_block_records(amc_handle *h, const uint64_t *records, int n, int n_blocks);
+int  amc_anneal_block_counts(amc_handle *h, uint64_t *counts);
 
 /* MH steps done per chain so far (the Philox step index); settable for resume. */
 int  amc_get_step(amc_handle *h, uint64_t *t);
@@ -828,7 +856,8 @@ int  amc_chain_stats_clear(amc_handle *h);
  * without waiting for the stream (what a caller sizes its arrays by).  Both are AMC_ERR_STATE without a partition.
  * A respacing that is taken zeroes every block's rows; amc_upload_state, amc_init_uniform forget the blocked mark as they forget the
  * plain one.  amc_anneal is AMC_ERR_STATE while a partition is set: resampling makes copies of one parent share blocks, so the blocks
- * stop being independent and a jackknife over them has no meaning.
+ * stop being independent and a jackknife over them has no meaning (blocks of FAMILIES stay independent: amc_set_anneal_blocks above is
+ * population annealing's own partition; the two cannot be set together, AMC_ERR_STATE).
  * amc_set_bridge_blocks / amc_set_corr_blocks serve checkpoints: they restore the blocked accumulators from what the _blocks fetches
  * gave (n_blocks = B of the partition, set beforehand with the same chunk), every block's records checked as amc_set_bridge /
  * amc_set_corr check theirs and refused the same way; besides, a block without a local ladder must be all zero and the blocks with one

@@ -24,7 +24,7 @@ from .convergence import Convergence, callback_rhat, rhat_from_records, tau_batc
 from .energy_histogram import (EnergyHistogram, callback_reweight_error, callback_reweight_moments,
                                callback_reweight_moments_error)
 from . import reweighting
-from .annealing import ANNEAL_SEARCH_STATUS, PopulationAnnealing, callback_anneal_beta, callback_anneal_log_z, callback_rho_t
+from .annealing import ANNEAL_SEARCH_STATUS, PopulationAnnealing, callback_anneal_beta, callback_anneal_log_z, callback_anneal_log_z_error, callback_rho_t
 from .storage import StoreHistogram, StoreSnapshots, checkpoint, restore
 from .trajectories import DAT, TXT, StoreBackups, StoreLastFrames, StoreTrajectories
 from .system import Action, AriannaSystem, Policy
@@ -46,7 +46,7 @@ __all__ = [
     "Autocorrelation", "callback_rho", "callback_tau_int", "callback_tau_int_error", "rho_from_records", "tau_from_rho",
     "Convergence", "callback_rhat", "rhat_from_records", "tau_batch_from_records", "variances_from_records",
     "EnergyHistogram", "callback_reweight_error", "callback_reweight_moments", "callback_reweight_moments_error", "reweighting",
-    "ANNEAL_SEARCH_STATUS", "PopulationAnnealing", "callback_anneal_beta", "callback_anneal_log_z", "callback_rho_t",
+    "ANNEAL_SEARCH_STATUS", "PopulationAnnealing", "callback_anneal_beta", "callback_anneal_log_z", "callback_anneal_log_z_error", "callback_rho_t",
     "DAT", "TXT", "StoreBackups", "StoreLastFrames", "StoreTrajectories",
     "Action", "AriannaSystem", "Policy", "CustomPotential", "Displacement", "Move", "ParticleChains", "ScaledGaussian", "ScriptAction", "ScriptPolicy", "StandardGaussian", "potential",
 ]

@@ -250,6 +250,10 @@ def load() -> C.CDLL:
         "amc_anneal_family_stats": (C.c_int, [H, u64p, u64p, u64p]),
         "amc_download_families": (C.c_int, [H, C.POINTER(C.c_uint32)]),
         "amc_upload_families": (C.c_int, [H, C.POINTER(C.c_uint32)]),
+        "amc_set_anneal_blocks": (C.c_int, [H, C.c_int, C.c_int64]),
+        "amc_anneal_fetch_blocks": (C.c_int, [H, u64p, C.c_int, ip, ip, C.c_int]),
+        "amc_set_anneal_block_records": (C.c_int, [H, u64p, C.c_int, C.c_int]),
+        "amc_anneal_block_counts": (C.c_int, [H, u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -778,6 +782,34 @@ class HipEngine:
         if fam.shape != (self.n_chains,):
             raise AmcError(f"upload_families: one id per chain ({self.n_chains})")
         _check(self._lib.amc_upload_families(self._h, _ptr(fam)))
+
+    def set_anneal_blocks(self, n_blocks: int, chunk: int = 0) -> None:
+        """The partition into blocks of families, block of chain c = (fam[c] // chunk) % n_blocks (0: off; chunk = 0: ceil(M / B)); needs
+        families on.  Every annealing step from then on appends a block record."""
+        _check(self._lib.amc_set_anneal_blocks(self._h, int(n_blocks), int(chunk)))
+
+    def anneal_block_records(self, reset: bool = False) -> np.ndarray:
+        """The block records in the log, shape (n, 2, B) uint64: n_b before the resampling, then T_b = the sum of W over block b
+        (synchronises); ``reset`` empties this log (not the records' log)."""
+        n, B = C.c_int(0), C.c_int(0)
+        _check(self._lib.amc_anneal_fetch_blocks(self._h, None, 0, C.byref(n), C.byref(B), 0))
+        out = np.zeros((n.value, 2, B.value), dtype=np.uint64)
+        _check(self._lib.amc_anneal_fetch_blocks(self._h, _ptr(out), n.value, C.byref(n), C.byref(B), 1 if reset else 0))
+        return out
+
+    def set_anneal_block_records(self, records) -> None:
+        rec = np.ascontiguousarray(records, dtype=np.uint64)
+        if rec.ndim != 3 or rec.shape[1] != 2:
+            raise AmcError(f"set_anneal_block_records: records of shape (n, 2, B), got {rec.shape}")
+        _check(self._lib.amc_set_anneal_block_records(self._h, _ptr(rec), int(rec.shape[0]), int(rec.shape[2])))
+
+    def anneal_block_counts(self) -> np.ndarray:
+        """n_b, the chains of every block of families as they stand (synchronises)."""
+        n, B = C.c_int(0), C.c_int(0)
+        _check(self._lib.amc_anneal_fetch_blocks(self._h, None, 0, C.byref(n), C.byref(B), 0))
+        out = np.zeros(B.value, dtype=np.uint64)
+        _check(self._lib.amc_anneal_block_counts(self._h, _ptr(out)))
+        return out
 
     # -- replica exchange along a temperature ladder (include/amc.h; DESIGN.md section 3.13) ----------------
     def set_ladder(self, n_rungs: int) -> None:

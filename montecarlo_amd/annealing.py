@@ -10,6 +10,9 @@ resampling, exact integers on the device), and the Metropolis sweeps that follow
 by chain slot and step, so copies of one parent part ways at their first sweep.  The mean weight of a step estimates
 Z(beta') / Z(beta): one run yields log Z along the whole schedule.  ``families=True`` carries the id of every chain's ancestor along;
 rho_t = sum_f n_f^2 / M, the mean family size seen from a chain, tells whether the population is large enough (rho_t << M).
+``blocks=B`` partitions the FAMILIES into B blocks -- descendants of different ancestors never share a parent, so these blocks stay
+independent where blocks of slots do not -- and the engine keeps the weight sums of every step per block: ``log_z(error=True)`` is a
+delete-one-block jackknife over them (DESIGN.md section 3.14 "Error bars").
 """
 from __future__ import annotations
 
@@ -19,7 +22,7 @@ import struct
 import numpy as np
 
 from . import sharding
-from ._capi import (AMC_ANNEAL_MAX_RECORDS, AMC_ANNEAL_RECORD_WORDS, AMC_ANNEAL_SEARCH_MAX_ROUNDS, AMC_ANNEAL_SEARCH_STALLED,
+from ._capi import (AMC_MAX_JK_BLOCKS, AMC_ANNEAL_MAX_RECORDS, AMC_ANNEAL_RECORD_WORDS, AMC_ANNEAL_SEARCH_MAX_ROUNDS, AMC_ANNEAL_SEARCH_STALLED,
                     AMC_ANNEAL_SEARCH_WORDS, AMC_ANNEAL_WEIGHT_BITS, AMC_EHIST_MAX_BINS)
 from .metropolis import Metropolis
 from .simulation import AriannaAlgorithm, Simulation, _calls
@@ -89,11 +92,20 @@ class PopulationAnnealing(AriannaAlgorithm):
     PopulationAnnealing(..., energy_histogram=dict(lo=..., hi=..., n_bins=..., max_outside=0.0)): before each annealing step, and once
     at ``finalise``, the energy histogram of the population at the beta in force is taken on the device (DESIGN.md section 3.17:
     [accumulate; fetch with reset]) and kept with its beta; ``histograms()`` returns them, ``reweight(betas)`` applies
-    multiple-histogram reweighting over the temperatures of the schedule.  Without the option nothing new is launched."""
+    multiple-histogram reweighting over the temperatures of the schedule.  Without the option nothing new is launched.
+
+    PopulationAnnealing(..., blocks=B, block_chunk=None) implies ``families=True`` and sets the engine's partition into blocks of
+    families, block of a chain = (family id div chunk) mod B (chunk None: ceil(M / B), every block one contiguous range of ancestors).
+    Every annealing step then appends a block record beside its record (one more launch per step); ``block_records()`` returns them,
+    ``log_z_ratios(error=True)`` / ``log_z(error=True)`` return (value, se) by the delete-one-block jackknife of
+    ``jackknife.anneal_log_z``.  Together with ``energy_histogram=...`` the histogram of every temperature is kept per block of families
+    (``histograms_blocks()``) and ``reweight(betas, error=True)`` returns the curve with its standard errors.  Without the option
+    nothing new is launched or allocated."""
 
     mutates_chains = True          # a callback due behind it at the same t observes the state AFTER the resampling
 
-    def __init__(self, chains, dependencies=None, betas=None, adaptive=None, families=False, energy_histogram=None, path=None, **extras):
+    def __init__(self, chains, dependencies=None, betas=None, adaptive=None, families=False, energy_histogram=None, blocks=None,
+                 block_chunk=None, path=None, **extras):
         assert dependencies is not None and len(dependencies) == 1 and isinstance(dependencies[0], Metropolis)
         self.metropolis: Metropolis = dependencies[0]
         if adaptive is not None and betas is not None:
@@ -115,15 +127,35 @@ class PopulationAnnealing(AriannaAlgorithm):
             raise ValueError("PopulationAnnealing: this engine has no annealing step (streams > 1 is not supported)")
         if self.adaptive is not None and not hasattr(self.metropolis.engine, "anneal_next_beta"):
             raise ValueError("PopulationAnnealing: this engine cannot choose the next beta (adaptive needs amc_anneal_next_beta)")
+        self.blocks = None                     # blocks=B: the partition (B, chunk) over the families
+        if blocks is None or blocks is False:
+            if block_chunk is not None:
+                raise ValueError(f"PopulationAnnealing: block_chunk = {block_chunk!r} without blocks")
+        else:
+            if int(blocks) != blocks or not 2 <= int(blocks) <= AMC_MAX_JK_BLOCKS:
+                raise ValueError(f"PopulationAnnealing: blocks = {blocks!r} must be an integer in [2, {AMC_MAX_JK_BLOCKS}]")
+            B, M = int(blocks), len(chains)
+            chunk = -(-M // B) if block_chunk is None else block_chunk
+            if int(chunk) != chunk or int(chunk) < 1:
+                raise ValueError(f"PopulationAnnealing: block_chunk = {block_chunk!r} must be an integer >= 1")
+            if -(-M // int(chunk)) < B:
+                raise ValueError(f"PopulationAnnealing: {M} families in chunks of {int(chunk)} make fewer chunks than blocks = {B} (a block "
+                                 "would hold no family)")
+            if not hasattr(self.metropolis.engine, "set_anneal_blocks"):
+                raise ValueError("PopulationAnnealing: this engine keeps no weight sums per block of families (blocks needs amc_set_anneal_blocks)")
+            self.blocks = (B, int(chunk))
+            families = True                    # the partition is a function of the family ids
         self.families = bool(families)
         self.hist_plan = None if energy_histogram is None else _histogram_plan(energy_histogram)
         if self.hist_plan is not None and not hasattr(self.metropolis.engine, "energy_histogram_accumulate"):
             raise ValueError("PopulationAnnealing: this engine has no energy histograms (energy_histogram needs amc_energy_histogram_accumulate)")
         self._hist = []                        # energy_histogram: (beta, row[n_bins + 3]) per temperature, oldest first
+        self._hist_blocks = []                 # ... with blocks=B: rows[B, n_bins + 3] per temperature beside them, one per block of families
         self._hist_final = False               # ... the last one was taken by finalise (a checkpoint leaves it out: the resumed run takes
                                                # the histogram of that beta itself, in front of its next step or at its own finalise)
         self.chains = chains
         self._records = []                     # records drained from the engine's log, oldest first
+        self._block_records = []               # blocks=B: the block records drained beside them, [2, B] each
         self._search_log = []                  # adaptive: the diag of every search of this process, oldest first
         self.metropolis.annealing = self       # (storage.checkpoint: beta, the step index, the records and the families are state)
         self.rank, _ = sharding.world()
@@ -135,6 +167,8 @@ class PopulationAnnealing(AriannaAlgorithm):
                              "exclude each other")
         if self.families and not self.metropolis.families_restored:     # (restored: storage.restore brought them back)
             self.metropolis.engine.set_anneal_families(True)
+        if self.blocks is not None and not self.metropolis.anneal_blocks_restored:      # (behind the families: it needs them)
+            self.metropolis.engine.set_anneal_blocks(*self.blocks)
 
     def make_step(self, simulation: Simulation) -> None:
         eng = self.metropolis.engine
@@ -171,9 +205,17 @@ class PopulationAnnealing(AriannaAlgorithm):
         eng, plan = self.metropolis.engine, self.hist_plan
         if self._hist_final:
             self._hist.pop()
-        eng.energy_histogram_accumulate(plan["lo"], plan["hi"], plan["n_bins"])
-        counts, _, _ = eng.energy_histogram_fetch(reset=True)
-        self._hist.append((float(eng.beta), np.array(counts[0], dtype=np.uint64)))
+            if self.blocks is not None:
+                self._hist_blocks.pop()
+        if self.blocks is not None:            # a row per block of families; their sum is the plain histogram cell for cell
+            eng.energy_histogram_accumulate_blocks(plan["lo"], plan["hi"], plan["n_bins"])
+            per_block = np.array(eng.energy_histogram_fetch_blocks(reset=True)[0], dtype=np.uint64).reshape(self.blocks[0], plan["n_bins"] + 3)
+            self._hist_blocks.append(per_block)
+            self._hist.append((float(eng.beta), per_block.sum(axis=0, dtype=np.uint64)))
+        else:
+            eng.energy_histogram_accumulate(plan["lo"], plan["hi"], plan["n_bins"])
+            counts, _, _ = eng.energy_histogram_fetch(reset=True)
+            self._hist.append((float(eng.beta), np.array(counts[0], dtype=np.uint64)))
         self._hist_final = bool(final)
 
     def histograms(self):
@@ -185,10 +227,23 @@ class PopulationAnnealing(AriannaAlgorithm):
         return (np.array([b for b, _ in self._hist], dtype=np.float64),
                 np.array([c for _, c in self._hist], dtype=np.uint64).reshape(-1, n))
 
-    def reweight(self, betas, **kw):
+    def histograms_blocks(self):
+        """(betas[S], counts[S, B, n_bins + 3]): the histograms() per block of families -- chain c counted in the row of block
+        (family id div chunk) mod B; the sum over the blocks is histograms() cell for cell.  Needs energy_histogram=... and blocks=B."""
+        if self.hist_plan is None or self.blocks is None:
+            raise ValueError("PopulationAnnealing.histograms_blocks needs the histograms per block: build the PopulationAnnealing with "
+                             "energy_histogram=dict(...) and blocks=B")
+        n = self.hist_plan["n_bins"] + 3
+        return (np.array([b for b, _ in self._hist], dtype=np.float64),
+                np.array(self._hist_blocks, dtype=np.uint64).reshape(-1, self.blocks[0], n))
+
+    def reweight(self, betas, error: bool = False, **kw):
         """(log Z, <e>, <e^2>, C) at every beta of ``betas`` by multiple-histogram reweighting over the temperatures of the schedule
         (reweighting.wham / reweight); log Z is 0 at the first temperature.  Raises, naming the temperature and the cell, when a
-        histogram's share outside the bins exceeds ``max_outside``."""
+        histogram's share outside the bins exceeds ``max_outside``.
+        error=True (needs blocks=B): ((log Z, <e>, <e^2>, C), (their standard errors)) by the delete-one-block jackknife over the
+        blocks of families (jackknife.jackknife_counts): every replicate is the whole of WHAM and the reweighting on the counts of ALL
+        temperatures without block b -- the same families appear at every temperature, so the block is deleted everywhere at once."""
         from . import reweighting
         b, counts = self.histograms()
         if not len(b):
@@ -202,8 +257,20 @@ class PopulationAnnealing(AriannaAlgorithm):
                              f"samples in the cell '{('below lo', 'at or above hi', 'NaN')[c]}' (max_outside = {plan['max_outside']:g}): "
                              f"widen [lo, hi) = [{plan['lo']:g}, {plan['hi']:g})")
         energies = reweighting.bin_centres(plan["lo"], plan["hi"], plan["n_bins"])
-        log_g = reweighting.wham(counts[:, :plan["n_bins"]], b, energies, **kw)[0]
-        return reweighting.reweight(log_g, energies, betas)
+        if not error:
+            log_g = reweighting.wham(counts[:, :plan["n_bins"]], b, energies, **kw)[0]
+            return reweighting.reweight(log_g, energies, betas)
+        from . import jackknife
+        per_block = self.histograms_blocks()[1]                       # [S, B, n_bins + 3]
+        start = {}
+
+        def curve(c):                                                  # c[S, n_bins]: the full counts first, then every replicate's
+            log_g, f, _ = reweighting.wham(c, b, energies, **dict(kw, f0=start.get("f", kw.get("f0"))))
+            start.setdefault("f", f)                                   # the replicates start from the full solution
+            return np.array(reweighting.reweight(log_g, energies, np.atleast_1d(np.asarray(betas, dtype=np.float64))))
+
+        theta, se = jackknife.jackknife_counts(np.ascontiguousarray(per_block.transpose(1, 0, 2)[:, :, :plan["n_bins"]]), curve)
+        return tuple(theta), tuple(se)
 
     def histogram_state(self) -> dict:
         """The section of a checkpoint: the bins and the list, without the histogram finalise took."""
@@ -212,8 +279,11 @@ class PopulationAnnealing(AriannaAlgorithm):
         b, counts = self.histograms()
         keep = len(b) - (1 if self._hist_final else 0)
         plan = self.hist_plan
-        return dict(anneal_hist_bins=np.array([plan["lo"], plan["hi"], float(plan["n_bins"])]), anneal_hist_betas=b[:keep],
-                    anneal_hist_counts=counts[:keep])
+        out = dict(anneal_hist_bins=np.array([plan["lo"], plan["hi"], float(plan["n_bins"])]), anneal_hist_betas=b[:keep],
+                   anneal_hist_counts=counts[:keep])
+        if self.blocks is not None:            # blocks=B: the rows per block of families (no field otherwise)
+            out["anneal_hist_block_counts"] = self.histograms_blocks()[1][:keep]
+        return out
 
     def set_histogram_state(self, d) -> None:
         if self.hist_plan is None or "anneal_hist_bins" not in d:
@@ -226,6 +296,14 @@ class PopulationAnnealing(AriannaAlgorithm):
         counts = np.asarray(d["anneal_hist_counts"], dtype=np.uint64).reshape(-1, plan["n_bins"] + 3)
         self._hist = [(float(b), c.copy()) for b, c in zip(d["anneal_hist_betas"], counts)]
         self._hist_final = False
+        if self.blocks is not None:
+            if "anneal_hist_block_counts" not in d:
+                if len(counts):
+                    raise ValueError("checkpoint holds annealing histograms without histograms per block, this PopulationAnnealing asks for blocks")
+                self._hist_blocks = []
+            else:
+                per_block = np.asarray(d["anneal_hist_block_counts"], dtype=np.uint64).reshape(-1, self.blocks[0], plan["n_bins"] + 3)
+                self._hist_blocks = [c.copy() for c in per_block]
 
     @property
     def finished(self) -> bool:
@@ -241,8 +319,15 @@ class PopulationAnnealing(AriannaAlgorithm):
         return np.array(self._search_log, dtype=np.uint64).reshape(-1, AMC_ANNEAL_SEARCH_WORDS)
 
     def _drain(self) -> None:
-        rec = np.asarray(self.metropolis.engine.anneal_records(reset=True), dtype=np.uint64).reshape(-1, AMC_ANNEAL_RECORD_WORDS)
+        eng = self.metropolis.engine
+        rec = np.asarray(eng.anneal_records(reset=True), dtype=np.uint64).reshape(-1, AMC_ANNEAL_RECORD_WORDS)
         self._records.extend(rec.copy())
+        if self.blocks is not None:            # both logs in this one place: they stay aligned
+            blk = np.asarray(eng.anneal_block_records(reset=True), dtype=np.uint64).reshape(-1, 2, self.blocks[0])
+            if len(blk) != len(rec):
+                raise ValueError(f"PopulationAnnealing: the engine's log holds {len(rec)} records and {len(blk)} block records (steps were "
+                                 "taken without the partition, or one log was drained alone)")
+            self._block_records.extend(blk.copy())
 
     @property
     def beta(self) -> float:
@@ -255,16 +340,40 @@ class PopulationAnnealing(AriannaAlgorithm):
         self._drain()
         return np.array(self._records, dtype=np.uint64).reshape(-1, AMC_ANNEAL_RECORD_WORDS)
 
-    def log_z_ratios(self) -> np.ndarray:
+    def block_records(self) -> np.ndarray:
+        """[steps, 2, B] unsigned 64-bit words, one block record per annealing step so far: n_b, the chains of block b before the
+        resampling, then T_b, the sum of their integer weights (sum_b T_b = T_w, sum_b n_b = M).  Needs blocks=B; the host waits."""
+        if self.blocks is None:
+            raise ValueError("PopulationAnnealing.block_records needs the partition: build the PopulationAnnealing with blocks=B")
+        self._drain()
+        return np.array(self._block_records, dtype=np.uint64).reshape(-1, 2, self.blocks[0])
+
+    def _log_z_error(self, cumulative: bool):
+        from . import jackknife
+        if self.blocks is None:
+            raise ValueError("PopulationAnnealing: error=True needs the partition: build the PopulationAnnealing with blocks=B")
+        value, se, _ = jackknife.anneal_log_z(self.records(), self.block_records(), len(self.chains), cumulative=cumulative)
+        return value, se
+
+    def log_z_ratios(self, error: bool = False):
         """log(Z(beta_to) / Z(beta_from)) per annealing step: a_max + log T_w - log M - 30 log 2, the log of the mean reweighting
-        factor, formed from the integer records (the same number on any grid); NaN for a step that did not resample."""
+        factor, formed from the integer records (the same number on any grid); NaN for a step that did not resample.
+        error=True (needs blocks=B): (value, se), se by the delete-one-block jackknife over the blocks of families, per step."""
+        if error:
+            return self._log_z_error(cumulative=False)
         M = float(len(self.chains))
         out = [(_f64(r[3]) + math.log(int(r[4])) - math.log(M) - AMC_ANNEAL_WEIGHT_BITS * math.log(2.0)) if int(r[0]) == 0 else math.nan
                for r in self.records()]
         return np.array(out, dtype=np.float64)
 
-    def log_z(self) -> np.ndarray:
-        """log(Z(beta_i) / Z(beta_start)) after every annealing step: the cumulative sum of log_z_ratios() from the first beta."""
+    def log_z(self, error: bool = False):
+        """log(Z(beta_i) / Z(beta_start)) after every annealing step: the cumulative sum of log_z_ratios() from the first beta.
+        error=True (needs blocks=B): (value, se).  Replicate b of log Z after step t is the sum over s <= t of
+        a_max^s + log(T_w^s - T_b^s) - log(M - n_b^s) - 30 log 2 -- the replicate of the cumulative sum, not a sum of per-step errors
+        --, se^2 = (B' - 1) / B' sum_b (theta_b - mean)^2 over the B' blocks that held a family at the first step.  A replicate whose
+        argument is 0 (one block holds every chain, or all the weight) is NaN from that step on, and so is the se."""
+        if error:
+            return self._log_z_error(cumulative=True)
         return np.cumsum(self.log_z_ratios())
 
     def betas_done(self) -> np.ndarray:
@@ -291,7 +400,8 @@ class PopulationAnnealing(AriannaAlgorithm):
         else:
             betas = (f"\t\tBetas: adaptive, ESS / M >= {self.adaptive['target']} per step, to {self.adaptive['beta_end']} "
                      f"({self.adaptive['rounds']} rounds)\n")
-        io.write(f"\tPopulationAnnealing\n\t\tCalls: {_calls(scheduler)}\n{betas}\t\tFamilies: {str(self.families).lower()}\n")
+        blocks = "" if self.blocks is None else f"\t\tBlocks: {self.blocks[0]} of families, chunk {self.blocks[1]}\n"
+        io.write(f"\tPopulationAnnealing\n\t\tCalls: {_calls(scheduler)}\n{betas}\t\tFamilies: {str(self.families).lower()}\n{blocks}")
 
 
 def _find_annealing(simulation: Simulation) -> PopulationAnnealing:
@@ -311,6 +421,13 @@ def callback_anneal_log_z(simulation: Simulation) -> float:
     host waits for the queued steps."""
     lz = _find_annealing(simulation).log_z()
     return float(lz[-1]) if lz.size else 0.0
+
+
+def callback_anneal_log_z_error(simulation: Simulation) -> float:
+    """The jackknife standard error of callback_anneal_log_z (the last se of PopulationAnnealing.log_z(error=True); 0 before the first
+    step).  Needs PopulationAnnealing(..., blocks=B).  The host waits for the queued steps."""
+    se = _find_annealing(simulation).log_z(error=True)[1]
+    return float(se[-1]) if se.size else 0.0
 
 
 def callback_rho_t(simulation: Simulation) -> float:

@@ -3,6 +3,7 @@
 // another block: the multi-block prefix is the three-launch form):
 //   anneal_logw_kernel<POT>   a_i = double((-e_i) delta) per chain, and the maximum over the non-NaN ones (one 64-bit atomic per block)
 //   anneal_weights_kernel     W_i = floor(2^30 exp(a_i - a_max)) per chain, and the sum of every tile of ANNEAL_TILE chains
+//   anneal_block_sums_kernel  only under amc_set_anneal_blocks: n_b and T_b = sum of W per block of families, the step's block record
 //   anneal_total_kernel       one block: the exclusive prefix of the tile sums, T_w, the offset U, the step's record
 //   anneal_prefix_kernel      C_i = tile offset + scan inside the tile, and from it N_i, the number of child slots j with
 //                             j T_w + U < C_i M (128-bit integers); the children of chain i are the slots [N_(i-1), N_i)
@@ -31,6 +32,8 @@ enum { ANNEAL_R_STATUS = 0, ANNEAL_R_BETA_FROM = 1, ANNEAL_R_BETA_TO = 2, ANNEAL
        ANNEAL_R_PARENTS = 6, ANNEAL_R_MAX_CHILDREN = 7, ANNEAL_R_WORDS = 8 };
 // Status of a step: resampled; every a_i NaN; a_max = +Inf; a_max = -Inf (every weight zero).  Anything but ANNEAL_OK leaves x alone.
 enum { ANNEAL_OK = 0, ANNEAL_ALL_NAN = 1, ANNEAL_INF = 2, ANNEAL_NO_WEIGHT = 3 };
+// The most blocks of families (AMC_MAX_JK_BLOCKS of include/amc.h); a block record holds n_b, then T_b: 2 B words.
+enum { ANNEAL_MAX_BLOCKS = 64 };
 
 // A non-NaN double as an unsigned key whose integer order is the order of the values (-0 below +0), never 0.
 __device__ __forceinline__ uint64_t anneal_key(double a)
@@ -139,6 +142,57 @@ AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void anneal_weights_k
         (void)anneal_block_scan(sum, s_wave, &total);
         if (threadIdx.x == 0) tile_sums[tile] = total;
     }
+}
+
+// ---- weight sums per block of families (amc_set_anneal_blocks; DESIGN.md section 3.14 "Error bars") -----------------------------------
+// rec[b] = n_b, the chains whose family lies in block b = (fam div chunk) mod B, and rec[B + b] = T_b, the sum of their W (rec was
+// zeroed on the stream in front of this launch).  It runs behind anneal_weights_kernel and in front of anneal_prefix_kernel, which
+// overwrites W with N.  w == nullptr, or a status other than ANNEAL_OK (the word then still holds a): every W reads 0, n_b is counted.
+// A wave takes 64 consecutive chains per trip, four trips' loads in flight.  fam is non-decreasing after a resampling and a block of
+// the default chunk a contiguous range of ids, so the 64 lanes of a trip nearly always share one block: then ONE wave total
+// (wave_total_i64) and one pair of LDS atomics per wave; lanes that differ (chunk 1, uploaded ids in any order, a boundary, the ragged
+// end) deposit one by one.  The cells are 64-bit in LDS, then at most 2 B 64-bit global atomics per HIP block.  Integer sums: the same in
+// any order and on any grid.  chunk is the partition's, capped at 2^32 - 1 by the host (an id is below that: the quotient is 0 either way).
+AMC_KERNEL_LINKAGE __global__ __launch_bounds__(AMC_BLOCK) void anneal_block_sums_kernel(const unsigned long long* w, const uint32_t* fam, int64_t n_chains,
+                                                                                          const unsigned long long* scratch, uint32_t chunk, int n_blocks,
+                                                                                          unsigned long long* rec)
+{
+    __shared__ unsigned long long s_cells[2 * ANNEAL_MAX_BLOCKS];
+    if (threadIdx.x < 2 * n_blocks) s_cells[threadIdx.x] = 0ull;
+    __syncthreads();
+    const bool weigh = w != nullptr && anneal_status(scratch[ANNEAL_S_KEY]) == ANNEAL_OK;
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * AMC_BLOCK;
+    // (i0 is the wave's first chain: every lane of a wave makes the same trips, so the wave total below sees all 64 lanes)
+    for (int64_t i0 = (int64_t)blockIdx.x * AMC_BLOCK + (threadIdx.x - lane); i0 < n_chains; i0 += ANNEAL_ITEMS * stride) {
+        int b[ANNEAL_ITEMS];
+        unsigned long long wi[ANNEAL_ITEMS];
+#pragma unroll
+        for (int k = 0; k < ANNEAL_ITEMS; ++k) {
+            const int64_t i = i0 + k * stride + lane;
+            const bool in = i < n_chains;
+            b[k] = in ? (int)((fam[i] / chunk) % (uint32_t)n_blocks) : -1;
+            wi[k] = in && weigh ? w[i] : 0ull;
+        }
+#pragma unroll
+        for (int k = 0; k < ANNEAL_ITEMS; ++k) {
+            const int b0 = __builtin_amdgcn_readfirstlane(b[k]);
+            if (__all(b[k] == b0)) {                              // wave-uniform: all 64 lanes in one block, or all past the end
+                if (b0 < 0) continue;
+                long long t[1] = {(long long)wi[k]};
+                wave_total_i64<1>(t);
+                if (lane == 0) {
+                    atomicAdd(&s_cells[b0], 64ull);
+                    if (t[0]) atomicAdd(&s_cells[n_blocks + b0], (unsigned long long)t[0]);
+                }
+            } else if (b[k] >= 0) {
+                atomicAdd(&s_cells[b[k]], 1ull);
+                if (wi[k]) atomicAdd(&s_cells[n_blocks + b[k]], wi[k]);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * n_blocks && s_cells[threadIdx.x]) atomicAdd(&rec[threadIdx.x], s_cells[threadIdx.x]);
 }
 
 struct AnnealTotalArgs {

@@ -1,6 +1,7 @@
 // amc_anneal.hip -- population annealing: the annealing step (amc_anneal), its record log (amc_anneal_fetch,
 // amc_set_anneal_records), the annealing step index, the shared beta (amc_get_beta, amc_set_beta), the choice of the next beta
-// (amc_anneal_next_beta) and the families (amc_set_anneal_families .. amc_upload_families).  Everything here is allocated at its first use: a handle that never anneals has none of it.
+// (amc_anneal_next_beta) and the families (amc_set_anneal_families .. amc_upload_families) with the partition into blocks of families and its log of block records
+// (amc_set_anneal_blocks .. amc_anneal_block_counts).  Everything here is allocated at its first use: a handle that never anneals has none of it.
 #define AMC_KERNEL_LINKAGE static      // the template instantiations, and this object's own copies of the plain kernels it launches
 #include "amc_internal.h"
 
@@ -12,6 +13,9 @@ static_assert(AMC_ANNEAL_SEARCH_MAX_ROUNDS == amc::SEARCH_MAX_ROUNDS && AMC_ANNE
               "the search of include/amc.h and amc_anneal_search.h");
 
 static const size_t ANNEAL_LOG_BYTES = (size_t)AMC_ANNEAL_MAX_RECORDS * amc::ANNEAL_R_WORDS * sizeof(unsigned long long);
+
+static_assert(AMC_MAX_JK_BLOCKS == amc::ANNEAL_MAX_BLOCKS, "the blocks of include/amc.h and amc_anneal.h");
+static size_t blk_log_bytes(int B) { return (size_t)AMC_ANNEAL_MAX_RECORDS * 2 * (size_t)B * sizeof(unsigned long long); }
 
 static int64_t anneal_tiles(const amc_handle* h) { return (h->M + amc::ANNEAL_TILE - 1) / amc::ANNEAL_TILE; }
 
@@ -29,10 +33,33 @@ static int anneal_room(amc_handle* h)
     return zeroed_words(h, &h->ann.d_anneal_log, ANNEAL_LOG_BYTES);
 }
 
+// The partition over the families gone, its log with it.  hipFree waits for whatever still writes the memory.
+static void anneal_blocks_off(amc_handle* h)
+{
+    if (h->ehist.by_family) (void)ehist_fold(h);      // energy histograms kept under the partition that goes: folded into a plain one, nothing is lost
+    if (h->ann.d_blk_log) (void)hipFree(h->ann.d_blk_log);
+    h->ann.d_blk_log = nullptr;
+    h->ann.blk_B = h->ann.blk_n = 0;
+    h->ann.blk_chunk = 0;
+}
+
+// n_b (and T_b, with w) of the chains as they stand into rec[2 B], zeroed in front on the stream.
+static int anneal_block_sums(amc_handle* h, const unsigned long long* w, unsigned long long* rec)
+{
+    const int B = h->ann.blk_B;
+    const uint32_t chunk = (uint32_t)std::min<int64_t>(h->ann.blk_chunk, 0xFFFFFFFFll);      // (an id is below 2^32 - 1: the quotient is 0 either way)
+    AMC_HIP(hipMemsetAsync(rec, 0, 2 * (size_t)B * sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(amc::anneal_block_sums_kernel, dim3(grid_for(h, (h->M + amc::ANNEAL_ITEMS - 1) / amc::ANNEAL_ITEMS)), dim3(AMC_BLOCK), 0, h->stream, w,
+                       (const uint32_t*)h->ann.d_fam, h->M, (const unsigned long long*)h->ann.d_anneal_s, chunk, B, rec);
+    AMC_HIP(hipGetLastError());
+    return AMC_OK;
+}
+
 static int families_off(amc_handle* h)
 {
     if (!h->ann.d_fam) return AMC_OK;
     AMC_HIP(hipStreamSynchronize(h->stream));      // launches queued on the stream may still use them
+    anneal_blocks_off(h);                          // the partition is a function of the family ids
     (void)hipFree(h->ann.d_fam);
     (void)hipFree(h->ann.d_fam_alt);
     (void)hipFree(h->ann.d_fam_cnt);
@@ -58,11 +85,14 @@ int amc_anneal(amc_handle* h, double beta_new)
     if (h->ann.anneal_n >= AMC_ANNEAL_MAX_RECORDS)
         return fail(AMC_ERR_STATE, "amc_anneal: the record log is full (%d records; amc_anneal_fetch with reset empties it)", AMC_ANNEAL_MAX_RECORDS);
     if (h->ann.t_a >> 48) return fail(AMC_ERR_STATE, "amc_anneal: the annealing step index has reached 2^48");
+    if (h->ann.blk_B && h->ann.blk_n >= AMC_ANNEAL_MAX_RECORDS)
+        return fail(AMC_ERR_STATE, "amc_anneal: the log of block records is full (%d records; amc_anneal_fetch_blocks with reset empties it)", AMC_ANNEAL_MAX_RECORDS);
     AMC_HIP(hipSetDevice(h->device));
     // (what an exchange step does before it launches: a learning step left pending by a fused time step is taken now; reductions in
     // flight were queued on the same stream and have read x before the buffers change places)
     AMC_TRY(pg_resolve(h));
     AMC_TRY(anneal_room(h));
+    if (h->ann.blk_B) AMC_TRY(zeroed_words(h, &h->ann.d_blk_log, blk_log_bytes(h->ann.blk_B)));
     const int64_t n_tiles = anneal_tiles(h);
     const int grid_chains = grid_for(h, h->M), grid_tiles = grid_for(h, n_tiles * AMC_BLOCK);
     unsigned long long* rec = h->ann.d_anneal_log + (size_t)h->ann.anneal_n * amc::ANNEAL_R_WORDS;
@@ -81,6 +111,8 @@ int amc_anneal(amc_handle* h, double beta_new)
     hipLaunchKernelGGL(amc::anneal_weights_kernel, dim3(grid_tiles), dim3(AMC_BLOCK), 0, h->stream, h->ann.d_anneal_n, h->M, n_tiles,
                        (const unsigned long long*)h->ann.d_anneal_s, h->ann.d_anneal_tiles);
     AMC_HIP(hipGetLastError());
+    // blocks of families: the step's block record, from W -- behind the weights, in front of the prefix pass that overwrites them
+    if (h->ann.blk_B) AMC_TRY(anneal_block_sums(h, h->ann.d_anneal_n, h->ann.d_blk_log + (size_t)h->ann.blk_n * 2 * h->ann.blk_B));
     {
         amc::AnnealTotalArgs a;
         a.tile_sums = h->ann.d_anneal_tiles;
@@ -106,6 +138,7 @@ int amc_anneal(amc_handle* h, double beta_new)
     h->beta = beta_new;          // the host field: in force for every launch queued from now on (nothing on the device is derived from it)
     h->ann.t_a += 1;
     h->ann.anneal_n += 1;
+    if (h->ann.blk_B) h->ann.blk_n += 1;
     corr_forget(h);              // the copies have changed slots: the mark of the time correlation goes (include/amc.h "Time correlation")
     return AMC_OK;
 }
@@ -256,6 +289,7 @@ int amc_set_anneal_families(amc_handle* h, int on)
     AMC_HIP(hipSetDevice(h->device));
     if (!on) return families_off(h);
     if (h->M > 0xFFFFFFFFll) return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_families: n_chains = %lld, a family id holds 32 bits", (long long)h->M);
+    anneal_blocks_off(h);          // families afresh: block records of the ones that go say nothing about them
     if (!h->ann.d_fam) {
         AMC_HIP(hipMalloc(&h->ann.d_fam, (size_t)h->M * sizeof(uint32_t)));
         const hipError_t e = hipMalloc(&h->ann.d_fam_alt, (size_t)h->M * sizeof(uint32_t));
@@ -291,6 +325,73 @@ int amc_anneal_family_stats(amc_handle* h, uint64_t* n_families, uint64_t* sum_s
     *sum_sq = (uint64_t)host[1];
     *largest = (uint64_t)host[2];
     return AMC_OK;
+}
+
+// ---- blocks of families (DESIGN.md section 3.14 "Error bars") --------------------------------------------------------------------------
+int amc_set_anneal_blocks(amc_handle* h, int n_blocks, int64_t chunk)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_blocks: NULL handle");
+    if (n_blocks != 0 && (n_blocks < 2 || n_blocks > AMC_MAX_JK_BLOCKS))
+        return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_blocks: n_blocks = %d must be 0 (no partition) or lie in [2, %d]", n_blocks, AMC_MAX_JK_BLOCKS);
+    if (chunk < 0 || chunk > AMC_MAX_JK_CHUNK)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_blocks: chunk = %lld must lie in [1, 2^40], or be 0 for the default", (long long)chunk);
+    if (n_blocks) {
+        AMC_TRY(need_families(h, "amc_set_anneal_blocks"));
+        if (h->blocks.n_blocks)
+            return fail(AMC_ERR_STATE, "amc_set_anneal_blocks: a partition over the ladders is set (amc_set_blocks); the two exclude each other");
+    }
+    AMC_HIP(hipSetDevice(h->device));
+    anneal_blocks_off(h);          // records kept under another partition (or under none) are not sums of these blocks
+    if (n_blocks) {
+        h->ann.blk_B = n_blocks;
+        h->ann.blk_chunk = chunk ? chunk : (h->M + n_blocks - 1) / n_blocks;      // every block one contiguous range of ancestors
+    }
+    return AMC_OK;
+}
+
+int amc_anneal_fetch_blocks(amc_handle* h, uint64_t* records, int capacity, int* n, int* n_blocks, int reset)
+{
+    if (!h || !n || !n_blocks) return fail(AMC_ERR_BAD_ARG, "amc_anneal_fetch_blocks: NULL argument");
+    if (!h->ann.blk_B) return fail(AMC_ERR_STATE, "amc_anneal_fetch_blocks: no partition over the families is set (amc_set_anneal_blocks)");
+    *n = h->ann.blk_n;
+    *n_blocks = h->ann.blk_B;
+    if (!records) return AMC_OK;         // the sizes alone: nothing waits, nothing is copied, nothing is reset
+    if (capacity < h->ann.blk_n)
+        return fail(AMC_ERR_BAD_ARG, "amc_anneal_fetch_blocks: capacity = %d, the log holds %d block records", capacity, h->ann.blk_n);
+    AMC_HIP(hipSetDevice(h->device));
+    // (an empty log copies nothing and still waits)
+    AMC_TRY(copy_to_host_sync(h, records, h->ann.blk_n ? h->ann.d_blk_log : nullptr, (size_t)h->ann.blk_n * 2 * h->ann.blk_B * sizeof(uint64_t)));
+    if (reset) h->ann.blk_n = 0;
+    return AMC_OK;
+}
+
+int amc_set_anneal_block_records(amc_handle* h, const uint64_t* records, int n, int n_blocks)
+{
+    if (!h) return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_block_records: NULL handle");
+    if (!h->ann.blk_B) return fail(AMC_ERR_STATE, "amc_set_anneal_block_records: no partition over the families is set (amc_set_anneal_blocks)");
+    if (n < 0 || n > AMC_ANNEAL_MAX_RECORDS)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_block_records: n = %d must lie in [0, %d]", n, AMC_ANNEAL_MAX_RECORDS);
+    if (!records || n == 0) {
+        h->ann.blk_n = 0;
+        return AMC_OK;
+    }
+    if (n_blocks != h->ann.blk_B)
+        return fail(AMC_ERR_BAD_ARG, "amc_set_anneal_block_records: n_blocks = %d, the partition has %d blocks", n_blocks, h->ann.blk_B);
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_TRY(zeroed_words(h, &h->ann.d_blk_log, blk_log_bytes(h->ann.blk_B)));
+    AMC_TRY(copy_to_device_sync(h, h->ann.d_blk_log, records, (size_t)n * 2 * h->ann.blk_B * sizeof(uint64_t)));      // `records` is only valid during the call
+    h->ann.blk_n = n;
+    return AMC_OK;
+}
+
+int amc_anneal_block_counts(amc_handle* h, uint64_t* counts)
+{
+    if (!h || !counts) return fail(AMC_ERR_BAD_ARG, "amc_anneal_block_counts: NULL argument");
+    if (!h->ann.blk_B) return fail(AMC_ERR_STATE, "amc_anneal_block_counts: no partition over the families is set (amc_set_anneal_blocks)");
+    AMC_HIP(hipSetDevice(h->device));
+    if (!h->ann.d_blk_now) AMC_HIP(hipMalloc(&h->ann.d_blk_now, 2 * AMC_MAX_JK_BLOCKS * sizeof(unsigned long long)));
+    AMC_TRY(anneal_block_sums(h, nullptr, h->ann.d_blk_now));
+    return copy_to_host_sync(h, counts, h->ann.d_blk_now, (size_t)h->ann.blk_B * sizeof(uint64_t));
 }
 
 int amc_download_families(amc_handle* h, uint32_t* families)

@@ -1,6 +1,7 @@
 // amc_ehist.h -- energy histograms per group: energy_histogram_kernel<POT>, one pass that bins
 // e = potential_T(x) of every local chain into the row of its group (its rung; ONE group without a ladder),
-// energy_histogram_blocks_kernel<POT>, the same pass with a set of rows per jackknife block, and the plain kernels that zero the cells
+// energy_histogram_blocks_kernel<POT>, the same pass with a set of rows per jackknife block, energy_histogram_families_kernel<POT>, the
+// pass with a row per block of an annealed population's families, and the plain kernels that zero the cells
 // behind a respacing that was taken and fold the blocks' rows into one set.  Counts are integers: the same on any grid, in any order, on any split.
 // Part of the kernel sources of the many-chain Metropolis engine (gfx950 / CDNA4); amc_kernels.h includes all of them, in order.
 #pragma once
@@ -112,6 +113,41 @@ __global__ __launch_bounds__(AMC_BLOCK) void energy_histogram_blocks_kernel(cons
     if (lds) {
         __syncthreads();
         flush_cells(s_cells, mine.counts, cells);
+    }
+}
+
+// Per block of FAMILIES (amc_energy_histogram_accumulate_blocks under amc_set_anneal_blocks; DESIGN.md section 3.14 "Error bars"):
+// energy_histogram_kernel's pass for the ONE group of an annealed population, chain i counted into the row of the block of its
+// ancestor, b = (fam[i] div chunk) mod B -- counts[b][n_bins + 3].  The block is a property of the chain, not of the HIP block, so
+// the LDS array holds all B rows: u32 cells flushed as energy_histogram_kernel flushes them while B (n_bins + 3) <= EHIST_LDS_CELLS,
+// one 64-bit global atomic per chain beyond.  A u32 cell holds at most a HIP block's share of one pass (the host's check, as for the
+// plain pass).  chunk is capped at 2^32 - 1 by the host (anneal_block_sums_kernel).  Integer counts: the sum over the blocks is the
+// plain histogram cell for cell.
+template <int POT>
+__global__ __launch_bounds__(AMC_BLOCK) void energy_histogram_families_kernel(const EhistArgs a, const uint32_t* fam, uint32_t chunk, int n_blocks)
+{
+    __shared__ AMC_MATH_LDS_ALIGN double s_math[TAB_DOUBLES];
+    __shared__ unsigned int s_cells[EHIST_LDS_CELLS];
+    const int row = a.n_bins + 3, cells = n_blocks * row;
+    const bool lds = cells <= EHIST_LDS_CELLS;
+    if (lds)
+        for (int i = threadIdx.x; i < cells; i += AMC_BLOCK) s_cells[i] = 0u;
+    stage_math_tables<AMC_BLOCK>(s_math, threadIdx.x);        // (ends in a barrier: the cells are cleared too)
+
+    const int64_t step = (int64_t)gridDim.x * AMC_BLOCK;
+    int64_t i = (int64_t)blockIdx.x * AMC_BLOCK + threadIdx.x;
+    for (; i + 3 * step < a.n_chains; i += 4 * step) {        // four loads of x and of fam in flight per lane
+        const real_t x0 = a.x[i], x1 = a.x[i + step], x2 = a.x[i + 2 * step], x3 = a.x[i + 3 * step];
+        const uint32_t f0 = fam[i], f1 = fam[i + step], f2 = fam[i + 2 * step], f3 = fam[i + 3 * step];
+        ehist_count<POT>(a, x0, s_math, lds, s_cells, (int)((f0 / chunk) % (uint32_t)n_blocks) * row);
+        ehist_count<POT>(a, x1, s_math, lds, s_cells, (int)((f1 / chunk) % (uint32_t)n_blocks) * row);
+        ehist_count<POT>(a, x2, s_math, lds, s_cells, (int)((f2 / chunk) % (uint32_t)n_blocks) * row);
+        ehist_count<POT>(a, x3, s_math, lds, s_cells, (int)((f3 / chunk) % (uint32_t)n_blocks) * row);
+    }
+    for (; i < a.n_chains; i += step) ehist_count<POT>(a, a.x[i], s_math, lds, s_cells, (int)((fam[i] / chunk) % (uint32_t)n_blocks) * row);
+    if (lds) {
+        __syncthreads();
+        flush_cells(s_cells, a.counts, cells);
     }
 }
 

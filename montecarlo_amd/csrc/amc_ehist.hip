@@ -40,8 +40,15 @@ int ehist_fold(amc_handle* h)
     hipLaunchKernelGGL(amc::ehist_fold_kernel, dim3(grid_for(h, cells)), dim3(AMC_BLOCK), 0, h->stream, h->ehist.d_ehist, cells, h->ehist.blocks);
     AMC_HIP(hipGetLastError());
     h->ehist.blocks = 0;
+    h->ehist.by_family = false;
     return AMC_OK;
 }
+
+// The partition a blocked entry works under: the ladders' (amc_set_blocks), or -- the two exclude each other -- the one over an annealed
+// population's families (amc_set_anneal_blocks), whose blocks are a property of the chain, not of the slot.
+static inline bool ehist_by_family(const amc_handle* h) { return !h->blocks.n_blocks && h->ann.blk_B; }
+static inline int ehist_partition_blocks(const amc_handle* h) { return h->blocks.n_blocks ? h->blocks.n_blocks : h->ann.blk_B; }
+
 
 // Room for n_sets (the blocks; 1: plain) x G rows of n_bins + 3 cells under the bins (lo, hi, n_bins); the caller fills or zeroes it.
 static int ehist_begin(amc_handle* h, double lo, double hi, int n_bins, int blocks = 0)
@@ -107,6 +114,36 @@ static int ehist_rows_sum(const char* who, const char* what, const uint64_t* cou
     return AMC_OK;
 }
 
+// amc_energy_histogram_accumulate_blocks under amc_set_anneal_blocks: one pass of energy_histogram_families_kernel into counts[B][n_bins + 3].
+static int ehist_accumulate_families(amc_handle* h, const char* who, double lo, double hi, int n_bins)
+{
+    // a HIP block's u32 LDS cell holds its share of ONE pass: at most ceil(M / grid) chains (as the plain pass)
+    const int grid = hist_grid(h);
+    if ((h->M + grid - 1) / grid >= (int64_t)1 << 32)
+        return fail(AMC_ERR_STATE, "%s: %lld chains over a grid of %d blocks overflow a block's 32-bit cells", who, (long long)h->M, grid);
+    AMC_HIP(hipSetDevice(h->device));
+    AMC_TRY(pg_resolve(h));
+    const bool first = !h->ehist.d_ehist;
+    if (first) {
+        AMC_HIP(hipStreamSynchronize(h->stream));      // (as the other blocked accumulators wait where they allocate)
+        AMC_TRY(ehist_begin(h, lo, hi, n_bins, h->ann.blk_B));
+        h->ehist.by_family = true;
+        if (hipMemsetAsync(h->ehist.d_ehist, 0, ehist_cells(h) * sizeof(unsigned long long), h->stream) != hipSuccess) {
+            (void)ehist_clear(h);
+            return fail(AMC_ERR_HIP, "%s: clearing the accumulator failed", who);
+        }
+    }
+    amc::EhistArgs a = ehist_args(h);
+    const uint32_t* fam = h->ann.d_fam;
+    uint32_t chunk = (uint32_t)std::min<int64_t>(h->ann.blk_chunk, 0xFFFFFFFFll);
+    int B = h->ann.blk_B;
+    void* params[] = {&a, &fam, &chunk, &B};
+    const int rc = launch_by_potential(h, "amc::energy_histogram_families_kernel", (const void*)amc::energy_histogram_families_kernel<amc::POT_DOUBLE_WELL>,
+                                       (const void*)amc::energy_histogram_families_kernel<amc::POT_HARMONIC>, grid, params);
+    if (rc != AMC_OK && first) (void)ehist_clear(h);
+    return rc;
+}
+
 extern "C" {
 
 int amc_energy_histogram_accumulate(amc_handle* h, double lo, double hi, int n_bins)
@@ -145,12 +182,15 @@ int amc_energy_histogram_accumulate_blocks(amc_handle* h, double lo, double hi, 
     static const char* who = "amc_energy_histogram_accumulate_blocks";
     if (!h) return fail(AMC_ERR_BAD_ARG, "%s: NULL handle", who);
     if (!hist_args_ok(who, lo, hi, n_bins)) return AMC_ERR_BAD_ARG;
-    const int B = h->blocks.n_blocks, G = pass_groups(h);
+    const int B = ehist_partition_blocks(h), G = pass_groups(h);
+    const bool by_family = ehist_by_family(h);
     if (!B) return fail(AMC_ERR_STATE, "%s: no partition is set (amc_set_blocks)", who);
+    if (by_family && G != 1) return fail(AMC_ERR_STATE, "%s: blocks of families belong to one population at one shared beta, the handle has a ladder", who);
     if ((int64_t)B * G * (n_bins + 3) > AMC_EHIST_BLK_MAX_CELLS)
         return fail(AMC_ERR_BAD_ARG, "%s: %d blocks of %d rows of %d cells are more than AMC_EHIST_BLK_MAX_CELLS = %d cells", who, B, G, n_bins + 3,
                     AMC_EHIST_BLK_MAX_CELLS);
     AMC_TRY(ehist_same(h, who, true, lo, hi, n_bins));
+    if (by_family) return ehist_accumulate_families(h, who, lo, hi, n_bins);
     // the blocked form of the u32 check: a HIP block's cell holds at most lane_bound x AMC_BLOCK chains of one pass
     const int grid = amc::blk::grid_round(hist_grid(h), B);
     const int64_t lanes = amc::blk::lane_bound(h->M / G, B, h->blocks.chunk, G, grid, AMC_BLOCK);
@@ -243,6 +283,13 @@ int amc_energy_histogram_fetch_blocks(amc_handle* h, uint64_t* counts, int64_t c
                     h->ehist.n_bins + 3);
     AMC_HIP(hipSetDevice(h->device));
     AMC_TRY(copy_to_host_sync(h, counts, h->ehist.d_ehist, cells * sizeof(unsigned long long)));
+    if (h->ehist.by_family) {           // blocks of families change their size at every resampling: every chain lands in exactly one cell
+        uint64_t all = 0;
+        for (size_t i = 0; i < cells; ++i) all += counts[i];
+        *n_snapshots = all / (uint64_t)h->M;
+        if (reset) return ehist_clear(h);
+        return AMC_OK;
+    }
     // a block without a local ladder holds nothing; the snapshots from the first block that has one
     const amc::blk::Part part = blocks_part(h);
     for (int b = 0; b < B; ++b) {
@@ -282,8 +329,10 @@ int amc_set_energy_histogram_blocks(amc_handle* h, double lo, double hi, int n_b
 {
     static const char* who = "amc_set_energy_histogram_blocks";
     if (!h) return fail(AMC_ERR_BAD_ARG, "%s: NULL handle", who);
-    const int B = h->blocks.n_blocks, G = pass_groups(h);
+    const int B = ehist_partition_blocks(h), G = pass_groups(h);
+    const bool by_family = ehist_by_family(h);
     if (!B) return fail(AMC_ERR_STATE, "%s: no partition is set (amc_set_blocks)", who);
+    if (by_family && G != 1) return fail(AMC_ERR_STATE, "%s: blocks of families belong to one population at one shared beta, the handle has a ladder", who);
     if (!counts_or_null || n_snapshots == 0) {
         AMC_HIP(hipSetDevice(h->device));
         return ehist_clear(h);
@@ -293,6 +342,22 @@ int amc_set_energy_histogram_blocks(amc_handle* h, double lo, double hi, int n_b
     if ((int64_t)B * G * (n_bins + 3) > AMC_EHIST_BLK_MAX_CELLS)
         return fail(AMC_ERR_BAD_ARG, "%s: %d blocks of %d rows of %d cells are more than AMC_EHIST_BLK_MAX_CELLS = %d cells", who, B, G, n_bins + 3,
                     AMC_EHIST_BLK_MAX_CELLS);
+    if (by_family) {                    // a block's share changes with every resampling: all the cells hold every chain once per snapshot
+        if (n_snapshots > UINT64_MAX / (uint64_t)h->M) return fail(AMC_ERR_BAD_ARG, "%s: n_snapshots * n_chains does not fit 64 bits", who);
+        const uint64_t want = n_snapshots * (uint64_t)h->M;
+        uint64_t sum = 0;
+        bool over = false;
+        for (size_t i = 0; i < (size_t)B * (size_t)(n_bins + 3) && !over; ++i) {
+            over = counts_or_null[i] > want - sum;
+            if (!over) sum += counts_or_null[i];
+        }
+        if (over || sum != want) return fail(AMC_ERR_BAD_ARG, "%s: the cells do not sum to n_snapshots * n_chains = %llu", who, (unsigned long long)want);
+        AMC_HIP(hipSetDevice(h->device));
+        AMC_TRY(ehist_clear(h));
+        AMC_TRY(ehist_begin(h, lo, hi, n_bins, B));
+        h->ehist.by_family = true;
+        return copy_to_device_sync(h, h->ehist.d_ehist, counts_or_null, ehist_cells(h) * sizeof(unsigned long long));
+    }
     // every (block, group) row holds the block's ladders once per snapshot; a block without a local ladder holds nothing
     const amc::blk::Part part = blocks_part(h);
     uint64_t want[AMC_MAX_JK_BLOCKS];

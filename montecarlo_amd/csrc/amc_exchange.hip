@@ -503,9 +503,11 @@ int amc_set_blocks(amc_handle* h, int n_blocks, int64_t chunk)
         return fail(AMC_ERR_BAD_ARG, "amc_set_blocks: n_blocks = %d must be 0 (no partition) or lie in [2, %d]", n_blocks, AMC_MAX_JK_BLOCKS);
     if (chunk < 0 || chunk > AMC_MAX_JK_CHUNK)      // (the traversal adds a chunk to a global ladder index: both stay far from 2^63)
         return fail(AMC_ERR_BAD_ARG, "amc_set_blocks: chunk = %lld must lie in [1, 2^40], or be 0 for the default", (long long)chunk);
+    if (n_blocks && h->ann.blk_B)
+        return fail(AMC_ERR_STATE, "amc_set_blocks: a partition over the annealing families is set (amc_set_anneal_blocks); the two exclude each other");
     AMC_HIP(hipSetDevice(h->device));
     // energy histograms kept under the partition that goes: their blocks' rows are added up on the stream, nothing is lost
-    AMC_TRY(ehist_fold(h));
+    if (!h->ehist.by_family) AMC_TRY(ehist_fold(h));      // (one kept per block of families stays: that partition is not this call's)
     AMC_TRY(emom_fold(h));          // ... and the moments per bin's sets
     // one full block-width of contiguous chains: every lane of a HIP block has a ladder of the chunk, in one trip
     if (n_blocks && chunk == 0) chunk = std::max(1, AMC_BLOCK / pass_groups(h));

@@ -231,6 +231,13 @@ struct AnnealState {
     unsigned int* d_fam_cnt = nullptr;          // [M] + 3 words: scratch of amc_anneal_family_stats (allocated at its first call)
     unsigned long long* d_anneal_search = nullptr;   // [SEARCH_S_WORDS] the words of amc_anneal_next_beta (allocated at its first call;
                                                      //   its energies go into d_anneal_n)
+    // Blocks of families (amc_set_anneal_blocks; DESIGN.md section 3.14 "Error bars"): the partition is set exactly while blk_B != 0
+    int blk_B = 0;                              // B; 0: no partition
+    int64_t blk_chunk = 0;                      // C: block of a chain = (fam div C) mod B
+    unsigned long long* d_blk_log = nullptr;    // [AMC_ANNEAL_MAX_RECORDS][2 B] the block records: n_b, then T_b (allocated by the first step under
+                                                //   the partition, freed when it goes)
+    int blk_n = 0;                              // block records in the log
+    unsigned long long* d_blk_now = nullptr;    // [2 AMC_MAX_JK_BLOCKS] scratch of amc_anneal_block_counts (allocated at its first call)
 };
 static inline void anneal_release(AnnealState& s)
 {
@@ -243,6 +250,8 @@ static inline void anneal_release(AnnealState& s)
     (void)hipFree(s.d_fam_alt);
     (void)hipFree(s.d_fam_cnt);
     (void)hipFree(s.d_anneal_search);
+    (void)hipFree(s.d_blk_log);
+    (void)hipFree(s.d_blk_now);
 }
 
 // Time correlation (amc_corr.hip): both buffers allocated at their first use -- a handle that never marks has
@@ -287,6 +296,7 @@ struct EhistState {
     int n_bins = 0;
     int groups = 0;                             // G when it was begun (amc_set_ladder clears it, so it is the handle's G while it stands)
     int blocks = 0;                             // B of a blocked accumulator (the handle's partition while it stands); 0: plain
+    bool by_family = false;                     // ... blocked under amc_set_anneal_blocks: a row per block of FAMILIES (amc_ehist.hip)
     double lo = 0.0, hi = 0.0;
 };
 static inline void ehist_release(EhistState& s)
@@ -305,6 +315,7 @@ struct EmomState {
     int n_bins = 0;
     int groups = 0;                             // G when it was begun (amc_set_ladder clears it)
     int blocks = 0;                             // B of a blocked accumulator (the handle's partition while it stands); 0: plain
+    bool by_family = false;                     // ... blocked under amc_set_anneal_blocks: a row per block of FAMILIES (amc_ehist.hip)
     int mask = 0, cols = 0;                     // the columns kept (AMC_EMOM_*), C = popcount(mask)
     double lo = 0.0, hi = 0.0, x_bound = 0.0;
     uint64_t n_snapshots = 0;                   // passes queued since the cells were last known to be zero: the capacity check's count (a

@@ -12,7 +12,7 @@ import numpy as np
 
 from ._capi import AMC_MAX_JK_BLOCKS, AMC_XSUM_WORDS, xsum_merge, xsum_round
 
-__all__ = ["block_counts", "check_blocks", "default_chunk", "jackknife", "jackknife_counts", "jackknife_integers", "leave_one_out",
+__all__ = ["anneal_log_z", "block_counts", "check_blocks", "default_chunk", "jackknife", "jackknife_counts", "jackknife_integers", "leave_one_out",
            "leave_one_out_integers", "use_blocks"]
 
 
@@ -210,3 +210,46 @@ def jackknife_integers(block_arrays, fn):
         dev = reps - reps.mean(axis=0)
         se = np.sqrt((B - 1) / B * (dev * dev).sum(axis=0))
     return theta, se
+
+
+def anneal_log_z(records, block_records, n_chains: int, cumulative: bool = True):
+    """(value[S], se[S], replicates[S, B]) of population annealing's log Z over blocks of FAMILIES (DESIGN.md section 3.14 "Error
+    bars"; HipEngine.set_anneal_blocks).  ``records[S, 8]`` are the steps' records, ``block_records[S, 2, B]`` the block records beside
+    them: n_b, the chains of block b before the resampling, and T_b, the sum of their integer weights.  The term of step s is
+    a_max + log T_w - log M - 30 log 2; replicate b, the same without block b, is a_max + log(T_w - T_b) - log(M - n_b) - 30 log 2 --
+    exact integer differences.  cumulative: value and replicates are the running sums over the steps (log Z(beta_s) / Z(beta_0): the
+    replicate of the SUM, not a sum of per-step errors); otherwise per step.  se^2 = (B' - 1) / B' sum (theta_b - mean theta_b)^2 over
+    the B' blocks that held a family at the first step (n_b > 0 there: a block that was empty from the start is no replicate, one that
+    dies out later stays one).  A replicate whose argument is 0 -- block b holds every chain, or all the weight -- is NaN, in the
+    cumulative form from that step on, and so is the se there; a step that did not resample (status != 0) is NaN as in log_z_ratios.
+    Fewer than two blocks with a family: se is NaN."""
+    import math
+    rec = np.asarray(records, dtype=np.uint64).reshape(-1, 8)
+    blk = np.asarray(block_records, dtype=np.uint64)
+    if blk.ndim != 3 or blk.shape[1] != 2 or blk.shape[0] != rec.shape[0]:
+        raise ValueError(f"anneal_log_z: {rec.shape[0]} records beside block records of shape {blk.shape} (one [2, B] per record)")
+    S, B, M = rec.shape[0], blk.shape[2], int(n_chains)
+    shift = 30 * math.log(2.0)
+    value, rep = np.full(S, math.nan), np.full((S, B), math.nan)
+    for s in range(S):
+        status, t_w = int(rec[s, 0]), int(rec[s, 4])
+        if sum(int(v) for v in blk[s, 0]) != M or (status == 0 and sum(int(v) for v in blk[s, 1]) != t_w):
+            raise ValueError(f"anneal_log_z: the block record of step {s} does not add up to its record (sum n_b = M, sum T_b = T_w)")
+        if status != 0:
+            continue
+        a_max = float(np.array(rec[s, 3], dtype=np.uint64).view(np.float64))
+        value[s] = a_max + math.log(t_w) - math.log(M) - shift
+        for b in range(B):
+            t, n = t_w - int(blk[s, 1, b]), M - int(blk[s, 0, b])
+            if t > 0 and n > 0:
+                rep[s, b] = a_max + math.log(t) - math.log(n) - shift
+    if cumulative:
+        value, rep = np.cumsum(value), np.cumsum(rep, axis=0)
+    se = np.full(S, math.nan)
+    if S:
+        alive = blk[0, 0] > 0
+        k = int(alive.sum())
+        if k >= 2:
+            th = rep[:, alive]
+            se = np.sqrt((k - 1) / k * ((th - th.mean(axis=1, keepdims=True)) ** 2).sum(axis=1))
+    return value, se, rep

@@ -117,6 +117,7 @@ class Metropolis(AriannaAlgorithm):
         self.convergence = None             # the Convergence that keeps these chains' running sums (its __init__)
         self.restored = False               # storage.restore put the state on the device: initialise() leaves it there
         self.families_restored = False      # storage.restore brought the annealing families back
+        self.anneal_blocks_restored = False # ... and the partition into blocks of families with its block records
         self._rung_window_used = False      # a tuning or a window restart has happened (tune_rung_sigma, restart_rung_window, storage.restore)
         self.device_params_dirty = False    # device-resident learning steps moved sigma (PolicyGradientUpdate; pull_parameters clears it)
         self._pending_red_epoch = None      # epoch of a reduction formed inside a sweep launch that nobody has claimed (make_step)

@@ -283,10 +283,15 @@ def _write_annealing(met, eng, d, est) -> None:
     pa = met.annealing
     if pa is not None:                              # population annealing: beta, the step index, the records and the families are state
         d.update(anneal_beta=float(eng.beta), anneal_step=int(eng.anneal_step), anneal_records=pa.records())
+        blk = pa.block_records() if pa.blocks is not None else None      # (drained with the records, while both logs are aligned)
         eng.set_anneal_records(d["anneal_records"][-AMC_ANNEAL_MAX_RECORDS:])      # (records() drained the engine's log: the run goes on with it)
         pa._records = list(d["anneal_records"][:-AMC_ANNEAL_MAX_RECORDS])
         if pa.families:
             d["families"] = eng.download_families()
+        if pa.blocks is not None:                   # blocks=B: the partition and the block records beside the records (no field otherwise)
+            d.update(anneal_blocks=np.array(pa.blocks, dtype=np.int64), anneal_block_records=blk)
+            eng.set_anneal_block_records(blk[-AMC_ANNEAL_MAX_RECORDS:])
+            pa._block_records = list(blk[:-AMC_ANNEAL_MAX_RECORDS])
         d.update(pa.histogram_state())              # energy_histogram=...: a histogram per temperature so far (no field otherwise)
 
 def _read_annealing(met, eng, d, est) -> None:
@@ -302,6 +307,23 @@ def _read_annealing(met, eng, d, est) -> None:
             eng.set_anneal_families(True)
             eng.upload_families(d["families"])
             met.families_restored = True
+        pa = met.annealing
+        if pa is not None and pa.blocks is None and "anneal_blocks" in d:
+            raise ValueError(f"checkpoint holds block records under the partition {tuple(int(v) for v in d['anneal_blocks'])}, this "
+                             "PopulationAnnealing asks for no blocks: they would be dropped")
+        if pa is not None and pa.blocks is not None:      # behind the families: the partition needs them
+            if "anneal_blocks" not in d:
+                if len(rec):
+                    raise ValueError("checkpoint holds annealing records without block records, this PopulationAnnealing asks for blocks")
+            else:
+                if tuple(int(v) for v in d["anneal_blocks"]) != tuple(pa.blocks):
+                    raise ValueError(f"checkpoint holds block records under the partition {tuple(int(v) for v in d['anneal_blocks'])}, this "
+                                     f"PopulationAnnealing asks for {tuple(pa.blocks)}")
+                blk = np.asarray(d["anneal_block_records"], dtype=np.uint64).reshape(-1, 2, pa.blocks[0])
+                eng.set_anneal_blocks(*pa.blocks)
+                eng.set_anneal_block_records(blk[-AMC_ANNEAL_MAX_RECORDS:])
+                pa._block_records = list(blk[:-AMC_ANNEAL_MAX_RECORDS])
+                met.anneal_blocks_restored = True
 
 
 def _write_correlation(met, eng, d, est) -> None:
