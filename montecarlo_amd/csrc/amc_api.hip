@@ -554,8 +554,8 @@ int amc_destroy(amc_handle* h)
     ladder_release(h->lad);
     anneal_release(h->ann);
     corr_release(h->corr);
-    ehist_release(h->ehist);
-    emom_release(h->emom);
+    bins_release(h->ehist);
+    bins_release(h->emom);
     chain_stats_release(h->cstat);
     blocks_release(h->blocks);
     if (h->h_params) (void)hipHostFree(h->h_params);

@@ -14,7 +14,8 @@
 //   amc_corr.hip        time correlation from one time origin (amc_corr_mark .. amc_corr_clear; per jackknife block: amc_corr_fetch_blocks;
 //                       the partition itself, amc_set_blocks, and amc_bridge_fetch_blocks are with the bridge sums in amc_exchange.hip)
 //   amc_ehist.hip       energy histograms per group (amc_energy_histogram_accumulate / _fetch, amc_set_energy_histogram; per jackknife
-//                       block: amc_energy_histogram_accumulate_blocks / _fetch_blocks, amc_set_energy_histogram_blocks)
+//                       block: amc_energy_histogram_accumulate_blocks / _fetch_blocks, amc_set_energy_histogram_blocks), and what the
+//                       life cycle of both accumulators over the energy bins shares (bins_*: respaced, fold, checks, fetch arithmetic)
 //   amc_emom.hip        moments per energy bin (amc_energy_moments_accumulate / _fetch, amc_set_energy_moments; per jackknife block:
 //                       amc_energy_moments_accumulate_blocks / _fetch_blocks, amc_set_energy_moments_blocks)
 //   amc_chainstats.hip  convergence per group: running sums per chain and their sums by group (amc_chain_stats_accumulate ..
@@ -287,45 +288,42 @@ static inline void blocks_release(BlocksState& s)
     (void)hipFree(s.d_corr_blk);
 }
 
-// Energy histograms per group (amc_ehist.hip): the accumulator is allocated by the first
-// amc_energy_histogram_accumulate after a reset -- a handle that never accumulates has none.  It stands exactly while d_ehist != nullptr.
-// Its FORM is fixed while it stands too: plain (blocks == 0), or blocked under the partition it was begun with
-// (amc_energy_histogram_accumulate_blocks: a set of rows per jackknife block); amc_set_blocks folds a blocked one into a plain one.
-struct EhistState {
-    unsigned long long* d_ehist = nullptr;      // [blocks or 1][groups][n_bins + 3] counts; the bins are fixed while it stands
+// The accumulators over the energy bins: what the energy histograms' and the moments' have in common, and all
+// their shared life cycle works on (bins_* below; amc_ehist.hip).  An accumulator is allocated at its first use -- a handle that never
+// accumulates has none -- and stands exactly while d_words != nullptr; without one the state is the default one.  Its FORM is fixed
+// while it stands: the bins, and plain (blocks == 0) or blocked under the partition it was begun with (a set per jackknife block, or
+// per block of families); amc_set_blocks folds a blocked one into a plain one.
+struct BinsState {
+    unsigned long long* d_words = nullptr;      // [blocks or 1] sets of [groups][n_bins + tail] counts, then [groups][cols][n_bins] signed 64-bit sums
     int n_bins = 0;
     int groups = 0;                             // G when it was begun (amc_set_ladder clears it, so it is the handle's G while it stands)
     int blocks = 0;                             // B of a blocked accumulator (the handle's partition while it stands); 0: plain
     bool by_family = false;                     // ... blocked under amc_set_anneal_blocks: a row per block of FAMILIES (amc_ehist.hip)
+    int tail = 0;                               // cells behind the bins of a count row: 3 (below, above, NaN), 4 with "beyond x_bound"
+    int cols = 0;                               // sum cells per (group, bin): none for the histograms, C = popcount(mask) for the moments
     double lo = 0.0, hi = 0.0;
 };
-static inline void ehist_release(EhistState& s)
+static inline size_t bins_count_cells(const BinsState& s) { return (size_t)s.groups * (size_t)(s.n_bins + s.tail); }      // of one set
+static inline size_t bins_sum_cells(const BinsState& s) { return (size_t)s.groups * (size_t)s.cols * (size_t)s.n_bins; }
+static inline size_t bins_set_words(const BinsState& s) { return bins_count_cells(s) + bins_sum_cells(s); }
+static inline size_t bins_words(const BinsState& s) { return bins_set_words(s) * (size_t)(s.blocks ? s.blocks : 1); }      // of all sets
+static inline void bins_release(BinsState& s)
 {
-    (void)hipFree(s.d_ehist);
+    (void)hipFree(s.d_words);
 }
 
+// Energy histograms per group (amc_ehist.hip): counts alone, tail = 3.
+typedef BinsState EhistState;
+
 // Moments per energy bin (amc_emom.hip; DESIGN.md section 3.17 "Moments per bin"): an accumulator of its own beside the energy
-// histograms', allocated by the first amc_energy_moments_accumulate after a reset -- a handle that never calls it has none.  It stands
-// exactly while d_emom != nullptr, and its form (bins, mask, bound) is fixed while it stands: plain (blocks == 0), or blocked under the
-// partition it was begun with (amc_energy_moments_accumulate_blocks: a set per jackknife block); amc_set_blocks folds a blocked one
-// into a plain one.
-struct EmomState {
-    unsigned long long* d_emom = nullptr;       // one set: [groups][n_bins + 4] counts, then [groups][cols][n_bins] signed 64-bit sums; one
-                                                // allocation of `blocks or 1` sets
-    int n_bins = 0;
-    int groups = 0;                             // G when it was begun (amc_set_ladder clears it)
-    int blocks = 0;                             // B of a blocked accumulator (the handle's partition while it stands); 0: plain
-    bool by_family = false;                     // ... blocked under amc_set_anneal_blocks: a row per block of FAMILIES (amc_ehist.hip)
-    int mask = 0, cols = 0;                     // the columns kept (AMC_EMOM_*), C = popcount(mask)
-    double lo = 0.0, hi = 0.0, x_bound = 0.0;
+// histograms', tail = 4, with the columns and the bound in its form.
+struct EmomState : BinsState {
+    int mask = 0;                               // the columns kept (AMC_EMOM_*)
+    double x_bound = 0.0;
     uint64_t n_snapshots = 0;                   // passes queued since the cells were last known to be zero: the capacity check's count (a
                                                 // respacing taken on the device zeroes the cells without the host knowing: amc_energy_moments_fetch
                                                 // brings the count back to what the rows hold)
 };
-static inline void emom_release(EmomState& s)
-{
-    (void)hipFree(s.d_emom);
-}
 
 // Convergence per group (amc_chainstats.hip): running sums per chain, both buffers allocated at their first
 // use -- a handle that never accumulates has neither.  The accumulators stand exactly while observable != 0.
@@ -566,16 +564,6 @@ AMC_INTERNAL int rung_pass_plan(amc_handle* h, int n_cols, bool blocked, RungPas
 AMC_INTERNAL int rung_pass_grid(const amc_handle* h);      // the grid of an unblocked pass: what a memory-bound pass over the chains takes
 // a kind-R record into words 0 .. 4 of an XS_ROW_R row, or a refusal naming who / where (amc_exchange.hip; amc_set_bridge*, amc_set_corr*)
 AMC_INTERNAL int r_row_from_record(const char* who, const char* where, const double* rec, amc::xs_word* row);
-// the energy histograms (amc_ehist.hip): the accumulator freed, no bins fixed (amc_set_ladder; waits for what still writes it); its cells
-// zeroed on the stream when the respacing just queued is taken (amc_respace_ladder); a blocked accumulator folded into a plain one on
-// the stream (amc_set_blocks).  Nothing happens on a handle without one.
-AMC_INTERNAL int ehist_clear(amc_handle* h);
-AMC_INTERNAL int ehist_respaced(amc_handle* h);
-AMC_INTERNAL int ehist_fold(amc_handle* h);
-// the moments per energy bin (amc_emom.hip): freed with the ladder, zeroed on the stream behind a respacing that is taken, as above
-AMC_INTERNAL int emom_clear(amc_handle* h);
-AMC_INTERNAL int emom_respaced(amc_handle* h);
-AMC_INTERNAL int emom_fold(amc_handle* h);
 AMC_INTERNAL void comm_release(amc_handle* h);   // drops the handle's communicator and its buffers (amc_comm.hip)
 // kernels compiled at run time (amc_rtc.hip)
 struct RtcCode { std::vector<char> code; std::string lowered; };
@@ -646,3 +634,56 @@ static inline int blocks_words(amc_handle* h, amc::xs_word** p, size_t* have, si
     AMC_HIP(hipMemsetAsync(*p, 0, need * sizeof(amc::xs_word), h->stream));
     return AMC_OK;
 }
+
+// The life cycle of an accumulator over the energy bins, for the histograms' and the moments' alike (S: EhistState or EmomState).
+// The accumulator gone, no form fixed: the default state.  hipFree waits for whatever still writes the memory.
+template <class S>
+static inline int bins_clear(S& s)
+{
+    (void)hipFree(s.d_words);
+    s = S();
+    return AMC_OK;
+}
+// Begun at its first use: room for the sets of `form`; with `zeroed`, cleared on the stream -- behind everything queued when it is
+// blocked, as the other blocked accumulators wait where they allocate (blocks_words).  Otherwise the caller fills it.  A failure
+// leaves nothing behind.
+template <class S>
+static inline int bins_begin(amc_handle* h, S& s, const S& form, const char* who, bool zeroed)
+{
+    if (zeroed && form.blocks) AMC_HIP(hipStreamSynchronize(h->stream));
+    unsigned long long* d = nullptr;
+    AMC_HIP(hipMalloc(&d, bins_words(form) * sizeof(unsigned long long)));
+    s = form;
+    s.d_words = d;
+    if (zeroed && hipMemsetAsync(d, 0, bins_words(s) * sizeof(unsigned long long), h->stream) != hipSuccess) {
+        (void)bins_clear(s);
+        return fail(AMC_ERR_HIP, "%s: clearing the accumulator failed", who);
+    }
+    return AMC_OK;
+}
+// One pass launched; a first call that is refused (a run-time build that fails, say) leaves no accumulator and no form behind.
+template <class S>
+static inline int bins_pass(amc_handle* h, S& s, bool first, const char* name, const void* double_well, const void* harmonic, int grid, void** params)
+{
+    const int rc = launch_by_potential(h, name, double_well, harmonic, grid, params);
+    if (rc != AMC_OK && first) (void)bins_clear(s);
+    return rc;
+}
+// amc_ehist.hip, for both accumulators.  The words zeroed on the stream when the respacing just queued is taken (amc_respace_ladder); a
+// blocked accumulator folded into a plain one on the stream (amc_set_blocks); nothing happens without one.  Then what the entries check
+// and what the fetches form on the host (see there).
+AMC_INTERNAL int bins_respaced(amc_handle* h, const BinsState& s);
+AMC_INTERNAL int bins_fold(amc_handle* h, BinsState& s);
+AMC_INTERNAL int bins_partition(const amc_handle* h, const char* who, bool families, int* n_blocks, bool* by_family);
+AMC_INTERNAL int bins_u32_ok(const amc_handle* h, const char* who, int grid);
+AMC_INTERNAL int bins_u32_blocked_ok(const amc_handle* h, const char* who, int n_blocks, int* grid);
+AMC_INTERNAL int bins_row_sum(const char* who, const char* what, const uint64_t* row, size_t n, uint64_t want, int g, int s);
+AMC_INTERNAL int bins_merge_blocks(amc_handle* h, const BinsState& s, uint64_t* set);
+AMC_INTERNAL uint64_t bins_snapshots(const amc_handle* h, const BinsState& s, const uint64_t* counts, bool blocked);
+// (what amc_set_ladder, amc_set_blocks, amc_set_anneal_blocks and amc_respace_ladder call)
+static inline int ehist_clear(amc_handle* h) { return bins_clear(h->ehist); }
+static inline int ehist_respaced(amc_handle* h) { return bins_respaced(h, h->ehist); }
+static inline int ehist_fold(amc_handle* h) { return bins_fold(h, h->ehist); }
+static inline int emom_clear(amc_handle* h) { return bins_clear(h->emom); }
+static inline int emom_respaced(amc_handle* h) { return bins_respaced(h, h->emom); }
+static inline int emom_fold(amc_handle* h) { return bins_fold(h, h->emom); }

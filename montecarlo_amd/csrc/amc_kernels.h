@@ -26,11 +26,13 @@
 //   amc_anneal_search.h  population annealing: the next beta from a target on the effective-sample fraction (energies, sums, decision)
 //   amc_corr.h         time correlation from one time origin: the sums of O, O^2, a O by group, one slot per lag
 //   amc_blocks.h       jackknife blocks: the traversal's index arithmetic, the bridge sums and the time correlation per block of ladders
-//   amc_ehist.h        energy histograms per group: energy_histogram_kernel, energy_histogram_blocks_kernel (a set of rows per
-//                      jackknife block), the cells zeroed behind a respacing, the blocks' rows folded into one set
-//   amc_emom.h         moments per energy bin: energy_moments_kernel (the energy histograms' pass with integer sums of x, x^2 and
-//                      [x > 0] per bin beside the counts), energy_moments_blocks_kernel (a set of cells per jackknife block), the
-//                      deposit rule the host compiles too
+//   amc_ehist.h        the passes over the energy bins: a HIP block's cells (set up, flushed) and the three traversals of the chains
+//                      (by group, by jackknife block, by family), each once; the energy histograms per group:
+//                      energy_histogram_kernel, energy_histogram_blocks_kernel (a set of rows per jackknife block),
+//                      energy_histogram_families_kernel (a row per block of families); an accumulator's words zeroed behind a
+//                      respacing, its blocks' sets folded into one
+//   amc_emom.h         moments per energy bin: the same cells and traversals with integer sums of x, x^2 and [x > 0] per bin beside
+//                      the counts (energy_moments_kernel, energy_moments_blocks_kernel), the deposit rule the host compiles too
 //   amc_chainstats.h   convergence per group: running sums per chain (chain_stats_add_kernel) and their sums by group
 #pragma once
 
